@@ -5,6 +5,9 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) to DIR/*.npy: with the same arguments the inputs
+and weights are the same seeded ones from run to run, so two builds can be compared output for output.
+
 One "step" = one pass of the whole hot path (log-mel front-end -> 24-layer FastConformer encoder
 -> joint projection -> batched greedy RNN-T decode) over one batch of 256 synthetic 10 s
 utterances per GPU.  `value` follows the bench contract: inputs already resident in HBM when the timed region
@@ -316,6 +319,33 @@ def timed_pipeline(model, bufs, steps, warmup, dec_streams):
     model.run_pipelined(bufs, steps, dec_streams=dec_streams)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
+
+
+DUMP_BYTES = 48 << 20               # --dump-outputs: budget of the joint-encoder sample (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, model, buf):
+    """--dump-outputs: what the timed path handed back for its last step's batch (`buf`), one .npy per array — ids / frames
+    [B][U] padded with -1, n_ids, enc_lens (and ALSD scores) in float64, and the joint-encoder projection of a fixed seeded
+    sample of rows in float32, zero past each row's length (rows listed in joint_enc_rows)."""
+    os.makedirs(path, exist_ok=True)
+    got = model.collect(buf)
+    B = buf.B
+    n = np.asarray([len(x) for x in got.ids])
+    ids, frames = np.full((B, max(int(n.max()), 1)), -1.0), np.full((B, max(int(n.max()), 1)), -1.0)
+    for b in range(B):
+        ids[b, :n[b]], frames[b, :n[b]] = got.ids[b], got.frames[b]
+    arrays = {"ids": ids, "frames": frames, "n_ids": n.astype(np.float64), "enc_lens": np.asarray(got.enc_lens, np.float64)}
+    if got.scores is not None:
+        arrays["scores"] = np.asarray(got.scores, np.float64)
+    k = max(1, min(B, 32, DUMP_BYTES // (buf.tp_max * buf.joint_enc.shape[2] * 4)))
+    rows = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+    je = buf.joint_enc[torch.from_numpy(rows).to(buf.joint_enc.device)].cpu().numpy().astype(np.float32)
+    for i, b in enumerate(rows):
+        je[i, got.enc_lens[b]:] = 0.0
+    arrays["joint_enc_rows"], arrays["joint_enc"] = rows.astype(np.float64), je
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def resident_sets(model, batch, seconds, n_sets, seed0):
@@ -923,7 +953,11 @@ def main():
                     help="decode consecutive batches on this many streams (n lanes need n + 1 resident batches)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="run encoder and decode of each batch back to back on one stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1004,6 +1038,8 @@ def main():
     gemm_launches = model.ctx.profile_launches(capi.PROF_GEMM) if prof else []
     model.ctx.profile_enable(0)
     dt = rdist.max_over_ranks(dt)
+    if args.dump_outputs and rank == 0:     # before anything else runs on the resident batches: step i used bufs[i % n_sets]
+        dump_outputs(args.dump_outputs, model, bufs[(args.steps - 1) % n_sets])
     # per-step completion intervals (steady state of the pipeline): median next to the mean
     marks = [t0] + list(step_done)
     intervals = sorted(b - a for a, b in zip(marks[1:-1], marks[2:])) if len(marks) > 3 else []

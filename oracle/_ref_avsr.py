@@ -2,8 +2,8 @@
 modeling_resnet,decoder,modeling_avhubert}.py), imported UNCHANGED from /root/reference.  TEST INFRASTRUCTURE (oracle/__init__.py),
 usable in the build container only: /root/reference does not exist on the GPU box, nothing under tests/ -m gpu, smoke() or
 bench.py may call this.  Its one consumer is tests/golden/make_avsr_golden.py, which runs the reference on this repo's seeded
-synthetic weights and inputs and commits the outputs as fixtures (tests/golden/avsr_ref_*.npz); tests/test_oracle_avsr.py also
-uses it — when the reference is present — to compare oracle/avsr.py with the reference directly on fresh inputs.
+synthetic weights and inputs and commits the outputs as fixtures (tests/golden/avsr_ref_*.npz), which tests/test_oracle_avsr.py
+compares oracle/avsr.py with.
 
 The package's __init__ imports the feature extractor, which needs cv2 / mediapipe / librosa / python_speech_features (absent
 here); the model modules do not, so they are imported under a stub parent package."""

@@ -2,7 +2,7 @@
 AVHubertForConditionalGeneration: forward :256-314, generate through transformers' GenerationMixin) on this repo's seeded
 synthetic weights and inputs.  Run in the BUILD container (CPU; the reference tree must be at /root/reference):
 
-    python tests/golden/make_avsr_golden.py [tiny] [base] [config]
+    python tests/golden/make_avsr_golden.py [tiny] [base] [config] [fresh]
 
 This is the one model family whose checker is the reference's own code: the modules are imported unchanged (oracle/_ref_avsr.py)
 under this container's torch / transformers, `load_state_dict(strict=True)` takes runtime/avsr_weights.py's synthetic state dict
@@ -21,6 +21,10 @@ Stored per configuration (B clips, T frames, ragged lengths):
   beam / beam_scores                  generate(num_beams=K, ...) sequences and sequences_scores for the first `beam_clips` clips
   logits                              teacher-forced forward(decoder_input_ids = greedy[:, :-1]).logits: clips 0-1 in full, all clips
                                       as logits @ Rv [V][8]
+
+`fresh` writes tests/golden/avsr_ref_fresh.npz: a second, smaller geometry (3 encoder layers, 1 decoder layer, 40 tokens; weight
+seed 17, 3 ragged clips of 17 frames, input seed 99) with its own teacher-forced ids — the encoder output, the logits and
+generate(num_beams=1 / 4, max_new_tokens=7) sequences, compared in tests/test_oracle_avsr.py against the oracle.
 """
 import hashlib
 import os
@@ -121,8 +125,36 @@ def write_configs():
         print("wrote", path, os.path.getsize(path), "bytes", flush=True)
 
 
+FRESH = dict(encoder_layers=3, decoder_layers=1, vocab_size=40)          # on AVSR_TINY; weight seed, input seed, clips, frames, tokens
+FRESH_RUN = (17, 99, 3, 17, 7)
+FRESH_IDS = [[0, 5, 7, 9], [0, 3, 3, 2], [0, 11, 2, 1]]
+
+
+def run_fresh():
+    wseed, iseed, B, T, new_tokens = FRESH_RUN
+    cfg = AVSR_TINY.with_(**FRESH)
+    sd = synthetic_state_dict_avsr(cfg, wseed)
+    model = ra.build(cfg, sd)
+    a, v, mask, _ = synthetic_clips(B, T, seed=iseed, ragged=True)
+    kw = dict(input_values=torch.from_numpy(a), pixel_values=torch.from_numpy(v), padding_mask=torch.from_numpy(mask))
+    ids = torch.tensor(FRESH_IDS)
+    store = {"input_sha256": np.frombuffer(hashlib.sha256(a.tobytes() + v.tobytes() + mask.tobytes()).digest(), np.uint8),
+             "decoder_input_ids": ids.numpy().astype(np.int32)}
+    with torch.no_grad():
+        store["enc"] = model.avhubert(**kw).last_hidden_state.numpy()
+        store["logits"] = model(**kw, decoder_input_ids=ids, decoder_attention_mask=torch.ones_like(ids)).logits.numpy()
+        for beams in (1, 4):
+            out = model.generate(**kw, num_beams=beams, do_sample=False, max_new_tokens=new_tokens, use_cache=False)
+            store[f"generate_beams{beams}"] = out.numpy().astype(np.int32)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "avsr_ref_fresh.npz")
+    np.savez_compressed(path, **store)
+    print("wrote", path, os.path.getsize(path), "bytes", flush=True)
+
+
 if __name__ == "__main__":
     if "config" in sys.argv[1:]:
         write_configs()
-    for name in ([a for a in sys.argv[1:] if a in RECIPES] or ([] if "config" in sys.argv[1:] else list(RECIPES))):
+    if "fresh" in sys.argv[1:]:
+        run_fresh()
+    for name in ([a for a in sys.argv[1:] if a in RECIPES] or ([] if {"config", "fresh"} & set(sys.argv[1:]) else list(RECIPES))):
         run(name)

@@ -91,7 +91,8 @@ def test_c_checker_vs_float64_restatement_over_whole_utterances_at_the_120m_shap
     bit are popped in the other order in one frame, which costs a pop and changes nothing that is returned.  That is the
     measured size of the float32-vs-Python-float difference; the test pins it: labels / frames identical
     everywhere, pop counts identical on >= 30 of 32 rows and never more than 2 apart.  Row 0 is recomputed here with the C
-    checker from a fresh oracle forward pass."""
+    checker: bit for bit from the joint projection the golden was computed from (its `f_rows`), and from a fresh oracle forward
+    pass, whose last float32 bits depend on the host CPU's GEMM kernels — same labels and pops, the score within 1e-4."""
     import hashlib
     import os
     from reazonspeech_amd.runtime.config import ESPNET_CONFORMER_120M
@@ -115,7 +116,13 @@ def test_c_checker_vs_float64_restatement_over_whole_utterances_at_the_120m_shap
     wav = np.pad(audio[0, :lens[0]], (16000, 8000))
     out = oe.forward(cfg, sd, torch.from_numpy(wav)[None], torch.tensor([len(wav)]), "fp32")
     n = int(out["enc_lens"][0])
-    got = og.espnet_beam(cfg, sd_beam, out["joint_enc"].numpy(), np.asarray([n], np.int32), beam=int(gold["beam"]), max_pops=int(gold["max_pops"]),
-                         out_cap=2 * n + 16, with_frames=True)[0]
-    assert got[0] == gold["beam_c_ids"][co[0]:co[1]].tolist() and got[3] == int(gold["beam_c_pops"][0])
-    assert np.float32(got[2]) == np.float32(gold["beam_c_score"][0])
+    assert n == int(gold["enc_lens"][0]) and np.abs(out["joint_enc"][0, :n].numpy() - gold["f_rows"][0, :n]).max() <= 1e-4
+    for name, f in (("stored", np.ascontiguousarray(gold["f_rows"][:1, :n])), ("fresh", np.ascontiguousarray(out["joint_enc"][:, :n].numpy()))):
+        got = og.espnet_beam(cfg, sd_beam, f, np.asarray([n], np.int32), beam=int(gold["beam"]), max_pops=int(gold["max_pops"]),
+                             out_cap=2 * n + 16, with_frames=True)[0]
+        assert got[0] == gold["beam_c_ids"][co[0]:co[1]].tolist() and got[3] == int(gold["beam_c_pops"][0]), name
+        if name == "stored":
+            assert got[1] == gold["beam_c_frames"][co[0]:co[1]].tolist()
+            assert np.float32(got[2]) == np.float32(gold["beam_c_score"][0])
+        else:
+            assert abs(float(got[2]) - float(gold["beam_c_score"][0])) <= 1e-4, (float(got[2]), float(gold["beam_c_score"][0]))
