@@ -831,6 +831,8 @@ int rs_launch_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, const float*
         return rs_fail(ctx, RS_EINVAL, "gemm_f32 (skinny): M <= 128, K %% 16, N %% 4 and 16-byte row pitches required (M %d N %d K %d)", M, N, K);
     if (flags & ~(RS_GEMM_BIAS | RS_GEMM_RELU | RS_GEMM_SILU | RS_GEMM_GELU | RS_GEMM_RESIDUAL | RS_GEMM_OUT_F32))
         return rs_fail(ctx, RS_EINVAL, "gemm_f32 (skinny): unsupported flags %d", flags);
+    if ((flags & RS_GEMM_BIAS) && !bias) return rs_fail(ctx, RS_EINVAL, "gemm_f32 (skinny): bias flag without a bias");
+    if ((flags & RS_GEMM_RESIDUAL) && !residual) return rs_fail(ctx, RS_EINVAL, "gemm_f32 (skinny): residual flag without a residual");
     GemmF32 p{A, W, out, bias, residual, nullptr, lda, ldw, ldc, M, N, K, flags, 1.0f, 0, 0};
     const dim3 grid((N + 15) / 16), block(64 * SK_WAVES);
     rs_prof_begin(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
@@ -846,6 +848,24 @@ int rs_launch_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, const float*
     rs_prof_end(ctx, RS_PROF_GEMM, s);
     RS_CHECK_LAUNCH(ctx, "gemm_f32_skinny");
     return RS_OK;
+}
+
+// Test hooks, deliberately not in rs_asr.h (no ABI change): the two float32 launchers that no public entry reaches on its own, for the
+// operator tests of tests/test_gpu_f32_products.py.  They return the launcher's code; the message is read with rs_last_error.
+extern "C" int rs_debug_conv3x3_f32(rs_ctx* ctx, const float* in, int n_img, int H, int W, int C, int OH, int OW, int stride, const float* w,
+                                    int Cout, const float* bn_scale, const float* bn_shift, const float* residual, const float* prelu, float* out,
+                                    int one_by_one, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (!in || !w || !out) return rs_fail(ctx, RS_EINVAL, "conv3x3_f32: null pointer");
+    return rs_launch_conv3x3_f32(ctx, in, n_img, H, W, C, OH, OW, stride, w, Cout, bn_scale, bn_shift, residual, prelu, out, one_by_one,
+                                 (hipStream_t)stream);
+}
+
+extern "C" int rs_debug_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, const float* W, int ldw, float* out, int ldc, int M, int N, int K,
+                                        int flags, const float* bias, const float* residual, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (!A || !W || !out) return rs_fail(ctx, RS_EINVAL, "gemm_f32 (skinny): null pointer");
+    return rs_launch_gemm_f32_skinny(ctx, A, lda, W, ldw, out, ldc, M, N, K, flags, bias, residual, (hipStream_t)stream);
 }
 
 size_t rs_encoder_f32_workspace_bytes(const rs_ctx* ctx, int B, int t_max) { return plan_f32(ctx, B, t_max).total; }
