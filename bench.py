@@ -2,16 +2,23 @@
 """bench.py — RTFx of the MI355X FastConformer-RNNT path (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) to DIR/*.npy: with the same arguments the inputs
 and weights are the same seeded ones from run to run, so two builds can be compared output for output.
 
+A plain run does only what the headline figure needs: set up, warm up, time the steps, dump the outputs if asked, and
+print the line — `value`, `ms_per_step`, the step intervals, `config` and the GEMM `roofline` of the timed steps, which
+costs no run of its own.  Everything described below that takes runs of its own (the PCIe-inclusive and host-boundary
+rates, the sequential-schedule GEMM figures, `cpu_baseline`, `parity`, `configs`) is added by `--full`; the `--no-*`
+switches trim a `--full` run.
+
 One "step" = one pass of the whole hot path (log-mel front-end -> 24-layer FastConformer encoder
 -> joint projection -> batched greedy RNN-T decode) over one batch of 256 synthetic 10 s
 utterances per GPU.  `value` follows the bench contract: inputs already resident in HBM when the timed region
-starts.  Next to it the same JSON line carries what SURVEY.md §8(d) defines — the host-to-host rate through the
+starts.  With `--full` the same JSON line carries what SURVEY.md §8(d) defines — the host-to-host rate through the
 PUBLIC boundary: `value_host_to_ids` (AsrModel.transcribe_waveforms: host float32 lists -> token ids, H2D / D2H,
 sorting, staging and the pipeline fill and drain inside the clock) and `value_transcribe_batch` (the same through
 `transcribe_batch`, text post-processing included) — and `configs`: BASELINE configs[1] (B = 32), the ragged set of
@@ -937,6 +944,9 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="utterances per GPU per step")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--tiny", action="store_true", help="debug: 2-layer toy config (NOT a valid bench line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also everything that takes runs of its own: PCIe-inclusive and host-boundary "
+                         "rates, sequential-schedule GEMM roofline, cpu_baseline, parity, configs (trimmed by the --no-* switches)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-fp32-parity", action="store_true", help="skip the float32-parity-mode pass over all 256 rows")
@@ -1048,7 +1058,7 @@ def main():
     # PCIe-inclusive rate of the SAME resident-batch loop (never `value`): every batch is copied from pinned host
     # memory first and its hypotheses are copied back after decode
     dt_host = None
-    if pipelined and world == 1:
+    if args.full and pipelined and world == 1:
         model.run_pipelined(bufs, 2, from_host=True, dec_streams=args.dec_streams)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1059,7 +1069,7 @@ def main():
     # SURVEY.md §8(d)'s metric through the PUBLIC boundary: a list of host float32 utterances in, token ids (and, second
     # figure, TranscribeResult text) out — sorting, pinned staging, H2D, the pipeline's fill and drain, D2H all inside
     api = None
-    if world == 1 and not args.tiny and args.api_batches > 0:
+    if args.full and world == 1 and not args.tiny and args.api_batches > 0:
         try:
             from reazonspeech_amd.nemo.asr import transcribe_batch, audio_from_numpy, TranscribeConfig
             waves = [host_sets[k % n_sets][0][i, :host_sets[k % n_sets][1][i]] for k in range(args.api_batches) for i in range(args.batch)]
@@ -1095,7 +1105,7 @@ def main():
     # the same GEMM launches without the decode stream next to them (sequential schedule, 2 steps): how much of the
     # in-pipeline figure is CU sharing with the decode kernels rather than the kernel itself
     gemm_seq = None
-    if prof and pipelined and world == 1:
+    if args.full and prof and pipelined and world == 1:
         model.ctx.profile_reset()
         model.ctx.profile_enable(capi.PROF_GEMM)
         for i in range(2):
@@ -1122,7 +1132,7 @@ def main():
             "value_definition": "bench contract: whole-job RTFx with the step's inputs already resident in HBM.  SURVEY 8(d)'s "
                                 "definition (host float32 -> TranscribeResult through the public transcribe_batch, H2D / D2H, "
                                 "pipeline fill and drain inside the clock) is `value_transcribe_batch`; `value_host_to_ids` stops "
-                                "at token ids",
+                                "at token ids (both measured by --full)",
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": f"FastConformer-RNNT {cfg.n_params() / 1e6:.0f}M, {args.batch} x "
                                    f"{args.seconds:g} s utterances per GPU (+0.5 s pad each side), "
@@ -1178,14 +1188,14 @@ def main():
                 seq = gemm_seq["flops"] / (gemm_seq["ms"] * 1e-3) / 1e12
                 out["roofline"]["achieved_sequential_schedule"] = round(seq, 1)
                 out["roofline"]["frac_sequential_schedule"] = round(seq / MFMA_BF16_PEAK_TFLOPS, 4)
-        if world == 1 and not args.no_cpu_baseline and not alsd:     # the CPU leg and its parity check are the greedy path's
+        if args.full and world == 1 and not args.no_cpu_baseline and not alsd:     # the CPU leg and its parity check are the greedy path's
             budget, k = (5.0, 2) if args.tiny else (20.0, 8)
             out["cpu_baseline"], cpu_outputs = cpu_baseline(cfg, sd, audio0, lens0, seconds_budget=budget, max_utt=k)
             try:
                 out["parity"] = parity_vs_cpu_leg(model, cfg, sd, bufs[0], audio0, lens0, cpu_outputs)
             except Exception as e:               # the bench line must still be printed
                 out["parity"] = {"error": repr(e)}
-        if world == 1 and not alsd and not args.tiny:
+        if args.full and world == 1 and not alsd and not args.tiny:
             if not isinstance(out.get("parity"), dict):
                 out["parity"] = {}
             if not args.no_fp32_parity and not args.att_context:
@@ -1197,7 +1207,7 @@ def main():
                 out["parity"]["decode_families_whole_batch"] = decode_family_check(model, bufs[0])
             except Exception as e:               # the bench line must still be printed
                 out["parity"]["decode_families_whole_batch"] = {"error": repr(e)}
-        if world == 1 and not args.tiny and not args.no_extra_configs and not alsd and not args.att_context:
+        if args.full and world == 1 and not args.tiny and not args.no_extra_configs and not alsd and not args.att_context:
             out["configs"] = extra_configs(model, cfg, sd, args, host_sets)
         print(json.dumps(out), flush=True)
     rdist.shutdown()

@@ -6,7 +6,7 @@
 #
 #   tests        python -m pytest tests -m gpu            -> <tag>_pytest_gpu.log, <tag>_parity_fullsize.json
 #   smoke        __graft_entry__.smoke()                  -> <tag>_smoke.log
-#   bench=N      python bench.py --steps N --warmup 3     -> <tag>_bench.json
+#   bench=N      python bench.py --full --steps N --warmup 3 -> <tag>_bench.json (the whole line: parity, configs, ...)
 #   trace        rocprofv3 --kernel-trace --stats of a short bench -> <tag>_kernel_stats.txt
 #   pmc          four --pmc passes (sequential schedule)  -> <tag>_pmc_per_kernel.txt (scripts/pmc_to_traffic.py turns it into profiles/gemm_traffic.json)
 #   gemm=ARGS    scripts/gemm_bench.py ARGS (commas = spaces; e.g. gemm=0,--yardstick) -> <tag>_gemm.txt
@@ -18,6 +18,7 @@
 #   ab:VAR=a,b   the bench with environment VAR set to a, then b (same box, interleaved twice) -> <tag>_ab_VAR.txt
 TAG=${1:?tag}; shift
 mkdir -p gpurun_out
+DEST=$_                 # the output folder made on the line above
 export TMPDIR=/tmp
 cd /tmp && cd - >/dev/null
 rocm-smi --showproductname 2>/dev/null | head -6 > gpurun_out/${TAG}_gpu.txt; nproc >> gpurun_out/${TAG}_gpu.txt
@@ -32,8 +33,8 @@ for WHAT in "$@"; do
       timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/${TAG}_smoke.log 2>&1; tail -2 gpurun_out/${TAG}_smoke.log ;;
     bench|bench=*)
       N=${WHAT#bench=}; [ "$N" == "bench" ] && N=20
-      timeout 900 python bench.py --steps $N --warmup 3 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-      cut -c1-600 gpurun_out/${TAG}_bench.json; tail -3 gpurun_out/${TAG}_bench.err ;;
+      timeout 900 python bench.py --full --steps $N --warmup 3 > "$DEST/${TAG}_bench.json" 2> "$DEST/${TAG}_bench.err"
+      cut -c1-600 "$DEST/${TAG}_bench.json"; tail -3 "$DEST/${TAG}_bench.err" ;;
     trace)
       OUT=gpurun_out/prof_$TAG; rm -rf $OUT
       timeout 900 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- python bench.py --steps 3 --warmup 1 $QUIET --no-profile > gpurun_out/${TAG}_trace.log 2>&1
