@@ -282,6 +282,15 @@ int rs_stream_destroy(void* stream);
  *                        ".b.f32" in NeMo's own row order, values then gates) and "pos.table.f32"; rs_workspace_bytes
  *                        accounts for the mode once they are registered.  ~20x slower; front-end and decode are float32 in
  *                        both modes.
+ *   "precision_i8"       (Zipformer contexts; default 0) 1: the INT8 mode — what onnxruntime computes from the reference's
+ *                        "int8" / "int8-fp32" ONNX files (quantize_dynamic: every MatMul with a constant weight becomes
+ *                        DynamicQuantizeLinear + MatMulInteger + scale Mul): rs_encoder_forward runs the "precision_f32" encoder,
+ *                        and every Linear with a registered "<name>.i8" (int8 [N][K padded to 32] in the layout of "<name>.f32",
+ *                        "<name>.i8.cs" int32 [N] column sums, "<name>.i8.q" f32 [4] = (sw, zw, 0, 0)) runs as rs_gemm_i8q with
+ *                        (sx, zx) taken per utterance over its own rows; a quantized linear_pos ("S{s}.L{j}.attw.pos.w.i8") also
+ *                        needs "pos.enc" (the relative-position encoding, f32 [2 cap - 1][pos_dim]).  Needs the "*.f32" tensors
+ *                        for everything else.  Not bit-exact against onnxruntime (which has never run here): a restatement
+ *                        of its int8 graph (tests/k2_int8_ref.py).
  *   "gemm_f32_x3"        (default 0) 1: the float32 products of rs_gemm_f32-class launches (the "precision_f32" encoder, the AV-HuBERT
  *                        encoder) are formed from three bf16 matrix-core terms — hi / lo split of both operands, hi.hi + hi.lo + lo.hi,
  *                        float32 accumulation: 16 mantissa bits per operand — instead of the exact v_mfma_f32_16x16x4_f32 chain:
@@ -418,6 +427,18 @@ int rs_gemm_f32(rs_ctx* ctx, const float* A, int lda, const float* W, int ldw, f
                 int mask_rows_per_step, int mask_steps, void* stream);
 int rs_relpos_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, const float* bias_u, const float* bias_v,
                             const int32_t* lens, int B, int T, float* ctx_out, void* stream);
+/* The int8 mode's operator (rs_set_option "precision_i8"): onnxruntime's dynamically quantized MatMul
+ * (DynamicQuantizeLinear -> MatMulInteger -> Cast -> Mul(sx * sw) -> bias Add), restated per GROUP of `group` rows (one group per
+ * utterance, M = n_groups * group).  For group g: sx = (max(0, max x) - min(0, min x)) / 255 (1 when that is 0) and
+ * zx = round(-min(0, min x) / sx) over the first lens[g] rows of A (columns < K), written to qp f32 [n_groups][2] = (sx, zx);
+ * xq = clamp(round(x / sx) + zx, 0, 255) (round half to even, x / sx correctly rounded);
+ * out[m][n] = epilogue(float(sum_{k < K} (xq[m][k] - zx) (W[n][k] - zw)) * fl(sx * sw) + bias[n]), the integer sum exact
+ * (v_mfma_i32_16x16x64_i8), then SWOOSHL or SWOOSHR, then + residual[m][n] (pitch ldc, may alias out).
+ * A f32 [M][lda]; W int8 [N][ldw] (ldw % 16 == 0, 16-byte aligned, columns >= K ignored); colsum int32 [N] = sum_{k < K} W[n][k];
+ * wq f32 [2] = (sw, zw) on the device; flags: RS_GEMM_BIAS / SWOOSHL / SWOOSHR / RESIDUAL (RS_GEMM_OUT_F32 implied). */
+int rs_gemm_i8q(rs_ctx* ctx, const float* A, int lda, const int32_t* lens, int group, const int8_t* W, int ldw, const int32_t* colsum,
+                const float* wq, float* out, int ldc, int M, int N, int K, int flags, const float* bias, const float* residual, float* qp,
+                void* stream);
 int rs_glu_dwconv_silu_f32(rs_ctx* ctx, const float* x, const float* dw_w, const float* dw_b, const int32_t* lens, int B,
                            int T, int d, int k, float* out, void* stream);
 

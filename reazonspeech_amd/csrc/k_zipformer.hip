@@ -40,10 +40,28 @@ struct rs_k2_layer32 {
     const float *attw_in_w, *sa_in_w[2], *sa_out_w[2], *ff_in_w[3], *ff_out_w[3], *na_in_w, *na_out_w, *cm_in_w[2], *cm_in_b[2], *cm_out_w[2];
 };
 
+// int8 mode ("precision_i8"): a quantized Linear of the int8 ONNX files — "<name>.i8" int8 [N][pad32(K)] in the layout of
+// "<name>.f32" (padding columns zero), "<name>.i8.cs" int32 [N] column sums over K, "<name>.i8.q" f32 [4] = (sw, zw, 0, 0).
+// w == nullptr: that Linear is not quantized and stays on the float32 GEMM.
+struct rs_k2_q8 {
+    const int8_t* w = nullptr;
+    const int32_t* cs = nullptr;
+    const float* wq = nullptr;
+    int ldw = 0;
+};
+
+struct rs_k2_layer8 {
+    rs_k2_q8 attw_in, pos, sa_in[2], sa_out[2], ff_in[3], ff_out[3], na_in, na_out, cm_in[2], cm_out[2];
+};
+
 struct rs_k2 {
     rs_k2_dims d{};
     std::vector<std::vector<rs_k2_layer>> stacks;
     std::vector<std::vector<rs_k2_layer32>> stacks32;
+    std::vector<std::vector<rs_k2_layer8>> stacks8;
+    rs_k2_q8 emb_out8, jenc8;
+    const float* pos_enc = nullptr;  // "pos.enc" f32 [2 * pos_cap - 1][pos_dim]: the encoding itself, for a quantized linear_pos
+    bool has_i8 = false;             // at least one "<name>.i8" is registered
     const float *conv2_w32 = nullptr, *cnx_pw1_w32 = nullptr, *cnx_pw2_w32 = nullptr, *emb_out_w32 = nullptr, *jenc_w32 = nullptr;
     const float *ds_w[8] = {}, *comb_scale[8] = {}, *out_ds_w = nullptr;
     const float *conv0_w = nullptr, *conv0_b = nullptr, *conv1_w = nullptr, *conv1_b = nullptr, *conv2_b = nullptr, *cnx_dw_w = nullptr,
@@ -1016,12 +1034,18 @@ __global__ __launch_bounds__(256) void k2f_cnx_dw_kernel(const float* __restrict
 // attention weights in float32: one wave per (query, head, utterance); a lane owns keys lane, lane + 64, ..
 //   s[i][j] = q_i . k_j + p_i . pos[j - i];  W[b][h][i][:] = softmax over the utterance's own keys; padded queries / keys: 0
 // qkp f32 [B*T][ld] as in the bf16 kernel; W f32 [B][H][T][Tp].  grid (ceil(T / 4), H, B), block 256
+// pos_stride != 0 (int8 mode): utterance b has a table of its own at pos + b * pos_stride whose row n <-> relative position n - (len - 1)
 __global__ __launch_bounds__(256) void k2f_attn_weights_kernel(const float* __restrict__ qkp, int ld, const float* __restrict__ pos, int cap, int H,
-                                                               const int32_t* __restrict__ lens, int T, int Tp, float* __restrict__ W) {
+                                                               const int32_t* __restrict__ lens, int T, int Tp, float* __restrict__ W,
+                                                               long long pos_stride) {
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6), h = blockIdx.y, b = blockIdx.z;
     if (i >= T) return;
     int len = lens[b];
     len = len < T ? len : T;
+    if (pos_stride) {
+        pos += (size_t)b * pos_stride;
+        cap = len;
+    }
     float* wrow = W + (((size_t)b * H + h) * T + i) * Tp;
     if (i >= len) {
         for (int j = lane; j < Tp; j += 64) wrow[j] = 0.0f;
@@ -1131,6 +1155,21 @@ __global__ __launch_bounds__(256) void k2f_glu_dwconv_swoosh_kernel(const float*
     out[((size_t)b * T + t) * d + c] = swoosh_r_exact(acc + bias[c]);
 }
 
+// int8 mode, linear_pos per utterance: rows 0 .. 2 len - 2 of group b are the encoding's rows for relative positions
+// -(len - 1) .. len - 1 (the 2 T - 1 rows sherpa-onnx's one-utterance graph feeds linear_pos), the group's other rows zeros;
+// lens2[b] = 2 len - 1.  pe f32 [2 cap - 1][P] (row n <-> n - (cap - 1)) -> out f32 [B][2 Ts - 1][P].  grid (2 Ts - 1, B), block 64
+__global__ __launch_bounds__(64) void k2_pos_rows_kernel(const float* __restrict__ pe, int cap, int P, const int32_t* __restrict__ lens, int Ts,
+                                                         float* __restrict__ out, int32_t* __restrict__ lens2) {
+    const int r = blockIdx.x, b = blockIdx.y, G = 2 * Ts - 1;
+    int len = lens[b];
+    len = len < Ts ? len : Ts;
+    if (r == 0 && threadIdx.x == 0) lens2[b] = len > 0 ? 2 * len - 1 : 0;
+    float* o = out + ((size_t)b * G + r) * P;
+    const bool valid = r < 2 * len - 1;
+    const float* src = pe + (size_t)(cap - len + r) * P;
+    for (int c = threadIdx.x; c < P; c += 64) o[c] = valid ? src[c] : 0.0f;
+}
+
 // per-stack lengths: l[s][b] = ceil(len3[b] / ds[s]); len3[b] = max((n_frames[b] - 7) / 2, 0).  rows: 0 = len3, 1 + s = stack s
 __global__ void k2_lens_kernel(const int32_t* __restrict__ n_frames, int B, int n_stacks, int ds0, int ds1, int ds2, int ds3, int ds4, int ds5, int ds6,
                                int ds7, int32_t* __restrict__ out) {
@@ -1227,7 +1266,7 @@ struct K2PlanF32 {
     int T, T1, T2, T3, To, F, F2, F3;
     int Ts[8], Tp[8];
     size_t off_lens, off_a0, off_a1, off_col, off_a2, off_dwo, off_h, off_stackout[8], off_x, off_x0, off_src, off_qkp, off_w, off_big, off_av, off_gate,
-        off_enc, total;
+        off_enc, off_qp, off_lens2, off_pos_in, off_pos_tab, total;
 };
 
 K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max) {
@@ -1273,6 +1312,15 @@ K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max) {
     p.off_av = take(av_b);
     p.off_gate = take(gate_b);
     p.off_enc = take((size_t)B * (p.To > 0 ? p.To : 1) * k.out_dim * 4);
+    if (k.has_i8) {                  // int8 mode: (sx, zx) per utterance, and the per-utterance linear_pos input rows and tables
+        size_t tab = 0;
+        for (int s = 0; s < d.n_stacks; ++s) tab = std::max(tab, (size_t)(2 * p.Ts[s] - 1) * d.num_heads[s] * K2_PD);
+        const size_t G = 2 * (size_t)p.Ts[0] - 1;     // (the first stack runs at the full rate: the longest)
+        p.off_qp = take((size_t)B * 2 * 4);
+        p.off_lens2 = take((size_t)B * 4);
+        p.off_pos_in = take((size_t)B * G * d.pos_dim * 4);
+        p.off_pos_tab = take((size_t)B * tab * 4);
+    }
     p.total = o + 256;
     return p;
 }
@@ -1454,7 +1502,59 @@ int rs_k2_finalize_impl(rs_ctx* ctx) {
         }
         ctx->has_f32 = true;
     }
+    // optional: the int8 mode's quantized Linears ("<name>.i8", ".i8.cs", ".i8.q": each Linear on its own)
+    k.has_i8 = false;
+    k.stacks8.clear();
+    k.emb_out8 = rs_k2_q8{};
+    k.jenc8 = rs_k2_q8{};
+    k.pos_enc = nullptr;
+    auto q8 = [&](const std::string& name, size_t N, size_t K, rs_k2_q8& q) -> int {
+        q = rs_k2_q8{};
+        if (!ctx->tensors.count(name + ".i8")) return RS_OK;
+        const int ldw = pad32((int)K);
+        if (int r = k2_get(ctx, name + ".i8", N * ldw, q.w); r != RS_OK) return r;
+        if (int r = k2_get(ctx, name + ".i8.cs", N, q.cs); r != RS_OK) return r;
+        if (int r = k2_get(ctx, name + ".i8.q", 4, q.wq); r != RS_OK) return r;
+        q.ldw = ldw;
+        k.has_i8 = true;
+        return RS_OK;
+    };
+#define K2_Q8(name, n, kk, field) do { rc = q8(name, (size_t)(n), (size_t)(kk), field); if (rc != RS_OK) return rc; } while (0)
+    K2_Q8("emb.out.w", d0, (size_t)k.embed_freq * c3, k.emb_out8);
+    K2_Q8("joint.enc.w", J, k.out_dim, k.jenc8);
+    k.stacks8.assign(d.n_stacks, {});
+    bool any_pos = false;
+    for (int s = 0; s < d.n_stacks; ++s) {
+        const size_t dd = d.encoder_dim[s], H = d.num_heads[s], hid = 3 * dd / 4;
+        const size_t ff[3] = {(size_t)d.ff_dim[s] * 3 / 4, (size_t)d.ff_dim[s], (size_t)d.ff_dim[s] * 5 / 4};
+        k.stacks8[s].assign(d.num_layers[s], rs_k2_layer8{});
+        for (int j = 0; j < d.num_layers[s]; ++j) {
+            rs_k2_layer8& L = k.stacks8[s][j];
+            const std::string p = "S" + std::to_string(s) + ".L" + std::to_string(j) + ".";
+            K2_Q8(p + "attw.in.w", (2 * K2_QD + K2_PD) * H, dd, L.attw_in);
+            K2_Q8(p + "attw.pos.w", H * K2_PD, d.pos_dim, L.pos);
+            any_pos = any_pos || L.pos.w;
+            for (int a = 0; a < 2; ++a) {
+                const std::string q = p + (a ? "sa2." : "sa1."), c = p + (a ? "cm2." : "cm1.");
+                K2_Q8(q + "in.w", H * K2_VD, dd, L.sa_in[a]);
+                K2_Q8(q + "out.w", dd, H * K2_VD, L.sa_out[a]);
+                K2_Q8(c + "in.w", 2 * dd, dd, L.cm_in[a]);
+                K2_Q8(c + "out.w", dd, dd, L.cm_out[a]);
+            }
+            for (int f = 0; f < 3; ++f) {
+                const std::string q = p + "ff" + std::to_string(f + 1) + ".";
+                K2_Q8(q + "in.w", ff[f], dd, L.ff_in[f]);
+                K2_Q8(q + "out.w", dd, ff[f], L.ff_out[f]);
+            }
+            K2_Q8(p + "na.in.w", 3 * hid, dd, L.na_in);
+            K2_Q8(p + "na.out.w", dd, hid, L.na_out);
+        }
+    }
+    if (any_pos) K2_GET("pos.enc", (size_t)(2 * k.pos_cap - 1) * d.pos_dim, k.pos_enc);
+#undef K2_Q8
     if (ctx->precision_f32 && !ctx->has_f32) ctx->precision_f32 = 0;
+    ctx->has_i8 = k.has_i8;
+    if (ctx->precision_i8 && !(ctx->has_f32 && k.has_i8)) ctx->precision_i8 = 0;
 #undef K2_GET
     ctx->decode_narrow = true;
     ctx->finalized = true;
@@ -1472,6 +1572,7 @@ int rs_k2_enc_frames_impl(const rs_ctx* ctx, int n_feat) {
 size_t rs_k2_workspace_bytes_impl(const rs_ctx* ctx, int B, int t_max) {
     const size_t a = k2_plan(ctx, B, t_max > 9 ? t_max : 9).total;
     if (!ctx->has_f32) return a;                      // the float32 parity mode keeps float32 activations: about twice the scratch
+                                                      // (and, with "*.i8" tensors, the int8 mode's scales and position rows)
     const size_t b = k2_plan_f32(ctx, B, t_max > 9 ? t_max : 9).total;
     return a > b ? a : b;
 }
@@ -1484,7 +1585,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
     if (t_max < 9) return rs_fail(ctx, RS_EINVAL, "zipformer: %d feature frames are too few for encoder_embed (9 are needed)", t_max);
-    if (ctx->precision_f32) return rs_k2_encoder_forward_f32(ctx, feats, n_frames, B, t_max, enc_out, joint_enc, enc_lens, workspace, workspace_bytes, s);
+    if (ctx->precision_f32 || ctx->precision_i8) return rs_k2_encoder_forward_f32(ctx, feats, n_frames, B, t_max, enc_out, joint_enc, enc_lens, workspace, workspace_bytes, s);
     const K2Plan pl = k2_plan(ctx, B, t_max);
     if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "zipformer: workspace %zu < %zu", workspace_bytes, pl.total);
     char* ws = reinterpret_cast<char*>(workspace);
@@ -1731,6 +1832,17 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
                     const float* res) -> int {
         return rs_launch_gemm_f32(ctx, A, lda, Wt, K, out, ldc, (int)M, N, K, flags, bias, 1.0f, res, nullptr, 0, 0, s);
     };
+    // int8 mode: a Linear with a registered "<name>.i8" runs as onnxruntime's quantized MatMul (k_int8.hip) with (sx, zx) taken per
+    // utterance over its own `lens[b]` rows of the `group` rows it has in A; K is the Linear's own width (A / weights may be padded)
+    const bool i8 = ctx->precision_i8 && k.has_i8;
+    float* qp = i8 ? fp(pl.off_qp) : nullptr;
+    auto lin = [&](const rs_k2_q8& q, const float* A, int lda, const float* Wt, int Kp, int K, float* out, int ldc, long long M, int N, int flags,
+                   const float* bias, const float* res, const int32_t* lens, int group) -> int {
+        if (!i8 || !q.w) return gemm(A, lda, Wt, Kp, out, ldc, M, N, flags, bias, res);
+        if (M <= 0 || group <= 0) return RS_OK;
+        if (int r = rs_launch_i8_range(ctx, A, lda, lens, group, (int)(M / group), K, qp, s); r != RS_OK) return r;
+        return rs_launch_gemm_i8q(ctx, A, lda, group, qp, q.w, q.ldw, q.cs, q.wq, out, ldc, (int)M, N, K, flags, bias, res, s);
+    };
     const int RES = RS_GEMM_BIAS | RS_GEMM_RESIDUAL;
     hipLaunchKernelGGL(k2_lens_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_frames, B, d.n_stacks, d.downsampling[0], d.downsampling[1],
                        d.downsampling[2], d.downsampling[3], d.downsampling[4], d.downsampling[5], d.downsampling[6], d.downsampling[7], lens_all);
@@ -1748,7 +1860,7 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
     RS_TRY(gemm(hbuf, 3 * c3, k.cnx_pw2_w32, 3 * c3, a2, c3, rows3, c3, RES, k.cnx_pw2_b, a2));
     const int d0 = d.encoder_dim[0];
     float* emb = x0;
-    RS_TRY(gemm(a2, F3 * c3, k.emb_out_w32, F3 * c3, emb, d0, M3, d0, RS_GEMM_BIAS, k.emb_out_b, nullptr));
+    RS_TRY(lin(k.emb_out8, a2, F3 * c3, k.emb_out_w32, F3 * c3, F3 * c3, emb, d0, M3, d0, RS_GEMM_BIAS, k.emb_out_b, nullptr, lens3, T3));
     hipLaunchKernelGGL(k2_biasnorm_kernel, dim3((unsigned)((M3 + 3) / 4)), dim3(256), 0, s, emb, k.emb_norm_bias, k.emb_norm_scale, (const float*)nullptr,
                        (const float*)nullptr, (int)M3, d0, emb, (uint16_t*)nullptr);
     if (k.tap_embed) RS_HIP(ctx, hipMemcpyAsync(k.tap_embed, emb, (size_t)M3 * d0 * 4, hipMemcpyDeviceToDevice, s));
@@ -1770,34 +1882,51 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
         for (int j = 0; j < d.num_layers[st]; ++j) {
             const rs_k2_layer& L = k.stacks[st][j];
             const rs_k2_layer32& L32 = k.stacks32[st][j];
+            const rs_k2_layer8 L8 = i8 ? k.stacks8[st][j] : rs_k2_layer8{};
             const size_t n = (size_t)M * dd;
             const bool last = j == d.num_layers[st] - 1;
             float* xs = nxt;
             // attention weights from the layer's input
-            RS_TRY(gemm(cur, dd, L32.attw_in_w, dd, qkp, nin, M, nin, RS_GEMM_BIAS, L.attw_in_b, nullptr));
-            hipLaunchKernelGGL(k2f_attn_weights_kernel, dim3((Ts + 3) / 4, H, B), dim3(256), 0, s, qkp, nin, L.pos_proj, k.pos_cap, H, lens, Ts, Tp, W);
+            RS_TRY(lin(L8.attw_in, cur, dd, L32.attw_in_w, dd, dd, qkp, nin, M, nin, RS_GEMM_BIAS, L.attw_in_b, nullptr, lens, Ts));
+            if (L8.pos.w) {
+                // linear_pos of each utterance's own 2 len - 1 position rows, with its own scale, into a table per utterance
+                const int G = 2 * Ts - 1, P = d.pos_dim;
+                float *pos_in = fp(pl.off_pos_in), *pos_tab = fp(pl.off_pos_tab);
+                int32_t* lens2 = reinterpret_cast<int32_t*>(ws + pl.off_lens2);
+                hipLaunchKernelGGL(k2_pos_rows_kernel, dim3(G, B), dim3(64), 0, s, k.pos_enc, k.pos_cap, P, lens, Ts, pos_in, lens2);
+                RS_CHECK_LAUNCH(ctx, "zipformer (int8 mode) position rows");
+                RS_TRY(lin(L8.pos, pos_in, P, nullptr, P, P, pos_tab, H * K2_PD, (long long)B * G, H * K2_PD, 0, nullptr, nullptr, lens2, G));
+                hipLaunchKernelGGL(k2f_attn_weights_kernel, dim3((Ts + 3) / 4, H, B), dim3(256), 0, s, qkp, nin, (const float*)pos_tab, k.pos_cap, H, lens, Ts,
+                                   Tp, W, (long long)G * H * K2_PD);
+            } else {
+                hipLaunchKernelGGL(k2f_attn_weights_kernel, dim3((Ts + 3) / 4, H, B), dim3(256), 0, s, qkp, nin, L.pos_proj, k.pos_cap, H, lens, Ts, Tp, W,
+                                   0LL);
+            }
             auto ffn = [&](int f, int width, const float* in, const float* res) -> int {
-                if (int r = gemm(in, dd, L32.ff_in_w[f], dd, big, width, M, width, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, L.ff_in_b[f], nullptr); r != RS_OK) return r;
-                return gemm(big, width, L32.ff_out_w[f], width, xs, dd, M, dd, RES, L.ff_out_b[f], res);
+                if (int r = lin(L8.ff_in[f], in, dd, L32.ff_in_w[f], dd, dd, big, width, M, width, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, L.ff_in_b[f], nullptr, lens, Ts);
+                    r != RS_OK)
+                    return r;
+                return lin(L8.ff_out[f], big, width, L32.ff_out_w[f], width, width, xs, dd, M, dd, RES, L.ff_out_b[f], res, lens, Ts);
             };
             auto self_attn = [&](int a) -> int {
-                if (int r = gemm(xs, dd, L32.sa_in_w[a], dd, big, vw, M, vw, RS_GEMM_BIAS, L.sa_in_b[a], nullptr); r != RS_OK) return r;
+                if (int r = lin(L8.sa_in[a], xs, dd, L32.sa_in_w[a], dd, dd, big, vw, M, vw, RS_GEMM_BIAS, L.sa_in_b[a], nullptr, lens, Ts); r != RS_OK) return r;
                 if (vwp != vw && hipMemsetAsync(av, 0, (size_t)M * vwp * 4, s) != hipSuccess) return rs_fail(ctx, RS_EHIP, "memset failed");
                 hipLaunchKernelGGL(k2f_pv_kernel, dim3(Ts, B), dim3((vw + 63) / 64 * 64), 0, s, W, H, Tp, big, vw, lens, Ts, av, vwp);
-                return gemm(av, vwp, L32.sa_out_w[a], vwp, xs, dd, M, dd, RES, L.sa_out_b[a], xs);
+                return lin(L8.sa_out[a], av, vwp, L32.sa_out_w[a], vwp, vw, xs, dd, M, dd, RES, L.sa_out_b[a], xs, lens, Ts);
             };
             auto conv_module = [&](int a) -> int {
-                if (int r = gemm(xs, dd, L32.cm_in_w[a], dd, big, 2 * dd, M, 2 * dd, RS_GEMM_BIAS, L32.cm_in_b[a], nullptr); r != RS_OK) return r;
+                if (int r = lin(L8.cm_in[a], xs, dd, L32.cm_in_w[a], dd, dd, big, 2 * dd, M, 2 * dd, RS_GEMM_BIAS, L32.cm_in_b[a], nullptr, lens, Ts); r != RS_OK)
+                    return r;
                 hipLaunchKernelGGL(k2f_glu_dwconv_swoosh_kernel, dim3((dd + 255) / 256, Ts, B), dim3(256), 0, s, big, L.cm_dw_w[a], L.cm_dw_b[a], lens, Ts, dd, kk, av);
-                return gemm(av, dd, L32.cm_out_w[a], dd, xs, dd, M, dd, RES, L.cm_out_b[a], xs);
+                return lin(L8.cm_out[a], av, dd, L32.cm_out_w[a], dd, dd, xs, dd, M, dd, RES, L.cm_out_b[a], xs, lens, Ts);
             };
             RS_TRY(ffn(0, d.ff_dim[st] * 3 / 4, cur, cur));         // xs = cur + ff1(cur)
             // non-linear attention
-            RS_TRY(gemm(xs, dd, L32.na_in_w, dd, big, 3 * hid, M, 3 * hid, RS_GEMM_BIAS, L.na_in_b, nullptr));
+            RS_TRY(lin(L8.na_in, xs, dd, L32.na_in_w, dd, dd, big, 3 * hid, M, 3 * hid, RS_GEMM_BIAS, L.na_in_b, nullptr, lens, Ts));
             if (hidp != hid) RS_HIP(ctx, hipMemsetAsync(av, 0, (size_t)M * hidp * 4, s));
             hipLaunchKernelGGL(k2f_na_gate_kernel, dim3((unsigned)(((size_t)M * hid + 255) / 256)), dim3(256), 0, s, big, hid, (size_t)M, gate);
             hipLaunchKernelGGL(k2f_na_pv_kernel, dim3((hid + 255) / 256, (Ts + 3) / 4, B), dim3(256), 0, s, W, H, Tp, gate, big, hid, lens, Ts, av, hidp);
-            RS_TRY(gemm(av, hidp, L32.na_out_w, hidp, xs, dd, M, dd, RES, L.na_out_b, xs));
+            RS_TRY(lin(L8.na_out, av, hidp, L32.na_out_w, hidp, hid, xs, dd, M, dd, RES, L.na_out_b, xs, lens, Ts));
             RS_TRY(self_attn(0));
             RS_TRY(conv_module(0));
             RS_TRY(ffn(1, d.ff_dim[st], xs, xs));
@@ -1835,7 +1964,8 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
     }
     hipLaunchKernelGGL(k2_output_kernel, dim3(pl.To, B), dim3(256), 0, s, pc, lens3, T3, pl.To, k.out_dim, k.out_ds_w, encf, (uint16_t*)nullptr, enc_lens);
     RS_CHECK_LAUNCH(ctx, "zipformer (float32 mode) output");
-    RS_TRY(gemm(encf, k.out_dim, k.jenc_w32, k.out_dim, joint_enc, d.joiner_dim, (long long)B * pl.To, d.joiner_dim, RS_GEMM_BIAS, ctx->jenc_b, nullptr));
+    RS_TRY(lin(k.jenc8, encf, k.out_dim, k.jenc_w32, k.out_dim, k.out_dim, joint_enc, d.joiner_dim, (long long)B * pl.To, d.joiner_dim, RS_GEMM_BIAS, ctx->jenc_b,
+               nullptr, enc_lens, pl.To));
 #undef RS_TRY
     return RS_OK;
 }

@@ -327,6 +327,13 @@ int rs_set_option(rs_ctx* ctx, const char* key, int value) {
         ctx->precision_f32 = value != 0;
         return RS_OK;
     }
+    if (!strcmp(key, "precision_i8")) {            // Zipformer: the float32 encoder with its quantized Linears ("*.i8") as onnxruntime's int8 MatMul
+        if (!ctx->k2) return rs_fail(ctx, RS_EINVAL, "option 'precision_i8' applies to a Zipformer context only");
+        if (value && !(ctx->has_f32 && ctx->has_i8))
+            return rs_fail(ctx, RS_EMISSING, "precision_i8: the float32 weights (\"*.f32\") and the quantized ones (\"*.i8\") must be registered and rs_finalize run");
+        ctx->precision_i8 = value != 0;
+        return RS_OK;
+    }
     if (!strcmp(key, "gemm_f32_x3")) {             // float32 products as three bf16 matrix-core terms (k_f32.hip X3): the AV-HuBERT family, and the
         ctx->gemm_f32_x3 = value != 0;             // "precision_f32" mode of the others ("fp32x3": not an IEEE chain; held to the same goldens)
         return RS_OK;

@@ -150,6 +150,8 @@ struct rs_ctx {
                                     // 0 = plain pw1 product, GLU in the depthwise kernel ($RS_FUSE_GLU; A/B and layout tests)
     bool has_f32 = false;           // the "*.f32" tensors of the float32 parity mode are registered (all or none)
     int precision_f32 = 0;          // rs_set_option("precision_f32"): 1 = rs_encoder_forward runs k_f32.hip's float32 encoder
+    bool has_i8 = false;            // Zipformer: at least one quantized Linear ("<name>.i8") is registered
+    int precision_i8 = 0;           // rs_set_option("precision_i8") (Zipformer only): the float32 encoder with its quantized Linears ("*.i8") on k_int8.hip
     rs_f32_weights f32;
     bool env_read = false;          // the $RS_* defaults were applied (once, by the first rs_finalize; rs_set_option wins afterwards)
     // parity taps (rs_encoder_set_taps): copies of the residual stream taken inside rs_encoder_forward
@@ -249,6 +251,11 @@ int rs_launch_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, con
                             const int32_t* lens, int B, int T, float* out, hipStream_t s);
 int rs_launch_glu_dwconv_f32(rs_ctx* ctx, const float* x, const float* w, const float* b, const int32_t* lens, int B, int T,
                              int d, int k, float* out, hipStream_t s);
+// int8 mode (k_int8.hip): (sx, zx) per group of `group` rows from the first lens[g] rows, columns < K -> qp f32 [n_groups][2]; then
+// out = epilogue(float(sum_k (xq - zx)(Wq - zw)) * fl(sx sw) + bias) with W int8 [N][ldw], colsum[n] = sum_{k < K} W[n][k], wq = (sw, zw)
+int rs_launch_i8_range(rs_ctx* ctx, const float* A, int lda, const int32_t* lens, int group, int n_groups, int K, float* qp, hipStream_t s);
+int rs_launch_gemm_i8q(rs_ctx* ctx, const float* A, int lda, int group, const float* qp, const int8_t* W, int ldw, const int32_t* colsum,
+                       const float* wq, float* out, int ldc, int M, int N, int K, int flags, const float* bias, const float* residual, hipStream_t s);
 size_t rs_encoder_f32_workspace_bytes(const rs_ctx* ctx, int B, int t_max);
 int rs_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out,
                            float* joint_enc, int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s);

@@ -56,14 +56,15 @@ def resolve_checkpoint(language, precision, checkpoint=None):
         return hf.snapshot_download(repo), files
 
 
-def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute="bf16", synthetic=False):
+def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
       device (str): "cuda" / "cuda:N"; None picks "cuda".  The reference's default is "cpu" (sherpa-onnx's provider); this
         package has no CPU path — "cpu" and "coreml" raise.
-      precision (str): "fp32", "int8" or "int8-fp32": which ONNX files are read, validated like the reference (:61-62).  The HIP
-        path computes bf16 x bf16 -> f32 from the float32 weights; quantized graphs are refused when they are actually read.
+      precision (str): "fp32", "int8" or "int8-fp32": which ONNX files are read, validated like the reference (:61-62).  The
+        float32 files run in the `compute` mode below; the int8 files ("int8": encoder, decoder and joiner *.int8.onnx;
+        "int8-fp32": the decoder's float file) are read by runtime/k2_onnx.py: read_k2_onnx_quantized and run in the int8 mode.
       language (str): "ja", "ja-en" or "ja-en-mls-5k" (:26-38)
       checkpoint (str): directory with tokens.txt and the three ONNX files (default: $REAZONSPEECH_K2_CHECKPOINT, then the
         Hugging Face cache, then the hub)
@@ -74,6 +75,11 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
         exact float32 decode.  "fp32": the parity mode — float32 weights, activations and arithmetic end to end, i.e. what
         onnxruntime computes from the reference's default float32 graphs; greedy ids identical to the float32 oracle, ~6x slower.
         "fp32x3": the float32 mode with its products formed from three bf16 matrix-core terms (2x faster; same 256-row golden, ids identical).
+        None (default): "bf16" for the float32 files, the int8 mode for the int8 files.  The INT8 mode is onnxruntime's int8 graph
+        restated: the float32 mode with every quantized Linear as DynamicQuantizeLinear (scale and zero point per utterance) +
+        MatMulInteger on the int8 matrix cores + the scale Mul (csrc/k_int8.hip); not bit-exact against onnxruntime, which has never
+        run here.  An explicit "bf16" / "fp32" / "fp32x3" with the int8 files raises ValueError.  With `synthetic` weights and an int8
+        `precision`, the float weights are quantized with onnxruntime's QInt8 recipe (runtime/k2_weights.py: quantize_k2_linears).
         (`precision` keeps the reference's meaning: WHICH files are read.)
 
     A real icefall export has never been read by runtime/k2_onnx.py (no file is reachable from the build environment): the reader
@@ -95,22 +101,39 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
                            "(use the reference package for those)")
     if not torch.cuda.is_available():
         raise RuntimeError("reazonspeech_amd needs a ROCm GPU: torch.cuda.is_available() is False")
-    if compute not in ("bf16", "fp32", "fp32x3"):
-        raise ValueError(f"compute must be 'bf16', 'fp32' or 'fp32x3', not {compute!r}")
+    if compute not in (None, "bf16", "fp32", "fp32x3"):
+        raise ValueError(f"compute must be None, 'bf16', 'fp32' or 'fp32x3', not {compute!r}")
+    quantized = precision in ("int8", "int8-fp32")
+    if quantized and compute is not None:
+        raise ValueError(f"precision {precision!r} reads the int8 ONNX files, which run in the int8 mode only: leave compute at None "
+                         f"(got {compute!r}; compute applies to precision='fp32')")
     want_synthetic = config is not None or synthetic or os.environ.get(SYNTHETIC_ENV, "0") not in ("", "0")
     if want_synthetic and not checkpoint:
         basedir, files = None, None
     else:
         basedir, files = resolve_checkpoint(language, precision, checkpoint)
-    if basedir:
+    paths = [os.path.join(basedir, files[p]) for p in ("encoder", "decoder", "joiner")] if basedir else None
+    q = None
+    if basedir and quantized:
+        from ...runtime.k2_onnx import read_k2_onnx_quantized
+        cfg, sd, q = read_k2_onnx_quantized(*paths)
+    elif basedir:
         from ...runtime.k2_onnx import read_k2_onnx
-        cfg, sd = read_k2_onnx(os.path.join(basedir, files["encoder"]), os.path.join(basedir, files["decoder"]), os.path.join(basedir, files["joiner"]))
+        cfg, sd = read_k2_onnx(*paths)
+    if basedir:
         tokens = read_tokens(os.path.join(basedir, files["tokens"]))
         if len(tokens) != cfg.vocab_size:
             raise ValueError(f"tokens.txt has {len(tokens)} symbols, the joiner {cfg.vocab_size} outputs")
         cfg = cfg.with_(unk_id=tokens.index("<unk>") if "<unk>" in tokens else -1)
-        return K2Model(cfg, sd, tokens, device=device, precision=compute)
+        if quantized:
+            return K2Model(cfg, sd, tokens, device=device, precision="int8", qweights=q)
+        return K2Model(cfg, sd, tokens, device=device, precision=compute or "bf16")
     cfg = config or ZIPFORMER_159M
     print(f"[reazonspeech_amd] WARNING: SEEDED SYNTHETIC weights of the {cfg.n_params() / 1e6:.0f}M Zipformer architecture were requested "
           f"(`config=` / `synthetic=True` / ${SYNTHETIC_ENV}): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
-    return K2Model(cfg, synthetic_state_dict_k2(cfg, seed), synthetic_tokens(cfg.vocab_size, seed), device=device, precision=compute)
+    sd = synthetic_state_dict_k2(cfg, seed)
+    if quantized:
+        from ...runtime.k2_weights import quantize_k2_linears, dequantize_k2_linears
+        q = quantize_k2_linears(cfg, sd)
+        return K2Model(cfg, dequantize_k2_linears(sd, q), synthetic_tokens(cfg.vocab_size, seed), device=device, precision="int8", qweights=q)
+    return K2Model(cfg, sd, synthetic_tokens(cfg.vocab_size, seed), device=device, precision=compute or "bf16")

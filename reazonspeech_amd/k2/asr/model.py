@@ -59,14 +59,17 @@ def synthetic_tokens(vocab_size, seed=0):
 
 
 class K2Model:
-    def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16"):
+    def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None):
         """precision: "bf16" = the throughput mode; "fp32" = float32 weights, activations and arithmetic end to end (what
-        onnxruntime computes from the reference's default float32 graphs: pkg/k2-asr/src/huggingface.py:16,40-45)"""
+        onnxruntime computes from the reference's default float32 graphs: pkg/k2-asr/src/huggingface.py:16,40-45); "fp32x3" = the
+        float32 mode with three-term bf16 products; "int8" = onnxruntime's int8 graph restated (the "int8" / "int8-fp32" files):
+        the float32 mode with every Linear of `qweights` ({icefall name: (Wq int8 [out][in], sw, zw)}: read_k2_onnx_quantized or
+        quantize_k2_linears) as a dynamically quantized MatMul, scales per utterance; `state_dict` then holds the dequantized weights"""
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
         self.cfg = cfg
         self.tokens = list(tokens)
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights)
         self.device = self.am.device
 
     # ---- sherpa-onnx's surface ------------------------------------------------------------------------------------------

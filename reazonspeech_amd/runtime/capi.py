@@ -31,6 +31,7 @@ EXPORTS = [
     "rs_layernorm", "rs_relpos_attention", "rs_glu_dwconv_silu", "rs_glu_dwconv_silu_layout", "rs_encoder_set_taps", "rs_set_option", "rs_stream_create", "rs_stream_destroy",
     "rs_rnnt_alsd", "rs_rnnt_alsd_workspace_bytes", "rs_rnnt_beam", "rs_rnnt_beam_workspace_bytes", "rs_host_stage_rows",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
+    "rs_gemm_i8q",
     "rs_k2_create", "rs_k2_encoder_set_taps",
     "rs_avsr_create", "rs_avsr_workspace_bytes", "rs_avsr_encoder_forward", "rs_avsr_encoder_set_taps", "rs_avsr_decoder_state_bytes",
     "rs_avsr_decoder_begin", "rs_avsr_decoder_step",
@@ -164,6 +165,7 @@ def load():
     lib.rs_gemm_f32.argtypes = [vp, vp, c_int, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, vp, c_float, vp, vp, c_int,
                                 c_int, vp]
     lib.rs_relpos_attention_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, vp, vp]
+    lib.rs_gemm_i8q.argtypes = [vp, vp, c_int, vp, c_int, vp, c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp]
     lib.rs_glu_dwconv_silu_f32.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp]
     lib.rs_encoder_set_ctc_out.argtypes = [vp, vp, vp]
     lib.rs_k2_create.argtypes = [POINTER(c_void_p), c_int, POINTER(RsK2Dims)]
@@ -407,6 +409,16 @@ class Context:
         self.check(self.lib.rs_gemm_bf16(self._h, _ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(out),
                                          out.stride(0), M, N, K, flags, _ptr(bias), float(alpha), _ptr(residual),
                                          _ptr(mask_lens), mask_rows, mask_steps, c_void_p(stream)))
+
+    def gemm_i8q(self, A, lens, group, W, colsum, wq, out, qp, K=None, flags=0, bias=None, residual=None, stream=0):
+        """the int8 mode's quantized Linear (include/rs_asr.h rs_gemm_i8q): A f32 [M][>= K] in groups of `group` rows with lens
+        int32 [M / group] valid rows each, W int8 [N][ldw], colsum int32 [N], wq f32 [2] = (sw, zw) -> out f32 [M][N], qp f32
+        [M / group][2] = (sx, zx)"""
+        M = A.shape[0]
+        N = W.shape[0]
+        K = A.shape[1] if K is None else int(K)
+        self.check(self.lib.rs_gemm_i8q(self._h, _ptr(A), A.stride(0), _ptr(lens), int(group), _ptr(W), W.stride(0), _ptr(colsum), _ptr(wq),
+                                        _ptr(out), out.stride(0), M, N, K, flags, _ptr(bias), _ptr(residual), _ptr(qp), c_void_p(stream)))
 
     def gemm_f32(self, A, W, out, flags=0, bias=None, alpha=1.0, residual=None, mask_lens=None, mask_rows=0, mask_steps=0,
                  stream=0):

@@ -12,7 +12,16 @@ OnnxJoiner(output_linear) after convert_scaled_to_non_scaled):
     SimpleDownsample's softmax(bias) a [ds, 1, 1] operand of a Mul in the downsample's scope (log of it is the bias up to a
     constant, which softmax ignores).
 The architecture is not in the metadata of an offline Zipformer2 export: it is derived from the tensor shapes.
-Quantized graphs (the "int8" / "int8-fp32" precisions) are refused."""
+`read_k2_onnx` refuses quantized graphs (the "int8" / "int8-fp32" precisions); `read_k2_onnx_quantized` reads them.
+
+[UPSTREAM, unverifiable here] the int8 files: icefall's export-onnx.py runs onnxruntime.quantization.quantize_dynamic(
+op_types_to_quantize=["MatMul"], weight_type=QInt8) on the float files.  Only MatMuls whose B operand is a constant are rewritten
+(MatMulConstBOnly): every Linear applied to a 3-D tensor — in the encoder file all the encoder's Linears, linear_pos and
+encoder_proj.  OnnxDecoder / OnnxJoiner squeeze to 2-D, so decoder_proj and output_linear export as Gemm and stay float32;
+convolutions and attention's activation x activation products stay float32.  Each rewritten MatMul becomes
+    DynamicQuantizeLinear(x) -> (xq uint8, sx, zx);  MatMulInteger(xq, Wq int8 [K][N], zx, zw) -> int32;  Cast -> float;
+    Mul(., Mul(sx, sw));  the original bias Add
+with a per-tensor weight scale sw and zero point zw (QInt8's default is symmetric, zw = 0; nothing here relies on that)."""
 import math
 import re
 
@@ -51,16 +60,21 @@ def _put(sd, seen, key, value):
     sd[key] = value
 
 
-def _collect(model, sd, seen):
-    if any(n.op_type in ("DynamicQuantizeLinear", "MatMulInteger", "QLinearMatMul", "ConvInteger", "DequantizeLinear") for n in model.nodes):
-        raise UnsupportedCheckpoint("a quantized (int8) ONNX graph: only the float32 files are read")
+def _collect(model, sd, seen, q=None):
+    """q is None: a quantized graph is refused; else its quantize_dynamic chains are read first (`_collect_quantized`)"""
+    chain = set()
+    if q is None:
+        if any(n.op_type in _QUANT_OPS for n in model.nodes):
+            raise UnsupportedCheckpoint("a quantized (int8) ONNX graph: only the float32 files are read")
+    else:
+        chain = _collect_quantized(model, sd, seen, q)
     init = model.initializers
     for name, arr in init.items():
         if re.search(r"\.(weight|bias|bypass_scale)$", name) and arr.dtype == np.float32:
             sd[_canonical(name)] = torch.from_numpy(np.array(arr))
     for n in model.nodes:
         consts = [i for i in n.inputs if i in init]
-        if not consts:
+        if not consts or id(n) in chain or n.op_type in _QUANT_OPS:
             continue
         scope = _canonical(_scope(n.name) + ".")[:-1]
         if n.op_type == "MatMul" and len(n.inputs) == 2 and n.inputs[1] in init and init[n.inputs[1]].ndim == 2:
@@ -82,6 +96,75 @@ def _collect(model, sd, seen):
                 if abs(total - 1.0) > 1e-4:
                     raise UnsupportedCheckpoint(f"the constant under {scope!r} sums to {total:.6f}: not a folded softmax(bias) (export layout differs)")
                 _put(sd, seen, scope + ".bias", torch.from_numpy(np.log(np.array(c, np.float64).reshape(-1)).astype(np.float32)))
+
+
+_QUANT_OPS = ("DynamicQuantizeLinear", "MatMulInteger", "QLinearMatMul", "ConvInteger", "DequantizeLinear")
+
+
+def _scalar(init, name, what, scope):
+    if name not in init:
+        raise UnsupportedCheckpoint(f"a quantized (int8) MatMul under {scope!r} whose {what} is not a constant: not the quantize_dynamic layout")
+    a = np.asarray(init[name])
+    if a.size != 1:
+        raise UnsupportedCheckpoint(f"a quantized (int8) MatMul under {scope!r} with a per-channel {what} ({a.size} values): only per-tensor "
+                                    "quantization (quantize_dynamic's default) is read")
+    return a.reshape(-1)[0]
+
+
+def _collect_quantized(model, sd, seen, q):
+    """the quantize_dynamic chains of one file (module docstring), recognised by graph structure: each MatMulInteger must take
+    its A operand and zero point from a DynamicQuantizeLinear, a constant int8 B with a per-tensor zero point, and feed a Cast
+    whose result is multiplied by Mul(sx, sw) with a per-tensor constant sw.  The Linear is the MatMulInteger's node scope (as
+    for a float MatMul); sd receives the dequantized weight (Wq - zw) sw [out][in], q the quantized one.  -> the chain's nodes"""
+    for n in model.nodes:
+        if n.op_type in ("QLinearMatMul", "ConvInteger", "DequantizeLinear"):
+            raise UnsupportedCheckpoint(f"a quantized (int8) ONNX graph with {n.op_type} ({n.name!r}): only quantize_dynamic's "
+                                        "DynamicQuantizeLinear + MatMulInteger form is read")
+    init = model.initializers
+    producer = {o: n for n in model.nodes for o in n.outputs}
+    users = {}
+    for n in model.nodes:
+        for i in n.inputs:
+            users.setdefault(i, []).append(n)
+    chain = set()
+    for n in model.nodes:
+        if n.op_type != "MatMulInteger":
+            continue
+        scope = _canonical(_scope(n.name) + ".")[:-1]
+        if len(n.inputs) < 2 or n.inputs[1] not in init or np.asarray(init[n.inputs[1]]).ndim != 2 or init[n.inputs[1]].dtype != np.int8:
+            raise UnsupportedCheckpoint(f"a quantized (int8) MatMulInteger under {scope!r} without a constant int8 weight: only MatMuls "
+                                        "with a constant B (MatMulConstBOnly) are read")
+        if scope.startswith("joiner.decoder_proj") or scope.startswith("joiner.output_linear"):
+            raise UnsupportedCheckpoint(f"a quantized (int8) {scope!r}: decoder_proj and output_linear are read as float32 Gemm "
+                                        "nodes only (the export squeezes them to 2-D, so quantize_dynamic leaves them float32)")
+        dql = producer.get(n.inputs[0])
+        if dql is None or dql.op_type != "DynamicQuantizeLinear" or len(dql.outputs) < 3 or len(n.inputs) < 3 or n.inputs[2] != dql.outputs[2]:
+            raise UnsupportedCheckpoint(f"a quantized (int8) MatMulInteger under {scope!r} whose activation does not come from a "
+                                        "DynamicQuantizeLinear: not the quantize_dynamic layout")
+        zw = int(_scalar(init, n.inputs[3], "weight zero point", scope)) if len(n.inputs) > 3 and n.inputs[3] else 0
+        cast = [u for u in users.get(n.outputs[0], []) if u.op_type == "Cast"]
+        muls = [u for u in users.get(cast[0].outputs[0], []) if u.op_type == "Mul"] if len(cast) == 1 else []
+        sw = None
+        for m in muls:
+            other = [i for i in m.inputs if i != cast[0].outputs[0]]
+            sm = producer.get(other[0]) if len(other) == 1 else None
+            if sm is not None and sm.op_type == "Mul" and dql.outputs[1] in sm.inputs:
+                sw_name = [i for i in sm.inputs if i != dql.outputs[1]]
+                if len(sw_name) == 1:
+                    sw = float(np.float32(_scalar(init, sw_name[0], "weight scale", scope)))
+                    chain.update((id(m), id(sm)))
+                    break
+        if sw is None:
+            raise UnsupportedCheckpoint(f"a quantized (int8) MatMulInteger under {scope!r} without its scale Mul(Cast(.), Mul(sx, sw)): "
+                                        "not the quantize_dynamic layout")
+        wq = np.ascontiguousarray(np.asarray(init[n.inputs[1]]).T)                         # [out][in]
+        deq = (wq.astype(np.float32) - np.float32(zw)) * np.float32(sw)
+        _put(sd, seen, scope + ".weight", torch.from_numpy(deq))
+        if scope in q:
+            raise UnsupportedCheckpoint(f"two quantized MatMuls map to {scope!r} (export layout differs from what this reader expects)")
+        q[scope] = (torch.from_numpy(wq), sw, zw)
+        chain.update((id(n), id(dql), id(cast[0])))
+    return chain
 
 
 def derive_config(sd) -> ZipformerConfig:
@@ -157,3 +240,20 @@ def read_k2_onnx(encoder_path, decoder_path, joiner_path):
     cfg = derive_config(sd)
     self_check(cfg, sd)
     return cfg, sd
+
+
+def read_k2_onnx_quantized(encoder_path, decoder_path, joiner_path):
+    """the "int8" / "int8-fp32" files (module docstring) -> (ZipformerConfig, state dict, q): the state dict holds the dequantized
+    float32 weights (Wq - zw) sw of the quantized Linears, so `derive_config` and `self_check` run unchanged; q maps every quantized
+    Linear (icefall name) to (Wq int8 [out][in], sw, zw).  Refused with "quantized" in the message: MatMulInteger with a
+    non-constant B, a per-channel scale or zero point, a chain without its scale Mul, QLinearMatMul / ConvInteger /
+    DequantizeLinear, and a quantized decoder_proj / output_linear (a deliberate limit: the export is expected to leave them
+    float32 Gemm nodes).  UNVERIFIED against a real export, like `read_k2_onnx`."""
+    sd, seen, q = {}, {}, {}
+    for path in (encoder_path, decoder_path, joiner_path):
+        _collect(onnx_lite.load(path), sd, seen, q)
+    cfg = derive_config(sd)
+    self_check(cfg, sd)
+    if not q:
+        raise UnsupportedCheckpoint("no quantized (int8) MatMul found: these are float32 files (read them with precision='fp32')")
+    return cfg, sd, q

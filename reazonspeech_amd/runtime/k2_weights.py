@@ -177,7 +177,50 @@ def pad_cols(w: torch.Tensor, mult: int = 64) -> torch.Tensor:
     return out
 
 
-def prepare_weights_k2(cfg: ZipformerConfig, sd: Dict[str, torch.Tensor], pos_cap: int = K2_POS_CAP, f32: bool = False):
+def quantized_linears_k2(cfg: ZipformerConfig):
+    """-> {icefall Linear name: device tensor name} of every Linear the int8 ONNX files quantize.  [UPSTREAM] quantize_dynamic
+    rewrites the MatMuls whose B operand is a constant: every Linear applied to a 3-D tensor — in the encoder file encoder_embed.out,
+    all Linears of the encoder layers, self_attn_weights.linear_pos (on the position rows) and encoder_proj.  decoder_proj and
+    output_linear export as Gemm (OnnxDecoder / OnnxJoiner squeeze to 2-D) and stay float32."""
+    out = {"encoder_embed.out": "emb.out.w", "joiner.encoder_proj": "joint.enc.w"}
+    for s in range(cfg.n_stacks):
+        for j in range(cfg.num_layers[s]):
+            L, p = layer_prefix(cfg, s, j), f"S{s}.L{j}."
+            out[L + "self_attn_weights.in_proj"] = p + "attw.in.w"
+            out[L + "self_attn_weights.linear_pos"] = p + "attw.pos.w"
+            for a, q in (("self_attn1", "sa1"), ("self_attn2", "sa2"), ("feed_forward1", "ff1"), ("feed_forward2", "ff2"),
+                         ("feed_forward3", "ff3"), ("nonlin_attention", "na"), ("conv_module1", "cm1"), ("conv_module2", "cm2")):
+                out[L + a + ".in_proj"] = p + q + ".in.w"
+                out[L + a + ".out_proj"] = p + q + ".out.w"
+    return out
+
+
+def quantize_weight_qint8(w: torch.Tensor):
+    """[UPSTREAM] onnxruntime quantize_dynamic, weight_type QInt8 (its default: symmetric, per tensor, range [-127, 127]):
+    sw = max|W| / 127 in float32 (1 for an all-zero W), Wq = clip(round_half_even(W / sw), -127, 127), zero point 0.
+    -> (Wq int8 tensor of W's shape, sw float, zw int)"""
+    a = w.detach().to(torch.float32).numpy()
+    amax = np.float32(np.abs(a).max()) if a.size else np.float32(0)
+    sw = np.float32(amax / np.float32(127.0)) if amax > 0 else np.float32(1.0)
+    q = np.clip(np.rint(a / sw), -127, 127).astype(np.int8)
+    return torch.from_numpy(q), float(sw), 0
+
+
+def quantize_k2_linears(cfg: ZipformerConfig, sd: Dict[str, torch.Tensor]):
+    """ORT's QInt8 recipe applied to the float weights of every quantized Linear (`quantized_linears_k2`): synthetic and benchmark
+    runs of the int8 mode, and the test writer of int8 files.  -> {icefall Linear name: (Wq int8 [out][in], sw, zw)}"""
+    return {name: quantize_weight_qint8(sd[name + ".weight"]) for name in quantized_linears_k2(cfg)}
+
+
+def dequantize_k2_linears(sd: Dict[str, torch.Tensor], q):
+    """the state dict with every quantized Linear's weight replaced by (Wq - zw) sw in float32: what the int8 files hold"""
+    out = dict(sd)
+    for name, (wq, sw, zw) in q.items():
+        out[name + ".weight"] = (wq.to(torch.float32) - float(zw)) * torch.tensor(sw, dtype=torch.float32)
+    return out
+
+
+def prepare_weights_k2(cfg: ZipformerConfig, sd: Dict[str, torch.Tensor], pos_cap: int = K2_POS_CAP, f32: bool = False, i8=None):
     """-> dict name -> CPU tensor as registered with rs_k2_set_tensor (include/rs_asr.h).  One-off host transforms:
       * GEMM weights bf16 [N][K] with K zero-padded to a multiple of 64 where the model's extent is not one (attention values
         H * 12, the 3/4-width non-linear attention of a 192-wide stack, the 3x3x32 patches of encoder_embed's third conv);
@@ -188,7 +231,11 @@ def prepare_weights_k2(cfg: ZipformerConfig, sd: Dict[str, torch.Tensor], pos_ca
         (float32 [2 * cap - 1][H * 4]) — the encoding depends on the relative position only;
       * decoder / joiner: float32, the joiner's two matrices fragment-major for the exact-f32 decode kernels;
       * f32 = True adds the float32 parity mode's dense weights as "<name>.f32" (unrounded; K zero-padded to a multiple of 32
-        where the bf16 copy pads to 64; the conv modules' in_proj and its bias in icefall's own row order: values, then gates)."""
+        where the bf16 copy pads to 64; the conv modules' in_proj and its bias in icefall's own row order: values, then gates);
+      * i8 = {icefall Linear name: (Wq int8 [out][in], sw, zw)} (read_k2_onnx_quantized / quantize_k2_linears) adds the int8 mode's
+        weights: "<name>.i8" int8 in the layout of "<name>.f32" (K zero-padded to a multiple of 32, encoder_embed.out's columns
+        permuted, the conv modules' in_proj in icefall's row order), "<name>.i8.cs" int32 column sums over the real K and
+        "<name>.i8.q" f32 (sw, zw, 0, 0); a quantized linear_pos also registers "pos.enc", the encoding rows it projects."""
     cfg.validate()
     out, used = {}, set()
     bf = lambda t: t.detach().to(torch.float32).to(torch.bfloat16).contiguous()   # noqa: E731
@@ -305,6 +352,22 @@ def prepare_weights_k2(cfg: ZipformerConfig, sd: Dict[str, torch.Tensor], pos_ca
                     out[p + q + ".in.w.f32"] = f32_(sd[L + cm + ".in_proj.weight"])
                     out[p + q + ".in.b.f32"] = f32_(sd[L + cm + ".in_proj.bias"])
                     out[p + q + ".out.w.f32"] = f32_(sd[L + cm + ".out_proj.weight"])
+    if i8:
+        names = quantized_linears_k2(cfg)
+        for key, (wq, sw, zw) in i8.items():
+            if key not in names:
+                raise UnsupportedCheckpoint(f"quantized weight {key!r} has no int8 counterpart in this implementation")
+            if tuple(wq.shape) != tuple(sd[key + ".weight"].shape) or wq.dtype != torch.int8:
+                raise UnsupportedCheckpoint(f"quantized weight {key!r}: int8 {tuple(sd[key + '.weight'].shape)} expected, got {wq.dtype} {tuple(wq.shape)}")
+            dev = names[key]
+            w = wq
+            if key == "encoder_embed.out":
+                w = w.reshape(d0, c3, F).permute(0, 2, 1).reshape(d0, F * c3)
+            out[dev + ".i8"] = pad_cols(w.contiguous(), 32)
+            out[dev + ".i8.cs"] = w.to(torch.int64).sum(dim=1).to(torch.int32).contiguous()
+            out[dev + ".i8.q"] = torch.tensor([sw, float(zw), 0.0, 0.0], dtype=torch.float32)
+            if dev.endswith("attw.pos.w"):
+                out["pos.enc"] = pe.contiguous()
     left = [k for k in sd if k not in used]
     if left:
         raise UnsupportedCheckpoint(f"{len(left)} checkpoint tensor(s) have no counterpart in this implementation: "

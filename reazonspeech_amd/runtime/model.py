@@ -130,13 +130,19 @@ class _BufView:
 
 class AsrModel:
     def __init__(self, cfg: ModelConfig, state_dict, tokenizer, device="cuda", pos_cap: int = DEFAULT_POS_CAP,
-                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None):
+                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None):
         """precision: "bf16" = the throughput mode (bf16 GEMM operands, float32 accumulation and residual stream);
         "fp32" = the parity mode: float32 weights, activations and arithmetic end to end, what the reference computes
         (pkg/nemo-asr/src/transcribe.py:26-28, :48-53) — about 20x slower, 2.4 GB more weights."""
         cfg.validate()
-        if precision not in ("bf16", "fp32", "fp32x3"):
-            raise ValueError(f"precision must be 'bf16', 'fp32' or 'fp32x3', not {precision!r}")
+        if precision not in ("bf16", "fp32", "fp32x3", "int8"):
+            raise ValueError(f"precision must be 'bf16', 'fp32', 'fp32x3' or 'int8', not {precision!r}")
+        # "int8" (the Zipformer family): onnxruntime's int8 graph restated — the float32 mode with every quantized Linear of
+        # `qweights` ({icefall name: (Wq int8, sw, zw)}) as a dynamically quantized MatMul on the int8 matrix cores (csrc/k_int8.hip)
+        self.i8 = precision == "int8"
+        if self.i8 and (getattr(cfg, "family", "") != "k2" or not qweights):
+            raise ValueError("precision 'int8' needs a Zipformer (k2) configuration and its quantized weights (qweights)")
+        precision = "fp32" if self.i8 else precision
         # "fp32x3": the float32 mode (float32 weights, activations, accumulation, IEEE exp / divide) with every float32 PRODUCT of its
         # GEMMs formed from three bf16 matrix-core terms (csrc/k_f32.hip X3: hi / lo split, 16 mantissa bits per operand) — 2x the
         # float32 mode's speed; not an IEEE chain, but held to the same 256-row goldens (ids identical on every row of all three)
@@ -166,7 +172,8 @@ class AsrModel:
             if getattr(cfg, "family", "") == "k2":
                 from .k2_weights import prepare_weights_k2
                 self._k2_sd = state_dict          # the position tables are re-projected when a longer utterance arrives
-                self._upload_k2(prepare_weights_k2(cfg, state_dict, pos_cap, f32=precision == "fp32"))
+                self._k2_q = qweights if self.i8 else None
+                self._upload_k2(prepare_weights_k2(cfg, state_dict, pos_cap, f32=precision == "fp32", i8=self._k2_q))
                 self.pos_cap = pos_cap
             elif cfg.espnet:
                 from .weights_espnet import prepare_weights_espnet
@@ -176,6 +183,8 @@ class AsrModel:
             if precision == "fp32":
                 self.ctx.set_option("precision_f32", 1)
                 self.ctx.set_option("gemm_f32_x3", 1 if self.x3 else 0)
+            if self.i8:
+                self.ctx.set_option("precision_i8", 1)
 
     # ------------------------------------------------------------------------------------------
     def _upload(self, tensors):
@@ -196,6 +205,8 @@ class AsrModel:
             if self.precision == "fp32":
                 c.set_option("precision_f32", 1)
                 c.set_option("gemm_f32_x3", 1 if self.x3 else 0)
+            if getattr(self, "i8", False):
+                c.set_option("precision_i8", 1)
 
     def _contexts(self):
         return [self.ctx] + [c for c, _ in self._dec_lanes]
@@ -236,8 +247,8 @@ class AsrModel:
             cap = 1 << (need - 1).bit_length()
             torch.cuda.synchronize(self.device)
             with torch.cuda.device(self.device):
-                tensors = prepare_weights_k2(self.cfg, self._k2_sd, cap)
-                self._upload_k2({k: v for k, v in tensors.items() if k.endswith("attw.pos_proj")})
+                tensors = prepare_weights_k2(self.cfg, self._k2_sd, cap, i8=self._k2_q)
+                self._upload_k2({k: v for k, v in tensors.items() if k.endswith("attw.pos_proj") or k == "pos.enc"})
             self.pos_cap = cap
             return
         if tp <= self.pos_cap:

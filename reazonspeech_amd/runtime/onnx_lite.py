@@ -171,7 +171,8 @@ def dump(path, model: Model):
     g += _ld(2, b"main_graph")
     for name, arr in model.initializers.items():
         arr = np.ascontiguousarray(arr)
-        dt = {np.dtype(np.float32): FLOAT, np.dtype(np.int64): INT64, np.dtype(np.int32): INT32}[arr.dtype]
+        dt = {np.dtype(np.float32): FLOAT, np.dtype(np.int64): INT64, np.dtype(np.int32): INT32, np.dtype(np.int8): INT8,
+              np.dtype(np.uint8): UINT8}[arr.dtype]
         body = b"".join(_vi(1, int(d)) for d in arr.shape) + _vi(2, dt) + _ld(8, name.encode()) + _ld(9, arr.tobytes())
         g += _ld(5, body)
     out = _vi(1, 8) + _ld(7, bytes(g))
