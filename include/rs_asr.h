@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 6
+#define RS_ABI_VERSION 7
 
 enum {
     RS_OK = 0,
@@ -382,6 +382,38 @@ size_t rs_rnnt_beam_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_m
 int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags,
                  int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- sherpa-onnx's modified_beam_search (Zipformer family) ---------------------------------------
+ * replaces: the search inside sherpa_onnx.OfflineRecognizer.from_transducer(..., decoding_method="modified_beam_search",
+ * max_active_paths=K) — the second offline transducer method of the constructor the reference builds its recognizer with
+ * (pkg/k2-asr/src/huggingface.py:73-83 passes "greedy_search" = rs_rnnt_greedy) — as model.decode_stream(stream) runs it
+ * (pkg/k2-asr/src/transcribe.py:39).  [UPSTREAM, not vendored] OfflineTransducerModifiedBeamSearchDecoder::Decode without LM /
+ * hotwords, Hypotheses::Add, GetMostProbable(length_norm):
+ *   per utterance one starting hypothesis, ys = [-1, blank] (context_size = 2), log_prob = 0.  For every frame t < enc_lens[b]
+ *   with the H <= K live hypotheses: logits[h] = output_linear(tanh(f[b][t] + decoder_proj(decoder(last 2 tokens of h))));
+ *   logits[h][blank] -= blank_penalty; lp[h][v] = log_softmax(logits[h])[v] + log_prob[h]; the K largest of the H x V values
+ *   (flat index h V + v) are taken in descending order: hypothesis h is copied, v is appended to ys and t to the timestamps
+ *   unless v is the blank or <unk>, log_prob = lp[h][v]; a hypothesis whose ys equals one already in the new set (length and
+ *   every token) is merged into it — log_prob = logaddexp(old, new), the tokens / timestamps of the one added first stay.
+ *   Result: the hypothesis with the largest log_prob / len(ys) (len counts the 2 context entries).
+ * Tie rules (upstream leaves them to a partial sort and an unordered map): equal values -> the lower flat index first;
+ * equal final scores -> the hypothesis that entered the last set first.  All arithmetic is float32 in one order (upstream keeps
+ * log_prob in double), stated in csrc/k_rnnt_mbs.hip and restated by tests/k2_mbs_checker.c, which the results equal bit for bit.
+ *
+ *   max_active_paths  K, 1..8 (1 = the greedy search's ids and frames)
+ *   blank_penalty     >= 0, subtracted from the blank logit before the log-softmax
+ *   flags             RS_MBS_LENGTH_NORM: the winner is the best log_prob / len(ys) (sherpa-onnx's default), else the best log_prob
+ *   ids / frames i32[B][out_cap]  tokens of the winner (without the context) and the encoder frame of each
+ *   n_ids i32[B],  scores f32[B]  log_prob of the winner, not normalised
+ * Workspace: rs_rnnt_mbs_workspace_bytes(ctx, B, max_active_paths, tp_max, out_cap), separate from rs_workspace_bytes (0 for
+ * invalid arguments).  The whole search is enqueued without a host round trip and the stream is synchronised once at the end.
+ * RS_EOVERFLOW if a result has more than out_cap tokens; RS_EINVAL for a context without the stateless decoder (the search is
+ * defined for the Zipformer family), max_active_paths outside 1..8 or a negative penalty. */
+enum { RS_MBS_LENGTH_NORM = 1 };
+size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap);
+int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- profiling hooks for bench.py (roofline.achieved) ------------------------------------
  * When enabled, the launcher brackets every launch of the selected kernel class with HIP

@@ -28,34 +28,6 @@ namespace {
 constexpr int MAX_BEAM = 8;
 constexpr int MAX_CAND = MAX_BEAM * (MAX_BEAM + 1);
 
-// natural log, mirrored operation for operation in oracle/rnnt_math.h
-__device__ __forceinline__ float rs_logf(float x) {
-    unsigned u = __float_as_uint(x);
-    int e = (int)(u >> 23) - 127;
-    float m = __uint_as_float((u & 0x007fffffu) | 0x3f800000u);
-    if (m > 1.41421356f) { m = m * 0.5f; e += 1; }
-    const float fe = (float)e;
-    const float r = m - 1.0f;
-    const float z = r * r;
-    float p = 7.0376836292e-2f;
-    p = fmaf(p, r, -1.1514610310e-1f);
-    p = fmaf(p, r, 1.1676998740e-1f);
-    p = fmaf(p, r, -1.2420140846e-1f);
-    p = fmaf(p, r, 1.4249322787e-1f);
-    p = fmaf(p, r, -1.6668057665e-1f);
-    p = fmaf(p, r, 2.0000714765e-1f);
-    p = fmaf(p, r, -2.4999993993e-1f);
-    p = fmaf(p, r, 3.3333331174e-1f);
-    float y = (p * r) * z;
-    y = fmaf(fe, -2.12194440e-4f, y);
-    y = fmaf(z, -0.5f, y);
-    return fmaf(fe, 0.693359375f, r + y);
-}
-__device__ __forceinline__ float rs_logaddexpf(float a, float b) {
-    const float hi = a >= b ? a : b, lo = a >= b ? b : a;
-    return hi + rs_logf(1.0f + rs_expf(lo - hi));
-}
-
 struct AlsdState {
     // per hypothesis row; [2] = ping-pong: step i reads set (i & 1) and writes set ((i + 1) & 1)
     int32_t* len[2];     // [rows] labels emitted

@@ -1,4 +1,5 @@
-// k_rnnt_common.h — pieces shared by the decode translation units (k_rnnt.hip: greedy, k_rnnt_alsd.hip: beam search).
+// k_rnnt_common.h — pieces shared by the decode translation units (k_rnnt.hip: greedy, k_rnnt_alsd.hip / k_rnnt_beam.hip /
+// k_rnnt_mbs.hip: the beam searches).
 // Both are compiled with -ffp-contract=off.
 #pragma once
 #include "rs_common.h"
@@ -27,6 +28,34 @@ __device__ __forceinline__ float rs_expf(float x) {
 }
 __device__ __forceinline__ float rs_sigmoidf(float x) { return 1.0f / (1.0f + rs_expf(-x)); }
 __device__ __forceinline__ float rs_tanhf(float x) { return 1.0f - 2.0f / (rs_expf(2.0f * x) + 1.0f); }
+
+// natural log and log(exp(a) + exp(b)), mirrored operation for operation in oracle/rnnt_math.h (the beam searches)
+__device__ __forceinline__ float rs_logf(float x) {
+    unsigned u = __float_as_uint(x);
+    int e = (int)(u >> 23) - 127;
+    float m = __uint_as_float((u & 0x007fffffu) | 0x3f800000u);
+    if (m > 1.41421356f) { m = m * 0.5f; e += 1; }
+    const float fe = (float)e;
+    const float r = m - 1.0f;
+    const float z = r * r;
+    float p = 7.0376836292e-2f;
+    p = fmaf(p, r, -1.1514610310e-1f);
+    p = fmaf(p, r, 1.1676998740e-1f);
+    p = fmaf(p, r, -1.2420140846e-1f);
+    p = fmaf(p, r, 1.4249322787e-1f);
+    p = fmaf(p, r, -1.6668057665e-1f);
+    p = fmaf(p, r, 2.0000714765e-1f);
+    p = fmaf(p, r, -2.4999993993e-1f);
+    p = fmaf(p, r, 3.3333331174e-1f);
+    float y = (p * r) * z;
+    y = fmaf(fe, -2.12194440e-4f, y);
+    y = fmaf(z, -0.5f, y);
+    return fmaf(fe, 0.693359375f, r + y);
+}
+__device__ __forceinline__ float rs_logaddexpf(float a, float b) {
+    const float hi = a >= b ? a : b, lo = a >= b ? b : a;
+    return hi + rs_logf(1.0f + rs_expf(lo - hi));
+}
 
 // Activation rows are gathered by index, so a lane-per-row load (what the MFMA A operand wants:
 // lane = row + 16*kk) would be 64 separate 16-byte requests per instruction and the texture

@@ -1,0 +1,435 @@
+// k_rnnt_mbs.hip — sherpa-onnx's modified_beam_search for the Zipformer family (stateless decoder + tanh joiner), the second
+// decoding method of sherpa_onnx.OfflineRecognizer.from_transducer, which K2Model stands for (reference call site:
+// pkg/k2-asr/src/huggingface.py:73-83; the reference passes greedy_search, `decoding_method="modified_beam_search"` with
+// `max_active_paths` is the constructor's other offline transducer method).
+//
+// [UPSTREAM, not vendored, PARITY UNPINNED like the greedy search] OfflineTransducerModifiedBeamSearchDecoder::Decode without
+// LM / hotwords, Hypotheses::Add, GetMostProbable(length_norm = true).  The algorithm, as built here:
+//   * per utterance one starting hypothesis ys = [-1, blank] (context_size = 2 entries), log_prob = 0, no timestamps;
+//   * for every encoder frame t < enc_lens[b], with H <= K live hypotheses (K = max_active_paths):
+//       1. dec[h] = decoder_proj(decoder(last two tokens of h))                   (k2_decoder_kernel + rnnt_pred16_kernel)
+//       2. logits[h][:] = output_linear(tanh(f[b][t] + dec[h])); blank_penalty > 0: logits[h][blank] -= blank_penalty
+//       3. lp[h][v] = ((logits[h][v] - max_h) - log(sum_h)) + log_prob[h]
+//       4. the K largest of the H x V values, flat index c = h V + v;  EQUAL VALUES: THE LOWER FLAT INDEX FIRST
+//       5. in that order: copy hypothesis h; v neither blank nor <unk>: append v to ys and t to the timestamps;
+//          log_prob = lp[h][v]; add to the new set — a hypothesis whose ys equals one already in the set (compared in full:
+//          length and every token) is merged into it: log_prob = logaddexp(old, new), the tokens / timestamps of the one
+//          added FIRST stay;
+//   * result: the hypothesis with the largest log_prob / len(ys) (len counts the 2 context entries; without
+//     RS_MBS_LENGTH_NORM the largest log_prob);  EQUAL FINAL SCORES: THE HYPOTHESIS THAT ENTERED THE LAST SET FIRST.
+// Upstream leaves both orders in capitals open (a partial sort, an unordered map) and keeps log_prob in double; here every
+// number is float32 in one order, restated by tests/k2_mbs_checker.c, which the results equal bit for bit:
+//   log-softmax of a row: thread i of 256 owns the columns v = i + 256 q.  max: any order (exact).  sum: s_i = the chain over
+//   q ascending of s = s + rs_expf(x - max), from 0; inside each wave of 64 the butterfly s_l = s_l + s_(l xor off) for
+//   off = 32, 16, 8, 4, 2, 1 (every lane ends with the same bits), then ((w0 + w1) + w2) + w3 over the four waves.
+//   merge: rs_logaddexpf(old, new) of k_rnnt_common.h.  final score: log_prob / (float)len(ys).
+//
+// The batch advances in lock step over the frames; hypothesis rows are r = utterance * K + slot.  One frame = 5 launches,
+// none of them waits for the host (the whole search is enqueued once, one synchronisation at the end):
+//   mbs_act_kernel      a_pre[r] = tanh(f[b][t] + g[dec[r]]) for the live rows (a blank extension keeps its parent's decoder
+//                       row by index: K decoder rows per utterance, a label extension takes a free one)
+//   rnnt_tile_kernel<4> exact f32 joint logits [rows][V] on v_mfma_f32_16x16x4_f32 -> zbuf (k_rnnt.hip, same K-slice order as
+//                       rs_oracle_joint_argmax)
+//   mbs_select_kernel   a workgroup per utterance: steps 3 - 5 and, at the utterance's last frame, the result
+//   k2_decoder_kernel + rnnt_pred16_kernel over the decoder rows that took a label
+// Utterances past their length are on no list and their workgroups return at once.
+// Compiled with -ffp-contract=off.
+#include "k_rnnt_common.h"
+
+int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
+int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
+                                         int rows_per_utt, int step, hipStream_t s);
+
+namespace {
+
+constexpr int MBS_MAX_K = 8;      // max_active_paths
+constexpr int MBS_THREADS = 256;  // of the selection kernel: 4 waves
+constexpr int MBS_CONTEXT = 2;    // context_size of the stateless decoder (k2_decoder_kernel reads two tokens)
+
+struct MbsState {
+    // hypothesis records, [2] = ping-pong: frame t reads set (t & 1) and writes set ((t + 1) & 1)
+    int32_t* len[2];     // [rows] tokens after the context
+    float* score[2];     // [rows] log_prob
+    int32_t* last0[2];   // [rows] token before last (context included)
+    int32_t* last1[2];   // [rows] last token
+    int32_t* dec[2];     // [rows] decoder row of the hypothesis, 0..K-1 inside its utterance
+    int32_t* y[2];       // [rows][cap] tokens
+    int32_t* fr[2];      // [rows][cap] frame of each token
+    int32_t* n_hyp[2];   // [B]
+    int cap;
+};
+
+__global__ void mbs_init_kernel(DecodeState st, MbsState ms, const int32_t* __restrict__ enc_lens, int B, int K, int blank,
+                                int32_t* __restrict__ n_ids, float* __restrict__ scores) {
+    // single workgroup: the starting hypothesis of every utterance, its decoder row and the first work lists
+    __shared__ int n_alive_s;
+    if (threadIdx.x == 0) n_alive_s = 0;
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const int row = b * K;
+        ms.len[0][row] = 0; ms.score[0][row] = 0.0f; ms.last0[0][row] = -1; ms.last1[0][row] = blank; ms.dec[0][row] = 0;
+        ms.n_hyp[0][b] = 1;
+        st.token2[row] = -1; st.token[row] = blank; st.act[b] = row;
+        n_ids[b] = 0; scores[b] = 0.0f;                  // the result of an utterance without frames
+        if (enc_lens[b] > 0) st.alive[atomicAdd(&n_alive_s, 1)] = row;
+    }
+    __syncthreads();
+    // counters: [0] decoder rows to compute, [1] overflow flag, [2],[3] live rows of list 0 / 1
+    if (threadIdx.x == 0) { st.counters[0] = B; st.counters[1] = 0; st.counters[2] = n_alive_s; st.counters[3] = 0; }
+}
+
+// a_pre[row] = act(f[utt][t] + g[utt * K + dec[row]]) for the rows of list (t & 1); one thread per 4 elements
+__global__ __launch_bounds__(256) void mbs_act_kernel(DecodeState st, MbsState ms, const float* __restrict__ f, float* __restrict__ a_pre,
+                                                      int rows, int Tp, int J, int K, int t) {
+    const int list = t & 1;
+    const int n = st.counters[2 + list];
+    const int q4 = J / 4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)n * q4; i += (long long)gridDim.x * 256) {
+        const int idx = (int)(i / q4), q = (int)(i - (long long)idx * q4);
+        const int row = st.alive[(size_t)list * rows + idx];
+        const int utt = row / K;
+        const int drow = utt * K + ms.dec[list][row];
+        const float4 a = reinterpret_cast<const float4*>(f + ((size_t)utt * Tp + t) * J)[q];
+        const float4 g = reinterpret_cast<const float4*>(st.g + (size_t)drow * J)[q];
+        float4 r;
+        if (st.joint_act) { r.x = rs_tanhf(a.x + g.x); r.y = rs_tanhf(a.y + g.y); r.z = rs_tanhf(a.z + g.z); r.w = rs_tanhf(a.w + g.w); }
+        else { r.x = fmaxf(a.x + g.x, 0.0f); r.y = fmaxf(a.y + g.y, 0.0f); r.z = fmaxf(a.z + g.z, 0.0f); r.w = fmaxf(a.w + g.w, 0.0f); }
+        reinterpret_cast<float4*>(a_pre + (size_t)row * J)[q] = r;
+    }
+}
+
+// (value desc, flat index asc): does (oz, ov) come before (bz, bv)?  An index < 0 is an empty entry.
+__device__ __forceinline__ bool mbs_before(float oz, int ov, float bz, int bv) {
+    return ov >= 0 && (bv < 0 || oz > bz || (oz == bz && ov < bv));
+}
+
+// NVR > 0: V <= 256 NVR and a hypothesis's logits row is read ONCE into NVR registers per thread, every load in flight before the
+// first comparison; maximum, exp-sum and the running top-K then walk the registers.  NVR = 0: any V, three passes over memory,
+// the same arithmetic in the same order.
+template <int NVR>
+__global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
+    DecodeState st, MbsState ms, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int rows, int K,
+    int V, int blank, int unk, int t, float blank_penalty, int length_norm, int out_cap, int32_t* __restrict__ ids,
+    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores) {
+    const int b = blockIdx.x;
+    const int T = enc_lens[b];
+    if (t >= T) return;                                   // skipped, not masked
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = t & 1, pn = p ^ 1;
+    const int H = ms.n_hyp[p][b];
+    const int cap = ms.cap;
+
+    __shared__ float s_max[MBS_MAX_K][4], s_sum[MBS_MAX_K][4];
+    __shared__ float s_cz[MBS_MAX_K][4];
+    __shared__ int s_cv[MBS_MAX_K][4];
+    __shared__ float s_val[MBS_MAX_K];                    // the K best (value, flat index), descending
+    __shared__ int s_idx[MBS_MAX_K];
+    __shared__ int s_prow[MBS_MAX_K], s_tok[MBS_MAX_K], s_dec[MBS_MAX_K];   // the new set, in the order of entry
+    __shared__ float s_score[MBS_MAX_K];
+    __shared__ int s_nnew;
+
+    // ---- steps 3 + 4a: every thread's K best of its own columns over all H rows (sorted: value desc, flat index asc; a thread
+    // meets its flat indices in ascending order, so a later equal value never displaces an earlier one) ----
+    float tz[MBS_MAX_K];
+    int tv[MBS_MAX_K];
+#pragma unroll
+    for (int k = 0; k < MBS_MAX_K; ++k) { tz[k] = -INFINITY; tv[k] = -1; }
+    float thr = -INFINITY;                                // value of the thread's K-th entry once its list is full
+    bool full = false;
+    for (int h = 0; h < H; ++h) {
+        const int row = b * K + h;
+        const float* zr = zbuf + (size_t)row * zstride;
+        const float hs = ms.score[p][row];
+        auto logit = [&](int v) {
+            float x = zr[v];
+            if (v == blank && blank_penalty > 0.0f) x = x - blank_penalty;
+            return x;
+        };
+        float zreg[NVR > 0 ? NVR : 1];
+        float m = -INFINITY;
+        if constexpr (NVR > 0) {
+#pragma unroll
+            for (int q = 0; q < NVR; ++q) {
+                const int v = tid + MBS_THREADS * q;
+                zreg[q] = zr[v < V ? v : V - 1];
+            }
+#pragma unroll
+            for (int q = 0; q < NVR; ++q) {
+                const int v = tid + MBS_THREADS * q;
+                if (v == blank && blank_penalty > 0.0f) zreg[q] = zreg[q] - blank_penalty;
+                if (v < V && zreg[q] > m) m = zreg[q];
+            }
+        } else {
+            for (int v = tid; v < V; v += MBS_THREADS) { const float x = logit(v); if (x > m) m = x; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const float o = __shfl_xor(m, off, 64); if (o > m) m = o; }
+        if (lane == 0) s_max[h][wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(s_max[h][0], s_max[h][1]), fmaxf(s_max[h][2], s_max[h][3]));
+        float sum = 0.0f;
+        if constexpr (NVR > 0) {
+#pragma unroll
+            for (int q = 0; q < NVR; ++q)
+                if (tid + MBS_THREADS * q < V) sum = sum + rs_expf(zreg[q] - m);
+        } else {
+            for (int v = tid; v < V; v += MBS_THREADS) sum = sum + rs_expf(logit(v) - m);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum = sum + __shfl_xor(sum, off, 64);
+        if (lane == 0) s_sum[h][wave] = sum;
+        __syncthreads();
+        const float lg = rs_logf(((s_sum[h][0] + s_sum[h][1]) + s_sum[h][2]) + s_sum[h][3]);
+        auto offer = [&](int v, float x) {
+            const float lp = ((x - m) - lg) + hs;
+            if (full && !(lp > thr)) return;
+            float cz = lp;
+            int cv = h * V + v;
+            bool ins = false;                             // once placed, everything behind shifts down one slot
+#pragma unroll
+            for (int k = 0; k < MBS_MAX_K; ++k) {
+                if (k < K && (ins || tv[k] < 0 || cz > tz[k])) {
+                    const float sz = tz[k]; const int sv = tv[k];
+                    tz[k] = cz; tv[k] = cv;
+                    cz = sz; cv = sv;
+                    ins = true;
+                }
+                if (k == K - 1) { thr = tz[k]; full = tv[k] >= 0; }
+            }
+        };
+        if constexpr (NVR > 0) {
+#pragma unroll
+            for (int q = 0; q < NVR; ++q) {
+                const int v = tid + MBS_THREADS * q;
+                if (v < V) offer(v, zreg[q]);
+            }
+        } else {
+            for (int v = tid; v < V; v += MBS_THREADS) offer(v, logit(v));
+        }
+    }
+
+    // ---- step 4b: the K best of the workgroup: K rounds, each pops the best list head (wave butterfly, then the 4 waves) ----
+    int n_cand = K;
+    for (int j = 0; j < K; ++j) {
+        float bz = tz[0];
+        int bv = tv[0];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float oz = __shfl_xor(bz, off, 64);
+            const int ov = __shfl_xor(bv, off, 64);
+            if (mbs_before(oz, ov, bz, bv)) { bz = oz; bv = ov; }
+        }
+        if (lane == 0) { s_cz[j][wave] = bz; s_cv[j][wave] = bv; }
+        __syncthreads();
+        bz = s_cz[j][0]; bv = s_cv[j][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (mbs_before(s_cz[j][w], s_cv[j][w], bz, bv)) { bz = s_cz[j][w]; bv = s_cv[j][w]; }
+        if (bv < 0) { n_cand = j; break; }                // fewer than K values exist (H V < K); uniform over the workgroup
+        if (tid == 0) { s_val[j] = bz; s_idx[j] = bv; }
+        if (tv[0] == bv) {                                // the owner pops its head
+#pragma unroll
+            for (int k = 0; k + 1 < MBS_MAX_K; ++k) { tz[k] = tz[k + 1]; tv[k] = tv[k + 1]; }
+            tz[MBS_MAX_K - 1] = -INFINITY; tv[MBS_MAX_K - 1] = -1;
+        }
+    }
+    __syncthreads();
+
+    // ---- step 5 (wave 0, every lane computes the same values): expansion, merging, decoder rows, the result ----
+    if (wave == 0) {
+        int cprow[MBS_MAX_K], ctok[MBS_MAX_K], cplen[MBS_MAX_K];
+        float csc[MBS_MAX_K];
+        const int32_t* cy[MBS_MAX_K];
+        unsigned dup = 0;
+#pragma unroll
+        for (int j = 0; j < MBS_MAX_K; ++j) {
+            cprow[j] = b * K; ctok[j] = -1; cplen[j] = 0; csc[j] = 0.0f; cy[j] = ms.y[p];
+            if (j < n_cand) {
+                const int c = s_idx[j];
+                const int h = c / V, v = c - h * V;
+                ctok[j] = (v != blank && v != unk) ? v : -1;
+                cprow[j] = b * K + h;
+                cplen[j] = ms.len[p][cprow[j]];
+                cy[j] = ms.y[p] + (size_t)cprow[j] * cap;
+                csc[j] = s_val[j];
+            }
+        }
+        // a candidate whose token sequence equals that of an earlier entry adds its probability to it
+#pragma unroll
+        for (int j = 1; j < MBS_MAX_K; ++j) {
+            if (j >= n_cand) continue;
+            bool merged = false;
+            const int n = cplen[j] + (ctok[j] >= 0 ? 1 : 0);
+#pragma unroll
+            for (int k = 0; k < j; ++k) {
+                if (merged || ((dup >> k) & 1u)) continue;
+                if (n != cplen[k] + (ctok[k] >= 0 ? 1 : 0)) continue;
+                bool differ = false;
+                for (int q = lane; q < n; q += 64) {
+                    const int a = q < cplen[j] ? cy[j][q] : ctok[j];
+                    const int c = q < cplen[k] ? cy[k][q] : ctok[k];
+                    differ = differ || (a != c);
+                }
+                if (__ballot(differ) != 0ull) continue;
+                csc[k] = rs_logaddexpf(csc[k], csc[j]);
+                dup |= 1u << j;
+                merged = true;
+            }
+        }
+        // decoder rows: a hypothesis that took no token keeps its parent's; the others take the free ones, lowest first
+        unsigned used = 0;
+#pragma unroll
+        for (int j = 0; j < MBS_MAX_K; ++j)
+            if (j < n_cand && !((dup >> j) & 1u) && ctok[j] < 0) used |= 1u << ms.dec[p][cprow[j]];
+        int nk = 0;
+        int win = -1, win_n = 0;
+        float win_norm = 0.0f, win_score = 0.0f;
+#pragma unroll
+        for (int j = 0; j < MBS_MAX_K; ++j) {
+            if (j >= n_cand || ((dup >> j) & 1u)) continue;
+            int d;
+            if (ctok[j] < 0) d = ms.dec[p][cprow[j]];
+            else { d = __ffs((int)~used) - 1; used |= 1u << d; }
+            if (lane == 0) { s_prow[nk] = cprow[j]; s_tok[nk] = ctok[j]; s_score[nk] = csc[j]; s_dec[nk] = d; }
+            const int n = cplen[j] + (ctok[j] >= 0 ? 1 : 0);
+            const float norm = length_norm ? csc[j] / (float)(n + MBS_CONTEXT) : csc[j];
+            if (win < 0 || norm > win_norm) { win = j; win_n = n; win_norm = norm; win_score = csc[j]; }
+            ++nk;
+        }
+        if (lane == 0) { s_nnew = nk; ms.n_hyp[pn][b] = nk; }
+        if (t == T - 1 && win >= 0) {                     // the utterance's last frame: the result
+            int wprow = 0, wtok = -1, wplen = 0;
+#pragma unroll
+            for (int j = 0; j < MBS_MAX_K; ++j) if (j == win) { wprow = cprow[j]; wtok = ctok[j]; wplen = cplen[j]; }
+            int n = win_n;
+            if (n > out_cap) { n = out_cap; if (lane == 0) st.counters[1] = 1; }
+            const int32_t *py = ms.y[p] + (size_t)wprow * cap, *pf = ms.fr[p] + (size_t)wprow * cap;
+            for (int q = lane; q < n; q += 64) {
+                ids[(size_t)b * out_cap + q] = q < wplen ? py[q] : wtok;
+                frames[(size_t)b * out_cap + q] = q < wplen ? pf[q] : t;
+            }
+            if (lane == 0) { n_ids[b] = n; scores[b] = win_score; }
+        }
+    }
+    __syncthreads();
+    if (t + 1 >= T) return;                               // nothing reads the set after the last frame
+
+    // ---- the new set: one wave per slot copies the parent's tokens / frames (+ the token taken) and writes the record ----
+    for (int k = wave; k < s_nnew; k += 4) {
+        const int prow = s_prow[k], tok = s_tok[k], row = b * K + k;
+        const int n = ms.len[p][prow];
+        const int32_t *py = ms.y[p] + (size_t)prow * cap, *pf = ms.fr[p] + (size_t)prow * cap;
+        int32_t *ny = ms.y[pn] + (size_t)row * cap, *nf = ms.fr[pn] + (size_t)row * cap;
+        for (int q = lane; q < n; q += 64) { ny[q] = py[q]; nf[q] = pf[q]; }
+        if (lane == 0) {
+            int nn = n;
+            int l0 = ms.last0[p][prow], l1 = ms.last1[p][prow];
+            if (tok >= 0) {
+                if (n < cap) { ny[n] = tok; nf[n] = t; nn = n + 1; }     // (n <= t < cap: at most one token per frame)
+                else st.counters[1] = 1;
+                l0 = l1; l1 = tok;
+                const int drow = b * K + s_dec[k];
+                st.token2[drow] = l0; st.token[drow] = l1;
+                st.act[atomicAdd(&st.counters[0], 1)] = drow;
+            }
+            ms.len[pn][row] = nn; ms.score[pn][row] = s_score[k];
+            ms.last0[pn][row] = l0; ms.last1[pn][row] = l1; ms.dec[pn][row] = s_dec[k];
+            const int pos = atomicAdd(&st.counters[2 + pn], 1);
+            st.alive[(size_t)pn * rows + pos] = row;
+        }
+    }
+}
+
+struct MbsPlan {
+    size_t state, g, rows4, rows_cap4, b4, z, total;
+};
+
+MbsPlan mbs_plan(const rs_ctx* ctx, int B, int K, int cap) {
+    const rs_dims& d = ctx->d;
+    const size_t rows = (size_t)B * K;
+    MbsPlan p;
+    p.state = rs_align(rows * d.pred_hidden * 4);
+    p.g = rs_align(rows * d.joint_hidden * 4);
+    p.rows4 = rs_align(rows * 4);
+    p.rows_cap4 = rs_align(rows * (size_t)cap * 4);
+    p.b4 = rs_align((size_t)B * 4);
+    p.z = rs_align(rows * (size_t)((d.n_logits + 63) / 64 * 64) * 4);
+    //        h c h_tmp c_tmp   g a_pre   tcur token token2 act + 5 records x2   alive x2   y, fr x2   n_hyp x2   counters   z
+    p.total = 4 * p.state + 2 * p.g + 14 * p.rows4 + 2 * p.rows4 + 4 * p.rows_cap4 + 2 * p.b4 + rs_align(64) + p.z + 1024;
+    return p;
+}
+
+}  // namespace
+
+size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max) {
+    if (B <= 0 || K <= 0 || K > MBS_MAX_K || tp_max < 0) return 0;
+    return mbs_plan(ctx, B, K, tp_max > 0 ? tp_max : 1).total;
+}
+
+int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
+                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, void* workspace,
+                     size_t workspace_bytes, hipStream_t s) {
+    const rs_dims& d = ctx->d;
+    const int D = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
+    if (B <= 0) return RS_OK;
+    if (!ctx->k2_conv_w || d.pred_layers != 1) return rs_fail(ctx, RS_EINVAL, "modified beam search: the context has no stateless decoder");
+    if (D % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "modified beam search: decoder_dim / joiner_dim must be multiples of 128");
+    if (K < 1 || K > MBS_MAX_K) return rs_fail(ctx, RS_EINVAL, "modified beam search: max_active_paths must be 1..%d", MBS_MAX_K);
+    if ((long long)K * V > 0x7fffffffLL) return rs_fail(ctx, RS_EINVAL, "modified beam search: vocabulary too large");
+    const int cap = tp_max > 0 ? tp_max : 1;              // at most one token per frame
+    const MbsPlan pl = mbs_plan(ctx, B, K, cap);
+    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, pl.total);
+    const int rows = B * K;
+    char* w = reinterpret_cast<char*>(workspace);
+    auto take = [&](size_t bytes) { char* q = w; w += bytes; return q; };
+    DecodeState st;
+    MbsState ms;
+    st.h = (float*)take(pl.state); st.c = (float*)take(pl.state);            // (the projection kernel's state commit copies
+    st.h_tmp = (float*)take(pl.state); st.c_tmp = (float*)take(pl.state);    //  h_tmp / c_tmp there; h_tmp is the decoder output)
+    st.g = (float*)take(pl.g);
+    float* a_pre = (float*)take(pl.g);
+    st.tcur = (int32_t*)take(pl.rows4); st.token = (int32_t*)take(pl.rows4); st.token2 = (int32_t*)take(pl.rows4);
+    st.act = (int32_t*)take(pl.rows4);
+    for (int k = 0; k < 2; ++k) {
+        ms.len[k] = (int32_t*)take(pl.rows4); ms.score[k] = (float*)take(pl.rows4); ms.last0[k] = (int32_t*)take(pl.rows4);
+        ms.last1[k] = (int32_t*)take(pl.rows4); ms.dec[k] = (int32_t*)take(pl.rows4);
+    }
+    st.alive = (int32_t*)take(2 * pl.rows4);
+    for (int k = 0; k < 2; ++k) { ms.y[k] = (int32_t*)take(pl.rows_cap4); ms.fr[k] = (int32_t*)take(pl.rows_cap4); }
+    ms.n_hyp[0] = (int32_t*)take(pl.b4); ms.n_hyp[1] = (int32_t*)take(pl.b4);
+    st.counters = (int32_t*)take(rs_align(64));
+    float* zbuf = (float*)take(pl.z);
+    ms.cap = cap;
+    st.sym = nullptr; st.pmax = nullptr; st.pidx = nullptr; st.a16 = nullptr; st.anorm = nullptr;
+    st.zapprox = zbuf; st.g_off = nullptr; st.a_pre = a_pre;
+    st.joint_act = d.joint_act;
+    st.unk = rs_k2_unk_id(ctx);
+    const int zstride = (V + 63) / 64 * 64;
+
+    rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+    RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * pl.state, s));                   // h .. c_tmp are adjacent
+    hipLaunchKernelGGL(mbs_init_kernel, dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores);
+    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+    RS_CHECK_LAUNCH(ctx, "modified beam search init");
+    const int act_blocks = (int)(((long long)rows * (J / 4) + 255) / 256);
+    for (int t = 0; t < tp_max; ++t) {
+        hipLaunchKernelGGL(mbs_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, ms, joint_enc, a_pre, rows, tp_max, J, K, t);
+        if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, rows, rows, tp_max, K, t, s); rc != RS_OK) {
+            rs_prof_end(ctx, RS_PROF_DECODE, s);
+            return rc;
+        }
+#define RS_MBS_ARGS st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t, blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores
+        if (V <= MBS_THREADS * 4) hipLaunchKernelGGL((mbs_select_kernel<4>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS);
+        else if (V <= MBS_THREADS * 42) hipLaunchKernelGGL((mbs_select_kernel<42>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS);
+        else hipLaunchKernelGGL((mbs_select_kernel<0>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS);
+#undef RS_MBS_ARGS
+        if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+    }
+    RS_CHECK_LAUNCH(ctx, "modified beam search step");
+    int32_t hc[4] = {0, 0, 0, 0};
+    RS_HIP(ctx, hipMemcpyAsync(hc, st.counters, sizeof hc, hipMemcpyDeviceToHost, s));
+    RS_HIP(ctx, hipStreamSynchronize(s));
+    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "modified beam search: a result has more than out_cap=%d tokens", out_cap);
+    return RS_OK;
+}

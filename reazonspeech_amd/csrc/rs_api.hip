@@ -12,6 +12,10 @@
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B);
 size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap);
+size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max);
+int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
+                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, void* workspace,
+                     size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops);
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
                       int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
@@ -740,6 +744,31 @@ int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
     }
     return rs_rnnt_beam_impl(ctx, joint_enc, enc_lens, B, tp_max, beam, (flags & RS_BEAM_SCORE_NORM) != 0, max_pops, out_cap, ids,
                              frames, n_ids, scores, pops, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
+    if (!ctx || !ctx->k2 || B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0) return 0;
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max);
+}
+
+int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_rnnt_mbs");
+    if (!ctx->k2) return rs_fail(ctx, RS_EINVAL, "modified beam search: defined for a Zipformer context (stateless decoder) only; this context has an LSTM prediction network (rs_rnnt_alsd / rs_rnnt_beam)");
+    if (B < 0 || tp_max < 0 || out_cap < 0) return rs_fail(ctx, RS_EINVAL, "modified beam search: negative size");
+    if (max_active_paths < 1 || max_active_paths > 8) return rs_fail(ctx, RS_EINVAL, "modified beam search: max_active_paths must be 1..8, got %d", max_active_paths);
+    if (!(blank_penalty >= 0.0f)) return rs_fail(ctx, RS_EINVAL, "modified beam search: blank_penalty must be >= 0");
+    if (B == 0) return RS_OK;
+    if (!joint_enc || !enc_lens || !ids || !frames || !n_ids || !scores || !workspace) return rs_fail(ctx, RS_EINVAL, "modified beam search: null pointer");
+    if (tp_max == 0) {
+        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, (size_t)B * 4, (hipStream_t)stream));
+        RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * 4, (hipStream_t)stream));
+        return RS_OK;
+    }
+    return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
+                            out_cap, ids, frames, n_ids, scores, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- profiling -------------------------------------------------------------------------------------

@@ -195,7 +195,8 @@ class RSEspnetAmdEvaluator(RSAmdEvaluator):
 class RSK2AmdEvaluator(RSAmdEvaluator):
     """Counterpart of `RSK2Evaluator` (pkg/evaluation/examples/rs-k2/eval.py:15-33) over `reazonspeech.k2.asr` of this package:
     `_evaluate` is the reference's hook (load on cuda:{rank % num_gpus}, `transcribe(model, audio).text`), `_evaluate_batch` —
-    which the reference leaves unimplemented (:32-33) — recognises the whole batch through `transcribe_batch`."""
+    which the reference leaves unimplemented (:32-33) — recognises the whole batch through `transcribe_batch`.  The search is the
+    model's: an evaluator whose `_load_model` passes `decoding_method="modified_beam_search"` scores the beam search unchanged."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)

@@ -56,7 +56,8 @@ def resolve_checkpoint(language, precision, checkpoint=None):
         return hf.snapshot_download(repo), files
 
 
-def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False):
+def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
+               decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -81,6 +82,10 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
         run here.  An explicit "bf16" / "fp32" / "fp32x3" with the int8 files raises ValueError.  With `synthetic` weights and an int8
         `precision`, the float weights are quantized with onnxruntime's QInt8 recipe (runtime/k2_weights.py: quantize_k2_linears).
         (`precision` keeps the reference's meaning: WHICH files are read.)
+      decoding_method (str), max_active_paths (int), blank_penalty (float): the keywords of
+        `sherpa_onnx.OfflineRecognizer.from_transducer` with its defaults.  "greedy_search" is what the reference passes (:81);
+        "modified_beam_search" keeps `max_active_paths` (1..8, default 4) hypotheses per utterance (rs_rnnt_mbs,
+        csrc/k_rnnt_mbs.hip: no LM, no hotwords).  Valid with every `precision` / `compute`; anything else raises ValueError.
 
     A real icefall export has never been read by runtime/k2_onnx.py (no file is reachable from the build environment): the reader
     is verified against files written in the documented export layout only, and checks itself after loading (every expected
@@ -94,6 +99,9 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     from ...runtime.k2_weights import synthetic_state_dict_k2
     from .model import K2Model, read_tokens, synthetic_tokens
     repo_files(language, precision)                       # argument errors first, like the reference
+    from .model import search_config
+    search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty)
+    search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):
@@ -126,8 +134,8 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
             raise ValueError(f"tokens.txt has {len(tokens)} symbols, the joiner {cfg.vocab_size} outputs")
         cfg = cfg.with_(unk_id=tokens.index("<unk>") if "<unk>" in tokens else -1)
         if quantized:
-            return K2Model(cfg, sd, tokens, device=device, precision="int8", qweights=q)
-        return K2Model(cfg, sd, tokens, device=device, precision=compute or "bf16")
+            return K2Model(cfg, sd, tokens, device=device, precision="int8", qweights=q, **search)
+        return K2Model(cfg, sd, tokens, device=device, precision=compute or "bf16", **search)
     cfg = config or ZIPFORMER_159M
     print(f"[reazonspeech_amd] WARNING: SEEDED SYNTHETIC weights of the {cfg.n_params() / 1e6:.0f}M Zipformer architecture were requested "
           f"(`config=` / `synthetic=True` / ${SYNTHETIC_ENV}): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
@@ -135,5 +143,5 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     if quantized:
         from ...runtime.k2_weights import quantize_k2_linears, dequantize_k2_linears
         q = quantize_k2_linears(cfg, sd)
-        return K2Model(cfg, dequantize_k2_linears(sd, q), synthetic_tokens(cfg.vocab_size, seed), device=device, precision="int8", qweights=q)
-    return K2Model(cfg, sd, synthetic_tokens(cfg.vocab_size, seed), device=device, precision=compute or "bf16")
+        return K2Model(cfg, dequantize_k2_linears(sd, q), synthetic_tokens(cfg.vocab_size, seed), device=device, precision="int8", qweights=q, **search)
+    return K2Model(cfg, sd, synthetic_tokens(cfg.vocab_size, seed), device=device, precision=compute or "bf16", **search)

@@ -58,14 +58,39 @@ def synthetic_tokens(vocab_size, seed=0):
     return toks
 
 
+DECODING_METHODS = ("greedy_search", "modified_beam_search")      # sherpa-onnx's offline transducer methods
+
+
+def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0):
+    """`cfg` with the search sherpa_onnx.OfflineRecognizer.from_transducer's keywords ask for (its names and defaults);
+    ValueError for anything it does not have or this package does not run.  Needs no GPU."""
+    if decoding_method not in DECODING_METHODS:
+        raise ValueError(f"decoding_method must be 'greedy_search' or 'modified_beam_search', not {decoding_method!r}")
+    if not float(blank_penalty) >= 0.0:
+        raise ValueError(f"blank_penalty must be >= 0, not {blank_penalty!r}")
+    if decoding_method == "greedy_search":
+        if float(blank_penalty) != 0.0:
+            raise ValueError("blank_penalty applies to decoding_method='modified_beam_search' only")
+        return cfg.with_(decoding="greedy_batch", beam_size=1, blank_penalty=0.0)
+    if not (isinstance(max_active_paths, int) and 1 <= max_active_paths <= 8):
+        raise ValueError(f"max_active_paths must be an integer in 1..8, not {max_active_paths!r}")
+    return cfg.with_(decoding="modified_beam_search", beam_size=int(max_active_paths), blank_penalty=float(blank_penalty))
+
+
 class K2Model:
-    def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None):
-        """precision: "bf16" = the throughput mode; "fp32" = float32 weights, activations and arithmetic end to end (what
+    def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
+                 decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0):
+        """decoding_method / max_active_paths / blank_penalty: sherpa_onnx.OfflineRecognizer.from_transducer's keywords with its
+        defaults (pkg/k2-asr/src/huggingface.py:73-83 passes "greedy_search"): "modified_beam_search" keeps max_active_paths (1..8)
+        hypotheses per utterance (csrc/k_rnnt_mbs.hip, rs_rnnt_mbs); valid with every precision — the search only consumes the
+        encoder projection.  Anything else raises ValueError.
+        precision: "bf16" = the throughput mode; "fp32" = float32 weights, activations and arithmetic end to end (what
         onnxruntime computes from the reference's default float32 graphs: pkg/k2-asr/src/huggingface.py:16,40-45); "fp32x3" = the
         float32 mode with three-term bf16 products; "int8" = onnxruntime's int8 graph restated (the "int8" / "int8-fp32" files):
         the float32 mode with every Linear of `qweights` ({icefall name: (Wq int8 [out][in], sw, zw)}: read_k2_onnx_quantized or
         quantize_k2_linears) as a dynamically quantized MatMul, scales per utterance; `state_dict` then holds the dequantized weights"""
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
+        cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty)
         self.cfg = cfg
         self.tokens = list(tokens)
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded

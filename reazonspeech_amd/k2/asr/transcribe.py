@@ -37,6 +37,9 @@ def transcribe(model, audio, config=None):
 
     Returns:
         TranscribeResult
+
+    The search is the model's: a model built with `load_model(decoding_method="modified_beam_search", max_active_paths=K)` is
+    decoded by the beam search, nothing changes here.
     """
     if config is None:
         config = TranscribeConfig()
@@ -49,7 +52,8 @@ def transcribe(model, audio, config=None):
 
 def transcribe_batch(model, audios, config=None):
     """Additive: many utterances as one (or several pipelined) batches on the device; per utterance the same result as
-    `transcribe` (every kernel masks by the utterance's own length)."""
+    `transcribe` (every kernel masks by the utterance's own length).  The search (greedy or modified beam search) is the one the
+    model was built with (`load_model(decoding_method=...)`)."""
     streams = []
     for a in audios:
         a = _prepare(a)

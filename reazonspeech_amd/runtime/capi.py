@@ -21,6 +21,7 @@ GEMM_BIAS, GEMM_RELU, GEMM_SILU, GEMM_RESIDUAL, GEMM_OUT_F32, GEMM_ROWMASK, GEMM
 GEMM_SWOOSHL, GEMM_SWOOSHR, GEMM_GELU = 128, 256, 512
 GLU_HALVES, GLU_BLOCK32, GLU_APPLIED = 0, 1, 2
 ALSD_SCORE_NORM, ALSD_MERGE = 1, 2
+MBS_LENGTH_NORM = 1
 PROF_GEMM, PROF_ATTN, PROF_FRONTEND, PROF_DECODE, PROF_ELEMENTWISE, PROF_SUBSAMPLE = 1, 2, 4, 8, 16, 32
 
 # every symbol include/rs_asr.h declares (tests/test_capi_exports.py checks the .so exports them)
@@ -30,6 +31,7 @@ EXPORTS = [
     "rs_rnnt_greedy", "rs_profile_enable", "rs_profile_read", "rs_profile_reset", "rs_gemm_bf16",
     "rs_layernorm", "rs_relpos_attention", "rs_glu_dwconv_silu", "rs_glu_dwconv_silu_layout", "rs_encoder_set_taps", "rs_set_option", "rs_stream_create", "rs_stream_destroy",
     "rs_rnnt_alsd", "rs_rnnt_alsd_workspace_bytes", "rs_rnnt_beam", "rs_rnnt_beam_workspace_bytes", "rs_host_stage_rows",
+    "rs_rnnt_mbs", "rs_rnnt_mbs_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
     "rs_k2_create", "rs_k2_encoder_set_taps",
@@ -147,6 +149,9 @@ def load():
     lib.rs_rnnt_beam_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_beam.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_beam.restype = c_int
+    lib.rs_rnnt_mbs_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
+    lib.rs_rnnt_mbs_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_mbs.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_alsd_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
     lib.rs_rnnt_alsd_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_alsd.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp, vp,
@@ -179,7 +184,7 @@ def load():
     lib.rs_avsr_decoder_state_bytes.restype = c_size_t
     lib.rs_avsr_decoder_begin.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, c_size_t, vp]
     lib.rs_avsr_decoder_step.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, c_int, c_int, vp, vp, c_size_t, vp]
-    if lib.rs_abi_version() != 6:
+    if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
     return lib
@@ -376,6 +381,21 @@ class Context:
         self.check(self.lib.rs_rnnt_beam(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, 1 if score_norm else 0,
                                          int(max_pops), ids.shape[1], _ptr(ids), _ptr(frames) if frames is not None else None, _ptr(n_ids), _ptr(scores), _ptr(pops), _ptr(ws),
                                          ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def mbs_workspace_bytes(self, B, max_active_paths, tp_max, out_cap):
+        n = self.lib.rs_rnnt_mbs_workspace_bytes(self._h, B, max_active_paths, tp_max, out_cap)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_mbs_workspace_bytes: invalid arguments (a Zipformer context, max_active_paths 1..8)")
+        return n
+
+    def rnnt_mbs(self, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, length_norm, ids, frames, n_ids, scores, ws,
+                 stream):
+        """sherpa-onnx's modified_beam_search (Zipformer contexts): ids / frames int32 [B][out_cap], n_ids int32 [B], scores
+        float32 [B] (log_prob of the winner, not normalised)"""
+        assert frames.shape == ids.shape
+        self.check(self.lib.rs_rnnt_mbs(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
+                                        MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids), _ptr(frames), _ptr(n_ids),
+                                        _ptr(scores), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
 
     # ---- profiling ----
     def profile_enable(self, mask):

@@ -49,13 +49,21 @@ class ZipformerConfig:
     frame_shift_ms: int = 10
     subsampling_factor: int = 4
 
+    # --- the search: sherpa-onnx's two offline transducer methods ---
+    decoding: str = "greedy_batch"     # "greedy_batch" = decoding_method="greedy_search" (huggingface.py:81, the reference's choice);
+    #                                    "modified_beam_search" = the constructor's other method (csrc/k_rnnt_mbs.hip)
+    beam_size: int = 1                 # modified_beam_search: max_active_paths, 1..8 (sherpa-onnx's default is 4)
+    blank_penalty: float = 0.0         # modified_beam_search: subtracted from the blank logit (sherpa-onnx's default 0)
+    mbs_length_norm: bool = True       # modified_beam_search: the winner is the best log_prob / len(ys) ([UPSTREAM] GetMostProbable(true))
+
     family = "k2"
     # what the shared host runtime (runtime/model.py: AsrModel) reads off a model configuration
     espnet = False
-    decoding = "greedy_batch"          # sherpa-onnx decoding_method="greedy_search" (huggingface.py:81)
-    has_scores = False
     max_symbols = 1                    # one symbol per frame
-    beam_size = 1
+
+    @property
+    def has_scores(self):
+        return self.decoding == "modified_beam_search"
 
     @property
     def joint_hidden(self):
@@ -155,6 +163,9 @@ class ZipformerConfig:
         assert self.decoder_dim % 128 == 0 and self.joiner_dim % 128 == 0 and self.decoder_dim % 4 == 0
         assert self.embed_channels[2] % 64 == 0 and (self.embed_freq * self.embed_channels[2]) % 64 == 0
         assert self.blank_id == 0
+        assert self.decoding in ("greedy_batch", "modified_beam_search"), "sherpa-onnx has greedy_search and modified_beam_search"
+        if self.decoding == "modified_beam_search":
+            assert 1 <= self.beam_size <= 8 and self.blank_penalty >= 0.0, "max_active_paths 1..8, blank_penalty >= 0"
         return self
 
 

@@ -334,8 +334,8 @@ class AsrModel:
 
     def decode(self, ctx, buf: _Buffers, ws, stream, max_pops=None, decoding=None):
         """stage 3 on `stream`: the checkpoint's decoding strategy (cfg.decoding).  Greedy fills buf.ids / buf.frames
-        (emission frames); ALSD fills buf.ids / buf.frames (alignment steps i = frame + labels before) / buf.scores.
-        Both synchronise the stream."""
+        (emission frames); ALSD fills buf.ids / buf.frames (alignment steps i = frame + labels before) / buf.scores; the
+        modified beam search of the Zipformer family fills buf.ids / buf.frames (frames) / buf.scores.  All synchronise the stream."""
         cfg = self.cfg
         if max_pops is not None or decoding is not None:     # per-call overrides (the caller's retry policy): never written into self.cfg
             cfg = cfg.with_(**({"beam_max_pops": int(max_pops)} if max_pops is not None else {}), **({"decoding": decoding} if decoding is not None else {}))
@@ -345,6 +345,13 @@ class AsrModel:
                 buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
             ctx.rnnt_beam(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops,
                           buf.ids, buf.n_ids, buf.scores, buf.pops, buf.ws_alsd, stream, frames=buf.frames)
+            return
+        if cfg.decoding == "modified_beam_search":    # Zipformer family: sherpa-onnx's second method (csrc/k_rnnt_mbs.hip)
+            n = ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1])
+            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
+                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            ctx.rnnt_mbs(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
+                         buf.ids, buf.frames, buf.n_ids, buf.scores, buf.ws_alsd, stream)
             return
         if cfg.decoding != "alsd":
             ctx.rnnt_greedy(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, buf.u_max, buf.ids, buf.frames, buf.n_ids,
@@ -578,12 +585,12 @@ class AsrModel:
         decoding = decoding or self.cfg.decoding
         if host is None:
             host = (buf.n_ids.cpu(), buf.ids.cpu(), buf.frames.cpu(), buf.enc_lens.cpu(),
-                    buf.scores.cpu() if decoding in ("alsd", "beam") else None)
+                    buf.scores.cpu() if decoding in ("alsd", "beam", "modified_beam_search") else None)
         n, ids, frames, el = (t.numpy() for t in host[:4])
         if decoding == "alsd":      # alignment step i = frame + labels emitted before
             frames = frames - np.arange(frames.shape[1], dtype=frames.dtype)[None, :]
             scores = host[4].numpy().tolist()
-        elif decoding == "beam":    # frames = the frame each label was appended at ([UPSTREAM] NeMo Hypothesis.timestep)
+        elif decoding in ("beam", "modified_beam_search"):    # frames = the frame each label was appended at ([UPSTREAM] NeMo Hypothesis.timestep)
             scores = host[4].numpy().tolist()
         else:
             scores = None
