@@ -186,6 +186,63 @@ int rs_avsr_decoder_begin(rs_ctx* ctx, const float* enc, int B, int T, int beams
                           void* stream);
 int rs_avsr_decoder_step(rs_ctx* ctx, const int32_t* tokens, const int32_t* src_rows, int step, const float* padding_mask, int B,
                          int T, int beams, int max_len, float* logits, void* state, size_t state_bytes, void* stream);
+
+/* ---- reazonspeech.avsr: generate()'s searches on the device (csrc/k_avsr_search.hip; added within ABI 7) ---------------------------
+ * Replaces: what transformers' GenerationMixin does with the logits inside AVHubertForConditionalGeneration.generate()
+ * (modeling_avhubert.py:216,372-391; README.rst:41 `model.generate(**inputs, num_beams=5, max_new_tokens=256)`):
+ *   greedy != 0   GenerationMixin._sample with do_sample False: argmax per row over v < vocab, EQUAL VALUES TAKE THE LOWER INDEX; a
+ *                 row that emitted eos is fed / filled with pad_token_id; stops when no row is unfinished.  beams must be 1.
+ *   greedy == 0   GenerationMixin._beam_search (v4.50+, early_stopping False, one eos token) with `beams` = num_beams in 1..8: per clip
+ *                 and step the 2 beams best (beam, token) continuations by log_softmax + running score, ORDERED BY VALUE DESCENDING,
+ *                 THEN FLAT INDEX beam * vocab + token ASCENDING; the `beams` best that do not end run on (equal values: the earlier
+ *                 candidate); those among the first `beams` that end (eos, or the last position) compete with score / (generated
+ *                 length) ** length_penalty for the clip's finished slots (equal scores: the earlier position, finished slots before
+ *                 candidates); a clip stops adding finished hypotheses once its best running score cannot beat its worst finished
+ *                 one; the search ends when no clip can improve or nothing can continue.
+ * Arithmetic is float32 in the order of reazonspeech_amd/avsr/generation.py.  log_softmax of a row x: m = max x; S = sum of
+ * rs_expf(x[v] - m) with thread t of 256 adding its columns v = t, t + 256, ... in increasing v and the 256 partial sums combined by a
+ * binary tree (stride 128, 64, ..., 1: p[t] += p[t + stride]); logp[v] = ((x[v] - m) - rs_logf(S)) + running score.  The length
+ * divisor is (float)pow((double)position, (double)length_penalty) computed on the host. */
+typedef struct rs_avsr_search {
+    int32_t beams;                 /* hypothesis rows per clip, 1..8 */
+    int32_t max_new_tokens;        /* >= 1; 1 + max_new_tokens <= max_positions */
+    int32_t bos_token_id;          /* the decoder prompt is this one token */
+    int32_t eos_token_id;
+    int32_t pad_token_id;
+    int32_t greedy;                /* != 0: _sample (beams must be 1); 0: _beam_search (also with beams 1) */
+    float length_penalty;          /* beam search only; transformers' default 1.0 */
+} rs_avsr_search;
+/* The search alone, step by step over caller-supplied logits f32[B * beams][vocab rounded up to 4] (columns >= vocab are never
+ * read) — this family's single-operator hook; rs_avsr_generate is built from it.  `state` is caller-owned device memory of
+ * rs_avsr_search_state_bytes(B, beams, 1 + max_new_tokens) bytes.  Call _begin, then _step for step = 0, 1, ... in order; nothing
+ * synchronises except _peek and _finish.  A step issued after the search has stopped changes nothing.
+ *   rs_avsr_search_rows     device pointers (inside `state`) to tokens i32[rows] and src_rows i32[rows]: what the next
+ *                           rs_avsr_decoder_step takes (greedy: pass src_rows NULL to the decoder)
+ *   rs_avsr_search_peek     host copies (any may be NULL) of tokens, src_rows, running scores f32[rows], finished scores f32[rows], and
+ *                           *goes_on = 1 if step `step` is to run (the device's go word of that step: greedy, the number of unfinished
+ *                           rows; beam, low half = clips that can improve, high half = clips with a candidate that does not end)
+ *   rs_avsr_search_finish   sequences i32[B][1 + max_new_tokens] (bos first, pad_token_id past a clip's end), lengths i32[B], scores
+ *                           f32[B] (beam: the best finished hypothesis and its score; NULL allowed; greedy: zeros); device pointers
+ * RS_EINVAL for a context that is not avsr, beams outside 1..8, 1 + max_new_tokens > max_positions, vocab < 4; RS_EWORKSPACE for a
+ * short state.  The *_state_bytes queries return 0 for such arguments. */
+size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len);
+int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes, void* stream);
+int rs_avsr_search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, int B, int vocab, void* state,
+                        size_t state_bytes, void* stream);
+int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, const int32_t** tokens,
+                        const int32_t** src_rows);
+int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int step, int32_t* tokens,
+                        int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on, void* stream);
+int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int32_t* sequences,
+                          int32_t* lengths, float* scores, void* stream);
+/* Replaces: generate() after the encoder.  enc f32[B][T][d] and padding_mask f32[B][T] as for rs_avsr_decoder_*; runs
+ * rs_avsr_decoder_begin once, then per token rs_avsr_decoder_step on the tokens / src_rows the last selection left on the device and
+ * rs_avsr_search_step on its logits.  The host reads one 4-byte go word per step, two steps behind the launches; no other host
+ * traffic per token.  Outputs as rs_avsr_search_finish.  `state`: rs_avsr_generate_state_bytes(B, T, beams, 1 + max_new_tokens)
+ * bytes (decoder state + search state + logits).  Synchronises the stream internally (the trip count depends on the data). */
+size_t rs_avsr_generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len);
+int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
+                     int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream);
 void rs_destroy(rs_ctx* ctx);
 const char* rs_last_error(const rs_ctx* ctx);
 int rs_abi_version(void);

@@ -6,7 +6,8 @@
     enc = model.avhubert(input_values=..., pixel_values=..., padding_mask=...).last_hidden_state
 
 Everything between the input tensors and the logits runs in librs_asr.so (csrc/k_avsr.hip, float32 like the reference); the search
-over the logits is host logic (generation.py).  Training-time arguments (labels, dropout, layerdrop) have no counterpart."""
+over the logits is host logic (generation.py) or, with search="device", runs on the device too (csrc/k_avsr_search.hip).
+Training-time arguments (labels, dropout, layerdrop) have no counterpart."""
 from dataclasses import dataclass
 from typing import Optional
 
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 from ..runtime.avsr_config import AvsrConfig, AVSR_BASE
-from ..runtime.avsr_model import AvsrDevice
+from ..runtime.avsr_model import AvsrDevice, resolve_search
 from . import generation
 
 AVHubertConfig = AvsrConfig
@@ -61,21 +62,24 @@ class AVHubertModel:
 
 
 class AVHubertForConditionalGeneration:
-    def __init__(self, config: AvsrConfig, state_dict, device="cuda", products=None):
-        """products: None ($REAZONSPEECH_AVSR_PRODUCTS, default "exact") | "exact" | "x3" — runtime/avsr_model.py set_products"""
+    def __init__(self, config: AvsrConfig, state_dict, device="cuda", products=None, search=None):
+        """products: None ($REAZONSPEECH_AVSR_PRODUCTS, default "exact") | "exact" | "x3" — runtime/avsr_model.py set_products
+        search: None ($REAZONSPEECH_AVSR_SEARCH, default "host") | "host" (generation.py over the device logits) | "device"
+        (rs_avsr_generate: greedy and beam search with up to 8 beams decided on the device, csrc/k_avsr_search.hip)"""
         if config.vocab_size is None:
             raise ValueError("the configuration does not define `vocab_size`")                    # modeling_avhubert.py:232-238
+        self.search = resolve_search(search)
         self.config = config
         self.dev = AvsrDevice(config, state_dict, device, products=products)
         self.device = self.dev.device
         self.avhubert = AVHubertModel(config, _dev=self.dev)
 
     @classmethod
-    def from_pretrained(cls, path, device="cuda", products=None):
+    def from_pretrained(cls, path, device="cuda", products=None, search=None):
         """a directory with config.json + model.safetensors / pytorch_model.bin under the reference's parameter names"""
         from ..runtime.avsr_weights import read_avsr
         cfg, sd = read_avsr(path)
-        return cls(cfg, sd, device=device, products=products)
+        return cls(cfg, sd, device=device, products=products, search=search)
 
     def get_encoder(self):
         return self.avhubert
@@ -115,9 +119,16 @@ class AVHubertForConditionalGeneration:
                 raise TypeError(f"generate(): option `{k}` is not built (greedy and beam search with num_beams, max_new_tokens / max_length, length_penalty are)")
             if neutral[k] is not None and v is not None and v != neutral[k]:
                 raise NotImplementedError(f"generate(): `{k}={v!r}` changes the search and is not built (only {neutral[k]!r})")
+        if self.search == "device" and num_beams > AvsrDevice.MAX_DEVICE_BEAMS:
+            raise ValueError(f"search='device': num_beams={num_beams} exceeds the device search's limit of {AvsrDevice.MAX_DEVICE_BEAMS} "
+                             "(build the model with search='host' for wider beams)")
         enc = self.avhubert(input_values=input_values, pixel_values=pixel_values, padding_mask=padding_mask).last_hidden_state
         mask = padding_mask if padding_mask is not None else np.zeros(enc.shape[:2], np.float32)
-        if num_beams <= 1:
+        if self.search == "device":
+            greedy = num_beams <= 1
+            seq, scores = self.dev.generate(enc, mask, 1 if greedy else int(num_beams), int(max_new_tokens), greedy, float(length_penalty))
+            scores = None if greedy else scores
+        elif num_beams <= 1:
             seq, scores = generation.greedy_search(self.dev, enc, mask, int(max_new_tokens)), None
         else:
             seq, scores = generation.beam_search(self.dev, enc, mask, int(num_beams), int(max_new_tokens), float(length_penalty))
@@ -127,7 +138,7 @@ class AVHubertForConditionalGeneration:
         return seq
 
 
-def synthetic_model(config: AvsrConfig = AVSR_BASE, seed: int = 0, device="cuda", products=None):
+def synthetic_model(config: AvsrConfig = AVSR_BASE, seed: int = 0, device="cuda", products=None, search=None):
     """seeded synthetic weights under the reference's parameter names (benchmarks / tests: no checkpoint is reachable offline)"""
     from ..runtime.avsr_weights import synthetic_state_dict_avsr
-    return AVHubertForConditionalGeneration(config, synthetic_state_dict_avsr(config, seed), device=device, products=products)
+    return AVHubertForConditionalGeneration(config, synthetic_state_dict_avsr(config, seed), device=device, products=products, search=search)

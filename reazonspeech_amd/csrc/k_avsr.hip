@@ -1024,3 +1024,6 @@ extern "C" int rs_avsr_decoder_step(rs_ctx* ctx, const int32_t* tokens, const in
 #undef RS_TRY
     return RS_OK;
 }
+
+// the dimensions of an avsr context for the other translation units (k_avsr_search.hip); nullptr for another family's context
+const rs_avsr_dims* rs_avsr_dims_of(const rs_ctx* ctx) { return ctx && ctx->avsr ? &ctx->avsr->d : nullptr; }

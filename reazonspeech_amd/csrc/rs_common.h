@@ -272,6 +272,7 @@ int rs_launch_im2col3x3s2_f32(rs_ctx* ctx, const float* in, int Bc, int T1, int 
 static inline int rs_ctc_pad(int v) { return (v + 3) / 4 * 4; }
 // Zipformer family (k_zipformer.hip): the entry points of rs_api.hip dispatch to these when ctx->k2 is set
 int rs_avsr_finalize_impl(rs_ctx* ctx);
+const rs_avsr_dims* rs_avsr_dims_of(const rs_ctx* ctx);   // k_avsr.hip: nullptr unless an avsr context
 int rs_k2_finalize_impl(rs_ctx* ctx);
 int rs_k2_unk_id(const rs_ctx* ctx);
 size_t rs_k2_workspace_bytes_impl(const rs_ctx* ctx, int B, int t_max);

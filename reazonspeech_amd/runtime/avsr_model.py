@@ -11,8 +11,18 @@ from .avsr_config import AvsrConfig
 from .avsr_weights import prepare_weights_avsr
 
 
+def resolve_search(search):
+    """search: None ($REAZONSPEECH_AVSR_SEARCH, default "host") | "host" | "device" — where generate() decides (AvsrDevice.generate)"""
+    search = search or os.environ.get("REAZONSPEECH_AVSR_SEARCH", "host")
+    if search not in AvsrDevice.SEARCHES:
+        raise ValueError(f"search={search!r}: one of {AvsrDevice.SEARCHES}")
+    return search
+
+
 class AvsrDevice:
     PRODUCTS = ("exact", "x3")
+    SEARCHES = ("host", "device")
+    MAX_DEVICE_BEAMS = capi.RsAvsrSearch.MAX_BEAMS
 
     def __init__(self, cfg: AvsrConfig, state_dict, device="cuda", products=None):
         cfg.validate()
@@ -34,6 +44,7 @@ class AvsrDevice:
         self.vp = (cfg.vocab_size + 3) // 4 * 4
         self._ws = None
         self._state = None
+        self._gen_state = None
         self._taps = None
 
     def set_products(self, products: str):
@@ -130,3 +141,37 @@ class AvsrDevice:
 
     def decoding(self, enc, padding_mask, beams, max_len):
         return AvsrDevice.Decoding(self, enc, padding_mask, beams, max_len)
+
+    # ---- generate() on the device ----------------------------------------------------------------------------------------------
+    def search_params(self, beams, max_new_tokens, greedy, length_penalty=1.0):
+        cfg = self.cfg
+        return capi.RsAvsrSearch(int(beams), int(max_new_tokens), cfg.bos_token_id, cfg.eos_token_id, cfg.pad_token_id, int(bool(greedy)),
+                                 float(length_penalty))
+
+    def generate(self, enc, padding_mask, beams, max_new_tokens, greedy, length_penalty=1.0):
+        """rs_avsr_generate (csrc/k_avsr_search.hip): decoder steps and the search of every token on the device, one 4-byte stop word
+        read per step.  enc float32 [B][T][d] on the device -> (sequences int64 [B][L] trimmed to the longest result, scores float32
+        [B]), both on the CPU.  No torch kernel runs here: torch allocates, the library computes, the results are copied out."""
+        if beams > self.MAX_DEVICE_BEAMS:
+            raise ValueError(f"search='device': num_beams={beams} exceeds the device search's limit of {self.MAX_DEVICE_BEAMS} (use search='host')")
+        lib, h = self.ctx.lib, self.ctx._h
+        B, T = enc.shape[:2]
+        max_len = 1 + int(max_new_tokens)
+        sp = self.search_params(beams, max_new_tokens, greedy, length_penalty)
+        enc = enc.contiguous()
+        mask = self._dev(padding_mask)
+        with torch.cuda.device(self.device):
+            need = int(lib.rs_avsr_generate_state_bytes(h, B, T, int(beams), max_len))
+            if need == 0:
+                raise ValueError(f"search='device': invalid arguments (beams {beams}, max_new_tokens {max_new_tokens})")
+            if self._gen_state is None or self._gen_state.numel() < need:
+                self._gen_state = None
+                self._gen_state = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            seq = torch.empty((B, max_len), dtype=torch.int32, device=self.device)
+            lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+            scores = torch.empty((B,), dtype=torch.float32, device=self.device)
+            self.ctx.check(lib.rs_avsr_generate(h, capi._ptr(enc), capi._ptr(mask), B, T, ctypes.byref(sp), capi._ptr(seq), capi._ptr(lens),
+                                                capi._ptr(scores), capi._ptr(self._gen_state), self._gen_state.numel(),
+                                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            seq, lens, scores = seq.cpu(), lens.cpu(), scores.cpu()
+        return seq[:, :int(lens.max())].numpy().astype(np.int64), scores.numpy()

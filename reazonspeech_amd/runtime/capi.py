@@ -37,6 +37,8 @@ EXPORTS = [
     "rs_k2_create", "rs_k2_encoder_set_taps",
     "rs_avsr_create", "rs_avsr_workspace_bytes", "rs_avsr_encoder_forward", "rs_avsr_encoder_set_taps", "rs_avsr_decoder_state_bytes",
     "rs_avsr_decoder_begin", "rs_avsr_decoder_step",
+    "rs_avsr_search_state_bytes", "rs_avsr_search_begin", "rs_avsr_search_step", "rs_avsr_search_rows", "rs_avsr_search_peek",
+    "rs_avsr_search_finish", "rs_avsr_generate_state_bytes", "rs_avsr_generate",
 ]
 
 
@@ -98,6 +100,15 @@ class RsAvsrDims(Structure):
         return cls(cfg.encoder_layers, cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.encoder_attention_heads, cfg.conv_pos, cfg.conv_pos_groups,
                    cfg.audio_feat_dim, int(cfg.modality_fuse == "concat"), cfg.image_size, cfg.decoder_layers, cfg.decoder_embed_dim,
                    cfg.decoder_ffn_embed_dim, cfg.decoder_attention_heads, cfg.max_target_positions, cfg.vocab_size, cfg.layer_norm_eps)
+
+
+class RsAvsrSearch(Structure):
+    """mirror of `struct rs_avsr_search` (generate()'s searches on the device: csrc/k_avsr_search.hip)"""
+    MAX_BEAMS = 8
+    _fields_ = [
+        ("beams", c_int32), ("max_new_tokens", c_int32), ("bos_token_id", c_int32), ("eos_token_id", c_int32), ("pad_token_id", c_int32),
+        ("greedy", c_int32), ("length_penalty", c_float),
+    ]
 
 
 class RsError(RuntimeError):
@@ -184,6 +195,17 @@ def load():
     lib.rs_avsr_decoder_state_bytes.restype = c_size_t
     lib.rs_avsr_decoder_begin.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, c_size_t, vp]
     lib.rs_avsr_decoder_step.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, c_int, c_int, vp, vp, c_size_t, vp]
+    sp = POINTER(RsAvsrSearch)
+    lib.rs_avsr_search_state_bytes.argtypes = [vp, c_int, c_int, c_int]
+    lib.rs_avsr_search_state_bytes.restype = c_size_t
+    lib.rs_avsr_search_begin.argtypes = [vp, sp, c_int, c_int, vp, c_size_t, vp]
+    lib.rs_avsr_search_step.argtypes = [vp, vp, c_int, sp, c_int, c_int, vp, c_size_t, vp]
+    lib.rs_avsr_search_rows.argtypes = [vp, sp, c_int, vp, c_size_t, POINTER(c_void_p), POINTER(c_void_p)]
+    lib.rs_avsr_search_peek.argtypes = [vp, sp, c_int, vp, c_size_t, c_int, vp, vp, vp, vp, POINTER(c_int32), vp]
+    lib.rs_avsr_search_finish.argtypes = [vp, sp, c_int, vp, c_size_t, vp, vp, vp, vp]
+    lib.rs_avsr_generate_state_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
+    lib.rs_avsr_generate_state_bytes.restype = c_size_t
+    lib.rs_avsr_generate.argtypes = [vp, vp, vp, c_int, c_int, sp, vp, vp, vp, vp, c_size_t, vp]
     if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
