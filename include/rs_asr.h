@@ -243,6 +243,46 @@ int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, int B, void
 size_t rs_avsr_generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len);
 int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
                      int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream);
+/* The same searches with transformers' logits processors and beam-search switches (still ABI 7; the entry points above are these
+ * with neutral options and stay bit-identical).  Semantics are those of transformers.generation (logits_process.py; utils.py
+ * _get_logits_processor, _sample, _beam_search): per hypothesis row, over its own prefix with bos,
+ *   1. repetition_penalty p: s = s < 0 ? s * p : s / p for every token of the prefix (one float32 operation)
+ *   2. no_repeat_ngram_size n: -inf for a token that would complete an n-gram already in the prefix (n = 1: every token seen; nothing
+ *      while the prefix has fewer than n tokens)
+ *   3. min_new_tokens m: -inf for eos while fewer than m tokens have been generated
+ * applied, greedy, to the raw logits before the argmax, and, beam, to (x[v] - m) - rs_logf(S) before the running score is added, with
+ * m and S those of the raw logits (no renormalisation).  -inf candidates follow the same order (value, then flat index).
+ *   early_stopping 0  transformers' False: as above
+ *                  1  True: a clip whose `beams` finished slots are full takes no more, and the search ends when every clip is full
+ *                  2  "never": with length_penalty > 0 the can-improve test divides the best running score by
+ *                     (float)pow((double)max_new_tokens, (double)length_penalty) instead of by the current length's divisor
+ *   num_return_sequences n in 1..beams: _finish / _generate write the n best finished hypotheses of every clip, clip-major:
+ *      sequences i32[B * n][1 + max_new_tokens], lengths i32[B * n] (0: the slot never finished and holds bos + pad), scores f32[B * n]
+ * RS_EINVAL for repetition_penalty <= 0, a negative size, early_stopping outside 0..2, n outside 1..beams, greedy with n > 1. */
+typedef struct rs_avsr_search_opts {
+    float repetition_penalty;      /* > 0; 1.0: none */
+    int32_t no_repeat_ngram_size;  /* >= 0; 0: none */
+    int32_t min_new_tokens;        /* >= 0 */
+    int32_t early_stopping;        /* 0 False, 1 True, 2 "never" (beam search only) */
+    int32_t num_return_sequences;  /* 1..beams (greedy: 1) */
+} rs_avsr_search_opts;
+/* `opts` NULL means neutral.  The state of the _opts forms is rs_avsr_search_state_bytes_opts / rs_avsr_generate_state_bytes_opts
+ * bytes (vocab: large vocabularies keep their per-row token marks there); its front has the layout of the plain forms, so
+ * rs_avsr_search_rows serves both.  rs_avsr_search_peek_opts is _peek whose *goes_on also honours early_stopping 1. */
+size_t rs_avsr_search_state_bytes_opts(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts);
+int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
+                              size_t state_bytes, void* stream);
+int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts,
+                             int B, int vocab, void* state, size_t state_bytes, void* stream);
+int rs_avsr_search_peek_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state,
+                             size_t state_bytes, int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores,
+                             int32_t* goes_on, void* stream);
+int rs_avsr_search_finish_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state,
+                               size_t state_bytes, int32_t* sequences, int32_t* lengths, float* scores, void* stream);
+size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts);
+int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
+                          const rs_avsr_search_opts* opts, int32_t* sequences, int32_t* lengths, float* scores, void* state,
+                          size_t state_bytes, void* stream);
 void rs_destroy(rs_ctx* ctx);
 const char* rs_last_error(const rs_ctx* ctx);
 int rs_abi_version(void);

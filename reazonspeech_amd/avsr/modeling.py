@@ -101,10 +101,45 @@ class AVHubertForConditionalGeneration:
 
     __call__ = forward
 
+    @staticmethod
+    def _device_options(opts, num_beams):
+        """generate()'s search options -> AvsrDevice.search_opts' keywords, refused with transformers' own error types
+        (generation/utils.py _validate_generation_mode / configuration_utils.py validate, logits_process.py constructors)"""
+        out = {}
+        p = opts.get("repetition_penalty", 1.0)
+        if not isinstance(p, (int, float)) or isinstance(p, bool) or not p > 0:
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {p}")
+        out["repetition_penalty"] = float(p)
+        n = opts.get("no_repeat_ngram_size", 0)
+        if not isinstance(n, int) or n < 0:
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {n}")
+        out["no_repeat_ngram_size"] = n
+        m, ml = opts.get("min_new_tokens", 0), opts.get("min_length", 0)
+        for name, val in (("min_new_tokens", m), ("min_length", ml)):
+            if not isinstance(val, int) or val < 0:
+                raise ValueError(f"`{name}` has to be a positive integer, but is {val}")
+        out["min_new_tokens"] = max(m, ml - 1)                               # min_length counts the bos token, like max_length
+        es = opts.get("early_stopping", False)
+        if not (isinstance(es, bool) or es == "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es}.")
+        out["early_stopping"] = es if num_beams > 1 else False               # a beam-search switch: greedy search never reads it
+        r = opts.get("num_return_sequences", 1)
+        if not isinstance(r, int) or r < 1:
+            raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {r}")
+        if num_beams <= 1 and r > 1:
+            raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {r}).")
+        if r > max(1, num_beams):
+            raise ValueError(f"`num_return_sequences` ({r}) has to be smaller or equal to `num_beams` ({num_beams}).")
+        out["num_return_sequences"] = r
+        return out
+
     def generate(self, input_values=None, pixel_values=None, padding_mask=None, num_beams=1, max_new_tokens=20, do_sample=False,
                  length_penalty=1.0, return_dict_in_generate=False, **kwargs):
         """transformers' generate() for the two modes the reference's README uses: greedy (num_beams 1) and beam search.
-        -> LongTensor [B][<= 1 + max_new_tokens] starting with bos (CPU), or BeamOutput with `sequences_scores`"""
+        -> LongTensor [B][<= 1 + max_new_tokens] starting with bos (CPU), or BeamOutput with `sequences_scores`
+        With search="device" also repetition_penalty, no_repeat_ngram_size, min_new_tokens / min_length, early_stopping (False, True,
+        "never") and num_return_sequences = n <= num_beams (sequences [B * n][L] clip-major, sequences_scores [B * n]), with
+        transformers' semantics; do_sample, bad_words_ids, per-step scores, beam_indices and logits_processor lists stay refused."""
         if do_sample:
             raise NotImplementedError("sampling is not built (the reference's documented call is deterministic beam search)")
         # transformers' generate() takes dozens of options; the ones that change the search and are not restated here must not be
@@ -114,19 +149,31 @@ class AVHubertForConditionalGeneration:
         neutral = {"use_cache": None, "output_scores": None, "early_stopping": False, "num_return_sequences": 1, "num_beam_groups": 1,
                    "repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "temperature": 1.0, "top_k": None, "top_p": None,
                    "attention_mask": None, "max_length": None}
+        # the options the device search has (csrc/k_avsr_search.hip, rs_avsr_search_opts); the host path refuses them as before
+        device_opts = {"early_stopping", "num_return_sequences", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "min_length"}
+        on_device = self.search == "device"
+        opts = {}
         for k, v in kwargs.items():
+            if on_device and k in device_opts:
+                if v is not None:
+                    opts[k] = v
+                continue
             if k not in neutral:
-                raise TypeError(f"generate(): option `{k}` is not built (greedy and beam search with num_beams, max_new_tokens / max_length, length_penalty are)")
+                hint = ' (search="device" has it)' if k in device_opts else ""
+                raise TypeError(f"generate(): option `{k}` is not built{hint} (greedy and beam search with num_beams, max_new_tokens / max_length, length_penalty are)")
             if neutral[k] is not None and v is not None and v != neutral[k]:
-                raise NotImplementedError(f"generate(): `{k}={v!r}` changes the search and is not built (only {neutral[k]!r})")
-        if self.search == "device" and num_beams > AvsrDevice.MAX_DEVICE_BEAMS:
+                hint = '; search="device" has it' if k in device_opts else ""
+                raise NotImplementedError(f"generate(): `{k}={v!r}` changes the search and is not built (only {neutral[k]!r}{hint})")
+        if on_device and num_beams > AvsrDevice.MAX_DEVICE_BEAMS:
             raise ValueError(f"search='device': num_beams={num_beams} exceeds the device search's limit of {AvsrDevice.MAX_DEVICE_BEAMS} "
                              "(build the model with search='host' for wider beams)")
+        if on_device:
+            opts = self._device_options(opts, int(num_beams))
         enc = self.avhubert(input_values=input_values, pixel_values=pixel_values, padding_mask=padding_mask).last_hidden_state
         mask = padding_mask if padding_mask is not None else np.zeros(enc.shape[:2], np.float32)
         if self.search == "device":
             greedy = num_beams <= 1
-            seq, scores = self.dev.generate(enc, mask, 1 if greedy else int(num_beams), int(max_new_tokens), greedy, float(length_penalty))
+            seq, scores = self.dev.generate(enc, mask, 1 if greedy else int(num_beams), int(max_new_tokens), greedy, float(length_penalty), **opts)
             scores = None if greedy else scores
         elif num_beams <= 1:
             seq, scores = generation.greedy_search(self.dev, enc, mask, int(max_new_tokens)), None

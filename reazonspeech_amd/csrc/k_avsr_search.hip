@@ -34,6 +34,23 @@
 // word non-zero.  A step whose go[step] word says stop returns at once and leaves go[step + 1] zero, so every later step does too.
 // A clip that cannot improve any more keeps extending its running beams until the global stop, as transformers does.
 //
+// OPTIONS (rs_avsr_search_opts; transformers' logits processors and beam-search switches).  Neutral options take the code path
+// above unchanged (the <false> instantiations).  Otherwise, per step and hypothesis row, one byte per token in LDS (K Vp bytes up to
+// MARK_LDS_BYTES, else in the search state) is built from the row's own prefix run_seq[step & 1][0 .. step], bos included:
+//   0 untouched, 1 seen (repetition penalty), 2 banned (the token would complete an n-gram of the prefix, or it is eos while fewer
+//   than min_new_tokens tokens exist).  Every banned n-gram token is also a seen one, so 2 overwrites 1 after a barrier; bytes are
+//   written with plain stores of one value, so no atomics are needed.
+// The processed score of (row, v) is then an O(1) lookup wherever a score is read, in transformers' order (_get_logits_processor):
+//   s = seen ? (s < 0 ? s * penalty : s / penalty) : s;  s = banned ? -inf : s
+// greedy: s is the raw logit, before the argmax.  beam: s = (x[v] - m) - rs_logf(S), i.e. after the log-softmax and before the
+// running score is added; m and S stay those of the raw logits (no renormalisation).  -inf candidates keep the total order (value
+// descending, flat index ascending).
+//   early_stopping 1 (True): lp_fin[j] gets one more term first, (top_lp[j] / den) + (all K slots were finished before ? 1 : 0) * NEG;
+//       the clip adds 1 to a second word go2[step + 1] unless all its K slots are finished now, and a zero go2 word stops the search
+//   early_stopping 2 ("never") with length_penalty > 0: can_improve divides by den_heur = (float)pow(max_new_tokens, length_penalty)
+//       instead of den (host-computed; den_heur == den otherwise)
+//   num_return_sequences n: the finish kernel writes the n best finished slots of every clip, clip-major
+//
 // State buffers ping-pong by step parity: step s reads run_seq / fin_seq [s & 1] and writes [(s + 1) & 1]; positions beyond the
 // ones a step writes still hold pad_token_id from rs_avsr_search_begin.
 #include <math.h>
@@ -45,15 +62,27 @@ namespace {
 constexpr int NT = 256;
 constexpr int MAXK = 8;
 constexpr int LAG = 2;          // rs_avsr_generate: the host runs at most this many steps ahead of the stop word it has read
+constexpr int MARK_LDS_BYTES = 32768;   // the token marks of a clip's K rows live in LDS up to this size, else in the search state
+
+// the options as the kernels see them
+struct OptArgs {
+    float penalty;
+    int ngram, min_new, es_true;
+    int32_t* go2;               // early_stopping True: clips with an unfinished slot, per step (null otherwise)
+    uint8_t* marks;             // [rows][Vp] in the search state, or null: LDS
+};
 
 struct SearchPtrs {
     int32_t *tok, *src, *run_seq, *fin_seq, *fin_len, *is_fin, *can, *last, *go;
     float *run_score, *fin_score;
+    int32_t* go2;
+    uint8_t* marks;
 };
 struct SearchPlan {
-    size_t off_tok, off_src, off_run_seq, off_fin_seq, off_fin_len, off_is_fin, off_can, off_last, off_go, off_run_score, off_fin_score, total;
+    size_t off_tok, off_src, off_run_seq, off_fin_seq, off_fin_len, off_is_fin, off_can, off_last, off_go, off_run_score, off_fin_score, off_go2, off_marks, total;
 };
-SearchPlan search_plan(int B, int K, int max_len) {
+// go2_words / mark_bytes: the regions the options add behind today's layout (0: today's layout and size)
+SearchPlan search_plan(int B, int K, int max_len, size_t go2_words = 0, size_t mark_bytes = 0) {
     SearchPlan p{};
     const size_t R = (size_t)B * K;
     size_t o = 0;
@@ -64,6 +93,8 @@ SearchPlan search_plan(int B, int K, int max_len) {
     p.off_can = take((size_t)B * 4); p.off_last = take((size_t)B * 4);
     p.off_go = take((size_t)(max_len + 1) * 4);
     p.off_run_score = take(R * 4); p.off_fin_score = take(R * 4);
+    p.off_go2 = o; if (go2_words) take(go2_words * 4);
+    p.off_marks = o; if (mark_bytes) take(mark_bytes);
     p.total = o + 256;
     return p;
 }
@@ -74,13 +105,14 @@ SearchPtrs search_ptrs(void* state, const SearchPlan& pl) {
     p.tok = ip(pl.off_tok); p.src = ip(pl.off_src); p.run_seq = ip(pl.off_run_seq); p.fin_seq = ip(pl.off_fin_seq);
     p.fin_len = ip(pl.off_fin_len); p.is_fin = ip(pl.off_is_fin); p.can = ip(pl.off_can); p.last = ip(pl.off_last); p.go = ip(pl.off_go);
     p.run_score = reinterpret_cast<float*>(st + pl.off_run_score); p.fin_score = reinterpret_cast<float*>(st + pl.off_fin_score);
+    p.go2 = ip(pl.off_go2); p.marks = reinterpret_cast<uint8_t*>(st + pl.off_marks);
     return p;
 }
 
 __host__ __device__ inline bool goes_on(bool greedy, uint32_t w) { return greedy ? w != 0 : ((w & 0xffffu) != 0 && (w >> 16) != 0); }
 
 // grid B: the state before step 0
-__global__ __launch_bounds__(NT) void avsr_search_init_kernel(SearchPtrs p, int B, int K, int max_len, int greedy, int bos, int pad) {
+__global__ __launch_bounds__(NT) void avsr_search_init_kernel(SearchPtrs p, int B, int K, int max_len, int greedy, int bos, int pad, int32_t* go2) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const size_t R = (size_t)B * K;
     for (int i = tid; i < K * max_len; i += NT) {
@@ -101,7 +133,10 @@ __global__ __launch_bounds__(NT) void avsr_search_init_kernel(SearchPtrs p, int 
     }
     if (tid == 0) { p.can[b] = 1; p.last[b] = 0; }
     if (b == 0)
-        for (int i = tid; i <= max_len; i += NT) p.go[i] = i == 0 ? (greedy ? B : 0x10001) : 0;
+        for (int i = tid; i <= max_len; i += NT) {
+            p.go[i] = i == 0 ? (greedy ? B : 0x10001) : 0;
+            if (go2) go2[i] = i == 0 ? 1 : 0;
+        }
 }
 
 // (value, index) maximum, equal values: the lower index — over the 256 threads of a workgroup; every thread returns the result
@@ -120,9 +155,42 @@ __device__ __forceinline__ void block_argmax(float& v, int& i, float* sv, int* s
         if (sv[k] > v || (sv[k] == v && si[k] < i)) { v = sv[k]; i = si[k]; }
 }
 
+// the marks of `rows` hypothesis rows (the file's head comment): marks [rows][Vp] bytes, seq [rows][max_len] holds positions 0 .. step
+__device__ void build_marks(uint8_t* marks, const int32_t* seq, int rows, int max_len, int V, int Vp, int step, int eos, const OptArgs& o) {
+    const int tid = threadIdx.x, n = o.ngram;
+    uint32_t* words = reinterpret_cast<uint32_t*>(marks);
+    for (int i = tid; i < rows * (Vp / 4); i += NT) words[i] = 0u;
+    __syncthreads();
+    for (int k = 0; k < rows; ++k)
+        for (int pos = tid; pos <= step; pos += NT) {
+            const int t = seq[(size_t)k * max_len + pos];
+            if ((unsigned)t < (unsigned)V) marks[(size_t)k * Vp + t] = 1;
+        }
+    __syncthreads();
+    if (n > 0 && step + 1 >= n)                          // windows [i, i + n) of the prefix whose first n - 1 tokens equal its last n - 1
+        for (int k = 0; k < rows; ++k) {
+            const int32_t* sq = seq + (size_t)k * max_len;
+            for (int i = tid; i + n - 1 <= step; i += NT) {
+                bool match = true;
+                for (int j = 0; j < n - 1 && match; ++j) match = sq[i + j] == sq[step + 2 - n + j];
+                const int t = sq[i + n - 1];
+                if (match && (unsigned)t < (unsigned)V) marks[(size_t)k * Vp + t] = 2;
+            }
+        }
+    if (step < o.min_new && tid < rows && (unsigned)eos < (unsigned)V) marks[(size_t)tid * Vp + eos] = 2;
+    __syncthreads();
+}
+
+__device__ __forceinline__ float processed(float s, uint8_t mark, float penalty) {
+    if (mark == 1) s = s < 0.0f ? s * penalty : s / penalty;
+    return mark == 2 ? -INFINITY : s;
+}
+
 // grid B (rows): transformers' _sample with do_sample False for one step
+template <bool OPTS>
 __global__ __launch_bounds__(NT) void avsr_greedy_step_kernel(const float* __restrict__ logits, int V, int Vp, int step, int max_len, int eos, int pad,
-                                                              SearchPtrs p) {
+                                                              SearchPtrs p, OptArgs o) {
+    extern __shared__ __align__(16) uint8_t lds_marks[];
     __shared__ float sv[NT / 64];
     __shared__ int si[NT / 64];
     if (p.go[step] == 0) return;
@@ -130,9 +198,18 @@ __global__ __launch_bounds__(NT) void avsr_greedy_step_kernel(const float* __res
     const float* row = logits + (size_t)b * Vp;
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    for (int v = tid; v < V; v += NT) {
-        const float x = row[v];
-        if (x > best) { best = x; bi = v; }
+    if constexpr (OPTS) {
+        uint8_t* marks = o.marks ? o.marks + (size_t)b * Vp : lds_marks;
+        build_marks(marks, p.run_seq + (size_t)b * max_len, 1, max_len, V, Vp, step, eos, o);
+        for (int v = tid; v < V; v += NT) {
+            const float x = processed(row[v], marks[v], o.penalty);
+            if (x > best) { best = x; bi = v; }
+        }
+    } else {
+        for (int v = tid; v < V; v += NT) {
+            const float x = row[v];
+            if (x > best) { best = x; bi = v; }
+        }
     }
     block_argmax(best, bi, sv, si);
     if (tid == 0) {
@@ -150,8 +227,10 @@ __global__ __launch_bounds__(NT) void avsr_greedy_step_kernel(const float* __res
 }
 
 // grid B (clips): transformers' _beam_search for one step (the file's head comment)
+template <bool OPTS>
 __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restrict__ logits, int V, int Vp, int K, int step, int max_len, int eos, float den,
-                                                            int B, SearchPtrs p) {
+                                                            float den_heur, int B, SearchPtrs p, OptArgs o) {
+    extern __shared__ __align__(16) uint8_t lds_marks[];
     __shared__ float red[MAXK][NT];
     __shared__ float row_max[MAXK], row_lse[MAXK], row_run[MAXK];
     __shared__ float top_lp[2 * MAXK], lp_run[2 * MAXK], m_score[3 * MAXK], new_score[MAXK];
@@ -160,9 +239,17 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
     __shared__ float sv[NT / 64];
     __shared__ int si[NT / 64];
     if (!goes_on(false, (uint32_t)p.go[step])) return;
+    if constexpr (OPTS)
+        if (o.go2 && o.go2[step] == 0) return;
     const int b = blockIdx.x, tid = threadIdx.x, cur = step + 1;
     const size_t R = (size_t)B * K;
     const float* lg = logits + (size_t)b * K * Vp;
+    const uint8_t* marks = nullptr;
+    if constexpr (OPTS) {
+        uint8_t* mk = o.marks ? o.marks + (size_t)b * K * Vp : lds_marks;
+        build_marks(mk, p.run_seq + ((size_t)(step & 1) * R + (size_t)b * K) * max_len, K, max_len, V, Vp, step, eos, o);
+        marks = mk;
+    }
 
     // 1. per-row maximum and sum of exponentials
     for (int k = 0; k < K; ++k) {
@@ -203,7 +290,9 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
         for (int k = 0; k < K; ++k) {
             const float m = row_max[k], lse = row_lse[k], run = row_run[k];
             for (int v = tid; v < V; v += NT) {
-                const float val = ((lg[(size_t)k * Vp + v] - m) - lse) + run;
+                float val = (lg[(size_t)k * Vp + v] - m) - lse;
+                if constexpr (OPTS) val = processed(val, marks[(size_t)k * Vp + v], o.penalty);
+                val = val + run;
                 const int idx = k * V + v;
                 const bool after = val < prev_v || (val == prev_v && idx > prev_i);
                 if (after && (val > bv || (val == bv && idx < bi))) { bv = val; bi = idx; }
@@ -240,9 +329,15 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
             old_len[j] = p.fin_len[b * K + j];
             old_fin[j] = p.is_fin[b * K + j];
         }
+        int full = 0;                                     // early_stopping True: all K slots were finished before this step
+        if constexpr (OPTS) {
+            full = o.es_true;
+            for (int j = 0; j < K; ++j) full &= old_fin[j] != 0;
+        }
         for (int j = 0; j < 2 * K; ++j) {
             just[j] = ends[j] && j < K;
             float f = top_lp[j] / den;
+            if constexpr (OPTS) f = f + (full ? 1.0f : 0.0f) * NEG;
             f = f + (ci ? 0.0f : 1.0f) * NEG;
             f = f + (just[j] ? 0.0f : 1.0f) * NEG;
             m_score[K + j] = f;
@@ -260,11 +355,12 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
             new_score[j] = m_score[w];
             mn = fminf(mn, m_score[w]);
         }
-        const float best_running = lp_run[keep[0]] / den;
-        int any = 0;
+        const float best_running = lp_run[keep[0]] / den_heur;
+        int any = 0, all_fin = 1;
         for (int j = 0; j < K; ++j) {
             const int w = best[j];
             const int nf = w < K ? old_fin[w] : just[w - K];
+            all_fin &= nf != 0;
             p.fin_score[b * K + j] = new_score[j];
             p.fin_len[b * K + j] = w < K ? old_len[w] : cur + 1;
             p.is_fin[b * K + j] = nf;
@@ -279,6 +375,8 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
         p.can[b] = ci_new;
         p.last[b] = cur;
         atomicAdd(&p.go[cur], (ci_new ? 1 : 0) + (all_end ? 0 : 0x10000));
+        if constexpr (OPTS)
+            if (o.go2 && !all_fin) atomicAdd(&o.go2[cur], 1);
     }
     __syncthreads();
     const int32_t* run_s = p.run_seq + ((size_t)(step & 1) * R + (size_t)b * K) * max_len;
@@ -297,21 +395,45 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
     }
 }
 
-// grid B: the result of clip b: its best finished hypothesis (beam) or its row (greedy), from the buffers the last step wrote
-__global__ __launch_bounds__(NT) void avsr_search_finish_kernel(SearchPtrs p, int B, int K, int max_len, int greedy, int32_t* sequences, int32_t* lengths,
-                                                                float* scores) {
+// grid B: the result of clip b: its n_ret best finished hypotheses (beam; slots 0 .. n_ret - 1, output rows b n_ret + j) or its row
+// (greedy, n_ret 1), from the buffers the last step wrote
+__global__ __launch_bounds__(NT) void avsr_search_finish_kernel(SearchPtrs p, int B, int K, int max_len, int greedy, int n_ret, int32_t* sequences,
+                                                                int32_t* lengths, float* scores) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const size_t R = (size_t)B * K;
     const int n = p.last[b];
     const int32_t* src = greedy ? p.run_seq + (size_t)b * max_len : p.fin_seq + ((size_t)(n & 1) * R + (size_t)b * K) * max_len;
-    for (int i = tid; i < max_len; i += NT) sequences[(size_t)b * max_len + i] = src[i];
-    if (tid == 0) {
-        lengths[b] = p.fin_len[(size_t)b * K];
-        if (scores) scores[b] = greedy ? 0.0f : p.fin_score[(size_t)b * K];
+    for (int i = tid; i < n_ret * max_len; i += NT) sequences[(size_t)b * n_ret * max_len + i] = src[i];
+    if (tid < n_ret) {
+        lengths[b * n_ret + tid] = p.fin_len[(size_t)b * K + tid];
+        if (scores) scores[b * n_ret + tid] = greedy ? 0.0f : p.fin_score[(size_t)b * K + tid];
     }
 }
 
-int check_search(rs_ctx* ctx, const rs_avsr_search* sp, int B, int vocab, const void* state, size_t state_bytes, const char* what, SearchPlan* pl) {
+// the options of a call: neutral for a null pointer; what the kernels and the state layout need of them
+struct Opts {
+    rs_avsr_search_opts o{1.0f, 0, 0, 0, 1};
+    bool kernel() const { return o.repetition_penalty != 1.0f || o.no_repeat_ngram_size > 0 || o.min_new_tokens > 0 || o.early_stopping == 1; }
+    bool es_true() const { return o.early_stopping == 1; }
+};
+size_t mark_bytes(bool opts_kernel, int B, int K, int vocab) {       // marks kept in the state: only where a clip's K rows exceed the LDS share
+    const size_t Vp = (size_t)(vocab + 3) / 4 * 4;
+    return opts_kernel && (size_t)K * Vp > (size_t)MARK_LDS_BYTES ? (size_t)B * K * Vp : 0;
+}
+SearchPlan search_plan_opts(const Opts& op, int B, int K, int max_len, int vocab) {
+    return search_plan(B, K, max_len, op.es_true() ? (size_t)max_len + 1 : 0, mark_bytes(op.kernel(), B, K, vocab));
+}
+OptArgs opt_args(const Opts& op, const SearchPtrs& p, const SearchPlan& pl) {
+    OptArgs a;
+    a.penalty = op.o.repetition_penalty; a.ngram = op.o.no_repeat_ngram_size; a.min_new = op.o.min_new_tokens; a.es_true = op.es_true() ? 1 : 0;
+    a.go2 = op.es_true() ? p.go2 : nullptr;
+    a.marks = pl.off_marks + 256 < pl.total ? p.marks : nullptr;
+    return a;
+}
+
+// vocab 0: a call that touches the front of the state only (rows, peek, finish): the marks do not count towards the size it needs
+int check_search(rs_ctx* ctx, const rs_avsr_search* sp, const rs_avsr_search_opts* opts, int B, int vocab, const void* state, size_t state_bytes,
+                 const char* what, SearchPlan* pl, Opts* op) {
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
     if (!d) return rs_fail(ctx, RS_EINVAL, "%s: defined for an avsr context (rs_avsr_create) only", what);
     if (!sp || !state) return rs_fail(ctx, RS_EINVAL, "%s: null pointer", what);
@@ -321,56 +443,103 @@ int check_search(rs_ctx* ctx, const rs_avsr_search* sp, int B, int vocab, const 
     if (1 + (long long)sp->max_new_tokens > d->max_positions)
         return rs_fail(ctx, RS_EINVAL, "%s: 1 + max_new_tokens = %lld positions exceed max_target_positions %d", what, 1 + (long long)sp->max_new_tokens, d->max_positions);
     if (B <= 0 || B > 32767) return rs_fail(ctx, RS_EINVAL, "%s: %d clips (1 .. 32767)", what, B);
-    if (vocab < 4 || (long long)vocab * sp->beams > 0x7fffffffLL) return rs_fail(ctx, RS_EINVAL, "%s: vocabulary %d (at least 4)", what, vocab);
-    *pl = search_plan(B, sp->beams, 1 + sp->max_new_tokens);
+    const bool front = vocab == 0;
+    if (!front && (vocab < 4 || (long long)vocab * sp->beams > 0x7fffffffLL)) return rs_fail(ctx, RS_EINVAL, "%s: vocabulary %d (at least 4)", what, vocab);
+    if (opts) {
+        op->o = *opts;
+        if (!(opts->repetition_penalty > 0.0f)) return rs_fail(ctx, RS_EINVAL, "%s: repetition_penalty must be > 0, got %g", what, (double)opts->repetition_penalty);
+        if (opts->no_repeat_ngram_size < 0 || opts->min_new_tokens < 0)
+            return rs_fail(ctx, RS_EINVAL, "%s: no_repeat_ngram_size %d / min_new_tokens %d must not be negative", what, opts->no_repeat_ngram_size, opts->min_new_tokens);
+        if (opts->early_stopping < 0 || opts->early_stopping > 2) return rs_fail(ctx, RS_EINVAL, "%s: early_stopping %d (0 False, 1 True, 2 never)", what, opts->early_stopping);
+        if (opts->num_return_sequences < 1 || opts->num_return_sequences > sp->beams)
+            return rs_fail(ctx, RS_EINVAL, "%s: num_return_sequences %d outside 1..beams (%d)", what, opts->num_return_sequences, sp->beams);
+        if (sp->greedy && opts->num_return_sequences > 1) return rs_fail(ctx, RS_EINVAL, "%s: greedy search returns one sequence per clip, got num_return_sequences %d", what, opts->num_return_sequences);
+        if (sp->greedy) op->o.early_stopping = 0;          // a beam-search switch: _sample never reads it
+    }
+    *pl = search_plan_opts(*op, B, sp->beams, 1 + sp->max_new_tokens, front ? 4 : vocab);
     if (state_bytes < pl->total) return rs_fail(ctx, RS_EWORKSPACE, "%s: state %zu < %zu", what, state_bytes, pl->total);
     return RS_OK;
 }
 
-}  // namespace
-
-extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len) {
-    if (!rs_avsr_dims_of(ctx) || B <= 0 || beams < 1 || beams > MAXK || max_len < 2) return 0;
-    return search_plan(B, beams, max_len).total;
+bool opts_ok_for_bytes(const rs_avsr_search_opts* o, int beams) {
+    return !o || (o->repetition_penalty > 0.0f && o->no_repeat_ngram_size >= 0 && o->min_new_tokens >= 0 && o->early_stopping >= 0 && o->early_stopping <= 2 &&
+                  o->num_return_sequences >= 1 && o->num_return_sequences <= beams);
 }
 
-extern "C" int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes, void* stream) {
+}  // namespace
+
+extern "C" size_t rs_avsr_search_state_bytes_opts(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts) {
+    if (!rs_avsr_dims_of(ctx) || B <= 0 || beams < 1 || beams > MAXK || max_len < 2 || vocab < 4 || !opts_ok_for_bytes(opts, beams)) return 0;
+    Opts op;
+    if (opts) op.o = *opts;
+    return search_plan_opts(op, B, beams, max_len, vocab).total;
+}
+extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len) {
+    return rs_avsr_search_state_bytes_opts(ctx, B, beams, max_len, 4, nullptr);
+}
+
+extern "C" int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
+                                         size_t state_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
     SearchPlan pl;
-    const int rc = check_search(ctx, search, B, vocab, state, state_bytes, "rs_avsr_search_begin", &pl);
+    Opts op;
+    const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_begin", &pl, &op);
     if (rc != RS_OK) return rc;
-    hipLaunchKernelGGL(avsr_search_init_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, search_ptrs(state, pl), B, search->beams, 1 + search->max_new_tokens,
-                       search->greedy ? 1 : 0, search->bos_token_id, search->pad_token_id);
+    const SearchPtrs p = search_ptrs(state, pl);
+    hipLaunchKernelGGL(avsr_search_init_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
+                       search->greedy ? 1 : 0, search->bos_token_id, search->pad_token_id, op.es_true() ? p.go2 : nullptr);
     RS_CHECK_LAUNCH(ctx, "avsr search begin");
     return RS_OK;
 }
+extern "C" int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes, void* stream) {
+    return rs_avsr_search_begin_opts(ctx, search, nullptr, B, vocab, state, state_bytes, stream);
+}
 
-extern "C" int rs_avsr_search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes,
-                                   void* stream) {
+extern "C" int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B,
+                                        int vocab, void* state, size_t state_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
     SearchPlan pl;
-    const int rc = check_search(ctx, search, B, vocab, state, state_bytes, "rs_avsr_search_step", &pl);
+    Opts op;
+    const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_step", &pl, &op);
     if (rc != RS_OK) return rc;
     if (!logits || step < 0 || step >= search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_step: bad argument (step %d of %d)", step, search->max_new_tokens);
     const int max_len = 1 + search->max_new_tokens, Vp = (vocab + 3) / 4 * 4;
     const SearchPtrs p = search_ptrs(state, pl);
+    const OptArgs oa = opt_args(op, p, pl);
+    const bool ok = op.kernel();
+    // the marks of a workgroup's rows: dynamic LDS unless they live in the state
+    const size_t lds = ok && !oa.marks ? (size_t)(search->greedy ? 1 : search->beams) * Vp : 0;
     if (search->greedy) {
-        hipLaunchKernelGGL(avsr_greedy_step_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, logits, vocab, Vp, step, max_len, search->eos_token_id,
-                           search->pad_token_id, p);
+        if (ok)
+            hipLaunchKernelGGL(avsr_greedy_step_kernel<true>, dim3(B), dim3(NT), lds, (hipStream_t)stream, logits, vocab, Vp, step, max_len, search->eos_token_id,
+                               search->pad_token_id, p, oa);
+        else
+            hipLaunchKernelGGL(avsr_greedy_step_kernel<false>, dim3(B), dim3(NT), 0, (hipStream_t)stream, logits, vocab, Vp, step, max_len, search->eos_token_id,
+                               search->pad_token_id, p, oa);
     } else {
         const float den = (float)pow((double)(step + 1), (double)search->length_penalty);
-        hipLaunchKernelGGL(avsr_beam_step_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, logits, vocab, Vp, search->beams, step, max_len, search->eos_token_id,
-                           den, B, p);
+        const float den_heur = op.o.early_stopping == 2 && search->length_penalty > 0.0f ? (float)pow((double)search->max_new_tokens, (double)search->length_penalty) : den;
+        if (ok)
+            hipLaunchKernelGGL(avsr_beam_step_kernel<true>, dim3(B), dim3(NT), lds, (hipStream_t)stream, logits, vocab, Vp, search->beams, step, max_len,
+                               search->eos_token_id, den, den_heur, B, p, oa);
+        else
+            hipLaunchKernelGGL(avsr_beam_step_kernel<false>, dim3(B), dim3(NT), 0, (hipStream_t)stream, logits, vocab, Vp, search->beams, step, max_len,
+                               search->eos_token_id, den, den_heur, B, p, oa);
     }
     RS_CHECK_LAUNCH(ctx, "avsr search step");
     return RS_OK;
+}
+extern "C" int rs_avsr_search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes,
+                                   void* stream) {
+    return rs_avsr_search_step_opts(ctx, logits, step, search, nullptr, B, vocab, state, state_bytes, stream);
 }
 
 extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, const int32_t** tokens,
                                    const int32_t** src_rows) {
     if (!ctx) return RS_EINVAL;
     SearchPlan pl;
-    const int rc = check_search(ctx, search, B, 4, state, state_bytes, "rs_avsr_search_rows", &pl);
+    Opts op;
+    const int rc = check_search(ctx, search, nullptr, B, 0, state, state_bytes, "rs_avsr_search_rows", &pl, &op);
     if (rc != RS_OK) return rc;
     const SearchPtrs p = search_ptrs(state, pl);
     if (tokens) *tokens = p.tok;
@@ -378,51 +547,62 @@ extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, in
     return RS_OK;
 }
 
-extern "C" int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int step, int32_t* tokens, int32_t* src_rows,
-                                   float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
+extern "C" int rs_avsr_search_peek_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
+                                        int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
     if (!ctx) return RS_EINVAL;
     SearchPlan pl;
-    const int rc = check_search(ctx, search, B, 4, state, state_bytes, "rs_avsr_search_peek", &pl);
+    Opts op;
+    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_peek", &pl, &op);
     if (rc != RS_OK) return rc;
     if (step < 0 || step > search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_peek: step %d of %d", step, search->max_new_tokens);
     const SearchPtrs p = search_ptrs(state, pl);
     const size_t R = (size_t)B * search->beams;
     hipStream_t s = (hipStream_t)stream;
-    uint32_t w = 0;
+    uint32_t w = 0, w2 = 1;
     if (tokens) RS_HIP(ctx, hipMemcpyAsync(tokens, p.tok, R * 4, hipMemcpyDeviceToHost, s));
     if (src_rows) RS_HIP(ctx, hipMemcpyAsync(src_rows, p.src, R * 4, hipMemcpyDeviceToHost, s));
     if (run_scores) RS_HIP(ctx, hipMemcpyAsync(run_scores, p.run_score, R * 4, hipMemcpyDeviceToHost, s));
     if (fin_scores) RS_HIP(ctx, hipMemcpyAsync(fin_scores, p.fin_score, R * 4, hipMemcpyDeviceToHost, s));
     RS_HIP(ctx, hipMemcpyAsync(&w, p.go + step, 4, hipMemcpyDeviceToHost, s));
+    if (op.es_true()) RS_HIP(ctx, hipMemcpyAsync(&w2, p.go2 + step, 4, hipMemcpyDeviceToHost, s));
     RS_HIP(ctx, hipStreamSynchronize(s));
-    if (goes_on_out) *goes_on_out = goes_on(search->greedy != 0, w) ? 1 : 0;
+    if (goes_on_out) *goes_on_out = goes_on(search->greedy != 0, w) && w2 != 0 ? 1 : 0;
     return RS_OK;
 }
+extern "C" int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int step, int32_t* tokens, int32_t* src_rows,
+                                   float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
+    return rs_avsr_search_peek_opts(ctx, search, nullptr, B, state, state_bytes, step, tokens, src_rows, run_scores, fin_scores, goes_on_out, stream);
+}
 
-extern "C" int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int32_t* sequences, int32_t* lengths,
-                                     float* scores, void* stream) {
+extern "C" int rs_avsr_search_finish_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
+                                          int32_t* sequences, int32_t* lengths, float* scores, void* stream) {
     if (!ctx) return RS_EINVAL;
     SearchPlan pl;
-    const int rc = check_search(ctx, search, B, 4, state, state_bytes, "rs_avsr_search_finish", &pl);
+    Opts op;
+    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_finish", &pl, &op);
     if (rc != RS_OK) return rc;
     if (!sequences || !lengths) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_finish: null pointer");
     hipLaunchKernelGGL(avsr_search_finish_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, search_ptrs(state, pl), B, search->beams, 1 + search->max_new_tokens,
-                       search->greedy ? 1 : 0, sequences, lengths, scores);
+                       search->greedy ? 1 : 0, op.o.num_return_sequences, sequences, lengths, scores);
     RS_CHECK_LAUNCH(ctx, "avsr search finish");
     RS_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
     return RS_OK;
+}
+extern "C" int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int32_t* sequences, int32_t* lengths,
+                                     float* scores, void* stream) {
+    return rs_avsr_search_finish_opts(ctx, search, nullptr, B, state, state_bytes, sequences, lengths, scores, stream);
 }
 
 // ---- generate(): decoder step + search step per token, the stop word read LAG steps behind ------------------------------------------
 namespace {
 struct GenPlan { size_t off_dec, off_search, off_logits, total; };
-GenPlan gen_plan(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
+GenPlan gen_plan(const rs_ctx* ctx, int B, int T, int beams, int max_len, const Opts& op) {
     GenPlan g{};
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
     const size_t dec = rs_avsr_decoder_state_bytes(ctx, B, T, beams, max_len);
     g.off_dec = 0;
     g.off_search = rs_align(dec);
-    g.off_logits = g.off_search + rs_align(search_plan(B, beams, max_len).total);
+    g.off_logits = g.off_search + rs_align(search_plan_opts(op, B, beams, max_len, d->vocab_size).total);
     g.total = g.off_logits + rs_align((size_t)B * beams * ((d->vocab_size + 3) / 4 * 4) * 4) + 256;
     return g;
 }
@@ -437,24 +617,31 @@ struct StopWatch {              // pinned words the go[] entries are copied to, 
 };
 }  // namespace
 
+extern "C" size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts) {
+    if (!rs_avsr_dims_of(ctx) || B <= 0 || T <= 0 || beams < 1 || beams > MAXK || max_len < 2 || !opts_ok_for_bytes(opts, beams)) return 0;
+    Opts op;
+    if (opts) op.o = *opts;
+    return gen_plan(ctx, B, T, beams, max_len, op).total;
+}
 extern "C" size_t rs_avsr_generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
-    if (!rs_avsr_dims_of(ctx) || B <= 0 || T <= 0 || beams < 1 || beams > MAXK || max_len < 2) return 0;
-    return gen_plan(ctx, B, T, beams, max_len).total;
+    return rs_avsr_generate_state_bytes_opts(ctx, B, T, beams, max_len, nullptr);
 }
 
-extern "C" int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search, int32_t* sequences,
-                                int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream) {
+extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
+                                     const rs_avsr_search_opts* opts, int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes,
+                                     void* stream) {
     if (!ctx) return RS_EINVAL;
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
     if (!d) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: defined for an avsr context (rs_avsr_create) only");
     if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_generate");
     if (!search || !enc || !padding_mask || !sequences || !lengths || !state || T <= 0) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: bad argument");
     SearchPlan spl;
-    int rc = check_search(ctx, search, B, d->vocab_size, state, (size_t)-1, "rs_avsr_generate", &spl);
+    Opts op;
+    int rc = check_search(ctx, search, opts, B, d->vocab_size, state, (size_t)-1, "rs_avsr_generate", &spl, &op);
     if (rc != RS_OK) return rc;
     const int K = search->beams, max_len = 1 + search->max_new_tokens;
-    const bool greedy = search->greedy != 0;
-    const GenPlan g = gen_plan(ctx, B, T, K, max_len);
+    const bool greedy = search->greedy != 0, two_words = op.es_true();
+    const GenPlan g = gen_plan(ctx, B, T, K, max_len, op);
     if (state_bytes < g.total) return rs_fail(ctx, RS_EWORKSPACE, "rs_avsr_generate: state %zu < %zu", state_bytes, g.total);
     char* st = reinterpret_cast<char*>(state);
     void* dec_state = st + g.off_dec;
@@ -464,27 +651,32 @@ extern "C" int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padd
     hipStream_t s = (hipStream_t)stream;
     const SearchPtrs p = search_ptrs(s_state, spl);
 
-    StopWatch sw;
-    RS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&sw.words), (size_t)(max_len + 1) * 4, hipHostMallocDefault));
+    StopWatch sw;                // words[i]: go[i]; words[max_len + 1 + i]: go2[i] (early_stopping True)
+    RS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&sw.words), (size_t)(max_len + 1) * 4 * 2, hipHostMallocDefault));
     for (; sw.n_ev < LAG + 1; ++sw.n_ev) RS_HIP(ctx, hipEventCreateWithFlags(&sw.ev[sw.n_ev], hipEventDisableTiming));
 
     rc = rs_avsr_decoder_begin(ctx, enc, B, T, K, max_len, dec_state, dec_bytes, stream);
     if (rc != RS_OK) return rc;
-    rc = rs_avsr_search_begin(ctx, search, B, d->vocab_size, s_state, s_bytes, stream);
+    rc = rs_avsr_search_begin_opts(ctx, search, opts, B, d->vocab_size, s_state, s_bytes, stream);
     if (rc != RS_OK) return rc;
     for (int step = 0; step < search->max_new_tokens; ++step) {
         // greedy rows keep their caches (no re-parenting); beam rows are re-parented by the rows the last selection wrote
         rc = rs_avsr_decoder_step(ctx, p.tok, greedy ? nullptr : p.src, step, padding_mask, B, T, K, max_len, logits, dec_state, dec_bytes, stream);
         if (rc != RS_OK) return rc;
-        rc = rs_avsr_search_step(ctx, logits, step, search, B, d->vocab_size, s_state, s_bytes, stream);
+        rc = rs_avsr_search_step_opts(ctx, logits, step, search, opts, B, d->vocab_size, s_state, s_bytes, stream);
         if (rc != RS_OK) return rc;
         RS_HIP(ctx, hipMemcpyAsync(sw.words + step + 1, p.go + step + 1, 4, hipMemcpyDeviceToHost, s));
+        if (two_words) RS_HIP(ctx, hipMemcpyAsync(sw.words + max_len + 1 + step + 1, p.go2 + step + 1, 4, hipMemcpyDeviceToHost, s));
         RS_HIP(ctx, hipEventRecord(sw.ev[step % (LAG + 1)], s));
         if (step >= LAG) {       // the word of step - LAG: steps issued past the stop return at once and change nothing
             const int e = step - LAG;
             RS_HIP(ctx, hipEventSynchronize(sw.ev[e % (LAG + 1)]));
-            if (!goes_on(greedy, (uint32_t)sw.words[e + 1])) break;
+            if (!goes_on(greedy, (uint32_t)sw.words[e + 1]) || (two_words && sw.words[max_len + 1 + e + 1] == 0)) break;
         }
     }
-    return rs_avsr_search_finish(ctx, search, B, s_state, s_bytes, sequences, lengths, scores, stream);
+    return rs_avsr_search_finish_opts(ctx, search, opts, B, s_state, s_bytes, sequences, lengths, scores, stream);
+}
+extern "C" int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search, int32_t* sequences,
+                                int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream) {
+    return rs_avsr_generate_opts(ctx, enc, padding_mask, B, T, search, nullptr, sequences, lengths, scores, state, state_bytes, stream);
 }

@@ -148,30 +148,42 @@ class AvsrDevice:
         return capi.RsAvsrSearch(int(beams), int(max_new_tokens), cfg.bos_token_id, cfg.eos_token_id, cfg.pad_token_id, int(bool(greedy)),
                                  float(length_penalty))
 
-    def generate(self, enc, padding_mask, beams, max_new_tokens, greedy, length_penalty=1.0):
-        """rs_avsr_generate (csrc/k_avsr_search.hip): decoder steps and the search of every token on the device, one 4-byte stop word
-        read per step.  enc float32 [B][T][d] on the device -> (sequences int64 [B][L] trimmed to the longest result, scores float32
-        [B]), both on the CPU.  No torch kernel runs here: torch allocates, the library computes, the results are copied out."""
+    def search_opts(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, early_stopping=False, num_return_sequences=1):
+        es = capi.RsAvsrSearchOpts.EARLY_STOPPING
+        if not (isinstance(early_stopping, (bool, str)) and early_stopping in es):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping!r}")
+        return capi.RsAvsrSearchOpts(float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), es[early_stopping],
+                                     int(num_return_sequences))
+
+    def generate(self, enc, padding_mask, beams, max_new_tokens, greedy, length_penalty=1.0, **opts):
+        """rs_avsr_generate_opts (csrc/k_avsr_search.hip): decoder steps and the search of every token on the device, one 4-byte stop
+        word read per step (two with early_stopping=True).  enc float32 [B][T][d] on the device -> (sequences int64 [B * n][L] trimmed to
+        the longest result, scores float32 [B * n]), both on the CPU, n = num_return_sequences.  opts: search_opts' keywords; without any
+        the call is rs_avsr_generate's.  No torch kernel runs here: torch allocates, the library computes, the results are copied out."""
         if beams > self.MAX_DEVICE_BEAMS:
             raise ValueError(f"search='device': num_beams={beams} exceeds the device search's limit of {self.MAX_DEVICE_BEAMS} (use search='host')")
         lib, h = self.ctx.lib, self.ctx._h
         B, T = enc.shape[:2]
         max_len = 1 + int(max_new_tokens)
         sp = self.search_params(beams, max_new_tokens, greedy, length_penalty)
+        so = self.search_opts(**opts)
+        n = so.num_return_sequences
+        if n < 1 or n > int(beams) or (greedy and n > 1):
+            raise ValueError(f"search='device': num_return_sequences={n} with {'greedy search' if greedy else f'num_beams={beams}'}")
         enc = enc.contiguous()
         mask = self._dev(padding_mask)
         with torch.cuda.device(self.device):
-            need = int(lib.rs_avsr_generate_state_bytes(h, B, T, int(beams), max_len))
+            need = int(lib.rs_avsr_generate_state_bytes_opts(h, B, T, int(beams), max_len, ctypes.byref(so)))
             if need == 0:
-                raise ValueError(f"search='device': invalid arguments (beams {beams}, max_new_tokens {max_new_tokens})")
+                raise ValueError(f"search='device': invalid arguments (beams {beams}, max_new_tokens {max_new_tokens}, options {opts})")
             if self._gen_state is None or self._gen_state.numel() < need:
                 self._gen_state = None
                 self._gen_state = torch.empty((need,), dtype=torch.uint8, device=self.device)
-            seq = torch.empty((B, max_len), dtype=torch.int32, device=self.device)
-            lens = torch.empty((B,), dtype=torch.int32, device=self.device)
-            scores = torch.empty((B,), dtype=torch.float32, device=self.device)
-            self.ctx.check(lib.rs_avsr_generate(h, capi._ptr(enc), capi._ptr(mask), B, T, ctypes.byref(sp), capi._ptr(seq), capi._ptr(lens),
-                                                capi._ptr(scores), capi._ptr(self._gen_state), self._gen_state.numel(),
-                                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            seq = torch.empty((B * n, max_len), dtype=torch.int32, device=self.device)
+            lens = torch.empty((B * n,), dtype=torch.int32, device=self.device)
+            scores = torch.empty((B * n,), dtype=torch.float32, device=self.device)
+            self.ctx.check(lib.rs_avsr_generate_opts(h, capi._ptr(enc), capi._ptr(mask), B, T, ctypes.byref(sp), ctypes.byref(so), capi._ptr(seq),
+                                                     capi._ptr(lens), capi._ptr(scores), capi._ptr(self._gen_state), self._gen_state.numel(),
+                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
             seq, lens, scores = seq.cpu(), lens.cpu(), scores.cpu()
-        return seq[:, :int(lens.max())].numpy().astype(np.int64), scores.numpy()
+        return seq[:, :max(1, int(lens.max()))].numpy().astype(np.int64), scores.numpy()

@@ -39,6 +39,8 @@ EXPORTS = [
     "rs_avsr_decoder_begin", "rs_avsr_decoder_step",
     "rs_avsr_search_state_bytes", "rs_avsr_search_begin", "rs_avsr_search_step", "rs_avsr_search_rows", "rs_avsr_search_peek",
     "rs_avsr_search_finish", "rs_avsr_generate_state_bytes", "rs_avsr_generate",
+    "rs_avsr_search_state_bytes_opts", "rs_avsr_search_begin_opts", "rs_avsr_search_step_opts", "rs_avsr_search_peek_opts",
+    "rs_avsr_search_finish_opts", "rs_avsr_generate_state_bytes_opts", "rs_avsr_generate_opts",
 ]
 
 
@@ -109,6 +111,19 @@ class RsAvsrSearch(Structure):
         ("beams", c_int32), ("max_new_tokens", c_int32), ("bos_token_id", c_int32), ("eos_token_id", c_int32), ("pad_token_id", c_int32),
         ("greedy", c_int32), ("length_penalty", c_float),
     ]
+
+
+class RsAvsrSearchOpts(Structure):
+    """mirror of `struct rs_avsr_search_opts` (transformers' logits processors and beam-search switches of the device search)"""
+    EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+    _fields_ = [
+        ("repetition_penalty", c_float), ("no_repeat_ngram_size", c_int32), ("min_new_tokens", c_int32), ("early_stopping", c_int32),
+        ("num_return_sequences", c_int32),
+    ]
+
+    @classmethod
+    def neutral(cls):
+        return cls(1.0, 0, 0, 0, 1)
 
 
 class RsError(RuntimeError):
@@ -206,6 +221,16 @@ def load():
     lib.rs_avsr_generate_state_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
     lib.rs_avsr_generate_state_bytes.restype = c_size_t
     lib.rs_avsr_generate.argtypes = [vp, vp, vp, c_int, c_int, sp, vp, vp, vp, vp, c_size_t, vp]
+    op = POINTER(RsAvsrSearchOpts)
+    lib.rs_avsr_search_state_bytes_opts.argtypes = [vp, c_int, c_int, c_int, c_int, op]
+    lib.rs_avsr_search_state_bytes_opts.restype = c_size_t
+    lib.rs_avsr_search_begin_opts.argtypes = [vp, sp, op, c_int, c_int, vp, c_size_t, vp]
+    lib.rs_avsr_search_step_opts.argtypes = [vp, vp, c_int, sp, op, c_int, c_int, vp, c_size_t, vp]
+    lib.rs_avsr_search_peek_opts.argtypes = [vp, sp, op, c_int, vp, c_size_t, c_int, vp, vp, vp, vp, POINTER(c_int32), vp]
+    lib.rs_avsr_search_finish_opts.argtypes = [vp, sp, op, c_int, vp, c_size_t, vp, vp, vp, vp]
+    lib.rs_avsr_generate_state_bytes_opts.argtypes = [vp, c_int, c_int, c_int, c_int, op]
+    lib.rs_avsr_generate_state_bytes_opts.restype = c_size_t
+    lib.rs_avsr_generate_opts.argtypes = [vp, vp, vp, c_int, c_int, sp, op, vp, vp, vp, vp, c_size_t, vp]
     if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
