@@ -512,6 +512,32 @@ int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, in
                 float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC segmentation of a batch (ESPnet family: time stamps of a recognised text) ------------------
+ * Replaces: ctc_segmentation.ctc_segmentation(config, lpz, ground_truth_mat) of the third-party aligner the reference calls
+ * once per window (pkg/espnet-asr/src/ctc.py:60-75), for the default CtcSegmentationParameters — the only ones the reference
+ * sets: blank_transition_cost_zero = False, preamble_transition_cost_zero = True, backtrack_from_max_t = False, max_prob = -1e10.
+ *   probs f32[B*tp_max][ld]     the posteriors rs_encoder_set_ctc_out registered (row pitch ld >= vocabulary; columns past the
+ *                               vocabulary and rows past enc_lens[b] are never read)
+ *   enc_lens i32[B]             frames T of each utterance
+ *   gt i32[B][c_max][S]         prepare_text's ground-truth matrix per utterance: the token that ENDS at symbol c and is s + 1
+ *                               characters long, -1 = none (also the padding rows); gt_lens i32[B] = symbols C of each row
+ *   blank                       column of the blank posterior
+ *   frames i32[B][c_max]        the frame at which each symbol's switch transition was taken; 0 where the host aligner leaves its
+ *                               `timings` at 0 (timings = frames * index_duration, in float64 on the host)
+ *   status i32[B]               0 aligned; 1 more symbols than frames (the aligner's "Audio is shorter than text!"); 2 the
+ *                               backtracking reached frame 0 before symbol 0 (the aligner's IndexError); 3 not alignable here: more
+ *                               than 8000 frames (min_window_size; the aligner's own windowing is not restated), or lengths
+ *                               outside tp_max / c_max
+ * The forward table is float32 with adds and maxima only, in the aligner's order, and the backtracking comparisons are made in
+ * double: frames equal the host aligner's to the last bit (csrc/k_ctc_align.hip).  Asynchronous on `stream`; no host round trip.
+ * Workspace: rs_ctc_align_workspace_bytes (one decision byte per (b, t, c); 0 for invalid arguments), separate from
+ * rs_workspace_bytes.  RS_EINVAL — before anything is enqueued — for S outside 1..8, c_max < 2, a blank outside the row pitch or
+ * a workspace that is too small. */
+size_t rs_ctc_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int c_max, int S);
+int rs_ctc_align(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
+                 const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ---- profiling hooks for bench.py (roofline.achieved) ------------------------------------
  * When enabled, the launcher brackets every launch of the selected kernel class with HIP
  * events on the launch stream.  rs_profile_read synchronises those events and returns the

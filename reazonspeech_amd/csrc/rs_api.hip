@@ -23,6 +23,9 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
                       float* scores, void* workspace, size_t workspace_bytes, hipStream_t s);
+size_t rs_ctc_align_workspace_bytes_impl(int B, int tp_max, int c_max);
+int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
+                      const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* ws, hipStream_t s);
 int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int u_max,
                         int32_t* ids, int32_t* frames, int32_t* n_ids, void* workspace, size_t workspace_bytes,
                         hipStream_t s);
@@ -769,6 +772,27 @@ int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, in
     }
     return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
                             out_cap, ids, frames, n_ids, scores, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t rs_ctc_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int c_max, int S) {
+    if (!ctx || B <= 0 || tp_max < 0 || c_max < 2 || S < 1 || S > 8) return 0;
+    return rs_ctc_align_workspace_bytes_impl(B, tp_max > 0 ? tp_max : 1, c_max);
+}
+
+int rs_ctc_align(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
+                 const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (B < 0 || tp_max < 0) return rs_fail(ctx, RS_EINVAL, "ctc_align: negative size");
+    if (S < 1 || S > 8) return rs_fail(ctx, RS_EINVAL, "ctc_align: the longest token must have 1..8 characters, got S=%d", S);
+    if (c_max < 2) return rs_fail(ctx, RS_EINVAL, "ctc_align: c_max must be >= 2 (a ground truth has at least its two separators), got %d", c_max);
+    if (ld < 1 || blank < 0 || blank >= ld) return rs_fail(ctx, RS_EINVAL, "ctc_align: blank %d outside the row pitch %d", blank, ld);
+    if (B == 0) return RS_OK;
+    if (!probs || !enc_lens || !gt || !gt_lens || !frames || !status || !workspace) return rs_fail(ctx, RS_EINVAL, "ctc_align: null pointer");
+    const size_t need = rs_ctc_align_workspace_bytes(ctx, B, tp_max, c_max, S);
+    if (workspace_bytes < need)
+        return rs_fail(ctx, RS_EINVAL, "ctc_align: workspace of %zu bytes, rs_ctc_align_workspace_bytes asks for %zu", workspace_bytes, need);
+    return rs_ctc_align_impl(ctx, probs, ld, enc_lens, B, tp_max, gt, gt_lens, c_max, S, blank, frames, status, workspace, (hipStream_t)stream);
 }
 
 // ---- profiling -------------------------------------------------------------------------------------

@@ -41,9 +41,12 @@ def find_blank(model, samples, threshold=0.98):
     when nothing qualifies — or on a tie in length — the earliest candidate wins, the first being the empty stretch at the
     very end of the window (nsamples, nsamples)."""
     n_samples = len(samples)
-    post = ctc_decode(model, samples)
-    n_frames = post.shape[0]
-    silent = np.asarray(post[:, model.asr_model.blank_id] > threshold)
+    if getattr(model, "segmentation", "host") == "device":      # only the blank column leaves the device (same numbers)
+        blank_prob = model.blank_posteriors(samples)
+    else:
+        blank_prob = ctc_decode(model, samples)[:, model.asr_model.blank_id]
+    n_frames = blank_prob.shape[0]
+    silent = np.asarray(blank_prob > threshold)
     # run-length pass: +1 where a silent run begins, -1 at the first frame after it
     edges = np.diff(np.concatenate(([0], silent.astype(np.int8), [0])))
     first = np.flatnonzero(edges == 1)
@@ -93,10 +96,19 @@ def find_end_of_segment(text, timings, start):
 def split_text(model, samples, text):
     """[(start sample, end sample, text)] segments of a recognised window (ctc.py:88-101).  When the alignment cannot be
     computed — the reference catches every exception there — the whole window is one segment."""
+    if getattr(model, "segmentation", "host") == "device":
+        return segments_from_timings(model.align_batch([samples], [text])[0], len(samples), text)
     try:
         timings = get_timings(model, samples, text)
     except Exception:
-        return [(0, len(samples), text)]
+        timings = None
+    return segments_from_timings(timings, len(samples), text)
+
+
+def segments_from_timings(timings, n_samples, text):
+    """the segment loop of `split_text` over the timings of one window; `timings` None = no alignment: one whole-window segment"""
+    if timings is None:
+        return [(0, n_samples, text)]
     pieces = []
     head = 0
     while head < len(text):

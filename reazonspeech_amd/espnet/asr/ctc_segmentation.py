@@ -85,6 +85,57 @@ def prepare_text(config, text, char_list=None):
     return mat, utt_begin_indices
 
 
+def pack_ground_truth(config, texts):
+    """The ground truths of a batch for the device aligner (include/rs_asr.h rs_ctc_align; additive — the package has no batch
+    form).  -> (gt int32 [B][c_max][S], gt_lens int32 [B], bounds): row b holds `prepare_text(config, [texts[b]])`'s matrix in
+    its first gt_lens[b] symbols, and bounds[b] is that call's `utt_begin_indices`; everything else is -1.  The character index
+    and the token lengths are built once for the batch, and a span is looked up only when the list has a token of its length
+    (a span that holds a separator is looked up regardless: the separator is replaced by the blank token's text, which changes
+    the length), so the result is prepare_text's entry for entry."""
+    blank = config.char_list[config.blank]
+    space = config.space
+    index = {}
+    for i, c in enumerate(config.char_list):
+        index.setdefault(c, i)
+    S = max(len(c) for c in config.char_list)
+    lengths = sorted({len(c) for c in config.char_list if 0 < len(c) <= S})
+    rows, bounds = [], []
+    for utt in texts:
+        ground_truth = config.start_of_ground_truth
+        if not ground_truth.endswith(space):
+            ground_truth += space
+        begin = len(ground_truth) - 1
+        for char in utt:
+            if char.isspace() and config.replace_spaces_with_blanks:
+                if not ground_truth.endswith(space):
+                    ground_truth += space
+            elif char in index and char not in config.excluded_characters:
+                ground_truth += char
+        if not ground_truth.endswith(space):
+            ground_truth += space
+        bounds.append([begin, len(ground_truth) - 1])
+        n = len(ground_truth)
+        mat = np.full((n, S), -1, np.int32)
+        seps = [k for k, ch in enumerate(ground_truth) if ch == space]
+        for length in lengths:                                   # spans without a separator: only the lengths the list has
+            s = length - 1
+            for i in range(s, n):
+                hit = index.get(ground_truth[i - s:i + 1])
+                if hit is not None:
+                    mat[i, s] = hit
+        for k in seps:                                           # spans that hold a separator: every length, like prepare_text
+            for i in range(k, min(n, k + S)):
+                for s in range(i - k, min(S, i + 1)):
+                    span = ground_truth[i - s:i + 1].replace(space, blank)
+                    mat[i, s] = index.get(span, -1)
+        rows.append(mat)
+    c_max = max((m.shape[0] for m in rows), default=2)
+    gt = np.full((len(rows), c_max, S), -1, np.int32)
+    for b, m in enumerate(rows):
+        gt[b, :m.shape[0]] = m
+    return gt, np.asarray([m.shape[0] for m in rows], np.int32), bounds
+
+
 def ctc_segmentation(config, lpz, ground_truth):
     """lpz float [T][V], ground_truth int64 [C][S] (prepare_text) -> (timings float64 [C], char_probs float64 [T], state_list)"""
     lpz = np.asarray(lpz, np.float32)

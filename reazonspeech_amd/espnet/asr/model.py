@@ -17,6 +17,7 @@ import torch
 from ...runtime.model import AsrModel
 
 PADDING = (16000, 8000)          # transcribe.py:10
+SEGMENTATION_MODES = ("host", "device")
 
 
 class _Ctc:
@@ -48,8 +49,9 @@ class _AsrModelView:
 
 
 class EspnetModel:
-    def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16"):
+    def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host"):
         assert cfg.espnet and len(token_list) == cfg.vocab_size
+        self.segmentation = segmentation
         if beam_size is not None and int(beam_size) > 1:
             cfg = cfg.with_(decoding="beam", beam_size=int(beam_size), beam_score_norm=True, beam_max_pops=int(max_pops))
         self.beam_size = cfg.beam_size if cfg.decoding == "beam" else 1
@@ -148,6 +150,81 @@ class EspnetModel:
     def ctc_posteriors(self, samples):
         """softmax(ctc_lo(encoder(samples))) as float32 numpy [T'][vocab] (ctc.py:12-27 — no padding)"""
         return self._encode_with_ctc(samples)[1][0].numpy()
+
+    # ---- segmentation = "device" -------------------------------------------------------------------------------------
+    @property
+    def segmentation(self):
+        """where the time stamps of a recognised text are computed: "host" = one encoder pass and one run of the numpy aligner
+        per window (ctc.get_timings); "device" = one encoder pass and one rs_ctc_align launch per batch (`align_batch`), and the
+        blank finder reads only the blank column.  Same results; may be changed at any time."""
+        return self._segmentation
+
+    @segmentation.setter
+    def segmentation(self, value):
+        if value not in SEGMENTATION_MODES:
+            raise ValueError(f"segmentation must be one of {SEGMENTATION_MODES}, got {value!r}")
+        self._segmentation = value
+
+    def blank_posteriors(self, samples):
+        """the blank column of `ctc_posteriors(samples)`, float32 numpy [T']: only that column leaves the device"""
+        am = self.am
+        buf = am.stage([np.asarray(samples, np.float32)])
+        col = torch.empty((buf.B * buf.tp_max,), dtype=torch.float32, device=am.device)
+        with torch.cuda.device(am.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            am.ctx.set_ctc_out(None, col)
+            try:
+                am.ctx.frontend(buf.audio, buf.lens, 0, 0, buf.t_max, buf.feats, buf.n_frames, buf.ws, stream)
+                am.ctx.encoder(buf.feats, buf.n_frames, buf.B, buf.t_max, None, buf.joint_enc, buf.enc_lens, buf.ws, stream)
+            finally:
+                am.ctx.set_ctc_out(None, None)
+            n = int(buf.enc_lens.cpu()[0])
+            return col[:n].cpu().numpy()
+
+    def align_batch(self, waves, texts, max_batch=256):
+        """`ctc.get_timings(self, waves[i], texts[i])` for a batch: -> [float64 array, one sample position per kept character of
+        the text, or None where the host path raises (more symbols than frames, ...)].  Per chunk of `max_batch` windows: ONE
+        front-end + encoder pass over the un-padded windows with the posteriors kept on the device, the ground truths packed on
+        the host while it runs, one rs_ctc_align launch, and only the frame indices and the status words copied back."""
+        from . import ctc_segmentation
+        assert len(waves) == len(texts)
+        am, cfg = self.am, self.cfg
+        params = ctc_segmentation.CtcSegmentationParameters(char_list=self.token_list[:-1])     # as ctc.get_timings
+        vp = (cfg.n_logits + 3) // 4 * 4            # row pitch of the posteriors (include/rs_asr.h: rs_encoder_set_ctc_out)
+        out = []
+        for lo in range(0, len(waves), max_batch):
+            chunk = [np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]]
+            buf = am.stage(chunk)
+            B = buf.B
+            with torch.cuda.device(am.device):
+                stream = torch.cuda.current_stream().cuda_stream
+                probs = torch.empty((B * buf.tp_max, vp), dtype=torch.float32, device=am.device)
+                am.ctx.set_ctc_out(probs, None)
+                try:
+                    am.ctx.frontend(buf.audio, buf.lens, 0, 0, buf.t_max, buf.feats, buf.n_frames, buf.ws, stream)
+                    am.ctx.encoder(buf.feats, buf.n_frames, B, buf.t_max, None, buf.joint_enc, buf.enc_lens, buf.ws, stream)
+                finally:
+                    am.ctx.set_ctc_out(None, None)
+                # (the launches above are asynchronous: the packing below runs on the host while the encoder runs)
+                gt, gt_lens, bounds = ctc_segmentation.pack_ground_truth(params, texts[lo:lo + max_batch])
+                c_max, S = gt.shape[1], gt.shape[2]
+                if S > 8:
+                    raise ValueError(f"segmentation='device' aligns token lists whose longest token has at most 8 characters, got {S}")
+                d_gt = torch.from_numpy(gt).to(am.device, non_blocking=True)
+                d_len = torch.from_numpy(gt_lens).to(am.device, non_blocking=True)
+                frames = torch.empty((B, c_max), dtype=torch.int32, device=am.device)
+                status = torch.empty((B,), dtype=torch.int32, device=am.device)
+                ws = torch.empty((am.ctx.ctc_align_workspace_bytes(B, buf.tp_max, c_max, S),), dtype=torch.uint8, device=am.device)
+                am.ctx.ctc_align(probs, buf.enc_lens, B, buf.tp_max, d_gt, d_len, params.blank, frames, status, ws, stream)
+                frames, status, enc_lens = frames.cpu().numpy(), status.cpu().numpy(), buf.enc_lens.cpu().numpy()
+            for b, w in enumerate(chunk):
+                if status[b] != 0:
+                    out.append(None)
+                    continue
+                index_duration = len(w) / (int(enc_lens[b]) + 1)
+                per_symbol = frames[b, :gt_lens[b]].astype(np.float64) * index_duration
+                out.append(per_symbol[bounds[b][0] + 1:bounds[b][1]])
+        return out
 
 
 def synthetic_token_list(vocab_size: int, seed: int = 0):

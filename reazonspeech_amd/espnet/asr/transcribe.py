@@ -11,7 +11,7 @@ import torch
 
 from .audio import norm_audio
 from .interface import TranscribeConfig, TranscribeResult, Segment
-from .ctc import split_text, find_blank
+from .ctc import split_text, find_blank, segments_from_timings
 
 # Hyper parameters (transcribe.py:9-10)
 WINDOW_SECONDS = 20
@@ -21,7 +21,8 @@ PADDING = (16000, 8000)
 CHECKPOINT_ENV = "REAZONSPEECH_ESPNET_CHECKPOINT"
 
 
-def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False):
+def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False,
+               segmentation="host"):
     """Load the ReazonSpeech ESPnet model onto a ROCm GPU (transcribe.py:12-32).
 
     Args:
@@ -39,6 +40,10 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         warning (model.py: EspnetModel._search) — never truncated, and the windows already decoded are kept.
       precision (str): "bf16" = the throughput mode; "fp32" = the float32 parity mode (float32 weights, activations and
         arithmetic end to end — what ESPnet computes on the reference's path; include/rs_asr.h "precision_f32").
+      segmentation (str): where the time stamps of the segments are computed.  "host" (default) = like the reference, one more
+        encoder pass and one run of the CTC aligner in numpy per window; "device" = one batched encoder pass and one
+        rs_ctc_align launch for all windows of a `transcribe_batch` call (`EspnetModel.align_batch`), and the blank finder
+        copies back the blank column only.  The results are the same; stored as `model.segmentation`, may be changed later.
 
     The reference downloads `reazon-research/reazonspeech-espnet-v2` through espnet_model_zoo (:27-31), which an offline box
     cannot do: give `checkpoint=` / the environment variable.  Without a checkpoint this RAISES; seeded synthetic weights of
@@ -46,7 +51,9 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
     $REAZONSPEECH_AMD_SYNTHETIC=1 — and a warning says so."""
     from ...runtime.config import ESPNET_CONFORMER_120M
     from ...runtime.weights_espnet import synthetic_state_dict_espnet
-    from .model import EspnetModel, synthetic_token_list
+    from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES
+    if segmentation not in SEGMENTATION_MODES:
+        raise ValueError(f"segmentation must be one of {SEGMENTATION_MODES}, got {segmentation!r}")
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if str(device).startswith("cpu"):
@@ -59,7 +66,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
             raise FileNotFoundError(f"checkpoint {checkpoint!r} does not exist")
         cfg, sd, tokens = read_espnet(checkpoint)
         return EspnetModel(cfg, sd, tokens, device=device, beam_size=20 if beam_size is None else beam_size, max_pops=max_pops,
-                           precision=precision)
+                           precision=precision, segmentation=segmentation)
     cfg = config or ESPNET_CONFORMER_120M
     if config is None:
         if not (synthetic or os.environ.get("REAZONSPEECH_AMD_SYNTHETIC", "0") not in ("", "0")):
@@ -69,7 +76,8 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         print("[reazonspeech_amd] WARNING: SEEDED SYNTHETIC weights of the 120M Conformer-Transducer architecture were requested "
               "(`synthetic=True` / $REAZONSPEECH_AMD_SYNTHETIC): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
     return EspnetModel(cfg, synthetic_state_dict_espnet(cfg, seed), synthetic_token_list(cfg.vocab_size, seed), device=device,
-                       beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision)
+                       beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision,
+                       segmentation=segmentation)
 
 
 def _windows(model, waveform, window):
@@ -116,7 +124,8 @@ def transcribe(model, audio, config=None):
 
 def transcribe_batch(model, audios, config=None):
     """Additive: many SHORT utterances (each at most one 20 s window) recognised as one batch on the device, then segmented
-    one by one on the host.  An utterance longer than a window goes through `transcribe` on its own."""
+    one by one on the host — or, with `model.segmentation == "device"`, aligned as one batch on the device as well
+    (`EspnetModel.align_batch`).  An utterance longer than a window goes through `transcribe` on its own."""
     if config is None:
         config = TranscribeConfig(verbose=False)
     norm = [norm_audio(a) for a in audios]
@@ -124,9 +133,13 @@ def transcribe_batch(model, audios, config=None):
     short = [i for i, a in enumerate(norm) if len(a.waveform) <= window]
     out = [None] * len(norm)
     texts = model.recognize_batch([norm[i].waveform for i in short]) if short else []
-    for i, asr in zip(short, texts):
-        samples = norm[i].waveform
-        segs = [Segment(start / 16000, end / 16000, text) for start, end, text in split_text(model, samples, asr)]
+    if short and getattr(model, "segmentation", "host") == "device":
+        timings = model.align_batch([norm[i].waveform for i in short], texts)
+        pieces = [segments_from_timings(t, len(norm[i].waveform), asr) for i, asr, t in zip(short, texts, timings)]
+    else:
+        pieces = [split_text(model, norm[i].waveform, asr) for i, asr in zip(short, texts)]
+    for i, asr, segments in zip(short, texts, pieces):
+        segs = [Segment(start / 16000, end / 16000, text) for start, end, text in segments]
         out[i] = TranscribeResult(asr, segs)
     for i, a in enumerate(norm):
         if out[i] is None:

@@ -41,6 +41,7 @@ EXPORTS = [
     "rs_avsr_search_finish", "rs_avsr_generate_state_bytes", "rs_avsr_generate",
     "rs_avsr_search_state_bytes_opts", "rs_avsr_search_begin_opts", "rs_avsr_search_step_opts", "rs_avsr_search_peek_opts",
     "rs_avsr_search_finish_opts", "rs_avsr_generate_state_bytes_opts", "rs_avsr_generate_opts",
+    "rs_ctc_align_workspace_bytes", "rs_ctc_align",
 ]
 
 
@@ -231,6 +232,9 @@ def load():
     lib.rs_avsr_generate_state_bytes_opts.argtypes = [vp, c_int, c_int, c_int, c_int, op]
     lib.rs_avsr_generate_state_bytes_opts.restype = c_size_t
     lib.rs_avsr_generate_opts.argtypes = [vp, vp, vp, c_int, c_int, sp, op, vp, vp, vp, vp, c_size_t, vp]
+    lib.rs_ctc_align_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
+    lib.rs_ctc_align_workspace_bytes.restype = c_size_t
+    lib.rs_ctc_align.argtypes = [vp, vp, c_int, vp, c_int, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, c_size_t, vp]
     if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
@@ -443,6 +447,21 @@ class Context:
         self.check(self.lib.rs_rnnt_mbs(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
                                         MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids), _ptr(frames), _ptr(n_ids),
                                         _ptr(scores), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def ctc_align_workspace_bytes(self, B, tp_max, c_max, S):
+        n = self.lib.rs_ctc_align_workspace_bytes(self._h, int(B), int(tp_max), int(c_max), int(S))
+        if n == 0:
+            raise RsError(RS_EINVAL, f"rs_ctc_align_workspace_bytes: invalid arguments (B={B}, tp_max={tp_max}, c_max={c_max} >= 2, S={S} in 1..8)")
+        return n
+
+    def ctc_align(self, probs, enc_lens, B, tp_max, gt, gt_lens, blank, frames, status, ws, stream, S=None, ws_bytes=None):
+        """CTC segmentation of a batch (include/rs_asr.h rs_ctc_align): probs f32 [B*tp_max][ld], enc_lens i32 [B], gt i32
+        [B][c_max][S] (-1 = no token), gt_lens i32 [B] -> frames i32 [B][c_max], status i32 [B].  Asynchronous on `stream`.
+        `S` / `ws_bytes` default to gt's last extent and the size of `ws`."""
+        assert gt.dim() == 3 and gt.shape[0] == B and frames.shape == (B, gt.shape[1])
+        self.check(self.lib.rs_ctc_align(self._h, _ptr(probs), probs.stride(0), _ptr(enc_lens), int(B), int(tp_max), _ptr(gt), _ptr(gt_lens),
+                                         gt.shape[1], gt.shape[2] if S is None else int(S), int(blank), _ptr(frames), _ptr(status), _ptr(ws),
+                                         ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes), c_void_p(stream)))
 
     # ---- profiling ----
     def profile_enable(self, mask):
