@@ -37,9 +37,12 @@ def tiny(gpu_device):
     return build(ZIPFORMER_TINY, 3)
 
 
-def run(model, waves, taps=True):
+def run(model, waves, taps=True, l_max=None):
+    """l_max: samples the buffer set is sized for (default: the longest utterance) -- it fixes the buffer's t_max and with it the
+    kernel forms the encoder picks (tests/test_gpu_k2_lengths.py)"""
     am, cfg = model.am, model.cfg
-    buf = am.stage(waves, buf=am.new_buffers(len(waves), max(len(w) for w in waves)))
+    l_max = max(int(l_max or 0), max(len(w) for w in waves))
+    buf = am.stage(waves, l_max=l_max, buf=am.new_buffers(len(waves), l_max))
     B = buf.B
     t3 = cfg.embed_frames(buf.t_max)
     emb = torch.zeros((B, t3, cfg.encoder_dim[0]), dtype=torch.float32, device=am.device)
