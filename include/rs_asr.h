@@ -538,6 +538,27 @@ int rs_ctc_align(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_len
                  const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- where to cut a long recording, for a batch of windows (ESPnet family) ---------------------------
+ * Replaces: find_blank(model, samples, threshold) of the reference (pkg/espnet-asr/src/ctc.py:29-58), which scans the blank
+ * posteriors of one 20 s window on the host, for B windows at once and without the column leaving the device.
+ *   blank_prob f32[B*tp_max]    the blank column rs_encoder_set_ctc_out(ctx, NULL, col) registered: row b at b*tp_max with
+ *                               enc_lens[b] valid frames; cells past enc_lens[b] are never read
+ *   enc_lens i32[B]             frames T of each window
+ *   n_samples i32[B]            samples n of each window (what the reference's len(samples) is)
+ *   threshold                   a frame is silent when its blank posterior is > threshold, compared in float32
+ *   cuts i32[B][2]              (start, end) in samples of the longest silent stretch: a maximal run of silent frames
+ *                               [first, after) that a non-silent frame closes (after < T; a run that reaches the last frame is
+ *                               ignored), mapped to samples as (int64)((double)idx / (double)(T + 1) * (double)n) — one double
+ *                               division, one double multiplication, truncation, like Python's int(idx / (frames + 1) * n) —
+ *                               and dropped when its start sample is 0.  The first stretch of the greatest end - start wins if
+ *                               that length is > 0; otherwise, and for T == 0, the result is (n, n).  A row whose enc_lens[b]
+ *                               lies outside 0..tp_max is written (-1, -1) and nothing of it is read.
+ * One wavefront per window, 64 frames per step (csrc/k_ctc_blank.hip).  No workspace; asynchronous on `stream`; no host round
+ * trip.  RS_EINVAL — before anything is enqueued — for a null context or pointer, B <= 0, tp_max <= 0 or a context of the
+ * Zipformer / avsr families (they have no CTC head). */
+int rs_ctc_find_blank(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_lens, const int32_t* n_samples,
+                      int B, int tp_max, float threshold, int32_t* cuts /* [B][2] */, void* stream);
+
 /* ---- profiling hooks for bench.py (roofline.achieved) ------------------------------------
  * When enabled, the launcher brackets every launch of the selected kernel class with HIP
  * events on the launch stream.  rs_profile_read synchronises those events and returns the

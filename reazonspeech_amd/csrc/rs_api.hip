@@ -26,6 +26,8 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
 size_t rs_ctc_align_workspace_bytes_impl(int B, int tp_max, int c_max);
 int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
                       const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* ws, hipStream_t s);
+int rs_ctc_find_blank_impl(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_lens, const int32_t* n_samples, int B, int tp_max,
+                           float threshold, int32_t* cuts, hipStream_t s);
 int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int u_max,
                         int32_t* ids, int32_t* frames, int32_t* n_ids, void* workspace, size_t workspace_bytes,
                         hipStream_t s);
@@ -435,8 +437,13 @@ EncPlan plan_encoder(const rs_ctx* ctx, int B, int t_max) {
         if (chunk > (size_t)B) chunk = (size_t)B;
         while (chunk > 1 && chunk * (size_t)(p.T[1] > 0 ? p.T[1] : 1) > 65535) --chunk;   // grid limit of the conv0 / gather kernels
         p.chunk = (int)chunk;
-        p.off_sa = o; o += rs_align(chunk * per_utt_sa);
-        p.off_col = o; o += gathered ? rs_align(chunk * per_utt_col) : 0;
+        // The extents reserved for sa / col are the chunk's BOUND, not chunk * per-utterance: floor(bound / per_utt) * per_utt goes
+        // up and down with the length, and a caller that allocates for its longest geometry and runs shorter ones in the same
+        // workspace (rs_workspace_bytes is asked once per buffer set) must never be told that a shorter batch needs more.
+        const size_t sa_bound = (size_t)B * per_utt_sa < ((size_t)1 << 31) ? (size_t)B * per_utt_sa : ((size_t)1 << 31);
+        const size_t col_bound = (size_t)B * per_utt_col < ((size_t)1 << 30) ? (size_t)B * per_utt_col : ((size_t)1 << 30);
+        p.off_sa = o; o += rs_align(sa_bound > per_utt_sa ? sa_bound : per_utt_sa);
+        p.off_col = o; o += gathered ? rs_align(col_bound > per_utt_col ? col_bound : per_utt_col) : 0;
         p.col_bytes = gathered ? chunk * per_utt_col : 0;
         p.off_sb = o; o += rs_align((size_t)B * (p.T[2] > 0 ? p.T[2] : 1) * p.F[2] * C * 2);
     } else {
@@ -793,6 +800,15 @@ int rs_ctc_align(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_len
     if (workspace_bytes < need)
         return rs_fail(ctx, RS_EINVAL, "ctc_align: workspace of %zu bytes, rs_ctc_align_workspace_bytes asks for %zu", workspace_bytes, need);
     return rs_ctc_align_impl(ctx, probs, ld, enc_lens, B, tp_max, gt, gt_lens, c_max, S, blank, frames, status, workspace, (hipStream_t)stream);
+}
+
+int rs_ctc_find_blank(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_lens, const int32_t* n_samples, int B, int tp_max,
+                      float threshold, int32_t* cuts, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (ctx->k2 || ctx->avsr) return rs_fail(ctx, RS_EINVAL, "ctc_find_blank: defined for a context with a CTC head (the ESPnet family) only");
+    if (B <= 0 || tp_max <= 0) return rs_fail(ctx, RS_EINVAL, "ctc_find_blank: B and tp_max must be positive, got B=%d tp_max=%d", B, tp_max);
+    if (!blank_prob || !enc_lens || !n_samples || !cuts) return rs_fail(ctx, RS_EINVAL, "ctc_find_blank: null pointer");
+    return rs_ctc_find_blank_impl(ctx, blank_prob, enc_lens, n_samples, B, tp_max, threshold, cuts, (hipStream_t)stream);
 }
 
 // ---- profiling -------------------------------------------------------------------------------------

@@ -80,18 +80,24 @@ class EspnetModel:
     def ids_to_text(self, ids):
         return self.tokens2text([self.token_list[i] for i in ids])
 
-    def recognize_batch(self, waves):
-        """padded like the reference pads each window (np.pad(samples, PADDING), transcribe.py:69) -> [text]"""
-        res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves])
+    def recognize_batch(self, waves, isolate_overflow=False):
+        """padded like the reference pads each window (np.pad(samples, PADDING), transcribe.py:69) -> [text].
+        `isolate_overflow`: see `_search`."""
+        res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves], isolate_overflow=isolate_overflow)
         return [self.ids_to_text(ids) for ids in res.ids]
 
-    def _search(self, waves, max_batch=256):
+    def _search(self, waves, max_batch=256, isolate_overflow=False):
         """the transducer search over a batch of (padded) windows.  Upstream's default beam search has no bound on the
         prediction-network evaluations a frame may take; the device search has one (`max_pops`, which sizes its workspace)
         and reports RS_EOVERFLOW instead of truncating.  The front end and the encoder run ONCE per batch; a decode that hits
         the bound is retried on the same joint projection with 4x and 16x the bound, then done greedily with a warning — one
         pathological window must not abort a whole file — and the result says so (`DecodedBatch.degraded`).  The overrides are
-        arguments of the decode call: nothing is written into the shared model configuration."""
+        arguments of the decode call: nothing is written into the shared model configuration.
+
+        `isolate_overflow` (default off: a chunk that still overflows turns greedy as a whole): the windows of such a chunk are
+        decoded again one by one, each with the retry ladder above, so that only the window that overflows turns greedy and its
+        chunk-mates keep the beam search's result — what a caller that pools unrelated windows into one chunk needs to return
+        what the window-by-window path returns."""
         from ...runtime.capi import RsError, RS_EOVERFLOW
         from ...runtime.model import DecodedBatch
         am = self.am
@@ -113,6 +119,12 @@ class EspnetModel:
                     except RsError as e:
                         if e.code != RS_EOVERFLOW:
                             raise
+                if used is None and isolate_overflow and buf.B > 1:
+                    for w in waves[lo:lo + max_batch]:
+                        one = self._search([w], max_batch=1)
+                        out.ids += one.ids; out.frames += one.frames; out.enc_lens += one.enc_lens
+                        out.scores += one.scores; out.degraded += one.degraded
+                    continue
                 if used is None:
                     import warnings
                     warnings.warn(f"beam search: a frame needed more than {16 * bound} prediction-network evaluations; this batch of windows "
@@ -180,6 +192,37 @@ class EspnetModel:
                 am.ctx.set_ctc_out(None, None)
             n = int(buf.enc_lens.cpu()[0])
             return col[:n].cpu().numpy()
+
+    def _blank_pass(self, buf, col, stream):
+        """front-end + encoder of a staged batch with only the blank column registered (asynchronous on `stream`)"""
+        am = self.am
+        am.ctx.set_ctc_out(None, col)
+        try:
+            am.ctx.frontend(buf.audio, buf.lens, 0, 0, buf.t_max, buf.feats, buf.n_frames, buf.ws, stream)
+            am.ctx.encoder(buf.feats, buf.n_frames, buf.B, buf.t_max, None, buf.joint_enc, buf.enc_lens, buf.ws, stream)
+        finally:
+            am.ctx.set_ctc_out(None, None)
+
+    def find_blank_batch(self, windows, threshold=0.98, max_batch=256):
+        """`ctc.find_blank(self, windows[i], threshold)` for a batch of windows -> [Blank].  Per chunk of `max_batch` windows:
+        ONE front-end + encoder pass with the blank column kept on the device, one rs_ctc_find_blank launch, and only the cut
+        points (B x 2 int32) copied back."""
+        from .ctc import Blank
+        am = self.am
+        out = []
+        for lo in range(0, len(windows), max_batch):
+            chunk = [np.asarray(w, np.float32) for w in windows[lo:lo + max_batch]]
+            buf = am.stage(chunk)
+            B = buf.B
+            with torch.cuda.device(am.device):
+                stream = torch.cuda.current_stream().cuda_stream
+                col = torch.empty((B * buf.tp_max,), dtype=torch.float32, device=am.device)
+                cuts = torch.empty((B, 2), dtype=torch.int32, device=am.device)
+                self._blank_pass(buf, col, stream)
+                am.ctx.ctc_find_blank(col, buf.enc_lens, buf.lens, B, buf.tp_max, threshold, cuts, stream)
+                cuts = cuts.cpu().numpy()
+            out += [Blank(int(s), int(e)) for s, e in cuts]
+        return out
 
     def align_batch(self, waves, texts, max_batch=256):
         """`ctc.get_timings(self, waves[i], texts[i])` for a batch: -> [float64 array, one sample position per kept character of

@@ -43,7 +43,8 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
       segmentation (str): where the time stamps of the segments are computed.  "host" (default) = like the reference, one more
         encoder pass and one run of the CTC aligner in numpy per window; "device" = one batched encoder pass and one
         rs_ctc_align launch for all windows of a `transcribe_batch` call (`EspnetModel.align_batch`), and the blank finder
-        copies back the blank column only.  The results are the same; stored as `model.segmentation`, may be changed later.
+        copies back the blank column only; `transcribe_batch` then takes recordings of any length and finds their cut points
+        on the device too (rs_ctc_find_blank).  The results are the same; stored as `model.segmentation`, may be changed later.
 
     The reference downloads `reazon-research/reazonspeech-espnet-v2` through espnet_model_zoo (:27-31), which an offline box
     cannot do: give `checkpoint=` / the environment variable.  Without a checkpoint this RAISES; seeded synthetic weights of
@@ -95,6 +96,42 @@ def _windows(model, waveform, window):
         offset += len(rest)
 
 
+def plan_windows(lengths, window, find_cuts):
+    """The pieces `_windows` cuts, for many recordings at once: -> [[(offset, n_samples), ...] per recording].
+
+    Only the chain of cut points is sequential — the cut of a window fixes where the next window of the SAME recording begins
+    and nothing else — so the recordings advance in lockstep: a round collects the next window `(recording, offset, window)`
+    of every recording that has more than `window` samples left, asks `find_cuts(requests)` ONCE for their `Blank`s (one
+    batched pass over as many windows as there are such recordings) and cuts each head at int((start + end) / 2).  A recording
+    with at most `window` samples left contributes its rest as its last piece; one of length 0 contributes no piece.  Pure host
+    code: what runs the blank finder is the caller's `find_cuts`."""
+    pieces = [[] for _ in lengths]
+    offsets = [0] * len(lengths)
+    live = []
+    for i, n in enumerate(lengths):
+        if n > window:
+            live.append(i)
+        elif n > 0:
+            pieces[i].append((0, n))
+    while live:
+        gaps = find_cuts([(i, offsets[i], window) for i in live])
+        assert len(gaps) == len(live)
+        still = []
+        for i, gap in zip(live, gaps):
+            head = min(int((gap.start + gap.end) / 2), window)      # `rest[:int((gap.start + gap.end) / 2)]` of `_windows`
+            if head <= 0:
+                raise RuntimeError(f"recording {i}: the cut at offset {offsets[i]} leaves an empty piece")
+            pieces[i].append((offsets[i], head))
+            offsets[i] += head
+            rest = lengths[i] - offsets[i]
+            if rest > window:
+                still.append(i)
+            elif rest > 0:
+                pieces[i].append((offsets[i], rest))
+        live = still
+    return pieces
+
+
 def transcribe(model, audio, config=None):
     """Interface function to transcribe audio data (transcribe.py:34-82).
 
@@ -105,6 +142,10 @@ def transcribe(model, audio, config=None):
 
     Returns:
       TranscribeResult
+
+    The windows are recognised and time-stamped one after the other, like the reference's loop.  With
+    `segmentation="device"`, `transcribe_batch(model, [audio])` returns the same result with the windows of the recording
+    recognised and aligned as one batch.
     """
     config = config or TranscribeConfig()
     audio = norm_audio(audio)
@@ -123,25 +164,58 @@ def transcribe(model, audio, config=None):
 
 
 def transcribe_batch(model, audios, config=None):
-    """Additive: many SHORT utterances (each at most one 20 s window) recognised as one batch on the device, then segmented
-    one by one on the host — or, with `model.segmentation == "device"`, aligned as one batch on the device as well
-    (`EspnetModel.align_batch`).  An utterance longer than a window goes through `transcribe` on its own."""
+    """Additive: many utterances recognised as one batch on the device.
+
+    `model.segmentation == "host"`: SHORT utterances (each at most one 20 s window) are recognised as one batch and segmented
+    one by one on the host; an utterance longer than a window goes through `transcribe` on its own.
+
+    `model.segmentation == "device"`: recordings of ANY length.  The cut points of all long recordings are found in lockstep
+    (`plan_windows`: one batched blank pass and one rs_ctc_find_blank launch per round, `EspnetModel.find_blank_batch`), then
+    the pieces of all recordings — the whole of every short one included — form one pool that is recognised as batches
+    (`recognize_batch`) and aligned as batches (`align_batch`).  The results equal `transcribe`'s, in the caller's order.  A
+    caller with ONE long file passes `[audio]`: its windows are then recognised and aligned as a batch, not one at a time."""
     if config is None:
         config = TranscribeConfig(verbose=False)
     norm = [norm_audio(a) for a in audios]
     window = int(WINDOW_SECONDS * 16000)
+    if getattr(model, "segmentation", "host") == "device":
+        return _transcribe_pooled(model, norm, window)
     short = [i for i, a in enumerate(norm) if len(a.waveform) <= window]
     out = [None] * len(norm)
     texts = model.recognize_batch([norm[i].waveform for i in short]) if short else []
-    if short and getattr(model, "segmentation", "host") == "device":
-        timings = model.align_batch([norm[i].waveform for i in short], texts)
-        pieces = [segments_from_timings(t, len(norm[i].waveform), asr) for i, asr, t in zip(short, texts, timings)]
-    else:
-        pieces = [split_text(model, norm[i].waveform, asr) for i, asr in zip(short, texts)]
+    pieces = [split_text(model, norm[i].waveform, asr) for i, asr in zip(short, texts)]
     for i, asr, segments in zip(short, texts, pieces):
         segs = [Segment(start / 16000, end / 16000, text) for start, end, text in segments]
         out[i] = TranscribeResult(asr, segs)
     for i, a in enumerate(norm):
         if out[i] is None:
             out[i] = transcribe(model, a, TranscribeConfig(verbose=False))
+    return out
+
+
+def _transcribe_pooled(model, norm, window):
+    """`transcribe_batch` with the segmentation on the device: plan the pieces of every recording, then recognise and align
+    the pool of all pieces, longest first so that a chunk of 256 holds pieces of similar length"""
+    waves = [a.waveform for a in norm]
+    plan = plan_windows([len(w) for w in waves], window,
+                        lambda requests: model.find_blank_batch([waves[i][o:o + n] for i, o, n in requests]))
+    pool = [(i, o, n) for i, pieces in enumerate(plan) for o, n in pieces]
+    order = sorted(range(len(pool)), key=lambda k: (-pool[k][2], k))
+    samples = [waves[pool[k][0]][pool[k][1]:pool[k][1] + pool[k][2]] for k in order]
+    texts, timings = [None] * len(pool), [None] * len(pool)
+    if pool:
+        for k, text in zip(order, model.recognize_batch(samples, isolate_overflow=True)):
+            texts[k] = text
+        for k, t in zip(order, model.align_batch(samples, [texts[k] for k in order])):
+            timings[k] = t
+    out, k = [], 0
+    for a, pieces in zip(norm, plan):
+        rate = a.samplerate
+        joined, segments = [], []
+        for offset, n in pieces:
+            joined.append(texts[k])
+            segments.extend(Segment(start_seconds=(offset + first) / rate, end_seconds=(offset + last) / rate, text=piece)
+                            for first, last, piece in segments_from_timings(timings[k], n, texts[k]))
+            k += 1
+        out.append(TranscribeResult("".join(joined), segments))
     return out

@@ -41,7 +41,7 @@ EXPORTS = [
     "rs_avsr_search_finish", "rs_avsr_generate_state_bytes", "rs_avsr_generate",
     "rs_avsr_search_state_bytes_opts", "rs_avsr_search_begin_opts", "rs_avsr_search_step_opts", "rs_avsr_search_peek_opts",
     "rs_avsr_search_finish_opts", "rs_avsr_generate_state_bytes_opts", "rs_avsr_generate_opts",
-    "rs_ctc_align_workspace_bytes", "rs_ctc_align",
+    "rs_ctc_align_workspace_bytes", "rs_ctc_align", "rs_ctc_find_blank",
 ]
 
 
@@ -235,6 +235,7 @@ def load():
     lib.rs_ctc_align_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
     lib.rs_ctc_align_workspace_bytes.restype = c_size_t
     lib.rs_ctc_align.argtypes = [vp, vp, c_int, vp, c_int, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, c_size_t, vp]
+    lib.rs_ctc_find_blank.argtypes = [vp, vp, vp, vp, c_int, c_int, c_float, vp, vp]
     if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
@@ -462,6 +463,13 @@ class Context:
         self.check(self.lib.rs_ctc_align(self._h, _ptr(probs), probs.stride(0), _ptr(enc_lens), int(B), int(tp_max), _ptr(gt), _ptr(gt_lens),
                                          gt.shape[1], gt.shape[2] if S is None else int(S), int(blank), _ptr(frames), _ptr(status), _ptr(ws),
                                          ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes), c_void_p(stream)))
+
+    def ctc_find_blank(self, blank_prob, enc_lens, n_samples, B, tp_max, threshold, cuts, stream):
+        """where to cut each window of a batch (include/rs_asr.h rs_ctc_find_blank): blank_prob f32 [B*tp_max] (the column
+        `set_ctc_out(None, col)` fills), enc_lens / n_samples i32 [B] -> cuts i32 [B][2] = (start, end) in samples.  Asynchronous
+        on `stream`."""
+        self.check(self.lib.rs_ctc_find_blank(self._h, _ptr(blank_prob), _ptr(enc_lens), _ptr(n_samples), int(B), int(tp_max),
+                                              float(threshold), _ptr(cuts), c_void_p(stream)))
 
     # ---- profiling ----
     def profile_enable(self, mask):
