@@ -618,30 +618,28 @@ __global__ __launch_bounds__(256) void avsr_cache_append_kernel(const float* __r
 
 struct AvsrPlan {
     int H1, H2;                      // after the Conv3d (H / 2) and after the max-pool
-    size_t off_a0, off_a1, off_col, off_x, off_y, off_z, off_pool, off_apad, off_fused, off_h, off_t, off_qkv, off_big, total;
+    float *a0, *a1, *col, *x, *y, *z, *pool, *apad, *fused, *h, *t, *qkv, *big;
 };
+constexpr size_t AVSR_SLACK = 256;
 
-AvsrPlan avsr_plan(const rs_avsr& k, int B, int T) {
+AvsrPlan avsr_plan(const rs_avsr& k, int B, int T, rs_arena& a) {
     const rs_avsr_dims& d = k.d;
     AvsrPlan p{};
     p.H1 = d.image_size / 2;
     p.H2 = (p.H1 + 1) / 2;
     const size_t N = (size_t)B * T, dm = d.encoder_embed_dim;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += rs_align(bytes); return at; };
-    p.off_a0 = take(N * p.H1 * p.H1 * 64 * 4);
-    const size_t map = N * p.H2 * p.H2 * 64 * 4;           // the largest trunk map (layer 1); later layers halve the pixels and double the channels
-    p.off_x = take(map); p.off_y = take(map); p.off_z = take(map);
-    p.off_col = take(N * p.H2 * p.H2 * 64 * 4);           // the down-sampling branch's output (at most a stage-1 map)
-    p.off_a1 = take(map / 2);                              // strided rows of a down-sampling convolution
-    p.off_pool = take(N * 512 * 4);
-    p.off_apad = take(N * pad32(d.audio_feat_dim) * 4);
-    p.off_fused = take(N * 2 * dm * 4);
-    p.off_h = take(N * dm * 4);
-    p.off_t = take(N * dm * 4);
-    p.off_qkv = take(N * 3 * dm * 4);
-    p.off_big = take(N * (size_t)std::max(d.encoder_ffn_dim, 2 * d.encoder_embed_dim) * 4);
-    p.total = o + 256;
+    p.a0 = a.take<float>(N * p.H1 * p.H1 * 64);
+    const size_t map = N * p.H2 * p.H2 * 64;               // the largest trunk map (layer 1); later layers halve the pixels and double the channels
+    p.x = a.take<float>(map); p.y = a.take<float>(map); p.z = a.take<float>(map);
+    p.col = a.take<float>(map);                            // the down-sampling branch's output (at most a stage-1 map)
+    p.a1 = a.take<float>(map / 2);                         // strided rows of a down-sampling convolution
+    p.pool = a.take<float>(N * 512);
+    p.apad = a.take<float>(N * pad32(d.audio_feat_dim));
+    p.fused = a.take<float>(N * 2 * dm);
+    p.h = a.take<float>(N * dm);
+    p.t = a.take<float>(N * dm);
+    p.qkv = a.take<float>(N * 3 * dm);
+    p.big = a.take<float>(N * (size_t)std::max(d.encoder_ffn_dim, 2 * d.encoder_embed_dim));
     return p;
 }
 
@@ -791,7 +789,9 @@ extern "C" int rs_avsr_encoder_set_taps(rs_ctx* ctx, float* video, float* fused_
 
 extern "C" size_t rs_avsr_workspace_bytes(const rs_ctx* ctx, int B, int T) {
     if (!ctx || !ctx->avsr || B <= 0 || T <= 0) return 0;
-    return avsr_plan(*ctx->avsr, B, T).total;
+    rs_arena a;
+    avsr_plan(*ctx->avsr, B, T, a);
+    return a.bytes() + AVSR_SLACK;
 }
 
 extern "C" int rs_avsr_encoder_forward(rs_ctx* ctx, const float* input_values, const float* pixel_values, const float* padding_mask, int B, int T, float* enc_out,
@@ -804,13 +804,13 @@ extern "C" int rs_avsr_encoder_forward(rs_ctx* ctx, const float* input_values, c
     rs_avsr& k = *ctx->avsr;
     const rs_avsr_dims& d = k.d;
     hipStream_t s = (hipStream_t)stream;
-    const AvsrPlan pl = avsr_plan(k, B, T);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "avsr encoder: workspace %zu < %zu", workspace_bytes, pl.total);
+    rs_arena arena(workspace);
+    const AvsrPlan pl = avsr_plan(k, B, T, arena);
+    if (workspace_bytes < arena.bytes() + AVSR_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "avsr encoder: workspace %zu < %zu", workspace_bytes, arena.bytes() + AVSR_SLACK);
     if (T > 65535 || B > 65535) return rs_fail(ctx, RS_EINVAL, "avsr encoder: more than 65535 frames / clips per call");
-    char* ws = reinterpret_cast<char*>(workspace);
-    auto fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    float *a0 = fp(pl.off_a0), *x = fp(pl.off_x), *y = fp(pl.off_y), *z = fp(pl.off_z), *col = fp(pl.off_col), *a1 = fp(pl.off_a1), *pool = fp(pl.off_pool);
-    float *apad = fp(pl.off_apad), *fused = fp(pl.off_fused), *h = fp(pl.off_h), *t = fp(pl.off_t), *qkv = fp(pl.off_qkv), *big = fp(pl.off_big);
+    float *a0 = pl.a0, *x = pl.x, *y = pl.y, *z = pl.z, *col = pl.col, *a1 = pl.a1, *pool = pl.pool;
+    float *apad = pl.apad, *fused = pl.fused, *h = pl.h, *t = pl.t, *qkv = pl.qkv, *big = pl.big;
     const int dm = d.encoder_embed_dim, ffn = d.encoder_ffn_dim, H = d.image_size;
     const size_t N = (size_t)B * T;
     const int M = (int)N;
@@ -921,29 +921,30 @@ extern "C" int rs_avsr_encoder_forward(rs_ctx* ctx, const float* input_values, c
 // ---- decoder ----------------------------------------------------------------------------------------------------------------------------
 namespace {
 struct AvsrDecPlan {
-    size_t off_cross, off_cache[2], off_x, off_t, off_u, off_qkv, off_big, off_src, total;
+    float *cross, *cache[2], *x, *t, *u, *qkv, *big;
+    int32_t* src;
 };
-AvsrDecPlan avsr_dec_plan(const rs_avsr& k, int B, int T, int beams, int max_len) {
+constexpr size_t AVSR_DEC_SLACK = 256;
+AvsrDecPlan avsr_dec_plan(const rs_avsr& k, int B, int T, int beams, int max_len, rs_arena& a) {
     const rs_avsr_dims& d = k.d;
     const size_t dm = d.decoder_embed_dim, R = (size_t)B * beams, Ld = d.decoder_layers;
     AvsrDecPlan p{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += rs_align(bytes); return at; };
-    p.off_cross = take(Ld * (size_t)B * T * 2 * dm * 4);
-    p.off_cache[0] = take(Ld * 2 * R * max_len * dm * 4);
-    p.off_cache[1] = take(Ld * 2 * R * max_len * dm * 4);
-    p.off_x = take(R * dm * 4); p.off_t = take(R * dm * 4); p.off_u = take(R * dm * 4);
-    p.off_qkv = take(R * 3 * dm * 4);
-    p.off_big = take(R * (size_t)std::max(d.decoder_ffn_dim, d.decoder_embed_dim) * 4);
-    p.off_src = take(R * 4);
-    p.total = o + 256;
+    p.cross = a.take<float>(Ld * (size_t)B * T * 2 * dm);
+    p.cache[0] = a.take<float>(Ld * 2 * R * max_len * dm);
+    p.cache[1] = a.take<float>(Ld * 2 * R * max_len * dm);
+    p.x = a.take<float>(R * dm); p.t = a.take<float>(R * dm); p.u = a.take<float>(R * dm);
+    p.qkv = a.take<float>(R * 3 * dm);
+    p.big = a.take<float>(R * (size_t)std::max(d.decoder_ffn_dim, d.decoder_embed_dim));
+    p.src = a.take<int32_t>(R);
     return p;
 }
 }  // namespace
 
 extern "C" size_t rs_avsr_decoder_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
     if (!ctx || !ctx->avsr || B <= 0 || T <= 0 || beams <= 0 || max_len <= 0) return 0;
-    return avsr_dec_plan(*ctx->avsr, B, T, beams, max_len).total;
+    rs_arena a;
+    avsr_dec_plan(*ctx->avsr, B, T, beams, max_len, a);
+    return a.bytes() + AVSR_DEC_SLACK;
 }
 
 extern "C" int rs_avsr_decoder_begin(rs_ctx* ctx, const float* enc, int B, int T, int beams, int max_len, void* state, size_t state_bytes, void* stream) {
@@ -953,11 +954,13 @@ extern "C" int rs_avsr_decoder_begin(rs_ctx* ctx, const float* enc, int B, int T
     rs_avsr& k = *ctx->avsr;
     const rs_avsr_dims& d = k.d;
     if (max_len > d.max_positions) return rs_fail(ctx, RS_EINVAL, "avsr decoder: %d positions exceed max_target_positions %d", max_len, d.max_positions);
-    const AvsrDecPlan pl = avsr_dec_plan(k, B, T, beams, max_len);
-    if (state_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "avsr decoder: state %zu < %zu", state_bytes, pl.total);
+    rs_arena arena(state);
+    const AvsrDecPlan pl = avsr_dec_plan(k, B, T, beams, max_len, arena);
+    if (state_bytes < arena.bytes() + AVSR_DEC_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "avsr decoder: state %zu < %zu", state_bytes, arena.bytes() + AVSR_DEC_SLACK);
     hipStream_t s = (hipStream_t)stream;
     const int dm = d.decoder_embed_dim;
-    float* cross = reinterpret_cast<float*>(reinterpret_cast<char*>(state) + pl.off_cross);
+    float* const cross = pl.cross;
     for (int i = 0; i < d.decoder_layers; ++i) {          // cross-attention keys | values of every layer, once per utterance batch
         const rs_avsr_layer& L = k.dec[i];
         const int rc = rs_launch_gemm_f32(ctx, enc, dm, L.ca.kv_w, dm, cross + (size_t)i * B * T * 2 * dm, 2 * dm, B * T, 2 * dm, dm, RS_GEMM_BIAS, L.ca.kv_b, 1.0f, nullptr,
@@ -975,20 +978,20 @@ extern "C" int rs_avsr_decoder_step(rs_ctx* ctx, const int32_t* tokens, const in
         return rs_fail(ctx, RS_EINVAL, "avsr decoder step: bad argument (step %d of %d)", step, max_len);
     rs_avsr& k = *ctx->avsr;
     const rs_avsr_dims& d = k.d;
-    const AvsrDecPlan pl = avsr_dec_plan(k, B, T, beams, max_len);
-    if (state_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "avsr decoder: state %zu < %zu", state_bytes, pl.total);
+    rs_arena arena(state);
+    const AvsrDecPlan pl = avsr_dec_plan(k, B, T, beams, max_len, arena);
+    if (state_bytes < arena.bytes() + AVSR_DEC_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "avsr decoder: state %zu < %zu", state_bytes, arena.bytes() + AVSR_DEC_SLACK);
     hipStream_t s = (hipStream_t)stream;
-    char* st = reinterpret_cast<char*>(state);
-    auto fp = [&](size_t off) { return reinterpret_cast<float*>(st + off); };
     const int dm = d.decoder_embed_dim, R = B * beams, ffn = d.decoder_ffn_dim, Ld = d.decoder_layers, hd = dm / d.decoder_heads, Vp = pad4(d.vocab_size);
     // Self-attention caches: without re-parenting (greedy search: src_rows == NULL at every step) everything lives in buffer 0.  With
     // re-parenting (beam search: src_rows given at every step >= 1) step s writes buffer s & 1: the prefixes [0, s) are gathered from
     // the other buffer by source row first, then this step's keys / values are appended.
     const bool reorder = src_rows != nullptr;
-    float* cache_cur = fp(pl.off_cache[reorder ? (step & 1) : 0]);
+    float* cache_cur = pl.cache[reorder ? (step & 1) : 0];
     if (reorder && step > 0)
-        hipLaunchKernelGGL(avsr_cache_gather_kernel, dim3(step, R, Ld * 2), dim3(256), 0, s, fp(pl.off_cache[(step & 1) ^ 1]), cache_cur, src_rows, R, max_len, dm);
-    float *x = fp(pl.off_x), *t = fp(pl.off_t), *u = fp(pl.off_u), *qkv = fp(pl.off_qkv), *big = fp(pl.off_big), *cross = fp(pl.off_cross);
+        hipLaunchKernelGGL(avsr_cache_gather_kernel, dim3(step, R, Ld * 2), dim3(256), 0, s, pl.cache[(step & 1) ^ 1], cache_cur, src_rows, R, max_len, dm);
+    float *x = pl.x, *t = pl.t, *u = pl.u, *qkv = pl.qkv, *big = pl.big, *cross = pl.cross;
     int rc;
 #define RS_TRY(call) do { rc = (call); if (rc != RS_OK) return rc; } while (0)
     // up to 128 hypothesis rows: the few-rows form (N / 16 workgroups, K cut over the waves); more rows: the tiled kernel

@@ -78,34 +78,19 @@ struct SearchPtrs {
     int32_t* go2;
     uint8_t* marks;
 };
-struct SearchPlan {
-    size_t off_tok, off_src, off_run_seq, off_fin_seq, off_fin_len, off_is_fin, off_can, off_last, off_go, off_run_score, off_fin_score, off_go2, off_marks, total;
-};
-// go2_words / mark_bytes: the regions the options add behind today's layout (0: today's layout and size)
-SearchPlan search_plan(int B, int K, int max_len, size_t go2_words = 0, size_t mark_bytes = 0) {
-    SearchPlan p{};
-    const size_t R = (size_t)B * K;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += rs_align(bytes); return at; };
-    p.off_tok = take(R * 4); p.off_src = take(R * 4);
-    p.off_run_seq = take(2 * R * max_len * 4); p.off_fin_seq = take(2 * R * max_len * 4);
-    p.off_fin_len = take(R * 4); p.off_is_fin = take(R * 4);
-    p.off_can = take((size_t)B * 4); p.off_last = take((size_t)B * 4);
-    p.off_go = take((size_t)(max_len + 1) * 4);
-    p.off_run_score = take(R * 4); p.off_fin_score = take(R * 4);
-    p.off_go2 = o; if (go2_words) take(go2_words * 4);
-    p.off_marks = o; if (mark_bytes) take(mark_bytes);
-    p.total = o + 256;
-    return p;
-}
-SearchPtrs search_ptrs(void* state, const SearchPlan& pl) {
-    char* st = reinterpret_cast<char*>(state);
-    auto ip = [&](size_t off) { return reinterpret_cast<int32_t*>(st + off); };
+constexpr size_t SEARCH_SLACK = 256;
+// the search state's layout.  go2_words / mark_bytes: the pieces the options add behind the plain layout (0: not taken, the pointer is null)
+SearchPtrs search_layout(int B, int K, int max_len, size_t go2_words, size_t mark_bytes, rs_arena& a) {
     SearchPtrs p;
-    p.tok = ip(pl.off_tok); p.src = ip(pl.off_src); p.run_seq = ip(pl.off_run_seq); p.fin_seq = ip(pl.off_fin_seq);
-    p.fin_len = ip(pl.off_fin_len); p.is_fin = ip(pl.off_is_fin); p.can = ip(pl.off_can); p.last = ip(pl.off_last); p.go = ip(pl.off_go);
-    p.run_score = reinterpret_cast<float*>(st + pl.off_run_score); p.fin_score = reinterpret_cast<float*>(st + pl.off_fin_score);
-    p.go2 = ip(pl.off_go2); p.marks = reinterpret_cast<uint8_t*>(st + pl.off_marks);
+    const size_t R = (size_t)B * K;
+    p.tok = a.take<int32_t>(R); p.src = a.take<int32_t>(R);
+    p.run_seq = a.take<int32_t>(2 * R * max_len); p.fin_seq = a.take<int32_t>(2 * R * max_len);
+    p.fin_len = a.take<int32_t>(R); p.is_fin = a.take<int32_t>(R);
+    p.can = a.take<int32_t>(B); p.last = a.take<int32_t>(B);
+    p.go = a.take<int32_t>((size_t)max_len + 1);
+    p.run_score = a.take<float>(R); p.fin_score = a.take<float>(R);
+    p.go2 = go2_words ? a.take<int32_t>(go2_words) : nullptr;
+    p.marks = mark_bytes ? a.take<uint8_t>(mark_bytes) : nullptr;
     return p;
 }
 
@@ -420,20 +405,24 @@ size_t mark_bytes(bool opts_kernel, int B, int K, int vocab) {       // marks ke
     const size_t Vp = (size_t)(vocab + 3) / 4 * 4;
     return opts_kernel && (size_t)K * Vp > (size_t)MARK_LDS_BYTES ? (size_t)B * K * Vp : 0;
 }
-SearchPlan search_plan_opts(const Opts& op, int B, int K, int max_len, int vocab) {
-    return search_plan(B, K, max_len, op.es_true() ? (size_t)max_len + 1 : 0, mark_bytes(op.kernel(), B, K, vocab));
+SearchPtrs search_layout_opts(const Opts& op, int B, int K, int max_len, int vocab, rs_arena& a) {
+    return search_layout(B, K, max_len, op.es_true() ? (size_t)max_len + 1 : 0, mark_bytes(op.kernel(), B, K, vocab), a);
 }
-OptArgs opt_args(const Opts& op, const SearchPtrs& p, const SearchPlan& pl) {
+size_t search_bytes(const Opts& op, int B, int K, int max_len, int vocab) {
+    rs_arena a;
+    search_layout_opts(op, B, K, max_len, vocab, a);
+    return a.bytes() + SEARCH_SLACK;
+}
+OptArgs opt_args(const Opts& op, const SearchPtrs& p) {      // (go2 / marks are null where the layout did not take them)
     OptArgs a;
     a.penalty = op.o.repetition_penalty; a.ngram = op.o.no_repeat_ngram_size; a.min_new = op.o.min_new_tokens; a.es_true = op.es_true() ? 1 : 0;
-    a.go2 = op.es_true() ? p.go2 : nullptr;
-    a.marks = pl.off_marks + 256 < pl.total ? p.marks : nullptr;
+    a.go2 = p.go2;
+    a.marks = p.marks;
     return a;
 }
 
-// vocab 0: a call that touches the front of the state only (rows, peek, finish): the marks do not count towards the size it needs
-int check_search(rs_ctx* ctx, const rs_avsr_search* sp, const rs_avsr_search_opts* opts, int B, int vocab, const void* state, size_t state_bytes,
-                 const char* what, SearchPlan* pl, Opts* op) {
+// the arguments of a search call -> its options.  vocab 0: a call that touches the front of the state only (rows, peek, finish)
+int check_search_args(rs_ctx* ctx, const rs_avsr_search* sp, const rs_avsr_search_opts* opts, int B, int vocab, const void* state, const char* what, Opts* op) {
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
     if (!d) return rs_fail(ctx, RS_EINVAL, "%s: defined for an avsr context (rs_avsr_create) only", what);
     if (!sp || !state) return rs_fail(ctx, RS_EINVAL, "%s: null pointer", what);
@@ -456,8 +445,16 @@ int check_search(rs_ctx* ctx, const rs_avsr_search* sp, const rs_avsr_search_opt
         if (sp->greedy && opts->num_return_sequences > 1) return rs_fail(ctx, RS_EINVAL, "%s: greedy search returns one sequence per clip, got num_return_sequences %d", what, opts->num_return_sequences);
         if (sp->greedy) op->o.early_stopping = 0;          // a beam-search switch: _sample never reads it
     }
-    *pl = search_plan_opts(*op, B, sp->beams, 1 + sp->max_new_tokens, front ? 4 : vocab);
-    if (state_bytes < pl->total) return rs_fail(ctx, RS_EWORKSPACE, "%s: state %zu < %zu", what, state_bytes, pl->total);
+    return RS_OK;
+}
+// the arguments, then the state carved: for a front-only call (vocab 0) the marks do not count towards the size it needs
+int check_search(rs_ctx* ctx, const rs_avsr_search* sp, const rs_avsr_search_opts* opts, int B, int vocab, void* state, size_t state_bytes,
+                 const char* what, SearchPtrs* p, Opts* op) {
+    const int rc = check_search_args(ctx, sp, opts, B, vocab, state, what, op);
+    if (rc != RS_OK) return rc;
+    rs_arena arena(state);
+    *p = search_layout_opts(*op, B, sp->beams, 1 + sp->max_new_tokens, vocab == 0 ? 4 : vocab, arena);
+    if (state_bytes < arena.bytes() + SEARCH_SLACK) return rs_fail(ctx, RS_EWORKSPACE, "%s: state %zu < %zu", what, state_bytes, arena.bytes() + SEARCH_SLACK);
     return RS_OK;
 }
 
@@ -472,7 +469,7 @@ extern "C" size_t rs_avsr_search_state_bytes_opts(const rs_ctx* ctx, int B, int 
     if (!rs_avsr_dims_of(ctx) || B <= 0 || beams < 1 || beams > MAXK || max_len < 2 || vocab < 4 || !opts_ok_for_bytes(opts, beams)) return 0;
     Opts op;
     if (opts) op.o = *opts;
-    return search_plan_opts(op, B, beams, max_len, vocab).total;
+    return search_bytes(op, B, beams, max_len, vocab);
 }
 extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len) {
     return rs_avsr_search_state_bytes_opts(ctx, B, beams, max_len, 4, nullptr);
@@ -481,13 +478,12 @@ extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams
 extern "C" int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
                                          size_t state_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
-    SearchPlan pl;
+    SearchPtrs p;
     Opts op;
-    const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_begin", &pl, &op);
+    const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_begin", &p, &op);
     if (rc != RS_OK) return rc;
-    const SearchPtrs p = search_ptrs(state, pl);
     hipLaunchKernelGGL(avsr_search_init_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
-                       search->greedy ? 1 : 0, search->bos_token_id, search->pad_token_id, op.es_true() ? p.go2 : nullptr);
+                       search->greedy ? 1 : 0, search->bos_token_id, search->pad_token_id, p.go2);
     RS_CHECK_LAUNCH(ctx, "avsr search begin");
     return RS_OK;
 }
@@ -498,14 +494,13 @@ extern "C" int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, i
 extern "C" int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B,
                                         int vocab, void* state, size_t state_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
-    SearchPlan pl;
+    SearchPtrs p;
     Opts op;
-    const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_step", &pl, &op);
+    const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_step", &p, &op);
     if (rc != RS_OK) return rc;
     if (!logits || step < 0 || step >= search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_step: bad argument (step %d of %d)", step, search->max_new_tokens);
     const int max_len = 1 + search->max_new_tokens, Vp = (vocab + 3) / 4 * 4;
-    const SearchPtrs p = search_ptrs(state, pl);
-    const OptArgs oa = opt_args(op, p, pl);
+    const OptArgs oa = opt_args(op, p);
     const bool ok = op.kernel();
     // the marks of a workgroup's rows: dynamic LDS unless they live in the state
     const size_t lds = ok && !oa.marks ? (size_t)(search->greedy ? 1 : search->beams) * Vp : 0;
@@ -537,11 +532,10 @@ extern "C" int rs_avsr_search_step(rs_ctx* ctx, const float* logits, int step, c
 extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, const int32_t** tokens,
                                    const int32_t** src_rows) {
     if (!ctx) return RS_EINVAL;
-    SearchPlan pl;
+    SearchPtrs p;
     Opts op;
-    const int rc = check_search(ctx, search, nullptr, B, 0, state, state_bytes, "rs_avsr_search_rows", &pl, &op);
+    const int rc = check_search(ctx, search, nullptr, B, 0, state, state_bytes, "rs_avsr_search_rows", &p, &op);
     if (rc != RS_OK) return rc;
-    const SearchPtrs p = search_ptrs(state, pl);
     if (tokens) *tokens = p.tok;
     if (src_rows) *src_rows = p.src;
     return RS_OK;
@@ -550,12 +544,11 @@ extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, in
 extern "C" int rs_avsr_search_peek_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                         int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
     if (!ctx) return RS_EINVAL;
-    SearchPlan pl;
+    SearchPtrs p;
     Opts op;
-    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_peek", &pl, &op);
+    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_peek", &p, &op);
     if (rc != RS_OK) return rc;
     if (step < 0 || step > search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_peek: step %d of %d", step, search->max_new_tokens);
-    const SearchPtrs p = search_ptrs(state, pl);
     const size_t R = (size_t)B * search->beams;
     hipStream_t s = (hipStream_t)stream;
     uint32_t w = 0, w2 = 1;
@@ -577,12 +570,12 @@ extern "C" int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, in
 extern "C" int rs_avsr_search_finish_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                           int32_t* sequences, int32_t* lengths, float* scores, void* stream) {
     if (!ctx) return RS_EINVAL;
-    SearchPlan pl;
+    SearchPtrs p;
     Opts op;
-    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_finish", &pl, &op);
+    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_finish", &p, &op);
     if (rc != RS_OK) return rc;
     if (!sequences || !lengths) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_finish: null pointer");
-    hipLaunchKernelGGL(avsr_search_finish_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, search_ptrs(state, pl), B, search->beams, 1 + search->max_new_tokens,
+    hipLaunchKernelGGL(avsr_search_finish_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
                        search->greedy ? 1 : 0, op.o.num_return_sequences, sequences, lengths, scores);
     RS_CHECK_LAUNCH(ctx, "avsr search finish");
     RS_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
@@ -595,15 +588,17 @@ extern "C" int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, 
 
 // ---- generate(): decoder step + search step per token, the stop word read LAG steps behind ------------------------------------------
 namespace {
-struct GenPlan { size_t off_dec, off_search, off_logits, total; };
-GenPlan gen_plan(const rs_ctx* ctx, int B, int T, int beams, int max_len, const Opts& op) {
+// the decoder's state and the search's state as two pieces (each with its own layout and slack inside), then a step's logits
+struct GenPlan { char *dec, *search; float* logits; size_t dec_bytes, search_bytes; };
+constexpr size_t GEN_SLACK = 256;
+GenPlan gen_plan(const rs_ctx* ctx, int B, int T, int beams, int max_len, const Opts& op, rs_arena& a) {
     GenPlan g{};
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
-    const size_t dec = rs_avsr_decoder_state_bytes(ctx, B, T, beams, max_len);
-    g.off_dec = 0;
-    g.off_search = rs_align(dec);
-    g.off_logits = g.off_search + rs_align(search_plan_opts(op, B, beams, max_len, d->vocab_size).total);
-    g.total = g.off_logits + rs_align((size_t)B * beams * ((d->vocab_size + 3) / 4 * 4) * 4) + 256;
+    g.dec_bytes = rs_align(rs_avsr_decoder_state_bytes(ctx, B, T, beams, max_len));
+    g.search_bytes = rs_align(search_bytes(op, B, beams, max_len, d->vocab_size));
+    g.dec = a.take<char>(g.dec_bytes);
+    g.search = a.take<char>(g.search_bytes);
+    g.logits = a.take<float>((size_t)B * beams * ((d->vocab_size + 3) / 4 * 4));
     return g;
 }
 struct StopWatch {              // pinned words the go[] entries are copied to, and the events that say when they have arrived
@@ -621,7 +616,9 @@ extern "C" size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, in
     if (!rs_avsr_dims_of(ctx) || B <= 0 || T <= 0 || beams < 1 || beams > MAXK || max_len < 2 || !opts_ok_for_bytes(opts, beams)) return 0;
     Opts op;
     if (opts) op.o = *opts;
-    return gen_plan(ctx, B, T, beams, max_len, op).total;
+    rs_arena a;
+    gen_plan(ctx, B, T, beams, max_len, op, a);
+    return a.bytes() + GEN_SLACK;
 }
 extern "C" size_t rs_avsr_generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
     return rs_avsr_generate_state_bytes_opts(ctx, B, T, beams, max_len, nullptr);
@@ -635,21 +632,20 @@ extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float*
     if (!d) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: defined for an avsr context (rs_avsr_create) only");
     if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_generate");
     if (!search || !enc || !padding_mask || !sequences || !lengths || !state || T <= 0) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: bad argument");
-    SearchPlan spl;
     Opts op;
-    int rc = check_search(ctx, search, opts, B, d->vocab_size, state, (size_t)-1, "rs_avsr_generate", &spl, &op);
+    int rc = check_search_args(ctx, search, opts, B, d->vocab_size, state, "rs_avsr_generate", &op);
     if (rc != RS_OK) return rc;
     const int K = search->beams, max_len = 1 + search->max_new_tokens;
     const bool greedy = search->greedy != 0, two_words = op.es_true();
-    const GenPlan g = gen_plan(ctx, B, T, K, max_len, op);
-    if (state_bytes < g.total) return rs_fail(ctx, RS_EWORKSPACE, "rs_avsr_generate: state %zu < %zu", state_bytes, g.total);
-    char* st = reinterpret_cast<char*>(state);
-    void* dec_state = st + g.off_dec;
-    void* s_state = st + g.off_search;
-    float* logits = reinterpret_cast<float*>(st + g.off_logits);
-    const size_t dec_bytes = g.off_search, s_bytes = g.off_logits - g.off_search;
+    rs_arena arena(state);
+    const GenPlan g = gen_plan(ctx, B, T, K, max_len, op, arena);
+    if (state_bytes < arena.bytes() + GEN_SLACK) return rs_fail(ctx, RS_EWORKSPACE, "rs_avsr_generate: state %zu < %zu", state_bytes, arena.bytes() + GEN_SLACK);
+    void *const dec_state = g.dec, *const s_state = g.search;
+    float* const logits = g.logits;
+    const size_t dec_bytes = g.dec_bytes, s_bytes = g.search_bytes;
     hipStream_t s = (hipStream_t)stream;
-    const SearchPtrs p = search_ptrs(s_state, spl);
+    rs_arena s_arena(s_state);
+    const SearchPtrs p = search_layout_opts(op, B, K, max_len, d->vocab_size, s_arena);
 
     StopWatch sw;                // words[i]: go[i]; words[max_len + 1 + i]: go2[i] (early_stopping True)
     RS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&sw.words), (size_t)(max_len + 1) * 4 * 2, hipHostMallocDefault));

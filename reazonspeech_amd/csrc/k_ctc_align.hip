@@ -187,15 +187,21 @@ __global__ __launch_bounds__(ALIGN_THREADS) void ctc_align_kernel(const float* _
 
 }  // namespace
 
+// the layout: one back-pointer byte per (utterance, frame, symbol)
+static uint8_t* align_layout(int B, int tp_max, int c_max, rs_arena& a) { return a.take<uint8_t>((size_t)B * (size_t)tp_max * (size_t)c_max); }
+
 size_t rs_ctc_align_workspace_bytes_impl(int B, int tp_max, int c_max) {
-    return rs_align((size_t)B * (size_t)tp_max * (size_t)c_max);
+    rs_arena a;
+    align_layout(B, tp_max, c_max, a);
+    return a.bytes();
 }
 
 int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
                       const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* ws, hipStream_t s) {
     const int cap = c_max < ALIGN_MAX_T ? c_max : ALIGN_MAX_T;           // a row with more symbols than frames is never computed
     const size_t lds = (size_t)2 * cap * sizeof(float);
-    uint8_t* dec = static_cast<uint8_t*>(ws);
+    rs_arena arena(ws);                                                  // (rs_ctc_align compared the size with the query's)
+    uint8_t* dec = align_layout(B, tp_max, c_max, arena);
     rs_prof_begin(ctx, RS_PROF_DECODE, s, (double)B * tp_max * c_max * (3.0 * S + 2.0), (double)B * tp_max * c_max * (4.0 * S + 1.0));
 #define RS_ALIGN_ARGS probs, ld, enc_lens, tp_max, gt, gt_lens, c_max, S, blank, cap, dec, frames, status
     if (c_max <= ALIGN_THREADS) hipLaunchKernelGGL(ctc_align_kernel<1>, dim3(B), dim3(ALIGN_THREADS), lds, s, RS_ALIGN_ARGS);

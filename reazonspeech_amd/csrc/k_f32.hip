@@ -672,11 +672,13 @@ __global__ __launch_bounds__(256) void glu_dwconv_silu_f32_kernel(const float* _
 
 struct EncPlanF32 {
     int T[5], F[5];
-    size_t off_lens, off_sa, off_sb, off_col, off_x, off_hn, off_big, off_ctx, off_posp, off_ctc, total;
+    int32_t* lens;
+    float *sa, *col, *sb, *x, *hn, *big, *ctxb, *posp, *ctc;   // ctc: nullptr without a CTC head
     int chunk;       // Conv2dSubsampling: utterances per pass of conv0 / patch gather / dense-conv GEMM
 };
+constexpr size_t ENC_F32_SLACK = 256;
 
-EncPlanF32 plan_f32(const rs_ctx* ctx, int B, int t_max) {
+EncPlanF32 plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     const rs_dims& d = ctx->d;
     EncPlanF32 p{};
     p.T[0] = t_max; p.F[0] = d.n_mels;
@@ -685,36 +687,33 @@ EncPlanF32 plan_f32(const rs_ctx* ctx, int B, int t_max) {
     const size_t Tp = p.T[d.sub_stages] > 0 ? p.T[d.sub_stages] : 1, M = (size_t)B * Tp;
     size_t widest = (size_t)d.ff_dim;
     if (3 * dm > widest) widest = 3 * dm;
-    size_t o = 0;
-    p.off_lens = o; o += rs_align((size_t)4 * B * 4);
+    p.lens = a.take<int32_t>((size_t)4 * B);
     p.chunk = B;
-    p.off_col = 0;
     if (d.sub_kind == 1) {
-        // the layout of rs_api.hip's plan_encoder with float32 elements: conv0 output and 3x3 patches of ONE chunk of
-        // utterances (patch matrix near 1 GiB), the dense conv's output of the whole batch
-        const size_t T2 = p.T[2] > 0 ? p.T[2] : 1;
-        const size_t per_utt_col = T2 * p.F[2] * 9 * C * 4;
-        size_t chunk = ((size_t)1 << 30) / per_utt_col;
-        if (chunk < 1) chunk = 1;
-        if (chunk > (size_t)B) chunk = (size_t)B;
-        while (chunk > 1 && chunk * T2 > 65535) --chunk;
-        p.chunk = (int)chunk;
-        p.off_sa = o; o += rs_align(chunk * (size_t)(p.T[1] > 0 ? p.T[1] : 1) * p.F[1] * C * 4);
-        p.off_col = o; o += rs_align(chunk * per_utt_col);
-        p.off_sb = o; o += rs_align((size_t)B * T2 * p.F[2] * C * 4);
+        // the pieces of rs_api.hip's plan_encoder with float32 elements: conv0 output and 3x3 patches of ONE chunk of utterances, the
+        // dense conv's output of the whole batch.  Each chunked buffer stays within 1 GiB and is reserved by rs_sub_chunk_rule's
+        // bound, and the chunk is the smaller of the two rules' so that both reserves cover it.  CONDITION for the chunk to be the
+        // patch matrix's alone, as it was before the conv0 buffer had a rule of its own: T1 F1 <= 9 T2 F2.  It holds for 80 mels
+        // (F1 39, F2 19, T1 <= 4 T2: 39 T1 <= 156 T2 < 171 T2); a front end of very few features (F1 3, F2 1 at T1 4) would run
+        // more, smaller passes than the patch rule asks for, with the same results.
+        const size_t T1 = p.T[1] > 0 ? p.T[1] : 1, T2 = p.T[2] > 0 ? p.T[2] : 1;
+        const rs_sub_chunk col = rs_sub_chunk_rule(T2 * p.F[2] * 9 * C * 4, (size_t)1 << 30, T2, B);
+        const rs_sub_chunk sa = rs_sub_chunk_rule(T1 * p.F[1] * C * 4, (size_t)1 << 30, T2, B);
+        p.chunk = std::min(col.chunk, sa.chunk);
+        p.sa = a.take<float>(sa.reserve / 4);
+        p.col = a.take<float>(col.reserve / 4);
+        p.sb = a.take<float>((size_t)B * T2 * p.F[2] * C);
     } else {
         const size_t sub_elems = (size_t)B * p.T[2] * p.F[2] * C;
-        p.off_sa = o; o += rs_align(sub_elems * 4);
-        p.off_sb = o; o += rs_align(sub_elems * 4);
+        p.sa = a.take<float>(sub_elems);
+        p.sb = a.take<float>(sub_elems);
     }
-    p.off_x = o; o += rs_align(M * dm * 4);
-    p.off_hn = o; o += rs_align(M * dm * 4);
-    p.off_big = o; o += rs_align(M * widest * 4);
-    p.off_ctx = o; o += rs_align(M * dm * 4);
-    p.off_posp = o; o += rs_align((2 * Tp) * dm * 4);
-    p.off_ctc = o;
-    if (d.ctc_vocab > 0) o += rs_align(M * (size_t)rs_ctc_pad(d.ctc_vocab) * 4);
-    p.total = o + 256;
+    p.x = a.take<float>(M * dm);
+    p.hn = a.take<float>(M * dm);
+    p.big = a.take<float>(M * widest);
+    p.ctxb = a.take<float>(M * dm);
+    p.posp = a.take<float>((2 * Tp) * dm);
+    p.ctc = d.ctc_vocab > 0 ? a.take<float>(M * (size_t)rs_ctc_pad(d.ctc_vocab)) : nullptr;
     return p;
 }
 
@@ -868,7 +867,11 @@ extern "C" int rs_debug_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, co
     return rs_launch_gemm_f32_skinny(ctx, A, lda, W, ldw, out, ldc, M, N, K, flags, bias, residual, (hipStream_t)stream);
 }
 
-size_t rs_encoder_f32_workspace_bytes(const rs_ctx* ctx, int B, int t_max) { return plan_f32(ctx, B, t_max).total; }
+size_t rs_encoder_f32_workspace_bytes(const rs_ctx* ctx, int B, int t_max) {
+    rs_arena a;
+    plan_f32(ctx, B, t_max, a);
+    return a.bytes() + ENC_F32_SLACK;
+}
 
 // The float32 encoder: the call sequence of rs_encoder_forward (rs_api.hip) with float32 operands everywhere and no
 // fusion that moves a rounding (there is none to move: nothing is rounded below float32).
@@ -876,17 +879,12 @@ int rs_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_fra
                            float* joint_enc, int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const rs_f32_weights& w = ctx->f32;
-    const EncPlanF32 pl = plan_f32(ctx, B, t_max);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "encoder (float32 mode): workspace %zu < %zu", workspace_bytes, pl.total);
-    char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* lens_stage = reinterpret_cast<int32_t*>(ws + pl.off_lens);
-    float* sa = reinterpret_cast<float*>(ws + pl.off_sa);
-    float* sb = reinterpret_cast<float*>(ws + pl.off_sb);
-    float* x = reinterpret_cast<float*>(ws + pl.off_x);
-    float* hn = reinterpret_cast<float*>(ws + pl.off_hn);
-    float* big = reinterpret_cast<float*>(ws + pl.off_big);
-    float* ctxb = reinterpret_cast<float*>(ws + pl.off_ctx);
-    float* posp = reinterpret_cast<float*>(ws + pl.off_posp);
+    rs_arena arena(workspace);
+    const EncPlanF32 pl = plan_f32(ctx, B, t_max, arena);
+    if (workspace_bytes < arena.bytes() + ENC_F32_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "encoder (float32 mode): workspace %zu < %zu", workspace_bytes, arena.bytes() + ENC_F32_SLACK);
+    int32_t* const lens_stage = pl.lens;
+    float *const sa = pl.sa, *const sb = pl.sb, *const x = pl.x, *const hn = pl.hn, *const big = pl.big, *const ctxb = pl.ctxb, *const posp = pl.posp;
     const int C = d.sub_channels, dm = d.d_model, ff = d.ff_dim, S = d.sub_stages;
     const int Tp = pl.T[S], M = B * Tp;
     int rc;
@@ -900,7 +898,7 @@ int rs_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_fra
     if (Tp <= 0) return rs_fail(ctx, RS_EINVAL, "encoder (float32 mode): %d feature frames are too few for the subsampling", t_max);
     if (d.sub_kind == 1) {
         // ESPnet Conv2dSubsampling in float32: conv0 -> 3x3 patches -> the dense conv as one exact-f32 GEMM per chunk of utterances
-        float* col = reinterpret_cast<float*>(ws + pl.off_col);
+        float* const col = pl.col;
         const int T1 = pl.T[1], F1 = pl.F[1], T2 = pl.T[2], F2 = pl.F[2];
         for (int b0 = 0; b0 < B; b0 += pl.chunk) {
             const int bc = B - b0 < pl.chunk ? B - b0 : pl.chunk;
@@ -967,7 +965,7 @@ int rs_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_fra
     RS_TRY(gemm(x, dm, w.jenc_w, dm, joint_enc, d.joint_hidden, M, d.joint_hidden, RS_GEMM_BIAS, ctx->jenc_b, 1.0f, nullptr));
     if (d.ctc_vocab > 0 && (ctx->ctc_probs || ctx->ctc_blank)) {
         const int Vp = rs_ctc_pad(d.ctc_vocab);
-        float* z = ctx->ctc_probs ? ctx->ctc_probs : reinterpret_cast<float*>(ws + pl.off_ctc);
+        float* z = ctx->ctc_probs ? ctx->ctc_probs : pl.ctc;
         RS_TRY(gemm(x, dm, w.ctc_w, dm, z, Vp, M, Vp, RS_GEMM_BIAS, ctx->ctc_b, 1.0f, nullptr));
         RS_TRY(rs_launch_ctc_softmax(ctx, z, M, d.ctc_vocab, Vp, d.blank_id, ctx->ctc_blank, s));
     }

@@ -1062,19 +1062,30 @@ int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const 
 // frames an utterance may look ahead per greedy step (rnnt_tile_kernel<5>): the pmax / pidx scratch is sized for it
 constexpr int LOOKAHEAD_MAX = 8;
 
-size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B) {
+// the greedy decoder's layout (h and c adjacent: one memset clears both)
+static void greedy_layout(const rs_ctx* ctx, int B, rs_arena& a, DecodeState& st) {
     const rs_dims& d = ctx->d;
-    const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden;
-    const int nct = (d.n_logits + 63) / 64;
-    size_t n = 0;
-    n += 4 * rs_align((size_t)L * B * H * 4);
-    n += rs_align((size_t)B * J * 4);
-    n += 7 * rs_align((size_t)B * 4);
-    n += rs_align(64);
-    n += 2 * rs_align((size_t)B * LOOKAHEAD_MAX * nct * 4);
-    const size_t vpad = (size_t)(d.n_logits + 15) / 16 * 16;
-    n += rs_align((size_t)B * J * 2) + rs_align((size_t)B * 4) + rs_align((size_t)B * vpad * 4);   // screened joint
-    return n + 1024;
+    const size_t state = (size_t)d.pred_layers * B * d.pred_hidden, J = d.joint_hidden;
+    const size_t nct = (d.n_logits + 63) / 64, Vpad = (size_t)(d.n_logits + 15) / 16 * 16;
+    st.h = a.take<float>(state); st.c = a.take<float>(state);
+    st.h_tmp = a.take<float>(state); st.c_tmp = a.take<float>(state);
+    st.g = a.take<float>(B * J);
+    st.tcur = a.take<int32_t>(B); st.sym = a.take<int32_t>(B);
+    st.token = a.take<int32_t>(B); st.act = a.take<int32_t>(B);
+    if (ctx->k2_conv_w) st.token2 = a.take<int32_t>(B);
+    st.alive = a.take<int32_t>((size_t)2 * B);
+    st.counters = a.take<int32_t>(16);
+    st.pmax = a.take<float>(B * LOOKAHEAD_MAX * nct); st.pidx = a.take<int32_t>(B * LOOKAHEAD_MAX * nct);
+    st.a16 = a.take<uint16_t>(B * J); st.anorm = a.take<float>(B);     // screened joint
+    st.zapprox = a.take<float>(B * Vpad);
+}
+constexpr size_t GREEDY_SLACK = 1024;
+
+size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B) {
+    rs_arena a;
+    DecodeState st{};
+    greedy_layout(ctx, B, a, st);
+    return a.bytes() + GREEDY_SLACK;
 }
 
 int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int u_max,
@@ -1085,26 +1096,14 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
     if (B <= 0) return RS_OK;
     if (H % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "rnnt: pred_hidden/joint_hidden must be multiples of 128");
     if (L < 1 || L > 4) return rs_fail(ctx, RS_EINVAL, "rnnt: 1..4 LSTM layers supported");
-    if (workspace_bytes < rs_rnnt_workspace_bytes(ctx, B)) return rs_fail(ctx, RS_EWORKSPACE, "rnnt: workspace too small");
-    const int nct = (V + 63) / 64;
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* p = w; w += rs_align(bytes); return p; };
-    DecodeState st;
-    st.g_off = nullptr; st.a_pre = nullptr;
+    rs_arena arena(workspace);
+    DecodeState st{};
+    greedy_layout(ctx, B, arena, st);
+    if (workspace_bytes < arena.bytes() + GREEDY_SLACK) return rs_fail(ctx, RS_EWORKSPACE, "rnnt: workspace too small");
     st.joint_act = d.joint_act;
+    if (ctx->k2_conv_w) st.unk = ctx->k2 ? rs_k2_unk_id(ctx) : -1;
     const size_t state_bytes = (size_t)L * B * H * 4;
-    st.h = (float*)take(state_bytes); st.c = (float*)take(state_bytes);
-    st.h_tmp = (float*)take(state_bytes); st.c_tmp = (float*)take(state_bytes);
-    st.g = (float*)take((size_t)B * J * 4);
-    st.tcur = (int32_t*)take((size_t)B * 4); st.sym = (int32_t*)take((size_t)B * 4);
-    st.token = (int32_t*)take((size_t)B * 4); st.act = (int32_t*)take((size_t)B * 4);
-    if (ctx->k2_conv_w) { st.token2 = (int32_t*)take((size_t)B * 4); st.unk = ctx->k2 ? rs_k2_unk_id(ctx) : -1; }
-    st.alive = (int32_t*)take((size_t)2 * B * 4);
-    st.counters = (int32_t*)take(64);
-    st.pmax = (float*)take((size_t)B * LOOKAHEAD_MAX * nct * 4); st.pidx = (int32_t*)take((size_t)B * LOOKAHEAD_MAX * nct * 4);
-    const int Vpad = (V + 15) / 16 * 16;
-    st.a16 = (uint16_t*)take((size_t)B * J * 2); st.anorm = (float*)take((size_t)B * 4);
-    st.zapprox = (float*)take((size_t)B * Vpad * 4);
+    const int nct = (V + 63) / 64, Vpad = (V + 15) / 16 * 16;
     // the screened joint keeps a row's logits (<= 48 x 64) and a K slice (<= 8 blocks of 16) in registers, J / 32 <= 20 weight fragments
     const bool screen = ctx->decode_screen && ctx->jout_w16 && ctx->jout_wrm && ctx->jout_bpad && ctx->jout_wmax &&
                         J / SPLITK_TILE / 16 <= 8 && J / 32 <= 20;

@@ -354,33 +354,46 @@ __global__ __launch_bounds__(256) void alsd_reorder_kernel(AlsdState as, int pn,
         *reinterpret_cast<float4*>(g_dst + (size_t)row * J + k) = *reinterpret_cast<const float4*>(g_src + (size_t)prow * J + k);
 }
 
-struct AlsdPlan {
-    size_t state, g, rows4, rows_cap4, b4, b_cap4, z, total;
-};
-
-AlsdPlan alsd_plan(const rs_ctx* ctx, int B, int W, int cap) {
+// the search's layout: two ping-pong sets of the prediction-network state (st[k].h / .c / .g; everything else of st[0] and st[1] is
+// shared) and the hypothesis store
+void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, rs_arena& a, DecodeState st[2], AlsdState& as) {
     const rs_dims& d = ctx->d;
-    const size_t rows = (size_t)B * W;
-    AlsdPlan p;
-    p.state = rs_align((size_t)d.pred_layers * rows * d.pred_hidden * 4);
-    p.g = rs_align(rows * d.joint_hidden * 4);
-    p.rows4 = rs_align(rows * 4);
-    p.rows_cap4 = rs_align(rows * (size_t)cap * 4);
-    p.b4 = rs_align((size_t)B * 4);
-    p.b_cap4 = rs_align((size_t)B * cap * 4);
-    p.z = rs_align(rows * (size_t)((d.n_logits + 63) / 64 * 64) * 4);
-    //        h,c x2 sets + h_tmp,c_tmp   g x2   tcur sym token act parent len x2 score x2   alive x2   y,al x2
-    p.total = 6 * p.state + 2 * p.g + 9 * p.rows4 + 2 * p.rows4 + 4 * p.rows_cap4 +
-              //  n_hyp x2, fin_n, fin_norm, fin_score, done    fin_y, fin_al    counters   z
-              6 * p.b4 + 2 * p.b_cap4 + rs_align(64) + p.z + 1024;
-    return p;
+    const size_t rows = (size_t)B * W, state = (size_t)d.pred_layers * rows * d.pred_hidden, J = d.joint_hidden;
+    DecodeState q{};
+    q.joint_act = d.joint_act;
+    q.h = a.take<float>(state); q.c = a.take<float>(state);                  // adjacent: one memset
+    float* h1 = a.take<float>(state); float* c1 = a.take<float>(state);
+    q.h_tmp = a.take<float>(state); q.c_tmp = a.take<float>(state);
+    q.g = a.take<float>(rows * J); float* g1 = a.take<float>(rows * J);
+    q.tcur = a.take<int32_t>(rows); q.sym = a.take<int32_t>(rows);
+    q.token = a.take<int32_t>(rows); q.act = a.take<int32_t>(rows);
+    as.parent = a.take<int32_t>(rows);
+    as.len[0] = a.take<int32_t>(rows); as.len[1] = a.take<int32_t>(rows);
+    as.score[0] = a.take<float>(rows); as.score[1] = a.take<float>(rows);
+    q.alive = a.take<int32_t>(rows); a.take<int32_t>(rows);                  // [2][rows]: the second list follows at pitch `rows`
+    as.y[0] = a.take<int32_t>(rows * cap); as.y[1] = a.take<int32_t>(rows * cap);
+    as.al[0] = a.take<int32_t>(rows * cap); as.al[1] = a.take<int32_t>(rows * cap);
+    as.n_hyp[0] = a.take<int32_t>(B); as.n_hyp[1] = a.take<int32_t>(B);
+    as.fin_n = a.take<int32_t>(B); as.fin_norm = a.take<float>(B); as.fin_score = a.take<float>(B);
+    as.done = a.take<int32_t>(B);
+    as.fin_y = a.take<int32_t>((size_t)B * cap); as.fin_al = a.take<int32_t>((size_t)B * cap);
+    q.counters = a.take<int32_t>(16);
+    q.zapprox = a.take<float>(rows * (size_t)((d.n_logits + 63) / 64 * 64));
+    as.cap = cap;
+    st[0] = st[1] = q;
+    st[1].h = h1; st[1].c = c1; st[1].g = g1;
 }
+constexpr size_t ALSD_SLACK = 1024;
 
 }  // namespace
 
 size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap) {
     if (B <= 0 || beam <= 0 || cap <= 0) return 0;
-    return alsd_plan(ctx, B, beam, cap).total;
+    rs_arena a;
+    DecodeState st[2];
+    AlsdState as;
+    alsd_layout(ctx, B, beam, cap, a, st, as);
+    return a.bytes() + ALSD_SLACK;
 }
 
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
@@ -395,45 +408,20 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     if (W < 1 || W > MAX_BEAM) return rs_fail(ctx, RS_EINVAL, "alsd: beam size must be 1..%d", MAX_BEAM);
     const int max_steps = tp_max + alsd_budget(tp_max, ratio, abs_len);      // >= every utterance's alignment length
     const int cap = max_steps > 0 ? max_steps : 1;
-    const AlsdPlan pl = alsd_plan(ctx, B, W, cap);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, pl.total);
-    const int rows = B * W;
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* q = w; w += bytes; return q; };
+    rs_arena arena(workspace);
     DecodeState st[2];
     AlsdState as;
-    float* hset[2]; float* cset[2]; float* gset[2];
-    hset[0] = (float*)take(pl.state); cset[0] = (float*)take(pl.state);      // adjacent: one memset
-    hset[1] = (float*)take(pl.state); cset[1] = (float*)take(pl.state);
-    float* h_tmp = (float*)take(pl.state); float* c_tmp = (float*)take(pl.state);
-    gset[0] = (float*)take(pl.g); gset[1] = (float*)take(pl.g);
-    int32_t* tcur = (int32_t*)take(pl.rows4); int32_t* sym = (int32_t*)take(pl.rows4);
-    int32_t* token = (int32_t*)take(pl.rows4); int32_t* act = (int32_t*)take(pl.rows4);
-    as.parent = (int32_t*)take(pl.rows4);
-    as.len[0] = (int32_t*)take(pl.rows4); as.len[1] = (int32_t*)take(pl.rows4);
-    as.score[0] = (float*)take(pl.rows4); as.score[1] = (float*)take(pl.rows4);
-    int32_t* alive = (int32_t*)take(2 * pl.rows4);
-    as.y[0] = (int32_t*)take(pl.rows_cap4); as.y[1] = (int32_t*)take(pl.rows_cap4);
-    as.al[0] = (int32_t*)take(pl.rows_cap4); as.al[1] = (int32_t*)take(pl.rows_cap4);
-    as.n_hyp[0] = (int32_t*)take(pl.b4); as.n_hyp[1] = (int32_t*)take(pl.b4);
-    as.fin_n = (int32_t*)take(pl.b4); as.fin_norm = (float*)take(pl.b4); as.fin_score = (float*)take(pl.b4);
-    as.done = (int32_t*)take(pl.b4);
-    as.fin_y = (int32_t*)take(pl.b_cap4); as.fin_al = (int32_t*)take(pl.b_cap4);
-    int32_t* counters = (int32_t*)take(rs_align(64));
-    float* zbuf = (float*)take(pl.z);
-    as.cap = cap;
-    for (int k = 0; k < 2; ++k) {
-        DecodeState& q = st[k];
-        q.h = hset[k]; q.c = cset[k]; q.h_tmp = h_tmp; q.c_tmp = c_tmp; q.g = gset[k];
-        q.tcur = tcur; q.sym = sym; q.token = token; q.act = act; q.alive = alive; q.counters = counters;
-        q.pmax = nullptr; q.pidx = nullptr; q.a16 = nullptr; q.anorm = nullptr; q.zapprox = zbuf;
-        q.g_off = nullptr; q.a_pre = nullptr;
-        q.joint_act = d.joint_act;
-    }
+    alsd_layout(ctx, B, W, cap, arena, st, as);
+    if (workspace_bytes < arena.bytes() + ALSD_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, arena.bytes() + ALSD_SLACK);
+    const int rows = B * W;
+    float* const hset[2] = {st[0].h, st[1].h}; float* const cset[2] = {st[0].c, st[1].c}; float* const gset[2] = {st[0].g, st[1].g};
+    int32_t* const counters = st[0].counters;
+    float* const zbuf = st[0].zapprox;
     const int zstride = (V + 63) / 64 * 64;
 
     rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-    RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * pl.state, s));
+    RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * rs_align((size_t)L * rows * H * 4), s));   // h and c of set 0
     hipLaunchKernelGGL(alsd_init_kernel, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len);
     // start of sequence: blank token from zero state, slot 0 of every utterance (list built by the init kernel)
     if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }

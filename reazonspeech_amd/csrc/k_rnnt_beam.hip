@@ -635,52 +635,73 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
     BEAM_MARK(6)
 }
 
-struct BeamPlan {
-    size_t b4, bk4, h4, k4, nodes, nodes4, slots, freelist, rec, rp4, goff, state1, g, rows4, z, apre, total, step_lds, rec_lds;
-    int max_h, max_nodes, n_slots, slot_floats, zstride, R, KS, RP, rec_floats, rows;
+struct BeamPlan {                                                    // extents the launch needs besides the pointers
+    size_t step_lds, rec_lds, zero_bytes;
+    int zstride, rows;
+    float* a_pre;                                                    // DecodeState.a_pre, writable (beam_act_kernel fills it)
 };
 
-BeamPlan beam_plan(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max, int max_pops) {
+// the search's layout: fills the pointers and extents of `bs` and the decode state `st` of its prediction-network / joint launches
+BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max, int max_pops, rs_arena& a, BeamState& bs, DecodeState& st) {
     const rs_dims& d = ctx->d;
     BeamPlan p;
-    p.max_h = max_pops * (beam_k + 1) + 1;
-    p.max_nodes = (tp_max > 0 ? tp_max : 1) * max_pops + 1;        // a pop adds at most one node
-    p.n_slots = 2 * max_pops + 1;                                    // zero state + survivors (<= max_pops) + evaluations of a frame (<= max_pops)
-    p.slot_floats = 2 * d.pred_layers * d.pred_hidden + d.joint_hidden;
+    bs.max_pops = max_pops; bs.beam_k = beam_k;
+    bs.max_h = max_pops * (beam_k + 1) + 1;
+    bs.max_nodes = (tp_max > 0 ? tp_max : 1) * max_pops + 1;       // a pop adds at most one node
+    bs.n_slots = 2 * max_pops + 1;                                   // zero state + survivors (<= max_pops) + evaluations of a frame (<= max_pops)
+    bs.slot_floats = 2 * d.pred_layers * d.pred_hidden + d.joint_hidden;
     p.zstride = (d.n_logits + 63) / 64 * 64;
     int R = (beam + 12 + 3) / 4 * 4;                                 // a frame opens with >= beam survivors, usually a few more
     if (R > 64) R = 64;
     if (R > max_pops) R = max_pops;
-    p.R = R;
+    bs.R = R;
     int KS = 3;                                                      // evaluations asked for per iteration (the first is needed, the rest are guesses)
     if (const char* e = getenv("RS_BEAM_SPEC")) KS = atoi(e);
-    p.KS = KS < 1 ? 1 : KS > 8 ? 8 : KS;
-    p.RP = R + 32 + 1;                                               // batch + guesses of a frame + the needed one
-    p.rec_floats = 2 + 2 * beam_k;
-    p.rows = B * (R + p.KS);
-    p.b4 = rs_align((size_t)B * 4);
-    p.bk4 = rs_align((size_t)B * p.KS * 4);
-    p.h4 = rs_align((size_t)B * p.max_h * 4);
-    p.k4 = rs_align((size_t)B * max_pops * 4);
-    p.nodes = rs_align((size_t)B * p.max_nodes * 8);
-    p.nodes4 = rs_align((size_t)B * p.max_nodes * 4);
-    p.state1 = rs_align((size_t)d.pred_layers * B * p.KS * d.pred_hidden * 4);
-    p.slots = rs_align((size_t)B * p.n_slots * p.slot_floats * 4);
-    p.freelist = rs_align((size_t)B * p.n_slots * 4);
-    p.rec = rs_align((size_t)B * p.RP * p.rec_floats * 4);
-    p.rp4 = rs_align((size_t)B * p.RP * 4);
-    p.goff = rs_align((size_t)p.rows * 8);
-    p.g = rs_align((size_t)B * p.KS * d.joint_hidden * 4);
-    p.rows4 = rs_align((size_t)p.rows * 4);
-    p.z = rs_align((size_t)p.rows * p.zstride * 4);
-    p.apre = rs_align((size_t)p.rows * d.joint_hidden * 4);
-    p.total = 12 * p.b4 + 3 * p.bk4 + 7 * p.h4 + 4 * p.k4 + p.nodes + p.nodes4 + p.slots + p.freelist + p.rec + p.rp4 + p.goff + 4 * p.state1 + p.g +
-              4 * p.rows4 + 2 * rs_align(64) + rs_align(256) + p.z + p.apre + 1024;
-    p.step_lds = (size_t)p.max_h * 4 + (size_t)(p.max_h + 1) / 2 * 4 + (size_t)max_pops * 4 * 6 + (size_t)p.n_slots * 4 +
-                 (size_t)p.RP * p.rec_floats * 4 + (size_t)p.RP * 4;
+    bs.KS = KS < 1 ? 1 : KS > 8 ? 8 : KS;
+    bs.RP = R + 32 + 1;                                              // batch + guesses of a frame + the needed one
+    bs.rec_floats = 2 + 2 * beam_k;
+    p.rows = B * (R + bs.KS);
+    const size_t nB = B, rows = p.rows, pred_rows = nB * bs.KS, state1 = (size_t)d.pred_layers * pred_rows * d.pred_hidden;
+    // every int32 / float bookkeeping array first (one memset from bs.t), then the big buffers
+    bs.t = a.take<int32_t>(nB); bs.done = a.take<int32_t>(nB); bs.nh = a.take<int32_t>(nB); bs.nk = a.take<int32_t>(nB);
+    bs.npop = a.take<int32_t>(nB); bs.nfree = a.take<int32_t>(nB); bs.ninit = a.take<int32_t>(nB);
+    bs.nnode = a.take<int32_t>(nB); bs.pops = a.take<int32_t>(nB); bs.nb = a.take<int32_t>(nB);
+    bs.nrec = a.take<int32_t>(nB); bs.npark = a.take<int32_t>(nB);
+    bs.park_slot = a.take<int32_t>(pred_rows);
+    bs.flags = a.take<int32_t>(16);
+    st.counters = a.take<int32_t>(16);
+    bs.trace = a.take<unsigned long long>(32);
+    p.zero_bytes = a.bytes();
+    bs.h_score = a.take<float>(nB * bs.max_h); bs.h_node = a.take<int32_t>(nB * bs.max_h); bs.h_tok = a.take<int32_t>(nB * bs.max_h);
+    bs.h_slot = a.take<int32_t>(nB * bs.max_h); bs.h_len = a.take<int32_t>(nB * bs.max_h); bs.h_alive = a.take<int32_t>(nB * bs.max_h);
+    bs.h_rec = a.take<int32_t>(nB * bs.max_h);
+    bs.k_score = a.take<float>(nB * max_pops); bs.k_node = a.take<int32_t>(nB * max_pops); bs.k_slot = a.take<int32_t>(nB * max_pops);
+    bs.k_len = a.take<int32_t>(nB * max_pops);
+    bs.nodes = a.take<int2>(nB * bs.max_nodes);
+    bs.node_frame = a.take<int32_t>(nB * bs.max_nodes);
+    bs.freelist = a.take<int32_t>(nB * bs.n_slots);
+    bs.rec = a.take<float>(nB * bs.RP * bs.rec_floats);
+    bs.rec_slot = a.take<int32_t>(nB * bs.RP);
+    bs.row_rec = a.take<int32_t>(rows);
+    bs.g_off = a.take<long long>(rows);
+    st.g = a.take<float>(pred_rows * d.joint_hidden);               // joint.pred rows of the LSTM launch; the slots follow in the same
+    bs.slots = a.take<float>(nB * bs.n_slots * bs.slot_floats);     // allocation, so one base + offset addresses both
+    bs.slots_off = (long long)(bs.slots - st.g);
+    st.h = a.take<float>(state1); st.c = a.take<float>(state1);
+    st.h_tmp = a.take<float>(state1); st.c_tmp = a.take<float>(state1);
+    st.tcur = a.take<int32_t>(rows);                                 // per joint row
+    st.token = a.take<int32_t>(pred_rows); st.act = a.take<int32_t>(pred_rows);   // per prediction-network row
+    st.alive = a.take<int32_t>(rows); a.take<int32_t>(rows);         // [2][rows]: the second list follows at pitch `rows`
+    st.zapprox = a.take<float>(rows * p.zstride);
+    st.g_off = bs.g_off;
+    st.a_pre = p.a_pre = a.take<float>(rows * d.joint_hidden);
+    st.joint_act = d.joint_act;
+    p.step_lds = (size_t)bs.max_h * 4 + (size_t)(bs.max_h + 1) / 2 * 4 + (size_t)max_pops * 4 * 6 + (size_t)bs.n_slots * 4 +
+                 (size_t)bs.RP * bs.rec_floats * 4 + (size_t)bs.RP * 4;
     p.rec_lds = (size_t)4 * (p.zstride + 256) * 4;
     return p;
 }
+constexpr size_t BEAM_SLACK = 1024;
 
 int clamp_pops(int beam, int max_pops) { return max_pops > 0 ? max_pops : 16 * beam; }
 
@@ -689,7 +710,11 @@ int clamp_pops(int beam, int max_pops) { return max_pops > 0 ? max_pops : 16 * b
 size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops) {
     const int V = ctx->d.n_logits;
     const int bm = beam < V ? beam : V, beam_k = bm < V - 1 ? bm : V - 1;
-    return beam_plan(ctx, B, bm, beam_k, tp_max, clamp_pops(bm, max_pops)).total;
+    rs_arena a;
+    BeamState bs;
+    DecodeState st{};
+    beam_layout(ctx, B, bm, beam_k, tp_max, clamp_pops(bm, max_pops), a, bs, st);
+    return a.bytes() + BEAM_SLACK;
 }
 
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
@@ -704,56 +729,17 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     const int mp = clamp_pops(bm, max_pops);
     if (bm > 128) return rs_fail(ctx, RS_EINVAL, "beam search: beam size must be 1..128");
     if (mp < bm) return rs_fail(ctx, RS_EINVAL, "beam search: max_pops %d < beam %d (a frame needs at least `beam` pops)", mp, bm);
-    const BeamPlan pl = beam_plan(ctx, B, bm, beam_k, tp_max, mp);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "beam search: workspace %zu < %zu", workspace_bytes, pl.total);
+    rs_arena arena(workspace);
+    BeamState bs;
+    DecodeState st{};
+    const BeamPlan pl = beam_layout(ctx, B, bm, beam_k, tp_max, mp, arena, bs, st);
+    if (workspace_bytes < arena.bytes() + BEAM_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + BEAM_SLACK);
     if (pl.step_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: beam %d x max_pops %d needs %zu bytes of LDS (> 150 KB): lower max_pops", bm, mp, pl.step_lds);
     if (pl.rec_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: vocabulary %d exceeds the record kernel's LDS", V);
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* q = w; w += bytes; return q; };
-    BeamState bs;
-    DecodeState st;
-    // every int32 / float bookkeeping array first (one memset), then the big buffers
-    char* zero_from = w;
-    bs.t = (int32_t*)take(pl.b4); bs.done = (int32_t*)take(pl.b4); bs.nh = (int32_t*)take(pl.b4); bs.nk = (int32_t*)take(pl.b4);
-    bs.npop = (int32_t*)take(pl.b4); bs.nfree = (int32_t*)take(pl.b4); bs.ninit = (int32_t*)take(pl.b4);
-    bs.nnode = (int32_t*)take(pl.b4); bs.pops = (int32_t*)take(pl.b4); bs.nb = (int32_t*)take(pl.b4);
-    bs.nrec = (int32_t*)take(pl.b4); bs.npark = (int32_t*)take(pl.b4);
-    bs.park_slot = (int32_t*)take(pl.bk4);
-    bs.flags = (int32_t*)take(rs_align(64));
-    int32_t* counters = (int32_t*)take(rs_align(64));
-    unsigned long long* trace = (unsigned long long*)take(rs_align(256));
-    bs.trace = getenv("RS_BEAM_TRACE") ? trace : nullptr;
-    const size_t zero_bytes = (size_t)(w - zero_from);
-    bs.h_score = (float*)take(pl.h4); bs.h_node = (int32_t*)take(pl.h4); bs.h_tok = (int32_t*)take(pl.h4);
-    bs.h_slot = (int32_t*)take(pl.h4); bs.h_len = (int32_t*)take(pl.h4); bs.h_alive = (int32_t*)take(pl.h4);
-    bs.h_rec = (int32_t*)take(pl.h4);
-    bs.k_score = (float*)take(pl.k4); bs.k_node = (int32_t*)take(pl.k4); bs.k_slot = (int32_t*)take(pl.k4);
-    bs.k_len = (int32_t*)take(pl.k4);
-    bs.nodes = (int2*)take(pl.nodes);
-    bs.node_frame = (int32_t*)take(pl.nodes4);
-    bs.freelist = (int32_t*)take(pl.freelist);
-    bs.rec = (float*)take(pl.rec);
-    bs.rec_slot = (int32_t*)take(pl.rp4);
-    bs.row_rec = (int32_t*)take(pl.rows4);
-    bs.g_off = (long long*)take(pl.goff);
-    st.g = (float*)take(pl.g);                                      // joint.pred rows of the LSTM launch; the slots follow in the same
-    bs.slots = (float*)take(pl.slots);                               // allocation, so one base + offset addresses both
-    bs.slots_off = (long long)(bs.slots - st.g);
-    bs.max_h = pl.max_h; bs.max_pops = mp; bs.max_nodes = pl.max_nodes; bs.n_slots = pl.n_slots; bs.slot_floats = pl.slot_floats;
-    bs.R = pl.R; bs.KS = pl.KS; bs.RP = pl.RP; bs.rec_floats = pl.rec_floats; bs.beam_k = beam_k;
-    st.h = (float*)take(pl.state1); st.c = (float*)take(pl.state1);
-    st.h_tmp = (float*)take(pl.state1); st.c_tmp = (float*)take(pl.state1);
-    st.tcur = (int32_t*)take(pl.rows4);                              // per joint row
-    st.sym = nullptr;
-    st.token = (int32_t*)take(pl.bk4); st.act = (int32_t*)take(pl.bk4);   // per prediction-network row
-    st.alive = (int32_t*)take(2 * pl.rows4);
-    st.counters = counters;
-    st.pmax = nullptr; st.pidx = nullptr; st.a16 = nullptr; st.anorm = nullptr;
-    st.zapprox = (float*)take(pl.z);
-    st.g_off = bs.g_off;
-    float* a_pre = (float*)take(pl.apre);
-    st.a_pre = a_pre;
-    st.joint_act = d.joint_act;
+    unsigned long long* const trace = bs.trace;
+    if (!getenv("RS_BEAM_TRACE")) bs.trace = nullptr;
+    float* const a_pre = pl.a_pre;
 
     const bool rec_lds = getenv("RS_BEAM_RECORD_LDS") != nullptr;   // test hook: the any-vocabulary variant on a small one
     auto record = rec_lds ? beam_record_kernel<0> : V <= 64 * 16 ? beam_record_kernel<16> : V <= 64 * 48 ? beam_record_kernel<48> : beam_record_kernel<0>;
@@ -761,9 +747,9 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_first_kernel, (int)pl.step_lds); rc != RS_OK) return rc;
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)record, (int)pl.rec_lds); rc != RS_OK) return rc;
     rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-    RS_HIP(ctx, hipMemsetAsync(zero_from, 0, zero_bytes, s));
+    RS_HIP(ctx, hipMemsetAsync(bs.t, 0, pl.zero_bytes, s));
     // slot 0 of every utterance: the zero state the search starts from
-    RS_HIP(ctx, hipMemset2DAsync(bs.slots, (size_t)pl.n_slots * pl.slot_floats * 4, 0, (size_t)pl.slot_floats * 4, B, s));
+    RS_HIP(ctx, hipMemset2DAsync(bs.slots, (size_t)bs.n_slots * bs.slot_floats * 4, 0, (size_t)bs.slot_floats * 4, B, s));
     hipLaunchKernelGGL(beam_init_kernel, dim3((B + 255) / 256), dim3(256), 0, s, bs, enc_lens, B, d.blank_id, n_ids, scores, pops);
     hipLaunchKernelGGL(beam_first_kernel, dim3(B), dim3(256), pl.step_lds, s, bs, st, B, L, H, J);
     RS_CHECK_LAUNCH(ctx, "beam init");
@@ -775,14 +761,14 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     const int joint_rts = pl.rows / 32 < 64 ? (pl.rows + 31) / 32 : 64;
     const int act_blocks = 512;
     const int rec_blocks = pl.rows / 4 < 1024 ? (pl.rows + 3) / 4 : 1024;
-    const int rpu = pl.R + pl.KS;
+    const int rpu = bs.R + bs.KS;
     int32_t hf[2] = {0, 0};
     long long it = 0;
     bool finished = false;
     while (!finished && it < max_iters) {
         for (int c = 0; c < CHUNK; ++c, ++it) {
             const int step = (int)(it & 1);
-            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, B * pl.KS, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, B * bs.KS, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
             hipLaunchKernelGGL(beam_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, joint_enc, a_pre, pl.rows, tp_max, J, rpu, step);
             if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, pl.rows, joint_rts * 32, tp_max, rpu, step, s); rc != RS_OK) {
                 rs_prof_end(ctx, RS_PROF_DECODE, s);

@@ -340,30 +340,41 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
     }
 }
 
-struct MbsPlan {
-    size_t state, g, rows4, rows_cap4, b4, z, total;
-};
-
-MbsPlan mbs_plan(const rs_ctx* ctx, int B, int K, int cap) {
+// the search's layout (h .. c_tmp adjacent: one memset clears the four); -> DecodeState.a_pre, writable (mbs_act_kernel fills it)
+float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, rs_arena& a, DecodeState& st, MbsState& ms) {
     const rs_dims& d = ctx->d;
-    const size_t rows = (size_t)B * K;
-    MbsPlan p;
-    p.state = rs_align(rows * d.pred_hidden * 4);
-    p.g = rs_align(rows * d.joint_hidden * 4);
-    p.rows4 = rs_align(rows * 4);
-    p.rows_cap4 = rs_align(rows * (size_t)cap * 4);
-    p.b4 = rs_align((size_t)B * 4);
-    p.z = rs_align(rows * (size_t)((d.n_logits + 63) / 64 * 64) * 4);
-    //        h c h_tmp c_tmp   g a_pre   tcur token token2 act + 5 records x2   alive x2   y, fr x2   n_hyp x2   counters   z
-    p.total = 4 * p.state + 2 * p.g + 14 * p.rows4 + 2 * p.rows4 + 4 * p.rows_cap4 + 2 * p.b4 + rs_align(64) + p.z + 1024;
-    return p;
+    const size_t rows = (size_t)B * K, state = rows * d.pred_hidden;
+    st.h = a.take<float>(state); st.c = a.take<float>(state);                // (the projection kernel's state commit copies
+    st.h_tmp = a.take<float>(state); st.c_tmp = a.take<float>(state);        //  h_tmp / c_tmp there; h_tmp is the decoder output)
+    st.g = a.take<float>(rows * d.joint_hidden);
+    float* a_pre = a.take<float>(rows * d.joint_hidden);
+    st.tcur = a.take<int32_t>(rows); st.token = a.take<int32_t>(rows); st.token2 = a.take<int32_t>(rows);
+    st.act = a.take<int32_t>(rows);
+    for (int k = 0; k < 2; ++k) {
+        ms.len[k] = a.take<int32_t>(rows); ms.score[k] = a.take<float>(rows); ms.last0[k] = a.take<int32_t>(rows);
+        ms.last1[k] = a.take<int32_t>(rows); ms.dec[k] = a.take<int32_t>(rows);
+    }
+    st.alive = a.take<int32_t>(rows); a.take<int32_t>(rows);                 // [2][rows]: the second list follows at pitch `rows`
+    for (int k = 0; k < 2; ++k) { ms.y[k] = a.take<int32_t>(rows * cap); ms.fr[k] = a.take<int32_t>(rows * cap); }
+    ms.n_hyp[0] = a.take<int32_t>(B); ms.n_hyp[1] = a.take<int32_t>(B);
+    st.counters = a.take<int32_t>(16);
+    st.zapprox = a.take<float>(rows * (size_t)((d.n_logits + 63) / 64 * 64));
+    ms.cap = cap;
+    st.a_pre = a_pre;
+    st.joint_act = d.joint_act;
+    return a_pre;
 }
+constexpr size_t MBS_SLACK = 1024;
 
 }  // namespace
 
 size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max) {
     if (B <= 0 || K <= 0 || K > MBS_MAX_K || tp_max < 0) return 0;
-    return mbs_plan(ctx, B, K, tp_max > 0 ? tp_max : 1).total;
+    rs_arena a;
+    DecodeState st{};
+    MbsState ms;
+    mbs_layout(ctx, B, K, tp_max > 0 ? tp_max : 1, a, st, ms);
+    return a.bytes() + MBS_SLACK;
 }
 
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
@@ -377,37 +388,19 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     if (K < 1 || K > MBS_MAX_K) return rs_fail(ctx, RS_EINVAL, "modified beam search: max_active_paths must be 1..%d", MBS_MAX_K);
     if ((long long)K * V > 0x7fffffffLL) return rs_fail(ctx, RS_EINVAL, "modified beam search: vocabulary too large");
     const int cap = tp_max > 0 ? tp_max : 1;              // at most one token per frame
-    const MbsPlan pl = mbs_plan(ctx, B, K, cap);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, pl.total);
-    const int rows = B * K;
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](size_t bytes) { char* q = w; w += bytes; return q; };
-    DecodeState st;
+    rs_arena arena(workspace);
+    DecodeState st{};
     MbsState ms;
-    st.h = (float*)take(pl.state); st.c = (float*)take(pl.state);            // (the projection kernel's state commit copies
-    st.h_tmp = (float*)take(pl.state); st.c_tmp = (float*)take(pl.state);    //  h_tmp / c_tmp there; h_tmp is the decoder output)
-    st.g = (float*)take(pl.g);
-    float* a_pre = (float*)take(pl.g);
-    st.tcur = (int32_t*)take(pl.rows4); st.token = (int32_t*)take(pl.rows4); st.token2 = (int32_t*)take(pl.rows4);
-    st.act = (int32_t*)take(pl.rows4);
-    for (int k = 0; k < 2; ++k) {
-        ms.len[k] = (int32_t*)take(pl.rows4); ms.score[k] = (float*)take(pl.rows4); ms.last0[k] = (int32_t*)take(pl.rows4);
-        ms.last1[k] = (int32_t*)take(pl.rows4); ms.dec[k] = (int32_t*)take(pl.rows4);
-    }
-    st.alive = (int32_t*)take(2 * pl.rows4);
-    for (int k = 0; k < 2; ++k) { ms.y[k] = (int32_t*)take(pl.rows_cap4); ms.fr[k] = (int32_t*)take(pl.rows_cap4); }
-    ms.n_hyp[0] = (int32_t*)take(pl.b4); ms.n_hyp[1] = (int32_t*)take(pl.b4);
-    st.counters = (int32_t*)take(rs_align(64));
-    float* zbuf = (float*)take(pl.z);
-    ms.cap = cap;
-    st.sym = nullptr; st.pmax = nullptr; st.pidx = nullptr; st.a16 = nullptr; st.anorm = nullptr;
-    st.zapprox = zbuf; st.g_off = nullptr; st.a_pre = a_pre;
-    st.joint_act = d.joint_act;
+    float* const a_pre = mbs_layout(ctx, B, K, cap, arena, st, ms);
+    if (workspace_bytes < arena.bytes() + MBS_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + MBS_SLACK);
+    const int rows = B * K;
+    float* const zbuf = st.zapprox;
     st.unk = rs_k2_unk_id(ctx);
     const int zstride = (V + 63) / 64 * 64;
 
     rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-    RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * pl.state, s));                   // h .. c_tmp are adjacent
+    RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * rs_align((size_t)rows * D * 4), s));                  // h .. c_tmp are adjacent
     hipLaunchKernelGGL(mbs_init_kernel, dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores);
     if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
     RS_CHECK_LAUNCH(ctx, "modified beam search init");

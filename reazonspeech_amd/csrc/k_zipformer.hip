@@ -1185,11 +1185,13 @@ __global__ void k2_lens_kernel(const int32_t* __restrict__ n_frames, int B, int 
 struct K2Plan {
     int T, T1, T2, T3, To, F, F2, F3, Kp;
     int Ts[8], Tp[8];
-    size_t off_lens, off_a0, off_a1, off_col, off_a2, off_dwo, off_h, off_stackout[8], off_x, off_x0, off_src, off_xb, off_qkp, off_w, off_big, off_av, off_vt,
-        off_encb, total;
+    int32_t* lens;
+    uint16_t *a0, *a1, *col, *dwo, *h, *xb, *qkp, *w, *big, *av, *vt, *encb;
+    float *a2, *stackout[8], *x, *x0, *src;
 };
+constexpr size_t K2_SLACK = 256;
 
-K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max) {
+K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     const rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
     K2Plan p{};
@@ -1201,60 +1203,39 @@ K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max) {
     p.Kp = pad64(9 * d.embed_c2);
     const size_t T3 = p.T3 > 0 ? p.T3 : 1, T1 = p.T1 > 0 ? p.T1 : 1, T2 = p.T2 > 0 ? p.T2 : 1;
     const size_t rows3 = (size_t)B * T3 * p.F3;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += rs_align(bytes); return at; };
-    p.off_lens = take((size_t)(2 + d.n_stacks) * B * 4);
-    p.off_a0 = take((size_t)B * T1 * p.F * d.embed_c1 * 2);
-    p.off_a1 = take((size_t)B * T2 * p.F2 * d.embed_c2 * 2);
-    p.off_col = take(rows3 * p.Kp * 2);
-    p.off_a2 = take(rows3 * d.embed_c3 * 4);
-    p.off_dwo = take(rows3 * d.embed_c3 * 2);
-    p.off_h = take(rows3 * 3 * d.embed_c3 * 2);
-    int dmax = 0, nin_max = 0, big_max = 0, av_max = 0;
-    size_t w_max = 0;
+    p.lens = a.take<int32_t>((size_t)(2 + d.n_stacks) * B);
+    p.a0 = a.take<uint16_t>((size_t)B * T1 * p.F * d.embed_c1);
+    p.a1 = a.take<uint16_t>((size_t)B * T2 * p.F2 * d.embed_c2);
+    p.col = a.take<uint16_t>(rows3 * p.Kp);
+    p.a2 = a.take<float>(rows3 * d.embed_c3);
+    p.dwo = a.take<uint16_t>(rows3 * d.embed_c3);
+    p.h = a.take<uint16_t>(rows3 * 3 * d.embed_c3);
+    // elements of the largest stack's residual stream, q/k/p rows, attention weights, widest activation, value rows and V^T copy
+    size_t x_n = 0, qkp_n = 0, w_n = 0, big_n = 0, av_n = 0, vt_n = 0;
     for (int s = 0; s < d.n_stacks; ++s) {
-        const int dd = d.encoder_dim[s], H = d.num_heads[s], ds = d.downsampling[s];
-        p.Ts[s] = ceil_div((int)T3, ds);
+        const size_t dd = d.encoder_dim[s], H = d.num_heads[s];
+        p.Ts[s] = ceil_div((int)T3, d.downsampling[s]);
         p.Tp[s] = (p.Ts[s] + 31) / 32 * 32;
-        p.off_stackout[s] = take((size_t)B * T3 * dd * 4);
-        dmax = dd > dmax ? dd : dmax;
-        const int nin = (2 * K2_QD + K2_PD) * H;
+        p.stackout[s] = a.take<float>((size_t)B * T3 * dd);
         const size_t rows = (size_t)B * p.Ts[s];
-        if ((size_t)nin * rows > (size_t)nin_max) nin_max = 0;       // (sized below in bytes)
-        const size_t wb = (size_t)B * H * p.Ts[s] * p.Tp[s] * 2;
-        w_max = wb > w_max ? wb : w_max;
-        (void)big_max; (void)av_max;
+        x_n = std::max(x_n, (size_t)B * T3 * dd);
+        qkp_n = std::max(qkp_n, rows * (2 * K2_QD + K2_PD) * H);
+        w_n = std::max(w_n, (size_t)B * H * p.Ts[s] * p.Tp[s]);
+        const size_t widest = std::max(std::max((size_t)d.ff_dim[s] * 5 / 4, 3 * (3 * dd / 4)), 2 * dd);
+        big_n = std::max(big_n, rows * widest);
+        const size_t avw = std::max(std::max((size_t)pad64(3 * (int)dd / 4), (size_t)pad64((int)H * K2_VD)), dd);
+        av_n = std::max(av_n, rows * avw);
+        const size_t vc = std::max((size_t)pad64(3 * (int)dd / 4), (size_t)pad64((int)H * 16));
+        vt_n = std::max(vt_n, (size_t)B * vc * p.Tp[s]);
     }
-    size_t x_b = 0, qkp_b = 0, big_b = 0, av_b = 0, vt_b = 0;
-    for (int s = 0; s < d.n_stacks; ++s) {
-        const size_t rows = (size_t)B * p.Ts[s], dd = d.encoder_dim[s], H = d.num_heads[s];
-        const size_t full = (size_t)B * T3 * dd * 4;
-        x_b = full > x_b ? full : x_b;
-        const size_t q = rows * (2 * K2_QD + K2_PD) * H * 2;
-        qkp_b = q > qkp_b ? q : qkp_b;
-        size_t widest = (size_t)d.ff_dim[s] * 5 / 4;
-        const size_t na = 3 * (3 * dd / 4);
-        widest = na > widest ? na : widest;
-        widest = 2 * dd > widest ? 2 * dd : widest;
-        big_b = rows * widest * 2 > big_b ? rows * widest * 2 : big_b;
-        size_t avw = pad64(3 * (int)dd / 4);
-        avw = (size_t)pad64((int)H * K2_VD) > avw ? (size_t)pad64((int)H * K2_VD) : avw;
-        avw = dd > avw ? dd : avw;
-        av_b = rows * avw * 2 > av_b ? rows * avw * 2 : av_b;
-        size_t vc = pad64(3 * (int)dd / 4);
-        vc = (size_t)pad64((int)H * 16) > vc ? (size_t)pad64((int)H * 16) : vc;
-        const size_t vb = (size_t)B * vc * p.Tp[s] * 2;
-        vt_b = vb > vt_b ? vb : vt_b;
-    }
-    p.off_x = take(x_b); p.off_x0 = take(x_b); p.off_src = take(x_b);
-    p.off_xb = take(x_b / 2);
-    p.off_qkp = take(qkp_b);
-    p.off_w = take(w_max);
-    p.off_big = take(big_b);
-    p.off_av = take(av_b);
-    p.off_vt = take(vt_b);
-    p.off_encb = take((size_t)B * (p.To > 0 ? p.To : 1) * k.out_dim * 2);
-    p.total = o + 256;
+    p.x = a.take<float>(x_n); p.x0 = a.take<float>(x_n); p.src = a.take<float>(x_n);
+    p.xb = a.take<uint16_t>(x_n);
+    p.qkp = a.take<uint16_t>(qkp_n);
+    p.w = a.take<uint16_t>(w_n);
+    p.big = a.take<uint16_t>(big_n);
+    p.av = a.take<uint16_t>(av_n);
+    p.vt = a.take<uint16_t>(vt_n);
+    p.encb = a.take<uint16_t>((size_t)B * (p.To > 0 ? p.To : 1) * k.out_dim);
     return p;
 }
 
@@ -1265,11 +1246,12 @@ __host__ __device__ inline int pad32(int n) { return (n + 31) / 32 * 32; }
 struct K2PlanF32 {
     int T, T1, T2, T3, To, F, F2, F3;
     int Ts[8], Tp[8];
-    size_t off_lens, off_a0, off_a1, off_col, off_a2, off_dwo, off_h, off_stackout[8], off_x, off_x0, off_src, off_qkp, off_w, off_big, off_av, off_gate,
-        off_enc, off_qp, off_lens2, off_pos_in, off_pos_tab, total;
+    int32_t *lens, *lens2;
+    float *a0, *a1, *col, *a2, *dwo, *h, *stackout[8], *x, *x0, *src, *qkp, *w, *big, *av, *gate, *enc;
+    float *qp, *pos_in, *pos_tab;        // int8 mode only (with lens2), else nullptr
 };
 
-K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max) {
+K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     const rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
     K2PlanF32 p{};
@@ -1280,48 +1262,45 @@ K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max) {
     p.To = (p.T3 + 1) / 2;
     const size_t T3 = p.T3 > 0 ? p.T3 : 1, T1 = p.T1 > 0 ? p.T1 : 1, T2 = p.T2 > 0 ? p.T2 : 1;
     const size_t rows3 = (size_t)B * T3 * p.F3;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += rs_align(bytes); return at; };
-    p.off_lens = take((size_t)(2 + d.n_stacks) * B * 4);
-    p.off_a0 = take((size_t)B * T1 * p.F * d.embed_c1 * 4);
-    p.off_a1 = take((size_t)B * T2 * p.F2 * d.embed_c2 * 4);
-    p.off_col = take(rows3 * pad32(9 * d.embed_c2) * 4);
-    p.off_a2 = take(rows3 * d.embed_c3 * 4);
-    p.off_dwo = take(rows3 * d.embed_c3 * 4);
-    p.off_h = take(rows3 * 3 * d.embed_c3 * 4);
-    size_t x_b = 0, qkp_b = 0, w_b = 0, big_b = 0, av_b = 0, gate_b = 0;
+    p.lens = a.take<int32_t>((size_t)(2 + d.n_stacks) * B);
+    p.a0 = a.take<float>((size_t)B * T1 * p.F * d.embed_c1);
+    p.a1 = a.take<float>((size_t)B * T2 * p.F2 * d.embed_c2);
+    p.col = a.take<float>(rows3 * pad32(9 * d.embed_c2));
+    p.a2 = a.take<float>(rows3 * d.embed_c3);
+    p.dwo = a.take<float>(rows3 * d.embed_c3);
+    p.h = a.take<float>(rows3 * 3 * d.embed_c3);
+    size_t x_n = 0, qkp_n = 0, w_n = 0, big_n = 0, av_n = 0, gate_n = 0;
     for (int s = 0; s < d.n_stacks; ++s) {
         const size_t dd = d.encoder_dim[s], H = d.num_heads[s], hid = 3 * dd / 4;
         p.Ts[s] = ceil_div((int)T3, d.downsampling[s]);
         p.Tp[s] = (p.Ts[s] + 31) / 32 * 32;
         const size_t rows = (size_t)B * p.Ts[s];
-        p.off_stackout[s] = take((size_t)B * T3 * dd * 4);
-        x_b = std::max(x_b, (size_t)B * T3 * dd * 4);
-        qkp_b = std::max(qkp_b, rows * (2 * K2_QD + K2_PD) * H * 4);
-        w_b = std::max(w_b, (size_t)B * H * p.Ts[s] * p.Tp[s] * 4);
+        p.stackout[s] = a.take<float>((size_t)B * T3 * dd);
+        x_n = std::max(x_n, (size_t)B * T3 * dd);
+        qkp_n = std::max(qkp_n, rows * (2 * K2_QD + K2_PD) * H);
+        w_n = std::max(w_n, (size_t)B * H * p.Ts[s] * p.Tp[s]);
         const size_t widest = std::max(std::max((size_t)d.ff_dim[s] * 5 / 4, 3 * hid), 2 * dd);
-        big_b = std::max(big_b, rows * widest * 4);
+        big_n = std::max(big_n, rows * widest);
         const size_t avw = std::max(std::max((size_t)pad32((int)hid), (size_t)pad32((int)H * K2_VD)), dd);
-        av_b = std::max(av_b, rows * avw * 4);
-        gate_b = std::max(gate_b, rows * hid * 4);
+        av_n = std::max(av_n, rows * avw);
+        gate_n = std::max(gate_n, rows * hid);
     }
-    p.off_x = take(x_b); p.off_x0 = take(x_b); p.off_src = take(x_b);
-    p.off_qkp = take(qkp_b);
-    p.off_w = take(w_b);
-    p.off_big = take(big_b);
-    p.off_av = take(av_b);
-    p.off_gate = take(gate_b);
-    p.off_enc = take((size_t)B * (p.To > 0 ? p.To : 1) * k.out_dim * 4);
+    p.x = a.take<float>(x_n); p.x0 = a.take<float>(x_n); p.src = a.take<float>(x_n);
+    p.qkp = a.take<float>(qkp_n);
+    p.w = a.take<float>(w_n);
+    p.big = a.take<float>(big_n);
+    p.av = a.take<float>(av_n);
+    p.gate = a.take<float>(gate_n);
+    p.enc = a.take<float>((size_t)B * (p.To > 0 ? p.To : 1) * k.out_dim);
     if (k.has_i8) {                  // int8 mode: (sx, zx) per utterance, and the per-utterance linear_pos input rows and tables
         size_t tab = 0;
         for (int s = 0; s < d.n_stacks; ++s) tab = std::max(tab, (size_t)(2 * p.Ts[s] - 1) * d.num_heads[s] * K2_PD);
         const size_t G = 2 * (size_t)p.Ts[0] - 1;     // (the first stack runs at the full rate: the longest)
-        p.off_qp = take((size_t)B * 2 * 4);
-        p.off_lens2 = take((size_t)B * 4);
-        p.off_pos_in = take((size_t)B * G * d.pos_dim * 4);
-        p.off_pos_tab = take((size_t)B * tab * 4);
+        p.qp = a.take<float>((size_t)B * 2);
+        p.lens2 = a.take<int32_t>(B);
+        p.pos_in = a.take<float>((size_t)B * G * d.pos_dim);
+        p.pos_tab = a.take<float>((size_t)B * tab);
     }
-    p.total = o + 256;
     return p;
 }
 
@@ -1570,11 +1549,10 @@ int rs_k2_enc_frames_impl(const rs_ctx* ctx, int n_feat) {
 }
 
 size_t rs_k2_workspace_bytes_impl(const rs_ctx* ctx, int B, int t_max) {
-    const size_t a = k2_plan(ctx, B, t_max > 9 ? t_max : 9).total;
-    if (!ctx->has_f32) return a;                      // the float32 parity mode keeps float32 activations: about twice the scratch
-                                                      // (and, with "*.i8" tensors, the int8 mode's scales and position rows)
-    const size_t b = k2_plan_f32(ctx, B, t_max > 9 ? t_max : 9).total;
-    return a > b ? a : b;
+    rs_arena a, b;
+    k2_plan(ctx, B, t_max > 9 ? t_max : 9, a);
+    if (ctx->has_f32) k2_plan_f32(ctx, B, t_max > 9 ? t_max : 9, b);   // the float32 parity mode keeps float32 activations: about twice the
+    return std::max(a.bytes(), b.bytes()) + K2_SLACK;                  // scratch (and, with "*.i8" tensors, the int8 mode's scales and position rows)
 }
 
 static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out, float* joint_enc,
@@ -1586,27 +1564,15 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     const rs_k2_dims& d = k.d;
     if (t_max < 9) return rs_fail(ctx, RS_EINVAL, "zipformer: %d feature frames are too few for encoder_embed (9 are needed)", t_max);
     if (ctx->precision_f32 || ctx->precision_i8) return rs_k2_encoder_forward_f32(ctx, feats, n_frames, B, t_max, enc_out, joint_enc, enc_lens, workspace, workspace_bytes, s);
-    const K2Plan pl = k2_plan(ctx, B, t_max);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "zipformer: workspace %zu < %zu", workspace_bytes, pl.total);
-    char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* lens_all = reinterpret_cast<int32_t*>(ws + pl.off_lens);
+    rs_arena arena(workspace);
+    const K2Plan pl = k2_plan(ctx, B, t_max, arena);
+    if (workspace_bytes < arena.bytes() + K2_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "zipformer: workspace %zu < %zu", workspace_bytes, arena.bytes() + K2_SLACK);
+    int32_t* const lens_all = pl.lens;
     const int32_t* lens3 = lens_all;
-    uint16_t* a0 = reinterpret_cast<uint16_t*>(ws + pl.off_a0);
-    uint16_t* a1 = reinterpret_cast<uint16_t*>(ws + pl.off_a1);
-    uint16_t* col = reinterpret_cast<uint16_t*>(ws + pl.off_col);
-    float* a2 = reinterpret_cast<float*>(ws + pl.off_a2);
-    uint16_t* dwo = reinterpret_cast<uint16_t*>(ws + pl.off_dwo);
-    uint16_t* hbuf = reinterpret_cast<uint16_t*>(ws + pl.off_h);
-    float* x = reinterpret_cast<float*>(ws + pl.off_x);
-    float* x0 = reinterpret_cast<float*>(ws + pl.off_x0);
-    float* src = reinterpret_cast<float*>(ws + pl.off_src);
-    uint16_t* xb = reinterpret_cast<uint16_t*>(ws + pl.off_xb);
-    uint16_t* qkp = reinterpret_cast<uint16_t*>(ws + pl.off_qkp);
-    uint16_t* W = reinterpret_cast<uint16_t*>(ws + pl.off_w);
-    uint16_t* big = reinterpret_cast<uint16_t*>(ws + pl.off_big);
-    uint16_t* av = reinterpret_cast<uint16_t*>(ws + pl.off_av);
-    uint16_t* vT = reinterpret_cast<uint16_t*>(ws + pl.off_vt);
-    uint16_t* encb = reinterpret_cast<uint16_t*>(ws + pl.off_encb);
+    uint16_t *const a0 = pl.a0, *const a1 = pl.a1, *const col = pl.col, *const dwo = pl.dwo, *const hbuf = pl.h, *const xb = pl.xb, *const qkp = pl.qkp;
+    uint16_t *const W = pl.w, *const big = pl.big, *const av = pl.av, *const vT = pl.vt, *const encb = pl.encb;
+    float *const a2 = pl.a2, *const x = pl.x, *const x0 = pl.x0, *const src = pl.src;
     const int c1 = d.embed_c1, c2 = d.embed_c2, c3 = d.embed_c3, T3 = pl.T3, F3 = pl.F3;
     int rc;
 #define RS_TRY(call) do { rc = (call); if (rc != RS_OK) return rc; } while (0)
@@ -1698,7 +1664,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
         const int hid = 3 * dd / 4, hidp = pad64(hid), vw = H * K2_VD, vwp = pad64(vw), nin = (2 * K2_QD + K2_PD) * H;
         const int32_t* lens = lens_all + (size_t)(1 + st) * B;
         const long long M = (long long)B * Ts;
-        float* stack_out = reinterpret_cast<float*>(ws + pl.off_stackout[st]);
+        float* stack_out = pl.stackout[st];
         // Two working buffers per stack: `cur` holds a layer's input and stays intact for the whole layer (it is the x0 of both
         // bypass modules), the layer's first residual GEMM writes into `nxt` (out != residual) and everything after it works in
         // place there; the buffers swap roles per layer — no copy of the layer input (it was a 1.1 ms memcpy per batch).  The
@@ -1791,11 +1757,11 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     K2Pieces pc{};
     {
         int n = 0, cur_dim = d.encoder_dim[d.n_stacks - 1];
-        pc.p[n] = reinterpret_cast<const float*>(ws + pl.off_stackout[d.n_stacks - 1]); pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
+        pc.p[n] = pl.stackout[d.n_stacks - 1]; pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
         for (int st = d.n_stacks - 2; st >= 0; --st) {
             const int dd = d.encoder_dim[st];
             if (dd > cur_dim) {
-                pc.p[n] = reinterpret_cast<const float*>(ws + pl.off_stackout[st]); pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
+                pc.p[n] = pl.stackout[st]; pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
                 cur_dim = dd;
             }
         }
@@ -1816,15 +1782,15 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
                                      int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s) {
     rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
-    const K2PlanF32 pl = k2_plan_f32(ctx, B, t_max);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "zipformer (float32 mode): workspace %zu < %zu", workspace_bytes, pl.total);
-    char* ws = reinterpret_cast<char*>(workspace);
-    auto fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    int32_t* lens_all = reinterpret_cast<int32_t*>(ws + pl.off_lens);
+    rs_arena arena(workspace);
+    const K2PlanF32 pl = k2_plan_f32(ctx, B, t_max, arena);
+    if (workspace_bytes < arena.bytes() + K2_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "zipformer (float32 mode): workspace %zu < %zu", workspace_bytes, arena.bytes() + K2_SLACK);
+    int32_t* const lens_all = pl.lens;
     const int32_t* lens3 = lens_all;
-    float *a0 = fp(pl.off_a0), *a1 = fp(pl.off_a1), *col = fp(pl.off_col), *a2 = fp(pl.off_a2), *dwo = fp(pl.off_dwo), *hbuf = fp(pl.off_h);
-    float *x = fp(pl.off_x), *x0 = fp(pl.off_x0), *src = fp(pl.off_src), *qkp = fp(pl.off_qkp), *W = fp(pl.off_w), *big = fp(pl.off_big);
-    float *av = fp(pl.off_av), *gate = fp(pl.off_gate), *encf = enc_out ? enc_out : fp(pl.off_enc);
+    float *const a0 = pl.a0, *const a1 = pl.a1, *const col = pl.col, *const a2 = pl.a2, *const dwo = pl.dwo, *const hbuf = pl.h;
+    float *const x = pl.x, *const x0 = pl.x0, *const src = pl.src, *const qkp = pl.qkp, *const W = pl.w, *const big = pl.big;
+    float *const av = pl.av, *const gate = pl.gate, *const encf = enc_out ? enc_out : pl.enc;
     const int c1 = d.embed_c1, c2 = d.embed_c2, c3 = d.embed_c3, T3 = pl.T3, F3 = pl.F3;
     int rc;
 #define RS_TRY(call) do { rc = (call); if (rc != RS_OK) return rc; } while (0)
@@ -1835,7 +1801,7 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
     // int8 mode: a Linear with a registered "<name>.i8" runs as onnxruntime's quantized MatMul (k_int8.hip) with (sx, zx) taken per
     // utterance over its own `lens[b]` rows of the `group` rows it has in A; K is the Linear's own width (A / weights may be padded)
     const bool i8 = ctx->precision_i8 && k.has_i8;
-    float* qp = i8 ? fp(pl.off_qp) : nullptr;
+    float* qp = i8 ? pl.qp : nullptr;
     auto lin = [&](const rs_k2_q8& q, const float* A, int lda, const float* Wt, int Kp, int K, float* out, int ldc, long long M, int N, int flags,
                    const float* bias, const float* res, const int32_t* lens, int group) -> int {
         if (!i8 || !q.w) return gemm(A, lda, Wt, Kp, out, ldc, M, N, flags, bias, res);
@@ -1874,7 +1840,7 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
         const int hid = 3 * dd / 4, hidp = pad32(hid), vw = H * K2_VD, vwp = pad32(vw), nin = (2 * K2_QD + K2_PD) * H;
         const int32_t* lens = lens_all + (size_t)(1 + st) * B;
         const long long M = (long long)B * Ts;
-        float* stack_out = fp(pl.off_stackout[st]);
+        float* stack_out = pl.stackout[st];
         float* cur = x;
         float* nxt = x0;
         if (Ts > k.pos_cap) return rs_fail(ctx, RS_EINVAL, "zipformer: %d frames exceed the registered position tables (%d)", Ts, k.pos_cap);
@@ -1891,8 +1857,8 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
             if (L8.pos.w) {
                 // linear_pos of each utterance's own 2 len - 1 position rows, with its own scale, into a table per utterance
                 const int G = 2 * Ts - 1, P = d.pos_dim;
-                float *pos_in = fp(pl.off_pos_in), *pos_tab = fp(pl.off_pos_tab);
-                int32_t* lens2 = reinterpret_cast<int32_t*>(ws + pl.off_lens2);
+                float *pos_in = pl.pos_in, *pos_tab = pl.pos_tab;
+                int32_t* lens2 = pl.lens2;
                 hipLaunchKernelGGL(k2_pos_rows_kernel, dim3(G, B), dim3(64), 0, s, k.pos_enc, k.pos_cap, P, lens, Ts, pos_in, lens2);
                 RS_CHECK_LAUNCH(ctx, "zipformer (int8 mode) position rows");
                 RS_TRY(lin(L8.pos, pos_in, P, nullptr, P, P, pos_tab, H * K2_PD, (long long)B * G, H * K2_PD, 0, nullptr, nullptr, lens2, G));
@@ -1952,11 +1918,11 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
     K2Pieces pc{};
     {
         int n = 0, cur_dim = d.encoder_dim[d.n_stacks - 1];
-        pc.p[n] = fp(pl.off_stackout[d.n_stacks - 1]); pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
+        pc.p[n] = pl.stackout[d.n_stacks - 1]; pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
         for (int st = d.n_stacks - 2; st >= 0; --st) {
             const int dd = d.encoder_dim[st];
             if (dd > cur_dim) {
-                pc.p[n] = fp(pl.off_stackout[st]); pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
+                pc.p[n] = pl.stackout[st]; pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
                 cur_dim = dd;
             }
         }

@@ -405,12 +405,16 @@ namespace {
 
 struct EncPlan {
     int T[5], F[5];  // per stage time / freq extents (index 0 = mel)
-    size_t off_lens, off_sa, off_sb, off_x, off_hn, off_big, off_ctx, off_posp, off_stats, off_col, off_ctc, total;
+    int32_t* lens;
+    uint16_t *sa, *col, *sb;   // col: the gathered patch matrix ($RS_SUB_IM2COL), else nullptr
+    float* x;
+    uint16_t *hn, *big, *ctxb, *posp;
+    float *stats, *ctc;        // ctc: nullptr without a CTC head
     int chunk;       // Conv2dSubsampling: utterances per pass of conv0 / patch gather / dense-conv GEMM
-    size_t col_bytes = 0;   // > 0: the plan holds the gathered patch matrix ($RS_SUB_IM2COL)
 };
+constexpr size_t ENC_SLACK = 256;
 
-EncPlan plan_encoder(const rs_ctx* ctx, int B, int t_max) {
+EncPlan plan_encoder(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     const rs_dims& d = ctx->d;
     EncPlan p{};
     p.T[0] = t_max; p.F[0] = d.n_mels;
@@ -419,10 +423,8 @@ EncPlan plan_encoder(const rs_ctx* ctx, int B, int t_max) {
     const size_t Tp = p.T[d.sub_stages] > 0 ? p.T[d.sub_stages] : 1, M = (size_t)B * Tp;
     size_t widest = (size_t)d.ff_dim;
     if (3 * dm > widest) widest = 3 * dm;
-    size_t o = 0;
-    p.off_lens = o; o += rs_align((size_t)4 * B * 4);
+    p.lens = a.take<int32_t>((size_t)4 * B);
     p.chunk = B;
-    p.off_col = 0;
     if (d.sub_kind == 1) {
         // sa = conv0 output of ONE chunk of utterances [chunk][T1][F1][C]; sb = the dense conv's output of the WHOLE batch
         // [B][T2][F2][C].  The GEMM reads the 3 x 3 patches in place (rs_gemm_args.conv_C): the chunk keeps sa within the
@@ -430,36 +432,25 @@ EncPlan plan_encoder(const rs_ctx* ctx, int B, int t_max) {
         // col [chunk * T2 * F2][9C], the first form — 16 GB written and read again per 256 x 10 s, 4.2 ms) the chunk keeps col
         // near 1 GiB instead.
         const bool gathered = getenv("RS_SUB_IM2COL") != nullptr;
-        const size_t per_utt_col = (size_t)(p.T[2] > 0 ? p.T[2] : 1) * p.F[2] * 9 * C * 2;
-        const size_t per_utt_sa = (size_t)(p.T[1] > 0 ? p.T[1] : 1) * p.F[1] * C * 2;
-        size_t chunk = gathered ? ((size_t)1 << 30) / per_utt_col : ((size_t)1 << 31) / per_utt_sa;
-        if (chunk < 1) chunk = 1;
-        if (chunk > (size_t)B) chunk = (size_t)B;
-        while (chunk > 1 && chunk * (size_t)(p.T[1] > 0 ? p.T[1] : 1) > 65535) --chunk;   // grid limit of the conv0 / gather kernels
-        p.chunk = (int)chunk;
-        // The extents reserved for sa / col are the chunk's BOUND, not chunk * per-utterance: floor(bound / per_utt) * per_utt goes
-        // up and down with the length, and a caller that allocates for its longest geometry and runs shorter ones in the same
-        // workspace (rs_workspace_bytes is asked once per buffer set) must never be told that a shorter batch needs more.
-        const size_t sa_bound = (size_t)B * per_utt_sa < ((size_t)1 << 31) ? (size_t)B * per_utt_sa : ((size_t)1 << 31);
-        const size_t col_bound = (size_t)B * per_utt_col < ((size_t)1 << 30) ? (size_t)B * per_utt_col : ((size_t)1 << 30);
-        p.off_sa = o; o += rs_align(sa_bound > per_utt_sa ? sa_bound : per_utt_sa);
-        p.off_col = o; o += gathered ? rs_align(col_bound > per_utt_col ? col_bound : per_utt_col) : 0;
-        p.col_bytes = gathered ? chunk * per_utt_col : 0;
-        p.off_sb = o; o += rs_align((size_t)B * (p.T[2] > 0 ? p.T[2] : 1) * p.F[2] * C * 2);
+        const size_t T1 = p.T[1] > 0 ? p.T[1] : 1, T2 = p.T[2] > 0 ? p.T[2] : 1;
+        const rs_sub_chunk sa = rs_sub_chunk_rule(T1 * p.F[1] * C * 2, (size_t)1 << 31, T1, B);   // (grid limit of the conv0 / gather kernels)
+        const rs_sub_chunk col = rs_sub_chunk_rule(T2 * p.F[2] * 9 * C * 2, (size_t)1 << 30, T1, B);
+        p.chunk = gathered ? col.chunk : sa.chunk;
+        p.sa = a.take<uint16_t>(sa.reserve / 2);
+        p.col = gathered ? a.take<uint16_t>(col.reserve / 2) : nullptr;
+        p.sb = a.take<uint16_t>((size_t)B * T2 * p.F[2] * C);
     } else {
         const size_t sub_elems = (size_t)B * p.T[2] * p.F[2] * C;  // stage-2 extent is the largest stored one
-        p.off_sa = o; o += rs_align(sub_elems * 2);
-        p.off_sb = o; o += rs_align(sub_elems * 2);
+        p.sa = a.take<uint16_t>(sub_elems);
+        p.sb = a.take<uint16_t>(sub_elems);
     }
-    p.off_x = o; o += rs_align(M * dm * 4);
-    p.off_hn = o; o += rs_align(M * dm * 2);
-    p.off_big = o; o += rs_align(M * widest * 2);
-    p.off_ctx = o; o += rs_align(M * dm * 2);
-    p.off_posp = o; o += rs_align((2 * Tp) * dm * 2);
-    p.off_stats = o; o += rs_align(M * 2 * 4);          // (mean, rstd) per row of a deferred output norm
-    p.off_ctc = o;
-    if (d.ctc_vocab > 0) o += rs_align(M * (size_t)rs_ctc_pad(d.ctc_vocab) * 4);   // CTC logits when only the blank column is wanted
-    p.total = o + 256;
+    p.x = a.take<float>(M * dm);
+    p.hn = a.take<uint16_t>(M * dm);
+    p.big = a.take<uint16_t>(M * widest);
+    p.ctxb = a.take<uint16_t>(M * dm);
+    p.posp = a.take<uint16_t>((2 * Tp) * dm);
+    p.stats = a.take<float>(M * 2);                     // (mean, rstd) per row of a deferred output norm
+    p.ctc = d.ctc_vocab > 0 ? a.take<float>(M * (size_t)rs_ctc_pad(d.ctc_vocab)) : nullptr;   // CTC logits when only the blank column is wanted
     return p;
 }
 
@@ -476,7 +467,9 @@ size_t rs_workspace_bytes(const rs_ctx* ctx, int B, int max_samples) {
         const size_t m2 = fe > enc2 ? fe : enc2;
         return m2 > dec2 ? m2 : dec2;
     }
-    size_t enc = plan_encoder(ctx, B, t_max > 0 ? t_max : 1).total;
+    rs_arena measure;
+    plan_encoder(ctx, B, t_max > 0 ? t_max : 1, measure);
+    size_t enc = measure.bytes() + ENC_SLACK;
     if (ctx->has_f32) {                      // the float32 parity mode keeps float32 activations: about twice the scratch
         const size_t enc32 = rs_encoder_f32_workspace_bytes(ctx, B, t_max > 0 ? t_max : 1);
         if (enc32 > enc) enc = enc32;
@@ -527,18 +520,13 @@ int rs_encoder_forward(rs_ctx* ctx, const float* feats, const int32_t* n_frames,
     if (ctx->k2) return rs_k2_encoder_forward_impl(ctx, feats, n_frames, B, t_max, enc_out, joint_enc, enc_lens, workspace, workspace_bytes, s);
     if (ctx->precision_f32)
         return rs_encoder_forward_f32(ctx, feats, n_frames, B, t_max, enc_out, joint_enc, enc_lens, workspace, workspace_bytes, s);
-    const EncPlan pl = plan_encoder(ctx, B, t_max);
-    if (workspace_bytes < pl.total) return rs_fail(ctx, RS_EWORKSPACE, "encoder: workspace %zu < %zu", workspace_bytes, pl.total);
-    char* ws = reinterpret_cast<char*>(workspace);
-    int32_t* lens_stage = reinterpret_cast<int32_t*>(ws + pl.off_lens);
-    uint16_t* sa = reinterpret_cast<uint16_t*>(ws + pl.off_sa);
-    uint16_t* sb = reinterpret_cast<uint16_t*>(ws + pl.off_sb);
-    float* x = reinterpret_cast<float*>(ws + pl.off_x);
-    uint16_t* hn = reinterpret_cast<uint16_t*>(ws + pl.off_hn);
-    uint16_t* big = reinterpret_cast<uint16_t*>(ws + pl.off_big);
-    uint16_t* ctxb = reinterpret_cast<uint16_t*>(ws + pl.off_ctx);
-    uint16_t* posp = reinterpret_cast<uint16_t*>(ws + pl.off_posp);
-    float* ln_stats = reinterpret_cast<float*>(ws + pl.off_stats);
+    rs_arena arena(workspace);
+    const EncPlan pl = plan_encoder(ctx, B, t_max, arena);
+    if (workspace_bytes < arena.bytes() + ENC_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "encoder: workspace %zu < %zu", workspace_bytes, arena.bytes() + ENC_SLACK);
+    int32_t* const lens_stage = pl.lens;
+    uint16_t *const sa = pl.sa, *const sb = pl.sb, *const hn = pl.hn, *const big = pl.big, *const ctxb = pl.ctxb, *const posp = pl.posp;
+    float *const x = pl.x, *const ln_stats = pl.stats;
     const int C = d.sub_channels, dm = d.d_model, ff = d.ff_dim, S = d.sub_stages;
     const int Tp = pl.T[S], M = B * Tp;
     int rc;
@@ -550,12 +538,12 @@ int rs_encoder_forward(rs_ctx* ctx, const float* feats, const int32_t* n_frames,
     if (d.sub_kind == 1) {
         // ESPnet Conv2dSubsampling: conv0 (VALU) -> 3x3 patches -> dense conv as one GEMM per chunk of utterances (bias, ReLU,
         // rows past an utterance's T2 zeroed), into sb [B][T2][F2][C]
-        uint16_t* col = reinterpret_cast<uint16_t*>(ws + pl.off_col);
+        uint16_t* const col = pl.col;
         const int T1 = pl.T[1], F1 = pl.F[1], T2 = pl.T[2], F2 = pl.F[2];
         for (int b0 = 0; b0 < B; b0 += pl.chunk) {
             const int bc = B - b0 < pl.chunk ? B - b0 : pl.chunk;
             RS_TRY(rs_launch_sub2d_conv0(ctx, feats, lens_stage, b0, bc, t_max, T1, F1, sa, s));
-            const bool patches_in_place = pl.col_bytes == 0;                              // (plan_encoder: $RS_SUB_IM2COL)
+            const bool patches_in_place = col == nullptr;                                   // (plan_encoder: $RS_SUB_IM2COL)
             if (!patches_in_place) RS_TRY(rs_launch_im2col3x3s2(ctx, sa, bc, T1, F1, T2, F2, col, s));
             rs_gemm_args g{};
             if (patches_in_place) { g.A = sa; g.conv_C = C; g.conv_T1 = T1; g.conv_F1 = F1; g.conv_T2 = T2; g.conv_F2 = F2; }
@@ -677,7 +665,7 @@ int rs_encoder_forward(rs_ctx* ctx, const float* feats, const int32_t* n_frames,
                 ctx->jenc_b, 1.0f, nullptr));
     if (d.ctc_vocab > 0 && (ctx->ctc_probs || ctx->ctc_blank)) {
         // CTC posteriors of every frame: logits by the same GEMM family, softmax in place
-        float* z = ctx->ctc_probs ? ctx->ctc_probs : reinterpret_cast<float*>(ws + pl.off_ctc);
+        float* z = ctx->ctc_probs ? ctx->ctc_probs : pl.ctc;
         const int Vp = rs_ctc_pad(d.ctc_vocab);
         RS_TRY(gemm(hn, dm, ctx->ctc_w, dm, z, Vp, M, Vp, RS_GEMM_BIAS | RS_GEMM_OUT_F32, ctx->ctc_b, 1.0f, nullptr));
         RS_TRY(rs_launch_ctc_softmax(ctx, z, M, d.ctc_vocab, Vp, d.blank_id, ctx->ctc_blank, s));

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/rs_asr.h"
+#include "rs_arena.h"
 
 // ----------------------------------------------------------------------------------------
 // device helpers
@@ -195,8 +196,6 @@ int rs_fail(rs_ctx* ctx, int code, const char* fmt, ...);
 int rs_prof_class_index(int klass);
 void rs_prof_begin(rs_ctx* ctx, int klass, hipStream_t s, double flops, double bytes);
 void rs_prof_end(rs_ctx* ctx, int klass, hipStream_t s);
-
-static inline size_t rs_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // ----------------------------------------------------------------------------------------
 // kernel launchers (one per .hip file); all return RS_OK / RS_E*

@@ -186,6 +186,16 @@ def test_workspace_of_a_longer_geometry_covers_every_shorter_one(ctx):
     assert sizes[0] < sizes[-1]
 
 
+def test_workspace_of_a_longer_geometry_covers_every_shorter_one_in_float32(gpu_device):
+    """the same for a context with the float32 weights registered (`precision="fp32"`): its query is the larger of the bf16
+    and the float32 layouts, the float32 one dominates, and both reserve the subsampling chunk by the same rule"""
+    sd = synthetic_state_dict_espnet(ESPNET_TINY, 3)
+    ctx = EspnetModel(ESPNET_TINY, sd, synthetic_token_list(ESPNET_TINY.vocab_size, 3), device="cuda:0", precision="fp32").am.ctx
+    sizes = [ctx.workspace_bytes(96, n) for n in range(300000, 352001, 128)]
+    assert all(a <= b for a, b in zip(sizes, sizes[1:])), [(300000 + 128 * k, a, b) for k, (a, b) in enumerate(zip(sizes, sizes[1:])) if a > b][:4]
+    assert sizes[0] < sizes[-1]
+
+
 # ---- find_blank_batch against find_blank under "host" ----------------------------------------------------------------
 
 def test_find_blank_batch_equals_find_blank(tiny):
