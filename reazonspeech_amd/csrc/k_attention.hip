@@ -21,7 +21,6 @@
 // half is the previous block's upper half.  The per-row skew  bd[key][query] = BD^T[key - query + 31][query]
 // goes through a per-wave LDS scratch (conflict-free both ways: the query is the fastest index);
 // the same scratch first stages the 32 position rows (coalesced 256-byte reads from L2).
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
@@ -837,28 +836,17 @@ __global__ __launch_bounds__(64 * NW, WPE) void relpos_attention_stream_kernel(A
 }
 
 long long* g_attn_trace = nullptr;
-std::atomic<int> g_attn_persist{-1};         // -1: $RS_ATTN_PERSIST (default 0: measured slower) on first use
-int attn_persist() {
-    int v = g_attn_persist.load();
-    if (v < 0) { const char* e = getenv("RS_ATTN_PERSIST"); v = e ? atoi(e) : 0; g_attn_persist = v; }
-    return v;
-}
-std::atomic<int> g_attn_stream{-1};          // -1: $RS_ATTN_STREAM (default 0: measured slower, see the kernel's header) on first use
-int attn_stream() {
-    int v = g_attn_stream.load();
-    if (v < 0) { const char* e = getenv("RS_ATTN_STREAM"); v = e ? atoi(e) : 0; g_attn_stream = v; }
-    return v;
-}
 
 }  // namespace
 
 // debug hook (scripts/attn_trace.py): buffer of 40 int64 per workgroup, or nullptr to switch tracing off
 extern "C" void rs_debug_set_attn_trace(long long* buf) { g_attn_trace = buf; }
-// A/B hook: 1 = the streaming form for full attention (default), 0 = the staged kernel
-extern "C" void rs_debug_set_attn_stream(int v) { g_attn_stream = v; }
+// A/B hook: 1 = the streaming form for full attention, 0 = the staged kernel (default: the streaming form measured slower, see
+// the kernel's header)
+extern "C" void rs_debug_set_attn_stream(int v) { rs_knob_set(RS_KNOB_ATTN_STREAM, v); }
 // A/B hook: 1 = full attention runs on resident workgroups that walk the (query group, head, utterance) items (n >= 2: on
 // exactly n of them), 0 = one workgroup per item (default)
-extern "C" void rs_debug_set_attn_persist(int v) { g_attn_persist = v; }
+extern "C" void rs_debug_set_attn_persist(int v) { rs_knob_set(RS_KNOB_ATTN_PERSIST, v); }
 
 namespace {
 
@@ -894,30 +882,26 @@ int launch_attention_hd(rs_ctx* ctx, AttnParams& p, int B, int T, hipStream_t s)
     // 343.5 -> 386.4 us (head_dim 64, T' = 358): the hardware dispatcher refills a CU as soon as a workgroup's LDS is free,
     // an in-kernel item loop waits at its barrier for the slowest wave first.
     int resident = 0;
+    const int persist = rs_knob(RS_KNOB_ATTN_PERSIST), stream = rs_knob(RS_KNOB_ATTN_STREAM);
     auto persist_grid = [&](const dim3& g, size_t lds_bytes, int threads) {
-        if (attn_persist() <= 0 || window || p.trace) return false;
-        if (ctx->n_cus <= 0) {
-            int n = 0;
-            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
-            ctx->n_cus = n;
-        }
+        if (persist <= 0 || window || p.trace) return false;
         int per_cu = (int)((160 * 1024) / lds_bytes);
         const int by_threads = 2048 / threads;
         per_cu = per_cu < by_threads ? per_cu : by_threads;
         if (per_cu < 1) per_cu = 1;
-        resident = attn_persist() >= 2 ? attn_persist() : per_cu * ctx->n_cus;      // (>= 2: that many resident workgroups — tests)
+        resident = persist >= 2 ? persist : per_cu * rs_n_cus(ctx);      // (>= 2: that many resident workgroups — tests)
         p.n_groups = (int)g.x; p.n_heads = (int)g.y; p.n_items = (int)(g.x * g.y * g.z);
         return p.n_items > resident;                    // fewer items than slots: the classic grid is the same thing
     };
     {
         // the streaming form: full attention, any T ($RS_ATTN_STREAM=0: the staged kernel above, for the A/B)
-        if (attn_stream() > 0 && !window && !p.trace) {
+        if (stream > 0 && !window && !p.trace) {
             using S = SGeom<HD>;
             constexpr int NW = 5, NSLOT = 3, WPE = HD == 128 ? 3 : 4;
             const int qtiles = (T + 15) / 16, n_groups = (qtiles + NW - 1) / NW;
             const int n_items = n_groups * dm.n_heads * B;
             const size_t lds_s = (size_t)NSLOT * S::SLOT + (size_t)NW * S_SCR;
-            const int dbg = attn_stream() >> 4;
+            const int dbg = stream >> 4;
             auto kern = dbg ? relpos_attention_stream_kernel<HD, NW, NSLOT, WPE, true> : relpos_attention_stream_kernel<HD, NW, NSLOT, WPE, false>;
             if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)kern, (int)lds_s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_ATTN, s); return rc; }
             hipLaunchKernelGGL(kern, dim3(8 * ((n_items + 7) / 8)), dim3(64 * NW), lds_s, s, p, n_groups, dm.n_heads, n_items, dbg);
@@ -930,8 +914,7 @@ int launch_attention_hd(rs_ctx* ctx, AttnParams& p, int B, int T, hipStream_t s)
         // head_dim 64: small key chunks and fewer waves per workgroup so that TWO workgroups share a CU and the K / V staging of
         // one overlaps the products of the other (default 4 key blocks x 4 waves: 74 KB; $RS_ATTN64="kbc,nw" for the A/B,
         // "0" = the one-workgroup geometry).  Same order of the online softmax: bit-identical.
-        int kbc = 4, nwmax = 4;
-        if (const char* e = getenv("RS_ATTN64")) { kbc = atoi(e); const char* c = strchr(e, ','); nwmax = c ? atoi(c + 1) : 4; }
+        const int kbc = rs_knob(RS_KNOB_ATTN64), nwmax = rs_knob(RS_KNOB_ATTN64_NW);
         if (kbc > 0 && !window && !p.trace) {
             const int nw2 = qblocks < nwmax ? qblocks : (nwmax < 1 ? 1 : nwmax > 6 ? 6 : nwmax);
             const dim3 grid2((qblocks + nw2 - 1) / nw2, dm.n_heads, B), block2(64 * nw2);

@@ -879,7 +879,7 @@ extern "C" int rs_avsr_encoder_forward(rs_ctx* ctx, const float* input_values, c
     hipLaunchKernelGGL(avsr_mask_rows_kernel, blocks1d(N * dm), dim3(256), 0, s, h, padding_mask, dm, N * dm);
     {
         const int cg = dm / d.conv_pos_groups;
-        if (cg % 16 == 0 && cg <= 64 && !getenv("RS_AVSR_POSCONV_OLD")) {
+        if (cg % 16 == 0 && cg <= 64 && !rs_knob(RS_KNOB_AVSR_POSCONV_OLD)) {
             const size_t lds = (size_t)(64 + d.conv_pos) * (cg + 1) * 4;
             const dim3 grid((T + 63) / 64, d.conv_pos_groups, B);
 #define RS_AV_POS(NT)                                                                                                                         \

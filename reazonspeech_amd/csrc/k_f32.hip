@@ -790,8 +790,8 @@ int rs_launch_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, con
 #define RS_ATT_CASE(NV)                                                                                                  \
     hipLaunchKernelGGL((attention_f32_kernel<NV>), grid, block, 0, s, qkv, pos, bias_u, bias_v, lens, out, T, dm.d_model, hd, \
                        dm.att_left, dm.att_right, dm.n_global, scale)
-    static const bool one_wave_per_key_sum = getenv("RS_ATTN_F32_OLD") != nullptr;      // A/B and test hook: the first form
-    static const bool no_mfma = getenv("RS_ATTN_F32_KEYS") != nullptr;                 // A/B and test hook: the second form
+    const bool one_wave_per_key_sum = rs_knob(RS_KNOB_ATTN_F32_OLD) != 0;      // the first form
+    const bool no_mfma = rs_knob(RS_KNOB_ATTN_F32_KEYS) != 0;                  // the second form
     if (!one_wave_per_key_sum && !no_mfma && dm.att_left < 0 && dm.att_right < 0 && (hd == 64 || hd == 128)) {
         const dim3 grid16((T + 63) / 64, dm.n_heads, B);
         if (hd == 128) hipLaunchKernelGGL((attention_f32_mfma_kernel<128>), grid16, block, 0, s, qkv, pos, bias_u, bias_v, lens, out, T, dm.d_model, scale);

@@ -36,7 +36,6 @@
 #include <stdlib.h>
 
 #include <atomic>
-#include <mutex>
 
 #include "rs_common.h"
 
@@ -685,25 +684,12 @@ __global__ __launch_bounds__(512, 2) void gemm_smf16_kernel(GemmParams p) {
   }
 }
 
-// Process-wide A/B knobs (debug / tuning only; the defaults are the measured winners and nothing in the product path
-// writes them).  Atomics initialised once from the environment, so concurrent first launches from the encoder thread
-// and the decode workers are safe; they select code paths, not state, which is why they are not per context.
+// The launcher's switches are rows of rs_knobs.h: RS_GEMM_TILE (forced tile height; 0 = by shape), RS_GEMM_GROUP_M (row panels per XCD
+// tile group; 0 = by shape), RS_GEMM_PAIRS (2 = two tiles per workgroup with the LDS ring carried from the first into the second,
+// 1 = two tiles, the ring restarts, 0 = one tile per workgroup) and RS_GEMM_BREG (1 = 256- / 192-row launches keep the weight
+// operand out of LDS: fragment-major copy, global -> VGPR).  The defaults are the measured winners and nothing in the product
+// path writes them.
 std::atomic<long long*> g_trace{nullptr};
-std::atomic<int> g_tile{0};        // forced tile height (RS_GEMM_TILE / rs_debug_set_gemm_tile); 0 = by shape
-std::atomic<int> g_group_m{0};     // row panels per XCD tile group; 0 = by shape
-std::atomic<int> g_pairs{2};       // RS_GEMM_PAIRS: 2 = two tiles per workgroup with the LDS ring carried from the first into the second,
-                                   // 1 = two tiles, the ring restarts, 0 = one tile per workgroup
-std::atomic<int> g_breg{0};        // RS_GEMM_BREG: 1 = 256- / 192-row launches keep the weight operand out of LDS (fragment-major copy, global -> VGPR)
-void gemm_knobs_from_env() {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        auto env = [](const char* name, std::atomic<int>& v) { if (const char* e = getenv(name)) v = atoi(e); };
-        env("RS_GEMM_TILE", g_tile);
-        env("RS_GEMM_GROUP_M", g_group_m);
-        env("RS_GEMM_PAIRS", g_pairs);
-        env("RS_GEMM_BREG", g_breg);
-    });
-}
 
 // The fragment-major copy of a weight operand.  A registered tensor (rs_set_tensor: immutable for the life of the context) is
 // shuffled once and cached; anything else (tests, micro-benchmarks) is shuffled into a scratch on every launch.
@@ -739,7 +725,7 @@ int launch_smf16(rs_ctx* ctx, GemmParams& p, hipStream_t s) {
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + 255) / 256;
     const int ntiles = p.tiles_m * p.tiles_n;
-    p.pairs = p.trace ? 0 : g_pairs.load();
+    p.pairs = p.trace ? 0 : rs_knob(RS_KNOB_GEMM_PAIRS);
     int nwg;                                                      // 8 x the workgroups of the fullest XCD run (the others exit at once)
     {
         int np, ns;
@@ -753,7 +739,8 @@ int launch_smf16(rs_ctx* ctx, GemmParams& p, hipStream_t s) {
     }
     // row panels per XCD tile group (profiles/r02r_gemm_group_m_sweep.txt): N = 1024 (4 weight tiles) likes 2 panels at
     // K = 4096 and 6 below; one-tile-wide problems (the subsampling GEMMs) 16; everything else is flat from 6 up
-    p.group_m = g_group_m.load() > 0 ? g_group_m.load()
+    const int group_m = rs_knob(RS_KNOB_GEMM_GROUP_M);
+    p.group_m = group_m > 0 ? group_m
               : (p.tiles_n == 4 ? (p.K >= 4096 ? 2 : 6) : (p.K >= 4096 ? 4 : (p.tiles_n <= 8 && p.K <= 2560 ? 16 : 8)));
     const bool swoosh = p.flags & (RS_GEMM_SWOOSHL | RS_GEMM_SWOOSHR);
     const int out = (p.flags & RS_GEMM_RESIDUAL) ? (p.res_ln_stats ? OUT_RESLN : (p.out2 ? OUT_RES2 : OUT_RES))
@@ -766,7 +753,7 @@ int launch_smf16(rs_ctx* ctx, GemmParams& p, hipStream_t s) {
     }
     // register-resident weights ($RS_GEMM_BREG): the tall split-ring tiles of the FastConformer's epilogues, whole 64-column wave tiles
     if constexpr (BM >= 192) {
-        if (g_breg.load() > 0 && !p.trace && !mask && p.N % 64 == 0 && p.N >= 256 &&
+        if (rs_knob(RS_KNOB_GEMM_BREG) > 0 && !p.trace && !mask && p.N % 64 == 0 && p.N >= 256 &&
             (out == OUT_BF16 || out == OUT_RES || out == OUT_RESLN || out == OUT_F32 || out == OUT_GLU)) {
             if (int rc = wfm_operand(ctx, p.W, p.ldw, p.N, p.K, s, &p.Wfm); rc != RS_OK) return rc;
 #define RS_SMF_B(O)                                                                                                \
@@ -842,11 +829,11 @@ int pick_tile_height(int M, int N, int K, int n_cus, int flags) {
 }  // namespace
 
 // tuning hooks for A/B runs (scripts/gemm_bench.py, tests); not part of the public header
-extern "C" void rs_debug_set_gemm_tile(int bm) { gemm_knobs_from_env(); g_tile = bm; }
+extern "C" void rs_debug_set_gemm_tile(int bm) { rs_knob_set(RS_KNOB_GEMM_TILE, bm); }
 extern "C" void rs_debug_set_gemm_trace(long long* buf) { g_trace = buf; }
-extern "C" void rs_debug_set_gemm_group_m(int v) { gemm_knobs_from_env(); g_group_m = v; }
-extern "C" void rs_debug_set_gemm_pairs(int v) { gemm_knobs_from_env(); g_pairs = v; }
-extern "C" void rs_debug_set_gemm_breg(int v) { gemm_knobs_from_env(); g_breg = v; }
+extern "C" void rs_debug_set_gemm_group_m(int v) { rs_knob_set(RS_KNOB_GEMM_GROUP_M, v); }
+extern "C" void rs_debug_set_gemm_pairs(int v) { rs_knob_set(RS_KNOB_GEMM_PAIRS, v); }
+extern "C" void rs_debug_set_gemm_breg(int v) { rs_knob_set(RS_KNOB_GEMM_BREG, v); }
 extern "C" int rs_debug_gemm_tile_height(int M, int N, int K, int n_cus, int flags) { return pick_tile_height(M, N, K, n_cus > 0 ? n_cus : 256, flags); }
 
 static int launch_rows(rs_ctx* ctx, GemmParams& p, int bm, hipStream_t s) {
@@ -902,13 +889,8 @@ int rs_launch_gemm(rs_ctx* ctx, const rs_gemm_args& a, hipStream_t s) {
         for (int k = 0; k < 2 * (a.K / 64); ++k)
             if (((k * cv_inv) >> 16) != k / cv_tps) return rs_fail(ctx, RS_EINVAL, "gemm: K-tile reciprocal is not exact for C = %d", C);
     }
-    gemm_knobs_from_env();
-    if (ctx->n_cus <= 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
-        ctx->n_cus = n;
-    }
-    const int bm = g_tile.load() > 0 ? g_tile.load() : pick_tile_height(a.M, a.N, a.K, ctx->n_cus, a.flags);
+    const int tile = rs_knob(RS_KNOB_GEMM_TILE);
+    const int bm = tile > 0 ? tile : pick_tile_height(a.M, a.N, a.K, rs_n_cus(ctx), a.flags);
     if (bm != 256 && bm != 192 && bm != 128 && bm != 64) return rs_fail(ctx, RS_EINVAL, "gemm: RS_GEMM_TILE=%d (256, 192, 128 or 64)", bm);
     // the kernel addresses A and the output with 32-bit byte offsets: a taller problem runs as row chunks
     const size_t out_row = (size_t)a.ldc * (f32 ? 4 : 2), a_row = a.conv_C > 0 ? 2 : (size_t)a.lda * 2;   // (patches: the input size was checked above)

@@ -440,13 +440,11 @@ __global__ __launch_bounds__(256) void dwconv_act_kernel(const uint16_t* __restr
     }
 }
 
-int g_glu_generic = 0;
-
 }  // namespace
 
 // A/B hook (scripts/elementwise_bench.py): 1 = the generic any-kernel-size path, 2 = the f32-tile fast kernel also for the
 // gated layout (instead of the DMA-staged one)
-extern "C" void rs_debug_set_glu_generic(int v) { g_glu_generic = v; }
+extern "C" void rs_debug_set_glu_generic(int v) { rs_knob_set(RS_KNOB_GLU_GENERIC, v); }
 
 int rs_launch_layernorm(rs_ctx* ctx, const float* x, const float* g, const float* b, int M, int d, float eps,
                         uint16_t* out_bf16, float* out_f32, hipStream_t s) {
@@ -513,10 +511,11 @@ int rs_launch_glu_dwconv(rs_ctx* ctx, const uint16_t* x, int layout, const float
     if (k < 1 || k > KMAX || !(k & 1)) return rs_fail(ctx, RS_EINVAL, "glu_dwconv: kernel size %d unsupported", k);
     if (layout < 0 || layout > 2) return rs_fail(ctx, RS_EINVAL, "glu_dwconv: unknown input layout %d", layout);
     // the gated layout with a kernel size the sliding-window kernel is built for (the ESPnet conformer's k = 31)
-    if (layout == 2 && (k == 7 || k == 15 || k == 31) && g_glu_generic != 1) return rs_launch_dwconv_act(ctx, x, w, b, lens, B, T, d, k, 0, out, s);
+    const int glu_generic = rs_knob(RS_KNOB_GLU_GENERIC);
+    if (layout == 2 && (k == 7 || k == 15 || k == 31) && glu_generic != 1) return rs_launch_dwconv_act(ctx, x, w, b, lens, B, T, d, k, 0, out, s);
     const double bytes = (double)B * T * d * ((layout == 2 ? 2.0 : 4.0) + 2.0);
     rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), bytes);
-    if (k == 9 && g_glu_generic != 1) {
+    if (k == 9 && glu_generic != 1) {
         // register-window fast path (the FastConformer kernel size); 48-frame tiles
         constexpr int R = 6, TTF = 8 * R;
         const dim3 grid((T + TTF - 1) / TTF, d / CT, B), block(256);
@@ -528,7 +527,7 @@ int rs_launch_glu_dwconv(rs_ctx* ctx, const uint16_t* x, int layout, const float
         } while (0)
         if (layout == 0) RS_GLU_FAST(0);
         else if (layout == 1) RS_GLU_FAST(1);
-        else if (g_glu_generic == 2) RS_GLU_FAST(2);          // A/B: the f32-tile kernel on the gated layout
+        else if (glu_generic == 2) RS_GLU_FAST(2);          // A/B: the f32-tile kernel on the gated layout
         else hipLaunchKernelGGL((dwconv_silu_dma_kernel<9, R>), grid, block, 0, s, x, w, b, lens, T, d, out);
 #undef RS_GLU_FAST
     } else {

@@ -1006,8 +1006,7 @@ void launch_lstm_pred(rs_ctx* ctx, const DecodeState& st, int B, int rows_bound,
 
 // column-tile extent of a joint launch: a multiple of 8 when there is more than one row tile (see rnnt_tile_kernel)
 int joint_grid_x(int nct, int rts) {
-    static const bool off = getenv("RS_DECODE_NO_XCD") != nullptr;     // A/B hook
-    return rts > 1 && !off ? (nct + 7) / 8 * 8 : nct;
+    return rts > 1 && !rs_knob(RS_KNOB_DECODE_NO_XCD) ? (nct + 7) / 8 * 8 : nct;
 }
 
 int ensure_decode_lds(rs_ctx* ctx) {
@@ -1128,8 +1127,8 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
     // utterance — decode 3.7 - 3.8 ms against 2.9 - 3.4 ms of plain launches, -1 ... -2 ms only on 20 - 30 s utterances
     // and 40 ms for the first capture of a geometry — profiles/r03x_decode_graph_b1_ab.txt: not kept.)
     const int CHUNK = 16;
-    const bool lookahead = getenv("RS_DECODE_NO_LOOKAHEAD") == nullptr;   // A/B and test hook
-    const bool verify_wide = getenv("RS_VERIFY_WIDE") && atoi(getenv("RS_VERIFY_WIDE")) != 0;         // A/B and test hook: a workgroup per row for V <= 3072 too
+    const bool lookahead = !rs_knob(RS_KNOB_DECODE_NO_LOOKAHEAD);      // (tests/test_gpu_pipeline.py runs both)
+    const bool verify_wide = rs_knob(RS_KNOB_VERIFY_WIDE) != 0;         // a workgroup per row for V <= 3072 too
     int32_t host_counters[4] = {0, 0, 0, 0};
     int steps = 0, alive_bound = B;
     bool finished = false;
@@ -1187,7 +1186,7 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
         alive_bound = host_counters[2 + (steps & 1)];
     }
     rs_prof_end(ctx, RS_PROF_DECODE, s);
-    if (getenv("RS_DECODE_TRACE")) fprintf(stderr, "[decode trace] B=%d T'=%d: %d steps (screen %d, narrow %d, lookahead %d)\n", B, tp_max, steps, (int)screen, (int)narrow, (int)lookahead);
+    if (rs_knob(RS_KNOB_DECODE_TRACE)) fprintf(stderr, "[decode trace] B=%d T'=%d: %d steps (screen %d, narrow %d, lookahead %d)\n", B, tp_max, steps, (int)screen, (int)narrow, (int)lookahead);
     if (host_counters[1]) return rs_fail(ctx, RS_EOVERFLOW, "rnnt: an utterance emitted more than u_max=%d tokens", u_max);
     if (!finished) return rs_fail(ctx, RS_ESTATE, "rnnt: decode did not finish in %d steps", max_steps);
     return RS_OK;

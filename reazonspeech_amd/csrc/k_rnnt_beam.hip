@@ -655,8 +655,7 @@ BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max,
     if (R > 64) R = 64;
     if (R > max_pops) R = max_pops;
     bs.R = R;
-    int KS = 3;                                                      // evaluations asked for per iteration (the first is needed, the rest are guesses)
-    if (const char* e = getenv("RS_BEAM_SPEC")) KS = atoi(e);
+    const int KS = rs_knob(RS_KNOB_BEAM_SPEC);                       // evaluations asked for per iteration (the first is needed, the rest are guesses)
     bs.KS = KS < 1 ? 1 : KS > 8 ? 8 : KS;
     bs.RP = R + 32 + 1;                                              // batch + guesses of a frame + the needed one
     bs.rec_floats = 2 + 2 * beam_k;
@@ -738,10 +737,10 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     if (pl.step_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: beam %d x max_pops %d needs %zu bytes of LDS (> 150 KB): lower max_pops", bm, mp, pl.step_lds);
     if (pl.rec_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: vocabulary %d exceeds the record kernel's LDS", V);
     unsigned long long* const trace = bs.trace;
-    if (!getenv("RS_BEAM_TRACE")) bs.trace = nullptr;
+    if (!rs_knob(RS_KNOB_BEAM_TRACE)) bs.trace = nullptr;
     float* const a_pre = pl.a_pre;
 
-    const bool rec_lds = getenv("RS_BEAM_RECORD_LDS") != nullptr;   // test hook: the any-vocabulary variant on a small one
+    const bool rec_lds = rs_knob(RS_KNOB_BEAM_RECORD_LDS) != 0;     // test hook: the any-vocabulary variant on a small one
     auto record = rec_lds ? beam_record_kernel<0> : V <= 64 * 16 ? beam_record_kernel<16> : V <= 64 * 48 ? beam_record_kernel<48> : beam_record_kernel<0>;
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_step_kernel, (int)pl.step_lds); rc != RS_OK) return rc;
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_first_kernel, (int)pl.step_lds); rc != RS_OK) return rc;

@@ -1594,7 +1594,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     // ---- encoder_embed ------------------------------------------------------------------------------------------------
     rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
     hipLaunchKernelGGL(k2_conv0_kernel, dim3(pl.T1, B), dim3(256), 0, s, feats, t_max, pl.F, c1, k.conv0_w, k.conv0_b, a0);
-    static const bool conv1_first_form = getenv("RS_K2_CONV1_OLD") != nullptr;   // A/B and test hook (the form other channel counts run)
+    const bool conv1_first_form = rs_knob(RS_KNOB_K2_CONV1_OLD) != 0;   // the form other channel counts run
     if (c1 == 8 && c2 == 32 && pl.F2 <= 48 && !conv1_first_form) {
         hipLaunchKernelGGL(k2_conv1_mfma_kernel, dim3((pl.T2 + 4 * CONV1_TT - 1) / (4 * CONV1_TT), B), dim3(256), 0, s, a0, pl.T1, pl.F, pl.T2, pl.F2, k.conv1_w,
                            k.conv1_b, a1);
@@ -1604,18 +1604,13 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
         hipLaunchKernelGGL(k2_conv1_kernel, dim3(pl.T2, B), dim3(256), lds, s, a0, pl.T1, pl.F, c1, pl.T2, pl.F2, c2, k.conv1_w, k.conv1_b, a1);
     }
     const long long rows3 = (long long)B * T3 * F3;
-    static const bool conv2_fused_env = [] { const char* e = getenv("RS_K2_CONV2_FUSED"); return e ? atoi(e) != 0 : true; }();
-    const bool conv2_fused = (ctx->k2_conv2_fused < 0 ? conv2_fused_env : ctx->k2_conv2_fused != 0) && c2 == 32 && c3 == 128;
-    if (ctx->n_cus <= 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
-        ctx->n_cus = n;
-    }
+    const bool conv2_fused = (ctx->k2_conv2_fused < 0 ? rs_knob(RS_KNOB_K2_CONV2_FUSED) : ctx->k2_conv2_fused) != 0 && c2 == 32 && c3 == 128;
+    const int n_cus = rs_n_cus(ctx);
     if (conv2_fused) {
         // patches gathered into LDS, weights in registers: no patch matrix in HBM
         if (int rc2 = rs_ensure_dynamic_lds(ctx, (const void*)k2_conv2_fused_kernel, C2_LDS); rc2 != RS_OK) { rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s); return rc2; }
         const long long n_tiles = (rows3 + 127) / 128;
-        hipLaunchKernelGGL(k2_conv2_fused_kernel, dim3((unsigned)(n_tiles < ctx->n_cus ? n_tiles : ctx->n_cus)), dim3(512), C2_LDS, s, a1, pl.T2, pl.F2, T3, F3, k.conv2_w,
+        hipLaunchKernelGGL(k2_conv2_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), C2_LDS, s, a1, pl.T2, pl.F2, T3, F3, k.conv2_w,
                            pl.Kp, k.conv2_b, a2, rows3);
         rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
         RS_CHECK_LAUNCH(ctx, "zipformer encoder_embed convs");
@@ -1628,18 +1623,12 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
     hipLaunchKernelGGL(k2_cnx_dw_kernel<10>, dim3((T3 + CNX_TT - 1) / CNX_TT, B), dim3(256), 0, s, a2, lens3, T3, F3, c3, k.cnx_dw_w, k.cnx_dw_b, dwo);
     rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
-    static const bool cnx_fused_env = [] { const char* e = getenv("RS_K2_CNX_FUSED"); return e ? atoi(e) != 0 : true; }();
-    const bool cnx_fused = ctx->k2_cnx_fused < 0 ? cnx_fused_env : ctx->k2_cnx_fused != 0;
+    const bool cnx_fused = (ctx->k2_cnx_fused < 0 ? rs_knob(RS_KNOB_K2_CNX_FUSED) : ctx->k2_cnx_fused) != 0;
     if (cnx_fused && c3 == CX_C) {
         // both pointwise convolutions in one launch, the hidden tensor stays on the CU; result (bf16) in place over dwo
         RS_TRY(rs_ensure_dynamic_lds(ctx, (const void*)k2_cnx_pw_fused_kernel, CX_LDS));
-        if (ctx->n_cus <= 0) {
-            int n = 0;
-            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
-            ctx->n_cus = n;
-        }
         const long long n_tiles = (rows3 + CX_ROWS - 1) / CX_ROWS;
-        hipLaunchKernelGGL(k2_cnx_pw_fused_kernel, dim3((unsigned)(n_tiles < ctx->n_cus ? n_tiles : ctx->n_cus)), dim3(512), CX_LDS, s, dwo, k.cnx_pw1_w, k.cnx_pw1_b,
+        hipLaunchKernelGGL(k2_cnx_pw_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), CX_LDS, s, dwo, k.cnx_pw1_w, k.cnx_pw1_b,
                            k.cnx_pw2_w, k.cnx_pw2_b, a2, dwo, rows3);
         RS_CHECK_LAUNCH(ctx, "zipformer ConvNeXt pointwise pair");
     } else {
@@ -1686,7 +1675,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
                 if (lds > 64 * 1024) RS_TRY(rs_ensure_dynamic_lds(ctx, (const void*)k2_attn_weights_kernel, (int)lds));
                 if (Ts > k.pos_cap) return rs_fail(ctx, RS_EINVAL, "zipformer: %d frames exceed the registered position tables (%d)", Ts, k.pos_cap);
                 rs_prof_begin(ctx, RS_PROF_ATTN, s, (double)B * H * Ts * (double)Ts * (2.0 * K2_QD + 2.0 * K2_PD + 8.0) * 2.0, (double)B * H * Ts * (double)Tp * 2.0);
-                static const bool three_sweeps = getenv("RS_K2_ATTW_SWEEPS") != nullptr && atoi(getenv("RS_K2_ATTW_SWEEPS")) == 3;   // A/B and test hook
+                const bool three_sweeps = rs_knob(RS_KNOB_K2_ATTW_SWEEPS) == 3;
                 const dim3 grid((Ts + 63) / 64, H, B);
 #define RS_K2_ATTW1(NT)                                                                                                                     \
                 do {                                                                                                                        \

@@ -42,6 +42,19 @@ int rs_fail(rs_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
+int rs_n_cus(rs_ctx* ctx) {
+    if (ctx->n_cus <= 0) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->n_cus = n;
+    }
+    return ctx->n_cus;
+}
+
+// test and A/B hooks over the table of rs_knobs.h, by environment name (deliberately not in rs_asr.h, like rs_debug_conv3x3_f32)
+extern "C" int rs_debug_set_knob(const char* env_name, int value) { return rs_knob_set_named(env_name, value); }
+extern "C" int rs_debug_get_knob(const char* env_name, int* value) { return rs_knob_get_named(env_name, value); }
+
 int rs_ensure_dynamic_lds(rs_ctx* ctx, const void* func, int bytes) {
     static std::mutex mu;
     static std::set<std::pair<int, const void*>> done;
@@ -245,14 +258,14 @@ int rs_finalize(rs_ctx* ctx) {
             ctx->lstm_w4[l] = nullptr;
             if (ctx->tensors.count(nm)) { r.get(nm, 4 * H * 2 * H, ctx->lstm_w4[l]); if (r.rc != RS_OK) return r.rc; }
         }
-        // $RS_* A/B knobs are defaults: applied ONCE per context (rs_finalize runs again after every rs_set_tensor, e.g.
-        // when the position tables grow; a value chosen with rs_set_option must survive that)
+        // the environment's values of these rows are defaults: applied ONCE per context (rs_finalize runs again after every
+        // rs_set_tensor, e.g. when the position tables grow; a value chosen with rs_set_option must survive that)
         if (!ctx->env_read) {
             ctx->env_read = true;
-            if (const char* e = getenv("RS_DECODE_SCREEN")) ctx->decode_screen = atoi(e) != 0;     // 0 = exact evaluation of every column
-            if (const char* nw = getenv("RS_DECODE_NARROW")) ctx->decode_narrow = atoi(nw) != 0;   // 0 = the wide-tile kernels of round 1
-            if (const char* fg = getenv("RS_FUSE_GLU")) ctx->fuse_glu = atoi(fg) != 0;             // 0 = GLU in the conv kernel
-            if (const char* dn = getenv("RS_DEFER_OUT_NORM")) ctx->defer_out_norm = atoi(dn) != 0; // 0 = every output norm stores its f32 rows
+            if (rs_knob_given(RS_KNOB_DECODE_SCREEN)) ctx->decode_screen = rs_knob(RS_KNOB_DECODE_SCREEN) != 0;
+            if (rs_knob_given(RS_KNOB_DECODE_NARROW)) ctx->decode_narrow = rs_knob(RS_KNOB_DECODE_NARROW) != 0;
+            if (rs_knob_given(RS_KNOB_FUSE_GLU)) ctx->fuse_glu = rs_knob(RS_KNOB_FUSE_GLU) != 0;
+            if (rs_knob_given(RS_KNOB_DEFER_OUT_NORM)) ctx->defer_out_norm = rs_knob(RS_KNOB_DEFER_OUT_NORM) != 0;
         }
     }
     // optional: the float32 parity mode's dense weights ("<name>.f32", unrounded, the layouts of the bf16 tensors except
@@ -428,10 +441,10 @@ EncPlan plan_encoder(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     if (d.sub_kind == 1) {
         // sa = conv0 output of ONE chunk of utterances [chunk][T1][F1][C]; sb = the dense conv's output of the WHOLE batch
         // [B][T2][F2][C].  The GEMM reads the 3 x 3 patches in place (rs_gemm_args.conv_C): the chunk keeps sa within the
-        // kernel's 32-bit offsets (2 GiB here).  With $RS_SUB_IM2COL (A/B and test hook: the gathered patch matrix
+        // kernel's 32-bit offsets (2 GiB here).  With $RS_SUB_IM2COL (tests/test_gpu_knobs.py runs it: the gathered patch matrix
         // col [chunk * T2 * F2][9C], the first form — 16 GB written and read again per 256 x 10 s, 4.2 ms) the chunk keeps col
         // near 1 GiB instead.
-        const bool gathered = getenv("RS_SUB_IM2COL") != nullptr;
+        const bool gathered = rs_knob(RS_KNOB_SUB_IM2COL) != 0;
         const size_t T1 = p.T[1] > 0 ? p.T[1] : 1, T2 = p.T[2] > 0 ? p.T[2] : 1;
         const rs_sub_chunk sa = rs_sub_chunk_rule(T1 * p.F[1] * C * 2, (size_t)1 << 31, T1, B);   // (grid limit of the conv0 / gather kernels)
         const rs_sub_chunk col = rs_sub_chunk_rule(T2 * p.F[2] * 9 * C * 2, (size_t)1 << 30, T1, B);

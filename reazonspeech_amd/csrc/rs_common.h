@@ -9,6 +9,7 @@
 
 #include "../../include/rs_asr.h"
 #include "rs_arena.h"
+#include "rs_knobs.h"
 
 // ----------------------------------------------------------------------------------------
 // device helpers
@@ -141,20 +142,20 @@ struct rs_ctx {
     bool decode_screen = true;
     bool decode_narrow = true;      // narrow-tile LSTM / projection kernels (k_rnnt.hip)
     bool gemm_f32_x3 = false;       // rs_launch_gemm_f32 / rs_launch_conv3x3_f32 multiply with three bf16 terms per float32 product (k_f32.hip X3; avsr only)
-    int k2_conv2_fused = -1;        // Zipformer conv2 with its patches gathered into LDS: -1 = $RS_K2_CONV2_FUSED (default 1); rs_set_option("k2_conv2_fused")
-    int k2_cnx_fused = -1;          // Zipformer ConvNeXt pointwise pair as one kernel: -1 = $RS_K2_CNX_FUSED (default 1); rs_set_option("k2_cnx_fused")
+    int k2_conv2_fused = -1;        // Zipformer conv2 with its patches gathered into LDS: -1 = the table's RS_K2_CONV2_FUSED (default 1); rs_set_option("k2_conv2_fused")
+    int k2_cnx_fused = -1;          // Zipformer ConvNeXt pointwise pair as one kernel: -1 = the table's RS_K2_CNX_FUSED (default 1); rs_set_option("k2_cnx_fused")
     // position table cache: the caller registers "pos_table.<T>" tensors (bf16 [2T-1][d])
     // options (rs_set_option)
-    int n_cus = 0;                  // compute units of the device (queried on first use)
+    int n_cus = 0;                  // compute units of the device (rs_n_cus: queried on first use)
     int defer_out_norm = 1;         // 1 = a layer's output norm is applied by the next layer's first residual GEMM (f32 rows not stored); bit-identical to 0
     int fuse_glu = 1;               // conv module: 1 = GLU in the pw1 GEMM epilogue (every batch size: one rounding point, batch-invariant);
-                                    // 0 = plain pw1 product, GLU in the depthwise kernel ($RS_FUSE_GLU; A/B and layout tests)
+                                    // 0 = plain pw1 product, GLU in the depthwise kernel ($RS_FUSE_GLU; the layout tests set the option)
     bool has_f32 = false;           // the "*.f32" tensors of the float32 parity mode are registered (all or none)
     int precision_f32 = 0;          // rs_set_option("precision_f32"): 1 = rs_encoder_forward runs k_f32.hip's float32 encoder
     bool has_i8 = false;            // Zipformer: at least one quantized Linear ("<name>.i8") is registered
     int precision_i8 = 0;           // rs_set_option("precision_i8") (Zipformer only): the float32 encoder with its quantized Linears ("*.i8") on k_int8.hip
     rs_f32_weights f32;
-    bool env_read = false;          // the $RS_* defaults were applied (once, by the first rs_finalize; rs_set_option wins afterwards)
+    bool env_read = false;          // the table's context defaults were applied (once, by the first rs_finalize; rs_set_option wins afterwards)
     // parity taps (rs_encoder_set_taps): copies of the residual stream taken inside rs_encoder_forward
     float* tap_sub = nullptr;
     float* tap_layers = nullptr;
@@ -176,6 +177,8 @@ struct rs_ctx {
 int rs_ensure_dynamic_lds(rs_ctx* ctx, const void* func, int bytes);
 
 int rs_fail(rs_ctx* ctx, int code, const char* fmt, ...);
+// compute units of the context's device (256 when the query fails), cached in ctx->n_cus
+int rs_n_cus(rs_ctx* ctx);
 
 #define RS_HIP(ctx, call)                                                              \
     do {                                                                               \

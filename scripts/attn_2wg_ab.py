@@ -15,12 +15,18 @@ from reazonspeech_amd.runtime.synth import synthetic_batch  # noqa: E402
 from reazonspeech_amd.espnet.asr.model import EspnetModel, synthetic_token_list, PADDING  # noqa: E402
 
 
+def set_geometry(lib, mode):
+    """what $RS_ATTN64=mode would select (the library reads the environment once: in-process it is set through the table)"""
+    kbc, _, nw = mode.partition(",")
+    assert lib.rs_debug_set_knob(b"RS_ATTN64", int(kbc)) == 0 and lib.rs_debug_set_knob(b"RS_ATTN64_NW", int(nw or 4)) == 0
+
+
 def ab(am, waves, label, modes=("0", "4,4")):
     buf = am.stage(waves, buf=am.new_buffers(len(waves), max(len(w) for w in waves)))
     res = {}
     for rep in range(2):
         for mode in modes:
-            os.environ["RS_ATTN64"] = mode
+            set_geometry(am.ctx.lib, mode)
             am.run_device(buf)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -33,7 +39,7 @@ def ab(am, waves, label, modes=("0", "4,4")):
     times = "; ".join(f"[{m}] {res[m][0][0]:.2f} / {res[m][1][0]:.2f}" for m in modes)
     print(f"{label}: ms per batch (sequential, 2 repetitions) by $RS_ATTN64 = key blocks per chunk, waves per workgroup (0 = one workgroup "
           f"per CU: 6 blocks, 6 waves): {times}; joint projection and ids bit-identical across all: {same}", flush=True)
-    os.environ.pop("RS_ATTN64", None)
+    set_geometry(am.ctx.lib, "4,4")
     return same
 
 

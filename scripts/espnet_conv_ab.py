@@ -23,10 +23,7 @@ for B, ragged in ((256, False), (37, True), (1, False)):
     waves = [np.pad(audio[i, :lens[i]], PADDING) for i in range(B)]
     res = {}
     for mode in ("in_place", "im2col"):
-        if mode == "im2col":
-            os.environ["RS_SUB_IM2COL"] = "1"
-        else:
-            os.environ.pop("RS_SUB_IM2COL", None)
+        assert am.ctx.lib.rs_debug_set_knob(b"RS_SUB_IM2COL", int(mode == "im2col")) == 0      # (the library reads the environment once)
         buf = am.stage(waves, buf=am.new_buffers(B, max(len(w) for w in waves)))     # (the workspace plan depends on the mode)
         am.run_device(buf)
         torch.cuda.synchronize()
@@ -40,4 +37,4 @@ for B, ragged in ((256, False), (37, True), (1, False)):
     print(f"B={B} ragged={ragged}: in place {res['in_place'][0]:.2f} ms, gathered {res['im2col'][0]:.2f} ms per batch (sequential); "
           f"joint projection and ids bit-identical: {same}")
     assert same
-os.environ.pop("RS_SUB_IM2COL", None)
+am.ctx.lib.rs_debug_set_knob(b"RS_SUB_IM2COL", 0)

@@ -13,6 +13,7 @@ from reazonspeech_amd.runtime.synth import synthetic_batch
 from reazonspeech_amd.runtime.weights_espnet import synthetic_state_dict_espnet
 from reazonspeech_amd.espnet.asr.model import EspnetModel, synthetic_token_list
 from oracle import greedy as og
+from knobs import knob
 
 pytestmark = pytest.mark.gpu
 
@@ -83,20 +84,20 @@ def test_tiny_bit_exact(tiny, beam):
 
 
 @pytest.mark.parametrize("ks", ["1", "2", "8"])
-def test_guesses_do_not_change_results(tiny, monkeypatch, ks):
+def test_guesses_do_not_change_results(tiny, ks):
     """how many expansions are asked for ahead of need per iteration ($RS_BEAM_SPEC, default 3) is a scheduling matter"""
     model, sd, buf = tiny
     want = device_beam(model, buf, 10)
-    monkeypatch.setenv("RS_BEAM_SPEC", ks)
-    assert device_beam(model, buf, 10) == want
+    with knob(model.am.ctx.lib, "RS_BEAM_SPEC", int(ks)):
+        assert device_beam(model, buf, 10) == want
 
 
-def test_record_kernel_lds_variant(tiny, monkeypatch):
+def test_record_kernel_lds_variant(tiny):
     """vocabularies past 3072 entries take the record kernel that re-reads the row from LDS; forced here on the small one"""
     model, sd, buf = tiny
     want = device_beam(model, buf, 6)
-    monkeypatch.setenv("RS_BEAM_RECORD_LDS", "1")
-    assert device_beam(model, buf, 6) == want
+    with knob(model.am.ctx.lib, "RS_BEAM_RECORD_LDS", 1):
+        assert device_beam(model, buf, 6) == want
 
 
 def test_tiny_score_norm_off_and_empty_rows(tiny):

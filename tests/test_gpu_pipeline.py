@@ -23,6 +23,7 @@ from reazonspeech_amd.runtime.synth import synthetic_batch
 from reazonspeech_amd.runtime.tokenizer import SyntheticTokenizer
 from reazonspeech_amd.runtime.weights import synthetic_state_dict
 from oracle import model as om, greedy as og
+from knobs import knob
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "parakeet_tiny.npz")
@@ -120,12 +121,10 @@ def test_decode_bit_exact_given_same_encoder_output(tiny, gold):
 
 
 @pytest.mark.parametrize("lookahead,B", [(True, 37), (False, 37), (True, 3), (True, 150)])
-def test_decode_bit_exact_many_utterances(gpu_device, monkeypatch, lookahead, B):
+def test_decode_bit_exact_many_utterances(gpu_device, lookahead, B):
     """synthetic joint-encoder tensors straight into rs_rnnt_greedy: ragged lengths, an empty
     utterance, a batch that is not a multiple of the 16-row tile.  Small batches score several frames per utterance and step
     (look-ahead: 37 rows -> 4 frames, 3 rows -> 8, 150 rows -> 1 until the tail); $RS_DECODE_NO_LOOKAHEAD is the plain loop."""
-    if not lookahead:
-        monkeypatch.setenv("RS_DECODE_NO_LOOKAHEAD", "1")
     cfg = TINY
     sd = synthetic_state_dict(cfg, 11, blank_bias=4.0)
     model = AsrModel(cfg, sd, SyntheticTokenizer(cfg.vocab_size), device="cuda:0")
@@ -141,9 +140,10 @@ def test_decode_bit_exact_many_utterances(gpu_device, monkeypatch, lookahead, B)
     frames = torch.zeros_like(ids)
     n_ids = torch.zeros((B,), dtype=torch.int32, device=dev)
     ws = torch.empty((model.ctx.workspace_bytes(B, 16000),), dtype=torch.uint8, device=dev)
-    model.ctx.rnnt_greedy(f.to(dev), lens.to(dev), B, Tp, u_max, ids, frames, n_ids, ws,
-                          torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
+    with knob(model.ctx.lib, "RS_DECODE_NO_LOOKAHEAD", 0 if lookahead else 1):
+        model.ctx.rnnt_greedy(f.to(dev), lens.to(dev), B, Tp, u_max, ids, frames, n_ids, ws,
+                              torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
     ref = og.rnnt_greedy(cfg, sd, f.numpy(), lens.numpy())
     n = n_ids.cpu().numpy()
     assert sum(len(r[0]) for r in ref) > B, "test inputs should emit tokens"
