@@ -559,6 +559,30 @@ int rs_ctc_align(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_len
 int rs_ctc_find_blank(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_lens, const int32_t* n_samples,
                       int B, int tp_max, float threshold, int32_t* cuts /* [B][2] */, void* stream);
 
+/* ---- resample and down-mix a batch to the model's rate (added within ABI 7) ------------------------
+ * Replaces: norm_audio of the reference (pkg/nemo-asr/src/audio.py:54-68; the espnet and k2 packages have the same function):
+ * librosa.resample to 16 kHz, then librosa.to_mono — for a batch of recordings of ONE (rate, channel count), in one launch.
+ * The filter is the caller's: a linear-phase low-pass h of `numtaps` (odd) taps at the internal rate orig * up = target * down,
+ * up / down the reduced ratio (reazonspeech_amd/runtime/resample.py: plan(), the Kaiser-windowed sinc of the host path).
+ *   x        f32: the rows' [channels][row_len[b]] planes back to back; row b begins at x + row_off[b] (floats)
+ *   row_off  i64[B], row_len i32[B] (samples per channel)
+ *   table    f32[up][Jp], Jp = ceil(numtaps / up) rounded up to a multiple of 4: table[p][j] = up * h[p + j * up], 0 beyond numtaps
+ *   out      f32[B][out_pitch]: out[b][out_offset + n] = y[n] for n < n_out = ceil(row_len[b] * up / down),
+ *              y[n] = sum over m of xm[m] * table-entry(half + n * down - m * up),  half = (numtaps - 1) / 2,
+ *            where xm is the mean of the channels (sum in channel order, one division) and 0 outside the row — scipy's
+ *            resample_poly cut to librosa's length, up to float32 rounding: one fmaf per tap in increasing j = q - m,
+ *            q = (half + n * down) div up.  Every other element of the row, in front of out_offset and from out_offset + n_out
+ *            to out_pitch, is written 0: the layout rs_frontend_logmel reads (audio_stride = out_pitch).  Outputs that would
+ *            fall beyond out_pitch are not written.
+ *   out_lens i32[B] = n_out
+ * up = down = 1 with numtaps = 1 and table = {1, 0, 0, 0} is the down-mix alone.  A row's bits do not depend on the other rows of
+ * the launch.  No workspace; asynchronous on `stream`; no host round trip (csrc/k_resample.hip).  RS_EINVAL — before anything is
+ * enqueued — for a null context or pointer, B < 0, channels < 1, up / down / numtaps outside 1..2^24, an even numtaps, an
+ * out_offset outside 0..out_pitch, or a ratio whose window of 255 * down / up + 2 + Jp samples exceeds 16384 (the caller
+ * resamples such a rate on the host). */
+int rs_resample(rs_ctx* ctx, const float* x, const int64_t* row_off, const int32_t* row_len, int B, int channels, const float* table,
+                int up, int down, int numtaps, float* out, int64_t out_pitch, int out_offset, int32_t* out_lens, void* stream);
+
 /* ---- profiling hooks for bench.py (roofline.achieved) ------------------------------------
  * When enabled, the launcher brackets every launch of the selected kernel class with HIP
  * events on the launch stream.  rs_profile_read synchronises those events and returns the

@@ -28,6 +28,8 @@ int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* en
                       const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* ws, hipStream_t s);
 int rs_ctc_find_blank_impl(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_lens, const int32_t* n_samples, int B, int tp_max,
                            float threshold, int32_t* cuts, hipStream_t s);
+int rs_resample_impl(rs_ctx* ctx, const float* x, const int64_t* row_off, const int32_t* row_len, int B, int channels, const float* table,
+                     int up, int down, int numtaps, float* out, long long out_pitch, int out_offset, int32_t* out_lens, hipStream_t s);
 int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int u_max,
                         int32_t* ids, int32_t* frames, int32_t* n_ids, void* workspace, size_t workspace_bytes,
                         hipStream_t s);
@@ -810,6 +812,22 @@ int rs_ctc_find_blank(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_l
     if (B <= 0 || tp_max <= 0) return rs_fail(ctx, RS_EINVAL, "ctc_find_blank: B and tp_max must be positive, got B=%d tp_max=%d", B, tp_max);
     if (!blank_prob || !enc_lens || !n_samples || !cuts) return rs_fail(ctx, RS_EINVAL, "ctc_find_blank: null pointer");
     return rs_ctc_find_blank_impl(ctx, blank_prob, enc_lens, n_samples, B, tp_max, threshold, cuts, (hipStream_t)stream);
+}
+
+int rs_resample(rs_ctx* ctx, const float* x, const int64_t* row_off, const int32_t* row_len, int B, int channels, const float* table, int up,
+                int down, int numtaps, float* out, int64_t out_pitch, int out_offset, int32_t* out_lens, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (B < 0 || channels < 1) return rs_fail(ctx, RS_EINVAL, "resample: B must be >= 0 and channels >= 1, got B=%d channels=%d", B, channels);
+    if (up < 1 || down < 1 || up > (1 << 24) || down > (1 << 24))
+        return rs_fail(ctx, RS_EINVAL, "resample: up and down must lie in 1..2^24, got %d/%d", up, down);
+    if (numtaps < 1 || numtaps > (1 << 24) || numtaps % 2 == 0)
+        return rs_fail(ctx, RS_EINVAL, "resample: numtaps must be odd and at most 2^24, got %d", numtaps);
+    if (out_offset < 0 || out_pitch < out_offset)
+        return rs_fail(ctx, RS_EINVAL, "resample: out_offset %d outside the row pitch %lld", out_offset, (long long)out_pitch);
+    if (B == 0) return RS_OK;
+    if (!x || !row_off || !row_len || !table || !out || !out_lens) return rs_fail(ctx, RS_EINVAL, "resample: null pointer");
+    return rs_resample_impl(ctx, x, row_off, row_len, B, channels, table, up, down, numtaps, out, (long long)out_pitch, out_offset, out_lens,
+                            (hipStream_t)stream);
 }
 
 // ---- profiling -------------------------------------------------------------------------------------

@@ -49,7 +49,8 @@ class _AsrModelView:
 
 
 class EspnetModel:
-    def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host"):
+    def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host",
+                 resample="host"):
         assert cfg.espnet and len(token_list) == cfg.vocab_size
         self.segmentation = segmentation
         if beam_size is not None and int(beam_size) > 1:
@@ -57,7 +58,7 @@ class EspnetModel:
         self.beam_size = cfg.beam_size if cfg.decoding == "beam" else 1
         self.cfg = cfg
         self.token_list = list(token_list)
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision, resample=resample)
         self.device = self.am.device
         self.dtype = "float32"
         self._last_enc = self._last_ctc = None
@@ -136,6 +137,19 @@ class EspnetModel:
             out.scores += res.scores if res.scores is not None else [float("nan")] * buf.B
             out.degraded += [used != "beam"] * buf.B
         return out
+
+    # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option
+    @property
+    def resample(self):
+        return self.am.resample
+
+    @resample.setter
+    def resample(self, value):
+        from ...runtime.resample import check_mode
+        self.am.resample = check_mode(value)
+
+    def resample_batch(self, waveforms, rates):
+        return self.am.resample_batch(waveforms, rates)
 
     def recognize(self, samples):
         return self.recognize_batch([samples])[0]

@@ -9,8 +9,9 @@ import sys
 import numpy as np
 import torch
 
-from .audio import norm_audio
-from .interface import TranscribeConfig, TranscribeResult, Segment
+from ...runtime.resample import norm_batch
+from .audio import norm_audio, SAMPLERATE
+from .interface import AudioData, TranscribeConfig, TranscribeResult, Segment
 from .ctc import split_text, find_blank, segments_from_timings
 
 # Hyper parameters (transcribe.py:9-10)
@@ -22,7 +23,7 @@ CHECKPOINT_ENV = "REAZONSPEECH_ESPNET_CHECKPOINT"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False,
-               segmentation="host"):
+               segmentation="host", resample="host"):
     """Load the ReazonSpeech ESPnet model onto a ROCm GPU (transcribe.py:12-32).
 
     Args:
@@ -45,6 +46,9 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         rs_ctc_align launch for all windows of a `transcribe_batch` call (`EspnetModel.align_batch`), and the blank finder
         copies back the blank column only; `transcribe_batch` then takes recordings of any length and finds their cut points
         on the device too (rs_ctc_find_blank).  The results are the same; stored as `model.segmentation`, may be changed later.
+      resample (str): where input at another rate than 16 kHz, or with several channels, is normalised (`norm_audio`): "host"
+        (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count) group of a call
+        (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`.
 
     The reference downloads `reazon-research/reazonspeech-espnet-v2` through espnet_model_zoo (:27-31), which an offline box
     cannot do: give `checkpoint=` / the environment variable.  Without a checkpoint this RAISES; seeded synthetic weights of
@@ -53,8 +57,10 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
     from ...runtime.config import ESPNET_CONFORMER_120M
     from ...runtime.weights_espnet import synthetic_state_dict_espnet
     from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES
+    from ...runtime.resample import check_mode
     if segmentation not in SEGMENTATION_MODES:
         raise ValueError(f"segmentation must be one of {SEGMENTATION_MODES}, got {segmentation!r}")
+    check_mode(resample)
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if str(device).startswith("cpu"):
@@ -67,7 +73,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
             raise FileNotFoundError(f"checkpoint {checkpoint!r} does not exist")
         cfg, sd, tokens = read_espnet(checkpoint)
         return EspnetModel(cfg, sd, tokens, device=device, beam_size=20 if beam_size is None else beam_size, max_pops=max_pops,
-                           precision=precision, segmentation=segmentation)
+                           precision=precision, segmentation=segmentation, resample=resample)
     cfg = config or ESPNET_CONFORMER_120M
     if config is None:
         if not (synthetic or os.environ.get("REAZONSPEECH_AMD_SYNTHETIC", "0") not in ("", "0")):
@@ -78,7 +84,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
               "(`synthetic=True` / $REAZONSPEECH_AMD_SYNTHETIC): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
     return EspnetModel(cfg, synthetic_state_dict_espnet(cfg, seed), synthetic_token_list(cfg.vocab_size, seed), device=device,
                        beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision,
-                       segmentation=segmentation)
+                       segmentation=segmentation, resample=resample)
 
 
 def _windows(model, waveform, window):
@@ -148,7 +154,7 @@ def transcribe(model, audio, config=None):
     recognised and aligned as one batch.
     """
     config = config or TranscribeConfig()
-    audio = norm_audio(audio)
+    audio = AudioData(norm_batch(model, [audio], norm_audio)[0], SAMPLERATE)
     rate = audio.samplerate
     total = len(audio.waveform)
     texts, segments = [], []
@@ -176,7 +182,7 @@ def transcribe_batch(model, audios, config=None):
     caller with ONE long file passes `[audio]`: its windows are then recognised and aligned as a batch, not one at a time."""
     if config is None:
         config = TranscribeConfig(verbose=False)
-    norm = [norm_audio(a) for a in audios]
+    norm = [AudioData(w, SAMPLERATE) for w in norm_batch(model, audios, norm_audio)]
     window = int(WINDOW_SECONDS * 16000)
     if getattr(model, "segmentation", "host") == "device":
         return _transcribe_pooled(model, norm, window)

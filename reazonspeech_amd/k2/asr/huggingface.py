@@ -57,7 +57,7 @@ def resolve_checkpoint(language, precision, checkpoint=None):
 
 
 def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
-               decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0):
+               decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host"):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -86,6 +86,10 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
         `sherpa_onnx.OfflineRecognizer.from_transducer` with its defaults.  "greedy_search" is what the reference passes (:81);
         "modified_beam_search" keeps `max_active_paths` (1..8, default 4) hypotheses per utterance (rs_rnnt_mbs,
         csrc/k_rnnt_mbs.hip: no LM, no hotwords).  Valid with every `precision` / `compute`; anything else raises ValueError.
+      resample (str): where `transcribe` / `transcribe_batch` normalise input at another rate than 16 kHz or with several channels
+        (`norm_audio`): "host" (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count)
+        group of a call (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`;
+        anything else raises ValueError.  `K2Model.decode_streams` still expects 16 kHz streams.
 
     A real icefall export has never been read by runtime/k2_onnx.py (no file is reachable from the build environment): the reader
     is verified against files written in the documented export layout only, and checks itself after loading (every expected
@@ -99,9 +103,11 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     from ...runtime.k2_weights import synthetic_state_dict_k2
     from .model import K2Model, read_tokens, synthetic_tokens
     repo_files(language, precision)                       # argument errors first, like the reference
+    from ...runtime.resample import check_mode
+    check_mode(resample)
     from .model import search_config
     search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty)
-    search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty)
+    search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):

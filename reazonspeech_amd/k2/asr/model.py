@@ -79,7 +79,7 @@ def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blan
 
 class K2Model:
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
-                 decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None):
+                 decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host"):
         """decoding_method / max_active_paths / blank_penalty: sherpa_onnx.OfflineRecognizer.from_transducer's keywords with its
         defaults (pkg/k2-asr/src/huggingface.py:73-83 passes "greedy_search"): "modified_beam_search" keeps max_active_paths (1..8)
         hypotheses per utterance (csrc/k_rnnt_mbs.hip, rs_rnnt_mbs); valid with every precision — the search only consumes the
@@ -89,6 +89,7 @@ class K2Model:
         float32 mode with three-term bf16 products; "int8" = onnxruntime's int8 graph restated (the "int8" / "int8-fp32" files):
         the float32 mode with every Linear of `qweights` ({icefall name: (Wq int8 [out][in], sw, zw)}: read_k2_onnx_quantized or
         quantize_k2_linears) as a dynamically quantized MatMul, scales per utterance; `state_dict` then holds the dequantized weights
+        resample: "host" / "device": where `transcribe` / `transcribe_batch` normalise their input (runtime/resample.py)
         pos_cap: rows of relative positions the resident position tables start with (|rel| < pos_cap; None = the runtime's default);
         a longer utterance grows them (AsrModel.ensure_pos_cap), so this only moves the first growth"""
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
@@ -97,8 +98,21 @@ class K2Model:
         self.tokens = list(tokens)
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded
         cap = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, **cap)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, **cap)
         self.device = self.am.device
+
+    # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option
+    @property
+    def resample(self):
+        return self.am.resample
+
+    @resample.setter
+    def resample(self, value):
+        from ...runtime.resample import check_mode
+        self.am.resample = check_mode(value)
+
+    def resample_batch(self, waveforms, rates):
+        return self.am.resample_batch(waveforms, rates)
 
     # ---- sherpa-onnx's surface ------------------------------------------------------------------------------------------
     def create_stream(self):

@@ -2,15 +2,26 @@
 silence on both sides, warn above TOO_LONG_SECONDS, decode one stream, pair tokens with timestamps."""
 import warnings
 
-from .interface import TranscribeConfig, TranscribeResult, Subword
-from .audio import pad_audio, norm_audio
+from ...runtime.resample import norm_batch
+from .interface import AudioData, TranscribeConfig, TranscribeResult, Subword
+from .audio import pad_audio, norm_audio, SAMPLERATE
 
 PAD_SECONDS = 0.9
 TOO_LONG_SECONDS = 30.0
 
 
+def _prepare_batch(model, audios):
+    """`_prepare` for a list, normalised where `model.resample` says (host or device): -> [AudioData]"""
+    return [_pad_and_warn(AudioData(w, SAMPLERATE)) for w in norm_batch(model, audios, norm_audio)]
+
+
 def _prepare(audio):
-    audio = pad_audio(norm_audio(audio), PAD_SECONDS)
+    return _pad_and_warn(norm_audio(audio))
+
+
+def _pad_and_warn(audio):
+    """16 kHz mono in: the reference's padding and its warning"""
+    audio = pad_audio(audio, PAD_SECONDS)
     duration = audio.waveform.shape[0] / audio.samplerate
     if duration > TOO_LONG_SECONDS:      # the reference's warning (transcribe.py:27-34): upstream's memory grows with T^2
         warnings.warn(
@@ -43,7 +54,7 @@ def transcribe(model, audio, config=None):
     """
     if config is None:
         config = TranscribeConfig()
-    audio = _prepare(audio)
+    audio = _prepare_batch(model, [audio])[0]
     stream = model.create_stream()
     stream.accept_waveform(audio.samplerate, audio.waveform)
     model.decode_stream(stream)
@@ -55,8 +66,7 @@ def transcribe_batch(model, audios, config=None):
     `transcribe` (every kernel masks by the utterance's own length).  The search (greedy or modified beam search) is the one the
     model was built with (`load_model(decoding_method=...)`)."""
     streams = []
-    for a in audios:
-        a = _prepare(a)
+    for a in _prepare_batch(model, audios):
         st = model.create_stream()
         st.accept_waveform(a.samplerate, a.waveform)
         streams.append(st)

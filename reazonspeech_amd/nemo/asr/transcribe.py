@@ -10,11 +10,13 @@ post-processor expects (interface.Hypothesis).
 import os
 import sys
 
+import numpy as np
 import torch
 
 from .interface import TranscribeConfig, Hypothesis
 from .decode import decode_hypothesis, PAD_SECONDS
 from .audio import norm_audio
+from ...runtime.resample import norm_batch
 
 #: where a real checkpoint is looked for; the reference downloads
 #: 'reazon-research/reazonspeech-nemo-v2' from the HF hub (transcribe.py:26-28), which an
@@ -58,7 +60,7 @@ SYNTHETIC_ENV = "REAZONSPEECH_AMD_SYNTHETIC"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, decoding=None, beam_size=None,
-               precision="bf16", synthetic=False):
+               precision="bf16", synthetic=False, resample="host"):
     """Load the ReazonSpeech FastConformer-RNNT model onto a ROCm GPU.
 
     Args:
@@ -83,6 +85,11 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         "fp32x3": the float32 mode with every float32 PRODUCT of its GEMMs formed from three bf16 matrix-core terms (hi / lo split,
         float32 accumulation): twice the float32 mode's speed; not an IEEE chain, but every id of the 256-row float32-oracle goldens
         is reproduced (tests/test_gpu_fullsize.py).
+      resample (str): where input at another rate than 16 kHz, or with several channels, is normalised (`norm_audio`: resample,
+        then average the channels).  "host" (default) = scipy / soxr on the calling thread, one utterance at a time, as before;
+        "device" = one HIP launch per (rate, channel count) group of a `transcribe_batch` call (`AsrModel.resample_batch`,
+        rs_resample) with the host path's Kaiser filter — float32 rounding apart from the host path's result without soxr.
+        Stored as `model.resample`, may be changed later.  Anything else raises ValueError.
       pos_cap (int): encoder frames (80 ms each) the resident relative-position tables cover at load time
         (default 1024, about 82 s); longer utterances grow the tables on first use.
 
@@ -93,7 +100,9 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     from ...runtime.model import AsrModel
     from ...runtime.tokenizer import SentencePieceTokenizer, SyntheticTokenizer
     from ...runtime import weights as W
+    from ...runtime.resample import check_mode
 
+    check_mode(resample)
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if str(device).startswith("cpu"):
@@ -127,13 +136,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         cfg = cfg.with_(beam_size=int(beam_size))
     cfg.validate()
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-    return AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, **kw)
-
-
-def _prepare(audio):
-    """16 kHz mono float32 waveform (transcribe.py:44 minus the padding, which the kernel applies)"""
-    import numpy as np
-    return np.ascontiguousarray(norm_audio(audio).waveform, dtype=np.float32)
+    return AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, **kw)
 
 
 def transcribe_batch(model, audios, config=None, distributed=False):
@@ -152,7 +155,8 @@ def transcribe_batch(model, audios, config=None, distributed=False):
     """
     if config is None:
         config = TranscribeConfig()
-    waves = [_prepare(a) for a in audios]
+    # 16 kHz mono float32 waveforms (transcribe.py:44 minus the padding, which the kernel applies)
+    waves = [np.ascontiguousarray(w, dtype=np.float32) for w in norm_batch(model, audios, norm_audio)]
     if config.verbose:
         # the reference forwards `verbose` to NeMo (transcribe.py:52), which draws a tqdm bar on stderr
         print(f"[reazonspeech_amd] transcribing {len(waves)} utterance(s), "

@@ -42,6 +42,7 @@ EXPORTS = [
     "rs_avsr_search_state_bytes_opts", "rs_avsr_search_begin_opts", "rs_avsr_search_step_opts", "rs_avsr_search_peek_opts",
     "rs_avsr_search_finish_opts", "rs_avsr_generate_state_bytes_opts", "rs_avsr_generate_opts",
     "rs_ctc_align_workspace_bytes", "rs_ctc_align", "rs_ctc_find_blank",
+    "rs_resample",
 ]
 
 
@@ -236,6 +237,7 @@ def load():
     lib.rs_ctc_align_workspace_bytes.restype = c_size_t
     lib.rs_ctc_align.argtypes = [vp, vp, c_int, vp, c_int, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, c_size_t, vp]
     lib.rs_ctc_find_blank.argtypes = [vp, vp, vp, vp, c_int, c_int, c_float, vp, vp]
+    lib.rs_resample.argtypes = [vp, vp, vp, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, c_int64, c_int, vp, vp]
     if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
@@ -470,6 +472,15 @@ class Context:
         on `stream`."""
         self.check(self.lib.rs_ctc_find_blank(self._h, _ptr(blank_prob), _ptr(enc_lens), _ptr(n_samples), int(B), int(tp_max),
                                               float(threshold), _ptr(cuts), c_void_p(stream)))
+
+    def resample(self, x, row_off, row_len, B, channels, table, up, down, numtaps, out, out_offset, out_lens, stream):
+        """norm_audio for a batch of one (rate, channel count) (include/rs_asr.h rs_resample): x f32 = the rows' [channels][len]
+        planes back to back, row_off i64 [B] (floats), row_len i32 [B], table f32 [up][Jp] (runtime/resample.py: plan) -> out f32
+        [B][pitch] with row b at out[b][out_offset:], zeros elsewhere, and out_lens i32 [B].  Asynchronous on `stream`."""
+        assert out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1
+        self.check(self.lib.rs_resample(self._h, _ptr(x), _ptr(row_off), _ptr(row_len), int(B), int(channels), _ptr(table), int(up),
+                                        int(down), int(numtaps), _ptr(out), out.stride(0), int(out_offset), _ptr(out_lens),
+                                        c_void_p(stream)))
 
     # ---- profiling ----
     def profile_enable(self, mask):

@@ -130,11 +130,16 @@ class _BufView:
 
 class AsrModel:
     def __init__(self, cfg: ModelConfig, state_dict, tokenizer, device="cuda", pos_cap: int = DEFAULT_POS_CAP,
-                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None):
-        """precision: "bf16" = the throughput mode (bf16 GEMM operands, float32 accumulation and residual stream);
+                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host"):
+        """resample: where the packages' `norm_audio` work (resample to 16 kHz, average the channels) is done for input at another
+        rate or with several channels: "host" (default) = scipy / soxr per utterance as before, "device" = `resample_batch`.
+        precision: "bf16" = the throughput mode (bf16 GEMM operands, float32 accumulation and residual stream);
         "fp32" = the parity mode: float32 weights, activations and arithmetic end to end, what the reference computes
         (pkg/nemo-asr/src/transcribe.py:26-28, :48-53) — about 20x slower, 2.4 GB more weights."""
         cfg.validate()
+        from .resample import check_mode
+        self.resample = check_mode(resample)
+        self._resample_tables = {}      # rate -> the plan's table on the device
         if precision not in ("bf16", "fp32", "fp32x3", "int8"):
             raise ValueError(f"precision must be 'bf16', 'fp32', 'fp32x3' or 'int8', not {precision!r}")
         # "int8" (the Zipformer family): onnxruntime's int8 graph restated — the float32 mode with every quantized Linear of
@@ -577,6 +582,77 @@ class AsrModel:
             buf.audio.copy_(buf.h_audio, non_blocking=True)
             buf.lens.copy_(buf.h_lens, non_blocking=True)
         return buf
+
+    RESAMPLE_CHUNK = 1 << 28        # float32 samples (1 GiB) one rs_resample launch takes in, and at most writes
+
+    def resample_batch(self, waveforms, rates) -> List[np.ndarray]:
+        """`norm_audio` for a list on the device: waveforms[i] ([L] or [channels, L], any float type) at rates[i] Hz -> float32
+        16 kHz mono arrays, in the caller's order.  The list is grouped by (rate, channel count); each group is uploaded and
+        resampled by rs_resample (csrc/k_resample.hip) in chunks of at most RESAMPLE_CHUNK raw samples, and the rows are copied
+        back into host arrays (the callers — staging, espnet's window planning, k2's padding — consume host arrays).  The filter
+        is runtime/resample.py: plan(rate), also when soxr is installed.  16 kHz mono input passes through (as float32); a rate
+        whose filter the kernel does not take (more than 2^24 taps, or a window that does not fit its LDS) goes through the host
+        path with a warning.  A row's result does not depend on what else is in the list."""
+        from . import resample as rs
+        assert len(waveforms) == len(rates)
+        out = [None] * len(waveforms)
+        groups = {}
+        for i, (w, r) in enumerate(zip(waveforms, rates)):
+            w = np.asarray(w)
+            if w.ndim not in (1, 2):
+                raise ValueError(f"waveform {i}: expected [L] or [channels, L], got shape {w.shape}")
+            if int(r) == rs.SAMPLERATE and (w.ndim == 1 or w.shape[0] == 1):
+                out[i] = np.ascontiguousarray(w.reshape(-1), dtype=np.float32)
+                continue
+            groups.setdefault((int(r), 1 if w.ndim == 1 else w.shape[0]), []).append(i)
+        for (rate, channels), members in groups.items():
+            try:
+                pl = rs.plan(rate)
+                rs.check_window(pl)
+            except ValueError as e:             # only these two: any other refusal by rs_resample is a bug and raises
+                for i in members:
+                    out[i] = rs.host_fallback(waveforms[i], rate, str(e))
+                continue
+            lo = 0
+            while lo < len(members):            # a chunk: raw samples and padded output both within RESAMPLE_CHUNK (one row always fits)
+                hi, raw, longest = lo, 0, 0
+                while hi < len(members):
+                    n = np.asarray(waveforms[members[hi]]).shape[-1]
+                    if hi > lo and (raw + n * channels > self.RESAMPLE_CHUNK or (hi - lo + 1) * rs.n_out(max(longest, n), pl.up, pl.down) > self.RESAMPLE_CHUNK):
+                        break
+                    raw, longest, hi = raw + n * channels, max(longest, n), hi + 1
+                chunk = members[lo:hi]
+                rows = self._resample_chunk([waveforms[i] for i in chunk], rate, channels, pl)
+                for i, row in zip(chunk, rows):
+                    out[i] = row
+                lo = hi
+        return out
+
+    def _resample_chunk(self, waves, rate, channels, pl):
+        """one rs_resample launch: rows of one (rate, channels) -> [float32 array]"""
+        from . import resample as rs
+        host, offs, lens = rs.pack_rows(waves, channels)
+        n_outs = [rs.n_out(n, pl.up, pl.down) for n in lens]
+        pitch = max((max(n_outs) + 63) // 64 * 64, 64)
+        B = len(waves)
+        with torch.cuda.device(self.device):
+            x = torch.from_numpy(host).to(self.device)
+            row_off = torch.tensor(offs, dtype=torch.int64).to(self.device)
+            row_len = torch.tensor(lens, dtype=torch.int32).to(self.device)
+            out = torch.empty((B, pitch), dtype=torch.float32, device=self.device)
+            out_lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+            self.ctx.resample(x, row_off, row_len, B, channels, self.resample_table(rate, pl), pl.up, pl.down, pl.numtaps, out, 0,
+                              out_lens, torch.cuda.current_stream().cuda_stream)
+            h_out, h_lens = out.cpu(), out_lens.cpu().tolist()
+        assert h_lens == n_outs, (h_lens, n_outs)
+        return [h_out[b, :n].numpy().copy() for b, n in enumerate(n_outs)]
+
+    def resample_table(self, rate, pl):
+        """the plan's phase-major table on the device, uploaded once per rate"""
+        table = self._resample_tables.get(rate)
+        if table is None:
+            table = self._resample_tables[rate] = torch.from_numpy(pl.table.copy()).to(self.device)
+        return table
 
     def collect(self, buf, host=None, decoding=None) -> DecodedBatch:
         """hypotheses of a decoded batch as host lists; `host` = the (n_ids, ids, frames, enc_lens, scores) tensors a
