@@ -583,6 +583,50 @@ int rs_ctc_find_blank(rs_ctx* ctx, const float* blank_prob, const int32_t* enc_l
 int rs_resample(rs_ctx* ctx, const float* x, const int64_t* row_off, const int32_t* row_len, int B, int channels, const float* table,
                 int up, int down, int numtaps, float* out, int64_t out_pitch, int out_offset, int32_t* out_lens, void* stream);
 
+/* ---- AV-HuBERT feature extraction: raw audio and mouth crops in (added within ABI 7) ------------------
+ * Replaces: AVHubertFeatureExtractor.__call__ of the reference (pkg/avsr/src/avhubert/feature_extraction_avhubert.py:120-158,
+ * :199-232; reazonspeech_amd/avsr/feature_extraction.py is the host path these are pinned to) for decoded input: 16 kHz float32
+ * samples and uint8 mouth crops.  The extractor exists without a model, so both take a device index and a stream instead of a
+ * context (like rs_stream_create); the tables are the caller's (reazonspeech_amd/runtime/avsr_features.py: plan()).  No workspace;
+ * asynchronous on `stream`; no host round trip (csrc/k_avsr_features.hip).  They return RS_EINVAL — before anything is enqueued —
+ * for the arguments listed below, RS_EHIP when the device cannot be selected or a launch is refused, and set no error text.
+ *
+ * rs_avsr_logfbank: one launch per batch, python_speech_features.logfbank with its defaults + the 4-frame stacker + F.layer_norm.
+ *   audio    f32: the clips back to back; clip b is audio[row_off[b] .. row_off[b] + row_len[b])
+ *   row_off  i64[B] (floats), row_len i32[B] (samples; < 0: a clip without audio — its rows are zeros)
+ *   twiddle  f32[256][2] = (cos, -sin)(2 pi j / 512), 8-byte aligned
+ *   fb_idx   i32[26][2] = (first bin, tap count <= RS_AVSR_FBANK_MAXW) of each triangular filter,
+ *   fb_w     f32[26][RS_AVSR_FBANK_MAXW] its taps: the mel filterbank of logfbank, banded
+ *   out      f32[B][T][26 * stack]:
+ *     s'[0] = s[0], s'[i] = s[i] - 0.97 s[i-1] over the whole clip;  frame f = s'[160 f .. 160 f + 400), 0 beyond the clip;
+ *     frames = 1 if n <= 400 else 1 + ceil((n - 400) / 160);
+ *     E[f][m] = sum_k fb[m][k] * |DFT512(frame f)[k]|^2 / 512 over the bins k = 0 .. 256;
+ *     L[f][m] = logf(E[f][m] == 0 ? 2.220446e-16 : E[f][m])           (float64 machine epsilon; the accurate logf)
+ *     row r = L[stack r .. stack r + stack) flattened, frames >= `frames` as zeros (not log(eps)); rows >= ceil(frames / stack)
+ *     are all zero;  normalize != 0: (x - mean) / sqrt(var + 1e-5) over the 26 * stack features of every row < T, two-pass,
+ *     biased variance, no affine (a zero row stays exactly 0).
+ *   All of it in float32 (the host path evaluates logfbank in float64).  A row's bits do not depend on the other rows of the launch.
+ *   RS_EINVAL: a null pointer (B > 0), B < 0, T < 1, stack outside 1..8, a misaligned twiddle table.
+ *
+ * rs_avsr_pixels: one launch per group of clips whose frames share (H, W, channels).
+ *   frames     u8 [n_frames][H][W] grey or [n_frames][H][W][3] BGR, the group's clips back to back, 4-byte aligned
+ *   frame_idx  i32[B][idx_pitch]: the source frame of output frame (b, t < T) — the nearest-frame alignment to the audio rate is
+ *              the caller's; -1 (or an index >= n_frames) = a padding frame or a clip without video: grey level 0; < -1 = the
+ *              output frame belongs to another launch and is not written
+ *   lut        f32[256]: the value of each grey level, (float32(u) / 255 - mean) / std as the host path rounds it
+ *   out        f32[B][T][crop][crop], 16-byte aligned:
+ *     out[b][t][y][x] = lut[grey(frames[frame_idx[b][t]][top + y][left + x])],
+ *     grey(B, G, R) = (1868 B + 9617 G + 4899 R + 8192) >> 14 in integers (OpenCV's 8-bit COLOR_BGR2GRAY) for channels == 3.
+ *   RS_EINVAL: a null pointer (B > 0), B < 0, T < 1, n_frames < 0, H / W < 1, crop no positive multiple of 4 (the model takes
+ *   multiples of 8), a crop window outside the frame
+ *   (top < 0, left < 0, top + crop > H, left + crop > W), channels not 1 or 3, idx_pitch < T, misaligned frames / out. */
+#define RS_AVSR_FBANK_FILTERS 26
+#define RS_AVSR_FBANK_MAXW 48
+int rs_avsr_logfbank(int device, const float* audio, const int64_t* row_off, const int32_t* row_len, int B, int T, int stack,
+                     int normalize, const float* twiddle, const int32_t* fb_idx, const float* fb_w, float* out, void* stream);
+int rs_avsr_pixels(int device, const uint8_t* frames, int64_t n_frames, int H, int W, int channels, const int32_t* frame_idx,
+                   int idx_pitch, int B, int T, int crop, int top, int left, const float* lut, float* out, void* stream);
+
 /* ---- profiling hooks for bench.py (roofline.achieved) ------------------------------------
  * When enabled, the launcher brackets every launch of the selected kernel class with HIP
  * events on the launch stream.  rs_profile_read synchronises those events and returns the

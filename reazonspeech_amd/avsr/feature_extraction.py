@@ -1,6 +1,6 @@
 """`AVHubertFeatureExtractor` of `reazonspeech.avsr` (pkg/avsr/src/avhubert/feature_extraction_avhubert.py:16-241): raw audio and
-grey mouth-region video -> `input_values` [B][T][104], `pixel_values` [B][T][1][88][88], `padding_mask` [B][T].  Host code (numpy);
-the model runs on the device.
+grey mouth-region video -> `input_values` [B][T][104], `pixel_values` [B][T][1][88][88], `padding_mask` [B][T].  Host code (numpy) by
+default; with `features="device"` the same three tensors are made on the device (runtime/avsr_features.py), where the model runs.
 
 What is restated here: log filterbank features + stacking + per-frame layer norm (:120-137, :226), the image transform (centre crop,
 / 255, normalise: :37-44), the audio / video time alignment (:139-158) and batch padding (:199-232).  What needs packages this image
@@ -14,15 +14,9 @@ import os
 
 import numpy as np
 
+from ..runtime.avsr_features import mel_matrix, align_index, crop_window, resolve_features, FEATURE_MODES
+
 IMAGE_MEAN, IMAGE_STD = 0.421, 0.165
-
-
-def _hz2mel(hz):
-    return 2595.0 * np.log10(1.0 + hz / 700.0)
-
-
-def _mel2hz(mel):
-    return 700.0 * (10.0 ** (mel / 2595.0) - 1.0)
 
 
 def logfbank(signal, samplerate=16000, winlen=0.025, winstep=0.01, nfilt=26, nfft=512, preemph=0.97):
@@ -38,15 +32,7 @@ def logfbank(signal, samplerate=16000, winlen=0.025, winstep=0.01, nfilt=26, nff
     padded = np.concatenate([signal, np.zeros(((frames - 1) * fstep + flen - n,))])
     idx = np.arange(flen)[None, :] + (np.arange(frames) * fstep)[:, None]
     pspec = np.square(np.abs(np.fft.rfft(padded[idx], nfft))) / nfft
-    melpoints = np.linspace(_hz2mel(0.0), _hz2mel(samplerate / 2.0), nfilt + 2)
-    bins = np.floor((nfft + 1) * _mel2hz(melpoints) / samplerate)
-    fb = np.zeros((nfilt, nfft // 2 + 1))
-    for j in range(nfilt):
-        for i in range(int(bins[j]), int(bins[j + 1])):
-            fb[j, i] = (i - bins[j]) / (bins[j + 1] - bins[j])
-        for i in range(int(bins[j + 1]), int(bins[j + 2])):
-            fb[j, i] = (bins[j + 2] - i) / (bins[j + 2] - bins[j + 1])
-    feat = pspec @ fb.T
+    feat = pspec @ mel_matrix(samplerate, nfilt, nfft).T
     return np.log(np.where(feat == 0, np.finfo(float).eps, feat))
 
 
@@ -54,9 +40,17 @@ class AVHubertFeatureExtractor:
     model_input_names = ["input_values", "pixel_values"]
 
     def __init__(self, max_sample_size=None, normalize=True, stack_order_audio=4, image_crop_size=88, image_mean=IMAGE_MEAN, image_std=IMAGE_STD,
-                 sr=16000, **kwargs):
+                 sr=16000, features=None, device="cuda", **kwargs):
+        """features: None ($REAZONSPEECH_AVSR_FEATURES, default "host") | "host" (numpy on the calling thread, numpy arrays out) |
+        "device" (rs_avsr_logfbank / rs_avsr_pixels on `device`: the raw samples and uint8 mouth crops are uploaded and `__call__`
+        returns the same three keys, with the same shapes, as float32 torch tensors on the device; runtime/avsr_features.py).
+        Kept as `.features` and may be changed later.  A batch the kernels do not take — video frames that are not uint8, an
+        `image_crop_size` that is no multiple of 4 — goes through the host path as a whole, with one warning, and is uploaded.  The device path is pinned to this file's host path — `pixel_values` to the
+        bit, `input_values` to float32 rounding of the same algorithm — and the host path stays as it is: it runs logfbank's
+        pre-emphasis in float64 where the reference's python_speech_features runs it in float32 (finding 4)."""
         self.max_sample_size, self.normalize, self.stack_order_audio = max_sample_size, normalize, stack_order_audio
         self.image_crop_size, self.image_mean, self.image_std, self.sr = image_crop_size, image_mean, image_std, sr
+        self.features, self.device = resolve_features(features), device
 
     @classmethod
     def from_pretrained(cls, path, **kwargs):
@@ -72,10 +66,20 @@ class AVHubertFeatureExtractor:
         args.update(kwargs)
         return cls(**args)
 
-    def _load_audio(self, audio):
+    @staticmethod
+    def _refuse_audio_file(audio):
         if isinstance(audio, str):
             raise RuntimeError("decoding an audio file needs librosa (feature_extraction_avhubert.py:131), which this image does not have: "
                                "pass the 16 kHz samples as a float array")
+
+    @staticmethod
+    def _refuse_video_file(video, extract_mouth):
+        if isinstance(video, str) or extract_mouth:
+            raise RuntimeError("decoding a video file / extracting the mouth region needs cv2 and mediapipe "
+                               "(feature_extraction_avhubert.py:55-118), which this image does not have: pass grey mouth crops uint8 [T][H][W]")
+
+    def _load_audio(self, audio):
+        self._refuse_audio_file(audio)
         fb = logfbank(np.asarray(audio, dtype=np.float32), samplerate=self.sr).astype(np.float32)
         k = self.stack_order_audio                                        # :121-129 stacker
         if len(fb) % k:
@@ -83,9 +87,7 @@ class AVHubertFeatureExtractor:
         return fb.reshape(-1, k * fb.shape[1])
 
     def _load_video(self, video, extract_mouth=False):
-        if isinstance(video, str) or extract_mouth:
-            raise RuntimeError("decoding a video file / extracting the mouth region needs cv2 and mediapipe "
-                               "(feature_extraction_avhubert.py:55-118), which this image does not have: pass grey mouth crops uint8 [T][H][W]")
+        self._refuse_video_file(video, extract_mouth)
         v = np.asarray(video)
         if v.ndim == 4:
             # colour frames -> grey (:72-73 cv2.cvtColor(frame, COLOR_BGR2GRAY)): [UPSTREAM] OpenCV's 8-bit path is fixed point,
@@ -98,7 +100,7 @@ class AVHubertFeatureExtractor:
         """:37-44: CenterCrop(image_crop_size), scale to [0, 1], Normalize(mean, std)"""
         c = self.image_crop_size
         h, w = frames.shape[-2:]
-        top, left = int(round((h - c) / 2.0)), int(round((w - c) / 2.0))
+        top, left = crop_window(h, w, c)
         x = frames[..., top:top + c, left:left + c].astype(np.float32)
         if frames.dtype == np.uint8:
             x = x / 255.0
@@ -107,6 +109,17 @@ class AVHubertFeatureExtractor:
     def __call__(self, raw_audio=None, raw_video=None, extract_mouth=False, **kwargs):
         raw_audio = raw_audio if isinstance(raw_audio, list) else [raw_audio]
         raw_video = raw_video if isinstance(raw_video, list) else [raw_video]
+        if self.features not in FEATURE_MODES:
+            raise ValueError(f"features={self.features!r}: one of {FEATURE_MODES}")
+        if self.features == "device":
+            for a, v in zip(raw_audio, raw_video):
+                self._refuse_audio_file(a)
+                self._refuse_video_file(v, extract_mouth and v is not None)
+            from ..runtime import avsr_features
+            return avsr_features.extract_batch(self, raw_audio, raw_video, self.device)
+        return self._extract_host(raw_audio, raw_video, extract_mouth)
+
+    def _extract_host(self, raw_audio, raw_video, extract_mouth=False):
         audio = [self._load_audio(a) if a is not None else None for a in raw_audio]
         video = [self._load_video(v, extract_mouth) if v is not None else None for v in raw_video]
         c = self.image_crop_size
@@ -118,7 +131,7 @@ class AVHubertFeatureExtractor:
                 video[i] = np.zeros((audio[i].shape[0], 1, c, c), np.uint8)
         for i, (a, v) in enumerate(zip(audio, video)):                    # :139-158 nearest-frame alignment of the video to the audio rate
             if len(a) != len(v):
-                idx = np.minimum(np.floor(np.arange(len(a), dtype=np.float32) * len(v) / len(a)), len(v) - 1).astype(np.int64)
+                idx = align_index(len(a), len(v))
                 video[i] = v[idx]
         T = max(len(a) for a in audio)
         iv, pv, pm = [], [], []

@@ -30,6 +30,10 @@ int rs_ctc_find_blank_impl(rs_ctx* ctx, const float* blank_prob, const int32_t* 
                            float threshold, int32_t* cuts, hipStream_t s);
 int rs_resample_impl(rs_ctx* ctx, const float* x, const int64_t* row_off, const int32_t* row_len, int B, int channels, const float* table,
                      int up, int down, int numtaps, float* out, long long out_pitch, int out_offset, int32_t* out_lens, hipStream_t s);
+hipError_t rs_avsr_logfbank_launch(const float* audio, const int64_t* row_off, const int32_t* row_len, int B, int T, int stack, int normalize,
+                                   const float* twiddle, const int32_t* fb_idx, const float* fb_w, float* out, hipStream_t s);
+hipError_t rs_avsr_pixels_launch(const uint8_t* frames, long long n_frames, int H, int W, int channels, const int32_t* frame_idx, int idx_pitch,
+                                 int B, int T, int crop, int top, int left, const float* lut, float* out, hipStream_t s);
 int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int u_max,
                         int32_t* ids, int32_t* frames, int32_t* n_ids, void* workspace, size_t workspace_bytes,
                         hipStream_t s);
@@ -828,6 +832,48 @@ int rs_resample(rs_ctx* ctx, const float* x, const int64_t* row_off, const int32
     if (!x || !row_off || !row_len || !table || !out || !out_lens) return rs_fail(ctx, RS_EINVAL, "resample: null pointer");
     return rs_resample_impl(ctx, x, row_off, row_len, B, channels, table, up, down, numtaps, out, (long long)out_pitch, out_offset, out_lens,
                             (hipStream_t)stream);
+}
+
+// the avsr feature kernels run without a context: select `device` for the launch, and leave the caller's current device as it was
+namespace {
+struct rs_device_scope {
+    int cur = -1, dev;
+    bool ok;
+    explicit rs_device_scope(int device) : dev(device) {
+        ok = hipGetDevice(&cur) == hipSuccess && (cur == dev || hipSetDevice(dev) == hipSuccess);
+    }
+    ~rs_device_scope() {
+        if (ok && cur != dev) (void)hipSetDevice(cur);
+    }
+};
+}  // namespace
+
+int rs_avsr_logfbank(int device, const float* audio, const int64_t* row_off, const int32_t* row_len, int B, int T, int stack, int normalize,
+                     const float* twiddle, const int32_t* fb_idx, const float* fb_w, float* out, void* stream) {
+    if (B < 0 || T < 1 || stack < 1 || stack > 8) return RS_EINVAL;
+    if (B == 0) return RS_OK;
+    if (!audio || !row_off || !row_len || !twiddle || !fb_idx || !fb_w || !out) return RS_EINVAL;
+    if ((uintptr_t)twiddle & 7) return RS_EINVAL;
+    rs_device_scope scope(device);
+    if (!scope.ok) return RS_EHIP;
+    return rs_avsr_logfbank_launch(audio, row_off, row_len, B, T, stack, normalize != 0, twiddle, fb_idx, fb_w, out, (hipStream_t)stream) == hipSuccess
+               ? RS_OK : RS_EHIP;
+}
+
+int rs_avsr_pixels(int device, const uint8_t* frames, int64_t n_frames, int H, int W, int channels, const int32_t* frame_idx, int idx_pitch,
+                   int B, int T, int crop, int top, int left, const float* lut, float* out, void* stream) {
+    if (B < 0 || T < 1 || n_frames < 0 || H < 1 || W < 1 || crop < 4 || crop % 4) return RS_EINVAL;   // 16-byte stores: four pixels of a row
+    if (channels != 1 && channels != 3) return RS_EINVAL;
+    if (top < 0 || left < 0 || crop > H || crop > W || top > H - crop || left > W - crop) return RS_EINVAL;
+    if (idx_pitch < T) return RS_EINVAL;
+    if (B == 0) return RS_OK;
+    if (!frames || !frame_idx || !lut || !out) return RS_EINVAL;
+    if (((uintptr_t)frames & 3) || ((uintptr_t)out & 15)) return RS_EINVAL;
+    rs_device_scope scope(device);
+    if (!scope.ok) return RS_EHIP;
+    return rs_avsr_pixels_launch(frames, (long long)n_frames, H, W, channels, frame_idx, idx_pitch, B, T, crop, top, left, lut, out,
+                                 (hipStream_t)stream) == hipSuccess
+               ? RS_OK : RS_EHIP;
 }
 
 // ---- profiling -------------------------------------------------------------------------------------

@@ -43,6 +43,7 @@ EXPORTS = [
     "rs_avsr_search_finish_opts", "rs_avsr_generate_state_bytes_opts", "rs_avsr_generate_opts",
     "rs_ctc_align_workspace_bytes", "rs_ctc_align", "rs_ctc_find_blank",
     "rs_resample",
+    "rs_avsr_logfbank", "rs_avsr_pixels",
 ]
 
 
@@ -238,6 +239,8 @@ def load():
     lib.rs_ctc_align.argtypes = [vp, vp, c_int, vp, c_int, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, c_size_t, vp]
     lib.rs_ctc_find_blank.argtypes = [vp, vp, vp, vp, c_int, c_int, c_float, vp, vp]
     lib.rs_resample.argtypes = [vp, vp, vp, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, c_int64, c_int, vp, vp]
+    lib.rs_avsr_logfbank.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp]
+    lib.rs_avsr_pixels.argtypes = [c_int, vp, c_int64, c_int, c_int, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp]
     if lib.rs_abi_version() != 7:
         raise ImportError("librs_asr.so ABI version mismatch")
     _lib = lib
