@@ -484,8 +484,8 @@ int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
  * replaces: the search inside sherpa_onnx.OfflineRecognizer.from_transducer(..., decoding_method="modified_beam_search",
  * max_active_paths=K) — the second offline transducer method of the constructor the reference builds its recognizer with
  * (pkg/k2-asr/src/huggingface.py:73-83 passes "greedy_search" = rs_rnnt_greedy) — as model.decode_stream(stream) runs it
- * (pkg/k2-asr/src/transcribe.py:39).  [UPSTREAM, not vendored] OfflineTransducerModifiedBeamSearchDecoder::Decode without LM /
- * hotwords, Hypotheses::Add, GetMostProbable(length_norm):
+ * (pkg/k2-asr/src/transcribe.py:39).  [UPSTREAM, not vendored] OfflineTransducerModifiedBeamSearchDecoder::Decode without LM
+ * (hotwords: rs_rnnt_mbs_hotwords below), Hypotheses::Add, GetMostProbable(length_norm):
  *   per utterance one starting hypothesis, ys = [-1, blank] (context_size = 2), log_prob = 0.  For every frame t < enc_lens[b]
  *   with the H <= K live hypotheses: logits[h] = output_linear(tanh(f[b][t] + decoder_proj(decoder(last 2 tokens of h))));
  *   logits[h][blank] -= blank_penalty; lp[h][v] = log_softmax(logits[h])[v] + log_prob[h]; the K largest of the H x V values
@@ -511,6 +511,72 @@ size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_path
 int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
                 float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- hotwords (contextual biasing) in the modified beam search — added within ABI 7 ---------------
+ * replaces: the `hotwords_file=` / `hotwords_score=` keywords of sherpa_onnx.OfflineRecognizer.from_transducer and
+ * `create_stream(hotwords=...)`, as the modified_beam_search applies them.  [UPSTREAM, not vendored, PARITY UNPINNED]
+ * sherpa-onnx's ContextGraph (Build, FillFailOutput, ForwardOneStep(strict_mode = false), Finalize) and its use in
+ * OfflineTransducerModifiedBeamSearchDecoder::Decode, restated:
+ *   graph: a trie over the token ids of the phrases; root: token -1, level 0, node_score 0, fail = root.  Phrase i has score s_i.
+ *   A token that creates a node: token_score = s_i, node_score = parent.node_score + s_i; a token that meets a node:
+ *   token_score = max(s_i, token_score), node_score = parent.node_score + token_score; both: is_end |= (last token of the phrase),
+ *   output_score = is_end ? node_score : 0.  Fail links breadth-first (children of the root fail to the root; child c of cur on
+ *   token t: follow f = cur.fail, f.fail, ... to the first node with a child on t — that child — else the root); c.output = the
+ *   first is_end node on c.fail, c.fail.fail, ... before the root (none otherwise), c.output_score += c.output.output_score.
+ *   step(state, token) -> (delta, next):  state has a child n on the token: score = n.token_score.  Otherwise n = state.fail;
+ *   while n has no child on the token: n = n.fail, stop at the root; n = that child if there is one;
+ *   score = n.node_score - state.node_score.  n.output_score != 0 (the non-strict exit): out = n.is_end ? n.node_score :
+ *   n.output ? n.output.node_score : n.node_score; delta = (score + out) - n.node_score, next = root.  Otherwise
+ *   delta = score + n.output_score, next = n.
+ *   Finalize(state): delta = -state.node_score.
+ *   in the search (steps 4 - 5 of rs_rnnt_mbs): the starting hypothesis of an utterance with a graph carries context_state = the
+ *   graph's root.  The K best of the H x V values are selected as in rs_rnnt_mbs, WITHOUT any bonus.  A selected candidate that
+ *   appends a label v: (delta, state') = step(parent.context_state, v), log_prob = lp[h][v] + delta, context_state = state'; one
+ *   that appends nothing keeps its parent's state.  Merging as in rs_rnnt_mbs (logaddexp of the log_probs with their bonuses); the
+ *   tokens, timestamps AND context state of the one added first stay.  After the utterance's last frame every hypothesis of the
+ *   final set gets log_prob += -node_score(context_state); then the winner is chosen, by the rule and tie rule of rs_rnnt_mbs.
+ *   scores[b] = the winner's log_prob after that.  An utterance without a graph is searched exactly as by rs_rnnt_mbs.
+ * All numbers float32 in the order csrc/k_rnnt_mbs.hip states and tests/k2_hotwords_checker.c restates (bit for bit); scores that
+ * are multiples of 0.5 make every graph quantity exact.
+ *
+ * rs_hotwords: the graphs of a call as flat arrays, all graphs concatenated (node and child indices are global):
+ *   child_begin i32[n_nodes + 1]   CSR: the children of node n are the entries child_begin[n] .. child_begin[n + 1] - 1 of
+ *   child_tok / child_node i32[n_children]   token (ascending within a node) and node of each child
+ *   fail i32[n_nodes], output i32[n_nodes] (-1 = none), is_end i32[n_nodes] (0 / 1), level i32[n_nodes] (depth in the trie)
+ *   token_score / node_score / output_score f32[n_nodes]
+ *   graph_root i32[n_graphs]       root node of graph g;   max_level = the largest level
+ * rs_rnnt_mbs_hotwords reads DEVICE pointers; rs_hotwords_host is the same layout with HOST pointers, for rs_hotwords_check.
+ *   graph_of i32[B] (device)       graph of utterance b, -1 = none
+ * Every walk on the device is a counted loop (at most max_level + 1 fail steps, 32 bisection steps) and an index outside the
+ * table is treated as the root and never dereferenced: a corrupt table may give a wrong bonus, it cannot spin or read out of
+ * bounds.  rs_hotwords_check (pure host code, no context) validates a table before upload: counts, index ranges, children
+ * sorted strictly ascending, roots at level 0 that fail to themselves, level[child] = level[parent] + 1,
+ * level[fail[n]] < level[n] for every other node, level <= max_level; RS_EINVAL with the reason in msg (msg_bytes, may be NULL).
+ * rs_rnnt_mbs_hotwords with hw == NULL, n_graphs == 0 or graph_of == NULL is rs_rnnt_mbs (the same kernels, the same bits);
+ * otherwise the hotword form of the selection kernel runs: still five launches per frame, nothing waits for the host, one
+ * synchronisation at the end.  Workspace: rs_rnnt_mbs_hotwords_workspace_bytes.  Errors as rs_rnnt_mbs, and RS_EINVAL for
+ * negative counts or null arrays. */
+typedef struct rs_hotwords {
+    const int32_t* child_begin;
+    const int32_t* child_tok;
+    const int32_t* child_node;
+    const int32_t* fail;
+    const int32_t* output;
+    const int32_t* is_end;
+    const int32_t* level;
+    const float* token_score;
+    const float* node_score;
+    const float* output_score;
+    const int32_t* graph_root;
+    int32_t n_nodes, n_children, n_graphs, max_level;
+} rs_hotwords;
+typedef rs_hotwords rs_hotwords_host;
+int rs_hotwords_check(const rs_hotwords_host* table, char* msg, size_t msg_bytes);
+size_t rs_rnnt_mbs_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap);
+int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                         float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids,
+                         float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* ---- CTC segmentation of a batch (ESPnet family: time stamps of a recognised text) ------------------
  * Replaces: ctc_segmentation.ctc_segmentation(config, lpz, ground_truth_mat) of the third-party aligner the reference calls

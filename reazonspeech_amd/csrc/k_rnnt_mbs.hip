@@ -4,7 +4,8 @@
 // `max_active_paths` is the constructor's other offline transducer method).
 //
 // [UPSTREAM, not vendored, PARITY UNPINNED like the greedy search] OfflineTransducerModifiedBeamSearchDecoder::Decode without
-// LM / hotwords, Hypotheses::Add, GetMostProbable(length_norm = true).  The algorithm, as built here:
+// LM, Hypotheses::Add, GetMostProbable(length_norm = true); hotwords (ContextGraph) are the second half of this comment.  The
+// algorithm, as built here:
 //   * per utterance one starting hypothesis ys = [-1, blank] (context_size = 2 entries), log_prob = 0, no timestamps;
 //   * for every encoder frame t < enc_lens[b], with H <= K live hypotheses (K = max_active_paths):
 //       1. dec[h] = decoder_proj(decoder(last two tokens of h))                   (k2_decoder_kernel + rnnt_pred16_kernel)
@@ -33,8 +34,32 @@
 //   mbs_select_kernel   a workgroup per utterance: steps 3 - 5 and, at the utterance's last frame, the result
 //   k2_decoder_kernel + rnnt_pred16_kernel over the decoder rows that took a label
 // Utterances past their length are on no list and their workgroups return at once.
+//
+// HOTWORDS (rs_rnnt_mbs_hotwords).  [UPSTREAM, not vendored, PARITY UNPINNED] sherpa-onnx's ContextGraph — Build, FillFailOutput,
+// ForwardOneStep(strict_mode = false), Finalize — as OfflineTransducerModifiedBeamSearchDecoder::Decode uses it; the graph and
+// the step are stated in include/rs_asr.h.  In the search: every hypothesis row carries a node index (MbsState.ctx, ping-pong
+// like the records; the starting hypothesis carries its graph's root).  Step 4 is untouched — the K best are selected on values
+// WITHOUT any bonus.  In step 5, before the merge, each of the at most 8 candidates that appends a label v walks the graph once:
+// (delta, state') = step(parent's state, v), log_prob = lp[h][v] + delta; one that appends nothing keeps its parent's state.  The
+// merge adds log_probs with their bonuses inside; tokens, timestamps AND state of the entry added first stay.  At the utterance's
+// last frame every entry of the new set gets log_prob = log_prob + (-node_score[state]) (Finalize) BEFORE the winner is chosen;
+// scores[b] is the winner's log_prob after that.  Float32 order of one step, restated by tests/k2_hotwords_checker.c:
+//   child hit:  score = token_score[n];       otherwise:  score = node_score[n] - node_score[state]
+//   non-strict exit (output_score[n] != 0):  delta = (score + out) - node_score[n];     otherwise:  delta = score + output_score[n]
+// It is the hotword form of mbs_select_kernel (template parameter HW): no further launch, no host round trip.  The plain
+// instantiations are the ones launched when no utterance of the call has a graph; inside the hotword form a workgroup whose
+// utterance has none takes the plain statements.
+// The graph is read-only flat arrays (rs_hotwords), all graphs of the call concatenated.  A root can have thousands of children:
+// a child is found by bisection of the node's sorted token list (every lane of wave 0 computes the same value; no lane scans
+// a list).  THESE GPUS ARE SHARED, so the walk cannot spin or read out of bounds whatever the table holds: every loop is
+// counted (a fail step strictly lowers the level in a valid table, so max_level + 1 fail steps suffice and that is the bound;
+// a bisection halves an interval of < 2^31 entries, 32 steps), and a node or child index outside the table is replaced by the root
+// before it is used — a corrupt table can give a wrong bonus, nothing else.  rs_hotwords_check (rs_api.hip) refuses such tables
+// on the host before upload.
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
+
+#include <type_traits>
 
 int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
 int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
@@ -56,11 +81,70 @@ struct MbsState {
     int32_t* y[2];       // [rows][cap] tokens
     int32_t* fr[2];      // [rows][cap] frame of each token
     int32_t* n_hyp[2];   // [B]
+    int32_t* ctx[2];     // [rows] hotwords: node of the context graph the hypothesis stands at (nullptr without hotwords)
     int cap;
 };
 
+struct MbsNoHw {};       // the kernel argument of the plain form
+struct MbsHw {           // the graphs of a call (include/rs_asr.h rs_hotwords; device pointers) and each utterance's graph
+    rs_hotwords g;
+    const int32_t* graph_of;   // [B], -1 = none
+};
+
+// root of utterance b's graph, or -1 when it has none (an index outside the table counts as none)
+__device__ __forceinline__ int hw_root(const MbsHw& hw, int b) {
+    const int gi = hw.graph_of[b];
+    if (gi < 0 || gi >= hw.g.n_graphs) return -1;
+    const int r = hw.g.graph_root[gi];
+    return (r >= 0 && r < hw.g.n_nodes) ? r : -1;
+}
+__device__ __forceinline__ int hw_node(const rs_hotwords& g, int n, int root) { return (n >= 0 && n < g.n_nodes) ? n : root; }
+
+// the child of node n (valid) on token tok, or -1: bisection of the node's sorted token list, at most 32 steps
+__device__ __forceinline__ int hw_child(const rs_hotwords& g, int n, int tok, int root) {
+    int lo = g.child_begin[n], hi = g.child_begin[n + 1];
+    if (lo < 0) lo = 0;
+    if (hi > g.n_children) hi = g.n_children;
+    for (int it = 0; it < 32 && lo < hi; ++it) {
+        const int mid = lo + ((hi - lo) >> 1);
+        const int ct = g.child_tok[mid];
+        if (ct == tok) return hw_node(g, g.child_node[mid], root);
+        if (ct < tok) lo = mid + 1; else hi = mid;
+    }
+    return -1;
+}
+
+// ForwardOneStep(strict_mode = false): (state, tok) -> delta, next state.  `root` is valid; every index is made valid before use.
+__device__ float hw_step(const rs_hotwords& g, int root, int state, int tok, int* next) {
+    state = hw_node(g, state, root);
+    int n = hw_child(g, state, tok, root);
+    float score;
+    if (n >= 0) {
+        score = g.token_score[n];
+    } else {
+        n = hw_node(g, g.fail[state], root);
+        int c = hw_child(g, n, tok, root);
+        for (int it = 0; it <= g.max_level && c < 0 && n != root; ++it) {
+            n = hw_node(g, g.fail[n], root);
+            c = hw_child(g, n, tok, root);
+        }
+        if (c >= 0) n = c;
+        score = g.node_score[n] - g.node_score[state];
+    }
+    const float os = g.output_score[n];
+    if (os != 0.0f) {
+        const int o = g.output[n];
+        const float out = g.is_end[n] ? g.node_score[n] : ((o >= 0 && o < g.n_nodes) ? g.node_score[o] : g.node_score[n]);
+        *next = root;
+        return (score + out) - g.node_score[n];
+    }
+    *next = n;
+    return score + os;
+}
+
+template <bool HW>
 __global__ void mbs_init_kernel(DecodeState st, MbsState ms, const int32_t* __restrict__ enc_lens, int B, int K, int blank,
-                                int32_t* __restrict__ n_ids, float* __restrict__ scores) {
+                                int32_t* __restrict__ n_ids, float* __restrict__ scores, std::conditional_t<HW, MbsHw, MbsNoHw> hw) {
     // single workgroup: the starting hypothesis of every utterance, its decoder row and the first work lists
     __shared__ int n_alive_s;
     if (threadIdx.x == 0) n_alive_s = 0;
@@ -69,6 +153,7 @@ __global__ void mbs_init_kernel(DecodeState st, MbsState ms, const int32_t* __re
         const int row = b * K;
         ms.len[0][row] = 0; ms.score[0][row] = 0.0f; ms.last0[0][row] = -1; ms.last1[0][row] = blank; ms.dec[0][row] = 0;
         ms.n_hyp[0][b] = 1;
+        if constexpr (HW) { const int r = hw_root(hw, b); ms.ctx[0][row] = r < 0 ? 0 : r; }
         st.token2[row] = -1; st.token[row] = blank; st.act[b] = row;
         n_ids[b] = 0; scores[b] = 0.0f;                  // the result of an utterance without frames
         if (enc_lens[b] > 0) st.alive[atomicAdd(&n_alive_s, 1)] = row;
@@ -106,11 +191,11 @@ __device__ __forceinline__ bool mbs_before(float oz, int ov, float bz, int bv) {
 // NVR > 0: V <= 256 NVR and a hypothesis's logits row is read ONCE into NVR registers per thread, every load in flight before the
 // first comparison; maximum, exp-sum and the running top-K then walk the registers.  NVR = 0: any V, three passes over memory,
 // the same arithmetic in the same order.
-template <int NVR>
+template <int NVR, bool HW>
 __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
     DecodeState st, MbsState ms, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int rows, int K,
     int V, int blank, int unk, int t, float blank_penalty, int length_norm, int out_cap, int32_t* __restrict__ ids,
-    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores) {
+    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores, std::conditional_t<HW, MbsHw, MbsNoHw> hw) {
     const int b = blockIdx.x;
     const int T = enc_lens[b];
     if (t >= T) return;                                   // skipped, not masked
@@ -127,6 +212,9 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
     __shared__ int s_prow[MBS_MAX_K], s_tok[MBS_MAX_K], s_dec[MBS_MAX_K];   // the new set, in the order of entry
     __shared__ float s_score[MBS_MAX_K];
     __shared__ int s_nnew;
+    __shared__ int s_ctx[HW ? MBS_MAX_K : 1];             // hotwords: the context state of each entry of the new set
+    int root = -1;                                        // hotwords: the root of the utterance's graph, -1 = it has none
+    if constexpr (HW) root = hw_root(hw, b);
 
     // ---- steps 3 + 4a: every thread's K best of its own columns over all H rows (sorted: value desc, flat index asc; a thread
     // meets its flat indices in ascending order, so a later equal value never displaces an earlier one) ----
@@ -254,6 +342,23 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
                 csc[j] = s_val[j];
             }
         }
+        // hotwords: one walk per candidate that appends a label, before the merge; the others keep their parent's state
+        int cctx[HW ? MBS_MAX_K : 1];
+        if constexpr (HW) {
+#pragma unroll
+            for (int j = 0; j < MBS_MAX_K; ++j) {
+                cctx[j] = 0;
+                if (j < n_cand && root >= 0) {
+                    cctx[j] = ms.ctx[p][cprow[j]];
+                    if (ctok[j] >= 0) {
+                        int nx = root;
+                        const float delta = hw_step(hw.g, root, cctx[j], ctok[j], &nx);
+                        csc[j] = csc[j] + delta;
+                        cctx[j] = nx;
+                    }
+                }
+            }
+        }
         // a candidate whose token sequence equals that of an earlier entry adds its probability to it
 #pragma unroll
         for (int j = 1; j < MBS_MAX_K; ++j) {
@@ -290,10 +395,15 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
             int d;
             if (ctok[j] < 0) d = ms.dec[p][cprow[j]];
             else { d = __ffs((int)~used) - 1; used |= 1u << d; }
-            if (lane == 0) { s_prow[nk] = cprow[j]; s_tok[nk] = ctok[j]; s_score[nk] = csc[j]; s_dec[nk] = d; }
+            float sc = csc[j];
+            if constexpr (HW) {
+                if (root >= 0 && t == T - 1) sc = sc + (-hw.g.node_score[hw_node(hw.g, cctx[j], root)]);      // Finalize
+                if (lane == 0) s_ctx[nk] = cctx[j];
+            }
+            if (lane == 0) { s_prow[nk] = cprow[j]; s_tok[nk] = ctok[j]; s_score[nk] = sc; s_dec[nk] = d; }
             const int n = cplen[j] + (ctok[j] >= 0 ? 1 : 0);
-            const float norm = length_norm ? csc[j] / (float)(n + MBS_CONTEXT) : csc[j];
-            if (win < 0 || norm > win_norm) { win = j; win_n = n; win_norm = norm; win_score = csc[j]; }
+            const float norm = length_norm ? sc / (float)(n + MBS_CONTEXT) : sc;
+            if (win < 0 || norm > win_norm) { win = j; win_n = n; win_norm = norm; win_score = sc; }
             ++nk;
         }
         if (lane == 0) { s_nnew = nk; ms.n_hyp[pn][b] = nk; }
@@ -334,6 +444,7 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
             }
             ms.len[pn][row] = nn; ms.score[pn][row] = s_score[k];
             ms.last0[pn][row] = l0; ms.last1[pn][row] = l1; ms.dec[pn][row] = s_dec[k];
+            if constexpr (HW) ms.ctx[pn][row] = s_ctx[k];
             const int pos = atomicAdd(&st.counters[2 + pn], 1);
             st.alive[(size_t)pn * rows + pos] = row;
         }
@@ -341,7 +452,7 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
 }
 
 // the search's layout (h .. c_tmp adjacent: one memset clears the four); -> DecodeState.a_pre, writable (mbs_act_kernel fills it)
-float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, rs_arena& a, DecodeState& st, MbsState& ms) {
+float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, rs_arena& a, DecodeState& st, MbsState& ms) {
     const rs_dims& d = ctx->d;
     const size_t rows = (size_t)B * K, state = rows * d.pred_hidden;
     st.h = a.take<float>(state); st.c = a.take<float>(state);                // (the projection kernel's state commit copies
@@ -359,6 +470,8 @@ float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, rs_arena& a, DecodeS
     ms.n_hyp[0] = a.take<int32_t>(B); ms.n_hyp[1] = a.take<int32_t>(B);
     st.counters = a.take<int32_t>(16);
     st.zapprox = a.take<float>(rows * (size_t)((d.n_logits + 63) / 64 * 64));
+    ms.ctx[0] = ms.ctx[1] = nullptr;
+    if (hotwords) { ms.ctx[0] = a.take<int32_t>(rows); ms.ctx[1] = a.take<int32_t>(rows); }       // (last: the plain layout is a prefix)
     ms.cap = cap;
     st.a_pre = a_pre;
     st.joint_act = d.joint_act;
@@ -368,18 +481,18 @@ constexpr size_t MBS_SLACK = 1024;
 
 }  // namespace
 
-size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max) {
+size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords) {
     if (B <= 0 || K <= 0 || K > MBS_MAX_K || tp_max < 0) return 0;
     rs_arena a;
     DecodeState st{};
     MbsState ms;
-    mbs_layout(ctx, B, K, tp_max > 0 ? tp_max : 1, a, st, ms);
+    mbs_layout(ctx, B, K, tp_max > 0 ? tp_max : 1, hotwords, a, st, ms);
     return a.bytes() + MBS_SLACK;
 }
 
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
-                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, void* workspace,
-                     size_t workspace_bytes, hipStream_t s) {
+                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
+                     const int32_t* graph_of, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int D = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
@@ -391,7 +504,10 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     rs_arena arena(workspace);
     DecodeState st{};
     MbsState ms;
-    float* const a_pre = mbs_layout(ctx, B, K, cap, arena, st, ms);
+    const bool HWF = hotwords != nullptr && graph_of != nullptr && hotwords->n_graphs > 0;      // else: the plain kernels, today's bits
+    MbsHw hw{};
+    if (HWF) { hw.g = *hotwords; hw.graph_of = graph_of; }
+    float* const a_pre = mbs_layout(ctx, B, K, cap, HWF, arena, st, ms);
     if (workspace_bytes < arena.bytes() + MBS_SLACK)
         return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + MBS_SLACK);
     const int rows = B * K;
@@ -401,7 +517,8 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
 
     rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * rs_align((size_t)rows * D * 4), s));                  // h .. c_tmp are adjacent
-    hipLaunchKernelGGL(mbs_init_kernel, dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores);
+    if (HWF) hipLaunchKernelGGL((mbs_init_kernel<true>), dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, hw);
+    else hipLaunchKernelGGL((mbs_init_kernel<false>), dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, MbsNoHw{});
     if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
     RS_CHECK_LAUNCH(ctx, "modified beam search init");
     const int act_blocks = (int)(((long long)rows * (J / 4) + 255) / 256);
@@ -412,9 +529,13 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
             return rc;
         }
 #define RS_MBS_ARGS st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t, blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores
-        if (V <= MBS_THREADS * 4) hipLaunchKernelGGL((mbs_select_kernel<4>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS);
-        else if (V <= MBS_THREADS * 42) hipLaunchKernelGGL((mbs_select_kernel<42>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS);
-        else hipLaunchKernelGGL((mbs_select_kernel<0>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS);
+        if (HWF) {
+            if (V <= MBS_THREADS * 4) hipLaunchKernelGGL((mbs_select_kernel<4, true>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, hw);
+            else if (V <= MBS_THREADS * 42) hipLaunchKernelGGL((mbs_select_kernel<42, true>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, hw);
+            else hipLaunchKernelGGL((mbs_select_kernel<0, true>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, hw);
+        } else if (V <= MBS_THREADS * 4) hipLaunchKernelGGL((mbs_select_kernel<4, false>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, MbsNoHw{});
+        else if (V <= MBS_THREADS * 42) hipLaunchKernelGGL((mbs_select_kernel<42, false>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, MbsNoHw{});
+        else hipLaunchKernelGGL((mbs_select_kernel<0, false>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, MbsNoHw{});
 #undef RS_MBS_ARGS
         if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
     }

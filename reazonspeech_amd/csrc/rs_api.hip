@@ -12,10 +12,10 @@
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B);
 size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap);
-size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max);
+size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords);
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
-                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, void* workspace,
-                     size_t workspace_bytes, hipStream_t s);
+                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
+                     const int32_t* graph_of, void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops);
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
                       int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
@@ -765,12 +765,68 @@ int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
 
 size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
     if (!ctx || !ctx->k2 || B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0) return 0;
-    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max);
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, false);
 }
 
 int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
                 float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
                 void* workspace, size_t workspace_bytes, void* stream) {
+    return rs_rnnt_mbs_hotwords(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids,
+                                scores, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+size_t rs_rnnt_mbs_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
+    if (!ctx || !ctx->k2 || B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0) return 0;
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, true);
+}
+
+// pure host code: is `t` (HOST pointers) a table the device walk may be given?  (The walk is safe on any table; a table that
+// fails here would give bonuses nobody meant.)
+int rs_hotwords_check(const rs_hotwords_host* t, char* msg, size_t msg_bytes) {
+    auto fail = [&](const char* fmt, long long a, long long b, long long c) {
+        if (msg && msg_bytes) snprintf(msg, msg_bytes, fmt, a, b, c);
+        return (int)RS_EINVAL;
+    };
+    if (msg && msg_bytes) msg[0] = 0;
+    if (!t) return fail("hotwords: null table", 0, 0, 0);
+    if (t->n_nodes < 0 || t->n_children < 0 || t->n_graphs < 0 || t->max_level < 0) return fail("hotwords: negative count", 0, 0, 0);
+    if (t->n_graphs == 0) return RS_OK;
+    if (t->n_nodes < t->n_graphs) return fail("hotwords: %lld graphs but %lld nodes", t->n_graphs, t->n_nodes, 0);
+    if (!t->child_begin || !t->fail || !t->output || !t->is_end || !t->level || !t->token_score || !t->node_score || !t->output_score ||
+        !t->graph_root || (t->n_children > 0 && (!t->child_tok || !t->child_node)))
+        return fail("hotwords: null array", 0, 0, 0);
+    const int N = t->n_nodes, C = t->n_children;
+    if (t->child_begin[0] != 0 || t->child_begin[N] != C) return fail("hotwords: child_begin must run from 0 to n_children=%lld", C, 0, 0);
+    for (int g = 0; g < t->n_graphs; ++g) {
+        const int r = t->graph_root[g];
+        if (r < 0 || r >= N) return fail("hotwords: graph_root[%lld]=%lld outside the %lld nodes", g, r, N);
+        if (t->level[r] != 0 || t->fail[r] != r) return fail("hotwords: root %lld of graph %lld must have level 0 and fail to itself", r, g, 0);
+    }
+    for (int n = 0; n < N; ++n) {
+        const int lo = t->child_begin[n], hi = t->child_begin[n + 1];
+        if (lo < 0 || hi < lo || hi > C) return fail("hotwords: child_begin[%lld..] = %lld, %lld is not an ascending range of the children", n, lo, hi);
+        if (t->level[n] < 0 || t->level[n] > t->max_level) return fail("hotwords: level[%lld]=%lld outside 0..max_level=%lld", n, t->level[n], t->max_level);
+        const int f = t->fail[n], o = t->output[n];
+        if (f < 0 || f >= N) return fail("hotwords: fail[%lld]=%lld outside the %lld nodes", n, f, N);
+        if (o < -1 || o >= N) return fail("hotwords: output[%lld]=%lld outside the %lld nodes", n, o, N);
+        if (t->level[n] == 0) {
+            if (f != n) return fail("hotwords: node %lld has level 0 but fails to %lld", n, f, 0);
+        } else if (t->level[f] >= t->level[n]) {
+            return fail("hotwords: fail[%lld]=%lld does not lower the level (%lld)", n, f, t->level[n]);
+        }
+        for (int c = lo; c < hi; ++c) {
+            const int k = t->child_node[c];
+            if (k < 0 || k >= N) return fail("hotwords: child_node[%lld]=%lld outside the %lld nodes", c, k, N);
+            if (t->level[k] != t->level[n] + 1) return fail("hotwords: child %lld of node %lld is not one level below it", k, n, 0);
+            if (c > lo && t->child_tok[c] <= t->child_tok[c - 1]) return fail("hotwords: the children of node %lld are not sorted ascending (entry %lld)", n, c, 0);
+        }
+    }
+    return RS_OK;
+}
+
+int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                         float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                         const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
     if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_rnnt_mbs");
     if (!ctx->k2) return rs_fail(ctx, RS_EINVAL, "modified beam search: defined for a Zipformer context (stateless decoder) only; this context has an LSTM prediction network (rs_rnnt_alsd / rs_rnnt_beam)");
@@ -784,8 +840,18 @@ int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, in
         RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * 4, (hipStream_t)stream));
         return RS_OK;
     }
+    if (hw && graph_of && hw->n_graphs > 0) {
+        if (hw->n_nodes < hw->n_graphs || hw->n_children < 0 || hw->max_level < 0)
+            return rs_fail(ctx, RS_EINVAL, "modified beam search: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)",
+                           hw->n_nodes, hw->n_children, hw->n_graphs, hw->max_level);
+        if (!hw->child_begin || !hw->fail || !hw->output || !hw->is_end || !hw->level || !hw->token_score || !hw->node_score ||
+            !hw->output_score || !hw->graph_root || (hw->n_children > 0 && (!hw->child_tok || !hw->child_node)))
+            return rs_fail(ctx, RS_EINVAL, "modified beam search: hotwords: null array");
+    } else {
+        hw = nullptr;                                     // no graph in this call: today's kernels, today's bits
+    }
     return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
-                            out_cap, ids, frames, n_ids, scores, workspace, workspace_bytes, (hipStream_t)stream);
+                            out_cap, ids, frames, n_ids, scores, hw, hw ? graph_of : nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t rs_ctc_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int c_max, int S) {

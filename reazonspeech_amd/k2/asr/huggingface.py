@@ -57,7 +57,8 @@ def resolve_checkpoint(language, precision, checkpoint=None):
 
 
 def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
-               decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host"):
+               decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host", hotwords_file="",
+               hotwords_score=1.5, hotwords=None):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -85,7 +86,14 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
       decoding_method (str), max_active_paths (int), blank_penalty (float): the keywords of
         `sherpa_onnx.OfflineRecognizer.from_transducer` with its defaults.  "greedy_search" is what the reference passes (:81);
         "modified_beam_search" keeps `max_active_paths` (1..8, default 4) hypotheses per utterance (rs_rnnt_mbs,
-        csrc/k_rnnt_mbs.hip: no LM, no hotwords).  Valid with every `precision` / `compute`; anything else raises ValueError.
+        csrc/k_rnnt_mbs.hip: no LM).  Valid with every `precision` / `compute`; anything else raises ValueError.
+      hotwords_file (str), hotwords_score (float): sherpa-onnx's contextual biasing, its names and defaults ("" / 1.5): a file with one
+        phrase per line (blank lines ignored, an optional trailing ` :<float>` = the phrase's own score), every character looked up
+        in tokens.txt; a phrase with a character that is no token is skipped with a warning.  The modified beam search then adds
+        hotwords_score per matched token to hypotheses that spell a phrase out and takes it back when the match breaks off
+        (rs_rnnt_mbs_hotwords, runtime/k2_hotwords.py).  `hotwords` = the same as an in-memory list (strings, or sequences of token
+        ids).  The graph is built and uploaded once, here; `create_stream(hotwords=...)` / `transcribe(..., hotwords=...)` replace it
+        per utterance.  With "greedy_search" non-empty hotwords raise ValueError, as upstream refuses them.
       resample (str): where `transcribe` / `transcribe_batch` normalise input at another rate than 16 kHz or with several channels
         (`norm_audio`): "host" (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count)
         group of a call (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`;
@@ -106,8 +114,11 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     from ...runtime.resample import check_mode
     check_mode(resample)
     from .model import search_config
-    search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty)
-    search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample)
+    search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords)
+    if hotwords_file and not os.path.isfile(hotwords_file):
+        raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
+    search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample,
+                  hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):

@@ -4,13 +4,15 @@ It stands where `sherpa_onnx.OfflineRecognizer` stands in the reference (pkg/k2-
 calls the reference makes on it (transcribe.py:36-45):
     stream = model.create_stream(); stream.accept_waveform(samplerate, waveform); model.decode_stream(stream)
     stream.result.tokens / .timestamps / .text
-plus the batched form `decode_streams` (sherpa-onnx has it too).  [UPSTREAM] conventions of sherpa-onnx's result conversion
+plus the batched form `decode_streams` (sherpa-onnx has it too) and the recognizer's hotwords: `hotwords_file=` / `hotwords_score=`
+at construction, `create_stream(hotwords=...)` per utterance (runtime/k2_hotwords.py; the modified beam search only).  [UPSTREAM] conventions of sherpa-onnx's result conversion
 (offline-recognizer-transducer-impl.h Convert, symbol-table.cc): a token's text is its tokens.txt symbol with a leading U+2581 replaced by
 a space and `<0xNN>` byte tokens joined into UTF-8; text = the tokens concatenated; timestamp = frame index x 0.04 s."""
 import re
 
 import numpy as np
 
+from ...runtime import k2_hotwords
 from ...runtime.model import AsrModel
 
 _BYTE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
@@ -24,7 +26,8 @@ class _Result:
 class _Stream:
     """sherpa_onnx.OfflineStream: holds one utterance's samples, then its result"""
 
-    def __init__(self):
+    def __init__(self, hotwords=None):
+        self.hotwords = hotwords          # HotwordGraph of this stream (it replaces the model's), None = the model's
         self.samples = np.zeros((0,), np.float32)
         self.sample_rate = 16000
         self.result = _Result([], [], "")
@@ -61,9 +64,16 @@ def synthetic_tokens(vocab_size, seed=0):
 DECODING_METHODS = ("greedy_search", "modified_beam_search")      # sherpa-onnx's offline transducer methods
 
 
-def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0):
+def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, hotwords_file="", hotwords_score=1.5,
+                  hotwords=None):
     """`cfg` with the search sherpa_onnx.OfflineRecognizer.from_transducer's keywords ask for (its names and defaults);
-    ValueError for anything it does not have or this package does not run.  Needs no GPU."""
+    ValueError for anything it does not have or this package does not run.  Needs no GPU.  The hotwords keywords are checked
+    here (upstream refuses them with greedy_search too); the graph itself is the model's, not the configuration's."""
+    has_hotwords = bool(hotwords_file) or (hotwords is not None and len(hotwords) > 0)
+    if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
+        raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
+    if has_hotwords and decoding_method == "greedy_search":
+        raise ValueError("hotwords need decoding_method='modified_beam_search' (greedy_search has no hypotheses to bias)")
     if decoding_method not in DECODING_METHODS:
         raise ValueError(f"decoding_method must be 'greedy_search' or 'modified_beam_search', not {decoding_method!r}")
     if not float(blank_penalty) >= 0.0:
@@ -77,10 +87,22 @@ def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blan
     return cfg.with_(decoding="modified_beam_search", beam_size=int(max_active_paths), blank_penalty=float(blank_penalty))
 
 
+def stream_graphs(model_graph, streams):
+    """the graph each stream is decoded with: its own (create_stream(hotwords=...)) INSTEAD OF the model's, else the model's;
+    None when no stream has one"""
+    graphs = [st.hotwords if st.hotwords is not None else model_graph for st in streams]
+    return graphs if any(g is not None for g in graphs) else None
+
+
 class K2Model:
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
-                 decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host"):
-        """decoding_method / max_active_paths / blank_penalty: sherpa_onnx.OfflineRecognizer.from_transducer's keywords with its
+                 decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host",
+                 hotwords_file="", hotwords_score=1.5, hotwords=None):
+        """hotwords_file / hotwords_score: sherpa-onnx's keywords and defaults (contextual biasing of the modified beam search:
+        runtime/k2_hotwords.py for the file format, include/rs_asr.h rs_rnnt_mbs_hotwords for what a hotword does); `hotwords` = the
+        same as an in-memory list (strings "phrase" / "phrase :2.0", or token-id sequences).  The model's graph is built and
+        uploaded once here; with greedy_search they raise ValueError.
+        decoding_method / max_active_paths / blank_penalty: sherpa_onnx.OfflineRecognizer.from_transducer's keywords with its
         defaults (pkg/k2-asr/src/huggingface.py:73-83 passes "greedy_search"): "modified_beam_search" keeps max_active_paths (1..8)
         hypotheses per utterance (csrc/k_rnnt_mbs.hip, rs_rnnt_mbs); valid with every precision — the search only consumes the
         encoder projection.  Anything else raises ValueError.
@@ -93,13 +115,27 @@ class K2Model:
         pos_cap: rows of relative positions the resident position tables start with (|rel| < pos_cap; None = the runtime's default);
         a longer utterance grows them (AsrModel.ensure_pos_cap), so this only moves the first growth"""
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
-        cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty)
+        cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords)
         self.cfg = cfg
         self.tokens = list(tokens)
+        self.hotwords_score = float(hotwords_score)
+        self.hotwords = self.hotword_graph(hotwords, hotwords_file)       # the model's graph (None = no hotwords)
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded
         cap = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
         self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, **cap)
         self.device = self.am.device
+        if self.hotwords is not None:
+            self.am.hotword_set((self.hotwords,))         # checked and uploaded once, at load
+
+    def hotword_graph(self, hotwords, hotwords_file=""):
+        """a hotwords argument (a string of phrases separated by `/`, or a list; each phrase with an optional ` :score`) -> its
+        HotwordGraph, None for nothing; phrases without a score of their own take the model's hotwords_score"""
+        if isinstance(hotwords, k2_hotwords.HotwordGraph):
+            return hotwords
+        graph = k2_hotwords.make_graph(hotwords, self.tokens, self.cfg.blank_id, self.cfg.unk_id, self.hotwords_score, hotwords_file)
+        if graph is not None and self.cfg.decoding != "modified_beam_search":
+            raise ValueError("hotwords need decoding_method='modified_beam_search' (greedy_search has no hypotheses to bias)")
+        return graph
 
     # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option
     @property
@@ -115,8 +151,10 @@ class K2Model:
         return self.am.resample_batch(waveforms, rates)
 
     # ---- sherpa-onnx's surface ------------------------------------------------------------------------------------------
-    def create_stream(self):
-        return _Stream()
+    def create_stream(self, hotwords=None):
+        """hotwords: sherpa-onnx's per-stream hotwords — a string of phrases separated by `/` (or a list), each with an optional
+        ` :score`; the stream is then decoded with ITS graph instead of the model's"""
+        return _Stream(self.hotword_graph(hotwords))
 
     def decode_stream(self, stream):
         self.decode_streams([stream])
@@ -125,7 +163,7 @@ class K2Model:
         for st in streams:
             if st.sample_rate != self.cfg.sample_rate:
                 raise ValueError(f"sample rate {st.sample_rate}: the model expects {self.cfg.sample_rate} Hz (sherpa-onnx resamples; resample with norm_audio first)")
-        res = self.am.transcribe_waveforms([st.samples for st in streams])
+        res = self.am.transcribe_waveforms([st.samples for st in streams], hotwords=stream_graphs(self.hotwords, streams))
         for st, ids, frames in zip(streams, res.ids, res.frames):
             st.result = self.convert(ids, frames)
 

@@ -38,13 +38,43 @@ def _result(stream):
     return TranscribeResult(stream.result.text, subwords)
 
 
-def transcribe(model, audio, config=None):
+def _streams(model, audios, hotwords):
+    """one stream per prepared audio; `hotwords`: None, one specification (a string) for all, or a list with one entry per audio"""
+    if hotwords is None or isinstance(hotwords, str):
+        graph = model.hotword_graph(hotwords) if hotwords else None        # built once for the whole list
+        per_audio = [graph] * len(audios)
+    else:
+        if len(hotwords) != len(audios):
+            raise ValueError(f"hotwords: {len(hotwords)} entries for {len(audios)} audios (a list is one entry per audio; pass a string "
+                             "of phrases separated by '/' to use one specification for all)")
+        cache = {}
+        per_audio = []
+        for h in hotwords:
+            key = h if isinstance(h, str) else None
+            if h is None or (key is not None and key in cache):
+                per_audio.append(cache.get(key) if h is not None else None)
+                continue
+            g = model.hotword_graph(h)
+            if key is not None:
+                cache[key] = g
+            per_audio.append(g)
+    streams = []
+    for a, g in zip(audios, per_audio):
+        st = model.create_stream() if g is None else model.create_stream(hotwords=g)     # (no hotwords: the reference's call)
+        st.accept_waveform(a.samplerate, a.waveform)
+        streams.append(st)
+    return streams
+
+
+def transcribe(model, audio, config=None, hotwords=None):
     """Inference audio data using the K2 model (transcribe.py:10-45).
 
     Args:
         model (K2Model): what `load_model()` returned
         audio (AudioData): Audio data to transcribe
         config (TranscribeConfig): Additional settings
+        hotwords: phrases to favour in this call INSTEAD OF the model's (`create_stream(hotwords=...)`): a string of phrases
+            separated by `/`, or a list of phrases, each with an optional ` :score`; None = the model's hotwords, if any
 
     Returns:
         TranscribeResult
@@ -55,20 +85,17 @@ def transcribe(model, audio, config=None):
     if config is None:
         config = TranscribeConfig()
     audio = _prepare_batch(model, [audio])[0]
-    stream = model.create_stream()
-    stream.accept_waveform(audio.samplerate, audio.waveform)
+    stream = _streams(model, [audio], None if hotwords is None else [hotwords])[0]
     model.decode_stream(stream)
     return _result(stream)
 
 
-def transcribe_batch(model, audios, config=None):
+def transcribe_batch(model, audios, config=None, hotwords=None):
     """Additive: many utterances as one (or several pipelined) batches on the device; per utterance the same result as
     `transcribe` (every kernel masks by the utterance's own length).  The search (greedy or modified beam search) is the one the
-    model was built with (`load_model(decoding_method=...)`)."""
-    streams = []
-    for a in _prepare_batch(model, audios):
-        st = model.create_stream()
-        st.accept_waveform(a.samplerate, a.waveform)
-        streams.append(st)
+    model was built with (`load_model(decoding_method=...)`).  `hotwords`: None (the model's, if any), one string of phrases
+    separated by `/` for all audios, or a list with one entry per audio (None / a string / a list of phrases): every utterance is
+    biased by its own graph inside the one batch."""
+    streams = _streams(model, _prepare_batch(model, audios), hotwords)
     model.decode_streams(streams)
     return [_result(st) for st in streams]

@@ -32,6 +32,7 @@ EXPORTS = [
     "rs_layernorm", "rs_relpos_attention", "rs_glu_dwconv_silu", "rs_glu_dwconv_silu_layout", "rs_encoder_set_taps", "rs_set_option", "rs_stream_create", "rs_stream_destroy",
     "rs_rnnt_alsd", "rs_rnnt_alsd_workspace_bytes", "rs_rnnt_beam", "rs_rnnt_beam_workspace_bytes", "rs_host_stage_rows",
     "rs_rnnt_mbs", "rs_rnnt_mbs_workspace_bytes",
+    "rs_rnnt_mbs_hotwords", "rs_rnnt_mbs_hotwords_workspace_bytes", "rs_hotwords_check",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
     "rs_k2_create", "rs_k2_encoder_set_taps",
@@ -45,6 +46,34 @@ EXPORTS = [
     "rs_resample",
     "rs_avsr_logfbank", "rs_avsr_pixels",
 ]
+
+
+HOTWORD_ARRAYS = ("child_begin", "child_tok", "child_node", "fail", "output", "is_end", "level", "token_score", "node_score",
+                  "output_score", "graph_root")      # the pointer fields of `struct rs_hotwords`, in its order
+HOTWORD_FLOATS = ("token_score", "node_score", "output_score")
+
+
+class RsHotwords(Structure):
+    """mirror of `struct rs_hotwords` (device pointers) / `rs_hotwords_host` (host pointers)"""
+    _fields_ = [(name, c_void_p) for name in HOTWORD_ARRAYS] + [("n_nodes", c_int32), ("n_children", c_int32), ("n_graphs", c_int32),
+                                                               ("max_level", c_int32)]
+
+
+def hotwords_check(table):
+    """rs_hotwords_check on a host table: `table` = dict of numpy arrays (HOTWORD_ARRAYS: int32, the three scores float32) plus
+    "max_level".  Pure host code.  Raises RsError(RS_EINVAL, reason) for a table the search must not be given."""
+    import numpy as np
+    lib = load()
+    keep = {k: np.ascontiguousarray(table[k], dtype=np.float32 if k in HOTWORD_FLOATS else np.int32) for k in HOTWORD_ARRAYS}
+    t = RsHotwords(*[c_void_p(keep[k].ctypes.data) for k in HOTWORD_ARRAYS], len(keep["fail"]), len(keep["child_tok"]),
+                   len(keep["graph_root"]), int(table["max_level"]))
+    if len(keep["child_begin"]) != t.n_nodes + 1 or any(len(keep[k]) != t.n_nodes for k in ("output", "is_end", "level") + HOTWORD_FLOATS) \
+            or len(keep["child_node"]) != t.n_children:
+        raise RsError(RS_EINVAL, "hotwords: the arrays of the table disagree in length")
+    msg = ctypes.create_string_buffer(256)
+    rc = lib.rs_hotwords_check(byref(t), msg, len(msg))
+    if rc != RS_OK:
+        raise RsError(rc, msg.value.decode() or "rs_hotwords_check failed")
 
 
 class RsDims(Structure):
@@ -181,6 +210,11 @@ def load():
     lib.rs_rnnt_mbs_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
     lib.rs_rnnt_mbs_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_mbs.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp, vp, c_size_t, vp]
+    lib.rs_rnnt_mbs_hotwords_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
+    lib.rs_rnnt_mbs_hotwords_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_mbs_hotwords.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp, POINTER(RsHotwords), vp, vp,
+                                         c_size_t, vp]
+    lib.rs_hotwords_check.argtypes = [POINTER(RsHotwords), c_char_p, c_size_t]
     lib.rs_rnnt_alsd_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
     lib.rs_rnnt_alsd_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_alsd.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp, vp,
@@ -453,6 +487,22 @@ class Context:
         self.check(self.lib.rs_rnnt_mbs(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
                                         MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids), _ptr(frames), _ptr(n_ids),
                                         _ptr(scores), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def mbs_hotwords_workspace_bytes(self, B, max_active_paths, tp_max, out_cap):
+        n = self.lib.rs_rnnt_mbs_hotwords_workspace_bytes(self._h, B, max_active_paths, tp_max, out_cap)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_mbs_hotwords_workspace_bytes: invalid arguments (a Zipformer context, max_active_paths 1..8)")
+        return n
+
+    def rnnt_mbs_hotwords(self, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, length_norm, ids, frames, n_ids, scores,
+                          hotwords, graph_of, ws, stream):
+        """rnnt_mbs with contextual biasing: `hotwords` = an RsHotwords of device pointers (None = no graph: rs_rnnt_mbs itself),
+        `graph_of` int32 [B] on the device (-1 = the utterance has no graph)"""
+        assert frames.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
+        self.check(self.lib.rs_rnnt_mbs_hotwords(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths),
+                                                 float(blank_penalty), MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids),
+                                                 _ptr(frames), _ptr(n_ids), _ptr(scores), byref(hotwords) if hotwords is not None else None,
+                                                 _ptr(graph_of), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
 
     def ctc_align_workspace_bytes(self, B, tp_max, c_max, S):
         n = self.lib.rs_ctc_align_workspace_bytes(self._h, int(B), int(tp_max), int(c_max), int(S))

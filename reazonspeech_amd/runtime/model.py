@@ -60,6 +60,11 @@ class _Buffers:
         self.n_ids = torch.zeros((B,), dtype=i32, device=dev)
         self.scores = torch.zeros((B,), dtype=f32, device=dev)
         self.pops = torch.zeros((B,), dtype=i32, device=dev)     # "beam": prediction-network evaluations per utterance
+        # hotwords (Zipformer family, modified beam search): each utterance's graph in the batch's `hw_set` (-1 = none); `stage` /
+        # `fill_host` set both, `hw_set` None = the batch has no graph and the plain search runs
+        self.graph_of = torch.full((B,), -1, dtype=i32, device=dev)
+        self.h_graph_of = torch.full((B,), -1, dtype=i32).pin_memory()
+        self.hw_set = None
         self.ws_alsd = None              # beam-search scratch (grows with beam and alignment length): on first use
         self.ws = torch.empty((ctx.workspace_bytes(B, self.l_pad),), dtype=torch.uint8, device=dev)
         # the decoder of batch i overlaps the encoder of batch i+1 in the pipelined path: own scratch
@@ -111,6 +116,7 @@ class _BufView:
         self.ids = cut(base.ids, B, self.u_max)
         self.frames = cut(base.frames, B, self.u_max)
         self.n_ids, self.scores, self.pops = base.n_ids, base.scores, base.pops
+        self.graph_of, self.h_graph_of, self.hw_set = base.graph_of, base.h_graph_of, None
         self.ws, self.ws_dec = base.ws, base.ws_dec
         self.h_audio, self.h_lens = cut(base.h_audio, B, l_max), base.h_lens
         self.h_out = None
@@ -128,7 +134,23 @@ class _BufView:
         self.base.ws_alsd = v
 
 
+class _HotwordSet:
+    """the context graphs of a call on the device: one concatenated table (runtime/k2_hotwords.py: concat), checked by
+    rs_hotwords_check before the upload"""
+
+    def __init__(self, graphs, device):
+        from . import k2_hotwords
+        table = k2_hotwords.concat(graphs)
+        capi.hotwords_check(table)                        # raises RsError(RS_EINVAL): nothing is uploaded or launched with a bad table
+        self.n_graphs = len(graphs)
+        self.dev = {k: torch.from_numpy(table[k]).to(device) for k in capi.HOTWORD_ARRAYS}
+        self.struct = capi.RsHotwords(*[self.dev[k].data_ptr() if self.dev[k].numel() else None for k in capi.HOTWORD_ARRAYS],
+                                      len(table["fail"]), len(table["child_tok"]), len(graphs), int(table["max_level"]))
+
+
 class AsrModel:
+    HOTWORD_SETS = 8        # graph sets kept on the device (least recently used dropped)
+
     def __init__(self, cfg: ModelConfig, state_dict, tokenizer, device="cuda", pos_cap: int = DEFAULT_POS_CAP,
                  pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host"):
         """resample: where the packages' `norm_audio` work (resample to 16 kHz, average the channels) is done for input at another
@@ -168,6 +190,7 @@ class AsrModel:
         if pad_samples is not None:          # asymmetric padding in samples (espnet: PADDING = (16000, 8000), transcribe.py:10,69)
             self.pad_left, self.pad_right = int(pad_samples[0]), int(pad_samples[1])
         self._bufs = {}
+        self._hw_sets = {}              # (graph keys) -> _HotwordSet
         self._dec_lanes = []            # [(context, stream)] of the decode lanes beyond what was needed so far
         self._streams = None
         self._streams_prio = None
@@ -351,6 +374,14 @@ class AsrModel:
             ctx.rnnt_beam(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops,
                           buf.ids, buf.n_ids, buf.scores, buf.pops, buf.ws_alsd, stream, frames=buf.frames)
             return
+        hw = getattr(buf, "hw_set", None)
+        if cfg.decoding == "modified_beam_search" and hw is not None:     # ... with hotwords: the batch has at least one graph
+            n = ctx.mbs_hotwords_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1])
+            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
+                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            ctx.rnnt_mbs_hotwords(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
+                                  buf.ids, buf.frames, buf.n_ids, buf.scores, hw.struct, buf.graph_of, buf.ws_alsd, stream)
+            return
         if cfg.decoding == "modified_beam_search":    # Zipformer family: sherpa-onnx's second method (csrc/k_rnnt_mbs.hip)
             n = ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1])
             if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
@@ -520,6 +551,8 @@ class AsrModel:
                             w = buf.l_max
                             buf.audio[:, :w].copy_(buf.h_audio[:, :w], non_blocking=True)
                             buf.lens.copy_(buf.h_lens, non_blocking=True)
+                            if getattr(buf, "hw_set", None) is not None:
+                                buf.graph_of.copy_(buf.h_graph_of, non_blocking=True)
                     self.run_encoder(buf, enc_stream.cuda_stream)
                     ev = torch.cuda.Event()
                     ev.record(enc_stream)
@@ -548,7 +581,54 @@ class AsrModel:
         with torch.cuda.device(self.device):
             return _Buffers(self, B, (max(int(l_max), 1) + 63) // 64 * 64)
 
-    def fill_host(self, waveforms: Sequence[np.ndarray], buf):
+    # ---- hotwords (Zipformer family, modified beam search) ----------------------------------------------------------------------
+    def hotword_set(self, graphs):
+        """the device table of a tuple of distinct HotwordGraph: built, checked (rs_hotwords_check) and uploaded once, then
+        found again by content"""
+        key = tuple(g.key for g in graphs)
+        hs = self._hw_sets.pop(key, None)
+        if hs is None:
+            if len(self._hw_sets) >= self.HOTWORD_SETS:
+                self._hw_sets.pop(next(iter(self._hw_sets)))
+            with torch.cuda.device(self.device):
+                hs = _HotwordSet(graphs, self.device)
+        self._hw_sets[key] = hs                           # most recently used last
+        return hs
+
+    def graph_plan(self, hotwords, n):
+        """`hotwords`: None, or one HotwordGraph / None per utterance -> (device set, [graph index per utterance, -1 = none]) or None"""
+        if hotwords is None:
+            return None
+        if len(hotwords) != n:
+            raise ValueError(f"hotwords: {len(hotwords)} entries for {n} utterances")
+        if all(g is None for g in hotwords):
+            return None
+        if self.cfg.decoding != "modified_beam_search":
+            raise ValueError("hotwords need decoding_method='modified_beam_search'")
+        distinct, index = [], {}
+        for g in hotwords:
+            if g is not None and g.key not in index:
+                index[g.key] = len(distinct)
+                distinct.append(g)
+        return self.hotword_set(tuple(distinct)), [index[g.key] if g is not None else -1 for g in hotwords]
+
+    @staticmethod
+    def _set_graphs(buf, plan, members=None):
+        """the batch's graph indices into the pinned staging of `buf`; -> whether the batch has a graph (else the plain search runs)"""
+        buf.hw_set = None
+        if plan is None:
+            return False
+        hw, graph_of = plan
+        rows = graph_of if members is None else [graph_of[i] for i in members]
+        if all(g < 0 for g in rows):
+            return False
+        h = buf.h_graph_of.numpy()
+        h[:] = -1
+        h[:len(rows)] = rows
+        buf.hw_set = hw
+        return True
+
+    def fill_host(self, waveforms: Sequence[np.ndarray], buf, hotwords=None, members=None):
         """copy host waveforms (16 kHz mono float32, un-padded) into the buffer set's pinned staging buffers; the tail of
         every row is zeroed (the kernels mask by length, this only keeps the padding deterministic).  Returns the view of
         `buf` narrowed to this batch's longest utterance."""
@@ -559,10 +639,13 @@ class AsrModel:
         # one native call for the whole batch (it runs without the interpreter lock: a per-utterance numpy copy would
         # queue behind whatever Python thread holds it — the ids -> text post-processing of an earlier batch)
         capi.host_stage_rows(view.h_audio, view.l_max, waveforms, buf.h_lens)
+        # `hotwords`: the call's `graph_plan`, `members`: this batch's positions in it (the H2D copy is run_pipelined's)
+        self._set_graphs(view, hotwords, members)
         return view
 
-    def stage(self, waveforms: Sequence[np.ndarray], l_max: Optional[int] = None, buf: Optional[_Buffers] = None) -> _Buffers:
-        """copy host waveforms (16 kHz mono float32, un-padded) into a pinned buffer and on to HBM"""
+    def stage(self, waveforms: Sequence[np.ndarray], l_max: Optional[int] = None, buf: Optional[_Buffers] = None, hotwords=None) -> _Buffers:
+        """copy host waveforms (16 kHz mono float32, un-padded) into a pinned buffer and on to HBM; `hotwords`: the call's
+        `graph_plan` (every utterance of it is in this batch), None = no hotwords"""
         B = len(waveforms)
         longest = max((len(w) for w in waveforms), default=0)
         l_max = max(int(l_max or 0), longest, 1)
@@ -581,6 +664,8 @@ class AsrModel:
         with torch.cuda.device(self.device):
             buf.audio.copy_(buf.h_audio, non_blocking=True)
             buf.lens.copy_(buf.h_lens, non_blocking=True)
+            if self._set_graphs(buf, hotwords):
+                buf.graph_of.copy_(buf.h_graph_of, non_blocking=True)
         return buf
 
     RESAMPLE_CHUNK = 1 << 28        # float32 samples (1 GiB) one rs_resample launch takes in, and at most writes
@@ -673,17 +758,19 @@ class AsrModel:
         return DecodedBatch([ids[b, :n[b]].tolist() for b in range(buf.B)],
                             [frames[b, :n[b]].tolist() for b in range(buf.B)], el.tolist(), scores)
 
-    def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256) -> DecodedBatch:
+    def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None) -> DecodedBatch:
         """SPMD form of `transcribe_waveforms` for one process per GPU (`torch.distributed` initialised, RCCL):
         every rank passes the same list, decodes its length-balanced shard on its own GPU and receives all
         hypotheses (ids, frames, encoder lengths and — beam search — scores) in the caller's order after the path's one
-        collective (runtime/dist.py: sharded_decode).  With a single process it is `transcribe_waveforms`."""
+        collective (runtime/dist.py: sharded_decode).  With a single process it is `transcribe_waveforms`.  `hotwords` (one
+        HotwordGraph or None per utterance) follows each utterance to the rank that decodes it."""
         from . import dist as rdist
 
         def run_local(indices, batch):
             # `batch`: the chunk size of the dealing plan (ragged input is dealt as length-sorted chunks, balanced over the
             # ranks: runtime/dist.py shard_balanced) — this rank's batches are exactly its chunks
-            res = self.transcribe_waveforms([waveforms[i] for i in indices], max_batch=min(max_batch, batch))
+            res = self.transcribe_waveforms([waveforms[i] for i in indices], max_batch=min(max_batch, batch),
+                                            hotwords=None if hotwords is None else [hotwords[i] for i in indices])
             return res.ids, res.frames, res.enc_lens, res.scores
 
         ids, frames, enc_lens, scores = rdist.sharded_decode([len(w) for w in waveforms], run_local, max_batch=max_batch)
@@ -704,7 +791,7 @@ class AsrModel:
                 self._pool_sets = [_Buffers(self, B, l_max) for _ in range(n_sets)]
         return self._pool_sets[:n_sets]
 
-    def transcribe_waveforms(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, on_batch=None) -> DecodedBatch:
+    def transcribe_waveforms(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, on_batch=None, hotwords=None) -> DecodedBatch:
         """host float32 waveforms -> token ids / frames (the batched boundary).
 
         `on_batch(indices, decoded)`: called once per batch, in batch order, as soon as that batch's hypotheses are on
@@ -715,13 +802,18 @@ class AsrModel:
         `max_batch` (each padded only to ITS longest utterance) and pushed through the persistent pipeline of
         `run_pipelined` — four resident batches, two decode lanes, a stager thread that fills the pinned buffers of
         batch i+2 / i+3 while the GPU works on the batches before them, H2D on the encoder stream, hypotheses copied back
-        by the decode workers: no drain between batches.  Results come back in the caller's order."""
+        by the decode workers: no drain between batches.  Results come back in the caller's order.
+
+        `hotwords` (Zipformer family, modified beam search): None, or one HotwordGraph (runtime/k2_hotwords.py) or None per
+        utterance.  The distinct graphs of the call become one device table (`hotword_set`) and every utterance's graph index
+        travels with it through sorting and grouping; a batch without any graph runs the plain search."""
         n = len(waveforms)
         if n == 0:
             return DecodedBatch([], [], [])
         waveforms = [np.asarray(w, dtype=np.float32) for w in waveforms]
+        plan = self.graph_plan(hotwords, n)
         if n <= max_batch:
-            buf = self.stage(waveforms)
+            buf = self.stage(waveforms, hotwords=plan)
             self.run_device(buf)
             res = self.collect(buf)
             if on_batch is not None:
@@ -739,7 +831,7 @@ class AsrModel:
         pool = self._pool(max_batch, l_max, n_sets)
 
         def fill(i, buf):
-            return self.fill_host([waveforms[k] for k in groups[i]], buf)
+            return self.fill_host([waveforms[k] for k in groups[i]], buf, hotwords=plan, members=groups[i])
 
         # `on_batch` runs on its own thread, in batch order: a decode lane that ran the caller's post-processing itself
         # would start its next batch that much later (ids -> text is ~25 ms of Python per 256 utterances)

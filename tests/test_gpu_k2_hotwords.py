@@ -1,0 +1,261 @@
+"""-m gpu: hotwords in the modified beam search on the device (rs_rnnt_mbs_hotwords, csrc/k_rnnt_mbs.hip) against its C checker
+(tests/k2_hotwords_checker.c): ids, frames and the float32 score of every utterance BIT FOR BIT, given the device's own
+joiner.encoder_proj output.
+
+  toy geometry (V = 97)      K = 1, 2, 4, 8; 7 ragged utterances with a zero-frame row; three graphs + "none" spread over the rows
+                             (tests/k2_hotwords_ref.py: toy_graphs — A cut from the plain search's final sets, B overlapping phrases,
+                             C one single-token phrase); the checker's counters show that children, fail links, non-strict exits and
+                             Finalize were all met, and at K >= 2 the hotwords change a result; blank_penalty 1.5 and no length
+                             normalisation once each
+  159M decoder geometry      V = 10 720, J = D = 512, B = 5, Tp = 30, K = 4: one graph of 3000 random phrases over 400 first tokens
+                             (a long child list at the root, the any-V form of the selection kernel)
+  no graph                   graph_of all -1 == rs_rnnt_mbs, bits
+  batch invariance           an utterance alone with its graph == the same utterance in a ragged batch of other graphs / none
+  the public surface         K2Model(hotwords=...), transcribe == transcribe_batch row, per-audio hotwords, create_stream(hotwords=)
+                             overriding the model's graph, 9 utterances at max_batch = 4 through the host pipeline == one batch
+  errors                     RS_EINVAL on a nemo context; a table that fails rs_hotwords_check is refused before any launch
+"""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import k2_hotwords_ref as H
+import k2_mbs_ref as R
+from reazonspeech_amd.k2.asr import interface
+from reazonspeech_amd.k2.asr.model import K2Model, synthetic_tokens
+from reazonspeech_amd.runtime import capi, k2_hotwords as kh
+from reazonspeech_amd.runtime.config import TINY
+from reazonspeech_amd.runtime.k2_config import ZIPFORMER_TINY
+from reazonspeech_amd.runtime.k2_weights import synthetic_state_dict_k2
+from reazonspeech_amd.runtime.model import AsrModel, _HotwordSet
+from reazonspeech_amd.runtime.synth import synthetic_batch
+from reazonspeech_amd.runtime.tokenizer import SyntheticTokenizer
+from reazonspeech_amd.runtime.weights import synthetic_state_dict
+
+k2tr = importlib.import_module("reazonspeech_amd.k2.asr.transcribe")
+
+pytestmark = pytest.mark.gpu
+PAD = int(0.9 * 16000)
+
+
+def build(cfg, seed, sd=None, **kw):
+    sd = sd if sd is not None else synthetic_state_dict_k2(cfg, seed)
+    return K2Model(cfg, sd, synthetic_tokens(cfg.vocab_size, seed), device="cuda:0", **kw), sd
+
+
+def ragged_waves(n, seconds, seed, min_seconds):
+    audio, lens = synthetic_batch(n, seconds, seed=seed, ragged=True, min_seconds=min_seconds)
+    return [np.pad(audio[b, :lens[b]], PAD) for b in range(n)]
+
+
+def device_search(am, f, lens, K, hw=None, graph_of=None, blank_penalty=0.0, length_norm=True, plain=False):
+    """rs_rnnt_mbs_hotwords (or, `plain`, rs_rnnt_mbs) on a projection f [B][Tp][J] -> list of (ids, frames, score bits)"""
+    dev = am.device
+    B, Tp, _ = f.shape
+    out_cap = max(Tp, 1)
+    f = f.to(dev).contiguous()
+    lens = torch.as_tensor(np.asarray(lens), dtype=torch.int32).to(dev)
+    ids = torch.zeros((B, out_cap), dtype=torch.int32, device=dev)
+    frames = torch.zeros_like(ids)
+    n_ids = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    scores = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    if plain:
+        ws = torch.empty((am.ctx.mbs_workspace_bytes(B, K, Tp, out_cap),), dtype=torch.uint8, device=dev)
+        am.ctx.rnnt_mbs(f, lens, B, Tp, K, blank_penalty, length_norm, ids, frames, n_ids, scores, ws, stream)
+    else:
+        gof = None if graph_of is None else torch.as_tensor(np.asarray(graph_of), dtype=torch.int32).to(dev)
+        ws = torch.empty((am.ctx.mbs_hotwords_workspace_bytes(B, K, Tp, out_cap),), dtype=torch.uint8, device=dev)
+        am.ctx.rnnt_mbs_hotwords(f, lens, B, Tp, K, blank_penalty, length_norm, ids, frames, n_ids, scores,
+                                 hw.struct if hw is not None else None, gof, ws, stream)
+    torch.cuda.synchronize()
+    n = n_ids.cpu().numpy()
+    bits = scores.cpu().numpy().view(np.int32)
+    return [(ids[b, :n[b]].cpu().tolist(), frames[b, :n[b]].cpu().tolist(), int(bits[b])) for b in range(B)]
+
+
+def check(cfg, sd, am, f, lens, graphs, graph_of, **kw):
+    """device == checker, bits; -> (device rows, checker rows)"""
+    hw = _HotwordSet(graphs, am.device)
+    got = device_search(am, f, lens, hw=hw, graph_of=graph_of, **kw)
+    want = H.hw_checker(cfg, sd, f.cpu().numpy(), np.asarray(lens, np.int32), kh.concat(graphs), graph_of, **kw)
+    for b, (g, w) in enumerate(zip(got, want)):
+        assert g[0] == w["ids"] and g[1] == w["frames"], (kw, b, g[:2], w["ids"], w["frames"])
+        assert g[2] == w["score_bits"], (kw, b, g[2], w["score_bits"], w["score"])
+    return got, want
+
+
+def encoder_projection(model, waves):
+    am = model.am
+    buf = am.stage(waves, buf=am.new_buffers(len(waves), max(len(w) for w in waves)))
+    am.run_device(buf)
+    torch.cuda.synchronize()
+    got = am.collect(buf)
+    return buf.joint_enc.clone(), list(got.enc_lens)
+
+
+GRAPH_OF = [0, 1, -1, 2, -1, 1, 0]            # graphs A, B, C and "none" over the seven rows (row 2 has no frames)
+
+
+@pytest.fixture(scope="module")
+def tiny(gpu_device):
+    return build(ZIPFORMER_TINY, 3)
+
+
+@pytest.fixture(scope="module")
+def toy(tiny):
+    """the device's own projection of seven ragged utterances, the plain search's results on it (checker, K = 4) and the graphs"""
+    model, sd = tiny
+    f, lens = encoder_projection(model, ragged_waves(7, 3.0, 5, 0.7))
+    lens[2] = 0
+    plain = R.mbs_checker(ZIPFORMER_TINY, sd, f.cpu().numpy(), np.asarray(lens, np.int32), K=4)
+    graphs = [kh.build_graph(p) for p in H.toy_graphs(plain)]
+    return f, lens, graphs
+
+
+@pytest.mark.parametrize("K,kw", [(1, {}), (2, {}), (4, {}), (8, {}), (4, dict(blank_penalty=1.5)), (4, dict(length_norm=False))])
+def test_device_equals_checker_toy_geometry(tiny, toy, K, kw):
+    model, sd = tiny
+    f, lens, graphs = toy
+    got, want = check(ZIPFORMER_TINY, sd, model.am, f, lens, graphs, GRAPH_OF, K=K, **kw)
+    assert got[2] == ([], [], 0)                                          # no frames: no tokens, log_prob 0
+    plain = device_search(model.am, f, lens, K=K, plain=True, **kw)
+    for b, g in enumerate(GRAPH_OF):
+        if g < 0:
+            assert got[b] == plain[b], b                                  # a row without a graph inside a hotword batch: the plain bits
+    totals = {k: sum(w[k] for w in want) for k in ("child_hits", "fail_transitions", "exits")}
+    finalized = sum(w["finalize"] != 0.0 for w in want)
+    differ = [b for b in range(len(lens)) if got[b][0] != plain[b][0]]
+    print(f"K = {K} {kw}: {totals}, rows with a non-zero Finalize {finalized}, rows whose ids differ from the plain search {differ}")
+    redo = "the graphs are not met on this projection: the inputs need re-choosing (tests/k2_hotwords_ref.py toy_graphs)"
+    if not kw:
+        assert min(totals.values()) > 0 and finalized > 0, redo
+    if K >= 2:
+        assert differ, redo
+
+
+def test_159m_decoder_geometry_long_child_list(gpu_device):
+    cfg = ZIPFORMER_TINY.with_(vocab_size=10720, decoder_dim=512, joiner_dim=512).validate()
+    model, sd = build(cfg, 0)
+    g = torch.Generator().manual_seed(2)
+    B, Tp = 5, 30
+    f = torch.randn((B, Tp, cfg.joiner_dim), generator=g) * (0.8 + 0.4 * torch.rand((B, 1, 1), generator=g))
+    lens = [30, 17, 0, 25, 9]
+    plain = R.mbs_checker(cfg, sd, f.numpy(), np.asarray(lens, np.int32), K=4)
+    rng = np.random.default_rng(7)
+    seen = sorted({t for r in plain for y, _ in r["final"] for t in y})    # tokens the search proposes: the phrases must meet some
+    firsts = (seen + [int(t) for t in rng.permutation(np.arange(3, cfg.vocab_size)) if t not in set(seen)])[:400]
+    phrases = []
+    for _ in range(3000):
+        n = int(rng.integers(1, 5))
+        tail = [int(rng.choice(seen)) if rng.random() < 0.5 else int(rng.integers(3, cfg.vocab_size)) for _ in range(n - 1)]
+        phrases.append(((int(rng.choice(firsts)), *tail), float(rng.choice([1.0, 1.5, 2.0, 4.0]))))
+    graph = kh.build_graph(phrases)
+    root_children = graph.arrays["child_begin"][1] - graph.arrays["child_begin"][0]
+    assert root_children >= 390 and graph.max_level == 4
+    got, want = check(cfg, sd, model.am, f, lens, [graph], [0, 0, 0, -1, 0], K=4)
+    print("159M decoder geometry:", root_children, "children of the root; hits", sum(w["child_hits"] for w in want), "fails",
+          sum(w["fail_transitions"] for w in want), "exits", sum(w["exits"] for w in want))
+    assert sum(w["child_hits"] for w in want) > 0
+
+
+def test_no_graph_is_the_plain_search(tiny, toy):
+    model, _ = tiny
+    f, lens, graphs = toy
+    hw = _HotwordSet(graphs, model.am.device)
+    for K in (2, 4):
+        plain = device_search(model.am, f, lens, K=K, plain=True)
+        assert device_search(model.am, f, lens, K=K, hw=hw, graph_of=[-1] * 7) == plain
+        assert device_search(model.am, f, lens, K=K, hw=None, graph_of=None) == plain
+
+
+def test_alone_equals_inside_a_ragged_batch(tiny, toy):
+    model, _ = tiny
+    f, lens, graphs = toy
+    hw = _HotwordSet(graphs, model.am.device)
+    together = device_search(model.am, f, lens, K=4, hw=hw, graph_of=GRAPH_OF)
+    for b in (0, 1, 3):
+        one = _HotwordSet([graphs[GRAPH_OF[b]]], model.am.device)
+        alone = device_search(model.am, f[b:b + 1, :lens[b]], lens[b:b + 1], K=4, hw=one, graph_of=[0])
+        assert alone[0] == together[b], b
+
+
+def test_through_k2model_and_the_transcribe_functions(tiny, toy):
+    cfg = ZIPFORMER_TINY
+    _, sd = tiny
+    plain_model, _ = build(cfg, 3, sd=sd, decoding_method="modified_beam_search")
+    audio, lens = synthetic_batch(9, 2.0, seed=50, ragged=True, min_seconds=0.5)
+    audios = [interface.AudioData(audio[b, :lens[b]], 16000) for b in range(9)]
+    conf = interface.TranscribeConfig(verbose=False)
+    base = k2tr.transcribe_batch(plain_model, audios, conf)
+    # hotwords as token ids, cut from what the plain search says: the first tokens of some results and single tokens, score 4
+    waves = [np.pad(a.waveform, PAD) for a in audios]
+    dec = plain_model.am.transcribe_waveforms(waves)
+    spec_a = [(tuple(ids[:2]), 4.0) for ids in dec.ids if len(ids) >= 2][:4]
+    flat = [t for ids in dec.ids for t in ids]
+    spec_b = [((max(set(flat), key=flat.count),), 4.0)]
+    model, _ = build(cfg, 3, sd=sd, decoding_method="modified_beam_search", hotwords=spec_a)
+    assert model.hotwords is not None and model.hotwords.n_phrases == len(spec_a)
+    res = k2tr.transcribe_batch(model, audios, conf)
+    text = lambda rs: [r.text for r in rs]                                 # noqa: E731
+    assert text(res) != text(base), "the model's hotwords must change a transcript: re-choose the phrases"
+    for b in (0, 4):                                                       # transcribe == the transcribe_batch row
+        one = k2tr.transcribe(model, audios[b], conf)
+        assert one.text == res[b].text and [s.seconds for s in one.subwords] == [s.seconds for s in res[b].subwords]
+    # the runtime's results are the checker's on the device's projection, with the model's graph on every row
+    am = model.am
+    plan = am.graph_plan([model.hotwords] * 9, 9)
+    buf = am.stage(waves, buf=am.new_buffers(9, max(len(w) for w in waves)), hotwords=plan)
+    am.run_device(buf)
+    torch.cuda.synchronize()
+    got = am.collect(buf)
+    want = H.hw_checker(cfg, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), kh.concat([model.hotwords]), [0] * 9, K=4)
+    assert got.ids == [w["ids"] for w in want] and got.frames == [w["frames"] for w in want]
+    assert [np.float32(s) for s in got.scores] == [np.float32(w["score"]) for w in want]
+    assert ["".join(model.symbol(i) for i in ids) for ids in got.ids] == text(res)
+    # per-audio hotwords: None = the model's graph, a specification = that graph instead of it
+    per = [None, spec_b, None, spec_b, spec_a, None, spec_b, None, spec_b]
+    mixed = k2tr.transcribe_batch(model, audios, conf, hotwords=per)
+    only_b = k2tr.transcribe_batch(plain_model, audios, conf, hotwords=[spec_b] * 9)
+    assert text(mixed) == [(only_b if per[b] is spec_b else res)[b].text for b in range(9)]
+    assert k2tr.transcribe(model, audios[3], conf, hotwords=spec_b).text == only_b[3].text
+    # create_stream(hotwords=...) overrides the model's graph; a stream without uses the model's
+    streams = [model.create_stream(hotwords=spec_b if b % 2 else None) for b in range(9)]
+    for st, w in zip(streams, waves):
+        st.accept_waveform(16000, w)
+    model.decode_streams(streams)
+    assert [st.result.text for st in streams] == [(only_b if b % 2 else res)[b].text for b in range(9)]
+    # a list longer than max_batch goes through the host pipeline: the graph index follows its utterance through sorting and grouping
+    graphs = [model.hotword_graph(spec_b) if b % 2 else (model.hotwords if b % 3 else None) for b in range(9)]
+    whole = am.transcribe_waveforms(waves, hotwords=graphs)
+    parts = am.transcribe_waveforms(waves, max_batch=4, hotwords=graphs)
+    assert (whole.ids, whole.frames, whole.scores) == (parts.ids, parts.frames, parts.scores)
+    assert whole.ids != dec.ids
+
+
+def test_errors(tiny, toy):
+    model, _ = tiny
+    f, lens, graphs = toy
+    sd = synthetic_state_dict(TINY, 0)
+    nemo = AsrModel(TINY, sd, SyntheticTokenizer(TINY.vocab_size), device="cuda:0")
+    with pytest.raises(RuntimeError):
+        nemo.ctx.mbs_hotwords_workspace_bytes(2, 4, 10, 10)
+    dev = nemo.device
+    z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)          # noqa: E731
+    hw = _HotwordSet(graphs, dev)
+    with pytest.raises(capi.RsError, match="Zipformer") as e:
+        nemo.ctx.rnnt_mbs_hotwords(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 0.0, True, z(2, 10), z(2, 10),
+                                   z(2), torch.zeros((2,), device=dev), hw.struct, z(2), torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0)
+    assert e.value.code == capi.RS_EINVAL
+    # a table that fails the check never reaches the device: _HotwordSet raises before it uploads anything
+    bad = kh.build_graph([((5, 6, 7), 2.0), ((6, 7), 1.5)])
+    bad.arrays["fail"][2] = 2                                              # a fail link that does not lower the level
+    with pytest.raises(capi.RsError, match="does not lower the level") as e:
+        _HotwordSet([bad], model.am.device)
+    assert e.value.code == capi.RS_EINVAL
+    with pytest.raises(ValueError, match="modified_beam_search"):         # the greedy model refuses hotwords at every entrance
+        model.create_stream(hotwords=[(5, 6)])
+    with pytest.raises(ValueError, match="modified_beam_search"):
+        model.am.transcribe_waveforms([np.zeros(16000, np.float32)], hotwords=[graphs[0]])
