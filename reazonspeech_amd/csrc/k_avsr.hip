@@ -643,17 +643,6 @@ AvsrPlan avsr_plan(const rs_avsr& k, int B, int T, rs_arena& a) {
     return p;
 }
 
-template <typename T>
-int avsr_get(rs_ctx* ctx, const std::string& name, size_t elems, const T*& out) {
-    auto it = ctx->tensors.find(name);
-    if (it == ctx->tensors.end()) return rs_fail(ctx, RS_EMISSING, "weight tensor '%s' was not registered", name.c_str());
-    if (it->second.second != elems * sizeof(T))
-        return rs_fail(ctx, RS_EINVAL, "tensor '%s': expected %zu bytes, got %zu", name.c_str(), elems * sizeof(T), it->second.second);
-    if ((uintptr_t)it->second.first & 15) return rs_fail(ctx, RS_EINVAL, "tensor '%s' is not 16-byte aligned", name.c_str());
-    out = reinterpret_cast<const T*>(it->second.first);
-    return RS_OK;
-}
-
 void avsr_free(rs_avsr* k) { delete k; }
 
 int launch_attn(rs_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, size_t kstride, const float* kmask, int mask_pitch, int rows_per_kb,
@@ -726,51 +715,50 @@ extern "C" int rs_avsr_create(rs_ctx** out, int device, const rs_avsr_dims* dims
 int rs_avsr_finalize_impl(rs_ctx* ctx) {
     rs_avsr& k = *ctx->avsr;
     const rs_avsr_dims& d = k.d;
-    int rc;
     const size_t dm = d.encoder_embed_dim, ffn = d.encoder_ffn_dim, dffn = d.decoder_ffn_dim;
-#define AV_GET(name, elems, field) do { rc = avsr_get(ctx, name, (size_t)(elems), field); if (rc != RS_OK) return rc; } while (0)
-    AV_GET("fe.audio.w", dm * pad32(d.audio_feat_dim), k.audio_w); AV_GET("fe.audio.b", dm, k.audio_b);
-    AV_GET("v.conv3d.w", 245 * 64, k.conv3d_w); AV_GET("v.bn0.alpha", 64, k.bn0_a); AV_GET("v.bn0.beta", 64, k.bn0_b); AV_GET("v.prelu0", 64, k.prelu0);
+    rs_weights r(ctx);
+    r.get("fe.audio.w", dm * pad32(d.audio_feat_dim), k.audio_w); r.get("fe.audio.b", dm, k.audio_b);
+    r.get("v.conv3d.w", 245 * 64, k.conv3d_w); r.get("v.bn0.alpha", 64, k.bn0_a); r.get("v.bn0.beta", 64, k.bn0_b); r.get("v.prelu0", 64, k.prelu0);
     for (int L = 1; L <= 4; ++L)
         for (int b = 0; b < 2; ++b) {
             rs_avsr_block& B = k.blocks[L - 1][b];
             const std::string p = "v.l" + std::to_string(L) + "." + std::to_string(b) + ".";
             const size_t cin = b == 0 ? TRUNK_C[L - 1] : TRUNK_C[L], c = TRUNK_C[L];
-            AV_GET(p + "conv1.w", c * 9 * cin, B.conv1_w); AV_GET(p + "conv2.w", c * 9 * c, B.conv2_w);
-            AV_GET(p + "bn1.alpha", c, B.bn1_a); AV_GET(p + "bn1.beta", c, B.bn1_b); AV_GET(p + "bn2.alpha", c, B.bn2_a); AV_GET(p + "bn2.beta", c, B.bn2_b);
-            AV_GET(p + "relu1", c, B.relu1); AV_GET(p + "relu2", c, B.relu2);
+            r.get(p + "conv1.w", c * 9 * cin, B.conv1_w); r.get(p + "conv2.w", c * 9 * c, B.conv2_w);
+            r.get(p + "bn1.alpha", c, B.bn1_a); r.get(p + "bn1.beta", c, B.bn1_b); r.get(p + "bn2.alpha", c, B.bn2_a); r.get(p + "bn2.beta", c, B.bn2_b);
+            r.get(p + "relu1", c, B.relu1); r.get(p + "relu2", c, B.relu2);
             B.ds_w = B.ds_a = B.ds_b = nullptr;
-            if (b == 0 && L > 1) { AV_GET(p + "ds.w", c * cin, B.ds_w); AV_GET(p + "ds.bn.alpha", c, B.ds_a); AV_GET(p + "ds.bn.beta", c, B.ds_b); }
+            if (b == 0 && L > 1) { r.get(p + "ds.w", c * cin, B.ds_w); r.get(p + "ds.bn.alpha", c, B.ds_a); r.get(p + "ds.bn.beta", c, B.ds_b); }
         }
-    AV_GET("v.proj.w", dm * 512, k.vproj_w); AV_GET("v.proj.b", dm, k.vproj_b);
-    AV_GET("fuse.ln.g", 2 * dm, k.fuse_g); AV_GET("fuse.ln.b", 2 * dm, k.fuse_b);
-    AV_GET("fuse.proj.w", dm * 2 * dm, k.fproj_w); AV_GET("fuse.proj.b", dm, k.fproj_b);
+    r.get("v.proj.w", dm * 512, k.vproj_w); r.get("v.proj.b", dm, k.vproj_b);
+    r.get("fuse.ln.g", 2 * dm, k.fuse_g); r.get("fuse.ln.b", 2 * dm, k.fuse_b);
+    r.get("fuse.proj.w", dm * 2 * dm, k.fproj_w); r.get("fuse.proj.b", dm, k.fproj_b);
     const size_t cg = dm / d.conv_pos_groups;
-    AV_GET("enc.pos.w", (size_t)d.conv_pos_groups * d.conv_pos * cg * cg, k.pos_w); AV_GET("enc.pos.b", dm, k.pos_b);
-    AV_GET("enc.ln.g", dm, k.encln_g); AV_GET("enc.ln.b", dm, k.encln_b);
+    r.get("enc.pos.w", (size_t)d.conv_pos_groups * d.conv_pos * cg * cg, k.pos_w); r.get("enc.pos.b", dm, k.pos_b);
+    r.get("enc.ln.g", dm, k.encln_g); r.get("enc.ln.b", dm, k.encln_b);
     k.enc.assign(d.encoder_layers, rs_avsr_layer{});
     for (int i = 0; i < d.encoder_layers; ++i) {
         rs_avsr_layer& L = k.enc[i];
         const std::string p = "E" + std::to_string(i) + ".";
-        AV_GET(p + "qkv.w", 3 * dm * dm, L.sa.qkv_w); AV_GET(p + "qkv.b", 3 * dm, L.sa.qkv_b); AV_GET(p + "o.w", dm * dm, L.sa.o_w); AV_GET(p + "o.b", dm, L.sa.o_b);
-        AV_GET(p + "ln1.g", dm, L.ln1_g); AV_GET(p + "ln1.b", dm, L.ln1_b); AV_GET(p + "ln2.g", dm, L.ln2_g); AV_GET(p + "ln2.b", dm, L.ln2_b);
-        AV_GET(p + "ff1.w", ffn * dm, L.ff1_w); AV_GET(p + "ff1.b", ffn, L.ff1_b); AV_GET(p + "ff2.w", dm * ffn, L.ff2_w); AV_GET(p + "ff2.b", dm, L.ff2_b);
+        r.get(p + "qkv.w", 3 * dm * dm, L.sa.qkv_w); r.get(p + "qkv.b", 3 * dm, L.sa.qkv_b); r.get(p + "o.w", dm * dm, L.sa.o_w); r.get(p + "o.b", dm, L.sa.o_b);
+        r.get(p + "ln1.g", dm, L.ln1_g); r.get(p + "ln1.b", dm, L.ln1_b); r.get(p + "ln2.g", dm, L.ln2_g); r.get(p + "ln2.b", dm, L.ln2_b);
+        r.get(p + "ff1.w", ffn * dm, L.ff1_w); r.get(p + "ff1.b", ffn, L.ff1_b); r.get(p + "ff2.w", dm * ffn, L.ff2_w); r.get(p + "ff2.b", dm, L.ff2_b);
     }
-    AV_GET("dec.embed", (size_t)d.vocab_size * dm, k.embed); AV_GET("dec.pos", (size_t)d.max_positions * dm, k.dec_pos);
-    AV_GET("dec.ln.g", dm, k.decln_g); AV_GET("dec.ln.b", dm, k.decln_b);
-    AV_GET("dec.lm.w", (size_t)pad4(d.vocab_size) * dm, k.lm_w);
+    r.get("dec.embed", (size_t)d.vocab_size * dm, k.embed); r.get("dec.pos", (size_t)d.max_positions * dm, k.dec_pos);
+    r.get("dec.ln.g", dm, k.decln_g); r.get("dec.ln.b", dm, k.decln_b);
+    r.get("dec.lm.w", (size_t)pad4(d.vocab_size) * dm, k.lm_w);
     k.dec.assign(d.decoder_layers, rs_avsr_layer{});
     for (int i = 0; i < d.decoder_layers; ++i) {
         rs_avsr_layer& L = k.dec[i];
         const std::string p = "D" + std::to_string(i) + ".";
-        AV_GET(p + "sa.qkv.w", 3 * dm * dm, L.sa.qkv_w); AV_GET(p + "sa.qkv.b", 3 * dm, L.sa.qkv_b); AV_GET(p + "sa.o.w", dm * dm, L.sa.o_w); AV_GET(p + "sa.o.b", dm, L.sa.o_b);
-        AV_GET(p + "ca.q.w", dm * dm, L.ca.q_w); AV_GET(p + "ca.q.b", dm, L.ca.q_b); AV_GET(p + "ca.kv.w", 2 * dm * dm, L.ca.kv_w); AV_GET(p + "ca.kv.b", 2 * dm, L.ca.kv_b);
-        AV_GET(p + "ca.o.w", dm * dm, L.ca.o_w); AV_GET(p + "ca.o.b", dm, L.ca.o_b);
-        AV_GET(p + "ln1.g", dm, L.ln1_g); AV_GET(p + "ln1.b", dm, L.ln1_b); AV_GET(p + "ln2.g", dm, L.ln2_g); AV_GET(p + "ln2.b", dm, L.ln2_b);
-        AV_GET(p + "ln3.g", dm, L.ln3_g); AV_GET(p + "ln3.b", dm, L.ln3_b);
-        AV_GET(p + "ff1.w", dffn * dm, L.ff1_w); AV_GET(p + "ff1.b", dffn, L.ff1_b); AV_GET(p + "ff2.w", dm * dffn, L.ff2_w); AV_GET(p + "ff2.b", dm, L.ff2_b);
+        r.get(p + "sa.qkv.w", 3 * dm * dm, L.sa.qkv_w); r.get(p + "sa.qkv.b", 3 * dm, L.sa.qkv_b); r.get(p + "sa.o.w", dm * dm, L.sa.o_w); r.get(p + "sa.o.b", dm, L.sa.o_b);
+        r.get(p + "ca.q.w", dm * dm, L.ca.q_w); r.get(p + "ca.q.b", dm, L.ca.q_b); r.get(p + "ca.kv.w", 2 * dm * dm, L.ca.kv_w); r.get(p + "ca.kv.b", 2 * dm, L.ca.kv_b);
+        r.get(p + "ca.o.w", dm * dm, L.ca.o_w); r.get(p + "ca.o.b", dm, L.ca.o_b);
+        r.get(p + "ln1.g", dm, L.ln1_g); r.get(p + "ln1.b", dm, L.ln1_b); r.get(p + "ln2.g", dm, L.ln2_g); r.get(p + "ln2.b", dm, L.ln2_b);
+        r.get(p + "ln3.g", dm, L.ln3_g); r.get(p + "ln3.b", dm, L.ln3_b);
+        r.get(p + "ff1.w", dffn * dm, L.ff1_w); r.get(p + "ff1.b", dffn, L.ff1_b); r.get(p + "ff2.w", dm * dffn, L.ff2_w); r.get(p + "ff2.b", dm, L.ff2_b);
     }
-#undef AV_GET
+    if (!r.ok()) return r.fail(ctx);
     ctx->finalized = true;
     return RS_OK;
 }

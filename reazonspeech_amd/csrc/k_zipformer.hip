@@ -27,19 +27,6 @@
 
 #include "rs_common.h"
 
-struct rs_k2_layer {
-    const uint16_t *attw_in_w, *sa_in_w[2], *sa_out_w[2], *ff_in_w[3], *ff_out_w[3], *na_in_w, *na_out_w, *cm_in_w[2], *cm_out_w[2];
-    const float *attw_in_b, *pos_proj, *sa_in_b[2], *sa_out_b[2], *ff_in_b[3], *ff_out_b[3], *na_in_b, *na_out_b, *cm_in_b[2], *cm_dw_w[2],
-        *cm_dw_b[2], *cm_out_b[2], *norm_bias, *norm_scale, *bypass, *bypass_mid;
-};
-
-// float32 parity mode: the dense weights once more, unrounded ("<name>.f32"; the conv modules' in_proj in icefall's own row
-// order: values, then gates).  Biases, BiasNorm / bypass / down-sampling constants, depthwise taps and the projected position
-// rows are float32 in the throughput mode already and are shared.
-struct rs_k2_layer32 {
-    const float *attw_in_w, *sa_in_w[2], *sa_out_w[2], *ff_in_w[3], *ff_out_w[3], *na_in_w, *na_out_w, *cm_in_w[2], *cm_in_b[2], *cm_out_w[2];
-};
-
 // int8 mode ("precision_i8"): a quantized Linear of the int8 ONNX files — "<name>.i8" int8 [N][pad32(K)] in the layout of
 // "<name>.f32" (padding columns zero), "<name>.i8.cs" int32 [N] column sums over K, "<name>.i8.q" f32 [4] = (sw, zw, 0, 0).
 // w == nullptr: that Linear is not quantized and stays on the float32 GEMM.
@@ -50,24 +37,36 @@ struct rs_k2_q8 {
     int ldw = 0;
 };
 
-struct rs_k2_layer8 {
-    rs_k2_q8 attw_in, pos, sa_in[2], sa_out[2], ff_in[3], ff_out[3], na_in, na_out, cm_in[2], cm_out[2];
+// One Linear (or convolution run as one) y = W x + b with W [N][K], in every form a precision mode reads; k2_get_linear fills
+// it from the base name and it is all a forward function's call site needs to know about the weights.
+struct rs_k2_linear {
+    int N = 0, K = 0;
+    int ld16 = 0, ld32 = 0;        // row pitch of w = pad64(K) and of w32 = pad32(K): also the pitch of the operand rows
+    const uint16_t* w = nullptr;   // "<base>.w" bf16 [N][ld16]
+    const float* b = nullptr;      // "<base>.b" f32 [N]
+    // float32 parity mode: the weights once more, unrounded ("<base>.w.f32" f32 [N][ld32]).  The bias is the same tensor except for
+    // the conv modules' in_proj, whose float32 rows are in icefall's own order (values, then gates): "<base>.b.f32"
+    const float* w32 = nullptr;
+    const float* b32 = nullptr;
+    rs_k2_q8 q;                    // "<base>.w.i8" / ".i8.cs" / ".i8.q"
+};
+
+// `pos` is linear_pos, which exists in the int8 form only: the other modes read its product with the position encoding, pos_proj
+// (float32 in every mode, like the biases, BiasNorm / bypass constants and depthwise taps).
+struct rs_k2_layer {
+    rs_k2_linear attw_in, pos, sa_in[2], sa_out[2], ff_in[3], ff_out[3], na_in, na_out, cm_in[2], cm_out[2];
+    const float *pos_proj, *cm_dw_w[2], *cm_dw_b[2], *norm_bias, *norm_scale, *bypass, *bypass_mid;
 };
 
 struct rs_k2 {
     rs_k2_dims d{};
     std::vector<std::vector<rs_k2_layer>> stacks;
-    std::vector<std::vector<rs_k2_layer32>> stacks32;
-    std::vector<std::vector<rs_k2_layer8>> stacks8;
-    rs_k2_q8 emb_out8, jenc8;
+    rs_k2_linear conv2, cnx_pw1, cnx_pw2, emb_out, jenc;     // (ctx->jenc_w / jenc_b repeat jenc.w / jenc.b for the shared decode)
     const float* pos_enc = nullptr;  // "pos.enc" f32 [2 * pos_cap - 1][pos_dim]: the encoding itself, for a quantized linear_pos
     bool has_i8 = false;             // at least one "<name>.i8" is registered
-    const float *conv2_w32 = nullptr, *cnx_pw1_w32 = nullptr, *cnx_pw2_w32 = nullptr, *emb_out_w32 = nullptr, *jenc_w32 = nullptr;
     const float *ds_w[8] = {}, *comb_scale[8] = {}, *out_ds_w = nullptr;
-    const float *conv0_w = nullptr, *conv0_b = nullptr, *conv1_w = nullptr, *conv1_b = nullptr, *conv2_b = nullptr, *cnx_dw_w = nullptr,
-                *cnx_dw_b = nullptr, *cnx_pw1_b = nullptr, *cnx_pw2_b = nullptr, *emb_out_b = nullptr, *emb_norm_bias = nullptr,
-                *emb_norm_scale = nullptr;
-    const uint16_t *conv2_w = nullptr, *cnx_pw1_w = nullptr, *cnx_pw2_w = nullptr, *emb_out_w = nullptr;
+    const float *conv0_w = nullptr, *conv0_b = nullptr, *conv1_w = nullptr, *conv1_b = nullptr, *cnx_dw_w = nullptr, *cnx_dw_b = nullptr,
+                *emb_norm_bias = nullptr, *emb_norm_scale = nullptr;
     int pos_cap = 0;                 // rows of every "attw.pos_proj" table = 2 * pos_cap - 1
     int embed_freq = 0, out_dim = 0;
     float* tap_embed = nullptr;      // parity taps (rs_k2_encoder_set_taps)
@@ -79,6 +78,7 @@ namespace {
 constexpr int K2_QD = 32, K2_PD = 4, K2_VD = 12;
 
 __host__ __device__ inline int pad64(int n) { return (n + 63) / 64 * 64; }
+__host__ __device__ inline int pad32(int n) { return (n + 31) / 32 * 32; }
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ---- encoder_embed ---------------------------------------------------------------------------------------------------------
@@ -1182,9 +1182,27 @@ __global__ void k2_lens_kernel(const int32_t* __restrict__ n_frames, int B, int 
     for (int s = 0; s < n_stacks; ++s) out[(size_t)(1 + s) * B + b] = (l3 + ds[s] - 1) / ds[s];
 }
 
-struct K2Plan {
-    int T, T1, T2, T3, To, F, F2, F3, Kp;
+// frame and frequency counts of one call, shared by the two plans: T feature frames -> T1 / T2 / T3 after conv0 / conv1 / conv2
+// (F -> F2 -> F3 bins), To encoder frames; stack s runs Ts[s] = ceil(max(T3, 1) / downsampling) frames, Tp[s] = Ts padded to 32
+struct K2Geom {
+    int T, T1, T2, T3, To, F, F2, F3;
     int Ts[8], Tp[8];
+};
+K2Geom k2_geom(const rs_k2_dims& d, int t_max) {
+    K2Geom g{};
+    g.T = t_max; g.F = d.n_mels;
+    g.T1 = t_max - 2; g.T2 = g.T1 >= 3 ? (g.T1 - 3) / 2 + 1 : 0; g.T3 = g.T2 - 2;
+    if (g.T3 < 0) g.T3 = 0;
+    g.F2 = (g.F - 3) / 2 + 1; g.F3 = (g.F2 - 3) / 2 + 1;
+    g.To = (g.T3 + 1) / 2;
+    for (int s = 0; s < d.n_stacks; ++s) {
+        g.Ts[s] = ceil_div(g.T3 > 0 ? g.T3 : 1, d.downsampling[s]);
+        g.Tp[s] = (g.Ts[s] + 31) / 32 * 32;
+    }
+    return g;
+}
+
+struct K2Plan : K2Geom {
     int32_t* lens;
     uint16_t *a0, *a1, *col, *dwo, *h, *xb, *qkp, *w, *big, *av, *vt, *encb;
     float *a2, *stackout[8], *x, *x0, *src;
@@ -1195,18 +1213,13 @@ K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     const rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
     K2Plan p{};
-    p.T = t_max; p.F = d.n_mels;
-    p.T1 = t_max - 2; p.T2 = p.T1 >= 3 ? (p.T1 - 3) / 2 + 1 : 0; p.T3 = p.T2 - 2;
-    if (p.T3 < 0) p.T3 = 0;
-    p.F2 = (p.F - 3) / 2 + 1; p.F3 = (p.F2 - 3) / 2 + 1;
-    p.To = (p.T3 + 1) / 2;
-    p.Kp = pad64(9 * d.embed_c2);
+    static_cast<K2Geom&>(p) = k2_geom(d, t_max);
     const size_t T3 = p.T3 > 0 ? p.T3 : 1, T1 = p.T1 > 0 ? p.T1 : 1, T2 = p.T2 > 0 ? p.T2 : 1;
     const size_t rows3 = (size_t)B * T3 * p.F3;
     p.lens = a.take<int32_t>((size_t)(2 + d.n_stacks) * B);
     p.a0 = a.take<uint16_t>((size_t)B * T1 * p.F * d.embed_c1);
     p.a1 = a.take<uint16_t>((size_t)B * T2 * p.F2 * d.embed_c2);
-    p.col = a.take<uint16_t>(rows3 * p.Kp);
+    p.col = a.take<uint16_t>(rows3 * pad64(9 * d.embed_c2));
     p.a2 = a.take<float>(rows3 * d.embed_c3);
     p.dwo = a.take<uint16_t>(rows3 * d.embed_c3);
     p.h = a.take<uint16_t>(rows3 * 3 * d.embed_c3);
@@ -1214,8 +1227,6 @@ K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     size_t x_n = 0, qkp_n = 0, w_n = 0, big_n = 0, av_n = 0, vt_n = 0;
     for (int s = 0; s < d.n_stacks; ++s) {
         const size_t dd = d.encoder_dim[s], H = d.num_heads[s];
-        p.Ts[s] = ceil_div((int)T3, d.downsampling[s]);
-        p.Tp[s] = (p.Ts[s] + 31) / 32 * 32;
         p.stackout[s] = a.take<float>((size_t)B * T3 * dd);
         const size_t rows = (size_t)B * p.Ts[s];
         x_n = std::max(x_n, (size_t)B * T3 * dd);
@@ -1239,13 +1250,8 @@ K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     return p;
 }
 
-
-__host__ __device__ inline int pad32(int n) { return (n + 31) / 32 * 32; }
-
 // workspace of the float32 parity mode: the bf16 plan's tensors as float32, patches un-padded (K = 9 C2), no V^T copies
-struct K2PlanF32 {
-    int T, T1, T2, T3, To, F, F2, F3;
-    int Ts[8], Tp[8];
+struct K2PlanF32 : K2Geom {
     int32_t *lens, *lens2;
     float *a0, *a1, *col, *a2, *dwo, *h, *stackout[8], *x, *x0, *src, *qkp, *w, *big, *av, *gate, *enc;
     float *qp, *pos_in, *pos_tab;        // int8 mode only (with lens2), else nullptr
@@ -1255,11 +1261,7 @@ K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     const rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
     K2PlanF32 p{};
-    p.T = t_max; p.F = d.n_mels;
-    p.T1 = t_max - 2; p.T2 = p.T1 >= 3 ? (p.T1 - 3) / 2 + 1 : 0; p.T3 = p.T2 - 2;
-    if (p.T3 < 0) p.T3 = 0;
-    p.F2 = (p.F - 3) / 2 + 1; p.F3 = (p.F2 - 3) / 2 + 1;
-    p.To = (p.T3 + 1) / 2;
+    static_cast<K2Geom&>(p) = k2_geom(d, t_max);
     const size_t T3 = p.T3 > 0 ? p.T3 : 1, T1 = p.T1 > 0 ? p.T1 : 1, T2 = p.T2 > 0 ? p.T2 : 1;
     const size_t rows3 = (size_t)B * T3 * p.F3;
     p.lens = a.take<int32_t>((size_t)(2 + d.n_stacks) * B);
@@ -1272,8 +1274,6 @@ K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     size_t x_n = 0, qkp_n = 0, w_n = 0, big_n = 0, av_n = 0, gate_n = 0;
     for (int s = 0; s < d.n_stacks; ++s) {
         const size_t dd = d.encoder_dim[s], H = d.num_heads[s], hid = 3 * dd / 4;
-        p.Ts[s] = ceil_div((int)T3, d.downsampling[s]);
-        p.Tp[s] = (p.Ts[s] + 31) / 32 * 32;
         const size_t rows = (size_t)B * p.Ts[s];
         p.stackout[s] = a.take<float>((size_t)B * T3 * dd);
         x_n = std::max(x_n, (size_t)B * T3 * dd);
@@ -1304,15 +1304,52 @@ K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
     return p;
 }
 
-template <typename T>
-int k2_get(rs_ctx* ctx, const std::string& name, size_t elems, const T*& out) {
-    auto it = ctx->tensors.find(name);
-    if (it == ctx->tensors.end()) return rs_fail(ctx, RS_EMISSING, "weight tensor '%s' was not registered", name.c_str());
-    if (it->second.second != elems * sizeof(T))
-        return rs_fail(ctx, RS_EINVAL, "tensor '%s': expected %zu bytes, got %zu", name.c_str(), elems * sizeof(T), it->second.second);
-    if ((uintptr_t)it->second.first & 15) return rs_fail(ctx, RS_EINVAL, "tensor '%s' is not 16-byte aligned", name.c_str());
-    out = reinterpret_cast<const T*>(it->second.first);
-    return RS_OK;
+// The readers of a finalize, one per set of tensors: the sets are looked up side by side in one walk over the model, and an
+// error is reported set by set (the bf16 model first, then the float32 set, then the int8 one), in the walk's order within a set.
+struct K2Readers {
+    rs_weights w16, w32, w8;
+    bool f32;                // the float32 set is registered ("emb.out.w.f32" is): then every member of it is required
+    bool any_i8 = false;     // at least one Linear came with its int8 triple
+    explicit K2Readers(const rs_ctx* ctx) : w16(ctx), w32(ctx), w8(ctx), f32(w32.has("emb.out.w.f32")) {}
+};
+enum { K2_W16 = 1, K2_W32 = 2, K2_W8 = 4, K2_B32 = 8, K2_ALL = K2_W16 | K2_W32 | K2_W8 };
+
+// The Linear `base` with W [N][K], in the forms asked for: "<base>.w" / ".b"; "<base>.w.f32" (with K2_B32 also ".b.f32") when the
+// float32 set is there; "<base>.w.i8" / ".i8.cs" / ".i8.q" when this Linear's ".w.i8" is registered (each Linear on its own).
+void k2_get_linear(K2Readers& r, const std::string& base, size_t N, size_t K, int forms, rs_k2_linear& L) {
+    L.N = (int)N; L.K = (int)K; L.ld16 = pad64((int)K); L.ld32 = pad32((int)K);
+    if (forms & K2_W16) {
+        r.w16.get(base + ".w", N * L.ld16, L.w);
+        r.w16.get(base + ".b", N, L.b);
+        if (!(forms & K2_B32)) L.b32 = L.b;
+    }
+    if ((forms & K2_W32) && r.f32) {
+        r.w32.get(base + ".w.f32", N * L.ld32, L.w32);
+        if (forms & K2_B32) r.w32.get(base + ".b.f32", N, L.b32);
+    }
+    if ((forms & K2_W8) && r.w8.has(base + ".w.i8")) {
+        L.q.ldw = pad32((int)K);
+        r.w8.get(base + ".w.i8", N * L.q.ldw, L.q.w);
+        r.w8.get(base + ".w.i8.cs", N, L.q.cs);
+        r.w8.get(base + ".w.i8.q", 4, L.q.wq);
+        r.any_i8 = r.any_i8 || r.w8.ok();
+    }
+}
+
+// the encoder output's channels: the last stack's, then from each earlier stack that is wider the channels past the widest so far
+K2Pieces k2_pieces(const rs_k2_dims& d, float* const* stackout) {
+    K2Pieces pc{};
+    int n = 0, cur_dim = d.encoder_dim[d.n_stacks - 1];
+    pc.p[n] = stackout[d.n_stacks - 1]; pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
+    for (int st = d.n_stacks - 2; st >= 0; --st) {
+        const int dd = d.encoder_dim[st];
+        if (dd > cur_dim) {
+            pc.p[n] = stackout[st]; pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
+            cur_dim = dd;
+        }
+    }
+    pc.count = n;
+    return pc;
 }
 
 void k2_free(rs_k2* k) { delete k; }
@@ -1373,22 +1410,27 @@ extern "C" int rs_k2_encoder_set_taps(rs_ctx* ctx, float* embed_out, float* stac
 int rs_k2_finalize_impl(rs_ctx* ctx) {
     rs_k2& k = *ctx->k2;
     const rs_k2_dims& d = k.d;
-    int rc;
-#define K2_GET(name, elems, field) do { rc = k2_get(ctx, name, (size_t)(elems), field); if (rc != RS_OK) return rc; } while (0)
-    K2_GET("fe.window", d.frame_length, ctx->fe_window);
-    K2_GET("fe.twiddle", 512, ctx->fe_twiddle);
-    K2_GET("fe.fb_idx", d.n_mels * 2, ctx->fe_fb_idx);
-    K2_GET("fe.fb_w", d.n_mels * 32, ctx->fe_fb_w);
-    const int c1 = d.embed_c1, c2 = d.embed_c2, c3 = d.embed_c3, d0 = d.encoder_dim[0];
-    K2_GET("emb.conv0.w", 9 * c1, k.conv0_w); K2_GET("emb.conv0.b", c1, k.conv0_b);
-    K2_GET("emb.conv1.w", 9 * c1 * c2, k.conv1_w); K2_GET("emb.conv1.b", c2, k.conv1_b);
-    K2_GET("emb.conv2.w", (size_t)c3 * pad64(9 * c2), k.conv2_w); K2_GET("emb.conv2.b", c3, k.conv2_b);
-    K2_GET("emb.cnx.dw.w", 49 * c3, k.cnx_dw_w); K2_GET("emb.cnx.dw.b", c3, k.cnx_dw_b);
-    K2_GET("emb.cnx.pw1.w", 3 * c3 * c3, k.cnx_pw1_w); K2_GET("emb.cnx.pw1.b", 3 * c3, k.cnx_pw1_b);
-    K2_GET("emb.cnx.pw2.w", 3 * c3 * c3, k.cnx_pw2_w); K2_GET("emb.cnx.pw2.b", c3, k.cnx_pw2_b);
-    K2_GET("emb.out.w", (size_t)d0 * k.embed_freq * c3, k.emb_out_w); K2_GET("emb.out.b", d0, k.emb_out_b);
-    K2_GET("emb.norm.bias", d0, k.emb_norm_bias); K2_GET("emb.norm.scale", 4, k.emb_norm_scale);
+    K2Readers r(ctx);
+    rs_weights& w = r.w16;
+    w.get("fe.window", d.frame_length, ctx->fe_window);
+    w.get("fe.twiddle", 512, ctx->fe_twiddle);
+    w.get("fe.fb_idx", d.n_mels * 2, ctx->fe_fb_idx);
+    w.get("fe.fb_w", d.n_mels * 32, ctx->fe_fb_w);
+    const size_t c1 = d.embed_c1, c2 = d.embed_c2, c3 = d.embed_c3, d0 = d.encoder_dim[0], J = d.joiner_dim, D = d.decoder_dim, V = d.vocab_size;
+    k.conv2 = k.cnx_pw1 = k.cnx_pw2 = k.emb_out = k.jenc = rs_k2_linear{};
+    k.pos_enc = nullptr;
+    w.get("emb.conv0.w", 9 * c1, k.conv0_w); w.get("emb.conv0.b", c1, k.conv0_b);
+    w.get("emb.conv1.w", 9 * c1 * c2, k.conv1_w); w.get("emb.conv1.b", c2, k.conv1_b);
+    k2_get_linear(r, "emb.conv2", c3, 9 * c2, K2_W16 | K2_W32, k.conv2);
+    w.get("emb.cnx.dw.w", 49 * c3, k.cnx_dw_w); w.get("emb.cnx.dw.b", c3, k.cnx_dw_b);
+    k2_get_linear(r, "emb.cnx.pw1", 3 * c3, c3, K2_W16 | K2_W32, k.cnx_pw1);
+    k2_get_linear(r, "emb.cnx.pw2", c3, 3 * c3, K2_W16 | K2_W32, k.cnx_pw2);
+    k2_get_linear(r, "emb.out", d0, k.embed_freq * c3, K2_ALL, k.emb_out);
+    w.get("emb.norm.bias", d0, k.emb_norm_bias); w.get("emb.norm.scale", 4, k.emb_norm_scale);
+    // (joiner.encoder_proj's float32 and int8 forms: looked up here, ahead of the stacks' — the place they have in their sets)
+    k2_get_linear(r, "joint.enc", J, k.out_dim, K2_W32 | K2_W8, k.jenc);
     // the position tables all have 2 * cap - 1 rows
+    if (!w.ok()) return w.fail(ctx);
     {
         auto it = ctx->tensors.find("S0.L0.attw.pos_proj");
         if (it == ctx->tensors.end()) return rs_fail(ctx, RS_EMISSING, "weight tensor 'S0.L0.attw.pos_proj' was not registered");
@@ -1397,6 +1439,7 @@ int rs_k2_finalize_impl(rs_ctx* ctx) {
         k.pos_cap = (int)((it->second.second / row + 1) / 2);
     }
     k.stacks.assign(d.n_stacks, {});
+    bool any_pos = false;
     for (int s = 0; s < d.n_stacks; ++s) {
         const size_t dd = d.encoder_dim[s], H = d.num_heads[s], hid = 3 * dd / 4, kk = d.cnn_kernel[s];
         const size_t ff[3] = {(size_t)d.ff_dim[s] * 3 / 4, (size_t)d.ff_dim[s], (size_t)d.ff_dim[s] * 5 / 4};
@@ -1404,137 +1447,57 @@ int rs_k2_finalize_impl(rs_ctx* ctx) {
         for (int j = 0; j < d.num_layers[s]; ++j) {
             rs_k2_layer& L = k.stacks[s][j];
             const std::string p = "S" + std::to_string(s) + ".L" + std::to_string(j) + ".";
-            const size_t nin = (2 * K2_QD + K2_PD) * H;
-            K2_GET(p + "attw.in.w", nin * dd, L.attw_in_w); K2_GET(p + "attw.in.b", nin, L.attw_in_b);
-            K2_GET(p + "attw.pos_proj", (size_t)(2 * k.pos_cap - 1) * H * K2_PD, L.pos_proj);
-            for (int a = 0; a < 2; ++a) {
-                const std::string q = p + (a ? "sa2." : "sa1.");
-                K2_GET(q + "in.w", H * K2_VD * dd, L.sa_in_w[a]); K2_GET(q + "in.b", H * K2_VD, L.sa_in_b[a]);
-                K2_GET(q + "out.w", dd * pad64((int)(H * K2_VD)), L.sa_out_w[a]); K2_GET(q + "out.b", dd, L.sa_out_b[a]);
-                const std::string c = p + (a ? "cm2." : "cm1.");
-                K2_GET(c + "in.w", 2 * dd * dd, L.cm_in_w[a]); K2_GET(c + "in.b", 2 * dd, L.cm_in_b[a]);
-                K2_GET(c + "dw.w", kk * dd, L.cm_dw_w[a]); K2_GET(c + "dw.b", dd, L.cm_dw_b[a]);
-                K2_GET(c + "out.w", dd * dd, L.cm_out_w[a]); K2_GET(c + "out.b", dd, L.cm_out_b[a]);
-            }
-            for (int f = 0; f < 3; ++f) {
-                const std::string q = p + "ff" + std::to_string(f + 1) + ".";
-                K2_GET(q + "in.w", ff[f] * dd, L.ff_in_w[f]); K2_GET(q + "in.b", ff[f], L.ff_in_b[f]);
-                K2_GET(q + "out.w", dd * ff[f], L.ff_out_w[f]); K2_GET(q + "out.b", dd, L.ff_out_b[f]);
-            }
-            K2_GET(p + "na.in.w", 3 * hid * dd, L.na_in_w); K2_GET(p + "na.in.b", 3 * hid, L.na_in_b);
-            K2_GET(p + "na.out.w", dd * pad64((int)hid), L.na_out_w); K2_GET(p + "na.out.b", dd, L.na_out_b);
-            K2_GET(p + "norm.bias", dd, L.norm_bias); K2_GET(p + "norm.scale", 4, L.norm_scale);
-            K2_GET(p + "bypass.scale", dd, L.bypass); K2_GET(p + "bypass_mid.scale", dd, L.bypass_mid);
-        }
-        if (d.downsampling[s] > 1) {
-            K2_GET("S" + std::to_string(s) + ".ds.w", 8, k.ds_w[s]);
-            K2_GET("S" + std::to_string(s) + ".comb.scale", dd, k.comb_scale[s]);
-        }
-    }
-    K2_GET("out.ds.w", 8, k.out_ds_w);
-    const size_t J = d.joiner_dim, D = d.decoder_dim, V = d.vocab_size;
-    K2_GET("joint.enc.w", J * k.out_dim, ctx->jenc_w); K2_GET("joint.enc.b", J, ctx->jenc_b);
-    K2_GET("dec.embed", V * D, ctx->embed);
-    K2_GET("dec.conv.w", D * 4 * 2, ctx->k2_conv_w);
-    K2_GET("joint.pred.w", J * D, ctx->jpred_w); K2_GET("joint.pred.b", J, ctx->jpred_b);
-    K2_GET("joint.out.w", ((V + 15) / 16 * 16) * J, ctx->jout_w); K2_GET("joint.out.b", V, ctx->jout_b);
-    // optional: the screened joint's operands (all four or none), as for the other families
-    ctx->jout_w16 = nullptr; ctx->jout_wrm = ctx->jout_bpad = ctx->jout_wmax = nullptr;
-    if (ctx->tensors.count("joint.out.w16") || ctx->tensors.count("joint.out.wrm") || ctx->tensors.count("joint.out.bpad") || ctx->tensors.count("joint.out.wmax")) {
-        const size_t Vpad = (V + 15) / 16 * 16;
-        K2_GET("joint.out.w16", Vpad * J, ctx->jout_w16);
-        K2_GET("joint.out.wrm", V * J, ctx->jout_wrm);
-        K2_GET("joint.out.bpad", Vpad, ctx->jout_bpad);
-        K2_GET("joint.out.wmax", 4, ctx->jout_wmax);
-    }
-    // optional: the float32 parity mode's dense weights ("<name>.f32": all or none)
-    ctx->has_f32 = false;
-    k.stacks32.clear();
-    if (ctx->tensors.count("emb.out.w.f32")) {
-        K2_GET("emb.conv2.w.f32", (size_t)c3 * pad32(9 * c2), k.conv2_w32);
-        K2_GET("emb.cnx.pw1.w.f32", 3 * c3 * c3, k.cnx_pw1_w32); K2_GET("emb.cnx.pw2.w.f32", 3 * c3 * c3, k.cnx_pw2_w32);
-        K2_GET("emb.out.w.f32", (size_t)d0 * k.embed_freq * c3, k.emb_out_w32);
-        K2_GET("joint.enc.w.f32", J * k.out_dim, k.jenc_w32);
-        k.stacks32.assign(d.n_stacks, {});
-        for (int s = 0; s < d.n_stacks; ++s) {
-            const size_t dd = d.encoder_dim[s], H = d.num_heads[s], hid = 3 * dd / 4;
-            const size_t ff[3] = {(size_t)d.ff_dim[s] * 3 / 4, (size_t)d.ff_dim[s], (size_t)d.ff_dim[s] * 5 / 4};
-            k.stacks32[s].assign(d.num_layers[s], rs_k2_layer32{});
-            for (int j = 0; j < d.num_layers[s]; ++j) {
-                rs_k2_layer32& L = k.stacks32[s][j];
-                const std::string p = "S" + std::to_string(s) + ".L" + std::to_string(j) + ".";
-                K2_GET(p + "attw.in.w.f32", (2 * K2_QD + K2_PD) * H * dd, L.attw_in_w);
-                for (int a = 0; a < 2; ++a) {
-                    const std::string q = p + (a ? "sa2." : "sa1."), c = p + (a ? "cm2." : "cm1.");
-                    K2_GET(q + "in.w.f32", H * K2_VD * dd, L.sa_in_w[a]);
-                    K2_GET(q + "out.w.f32", dd * pad32((int)(H * K2_VD)), L.sa_out_w[a]);
-                    K2_GET(c + "in.w.f32", 2 * dd * dd, L.cm_in_w[a]); K2_GET(c + "in.b.f32", 2 * dd, L.cm_in_b[a]);
-                    K2_GET(c + "out.w.f32", dd * dd, L.cm_out_w[a]);
-                }
-                for (int f = 0; f < 3; ++f) {
-                    const std::string q = p + "ff" + std::to_string(f + 1) + ".";
-                    K2_GET(q + "in.w.f32", ff[f] * dd, L.ff_in_w[f]); K2_GET(q + "out.w.f32", dd * ff[f], L.ff_out_w[f]);
-                }
-                K2_GET(p + "na.in.w.f32", 3 * hid * dd, L.na_in_w);
-                K2_GET(p + "na.out.w.f32", dd * pad32((int)hid), L.na_out_w);
-            }
-        }
-        ctx->has_f32 = true;
-    }
-    // optional: the int8 mode's quantized Linears ("<name>.i8", ".i8.cs", ".i8.q": each Linear on its own)
-    k.has_i8 = false;
-    k.stacks8.clear();
-    k.emb_out8 = rs_k2_q8{};
-    k.jenc8 = rs_k2_q8{};
-    k.pos_enc = nullptr;
-    auto q8 = [&](const std::string& name, size_t N, size_t K, rs_k2_q8& q) -> int {
-        q = rs_k2_q8{};
-        if (!ctx->tensors.count(name + ".i8")) return RS_OK;
-        const int ldw = pad32((int)K);
-        if (int r = k2_get(ctx, name + ".i8", N * ldw, q.w); r != RS_OK) return r;
-        if (int r = k2_get(ctx, name + ".i8.cs", N, q.cs); r != RS_OK) return r;
-        if (int r = k2_get(ctx, name + ".i8.q", 4, q.wq); r != RS_OK) return r;
-        q.ldw = ldw;
-        k.has_i8 = true;
-        return RS_OK;
-    };
-#define K2_Q8(name, n, kk, field) do { rc = q8(name, (size_t)(n), (size_t)(kk), field); if (rc != RS_OK) return rc; } while (0)
-    K2_Q8("emb.out.w", d0, (size_t)k.embed_freq * c3, k.emb_out8);
-    K2_Q8("joint.enc.w", J, k.out_dim, k.jenc8);
-    k.stacks8.assign(d.n_stacks, {});
-    bool any_pos = false;
-    for (int s = 0; s < d.n_stacks; ++s) {
-        const size_t dd = d.encoder_dim[s], H = d.num_heads[s], hid = 3 * dd / 4;
-        const size_t ff[3] = {(size_t)d.ff_dim[s] * 3 / 4, (size_t)d.ff_dim[s], (size_t)d.ff_dim[s] * 5 / 4};
-        k.stacks8[s].assign(d.num_layers[s], rs_k2_layer8{});
-        for (int j = 0; j < d.num_layers[s]; ++j) {
-            rs_k2_layer8& L = k.stacks8[s][j];
-            const std::string p = "S" + std::to_string(s) + ".L" + std::to_string(j) + ".";
-            K2_Q8(p + "attw.in.w", (2 * K2_QD + K2_PD) * H, dd, L.attw_in);
-            K2_Q8(p + "attw.pos.w", H * K2_PD, d.pos_dim, L.pos);
-            any_pos = any_pos || L.pos.w;
+            k2_get_linear(r, p + "attw.in", (2 * K2_QD + K2_PD) * H, dd, K2_ALL, L.attw_in);
+            w.get(p + "attw.pos_proj", (size_t)(2 * k.pos_cap - 1) * H * K2_PD, L.pos_proj);
+            k2_get_linear(r, p + "attw.pos", H * K2_PD, d.pos_dim, K2_W8, L.pos);
+            L.pos.ld32 = d.pos_dim;          // (no float32 weights: its operand, the position encoding's own rows, is not padded)
+            any_pos = any_pos || L.pos.q.w;
             for (int a = 0; a < 2; ++a) {
                 const std::string q = p + (a ? "sa2." : "sa1."), c = p + (a ? "cm2." : "cm1.");
-                K2_Q8(q + "in.w", H * K2_VD, dd, L.sa_in[a]);
-                K2_Q8(q + "out.w", dd, H * K2_VD, L.sa_out[a]);
-                K2_Q8(c + "in.w", 2 * dd, dd, L.cm_in[a]);
-                K2_Q8(c + "out.w", dd, dd, L.cm_out[a]);
+                k2_get_linear(r, q + "in", H * K2_VD, dd, K2_ALL, L.sa_in[a]);
+                k2_get_linear(r, q + "out", dd, H * K2_VD, K2_ALL, L.sa_out[a]);
+                k2_get_linear(r, c + "in", 2 * dd, dd, K2_ALL | K2_B32, L.cm_in[a]);
+                w.get(c + "dw.w", kk * dd, L.cm_dw_w[a]); w.get(c + "dw.b", dd, L.cm_dw_b[a]);
+                k2_get_linear(r, c + "out", dd, dd, K2_ALL, L.cm_out[a]);
             }
             for (int f = 0; f < 3; ++f) {
                 const std::string q = p + "ff" + std::to_string(f + 1) + ".";
-                K2_Q8(q + "in.w", ff[f], dd, L.ff_in[f]);
-                K2_Q8(q + "out.w", dd, ff[f], L.ff_out[f]);
+                k2_get_linear(r, q + "in", ff[f], dd, K2_ALL, L.ff_in[f]);
+                k2_get_linear(r, q + "out", dd, ff[f], K2_ALL, L.ff_out[f]);
             }
-            K2_Q8(p + "na.in.w", 3 * hid, dd, L.na_in);
-            K2_Q8(p + "na.out.w", dd, hid, L.na_out);
+            k2_get_linear(r, p + "na.in", 3 * hid, dd, K2_ALL, L.na_in);
+            k2_get_linear(r, p + "na.out", dd, hid, K2_ALL, L.na_out);
+            w.get(p + "norm.bias", dd, L.norm_bias); w.get(p + "norm.scale", 4, L.norm_scale);
+            w.get(p + "bypass.scale", dd, L.bypass); w.get(p + "bypass_mid.scale", dd, L.bypass_mid);
+        }
+        if (d.downsampling[s] > 1) {
+            w.get("S" + std::to_string(s) + ".ds.w", 8, k.ds_w[s]);
+            w.get("S" + std::to_string(s) + ".comb.scale", dd, k.comb_scale[s]);
         }
     }
-    if (any_pos) K2_GET("pos.enc", (size_t)(2 * k.pos_cap - 1) * d.pos_dim, k.pos_enc);
-#undef K2_Q8
+    w.get("out.ds.w", 8, k.out_ds_w);
+    k2_get_linear(r, "joint.enc", J, k.out_dim, K2_W16, k.jenc);
+    w.get("dec.embed", V * D, ctx->embed);
+    w.get("dec.conv.w", D * 4 * 2, ctx->k2_conv_w);
+    w.get("joint.pred.w", J * D, ctx->jpred_w); w.get("joint.pred.b", J, ctx->jpred_b);
+    w.get("joint.out.w", ((V + 15) / 16 * 16) * J, ctx->jout_w); w.get("joint.out.b", V, ctx->jout_b);
+    if (!w.ok()) return w.fail(ctx);
+    ctx->jenc_w = k.jenc.w; ctx->jenc_b = k.jenc.b;
+    // optional: the screened joint's operands (all four or none), as for the other families
+    rs_get_screened_joint(ctx, w);
+    if (!w.ok()) return w.fail(ctx);
+    // optional: the float32 parity mode's dense weights ("<name>.f32": all or none)
+    ctx->has_f32 = false;
+    if (!r.w32.ok()) return r.w32.fail(ctx);
+    ctx->has_f32 = r.f32;
+    // optional: the int8 mode's quantized Linears ("<name>.i8", ".i8.cs", ".i8.q": each Linear on its own)
+    k.has_i8 = false;
+    if (any_pos) r.w8.get("pos.enc", (size_t)(2 * k.pos_cap - 1) * d.pos_dim, k.pos_enc);
+    if (!r.w8.ok()) return r.w8.fail(ctx);
+    k.has_i8 = r.any_i8;
     if (ctx->precision_f32 && !ctx->has_f32) ctx->precision_f32 = 0;
     ctx->has_i8 = k.has_i8;
     if (ctx->precision_i8 && !(ctx->has_f32 && k.has_i8)) ctx->precision_i8 = 0;
-#undef K2_GET
     ctx->decode_narrow = true;
     ctx->finalized = true;
     return RS_OK;
@@ -1576,13 +1539,14 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     const int c1 = d.embed_c1, c2 = d.embed_c2, c3 = d.embed_c3, T3 = pl.T3, F3 = pl.F3;
     int rc;
 #define RS_TRY(call) do { rc = (call); if (rc != RS_OK) return rc; } while (0)
-    // `copy`: the residual GEMM also stores its result rounded to bf16 (row pitch N) — the A operand of the branch that follows
-    auto gemm = [&](const uint16_t* A, int lda, const uint16_t* Wt, int K, void* out, int ldc, long long M, int N, int flags, const float* bias,
-                    const float* res, uint16_t* copy = nullptr) -> int {
+    // out [M][N] = epilogue(A [M][R.ld16] . R.w^T + R.b); `copy`: the residual GEMM also stores its result rounded to bf16 (row pitch N) —
+    // the A operand of the branch that follows; ldc: the output's row pitch where it is not N (the GLU halves the columns)
+    auto lin = [&](const rs_k2_linear& R, const uint16_t* A, void* out, long long M, int flags, const float* res = nullptr, uint16_t* copy = nullptr,
+                   int ldc = 0) -> int {
         rs_gemm_args g{};
-        g.A = A; g.lda = lda; g.W = Wt; g.ldw = K; g.out = out; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K;
-        g.flags = flags; g.bias = bias; g.alpha = 1.0f; g.residual = res;
-        g.out_bf16 = copy; g.ld_bf16 = N;
+        g.A = A; g.lda = R.ld16; g.W = R.w; g.ldw = R.ld16; g.out = out; g.ldc = ldc ? ldc : R.N; g.M = (int)M; g.N = R.N; g.K = R.ld16;
+        g.flags = flags; g.bias = R.b; g.alpha = 1.0f; g.residual = res;
+        g.out_bf16 = copy; g.ld_bf16 = R.N;
         return rs_launch_gemm(ctx, g, s);
     };
     const int RES = RS_GEMM_BIAS | RS_GEMM_RESIDUAL | RS_GEMM_OUT_F32;
@@ -1610,15 +1574,15 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
         // patches gathered into LDS, weights in registers: no patch matrix in HBM
         if (int rc2 = rs_ensure_dynamic_lds(ctx, (const void*)k2_conv2_fused_kernel, C2_LDS); rc2 != RS_OK) { rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s); return rc2; }
         const long long n_tiles = (rows3 + 127) / 128;
-        hipLaunchKernelGGL(k2_conv2_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), C2_LDS, s, a1, pl.T2, pl.F2, T3, F3, k.conv2_w,
-                           pl.Kp, k.conv2_b, a2, rows3);
+        hipLaunchKernelGGL(k2_conv2_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), C2_LDS, s, a1, pl.T2, pl.F2, T3, F3, k.conv2.w,
+                           k.conv2.ld16, k.conv2.b, a2, rows3);
         rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
         RS_CHECK_LAUNCH(ctx, "zipformer encoder_embed convs");
     } else {
-    hipLaunchKernelGGL(k2_im2col_kernel, dim3((unsigned)((rows3 + 3) / 4)), dim3(256), 0, s, a1, pl.T2, pl.F2, c2, T3, F3, pl.Kp, rows3, col);
+    hipLaunchKernelGGL(k2_im2col_kernel, dim3((unsigned)((rows3 + 3) / 4)), dim3(256), 0, s, a1, pl.T2, pl.F2, c2, T3, F3, k.conv2.ld16, rows3, col);
     rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
     RS_CHECK_LAUNCH(ctx, "zipformer encoder_embed convs");
-    RS_TRY(gemm(col, pl.Kp, k.conv2_w, pl.Kp, a2, c3, rows3, c3, RS_GEMM_BIAS | RS_GEMM_SWOOSHR | RS_GEMM_OUT_F32, k.conv2_b, nullptr));
+    RS_TRY(lin(k.conv2, col, a2, rows3, RS_GEMM_BIAS | RS_GEMM_SWOOSHR | RS_GEMM_OUT_F32));
     }
     rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
     hipLaunchKernelGGL(k2_cnx_dw_kernel<10>, dim3((T3 + CNX_TT - 1) / CNX_TT, B), dim3(256), 0, s, a2, lens3, T3, F3, c3, k.cnx_dw_w, k.cnx_dw_b, dwo);
@@ -1628,18 +1592,18 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
         // both pointwise convolutions in one launch, the hidden tensor stays on the CU; result (bf16) in place over dwo
         RS_TRY(rs_ensure_dynamic_lds(ctx, (const void*)k2_cnx_pw_fused_kernel, CX_LDS));
         const long long n_tiles = (rows3 + CX_ROWS - 1) / CX_ROWS;
-        hipLaunchKernelGGL(k2_cnx_pw_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), CX_LDS, s, dwo, k.cnx_pw1_w, k.cnx_pw1_b,
-                           k.cnx_pw2_w, k.cnx_pw2_b, a2, dwo, rows3);
+        hipLaunchKernelGGL(k2_cnx_pw_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), CX_LDS, s, dwo, k.cnx_pw1.w, k.cnx_pw1.b,
+                           k.cnx_pw2.w, k.cnx_pw2.b, a2, dwo, rows3);
         RS_CHECK_LAUNCH(ctx, "zipformer ConvNeXt pointwise pair");
     } else {
-    RS_TRY(gemm(dwo, c3, k.cnx_pw1_w, c3, hbuf, 3 * c3, rows3, 3 * c3, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, k.cnx_pw1_b, nullptr));
+    RS_TRY(lin(k.cnx_pw1, dwo, hbuf, rows3, RS_GEMM_BIAS | RS_GEMM_SWOOSHL));
     // (its bf16 copy lands in dwo, [B*T3][F3 * c3] in (f, c) order: the operand of `out`)
-    RS_TRY(gemm(hbuf, 3 * c3, k.cnx_pw2_w, 3 * c3, a2, c3, rows3, c3, RES, k.cnx_pw2_b, a2, dwo));
+    RS_TRY(lin(k.cnx_pw2, hbuf, a2, rows3, RES, a2, dwo));
     }
     const long long M3 = (long long)B * T3;
     const int d0 = d.encoder_dim[0];
     float* emb = x0;                       // encoder_embed's output; stack 0 reads it as `prev`
-    RS_TRY(gemm(dwo, F3 * c3, k.emb_out_w, F3 * c3, emb, d0, M3, d0, RS_GEMM_BIAS | RS_GEMM_OUT_F32, k.emb_out_b, nullptr));
+    RS_TRY(lin(k.emb_out, dwo, emb, M3, RS_GEMM_BIAS | RS_GEMM_OUT_F32));
     hipLaunchKernelGGL(k2_biasnorm_kernel, dim3((unsigned)((M3 + 3) / 4)), dim3(256), 0, s, emb, k.emb_norm_bias, k.emb_norm_scale, (const float*)nullptr,
                        (const float*)nullptr, (int)M3, d0, emb, (uint16_t*)nullptr);
     if (k.tap_embed) RS_HIP(ctx, hipMemcpyAsync(k.tap_embed, emb, (size_t)M3 * d0 * 4, hipMemcpyDeviceToDevice, s));
@@ -1668,7 +1632,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
             float* xs = nxt;
             if (j == 0) cast(cur, xb, n);           // later layers: the previous layer's BiasNorm wrote the bf16 copy
             // attention weights, shared by the three attention modules of the layer
-            RS_TRY(gemm(xb, dd, L.attw_in_w, dd, qkp, nin, M, nin, RS_GEMM_BIAS, L.attw_in_b, nullptr));
+            RS_TRY(lin(L.attw_in, xb, qkp, M, RS_GEMM_BIAS));
             {
                 const size_t lds = (size_t)(Ts + 64) * 16;
                 if (lds > 160 * 1024 - 1024) return rs_fail(ctx, RS_EINVAL, "zipformer: %d frames in stack %d exceed the attention kernel's position table in LDS", Ts, st);
@@ -1689,12 +1653,12 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
 #undef RS_K2_ATTW1
                 rs_prof_end(ctx, RS_PROF_ATTN, s);
             }
-            auto ffn = [&](int f, int width, const float* res, bool emit) -> int {
-                if (int r = gemm(xb, dd, L.ff_in_w[f], dd, big, width, M, width, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, L.ff_in_b[f], nullptr); r != RS_OK) return r;
-                return gemm(big, width, L.ff_out_w[f], width, xs, dd, M, dd, RES, L.ff_out_b[f], res, emit ? xb : nullptr);
+            auto ffn = [&](int f, const float* res, bool emit) -> int {
+                if (int r = lin(L.ff_in[f], xb, big, M, RS_GEMM_BIAS | RS_GEMM_SWOOSHL); r != RS_OK) return r;
+                return lin(L.ff_out[f], big, xs, M, RES, res, emit ? xb : nullptr);
             };
             auto self_attn = [&](int a) -> int {       // (the out projection always feeds another branch: it writes the bf16 copy)
-                if (int r = gemm(xb, dd, L.sa_in_w[a], dd, big, vw, M, vw, RS_GEMM_BIAS, L.sa_in_b[a], nullptr); r != RS_OK) return r;
+                if (int r = lin(L.sa_in[a], xb, big, M, RS_GEMM_BIAS); r != RS_OK) return r;
                 // `av` is shared by the three kinds of branch (row pitches vwp / hidp / dd): the columns that pad the out projection's
                 // K extent to a multiple of 64 are zeroed before every use
                 if (vwp != vw && hipMemsetAsync(av, 0, (size_t)M * vwp * 2, s) != hipSuccess) return rs_fail(ctx, RS_EHIP, "memset failed");
@@ -1703,29 +1667,29 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
                 hipLaunchKernelGGL((k2_vt_kernel<0>), dim3((Tp + 63) / 64, C / 64, B), dim3(256), 0, s, big, vw, vw, lens, Ts, Tp, C, vT);
                 hipLaunchKernelGGL((k2_pv_kernel<1, 0>), dim3((Ts + 127) / 128, 1, B * H), dim3(256), 0, s, W, H, Tp, vT, C, big, vw, 0, lens, Ts, av, vwp);
                 rs_prof_end(ctx, RS_PROF_ATTN, s);
-                return gemm(av, vwp, L.sa_out_w[a], vwp, xs, dd, M, dd, RES, L.sa_out_b[a], xs, xb);
+                return lin(L.sa_out[a], av, xs, M, RES, xs, xb);
             };
             auto conv_module = [&](int a) -> int {
-                if (int r = gemm(xb, dd, L.cm_in_w[a], dd, big, dd, M, 2 * dd, RS_GEMM_BIAS | RS_GEMM_GLU, L.cm_in_b[a], nullptr); r != RS_OK) return r;
+                if (int r = lin(L.cm_in[a], xb, big, M, RS_GEMM_BIAS | RS_GEMM_GLU, nullptr, nullptr, dd); r != RS_OK) return r;
                 if (int r = rs_launch_dwconv_act(ctx, big, L.cm_dw_w[a], L.cm_dw_b[a], lens, B, Ts, dd, kk, 1, av, s); r != RS_OK) return r;
-                return gemm(av, dd, L.cm_out_w[a], dd, xs, dd, M, dd, RES, L.cm_out_b[a], xs, xb);
+                return lin(L.cm_out[a], av, xs, M, RES, xs, xb);
             };
-            RS_TRY(ffn(0, d.ff_dim[st] * 3 / 4, cur, true));    // xs = cur + ff1(cur): the layer leaves `cur` and moves into `nxt`
+            RS_TRY(ffn(0, cur, true));    // xs = cur + ff1(cur): the layer leaves `cur` and moves into `nxt`
             // non-linear attention: head 0's weights over tanh-gated values, output gate, out projection
-            RS_TRY(gemm(xb, dd, L.na_in_w, dd, big, 3 * hid, M, 3 * hid, RS_GEMM_BIAS, L.na_in_b, nullptr));
+            RS_TRY(lin(L.na_in, xb, big, M, RS_GEMM_BIAS));
             if (hidp != hid) RS_HIP(ctx, hipMemsetAsync(av, 0, (size_t)M * hidp * 2, s));
             rs_prof_begin(ctx, RS_PROF_ATTN, s, (double)B * Ts * (double)Ts * 2.0 * hid, (double)B * Ts * (double)Tp * 2.0);
             hipLaunchKernelGGL((k2_vt_kernel<1>), dim3((Tp + 63) / 64, hidp / 64, B), dim3(256), 0, s, big, 3 * hid, hid, lens, Ts, Tp, hidp, vT);
             hipLaunchKernelGGL((k2_pv_kernel<4, 1>), dim3((Ts + 127) / 128, (hid + 63) / 64, B), dim3(256), 0, s, W, H, Tp, vT, hidp, big, 3 * hid, hid, lens, Ts, av, hidp);
             rs_prof_end(ctx, RS_PROF_ATTN, s);
-            RS_TRY(gemm(av, hidp, L.na_out_w, hidp, xs, dd, M, dd, RES, L.na_out_b, xs, xb));
+            RS_TRY(lin(L.na_out, av, xs, M, RES, xs, xb));
             RS_TRY(self_attn(0));
             RS_TRY(conv_module(0));
-            RS_TRY(ffn(1, d.ff_dim[st], xs, false));            // (bypass_mid rewrites x and its bf16 copy)
+            RS_TRY(ffn(1, xs, false));            // (bypass_mid rewrites x and its bf16 copy)
             hipLaunchKernelGGL(k2_bypass_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, xs, cur, L.bypass_mid, dd, n / 4, xb);
             RS_TRY(self_attn(1));
             RS_TRY(conv_module(1));
-            RS_TRY(ffn(2, d.ff_dim[st] * 5 / 4, xs, false));
+            RS_TRY(ffn(2, xs, false));
             float* dst = (last && ds == 1) ? stack_out : xs;
             hipLaunchKernelGGL(k2_biasnorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, xs, L.norm_bias, L.norm_scale, cur, L.bypass, (int)M, dd, dst,
                                last ? (uint16_t*)nullptr : xb);
@@ -1743,24 +1707,11 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
         d_prev = dd;
     }
     // ---- output: widest channels of every stack, down-sampling by 2, joiner.encoder_proj -----------------------------------------
-    K2Pieces pc{};
-    {
-        int n = 0, cur_dim = d.encoder_dim[d.n_stacks - 1];
-        pc.p[n] = pl.stackout[d.n_stacks - 1]; pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
-        for (int st = d.n_stacks - 2; st >= 0; --st) {
-            const int dd = d.encoder_dim[st];
-            if (dd > cur_dim) {
-                pc.p[n] = pl.stackout[st]; pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
-                cur_dim = dd;
-            }
-        }
-        pc.count = n;
-    }
+    const K2Pieces pc = k2_pieces(d, pl.stackout);
     const int To = pl.To;
     hipLaunchKernelGGL(k2_output_kernel, dim3(To, B), dim3(256), 0, s, pc, lens3, T3, To, k.out_dim, k.out_ds_w, enc_out, encb, enc_lens);
     RS_CHECK_LAUNCH(ctx, "zipformer output");
-    RS_TRY(gemm(encb, k.out_dim, ctx->jenc_w, k.out_dim, joint_enc, d.joiner_dim, (long long)B * To, d.joiner_dim, RS_GEMM_BIAS | RS_GEMM_OUT_F32, ctx->jenc_b,
-                nullptr));
+    RS_TRY(lin(k.jenc, encb, joint_enc, (long long)B * To, RS_GEMM_BIAS | RS_GEMM_OUT_F32));
 #undef RS_TRY
     return RS_OK;
 }
@@ -1783,20 +1734,18 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
     const int c1 = d.embed_c1, c2 = d.embed_c2, c3 = d.embed_c3, T3 = pl.T3, F3 = pl.F3;
     int rc;
 #define RS_TRY(call) do { rc = (call); if (rc != RS_OK) return rc; } while (0)
-    auto gemm = [&](const float* A, int lda, const float* Wt, int K, float* out, int ldc, long long M, int N, int flags, const float* bias,
-                    const float* res) -> int {
-        return rs_launch_gemm_f32(ctx, A, lda, Wt, K, out, ldc, (int)M, N, K, flags, bias, 1.0f, res, nullptr, 0, 0, s);
-    };
-    // int8 mode: a Linear with a registered "<name>.i8" runs as onnxruntime's quantized MatMul (k_int8.hip) with (sx, zx) taken per
-    // utterance over its own `lens[b]` rows of the `group` rows it has in A; K is the Linear's own width (A / weights may be padded)
+    // out [M][N] = epilogue(A [M][R.ld32] . W^T + R.b32).  W is R.w32 over the padded width — or, in the int8 mode for a Linear with a
+    // registered "<name>.i8", onnxruntime's quantized MatMul (k_int8.hip) over the Linear's own K with (sx, zx) taken per utterance
+    // over its own `lens[b]` rows of the `group` rows it has in A (the convolutions are never quantized and pass neither)
     const bool i8 = ctx->precision_i8 && k.has_i8;
     float* qp = i8 ? pl.qp : nullptr;
-    auto lin = [&](const rs_k2_q8& q, const float* A, int lda, const float* Wt, int Kp, int K, float* out, int ldc, long long M, int N, int flags,
-                   const float* bias, const float* res, const int32_t* lens, int group) -> int {
-        if (!i8 || !q.w) return gemm(A, lda, Wt, Kp, out, ldc, M, N, flags, bias, res);
+    auto lin = [&](const rs_k2_linear& R, const float* A, float* out, long long M, int flags, const float* res = nullptr, const int32_t* lens = nullptr,
+                   int group = 0) -> int {
+        const rs_k2_q8& q = R.q;
+        if (!i8 || !q.w) return rs_launch_gemm_f32(ctx, A, R.ld32, R.w32, R.ld32, out, R.N, (int)M, R.N, R.ld32, flags, R.b32, 1.0f, res, nullptr, 0, 0, s);
         if (M <= 0 || group <= 0) return RS_OK;
-        if (int r = rs_launch_i8_range(ctx, A, lda, lens, group, (int)(M / group), K, qp, s); r != RS_OK) return r;
-        return rs_launch_gemm_i8q(ctx, A, lda, group, qp, q.w, q.ldw, q.cs, q.wq, out, ldc, (int)M, N, K, flags, bias, res, s);
+        if (int r = rs_launch_i8_range(ctx, A, R.ld32, lens, group, (int)(M / group), R.K, qp, s); r != RS_OK) return r;
+        return rs_launch_gemm_i8q(ctx, A, R.ld32, group, qp, q.w, q.ldw, q.cs, q.wq, out, R.N, (int)M, R.N, R.K, flags, R.b32, res, s);
     };
     const int RES = RS_GEMM_BIAS | RS_GEMM_RESIDUAL;
     hipLaunchKernelGGL(k2_lens_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_frames, B, d.n_stacks, d.downsampling[0], d.downsampling[1],
@@ -1806,16 +1755,16 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
     if (rows3 > 0x7fffffffLL / 4) return rs_fail(ctx, RS_EINVAL, "zipformer (float32 mode): %lld patch rows exceed the float32 GEMM's row count", rows3);
     hipLaunchKernelGGL(k2f_conv0_kernel, dim3(pl.T1, B), dim3(256), 0, s, feats, t_max, pl.F, c1, k.conv0_w, k.conv0_b, a0);
     hipLaunchKernelGGL(k2f_conv1_kernel, dim3(pl.T2, B), dim3(256), 0, s, a0, pl.T1, pl.F, c1, pl.T2, pl.F2, c2, k.conv1_w, k.conv1_b, a1);
-    const int Kc = pad32(9 * c2);
+    const int Kc = k.conv2.ld32;
     hipLaunchKernelGGL(k2f_im2col_kernel, dim3((unsigned)((rows3 + 3) / 4)), dim3(256), 0, s, a1, pl.T2, pl.F2, c2, T3, F3, Kc, rows3, col);
     RS_CHECK_LAUNCH(ctx, "zipformer (float32 mode) encoder_embed convs");
-    RS_TRY(gemm(col, Kc, k.conv2_w32, Kc, a2, c3, rows3, c3, RS_GEMM_BIAS | RS_GEMM_SWOOSHR, k.conv2_b, nullptr));
+    RS_TRY(lin(k.conv2, col, a2, rows3, RS_GEMM_BIAS | RS_GEMM_SWOOSHR));
     hipLaunchKernelGGL(k2f_cnx_dw_kernel, dim3(T3, B), dim3(256), 0, s, a2, lens3, T3, F3, c3, k.cnx_dw_w, k.cnx_dw_b, dwo);
-    RS_TRY(gemm(dwo, c3, k.cnx_pw1_w32, c3, hbuf, 3 * c3, rows3, 3 * c3, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, k.cnx_pw1_b, nullptr));
-    RS_TRY(gemm(hbuf, 3 * c3, k.cnx_pw2_w32, 3 * c3, a2, c3, rows3, c3, RES, k.cnx_pw2_b, a2));
+    RS_TRY(lin(k.cnx_pw1, dwo, hbuf, rows3, RS_GEMM_BIAS | RS_GEMM_SWOOSHL));
+    RS_TRY(lin(k.cnx_pw2, hbuf, a2, rows3, RES, a2));
     const int d0 = d.encoder_dim[0];
     float* emb = x0;
-    RS_TRY(lin(k.emb_out8, a2, F3 * c3, k.emb_out_w32, F3 * c3, F3 * c3, emb, d0, M3, d0, RS_GEMM_BIAS, k.emb_out_b, nullptr, lens3, T3));
+    RS_TRY(lin(k.emb_out, a2, emb, M3, RS_GEMM_BIAS, nullptr, lens3, T3));
     hipLaunchKernelGGL(k2_biasnorm_kernel, dim3((unsigned)((M3 + 3) / 4)), dim3(256), 0, s, emb, k.emb_norm_bias, k.emb_norm_scale, (const float*)nullptr,
                        (const float*)nullptr, (int)M3, d0, emb, (uint16_t*)nullptr);
     if (k.tap_embed) RS_HIP(ctx, hipMemcpyAsync(k.tap_embed, emb, (size_t)M3 * d0 * 4, hipMemcpyDeviceToDevice, s));
@@ -1836,59 +1785,54 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
         hipLaunchKernelGGL(k2_stack_in_kernel, dim3(Ts, B), dim3(256), 0, s, prev, d_prev, lens3, T3, dd, ds, Ts, k.ds_w[st], ds == 1 ? (float*)nullptr : src, cur);
         for (int j = 0; j < d.num_layers[st]; ++j) {
             const rs_k2_layer& L = k.stacks[st][j];
-            const rs_k2_layer32& L32 = k.stacks32[st][j];
-            const rs_k2_layer8 L8 = i8 ? k.stacks8[st][j] : rs_k2_layer8{};
             const size_t n = (size_t)M * dd;
             const bool last = j == d.num_layers[st] - 1;
             float* xs = nxt;
             // attention weights from the layer's input
-            RS_TRY(lin(L8.attw_in, cur, dd, L32.attw_in_w, dd, dd, qkp, nin, M, nin, RS_GEMM_BIAS, L.attw_in_b, nullptr, lens, Ts));
-            if (L8.pos.w) {
+            RS_TRY(lin(L.attw_in, cur, qkp, M, RS_GEMM_BIAS, nullptr, lens, Ts));
+            if (i8 && L.pos.q.w) {
                 // linear_pos of each utterance's own 2 len - 1 position rows, with its own scale, into a table per utterance
                 const int G = 2 * Ts - 1, P = d.pos_dim;
                 float *pos_in = pl.pos_in, *pos_tab = pl.pos_tab;
                 int32_t* lens2 = pl.lens2;
                 hipLaunchKernelGGL(k2_pos_rows_kernel, dim3(G, B), dim3(64), 0, s, k.pos_enc, k.pos_cap, P, lens, Ts, pos_in, lens2);
                 RS_CHECK_LAUNCH(ctx, "zipformer (int8 mode) position rows");
-                RS_TRY(lin(L8.pos, pos_in, P, nullptr, P, P, pos_tab, H * K2_PD, (long long)B * G, H * K2_PD, 0, nullptr, nullptr, lens2, G));
+                RS_TRY(lin(L.pos, pos_in, pos_tab, (long long)B * G, 0, nullptr, lens2, G));
                 hipLaunchKernelGGL(k2f_attn_weights_kernel, dim3((Ts + 3) / 4, H, B), dim3(256), 0, s, qkp, nin, (const float*)pos_tab, k.pos_cap, H, lens, Ts,
                                    Tp, W, (long long)G * H * K2_PD);
             } else {
                 hipLaunchKernelGGL(k2f_attn_weights_kernel, dim3((Ts + 3) / 4, H, B), dim3(256), 0, s, qkp, nin, L.pos_proj, k.pos_cap, H, lens, Ts, Tp, W,
                                    0LL);
             }
-            auto ffn = [&](int f, int width, const float* in, const float* res) -> int {
-                if (int r = lin(L8.ff_in[f], in, dd, L32.ff_in_w[f], dd, dd, big, width, M, width, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, L.ff_in_b[f], nullptr, lens, Ts);
-                    r != RS_OK)
-                    return r;
-                return lin(L8.ff_out[f], big, width, L32.ff_out_w[f], width, width, xs, dd, M, dd, RES, L.ff_out_b[f], res, lens, Ts);
+            auto ffn = [&](int f, const float* in, const float* res) -> int {
+                if (int r = lin(L.ff_in[f], in, big, M, RS_GEMM_BIAS | RS_GEMM_SWOOSHL, nullptr, lens, Ts); r != RS_OK) return r;
+                return lin(L.ff_out[f], big, xs, M, RES, res, lens, Ts);
             };
             auto self_attn = [&](int a) -> int {
-                if (int r = lin(L8.sa_in[a], xs, dd, L32.sa_in_w[a], dd, dd, big, vw, M, vw, RS_GEMM_BIAS, L.sa_in_b[a], nullptr, lens, Ts); r != RS_OK) return r;
+                if (int r = lin(L.sa_in[a], xs, big, M, RS_GEMM_BIAS, nullptr, lens, Ts); r != RS_OK) return r;
                 if (vwp != vw && hipMemsetAsync(av, 0, (size_t)M * vwp * 4, s) != hipSuccess) return rs_fail(ctx, RS_EHIP, "memset failed");
                 hipLaunchKernelGGL(k2f_pv_kernel, dim3(Ts, B), dim3((vw + 63) / 64 * 64), 0, s, W, H, Tp, big, vw, lens, Ts, av, vwp);
-                return lin(L8.sa_out[a], av, vwp, L32.sa_out_w[a], vwp, vw, xs, dd, M, dd, RES, L.sa_out_b[a], xs, lens, Ts);
+                return lin(L.sa_out[a], av, xs, M, RES, xs, lens, Ts);
             };
             auto conv_module = [&](int a) -> int {
-                if (int r = lin(L8.cm_in[a], xs, dd, L32.cm_in_w[a], dd, dd, big, 2 * dd, M, 2 * dd, RS_GEMM_BIAS, L32.cm_in_b[a], nullptr, lens, Ts); r != RS_OK)
-                    return r;
+                if (int r = lin(L.cm_in[a], xs, big, M, RS_GEMM_BIAS, nullptr, lens, Ts); r != RS_OK) return r;
                 hipLaunchKernelGGL(k2f_glu_dwconv_swoosh_kernel, dim3((dd + 255) / 256, Ts, B), dim3(256), 0, s, big, L.cm_dw_w[a], L.cm_dw_b[a], lens, Ts, dd, kk, av);
-                return lin(L8.cm_out[a], av, dd, L32.cm_out_w[a], dd, dd, xs, dd, M, dd, RES, L.cm_out_b[a], xs, lens, Ts);
+                return lin(L.cm_out[a], av, xs, M, RES, xs, lens, Ts);
             };
-            RS_TRY(ffn(0, d.ff_dim[st] * 3 / 4, cur, cur));         // xs = cur + ff1(cur)
+            RS_TRY(ffn(0, cur, cur));         // xs = cur + ff1(cur)
             // non-linear attention
-            RS_TRY(lin(L8.na_in, xs, dd, L32.na_in_w, dd, dd, big, 3 * hid, M, 3 * hid, RS_GEMM_BIAS, L.na_in_b, nullptr, lens, Ts));
+            RS_TRY(lin(L.na_in, xs, big, M, RS_GEMM_BIAS, nullptr, lens, Ts));
             if (hidp != hid) RS_HIP(ctx, hipMemsetAsync(av, 0, (size_t)M * hidp * 4, s));
             hipLaunchKernelGGL(k2f_na_gate_kernel, dim3((unsigned)(((size_t)M * hid + 255) / 256)), dim3(256), 0, s, big, hid, (size_t)M, gate);
             hipLaunchKernelGGL(k2f_na_pv_kernel, dim3((hid + 255) / 256, (Ts + 3) / 4, B), dim3(256), 0, s, W, H, Tp, gate, big, hid, lens, Ts, av, hidp);
-            RS_TRY(lin(L8.na_out, av, hidp, L32.na_out_w, hidp, hid, xs, dd, M, dd, RES, L.na_out_b, xs, lens, Ts));
+            RS_TRY(lin(L.na_out, av, xs, M, RES, xs, lens, Ts));
             RS_TRY(self_attn(0));
             RS_TRY(conv_module(0));
-            RS_TRY(ffn(1, d.ff_dim[st], xs, xs));
+            RS_TRY(ffn(1, xs, xs));
             hipLaunchKernelGGL(k2_bypass_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, xs, cur, L.bypass_mid, dd, n / 4, (uint16_t*)nullptr);
             RS_TRY(self_attn(1));
             RS_TRY(conv_module(1));
-            RS_TRY(ffn(2, d.ff_dim[st] * 5 / 4, xs, xs));
+            RS_TRY(ffn(2, xs, xs));
             float* dst = (last && ds == 1) ? stack_out : xs;
             hipLaunchKernelGGL(k2_biasnorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, xs, L.norm_bias, L.norm_scale, cur, L.bypass, (int)M, dd, dst,
                                (uint16_t*)nullptr);
@@ -1904,23 +1848,10 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
         prev = stack_out;
         d_prev = dd;
     }
-    K2Pieces pc{};
-    {
-        int n = 0, cur_dim = d.encoder_dim[d.n_stacks - 1];
-        pc.p[n] = pl.stackout[d.n_stacks - 1]; pc.c0[n] = 0; pc.n[n] = cur_dim; pc.ld[n] = cur_dim; ++n;
-        for (int st = d.n_stacks - 2; st >= 0; --st) {
-            const int dd = d.encoder_dim[st];
-            if (dd > cur_dim) {
-                pc.p[n] = pl.stackout[st]; pc.c0[n] = cur_dim; pc.n[n] = dd - cur_dim; pc.ld[n] = dd; ++n;
-                cur_dim = dd;
-            }
-        }
-        pc.count = n;
-    }
+    const K2Pieces pc = k2_pieces(d, pl.stackout);
     hipLaunchKernelGGL(k2_output_kernel, dim3(pl.To, B), dim3(256), 0, s, pc, lens3, T3, pl.To, k.out_dim, k.out_ds_w, encf, (uint16_t*)nullptr, enc_lens);
     RS_CHECK_LAUNCH(ctx, "zipformer (float32 mode) output");
-    RS_TRY(lin(k.jenc8, encf, k.out_dim, k.jenc_w32, k.out_dim, k.out_dim, joint_enc, d.joiner_dim, (long long)B * pl.To, d.joiner_dim, RS_GEMM_BIAS, ctx->jenc_b,
-               nullptr, enc_lens, pl.To));
+    RS_TRY(lin(k.jenc, encf, joint_enc, (long long)B * pl.To, RS_GEMM_BIAS, nullptr, enc_lens, pl.To));
 #undef RS_TRY
     return RS_OK;
 }

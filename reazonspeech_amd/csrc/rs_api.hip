@@ -164,27 +164,15 @@ int rs_set_tensor(rs_ctx* ctx, const char* name, const void* dev_ptr, size_t nby
 
 }  // extern "C"
 
-namespace {
-
-struct Resolver {
-    rs_ctx* ctx;
-    int rc = RS_OK;
-    template <typename T>
-    void get(const std::string& name, size_t elems, const T*& out) {
-        if (rc != RS_OK) return;
-        auto it = ctx->tensors.find(name);
-        if (it == ctx->tensors.end()) { rc = rs_fail(ctx, RS_EMISSING, "weight tensor '%s' was not registered", name.c_str()); return; }
-        if (it->second.second != elems * sizeof(T)) {
-            rc = rs_fail(ctx, RS_EINVAL, "tensor '%s': expected %zu bytes, got %zu", name.c_str(), elems * sizeof(T),
-                         it->second.second);
-            return;
-        }
-        if ((uintptr_t)it->second.first & 15) { rc = rs_fail(ctx, RS_EINVAL, "tensor '%s' is not 16-byte aligned", name.c_str()); return; }
-        out = reinterpret_cast<const T*>(it->second.first);
-    }
-};
-
-}  // namespace
+void rs_get_screened_joint(rs_ctx* ctx, rs_weights& r) {
+    const size_t V = ctx->d.n_logits, J = ctx->d.joint_hidden, Vpad = (V + 15) / 16 * 16;
+    ctx->jout_w16 = nullptr; ctx->jout_wrm = ctx->jout_bpad = ctx->jout_wmax = nullptr;
+    if (!r.has("joint.out.w16") && !r.has("joint.out.wrm") && !r.has("joint.out.bpad") && !r.has("joint.out.wmax")) return;
+    r.get("joint.out.w16", Vpad * J, ctx->jout_w16);
+    r.get("joint.out.wrm", V * J, ctx->jout_wrm);
+    r.get("joint.out.bpad", Vpad, ctx->jout_bpad);
+    r.get("joint.out.wmax", 4, ctx->jout_wmax);
+}
 
 extern "C" {
 
@@ -193,7 +181,7 @@ int rs_finalize(rs_ctx* ctx) {
     if (ctx->avsr) return rs_avsr_finalize_impl(ctx);
     if (ctx->k2) return rs_k2_finalize_impl(ctx);
     const rs_dims& d = ctx->d;
-    Resolver r{ctx};
+    rs_weights r(ctx);
     const size_t C = d.sub_channels, dm = d.d_model, ff = d.ff_dim, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     r.get("fe.window", (size_t)d.win_length, ctx->fe_window);
     r.get("fe.twiddle", (size_t)512, ctx->fe_twiddle);
@@ -244,25 +232,16 @@ int rs_finalize(rs_ctx* ctx) {
     }
     r.get("joint.pred.w", J * H, ctx->jpred_w); r.get("joint.pred.b", J, ctx->jpred_b);
     r.get("joint.out.w", ((V + 15) / 16 * 16) * J, ctx->jout_w); r.get("joint.out.b", V, ctx->jout_b);   // fragment-major, rows padded to 16
-    if (r.rc != RS_OK) return r.rc;
+    if (!r.ok()) return r.fail(ctx);
     // optional: the screened joint's operands (bf16 [Vpad][J] row-major, f32 [V][J] row-major, bias padded with -3e38,
     // the largest row norm).  All four or none; without them the decode loop evaluates every column in exact f32.
     {
-        const size_t Vpad = (V + 15) / 16 * 16;
-        const bool any = ctx->tensors.count("joint.out.w16") || ctx->tensors.count("joint.out.wrm") ||
-                         ctx->tensors.count("joint.out.bpad") || ctx->tensors.count("joint.out.wmax");
-        ctx->jout_w16 = nullptr; ctx->jout_wrm = ctx->jout_bpad = ctx->jout_wmax = nullptr;
-        if (any) {
-            r.get("joint.out.w16", Vpad * J, ctx->jout_w16);
-            r.get("joint.out.wrm", V * J, ctx->jout_wrm);
-            r.get("joint.out.bpad", Vpad, ctx->jout_bpad);
-            r.get("joint.out.wmax", (size_t)4, ctx->jout_wmax);
-            if (r.rc != RS_OK) return r.rc;
-        }
+        rs_get_screened_joint(ctx, r);
+        if (!r.ok()) return r.fail(ctx);
         for (int l = 0; l < d.pred_layers; ++l) {
             const std::string nm = "pred.lstm" + std::to_string(l) + ".w4";
             ctx->lstm_w4[l] = nullptr;
-            if (ctx->tensors.count(nm)) { r.get(nm, 4 * H * 2 * H, ctx->lstm_w4[l]); if (r.rc != RS_OK) return r.rc; }
+            if (r.has(nm)) { r.get(nm, 4 * H * 2 * H, ctx->lstm_w4[l]); if (!r.ok()) return r.fail(ctx); }
         }
         // the environment's values of these rows are defaults: applied ONCE per context (rs_finalize runs again after every
         // rs_set_tensor, e.g. when the position tables grow; a value chosen with rs_set_option must survive that)
@@ -277,7 +256,7 @@ int rs_finalize(rs_ctx* ctx) {
     // optional: the float32 parity mode's dense weights ("<name>.f32", unrounded, the layouts of the bf16 tensors except
     // conv.pw1, which keeps NeMo's own row order) and its position table.  All or none.
     ctx->has_f32 = false;
-    if (ctx->tensors.count("sub.out.w.f32")) {
+    if (r.has("sub.out.w.f32")) {
         rs_f32_weights& w = ctx->f32;
         for (int s = 1; s < d.sub_stages && d.sub_kind == 0; ++s) r.get("sub.pw" + std::to_string(s) + ".w.f32", C * C, w.sub_pw_w[s - 1]);
         if (d.sub_kind == 1) r.get("sub.conv1.w.f32", C * 9 * C, w.sub_conv1_w);
@@ -295,7 +274,7 @@ int rs_finalize(rs_ctx* ctx) {
             r.get(p + "conv.pw2.w.f32", dm * dm, L.pw2_w);
         }
         r.get("joint.enc.w.f32", J * dm, w.jenc_w);
-        if (r.rc != RS_OK) return r.rc;
+        if (!r.ok()) return r.fail(ctx);
         auto pt = ctx->tensors.find("pos.table.f32");
         if (pt == ctx->tensors.end()) return rs_fail(ctx, RS_EMISSING, "weight tensor 'pos.table.f32' was not registered");
         const size_t rowf = dm * sizeof(float);

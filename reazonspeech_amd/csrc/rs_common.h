@@ -10,6 +10,7 @@
 #include "../../include/rs_asr.h"
 #include "rs_arena.h"
 #include "rs_knobs.h"
+#include "rs_tensors.h"
 
 // ----------------------------------------------------------------------------------------
 // device helpers
@@ -111,7 +112,7 @@ struct rs_ctx {
     int head_dim = 0, sub_freq = 0;
     bool finalized = false;
     std::string err;
-    std::unordered_map<std::string, std::pair<const void*, size_t>> tensors;
+    rs_tensor_table tensors;        // rs_set_tensor: name -> (pointer, bytes); read through rs_weights (below) by every rs_finalize
     // resolved weights
     const float *fe_window = nullptr, *fe_fb_w = nullptr, *fe_twiddle = nullptr;
     const int32_t* fe_fb_idx = nullptr;
@@ -177,6 +178,21 @@ struct rs_ctx {
 int rs_ensure_dynamic_lds(rs_ctx* ctx, const void* func, int bytes);
 
 int rs_fail(rs_ctx* ctx, int code, const char* fmt, ...);
+
+// The registered tensors as typed pointers (rs_tensors.h's sticky reader): the first failing get() is kept, every later one does
+// nothing and leaves its output alone; a finalize calls fail() where it needs the pointers to be good.
+struct rs_weights : rs_tensor_reader {
+    explicit rs_weights(const rs_ctx* ctx) : rs_tensor_reader(ctx->tensors) {}
+    template <typename T>
+    void get(const std::string& name, size_t elems, const T*& out) {
+        const void* p = out;
+        get_bytes(name, elems * sizeof(T), p);
+        out = static_cast<const T*>(p);
+    }
+    int fail(rs_ctx* ctx) const { return rs_fail(ctx, rc, "%s", msg.c_str()); }
+};
+// the screened joint's optional operands "joint.out.w16" / ".wrm" / ".bpad" / ".wmax" -> ctx->jout_*: all four or none (rs_api.hip)
+void rs_get_screened_joint(rs_ctx* ctx, rs_weights& r);
 // compute units of the context's device (256 when the query fails), cached in ctx->n_cus
 int rs_n_cus(rs_ctx* ctx);
 
