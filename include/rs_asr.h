@@ -578,6 +578,39 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
                          float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- token log-probabilities of a finished transducer search — added within ABI 7 ----------------
+ * gives what NeMo's Hypothesis.token_confidence (preserve_token_confidence, method max_prob), sherpa-onnx's per-token log-probs
+ * and ESPnet's scored hypotheses give: how sure the model was of every token it emitted.  A teacher-forced pass over the OUTPUT
+ * of any search of this header (rs_rnnt_greedy, rs_rnnt_alsd, rs_rnnt_beam, rs_rnnt_mbs / _hotwords); it runs after the search,
+ * shares none of its kernels' state and leaves ids / frames / n_ids as they are.  For token u of utterance b, emitted at frame t:
+ *     logp[b][u] = z[id] - logsumexp(z),   z = W_out . act(f[b][t] + g(y_<u)) + b_out
+ * with g(y_<u) the prediction network's output after the start context and the first u labels: the model's unmodified
+ * distribution (no blank penalty, no hotword bonus).  top1[b][u] = argmax_v z[v], the lowest index on ties, as the searches break
+ * them: for a greedy result top1 == ids; a beam search may have kept a token that was not the row's best.  Float32 in one order
+ * (the prediction network and logits of the searches, the log-sum-exp of oracle/rnnt_alsd.c), stated in csrc/k_rnnt_scores.hip
+ * and restated by tests/token_scores_checker.c, which the results equal bit for bit; a row's bits depend neither on the rest of
+ * the batch nor on the workspace given.
+ *
+ *   joint_enc, enc_lens, B, tp_max   what the search read
+ *   ids / frames i32[B][u_cap], n_ids i32[B]   what the search wrote (u_cap = its u_max / out_cap: the row pitch)
+ *   flags    RS_SCORES_FRAMES_ARE_STEPS: `frames` holds alignment steps (rs_rnnt_alsd: frame = step - index), converted on the
+ *            device; rs_rnnt_greedy, rs_rnnt_beam and rs_rnnt_mbs write frames: no flag
+ *   logp     f32[B][u_cap];  top1 i32[B][u_cap] or NULL.  Slots at u >= n_ids[b] are left untouched.
+ * Workspace: rs_rnnt_token_scores_workspace_bytes(ctx, B, u_cap) is the MINIMUM, separate from rs_workspace_bytes (0 for invalid
+ * arguments).  The (b, u) rows, compacted in (b, u) order, are scored in chunks: the minimum holds 32 rows per chunk, every
+ * further 32 rows cost 32 x 4 x (joint_hidden + 64 ceil(n_logits / 64)) bytes (+ the decoder rows of a Zipformer context), and a
+ * workspace that holds all B x u_cap rows makes one chunk.  Same bits whatever the chunk.
+ * Synchronises the stream internally (twice: the row count comes back first).  RS_EINVAL — before anything is enqueued — for an
+ * AV-HuBERT or unfinalised context, a negative size, an unknown flag, a null pointer or a workspace below the minimum.  The
+ * kernels check every frame against enc_lens (and tp_max), every id against n_logits and every count against u_cap before they
+ * index anything: a bad entry puts NaN (top1 -1) in its slot and the call returns RS_EINVAL after the sync; nothing is read or
+ * written out of range. */
+enum { RS_SCORES_FRAMES_ARE_STEPS = 1 };
+size_t rs_rnnt_token_scores_workspace_bytes(const rs_ctx* ctx, int B, int u_cap);
+int rs_rnnt_token_scores(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                         const int32_t* frames, const int32_t* n_ids, int u_cap, int flags, float* logp, int32_t* top1,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC segmentation of a batch (ESPnet family: time stamps of a recognised text) ------------------
  * Replaces: ctc_segmentation.ctc_segmentation(config, lpz, ground_truth_mat) of the third-party aligner the reference calls
  * once per window (pkg/espnet-asr/src/ctc.py:60-75), for the default CtcSegmentationParameters — the only ones the reference

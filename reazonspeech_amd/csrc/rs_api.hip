@@ -23,6 +23,10 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
                       float* scores, void* workspace, size_t workspace_bytes, hipStream_t s);
+size_t rs_rnnt_token_scores_workspace_bytes_impl(const rs_ctx* ctx, int B, int u_cap);
+int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                              const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
+                              void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_ctc_align_workspace_bytes_impl(int B, int tp_max, int c_max);
 int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
                       const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* ws, hipStream_t s);
@@ -831,6 +835,31 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
     }
     return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
                             out_cap, ids, frames, n_ids, scores, hw, hw ? graph_of : nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- token log-probabilities of a finished search (k_rnnt_scores.hip) ----
+static bool token_scores_ctx_ok(const rs_ctx* ctx) { return ctx && ctx->finalized && !ctx->avsr && ctx->embed && ctx->jout_w; }
+
+size_t rs_rnnt_token_scores_workspace_bytes(const rs_ctx* ctx, int B, int u_cap) {
+    if (!token_scores_ctx_ok(ctx) || B <= 0 || u_cap < 0) return 0;
+    return rs_rnnt_token_scores_workspace_bytes_impl(ctx, B, u_cap);
+}
+
+int rs_rnnt_token_scores(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                         const int32_t* frames, const int32_t* n_ids, int u_cap, int flags, float* logp, int32_t* top1, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (ctx->avsr) return rs_fail(ctx, RS_EINVAL, "token scores: defined for the transducer families; an AV-HuBERT context has no joint network");
+    if (!token_scores_ctx_ok(ctx)) return rs_fail(ctx, RS_EINVAL, "token scores: the context is not finalized");
+    if (B < 0 || tp_max < 0 || u_cap < 0) return rs_fail(ctx, RS_EINVAL, "token scores: negative size");
+    if (flags & ~RS_SCORES_FRAMES_ARE_STEPS) return rs_fail(ctx, RS_EINVAL, "token scores: unknown flag %d", flags);
+    if (B == 0 || u_cap == 0) return RS_OK;
+    if (!joint_enc || !enc_lens || !ids || !frames || !n_ids || !logp || !workspace) return rs_fail(ctx, RS_EINVAL, "token scores: null pointer");
+    if (workspace_bytes < rs_rnnt_token_scores_workspace_bytes_impl(ctx, B, u_cap))
+        return rs_fail(ctx, RS_EINVAL, "token scores: workspace %zu < %zu", workspace_bytes, rs_rnnt_token_scores_workspace_bytes_impl(ctx, B, u_cap));
+    if (tp_max == 0) return RS_OK;                         // no frames: no utterance has a token
+    return rs_rnnt_token_scores_impl(ctx, joint_enc, enc_lens, B, tp_max, ids, frames, n_ids, u_cap, (flags & RS_SCORES_FRAMES_ARE_STEPS) != 0,
+                                     logp, top1, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t rs_ctc_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int c_max, int S) {

@@ -5,7 +5,7 @@ subtitle writers, evaluation notebooks) keep working unchanged.  This family rep
 `transcribe()` produces one `Segment` per 30 s window with the window's bounds as its times (pkg/espnet-asr/src/transcribe.py:54-74).
 """
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -31,6 +31,31 @@ class TranscribeResult:
     """What `transcribe()` returns: the windows' texts concatenated, and the windows (interface.py:17-20)."""
     text: str
     segments: List[Segment] = field(default_factory=list)
+
+
+@dataclass
+class ScoredTranscribeResult(TranscribeResult):
+    """What `transcribe()` returns from a model loaded with `token_scores=True` (additive: a TranscribeResult with these fields
+    after the reference's).  `token_logprobs[i]` = log-probability of `token_ids[i]` under the model's own distribution at the
+    frame it was emitted (include/rs_asr.h rs_rnnt_token_scores); the pieces of a long recording are concatenated in order;
+    `confidence` = exp(mean(token_logprobs)), None without tokens."""
+    token_ids: List[int] = field(default_factory=list)
+    token_logprobs: List[float] = field(default_factory=list)
+    confidence: Optional[float] = None
+
+
+def mean_confidence(logprobs):
+    """exp(mean(logprobs)), None for an empty list"""
+    return float(np.exp(np.mean(np.asarray(logprobs, np.float64)))) if len(logprobs) else None
+
+
+def make_result(text, segments, scored=None):
+    """the plain result, or — `scored` = [(token ids, log-probabilities) per piece, in order] — the scored one"""
+    if scored is None:
+        return TranscribeResult(text, segments)
+    ids = [i for piece in scored for i in piece[0]]
+    lps = [v for piece in scored for v in piece[1]]
+    return ScoredTranscribeResult(text, segments, token_ids=ids, token_logprobs=lps, confidence=mean_confidence(lps))
 
 
 @dataclass

@@ -48,9 +48,18 @@ class _AsrModelView:
         return enc, torch.tensor([enc.shape[1]], dtype=torch.long)
 
 
+class _ScoredHypothesis:
+    """4th element of an n-best entry with `token_scores` on: the ids and the log-probability of each"""
+
+    def __init__(self, yseq, token_logprobs):
+        self.yseq, self.token_logprobs = list(yseq), list(token_logprobs)
+
+
 class EspnetModel:
     def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host",
-                 resample="host"):
+                 resample="host", token_scores=False):
+        """token_scores: the searches are followed by rs_rnnt_token_scores on the device; `recognize_batch_scored` and the 4th element
+        of `model(speech)`'s n-best entry carry the log-probability of every token.  Stored as `model.token_scores`."""
         assert cfg.espnet and len(token_list) == cfg.vocab_size
         self.segmentation = segmentation
         if beam_size is not None and int(beam_size) > 1:
@@ -58,7 +67,7 @@ class EspnetModel:
         self.beam_size = cfg.beam_size if cfg.decoding == "beam" else 1
         self.cfg = cfg
         self.token_list = list(token_list)
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision, resample=resample)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision, resample=resample, token_scores=token_scores)
         self.device = self.am.device
         self.dtype = "float32"
         self._last_enc = self._last_ctc = None
@@ -68,9 +77,11 @@ class EspnetModel:
     def __call__(self, speech):
         """Speech2Text.__call__: n-best list of (text, tokens, token ids, hypothesis); here nbest = 1 (upstream's default)"""
         wav = np.asarray(speech.detach().cpu().numpy() if isinstance(speech, torch.Tensor) else speech, dtype=np.float32).reshape(-1)
-        ids = self._search([wav]).ids[0]
+        res = self._search([wav])
+        ids = res.ids[0]
         tokens = [self.token_list[i] for i in ids]
-        return [(self.tokens2text(tokens), tokens, ids, None)]
+        hyp = _ScoredHypothesis(ids, res.token_logprobs[0]) if res.token_logprobs is not None else None
+        return [(self.tokens2text(tokens), tokens, ids, hyp)]
 
     # ---- direct forms -----------------------------------------------------------------------------------------------
     @staticmethod
@@ -86,6 +97,21 @@ class EspnetModel:
         `isolate_overflow`: see `_search`."""
         res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves], isolate_overflow=isolate_overflow)
         return [self.ids_to_text(ids) for ids in res.ids]
+
+    def recognize_batch_scored(self, waves, isolate_overflow=False):
+        """`recognize_batch` of a model with `token_scores` on -> ([text], [(token ids, log-probabilities)])"""
+        res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves], isolate_overflow=isolate_overflow)
+        if res.token_logprobs is None:
+            raise ValueError("recognize_batch_scored needs token_scores=True")
+        return [self.ids_to_text(ids) for ids in res.ids], list(zip(res.ids, res.token_logprobs))
+
+    @property
+    def token_scores(self):
+        return self.am.token_scores
+
+    @token_scores.setter
+    def token_scores(self, value):
+        self.am.token_scores = bool(value)
 
     def _search(self, waves, max_batch=256, isolate_overflow=False):
         """the transducer search over a batch of (padded) windows.  Upstream's default beam search has no bound on the
@@ -105,7 +131,7 @@ class EspnetModel:
         if am.cfg.decoding != "beam":
             return am.transcribe_waveforms(waves)
         bound = am.cfg.beam_max_pops or 16 * am.cfg.beam_size
-        out = DecodedBatch([], [], [], [], [])
+        out = DecodedBatch([], [], [], [], [], [] if am.token_scores else None)
         for lo in range(0, len(waves), max_batch):
             buf = am.stage([np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]])
             with torch.cuda.device(am.device):
@@ -125,6 +151,8 @@ class EspnetModel:
                         one = self._search([w], max_batch=1)
                         out.ids += one.ids; out.frames += one.frames; out.enc_lens += one.enc_lens
                         out.scores += one.scores; out.degraded += one.degraded
+                        if out.token_logprobs is not None:
+                            out.token_logprobs += one.token_logprobs
                     continue
                 if used is None:
                     import warnings
@@ -132,10 +160,13 @@ class EspnetModel:
                                   "is decoded with the greedy search instead", RuntimeWarning, stacklevel=3)
                     am.decode(am.ctx, buf, buf.ws, stream, decoding="greedy_batch")
                     used = "greedy_batch"
+                am.score(am.ctx, buf, stream, decoding=used)
                 res = am.collect(buf, decoding=used)
             out.ids += res.ids; out.frames += res.frames; out.enc_lens += res.enc_lens
             out.scores += res.scores if res.scores is not None else [float("nan")] * buf.B
             out.degraded += [used != "beam"] * buf.B
+            if out.token_logprobs is not None:
+                out.token_logprobs += res.token_logprobs
         return out
 
     # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option

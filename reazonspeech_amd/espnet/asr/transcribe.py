@@ -11,7 +11,7 @@ import torch
 
 from ...runtime.resample import norm_batch
 from .audio import norm_audio, SAMPLERATE
-from .interface import AudioData, TranscribeConfig, TranscribeResult, Segment
+from .interface import AudioData, TranscribeConfig, TranscribeResult, Segment, make_result
 from .ctc import split_text, find_blank, segments_from_timings
 
 # Hyper parameters (transcribe.py:9-10)
@@ -23,7 +23,7 @@ CHECKPOINT_ENV = "REAZONSPEECH_ESPNET_CHECKPOINT"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False,
-               segmentation="host", resample="host"):
+               segmentation="host", resample="host", token_scores=False):
     """Load the ReazonSpeech ESPnet model onto a ROCm GPU (transcribe.py:12-32).
 
     Args:
@@ -50,6 +50,11 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count) group of a call
         (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`.
 
+      token_scores (bool): every result is a `ScoredTranscribeResult` (interface.py): token ids, the log-probability of each under
+        the model's own distribution (computed on the device right after the search, rs_rnnt_token_scores) and
+        confidence = exp(mean); the pieces of a long recording are concatenated in order.  Valid with every `precision` and
+        `beam_size`.  Off (default): today's objects.  Stored as `model.token_scores`, may be changed later.
+
     The reference downloads `reazon-research/reazonspeech-espnet-v2` through espnet_model_zoo (:27-31), which an offline box
     cannot do: give `checkpoint=` / the environment variable.  Without a checkpoint this RAISES; seeded synthetic weights of
     the architecture (timings valid, transcripts meaningless) are loaded only on request — `config=`, `synthetic=True` or
@@ -73,7 +78,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
             raise FileNotFoundError(f"checkpoint {checkpoint!r} does not exist")
         cfg, sd, tokens = read_espnet(checkpoint)
         return EspnetModel(cfg, sd, tokens, device=device, beam_size=20 if beam_size is None else beam_size, max_pops=max_pops,
-                           precision=precision, segmentation=segmentation, resample=resample)
+                           precision=precision, segmentation=segmentation, resample=resample, token_scores=token_scores)
     cfg = config or ESPNET_CONFORMER_120M
     if config is None:
         if not (synthetic or os.environ.get("REAZONSPEECH_AMD_SYNTHETIC", "0") not in ("", "0")):
@@ -84,7 +89,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
               "(`synthetic=True` / $REAZONSPEECH_AMD_SYNTHETIC): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
     return EspnetModel(cfg, synthetic_state_dict_espnet(cfg, seed), synthetic_token_list(cfg.vocab_size, seed), device=device,
                        beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision,
-                       segmentation=segmentation, resample=resample)
+                       segmentation=segmentation, resample=resample, token_scores=token_scores)
 
 
 def _windows(model, waveform, window):
@@ -158,15 +163,19 @@ def transcribe(model, audio, config=None):
     rate = audio.samplerate
     total = len(audio.waveform)
     texts, segments = [], []
+    scored = [] if getattr(model, "token_scores", False) else None
     for offset, samples in _windows(model, audio.waveform, int(WINDOW_SECONDS * rate)):
-        text = model(np.pad(samples, PADDING, mode="constant"))[0][0]        # nbest[0] = (text, tokens, ids, hypothesis)
+        best = model(np.pad(samples, PADDING, mode="constant"))[0]           # nbest[0] = (text, tokens, ids, hypothesis)
+        text = best[0]
         texts.append(text)
+        if scored is not None:
+            scored.append((best[3].yseq, best[3].token_logprobs))
         segments.extend(Segment(start_seconds=(offset + first) / rate, end_seconds=(offset + last) / rate, text=piece)
                         for first, last, piece in split_text(model, samples, text))
         if config.verbose:       # the reference draws a tqdm bar over the samples (transcribe.py:55-56,79-80)
             done = offset + len(samples)
             print(f"\rTranscribe: {done}/{total}", end="" if done < total else "\n", file=sys.stderr, flush=True)
-    return TranscribeResult("".join(texts), segments)
+    return make_result("".join(texts), segments, scored)
 
 
 def transcribe_batch(model, audios, config=None):
@@ -188,11 +197,15 @@ def transcribe_batch(model, audios, config=None):
         return _transcribe_pooled(model, norm, window)
     short = [i for i, a in enumerate(norm) if len(a.waveform) <= window]
     out = [None] * len(norm)
-    texts = model.recognize_batch([norm[i].waveform for i in short]) if short else []
+    with_scores = getattr(model, "token_scores", False)
+    if with_scores and short:
+        texts, scored = model.recognize_batch_scored([norm[i].waveform for i in short])
+    else:
+        texts, scored = (model.recognize_batch([norm[i].waveform for i in short]) if short else []), None
     pieces = [split_text(model, norm[i].waveform, asr) for i, asr in zip(short, texts)]
-    for i, asr, segments in zip(short, texts, pieces):
+    for k, (i, asr, segments) in enumerate(zip(short, texts, pieces)):
         segs = [Segment(start / 16000, end / 16000, text) for start, end, text in segments]
-        out[i] = TranscribeResult(asr, segs)
+        out[i] = make_result(asr, segs, [scored[k]] if scored is not None else None)
     for i, a in enumerate(norm):
         if out[i] is None:
             out[i] = transcribe(model, a, TranscribeConfig(verbose=False))
@@ -209,8 +222,15 @@ def _transcribe_pooled(model, norm, window):
     order = sorted(range(len(pool)), key=lambda k: (-pool[k][2], k))
     samples = [waves[pool[k][0]][pool[k][1]:pool[k][1] + pool[k][2]] for k in order]
     texts, timings = [None] * len(pool), [None] * len(pool)
+    scored = [None] * len(pool) if getattr(model, "token_scores", False) else None
     if pool:
-        for k, text in zip(order, model.recognize_batch(samples, isolate_overflow=True)):
+        if scored is not None:
+            recognised, piece_scores = model.recognize_batch_scored(samples, isolate_overflow=True)
+            for k, sc in zip(order, piece_scores):
+                scored[k] = sc
+        else:
+            recognised = model.recognize_batch(samples, isolate_overflow=True)
+        for k, text in zip(order, recognised):
             texts[k] = text
         for k, t in zip(order, model.align_batch(samples, [texts[k] for k in order])):
             timings[k] = t
@@ -218,10 +238,11 @@ def _transcribe_pooled(model, norm, window):
     for a, pieces in zip(norm, plan):
         rate = a.samplerate
         joined, segments = [], []
+        first_piece = k
         for offset, n in pieces:
             joined.append(texts[k])
             segments.extend(Segment(start_seconds=(offset + first) / rate, end_seconds=(offset + last) / rate, text=piece)
                             for first, last, piece in segments_from_timings(timings[k], n, texts[k]))
             k += 1
-        out.append(TranscribeResult("".join(joined), segments))
+        out.append(make_result("".join(joined), segments, scored[first_piece:k] if scored is not None else None))
     return out

@@ -58,7 +58,7 @@ def resolve_checkpoint(language, precision, checkpoint=None):
 
 def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
                decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host", hotwords_file="",
-               hotwords_score=1.5, hotwords=None):
+               hotwords_score=1.5, hotwords=None, token_scores=False):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -118,7 +118,7 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     if hotwords_file and not os.path.isfile(hotwords_file):
         raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
     search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample,
-                  hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords)
+                  hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords, token_scores=token_scores)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):

@@ -6,7 +6,7 @@ package there are no segments and no token ids: the sherpa-onnx result the refer
 time stamp per token (pkg/k2-asr/src/transcribe.py:41-45).
 """
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -32,6 +32,23 @@ class TranscribeResult:
     """What `transcribe()` returns: the text (tokens joined) and the tokens with their times (interface.py:16-19)."""
     text: str
     subwords: List[Subword] = field(default_factory=list)
+
+
+@dataclass
+class ScoredTranscribeResult(TranscribeResult):
+    """What `transcribe()` returns from a model loaded with `token_scores=True` (additive: a TranscribeResult with these fields
+    after the reference's).  `token_logprobs[i]` = log-probability of `token_ids[i]` under the model's own distribution at the
+    frame it was emitted — no blank penalty, no hotword bonus (include/rs_asr.h rs_rnnt_token_scores); `subword_logprobs` is
+    aligned with `subwords` (here one subword per token); `confidence` = exp(mean(token_logprobs)), None without tokens."""
+    token_ids: List[int] = field(default_factory=list)
+    token_logprobs: List[float] = field(default_factory=list)
+    confidence: Optional[float] = None
+    subword_logprobs: List[float] = field(default_factory=list)
+
+
+def mean_confidence(logprobs):
+    """exp(mean(logprobs)), None for an empty list"""
+    return float(np.exp(np.mean(np.asarray(logprobs, np.float64)))) if len(logprobs) else None
 
 
 @dataclass

@@ -19,8 +19,11 @@ _BYTE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
 
 
 class _Result:
-    def __init__(self, tokens, timestamps, text):
+    def __init__(self, tokens, timestamps, text, token_ids=None, token_log_probs=None):
         self.tokens, self.timestamps, self.text = tokens, timestamps, text
+        # token_scores: the ids behind `tokens` and the log-probability of each ([UPSTREAM] sherpa-onnx keeps per-token log-probs in
+        # its hypotheses); None with the option off
+        self.token_ids, self.token_log_probs = token_ids, token_log_probs
 
 
 class _Stream:
@@ -97,8 +100,11 @@ def stream_graphs(model_graph, streams):
 class K2Model:
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
                  decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host",
-                 hotwords_file="", hotwords_score=1.5, hotwords=None):
-        """hotwords_file / hotwords_score: sherpa-onnx's keywords and defaults (contextual biasing of the modified beam search:
+                 hotwords_file="", hotwords_score=1.5, hotwords=None, token_scores=False):
+        """token_scores: `stream.result.token_log_probs` (and `.token_ids`) are filled: the log-probability of every token under the
+        model's own distribution (no blank penalty, no hotword bonus), computed on the device right after the search
+        (rs_rnnt_token_scores); valid with every precision and decoding method.  Stored as `model.token_scores`, may be changed later.
+        hotwords_file / hotwords_score: sherpa-onnx's keywords and defaults (contextual biasing of the modified beam search:
         runtime/k2_hotwords.py for the file format, include/rs_asr.h rs_rnnt_mbs_hotwords for what a hotword does); `hotwords` = the
         same as an in-memory list (strings "phrase" / "phrase :2.0", or token-id sequences).  The model's graph is built and
         uploaded once here; with greedy_search they raise ValueError.
@@ -122,7 +128,7 @@ class K2Model:
         self.hotwords = self.hotword_graph(hotwords, hotwords_file)       # the model's graph (None = no hotwords)
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded
         cap = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, **cap)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, token_scores=token_scores, **cap)
         self.device = self.am.device
         if self.hotwords is not None:
             self.am.hotword_set((self.hotwords,))         # checked and uploaded once, at load
@@ -150,6 +156,14 @@ class K2Model:
     def resample_batch(self, waveforms, rates):
         return self.am.resample_batch(waveforms, rates)
 
+    @property
+    def token_scores(self):
+        return self.am.token_scores
+
+    @token_scores.setter
+    def token_scores(self, value):
+        self.am.token_scores = bool(value)
+
     # ---- sherpa-onnx's surface ------------------------------------------------------------------------------------------
     def create_stream(self, hotwords=None):
         """hotwords: sherpa-onnx's per-stream hotwords — a string of phrases separated by `/` (or a list), each with an optional
@@ -164,8 +178,8 @@ class K2Model:
             if st.sample_rate != self.cfg.sample_rate:
                 raise ValueError(f"sample rate {st.sample_rate}: the model expects {self.cfg.sample_rate} Hz (sherpa-onnx resamples; resample with norm_audio first)")
         res = self.am.transcribe_waveforms([st.samples for st in streams], hotwords=stream_graphs(self.hotwords, streams))
-        for st, ids, frames in zip(streams, res.ids, res.frames):
-            st.result = self.convert(ids, frames)
+        for k, (st, ids, frames) in enumerate(zip(streams, res.ids, res.frames)):
+            st.result = self.convert(ids, frames, res.token_logprobs[k] if res.token_logprobs is not None else None)
 
     # ---- result conversion ------------------------------------------------------------------------------------------------
     def symbol(self, i):
@@ -173,7 +187,7 @@ class K2Model:
         s = self.tokens[i]
         return " " + s[1:] if s.startswith("▁") else s
 
-    def convert(self, ids, frames):
+    def convert(self, ids, frames, logprobs=None):
         syms = [self.symbol(i) for i in ids]
         # byte-fallback pieces (<0xE3> ...) join into UTF-8 text; the token list keeps them as they are
         out, pending = [], bytearray()
@@ -189,4 +203,5 @@ class K2Model:
         if pending:
             out.append(pending.decode("utf-8", errors="replace"))
         step = self.cfg.seconds_per_frame()
-        return _Result(syms, [float(np.float32(step * t)) for t in frames], "".join(out))
+        scored = {} if logprobs is None else dict(token_ids=list(ids), token_log_probs=list(logprobs))
+        return _Result(syms, [float(np.float32(step * t)) for t in frames], "".join(out), **scored)

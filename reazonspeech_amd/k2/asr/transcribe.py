@@ -3,7 +3,7 @@ silence on both sides, warn above TOO_LONG_SECONDS, decode one stream, pair toke
 import warnings
 
 from ...runtime.resample import norm_batch
-from .interface import AudioData, TranscribeConfig, TranscribeResult, Subword
+from .interface import AudioData, TranscribeConfig, TranscribeResult, ScoredTranscribeResult, Subword, mean_confidence
 from .audio import pad_audio, norm_audio, SAMPLERATE
 
 PAD_SECONDS = 0.9
@@ -35,6 +35,10 @@ def _pad_and_warn(audio):
 
 def _result(stream):
     subwords = [Subword(token=t, seconds=s) for t, s in zip(stream.result.tokens, stream.result.timestamps)]
+    lp = getattr(stream.result, "token_log_probs", None)
+    if lp is not None:                   # a model loaded with token_scores=True
+        return ScoredTranscribeResult(stream.result.text, subwords, token_ids=list(stream.result.token_ids), token_logprobs=list(lp),
+                                      confidence=mean_confidence(lp), subword_logprobs=list(lp))
     return TranscribeResult(stream.result.text, subwords)
 
 

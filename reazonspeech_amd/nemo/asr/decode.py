@@ -7,7 +7,7 @@ checks it against golden vectors produced by importing the reference file itself
 """
 import weakref
 
-from .interface import Subword, Segment, TranscribeResult
+from .interface import Subword, Segment, TranscribeResult, ScoredTranscribeResult, mean_confidence
 
 # decode.py:4-7
 PAD_SECONDS = 0.5
@@ -62,24 +62,29 @@ def _piece_text(tokenizer):
     return get
 
 
-def decode_hypothesis(model, hyp):
+def decode_hypothesis(model, hyp, token_logprobs=None):
     """Build a TranscribeResult from an ALSD-shaped hypothesis (decode.py:28-66).
 
-    `model` only has to provide `.tokenizer.ids_to_text(list[int]) -> str`.
+    `model` only has to provide `.tokenizer.ids_to_text(list[int]) -> str`.  `token_logprobs` (one per label of the hypothesis,
+    None = the reference's plain result): a ScoredTranscribeResult with the log-probabilities carried through the same indexing.
     """
     ids = hyp.y_sequence.tolist()[1:]          # decode.py:40 — drop the leading blank
     text = model.tokenizer.ids_to_text(ids)     # decode.py:41
 
     piece = _piece_text(model.tokenizer)
     subwords = []
+    subword_logprobs = []
     for idx, (token_id, step) in enumerate(zip(ids, hyp.timestamp)):
         token = piece(token_id)
         if not token:
             continue                            # bare U+2581 pieces decode to "" and are dropped AFTER idx was assigned (decode.py:53)
         seconds = max(SECONDS_PER_STEP * (step - idx - 1) - PAD_SECONDS, 0)   # decode.py:48
         subwords.append(Subword(seconds, token_id, token))
+        if token_logprobs is not None:
+            subword_logprobs.append(token_logprobs[idx])
 
     segments = []
+    segment_confidence = []
     start = 0
     while start < len(subwords):
         end = find_end_of_segment(subwords, start)
@@ -88,6 +93,13 @@ def decode_hypothesis(model, hyp):
             end_seconds=subwords[end].seconds + SECONDS_PER_STEP,   # decode.py:61
             text="".join(sw.token for sw in subwords[start:end + 1]),
         ))
+        if token_logprobs is not None:
+            segment_confidence.append(mean_confidence(subword_logprobs[start:end + 1]))
         start = end + 1
 
+    if token_logprobs is not None:
+        assert len(token_logprobs) == len(ids)
+        return ScoredTranscribeResult(text, subwords, segments, token_ids=list(ids), token_logprobs=list(token_logprobs),
+                                      confidence=mean_confidence(token_logprobs), subword_logprobs=subword_logprobs,
+                                      segment_confidence=segment_confidence)
     return TranscribeResult(text, subwords, segments)

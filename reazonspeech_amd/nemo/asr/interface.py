@@ -47,6 +47,25 @@ class TranscribeResult:
 
 
 @dataclass
+class ScoredTranscribeResult(TranscribeResult):
+    """What `transcribe()` returns from a model loaded with `token_scores=True` (additive: a TranscribeResult with these fields
+    after the reference's).  `token_logprobs[i]` = log-probability of `token_ids[i]` under the model's own distribution at the
+    frame it was emitted (include/rs_asr.h rs_rnnt_token_scores); `subword_logprobs` is aligned with `subwords` (pieces that
+    decode to "" are dropped from both, so it can be shorter than `token_logprobs`); `segment_confidence[k]` = exp(mean of the
+    log-probabilities of the subwords of `segments[k]`); `confidence` = exp(mean(token_logprobs)), None without tokens."""
+    token_ids: List[int] = field(default_factory=list)
+    token_logprobs: List[float] = field(default_factory=list)
+    confidence: Optional[float] = None
+    subword_logprobs: List[float] = field(default_factory=list)
+    segment_confidence: List[float] = field(default_factory=list)
+
+
+def mean_confidence(logprobs):
+    """exp(mean(logprobs)), None for an empty list"""
+    return float(np.exp(np.mean(np.asarray(logprobs, np.float64)))) if len(logprobs) else None
+
+
+@dataclass
 class TranscribeConfig:
     """Per-call options (interface.py:33-36)."""
     verbose: bool = True
@@ -91,6 +110,7 @@ class Hypothesis:
     timestamp: List[int]
     frames: List[int] = field(default_factory=list)
     score: Optional[float] = None
+    token_confidence: Optional[List[float]] = None      # token_scores: exp(log-probability) per label ([UPSTREAM] NeMo preserve_token_confidence, method max_prob)
 
     @classmethod
     def from_greedy(cls, ids, frames, blank_id):

@@ -60,7 +60,7 @@ SYNTHETIC_ENV = "REAZONSPEECH_AMD_SYNTHETIC"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, decoding=None, beam_size=None,
-               precision="bf16", synthetic=False, resample="host"):
+               precision="bf16", synthetic=False, resample="host", token_scores=False):
     """Load the ReazonSpeech FastConformer-RNNT model onto a ROCm GPU.
 
     Args:
@@ -90,6 +90,11 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         "device" = one HIP launch per (rate, channel count) group of a `transcribe_batch` call (`AsrModel.resample_batch`,
         rs_resample) with the host path's Kaiser filter — float32 rounding apart from the host path's result without soxr.
         Stored as `model.resample`, may be changed later.  Anything else raises ValueError.
+      token_scores (bool): every result is a `ScoredTranscribeResult` (interface.py): the log-probability of every emitted token
+        under the model's own distribution, per subword, and confidences per segment and utterance (exp of the mean) — computed on
+        the device right after the search (rs_rnnt_token_scores), valid with every `precision` and `decoding`; with
+        `raw_hypothesis`, `Hypothesis.token_confidence` = exp(log-probability) like NeMo's `max_prob` method.  Off (default):
+        today's objects.  Stored as `model.token_scores`, may be changed later.
       pos_cap (int): encoder frames (80 ms each) the resident relative-position tables cover at load time
         (default 1024, about 82 s); longer utterances grow the tables on first use.
 
@@ -136,7 +141,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         cfg = cfg.with_(beam_size=int(beam_size))
     cfg.validate()
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-    return AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, **kw)
+    return AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, **kw)
 
 
 def transcribe_batch(model, audios, config=None, distributed=False):
@@ -173,11 +178,17 @@ def transcribe_batch(model, audios, config=None, distributed=False):
                 hyp.score = decoded.scores[k]
             else:
                 hyp = Hypothesis.from_greedy(ids, frames, model.cfg.blank_id)
-            ret = decode_hypothesis(model, hyp)
+            lp = decoded.token_logprobs[k] if decoded.token_logprobs is not None else None
+            if lp is not None:
+                hyp.token_confidence = [float(np.exp(v)) for v in lp]
+            ret = decode_hypothesis(model, hyp, lp)
             if config.raw_hypothesis:
                 ret.hypothesis = hyp
             results[i] = ret
 
+    if distributed and getattr(model, "token_scores", False):
+        raise ValueError("token_scores is on: the distributed path does not gather token log-probabilities (transcribe_batch(distributed=False) "
+                         "on each rank, or load the model without token_scores)")
     if distributed:
         to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves))
     else:

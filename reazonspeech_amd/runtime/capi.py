@@ -22,6 +22,7 @@ GEMM_SWOOSHL, GEMM_SWOOSHR, GEMM_GELU = 128, 256, 512
 GLU_HALVES, GLU_BLOCK32, GLU_APPLIED = 0, 1, 2
 ALSD_SCORE_NORM, ALSD_MERGE = 1, 2
 MBS_LENGTH_NORM = 1
+SCORES_FRAMES_ARE_STEPS = 1
 PROF_GEMM, PROF_ATTN, PROF_FRONTEND, PROF_DECODE, PROF_ELEMENTWISE, PROF_SUBSAMPLE = 1, 2, 4, 8, 16, 32
 
 # every symbol include/rs_asr.h declares (tests/test_capi_exports.py checks the .so exports them)
@@ -33,6 +34,7 @@ EXPORTS = [
     "rs_rnnt_alsd", "rs_rnnt_alsd_workspace_bytes", "rs_rnnt_beam", "rs_rnnt_beam_workspace_bytes", "rs_host_stage_rows",
     "rs_rnnt_mbs", "rs_rnnt_mbs_workspace_bytes",
     "rs_rnnt_mbs_hotwords", "rs_rnnt_mbs_hotwords_workspace_bytes", "rs_hotwords_check",
+    "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
     "rs_k2_create", "rs_k2_encoder_set_taps",
@@ -215,6 +217,10 @@ def load():
     lib.rs_rnnt_mbs_hotwords.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp, POINTER(RsHotwords), vp, vp,
                                          c_size_t, vp]
     lib.rs_hotwords_check.argtypes = [POINTER(RsHotwords), c_char_p, c_size_t]
+    lib.rs_rnnt_token_scores_workspace_bytes.argtypes = [vp, c_int, c_int]
+    lib.rs_rnnt_token_scores_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_token_scores.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, vp, c_int, c_int, vp, vp, vp, c_size_t, vp]
+    lib.rs_rnnt_token_scores.restype = c_int
     lib.rs_rnnt_alsd_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
     lib.rs_rnnt_alsd_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_alsd.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp, vp,
@@ -503,6 +509,24 @@ class Context:
                                                  float(blank_penalty), MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids),
                                                  _ptr(frames), _ptr(n_ids), _ptr(scores), byref(hotwords) if hotwords is not None else None,
                                                  _ptr(graph_of), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def token_scores_workspace_bytes(self, B, u_cap):
+        """the MINIMUM workspace of `rnnt_token_scores` (32 rows per chunk); a larger one makes fewer chunks, same bits"""
+        n = self.lib.rs_rnnt_token_scores_workspace_bytes(self._h, B, u_cap)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_token_scores_workspace_bytes: invalid arguments (a finalized transducer context, B > 0, u_cap >= 0)")
+        return n
+
+    def rnnt_token_scores(self, joint_enc, enc_lens, B, tp_max, ids, frames, n_ids, logp, top1, ws, stream, frames_are_steps=False,
+                          ws_bytes=None):
+        """log-probability of every token of a finished search under the model's own distribution (include/rs_asr.h
+        rs_rnnt_token_scores): ids / frames int32 [B][u_cap] and n_ids int32 [B] as the search wrote them, logp float32 [B][u_cap],
+        top1 int32 [B][u_cap] or None; frames_are_steps: `frames` holds ALSD's alignment steps"""
+        assert frames.shape == ids.shape and logp.shape == ids.shape and (top1 is None or top1.shape == ids.shape)
+        self.check(self.lib.rs_rnnt_token_scores(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, _ptr(ids), _ptr(frames), _ptr(n_ids),
+                                                 ids.shape[1], SCORES_FRAMES_ARE_STEPS if frames_are_steps else 0, _ptr(logp), _ptr(top1),
+                                                 _ptr(ws), ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes),
+                                                 c_void_p(stream)))
 
     def ctc_align_workspace_bytes(self, B, tp_max, c_max, S):
         n = self.lib.rs_ctc_align_workspace_bytes(self._h, int(B), int(tp_max), int(c_max), int(S))

@@ -30,6 +30,7 @@ class DecodedBatch:
     enc_lens: List[int]
     scores: Optional[List[float]] = None
     degraded: Optional[List[bool]] = None     # per utterance: the requested search overflowed its bound and a weaker one was used (espnet `_search`)
+    token_logprobs: Optional[List[List[float]]] = None   # `AsrModel.token_scores`: log-probability of every id under the model's own distribution
 
 
 def alsd_label_budget(t_frames: int, max_target_len) -> int:
@@ -66,6 +67,7 @@ class _Buffers:
         self.h_graph_of = torch.full((B,), -1, dtype=i32).pin_memory()
         self.hw_set = None
         self.ws_alsd = None              # beam-search scratch (grows with beam and alignment length): on first use
+        self.score_bufs = None           # token scores (`AsrModel.score`): (workspace, logp, top1), on first use
         self.ws = torch.empty((ctx.workspace_bytes(B, self.l_pad),), dtype=torch.uint8, device=dev)
         # the decoder of batch i overlaps the encoder of batch i+1 in the pipelined path: own scratch
         self.ws_dec = torch.empty((ctx.workspace_bytes(B, 16),), dtype=torch.uint8, device=dev)
@@ -126,6 +128,14 @@ class _BufView:
         return self.base.narrow(l_max)
 
     @property
+    def score_bufs(self):
+        return self.base.score_bufs
+
+    @score_bufs.setter
+    def score_bufs(self, v):
+        self.base.score_bufs = v
+
+    @property
     def ws_alsd(self):
         return self.base.ws_alsd
 
@@ -152,8 +162,10 @@ class AsrModel:
     HOTWORD_SETS = 8        # graph sets kept on the device (least recently used dropped)
 
     def __init__(self, cfg: ModelConfig, state_dict, tokenizer, device="cuda", pos_cap: int = DEFAULT_POS_CAP,
-                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host"):
-        """resample: where the packages' `norm_audio` work (resample to 16 kHz, average the channels) is done for input at another
+                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host", token_scores: bool = False):
+        """token_scores: every decode is followed by `score` (rs_rnnt_token_scores, csrc/k_rnnt_scores.hip) on the same stream and
+        `DecodedBatch.token_logprobs` is filled; off (default): nothing runs and nothing is allocated.  May be changed later.
+        resample: where the packages' `norm_audio` work (resample to 16 kHz, average the channels) is done for input at another
         rate or with several channels: "host" (default) = scipy / soxr per utterance as before, "device" = `resample_batch`.
         precision: "bf16" = the throughput mode (bf16 GEMM operands, float32 accumulation and residual stream);
         "fp32" = the parity mode: float32 weights, activations and arithmetic end to end, what the reference computes
@@ -161,6 +173,7 @@ class AsrModel:
         cfg.validate()
         from .resample import check_mode
         self.resample = check_mode(resample)
+        self.token_scores = bool(token_scores)
         self._resample_tables = {}      # rate -> the plan's table on the device
         if precision not in ("bf16", "fp32", "fp32x3", "int8"):
             raise ValueError(f"precision must be 'bf16', 'fp32', 'fp32x3' or 'int8', not {precision!r}")
@@ -359,6 +372,38 @@ class AsrModel:
             self.ctx.encoder(buf.feats, buf.n_frames, buf.B, buf.t_max, want_enc, buf.joint_enc, buf.enc_lens,
                              buf.ws, stream)
             self.decode(self.ctx, buf, buf.ws, stream)
+            self.score(self.ctx, buf, stream)
+
+    SCORE_CHUNK_ROWS = 4096     # (b, u) rows whose logits `score` asks room for at once (60 MB at V + 1 = 3001); fewer rows, more chunks, same bits
+
+    def score(self, ctx, buf, stream, decoding=None):
+        """with `token_scores` on: log-probability of every id the search just wrote, under the model's own distribution, into
+        the buffer set's `score_bufs` (own workspace, allocated on first use like `ws_alsd`; `collect` reads it).  `decoding`: the
+        search that ran when it was overridden for the call.  Synchronises the stream."""
+        if not self.token_scores:
+            return
+        cfg = self.cfg
+        B, u_cap = buf.B, buf.ids.shape[1]
+        rows = min(self.SCORE_CHUNK_ROWS, B * u_cap)
+        hidden = getattr(cfg, "decoder_dim", None) or cfg.pred_hidden          # (the Zipformer family's decoder rows are per chunk too)
+        per_row = 4 * (2 * cfg.joint_hidden + (cfg.n_logits + 63) // 64 * 64 + 2 * hidden + 8)
+        need = ctx.token_scores_workspace_bytes(B, u_cap) + (rows + 31) // 32 * 32 * per_row
+        sb = buf.score_bufs
+        if sb is None or sb[0].numel() < need or sb[1].numel() < B * u_cap:
+            dev = self.device
+            sb = (torch.empty((need,), dtype=torch.uint8, device=dev), torch.empty((B * u_cap,), dtype=torch.float32, device=dev),
+                  torch.empty((B * u_cap,), dtype=torch.int32, device=dev))
+            buf.score_bufs = sb
+        logp, top1 = sb[1][:B * u_cap].view(B, u_cap), sb[2][:B * u_cap].view(B, u_cap)
+        ctx.rnnt_token_scores(buf.joint_enc, buf.enc_lens, B, buf.tp_max, buf.ids, buf.frames, buf.n_ids, logp, top1, sb[0], stream,
+                              frames_are_steps=(decoding or cfg.decoding) == "alsd")
+
+    def score_view(self, buf):
+        """the [B][u_cap] log-probabilities `score` left for this batch (None with `token_scores` off)"""
+        if not self.token_scores or buf.score_bufs is None:
+            return None
+        B, u_cap = buf.B, buf.ids.shape[1]
+        return buf.score_bufs[1][:B * u_cap].view(B, u_cap)
 
     def decode(self, ctx, buf: _Buffers, ws, stream, max_pops=None, decoding=None):
         """stage 3 on `stream`: the checkpoint's decoding strategy (cfg.decoding).  Greedy fills buf.ids / buf.frames
@@ -494,10 +539,13 @@ class AsrModel:
                             stream.wait_event(ev)
                             # decode scratch lives past the encoder's scratch in buf.ws_dec
                             self.decode(ctx_d, buf, buf.ws_dec, stream.cuda_stream)
+                            self.score(ctx_d, buf, stream.cuda_stream)
                             if from_host:
                                 with torch.cuda.stream(stream):
                                     buf.h_out = (buf.n_ids.cpu(), buf.ids.cpu(), buf.frames.cpu(), buf.enc_lens.cpu(),
                                                  buf.scores.cpu() if self.cfg.has_scores else None)
+                                    if self.token_scores:
+                                        buf.h_out = buf.h_out + (self.score_view(buf).cpu(),)
                             if after_decode is not None:
                                 if i > 0:
                                     hooked[i - 1].wait()
@@ -747,6 +795,9 @@ class AsrModel:
         if host is None:
             host = (buf.n_ids.cpu(), buf.ids.cpu(), buf.frames.cpu(), buf.enc_lens.cpu(),
                     buf.scores.cpu() if decoding in ("alsd", "beam", "modified_beam_search") else None)
+            lp = self.score_view(buf)
+            if lp is not None:
+                host = host + (lp.cpu(),)
         n, ids, frames, el = (t.numpy() for t in host[:4])
         if decoding == "alsd":      # alignment step i = frame + labels emitted before
             frames = frames - np.arange(frames.shape[1], dtype=frames.dtype)[None, :]
@@ -755,8 +806,12 @@ class AsrModel:
             scores = host[4].numpy().tolist()
         else:
             scores = None
-        return DecodedBatch([ids[b, :n[b]].tolist() for b in range(buf.B)],
-                            [frames[b, :n[b]].tolist() for b in range(buf.B)], el.tolist(), scores)
+        res = DecodedBatch([ids[b, :n[b]].tolist() for b in range(buf.B)],
+                           [frames[b, :n[b]].tolist() for b in range(buf.B)], el.tolist(), scores)
+        if len(host) > 5:
+            lp = host[5].numpy()
+            res.token_logprobs = [lp[b, :n[b]].tolist() for b in range(buf.B)]
+        return res
 
     def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None) -> DecodedBatch:
         """SPMD form of `transcribe_waveforms` for one process per GPU (`torch.distributed` initialised, RCCL):
@@ -765,6 +820,9 @@ class AsrModel:
         collective (runtime/dist.py: sharded_decode).  With a single process it is `transcribe_waveforms`.  `hotwords` (one
         HotwordGraph or None per utterance) follows each utterance to the rank that decodes it."""
         from . import dist as rdist
+        if self.token_scores:
+            raise ValueError("token_scores is on: transcribe_waveforms_sharded does not gather token log-probabilities; "
+                             "use transcribe_waveforms on each rank, or turn token_scores off")
 
         def run_local(indices, batch):
             # `batch`: the chunk size of the dealing plan (ragged input is dealt as length-sorted chunks, balanced over the
@@ -821,6 +879,7 @@ class AsrModel:
             return res
         order = sorted(range(n), key=lambda i: (len(waveforms[i]), i))
         ids, frames, enc_lens, scores = [None] * n, [None] * n, [None] * n, [None] * n
+        logprobs = [None] * n if self.token_scores else None
         groups = [order[i:i + max_batch] for i in range(0, n, max_batch)]
         # longest batch first: what is left after the last encoder is one decode, and the shortest batch's is the shortest
         # (a ragged list's drain shrinks from the longest batch's decode to the shortest's)
@@ -855,10 +914,13 @@ class AsrModel:
             for k, i in enumerate(group):
                 ids[i], frames[i], enc_lens[i] = res.ids[k], res.frames[k], res.enc_lens[k]
                 scores[i] = res.scores[k] if res.scores is not None else None
+                if logprobs is not None:
+                    logprobs[i] = res.token_logprobs[k]
             if post_q is not None:
                 m = len(group)
                 post_q.put((group, DecodedBatch(res.ids[:m], res.frames[:m], res.enc_lens[:m],
-                                                res.scores[:m] if res.scores is not None else None)))
+                                                res.scores[:m] if res.scores is not None else None,
+                                                token_logprobs=res.token_logprobs[:m] if logprobs is not None else None)))
 
         post = None
         if post_q is not None:
@@ -882,4 +944,4 @@ class AsrModel:
                 gc.enable()
         if post_err:
             raise post_err[0]
-        return DecodedBatch(ids, frames, enc_lens, scores if self.cfg.has_scores else None)
+        return DecodedBatch(ids, frames, enc_lens, scores if self.cfg.has_scores else None, token_logprobs=logprobs)
