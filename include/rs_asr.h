@@ -283,6 +283,46 @@ size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, int T, int be
 int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
                           const rs_avsr_search_opts* opts, int32_t* sequences, int32_t* lengths, float* scores, void* state,
                           size_t state_bytes, void* stream);
+/* The same searches, recording what they otherwise discard after each step (still ABI 7; the _opts forms are these without the
+ * recording and stay bit-identical; nothing the search decides changes).  Replaces: transformers.generation's
+ * `output_scores=True` / `return_dict_in_generate=True` bookkeeping in utils.py — `scores += (next_token_scores,)` of _sample,
+ * `all_scores += (log_probs,)` and the `running_beam_indices` / `beam_indices` gathers of _beam_search — and
+ * GenerationMixin.compute_transition_scores (the gather of scores[p][beam_indices[., p]][sequences[., p + 1]], and its log_softmax for
+ * normalize_logits=True).  Per returned hypothesis and generated position p (sequence index p + 1):
+ *   token_scores  f32[B * n][max_new_tokens]  the processed score of the token chosen there, transformers' scores[p][row][token]:
+ *                 greedy, the logit after the processors above; beam, (x[v] - m) - rs_logf(S) after them, before the running score
+ *   token_lse     f32[B * n][max_new_tokens]  the log-sum-exp of that row's processed scores over v < vocab at that step: M = max, Z =
+ *                 sum of rs_expf(s[v] - M) in the order of S above (thread t adds columns t, t + 256, ... in increasing v, then the
+ *                 binary tree of stride 128 .. 1; a -inf column adds exactly 0.0f), lse = M + rs_logf(Z); token_scores - token_lse is
+ *                 the token's log-probability under the processed distribution (normalize_logits=True)
+ *   beam_indices  i32[B * n][max_new_tokens]  beam search: the flat row clip * beams + beam whose scores the token was taken from (that
+ *                 step's src_rows; transformers' beam_indices); greedy: all -1, NULL allowed
+ * clip-major like `sequences`; with g = lengths - 1 generated tokens (eos included), positions p >= g hold 0.0f, 0.0f and -1, as does a
+ * slot that never finished.  steps_run i32[1] (NULL allowed): the number of steps the search ran.  All device pointers.
+ *   step_scores   f32[max_new_tokens][B * beams][vocab rounded up to 4] or NULL, on _step_scored and _generate_scored: step `step`
+ *                 writes the whole processed row of every hypothesis row, in the order it read them (transformers' `scores`
+ *                 tuple): columns v < vocab the processed score (-inf where banned), the padding columns 0.  Only steps that ran write.
+ * The state is rs_avsr_search_state_bytes_scored / rs_avsr_generate_state_bytes_scored bytes (the histories live in it, re-parented
+ * with the prefixes); its front has the plain layout, so rs_avsr_search_rows serves it.  A state begun with _begin_scored is
+ * stepped, peeked and finished with the _scored forms only.  RS_EINVAL, before anything is enqueued, for a context that is not
+ * avsr, a null token_scores / token_lse, or a null beam_indices in beam search; RS_EWORKSPACE for a short state; the
+ * *_state_bytes_scored queries return 0 for invalid arguments. */
+size_t rs_avsr_search_state_bytes_scored(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts);
+int rs_avsr_search_begin_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
+                                size_t state_bytes, void* stream);
+int rs_avsr_search_step_scored(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts,
+                               float* step_scores, int B, int vocab, void* state, size_t state_bytes, void* stream);
+int rs_avsr_search_peek_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state,
+                               size_t state_bytes, int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores,
+                               int32_t* goes_on, void* stream);
+int rs_avsr_search_finish_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state,
+                                 size_t state_bytes, int32_t* sequences, int32_t* lengths, float* scores, float* token_scores,
+                                 float* token_lse, int32_t* beam_indices, int32_t* steps_run, void* stream);
+size_t rs_avsr_generate_state_bytes_scored(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts);
+int rs_avsr_generate_scored(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
+                            const rs_avsr_search_opts* opts, float* step_scores, int32_t* sequences, int32_t* lengths, float* scores,
+                            float* token_scores, float* token_lse, int32_t* beam_indices, int32_t* steps_run, void* state,
+                            size_t state_bytes, void* stream);
 void rs_destroy(rs_ctx* ctx);
 const char* rs_last_error(const rs_ctx* ctx);
 int rs_abi_version(void);

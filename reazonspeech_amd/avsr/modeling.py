@@ -37,8 +37,21 @@ class Seq2SeqLMOutput:
 
 @dataclass
 class BeamOutput:
+    """generate(return_dict_in_generate=True).  The fields after `sequences_scores` are filled by search="device" only, W = the
+    sequences' width - 1 generated positions, rows clip-major like `sequences`:
+    scores          transformers' tuple, one float32 [B * num_beams][vocab] per step the search ran: the processed scores of every
+                    hypothesis row in the order the step read them (-inf where a processor banned a token); only with output_scores=True
+    beam_indices    int64 [B * n][W]: the row of `scores[p]` the token at position p was taken from, -1 past the end; None for greedy
+    token_scores    float32 [B * n][W]: scores[p][beam_indices[., p]][sequences[., p + 1]], 0 past the end (eos is the last token)
+    token_logprobs  float32 [B * n][W]: token_scores minus the log-sum-exp of that row of scores[p] (normalize_logits=True)
+    confidence      float64 [B * n]: exp(mean of the hypothesis' token_logprobs); nan for a slot that never finished"""
     sequences: torch.Tensor
     sequences_scores: Optional[torch.Tensor] = None
+    scores: Optional[tuple] = None
+    beam_indices: Optional[torch.Tensor] = None
+    token_scores: Optional[torch.Tensor] = None
+    token_logprobs: Optional[torch.Tensor] = None
+    confidence: Optional[torch.Tensor] = None
 
 
 class AVHubertModel:
@@ -139,7 +152,12 @@ class AVHubertForConditionalGeneration:
         -> LongTensor [B][<= 1 + max_new_tokens] starting with bos (CPU), or BeamOutput with `sequences_scores`
         With search="device" also repetition_penalty, no_repeat_ngram_size, min_new_tokens / min_length, early_stopping (False, True,
         "never") and num_return_sequences = n <= num_beams (sequences [B * n][L] clip-major, sequences_scores [B * n]), with
-        transformers' semantics; do_sample, bad_words_ids, per-step scores, beam_indices and logits_processor lists stay refused."""
+        transformers' semantics; do_sample, bad_words_ids and logits_processor lists stay refused.
+        With search="device", return_dict_in_generate=True also records, on the device, every token's score (BeamOutput: beam_indices,
+        token_scores, token_logprobs, confidence; compute_transition_scores() is served from them), and output_scores=True adds the
+        `scores` tuple.  One difference from transformers: past a greedy row's eos transformers gathers the pad token's logit of a
+        row fed with pad; here those positions are 0.0.  Without return_dict_in_generate nothing is recorded; search="host" ignores
+        output_scores as before."""
         if do_sample:
             raise NotImplementedError("sampling is not built (the reference's documented call is deterministic beam search)")
         # transformers' generate() takes dozens of options; the ones that change the search and are not restated here must not be
@@ -173,7 +191,12 @@ class AVHubertForConditionalGeneration:
         mask = padding_mask if padding_mask is not None else np.zeros(enc.shape[:2], np.float32)
         if self.search == "device":
             greedy = num_beams <= 1
-            seq, scores = self.dev.generate(enc, mask, 1 if greedy else int(num_beams), int(max_new_tokens), greedy, float(length_penalty), **opts)
+            K = 1 if greedy else int(num_beams)
+            if return_dict_in_generate:
+                seq, scores, rec = self.dev.generate(enc, mask, K, int(max_new_tokens), greedy, float(length_penalty), record=True,
+                                                     dump_scores=bool(kwargs.get("output_scores")), **opts)
+                return self._scored_output(seq, None if greedy else scores, rec)
+            seq, scores = self.dev.generate(enc, mask, K, int(max_new_tokens), greedy, float(length_penalty), **opts)
             scores = None if greedy else scores
         elif num_beams <= 1:
             seq, scores = generation.greedy_search(self.dev, enc, mask, int(max_new_tokens)), None
@@ -183,6 +206,36 @@ class AVHubertForConditionalGeneration:
         if return_dict_in_generate:
             return BeamOutput(seq, None if scores is None else torch.from_numpy(np.ascontiguousarray(scores)))
         return seq
+
+    def _scored_output(self, seq, scores, rec):
+        """the arrays rs_avsr_generate_scored recorded -> BeamOutput; kept for compute_transition_scores"""
+        ts, lse = rec["token_scores"], rec["token_lse"]
+        live = np.arange(1, ts.shape[1] + 1)[None, :] < rec["lengths"][:, None]
+        lp = np.where(live, ts - np.where(live, lse, 0.0), 0.0).astype(np.float32)
+        g = live.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            conf = np.exp(lp.astype(np.float64).sum(axis=1) / g)
+        t = lambda x: torch.from_numpy(np.ascontiguousarray(x))                                     # noqa: E731
+        out = BeamOutput(t(seq), None if scores is None else t(scores),
+                         scores=None if rec["step_scores"] is None else tuple(t(x) for x in rec["step_scores"]),
+                         beam_indices=None if rec["beam_indices"] is None else t(rec["beam_indices"].astype(np.int64)),
+                         token_scores=t(ts), token_logprobs=t(lp), confidence=t(conf))
+        self._scored = out
+        return out
+
+    def compute_transition_scores(self, sequences, scores=None, beam_indices=None, normalize_logits=False):
+        """transformers' GenerationMixin.compute_transition_scores for the sequences of the last generate(search="device",
+        return_dict_in_generate=True): float32 [B * n][W], served from the arrays the device recorded (`scores` and `beam_indices`
+        are accepted for the signature's sake and not read, so output_scores=True is not needed).  normalize_logits=True returns
+        token_logprobs.  Positions past a hypothesis' end hold 0 (also for greedy search, where transformers gathers the pad token's
+        logit)."""
+        last = getattr(self, "_scored", None)
+        if last is None:
+            raise ValueError('compute_transition_scores: no recorded generate() (search="device", return_dict_in_generate=True) precedes this call')
+        sequences = torch.as_tensor(sequences)
+        if sequences.shape != last.sequences.shape or not torch.equal(sequences.cpu().to(last.sequences.dtype), last.sequences):
+            raise ValueError("compute_transition_scores: `sequences` are not those of the last recorded generate()")
+        return (last.token_logprobs if normalize_logits else last.token_scores).clone()
 
 
 def synthetic_model(config: AvsrConfig = AVSR_BASE, seed: int = 0, device="cuda", products=None, search=None):

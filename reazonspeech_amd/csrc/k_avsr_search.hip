@@ -51,6 +51,25 @@
 //       instead of den (host-computed; den_heur == den otherwise)
 //   num_return_sequences n: the finish kernel writes the n best finished slots of every clip, clip-major
 //
+// RECORDING (the _scored entry points; the <.., true> instantiations; transformers' output_scores / beam_indices /
+// compute_transition_scores).  Nothing the search decides changes.  Beside run_seq / fin_seq every hypothesis row keeps, per sequence
+// position pos = p + 1 of generated position p, in buffers with the same ping-pong, re-parented and copied into the finished slots in
+// the same places:
+//   tok_score   the processed score s of the token chosen there, transformers' scores[p][row][token]: greedy, the logit after the
+//               processors; beam, (x[v] - m) - rs_logf(S) after the processors and before the running score is added
+//   tok_lse     the log-sum-exp of that row's processed scores s[v], v < V, at that step (normalize_logits=True subtracts it)
+//   beam_idx    beam only: the flat row clip * beams + beam the token was taken from (that step's src_rows; transformers' beam_indices)
+// SUMMATION ORDER of Z (tok_lse), the same as S's: M = max_v s[v] (exact in any order); thread t of 256 owns the columns v = t, t + 256,
+//   ... and adds rs_expf(s[v] - M) to a zero in increasing v, where a banned (-inf) column adds exactly 0.0f and is not passed through
+//   rs_expf; the 256 partial sums are combined by the binary tree of stride 128, 64, ..., 1; lse = M + rs_logf(Z).  A row whose every
+//   column is -inf has lse = -inf.  This is one more max pass and one more sum pass over the clip's K rows, re-read from global
+//   memory / L2 like the selection rounds; nothing of size K V goes into LDS.
+// With a dump pointer the max pass also stores the whole processed row: step_scores[step][row][v] = s[v] for v < V (-inf where
+// banned) and 0 for V <= v < Vp, rows in the order the step read them (transformers' `scores` tuple); only steps that ran write.
+// The finish kernel writes token_scores / token_lse / beam_indices [B n][max_new_tokens] for the n returned hypotheses of every clip;
+// positions past a hypothesis' generated tokens (eos included), and slots that never finished, hold 0.0f / 0.0f / -1.
+// Restated for the CPU, operation for operation, in tests/avsr_token_scores_checker.c.
+//
 // State buffers ping-pong by step parity: step s reads run_seq / fin_seq [s & 1] and writes [(s + 1) & 1]; positions beyond the
 // ones a step writes still hold pad_token_id from rs_avsr_search_begin.
 #include <math.h>
@@ -77,10 +96,14 @@ struct SearchPtrs {
     float *run_score, *fin_score;
     int32_t* go2;
     uint8_t* marks;
+    // recording (null otherwise): [2][rows][max_len] like run_seq / fin_seq, indexed by sequence position (position 0 unused)
+    float *run_ts, *run_tl, *fin_ts, *fin_tl;
+    int32_t *run_bi, *fin_bi;
 };
 constexpr size_t SEARCH_SLACK = 256;
-// the search state's layout.  go2_words / mark_bytes: the pieces the options add behind the plain layout (0: not taken, the pointer is null)
-SearchPtrs search_layout(int B, int K, int max_len, size_t go2_words, size_t mark_bytes, rs_arena& a) {
+// the search state's layout.  go2_words / rec / mark_bytes: the pieces the options and the recording add behind the plain layout (0: not
+// taken, the pointer is null); the marks come last: they are the one piece whose size depends on the vocabulary
+SearchPtrs search_layout(int B, int K, int max_len, size_t go2_words, size_t mark_bytes, bool rec, rs_arena& a) {
     SearchPtrs p;
     const size_t R = (size_t)B * K;
     p.tok = a.take<int32_t>(R); p.src = a.take<int32_t>(R);
@@ -90,6 +113,10 @@ SearchPtrs search_layout(int B, int K, int max_len, size_t go2_words, size_t mar
     p.go = a.take<int32_t>((size_t)max_len + 1);
     p.run_score = a.take<float>(R); p.fin_score = a.take<float>(R);
     p.go2 = go2_words ? a.take<int32_t>(go2_words) : nullptr;
+    const size_t H = rec ? 2 * R * max_len : 0;
+    p.run_ts = H ? a.take<float>(H) : nullptr; p.run_tl = H ? a.take<float>(H) : nullptr;
+    p.fin_ts = H ? a.take<float>(H) : nullptr; p.fin_tl = H ? a.take<float>(H) : nullptr;
+    p.run_bi = H ? a.take<int32_t>(H) : nullptr; p.fin_bi = H ? a.take<int32_t>(H) : nullptr;
     p.marks = mark_bytes ? a.take<uint8_t>(mark_bytes) : nullptr;
     return p;
 }
@@ -105,6 +132,11 @@ __global__ __launch_bounds__(NT) void avsr_search_init_kernel(SearchPtrs p, int 
         for (int par = 0; par < 2; ++par) {
             p.run_seq[((size_t)par * R + (size_t)b * K) * max_len + i] = tokv;
             p.fin_seq[((size_t)par * R + (size_t)b * K) * max_len + i] = tokv;
+            if (p.run_ts) {
+                const size_t at = ((size_t)par * R + (size_t)b * K) * max_len + i;
+                p.run_ts[at] = 0.0f; p.run_tl[at] = 0.0f; p.fin_ts[at] = 0.0f; p.fin_tl[at] = 0.0f;
+                p.run_bi[at] = -1; p.fin_bi[at] = -1;
+            }
         }
     }
     if (tid < K) {
@@ -171,10 +203,11 @@ __device__ __forceinline__ float processed(float s, uint8_t mark, float penalty)
     return mark == 2 ? -INFINITY : s;
 }
 
-// grid B (rows): transformers' _sample with do_sample False for one step
-template <bool OPTS>
+// grid B (rows): transformers' _sample with do_sample False for one step.  REC: the chosen token's processed logit and the row's
+// log-sum-exp go to run_ts / run_tl (one copy: greedy rows are never re-parented), the processed row to dump (if not null)
+template <bool OPTS, bool REC>
 __global__ __launch_bounds__(NT) void avsr_greedy_step_kernel(const float* __restrict__ logits, int V, int Vp, int step, int max_len, int eos, int pad,
-                                                              SearchPtrs p, OptArgs o) {
+                                                              SearchPtrs p, OptArgs o, float* __restrict__ dump) {
     extern __shared__ __align__(16) uint8_t lds_marks[];
     __shared__ float sv[NT / 64];
     __shared__ int si[NT / 64];
@@ -197,9 +230,34 @@ __global__ __launch_bounds__(NT) void avsr_greedy_step_kernel(const float* __res
         }
     }
     block_argmax(best, bi, sv, si);
+    float lse = 0.0f;
+    if constexpr (REC) {                                  // Z in the file's documented order; best is M
+        __shared__ float zred[NT];
+        float z = 0.0f;
+        for (int v = tid; v < V; v += NT) {
+            float x = row[v];
+            if constexpr (OPTS) x = processed(x, (o.marks ? o.marks + (size_t)b * Vp : lds_marks)[v], o.penalty);
+            z += x == -INFINITY ? 0.0f : rs_expf(x - best);
+            if (dump) dump[(size_t)b * Vp + v] = x;
+        }
+        if (dump)
+            for (int v = V + tid; v < Vp; v += NT) dump[(size_t)b * Vp + v] = 0.0f;
+        zred[tid] = z;
+        __syncthreads();
+        for (int stride = NT / 2; stride > 0; stride >>= 1) {
+            if (tid < stride) zred[tid] += zred[tid + stride];
+            __syncthreads();
+        }
+        lse = best == -INFINITY ? -INFINITY : best + rs_logf(zred[0]);
+    }
     if (tid == 0) {
         if (bi >= V) bi = 0;
         const int unfinished = p.can[b];
+        if constexpr (REC)
+            if (unfinished) {
+                p.run_ts[(size_t)b * max_len + step + 1] = best;
+                p.run_tl[(size_t)b * max_len + step + 1] = lse;
+            }
         const int nxt = unfinished ? bi : pad;
         p.run_seq[(size_t)b * max_len + step + 1] = nxt;
         p.tok[b] = nxt;
@@ -211,10 +269,10 @@ __global__ __launch_bounds__(NT) void avsr_greedy_step_kernel(const float* __res
     }
 }
 
-// grid B (clips): transformers' _beam_search for one step (the file's head comment)
-template <bool OPTS>
+// grid B (clips): transformers' _beam_search for one step (the file's head comment).  REC: RECORDING there
+template <bool OPTS, bool REC>
 __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restrict__ logits, int V, int Vp, int K, int step, int max_len, int eos, float den,
-                                                            float den_heur, int B, SearchPtrs p, OptArgs o) {
+                                                            float den_heur, int B, SearchPtrs p, OptArgs o, float* __restrict__ dump) {
     extern __shared__ __align__(16) uint8_t lds_marks[];
     __shared__ float red[MAXK][NT];
     __shared__ float row_max[MAXK], row_lse[MAXK], row_run[MAXK];
@@ -223,6 +281,7 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
     __shared__ int keep[MAXK], best[MAXK], old_len[MAXK], old_fin[MAXK], used[3 * MAXK];
     __shared__ float sv[NT / 64];
     __shared__ int si[NT / 64];
+    __shared__ float row_pmax[REC ? MAXK : 1], row_plse[REC ? MAXK : 1], cand_ts[REC ? 2 * MAXK : 1], cand_tl[REC ? 2 * MAXK : 1];
     if (!goes_on(false, (uint32_t)p.go[step])) return;
     if constexpr (OPTS)
         if (o.go2 && o.go2[step] == 0) return;
@@ -266,6 +325,48 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
     if (tid < K) row_lse[tid] = rs_logf(red[tid][0]);
     __syncthreads();
 
+    if constexpr (REC) {                                  // 1b. per row: maximum M and log-sum-exp of the processed scores (RECORDING)
+        for (int k = 0; k < K; ++k) {
+            const float m = row_max[k], l = row_lse[k];
+            float pm = -INFINITY;
+            for (int v = tid; v < V; v += NT) {
+                float s = (lg[(size_t)k * Vp + v] - m) - l;
+                if constexpr (OPTS) s = processed(s, marks[(size_t)k * Vp + v], o.penalty);
+                pm = fmaxf(pm, s);
+                if (dump) dump[((size_t)b * K + k) * Vp + v] = s;
+            }
+            if (dump)
+                for (int v = V + tid; v < Vp; v += NT) dump[((size_t)b * K + k) * Vp + v] = 0.0f;
+            red[k][tid] = pm;
+        }
+        __syncthreads();
+        for (int stride = NT / 2; stride > 0; stride >>= 1) {
+            if (tid < stride)
+                for (int k = 0; k < K; ++k) red[k][tid] = fmaxf(red[k][tid], red[k][tid + stride]);
+            __syncthreads();
+        }
+        if (tid < K) row_pmax[tid] = red[tid][0];
+        __syncthreads();
+        for (int k = 0; k < K; ++k) {
+            const float m = row_max[k], l = row_lse[k], M = row_pmax[k];
+            float z = 0.0f;
+            for (int v = tid; v < V; v += NT) {
+                float s = (lg[(size_t)k * Vp + v] - m) - l;
+                if constexpr (OPTS) s = processed(s, marks[(size_t)k * Vp + v], o.penalty);
+                z += s == -INFINITY ? 0.0f : rs_expf(s - M);
+            }
+            red[k][tid] = z;
+        }
+        __syncthreads();
+        for (int stride = NT / 2; stride > 0; stride >>= 1) {
+            if (tid < stride)
+                for (int k = 0; k < K; ++k) red[k][tid] += red[k][tid + stride];
+            __syncthreads();
+        }
+        if (tid < K) row_plse[tid] = row_pmax[tid] == -INFINITY ? -INFINITY : row_pmax[tid] + rs_logf(red[tid][0]);
+        __syncthreads();
+    }
+
     // 2. the 2 K best (value descending, flat index ascending)
     float prev_v = INFINITY;
     int prev_i = -1;
@@ -302,6 +403,11 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
             all_end &= ends[j];
             lp_run[j] = top_lp[j] + (ends[j] ? 1.0f : 0.0f) * NEG;
             used[j] = 0;
+            if constexpr (REC) {                          // the selection's own value before the running score was added
+                float s = (lg[(size_t)parent[j] * Vp + token[j]] - row_max[parent[j]]) - row_lse[parent[j]];
+                if constexpr (OPTS) s = processed(s, marks[(size_t)parent[j] * Vp + token[j]], o.penalty);
+                cand_ts[j] = s; cand_tl[j] = row_plse[parent[j]];
+            }
         }
         for (int j = 0; j < K; ++j) {                     // stable: the first of equal values
             int w = -1;
@@ -378,6 +484,28 @@ __global__ __launch_bounds__(NT) void avsr_beam_step_kernel(const float* __restr
             fin_d[(size_t)j * max_len + pos] = f;
         }
     }
+    if constexpr (REC) {                                  // the histories follow the prefixes: same parity, same re-parenting
+        const size_t src_o = ((size_t)(step & 1) * R + (size_t)b * K) * max_len, dst_o = ((size_t)(cur & 1) * R + (size_t)b * K) * max_len;
+        for (int j = 0; j < K; ++j) {
+            const int c = keep[j], w = best[j];
+            for (int pos = 1 + tid; pos <= cur && pos < max_len; pos += NT) {
+                const size_t rp = src_o + (size_t)parent[c] * max_len + pos, d = dst_o + (size_t)j * max_len + pos;
+                p.run_ts[d] = pos == cur ? cand_ts[c] : p.run_ts[rp];
+                p.run_tl[d] = pos == cur ? cand_tl[c] : p.run_tl[rp];
+                p.run_bi[d] = pos == cur ? b * K + parent[c] : p.run_bi[rp];
+                if (w < K) {
+                    const size_t fp = src_o + (size_t)w * max_len + pos;
+                    p.fin_ts[d] = p.fin_ts[fp]; p.fin_tl[d] = p.fin_tl[fp]; p.fin_bi[d] = p.fin_bi[fp];
+                } else {
+                    const int cw = w - K;
+                    const size_t wp = src_o + (size_t)parent[cw] * max_len + pos;
+                    p.fin_ts[d] = pos == cur ? cand_ts[cw] : p.run_ts[wp];
+                    p.fin_tl[d] = pos == cur ? cand_tl[cw] : p.run_tl[wp];
+                    p.fin_bi[d] = pos == cur ? b * K + parent[cw] : p.run_bi[wp];
+                }
+            }
+        }
+    }
 }
 
 // grid B: the result of clip b: its n_ret best finished hypotheses (beam; slots 0 .. n_ret - 1, output rows b n_ret + j) or its row
@@ -395,9 +523,30 @@ __global__ __launch_bounds__(NT) void avsr_search_finish_kernel(SearchPtrs p, in
     }
 }
 
+// grid B, after avsr_search_finish_kernel: the recorded histories of the same rows, [B n_ret][max_len - 1] (RECORDING); steps: last[0]
+__global__ __launch_bounds__(NT) void avsr_search_finish_scored_kernel(SearchPtrs p, int B, int K, int max_len, int greedy, int n_ret,
+                                                                       float* __restrict__ token_scores, float* __restrict__ token_lse,
+                                                                       int32_t* __restrict__ beam_indices, int32_t* __restrict__ steps) {
+    const int b = blockIdx.x, tid = threadIdx.x, N = max_len - 1;
+    const size_t R = (size_t)B * K;
+    const size_t at = greedy ? (size_t)b * max_len : ((size_t)(p.last[b] & 1) * R + (size_t)b * K) * max_len;
+    const float *ts = (greedy ? p.run_ts : p.fin_ts) + at, *tl = (greedy ? p.run_tl : p.fin_tl) + at;
+    const int32_t* bi = p.fin_bi + at;
+    for (int i = tid; i < n_ret * N; i += NT) {
+        const int j = i / N, pos = i % N + 1;
+        const bool live = pos < p.fin_len[(size_t)b * K + j];
+        const size_t o = (size_t)b * n_ret * N + i, h = (size_t)j * max_len + pos;
+        token_scores[o] = live ? ts[h] : 0.0f;
+        token_lse[o] = live ? tl[h] : 0.0f;
+        if (beam_indices) beam_indices[o] = live && !greedy ? bi[h] : -1;
+    }
+    if (b == 0 && tid == 0 && steps) *steps = p.last[0];
+}
+
 // the options of a call: neutral for a null pointer; what the kernels and the state layout need of them
 struct Opts {
     rs_avsr_search_opts o{1.0f, 0, 0, 0, 1};
+    bool rec = false;           // the _scored entry points: the histories are part of the state
     bool kernel() const { return o.repetition_penalty != 1.0f || o.no_repeat_ngram_size > 0 || o.min_new_tokens > 0 || o.early_stopping == 1; }
     bool es_true() const { return o.early_stopping == 1; }
 };
@@ -406,7 +555,7 @@ size_t mark_bytes(bool opts_kernel, int B, int K, int vocab) {       // marks ke
     return opts_kernel && (size_t)K * Vp > (size_t)MARK_LDS_BYTES ? (size_t)B * K * Vp : 0;
 }
 SearchPtrs search_layout_opts(const Opts& op, int B, int K, int max_len, int vocab, rs_arena& a) {
-    return search_layout(B, K, max_len, op.es_true() ? (size_t)max_len + 1 : 0, mark_bytes(op.kernel(), B, K, vocab), a);
+    return search_layout(B, K, max_len, op.es_true() ? (size_t)max_len + 1 : 0, mark_bytes(op.kernel(), B, K, vocab), op.rec, a);
 }
 size_t search_bytes(const Opts& op, int B, int K, int max_len, int vocab) {
     rs_arena a;
@@ -463,23 +612,21 @@ bool opts_ok_for_bytes(const rs_avsr_search_opts* o, int beams) {
                   o->num_return_sequences >= 1 && o->num_return_sequences <= beams);
 }
 
-}  // namespace
-
-extern "C" size_t rs_avsr_search_state_bytes_opts(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts) {
+// ---- the entry points: every family (plain, _opts, _scored) is one implementation with the options and the recording as arguments ----
+size_t search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts, bool rec) {
     if (!rs_avsr_dims_of(ctx) || B <= 0 || beams < 1 || beams > MAXK || max_len < 2 || vocab < 4 || !opts_ok_for_bytes(opts, beams)) return 0;
     Opts op;
+    op.rec = rec;
     if (opts) op.o = *opts;
     return search_bytes(op, B, beams, max_len, vocab);
 }
-extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len) {
-    return rs_avsr_search_state_bytes_opts(ctx, B, beams, max_len, 4, nullptr);
-}
 
-extern "C" int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
-                                         size_t state_bytes, void* stream) {
+int search_begin(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, bool rec, int B, int vocab, void* state, size_t state_bytes,
+                 void* stream) {
     if (!ctx) return RS_EINVAL;
     SearchPtrs p;
     Opts op;
+    op.rec = rec;
     const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_begin", &p, &op);
     if (rc != RS_OK) return rc;
     hipLaunchKernelGGL(avsr_search_init_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
@@ -487,15 +634,14 @@ extern "C" int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* sear
     RS_CHECK_LAUNCH(ctx, "avsr search begin");
     return RS_OK;
 }
-extern "C" int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes, void* stream) {
-    return rs_avsr_search_begin_opts(ctx, search, nullptr, B, vocab, state, state_bytes, stream);
-}
 
-extern "C" int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B,
-                                        int vocab, void* state, size_t state_bytes, void* stream) {
+// step_scores (rec only): f32[max_new_tokens][B * beams][Vp] or null
+int search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, bool rec, float* step_scores, int B,
+                int vocab, void* state, size_t state_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
     SearchPtrs p;
     Opts op;
+    op.rec = rec;
     const int rc = check_search(ctx, search, opts, B, vocab, state, state_bytes, "rs_avsr_search_step", &p, &op);
     if (rc != RS_OK) return rc;
     if (!logits || step < 0 || step >= search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_step: bad argument (step %d of %d)", step, search->max_new_tokens);
@@ -504,25 +650,106 @@ extern "C" int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int st
     const bool ok = op.kernel();
     // the marks of a workgroup's rows: dynamic LDS unless they live in the state
     const size_t lds = ok && !oa.marks ? (size_t)(search->greedy ? 1 : search->beams) * Vp : 0;
+    float* const dump = rec && step_scores ? step_scores + (size_t)step * B * search->beams * Vp : nullptr;
+    hipStream_t s = (hipStream_t)stream;
     if (search->greedy) {
-        if (ok)
-            hipLaunchKernelGGL(avsr_greedy_step_kernel<true>, dim3(B), dim3(NT), lds, (hipStream_t)stream, logits, vocab, Vp, step, max_len, search->eos_token_id,
-                               search->pad_token_id, p, oa);
-        else
-            hipLaunchKernelGGL(avsr_greedy_step_kernel<false>, dim3(B), dim3(NT), 0, (hipStream_t)stream, logits, vocab, Vp, step, max_len, search->eos_token_id,
-                               search->pad_token_id, p, oa);
+#define RS_GREEDY(O, R) \
+    hipLaunchKernelGGL((avsr_greedy_step_kernel<O, R>), dim3(B), dim3(NT), lds, s, logits, vocab, Vp, step, max_len, search->eos_token_id, search->pad_token_id, p, oa, dump)
+        if (rec) { if (ok) RS_GREEDY(true, true); else RS_GREEDY(false, true); }
+        else { if (ok) RS_GREEDY(true, false); else RS_GREEDY(false, false); }
+#undef RS_GREEDY
     } else {
         const float den = (float)pow((double)(step + 1), (double)search->length_penalty);
         const float den_heur = op.o.early_stopping == 2 && search->length_penalty > 0.0f ? (float)pow((double)search->max_new_tokens, (double)search->length_penalty) : den;
-        if (ok)
-            hipLaunchKernelGGL(avsr_beam_step_kernel<true>, dim3(B), dim3(NT), lds, (hipStream_t)stream, logits, vocab, Vp, search->beams, step, max_len,
-                               search->eos_token_id, den, den_heur, B, p, oa);
-        else
-            hipLaunchKernelGGL(avsr_beam_step_kernel<false>, dim3(B), dim3(NT), 0, (hipStream_t)stream, logits, vocab, Vp, search->beams, step, max_len,
-                               search->eos_token_id, den, den_heur, B, p, oa);
+#define RS_BEAM(O, R) \
+    hipLaunchKernelGGL((avsr_beam_step_kernel<O, R>), dim3(B), dim3(NT), lds, s, logits, vocab, Vp, search->beams, step, max_len, search->eos_token_id, den, den_heur, B, p, oa, dump)
+        if (rec) { if (ok) RS_BEAM(true, true); else RS_BEAM(false, true); }
+        else { if (ok) RS_BEAM(true, false); else RS_BEAM(false, false); }
+#undef RS_BEAM
     }
     RS_CHECK_LAUNCH(ctx, "avsr search step");
     return RS_OK;
+}
+
+int search_peek(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, bool rec, int B, void* state, size_t state_bytes, int step,
+                int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    SearchPtrs p;
+    Opts op;
+    op.rec = rec;
+    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_peek", &p, &op);
+    if (rc != RS_OK) return rc;
+    if (step < 0 || step > search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_peek: step %d of %d", step, search->max_new_tokens);
+    const size_t R = (size_t)B * search->beams;
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t w = 0, w2 = 1;
+    if (tokens) RS_HIP(ctx, hipMemcpyAsync(tokens, p.tok, R * 4, hipMemcpyDeviceToHost, s));
+    if (src_rows) RS_HIP(ctx, hipMemcpyAsync(src_rows, p.src, R * 4, hipMemcpyDeviceToHost, s));
+    if (run_scores) RS_HIP(ctx, hipMemcpyAsync(run_scores, p.run_score, R * 4, hipMemcpyDeviceToHost, s));
+    if (fin_scores) RS_HIP(ctx, hipMemcpyAsync(fin_scores, p.fin_score, R * 4, hipMemcpyDeviceToHost, s));
+    RS_HIP(ctx, hipMemcpyAsync(&w, p.go + step, 4, hipMemcpyDeviceToHost, s));
+    if (op.es_true()) RS_HIP(ctx, hipMemcpyAsync(&w2, p.go2 + step, 4, hipMemcpyDeviceToHost, s));
+    RS_HIP(ctx, hipStreamSynchronize(s));
+    if (goes_on_out) *goes_on_out = goes_on(search->greedy != 0, w) && w2 != 0 ? 1 : 0;
+    return RS_OK;
+}
+
+// the recorded outputs of a _scored call; beam_indices may be null for a greedy search, steps always
+struct ScoredOut { float *token_scores, *token_lse; int32_t *beam_indices, *steps; };
+bool scored_out_ok(const rs_avsr_search* search, const ScoredOut& so) { return so.token_scores && so.token_lse && (so.beam_indices || search->greedy); }
+
+int search_finish(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, const ScoredOut* so, int B, void* state, size_t state_bytes,
+                  int32_t* sequences, int32_t* lengths, float* scores, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    SearchPtrs p;
+    Opts op;
+    op.rec = so != nullptr;
+    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_finish", &p, &op);
+    if (rc != RS_OK) return rc;
+    if (!sequences || !lengths || (so && !scored_out_ok(search, *so))) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_finish: null pointer");
+    hipLaunchKernelGGL(avsr_search_finish_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
+                       search->greedy ? 1 : 0, op.o.num_return_sequences, sequences, lengths, scores);
+    RS_CHECK_LAUNCH(ctx, "avsr search finish");
+    if (so) {
+        hipLaunchKernelGGL(avsr_search_finish_scored_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
+                           search->greedy ? 1 : 0, op.o.num_return_sequences, so->token_scores, so->token_lse, so->beam_indices, so->steps);
+        RS_CHECK_LAUNCH(ctx, "avsr search finish (recorded scores)");
+    }
+    RS_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
+    return RS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t rs_avsr_search_state_bytes_opts(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts) {
+    return search_state_bytes(ctx, B, beams, max_len, vocab, opts, false);
+}
+extern "C" size_t rs_avsr_search_state_bytes_scored(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts) {
+    return search_state_bytes(ctx, B, beams, max_len, vocab, opts, true);
+}
+extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len) {
+    return rs_avsr_search_state_bytes_opts(ctx, B, beams, max_len, 4, nullptr);
+}
+
+extern "C" int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
+                                         size_t state_bytes, void* stream) {
+    return search_begin(ctx, search, opts, false, B, vocab, state, state_bytes, stream);
+}
+extern "C" int rs_avsr_search_begin_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
+                                           size_t state_bytes, void* stream) {
+    return search_begin(ctx, search, opts, true, B, vocab, state, state_bytes, stream);
+}
+extern "C" int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes, void* stream) {
+    return rs_avsr_search_begin_opts(ctx, search, nullptr, B, vocab, state, state_bytes, stream);
+}
+
+extern "C" int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B,
+                                        int vocab, void* state, size_t state_bytes, void* stream) {
+    return search_step(ctx, logits, step, search, opts, false, nullptr, B, vocab, state, state_bytes, stream);
+}
+extern "C" int rs_avsr_search_step_scored(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts,
+                                          float* step_scores, int B, int vocab, void* state, size_t state_bytes, void* stream) {
+    return search_step(ctx, logits, step, search, opts, true, step_scores, B, vocab, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes,
                                    void* stream) {
@@ -543,24 +770,12 @@ extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, in
 
 extern "C" int rs_avsr_search_peek_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                         int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
-    if (!ctx) return RS_EINVAL;
-    SearchPtrs p;
-    Opts op;
-    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_peek", &p, &op);
-    if (rc != RS_OK) return rc;
-    if (step < 0 || step > search->max_new_tokens) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_peek: step %d of %d", step, search->max_new_tokens);
-    const size_t R = (size_t)B * search->beams;
-    hipStream_t s = (hipStream_t)stream;
-    uint32_t w = 0, w2 = 1;
-    if (tokens) RS_HIP(ctx, hipMemcpyAsync(tokens, p.tok, R * 4, hipMemcpyDeviceToHost, s));
-    if (src_rows) RS_HIP(ctx, hipMemcpyAsync(src_rows, p.src, R * 4, hipMemcpyDeviceToHost, s));
-    if (run_scores) RS_HIP(ctx, hipMemcpyAsync(run_scores, p.run_score, R * 4, hipMemcpyDeviceToHost, s));
-    if (fin_scores) RS_HIP(ctx, hipMemcpyAsync(fin_scores, p.fin_score, R * 4, hipMemcpyDeviceToHost, s));
-    RS_HIP(ctx, hipMemcpyAsync(&w, p.go + step, 4, hipMemcpyDeviceToHost, s));
-    if (op.es_true()) RS_HIP(ctx, hipMemcpyAsync(&w2, p.go2 + step, 4, hipMemcpyDeviceToHost, s));
-    RS_HIP(ctx, hipStreamSynchronize(s));
-    if (goes_on_out) *goes_on_out = goes_on(search->greedy != 0, w) && w2 != 0 ? 1 : 0;
-    return RS_OK;
+    return search_peek(ctx, search, opts, false, B, state, state_bytes, step, tokens, src_rows, run_scores, fin_scores, goes_on_out, stream);
+}
+extern "C" int rs_avsr_search_peek_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
+                                          int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out,
+                                          void* stream) {
+    return search_peek(ctx, search, opts, true, B, state, state_bytes, step, tokens, src_rows, run_scores, fin_scores, goes_on_out, stream);
 }
 extern "C" int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int step, int32_t* tokens, int32_t* src_rows,
                                    float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
@@ -569,17 +784,13 @@ extern "C" int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, in
 
 extern "C" int rs_avsr_search_finish_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                           int32_t* sequences, int32_t* lengths, float* scores, void* stream) {
-    if (!ctx) return RS_EINVAL;
-    SearchPtrs p;
-    Opts op;
-    const int rc = check_search(ctx, search, opts, B, 0, state, state_bytes, "rs_avsr_search_finish", &p, &op);
-    if (rc != RS_OK) return rc;
-    if (!sequences || !lengths) return rs_fail(ctx, RS_EINVAL, "rs_avsr_search_finish: null pointer");
-    hipLaunchKernelGGL(avsr_search_finish_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p, B, search->beams, 1 + search->max_new_tokens,
-                       search->greedy ? 1 : 0, op.o.num_return_sequences, sequences, lengths, scores);
-    RS_CHECK_LAUNCH(ctx, "avsr search finish");
-    RS_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
-    return RS_OK;
+    return search_finish(ctx, search, opts, nullptr, B, state, state_bytes, sequences, lengths, scores, stream);
+}
+extern "C" int rs_avsr_search_finish_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
+                                            int32_t* sequences, int32_t* lengths, float* scores, float* token_scores, float* token_lse, int32_t* beam_indices,
+                                            int32_t* steps_run, void* stream) {
+    const ScoredOut so{token_scores, token_lse, beam_indices, steps_run};
+    return search_finish(ctx, search, opts, &so, B, state, state_bytes, sequences, lengths, scores, stream);
 }
 extern "C" int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int32_t* sequences, int32_t* lengths,
                                      float* scores, void* stream) {
@@ -610,29 +821,41 @@ struct StopWatch {              // pinned words the go[] entries are copied to, 
         if (words) (void)hipHostFree(words);
     }
 };
-}  // namespace
 
-extern "C" size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts) {
+size_t generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts, bool rec) {
     if (!rs_avsr_dims_of(ctx) || B <= 0 || T <= 0 || beams < 1 || beams > MAXK || max_len < 2 || !opts_ok_for_bytes(opts, beams)) return 0;
     Opts op;
+    op.rec = rec;
     if (opts) op.o = *opts;
     rs_arena a;
     gen_plan(ctx, B, T, beams, max_len, op, a);
     return a.bytes() + GEN_SLACK;
 }
+}  // namespace
+
+extern "C" size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts) {
+    return generate_state_bytes(ctx, B, T, beams, max_len, opts, false);
+}
+extern "C" size_t rs_avsr_generate_state_bytes_scored(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts) {
+    return generate_state_bytes(ctx, B, T, beams, max_len, opts, true);
+}
 extern "C" size_t rs_avsr_generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
     return rs_avsr_generate_state_bytes_opts(ctx, B, T, beams, max_len, nullptr);
 }
 
-extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
-                                     const rs_avsr_search_opts* opts, int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes,
-                                     void* stream) {
+namespace {
+// so null: nothing is recorded (the plain and _opts forms)
+int generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search, const rs_avsr_search_opts* opts,
+             const ScoredOut* so, float* step_scores, int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream) {
     if (!ctx) return RS_EINVAL;
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
     if (!d) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: defined for an avsr context (rs_avsr_create) only");
     if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_generate");
-    if (!search || !enc || !padding_mask || !sequences || !lengths || !state || T <= 0) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: bad argument");
+    if (!search || !enc || !padding_mask || !sequences || !lengths || !state || T <= 0 || (so && !scored_out_ok(search, *so)))
+        return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: bad argument");
+    const bool rec = so != nullptr;
     Opts op;
+    op.rec = rec;
     int rc = check_search_args(ctx, search, opts, B, d->vocab_size, state, "rs_avsr_generate", &op);
     if (rc != RS_OK) return rc;
     const int K = search->beams, max_len = 1 + search->max_new_tokens;
@@ -653,13 +876,13 @@ extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float*
 
     rc = rs_avsr_decoder_begin(ctx, enc, B, T, K, max_len, dec_state, dec_bytes, stream);
     if (rc != RS_OK) return rc;
-    rc = rs_avsr_search_begin_opts(ctx, search, opts, B, d->vocab_size, s_state, s_bytes, stream);
+    rc = search_begin(ctx, search, opts, rec, B, d->vocab_size, s_state, s_bytes, stream);
     if (rc != RS_OK) return rc;
     for (int step = 0; step < search->max_new_tokens; ++step) {
         // greedy rows keep their caches (no re-parenting); beam rows are re-parented by the rows the last selection wrote
         rc = rs_avsr_decoder_step(ctx, p.tok, greedy ? nullptr : p.src, step, padding_mask, B, T, K, max_len, logits, dec_state, dec_bytes, stream);
         if (rc != RS_OK) return rc;
-        rc = rs_avsr_search_step_opts(ctx, logits, step, search, opts, B, d->vocab_size, s_state, s_bytes, stream);
+        rc = search_step(ctx, logits, step, search, opts, rec, step_scores, B, d->vocab_size, s_state, s_bytes, stream);
         if (rc != RS_OK) return rc;
         RS_HIP(ctx, hipMemcpyAsync(sw.words + step + 1, p.go + step + 1, 4, hipMemcpyDeviceToHost, s));
         if (two_words) RS_HIP(ctx, hipMemcpyAsync(sw.words + max_len + 1 + step + 1, p.go2 + step + 1, 4, hipMemcpyDeviceToHost, s));
@@ -670,7 +893,21 @@ extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float*
             if (!goes_on(greedy, (uint32_t)sw.words[e + 1]) || (two_words && sw.words[max_len + 1 + e + 1] == 0)) break;
         }
     }
-    return rs_avsr_search_finish_opts(ctx, search, opts, B, s_state, s_bytes, sequences, lengths, scores, stream);
+    return search_finish(ctx, search, opts, so, B, s_state, s_bytes, sequences, lengths, scores, stream);
+}
+}  // namespace
+
+extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
+                                     const rs_avsr_search_opts* opts, int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes,
+                                     void* stream) {
+    return generate(ctx, enc, padding_mask, B, T, search, opts, nullptr, nullptr, sequences, lengths, scores, state, state_bytes, stream);
+}
+extern "C" int rs_avsr_generate_scored(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
+                                       const rs_avsr_search_opts* opts, float* step_scores, int32_t* sequences, int32_t* lengths, float* scores,
+                                       float* token_scores, float* token_lse, int32_t* beam_indices, int32_t* steps_run, void* state, size_t state_bytes,
+                                       void* stream) {
+    const ScoredOut so{token_scores, token_lse, beam_indices, steps_run};
+    return generate(ctx, enc, padding_mask, B, T, search, opts, &so, step_scores, sequences, lengths, scores, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search, int32_t* sequences,
                                 int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream) {

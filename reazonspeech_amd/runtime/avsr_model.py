@@ -155,11 +155,14 @@ class AvsrDevice:
         return capi.RsAvsrSearchOpts(float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), es[early_stopping],
                                      int(num_return_sequences))
 
-    def generate(self, enc, padding_mask, beams, max_new_tokens, greedy, length_penalty=1.0, **opts):
+    def generate(self, enc, padding_mask, beams, max_new_tokens, greedy, length_penalty=1.0, record=False, dump_scores=False, **opts):
         """rs_avsr_generate_opts (csrc/k_avsr_search.hip): decoder steps and the search of every token on the device, one 4-byte stop
         word read per step (two with early_stopping=True).  enc float32 [B][T][d] on the device -> (sequences int64 [B * n][L] trimmed to
         the longest result, scores float32 [B * n]), both on the CPU, n = num_return_sequences.  opts: search_opts' keywords; without any
-        the call is rs_avsr_generate's.  No torch kernel runs here: torch allocates, the library computes, the results are copied out."""
+        the call is rs_avsr_generate's.  No torch kernel runs here: torch allocates, the library computes, the results are copied out.
+        record=True (rs_avsr_generate_scored) -> (sequences, scores, rec) with rec a dict of CPU arrays, W = the sequences' width - 1:
+        token_scores / token_lse float32 [B * n][W], beam_indices int32 [B * n][W] (None for greedy), lengths int32 [B * n], steps (the
+        steps the search ran) and, with dump_scores=True, step_scores float32 [steps][B * beams][vocab] (every step's processed rows)."""
         if beams > self.MAX_DEVICE_BEAMS:
             raise ValueError(f"search='device': num_beams={beams} exceeds the device search's limit of {self.MAX_DEVICE_BEAMS} (use search='host')")
         lib, h = self.ctx.lib, self.ctx._h
@@ -173,7 +176,8 @@ class AvsrDevice:
         enc = enc.contiguous()
         mask = self._dev(padding_mask)
         with torch.cuda.device(self.device):
-            need = int(lib.rs_avsr_generate_state_bytes_opts(h, B, T, int(beams), max_len, ctypes.byref(so)))
+            state_bytes = lib.rs_avsr_generate_state_bytes_scored if record else lib.rs_avsr_generate_state_bytes_opts
+            need = int(state_bytes(h, B, T, int(beams), max_len, ctypes.byref(so)))
             if need == 0:
                 raise ValueError(f"search='device': invalid arguments (beams {beams}, max_new_tokens {max_new_tokens}, options {opts})")
             if self._gen_state is None or self._gen_state.numel() < need:
@@ -182,8 +186,24 @@ class AvsrDevice:
             seq = torch.empty((B * n, max_len), dtype=torch.int32, device=self.device)
             lens = torch.empty((B * n,), dtype=torch.int32, device=self.device)
             scores = torch.empty((B * n,), dtype=torch.float32, device=self.device)
-            self.ctx.check(lib.rs_avsr_generate_opts(h, capi._ptr(enc), capi._ptr(mask), B, T, ctypes.byref(sp), ctypes.byref(so), capi._ptr(seq),
-                                                     capi._ptr(lens), capi._ptr(scores), capi._ptr(self._gen_state), self._gen_state.numel(),
-                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            seq, lens, scores = seq.cpu(), lens.cpu(), scores.cpu()
-        return seq[:, :max(1, int(lens.max()))].numpy().astype(np.int64), scores.numpy()
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if not record:
+                self.ctx.check(lib.rs_avsr_generate_opts(h, capi._ptr(enc), capi._ptr(mask), B, T, ctypes.byref(sp), ctypes.byref(so), capi._ptr(seq),
+                                                         capi._ptr(lens), capi._ptr(scores), capi._ptr(self._gen_state), self._gen_state.numel(), stream))
+                seq, lens, scores = seq.cpu(), lens.cpu(), scores.cpu()
+                return seq[:, :max(1, int(lens.max()))].numpy().astype(np.int64), scores.numpy()
+            N, V = int(max_new_tokens), self.cfg.vocab_size
+            ts = torch.empty((B * n, N), dtype=torch.float32, device=self.device)
+            tl = torch.empty((B * n, N), dtype=torch.float32, device=self.device)
+            bi = None if greedy else torch.empty((B * n, N), dtype=torch.int32, device=self.device)
+            steps = torch.zeros((1,), dtype=torch.int32, device=self.device)
+            dump = torch.empty((N, B * int(beams), (V + 3) // 4 * 4), dtype=torch.float32, device=self.device) if dump_scores else None
+            self.ctx.check(lib.rs_avsr_generate_scored(h, capi._ptr(enc), capi._ptr(mask), B, T, ctypes.byref(sp), ctypes.byref(so), capi._ptr(dump),
+                                                       capi._ptr(seq), capi._ptr(lens), capi._ptr(scores), capi._ptr(ts), capi._ptr(tl), capi._ptr(bi),
+                                                       capi._ptr(steps), capi._ptr(self._gen_state), self._gen_state.numel(), stream))
+            seq, lens, scores, n_steps = seq.cpu(), lens.cpu(), scores.cpu(), int(steps.cpu()[0])
+            L = max(1, int(lens.max()))
+            rec = {"token_scores": ts.cpu().numpy()[:, :L - 1], "token_lse": tl.cpu().numpy()[:, :L - 1],
+                   "beam_indices": None if bi is None else bi.cpu().numpy()[:, :L - 1], "lengths": lens.numpy(), "steps": n_steps,
+                   "step_scores": None if dump is None else dump[:n_steps, :, :V].cpu().numpy()}
+        return seq[:, :L].numpy().astype(np.int64), scores.numpy(), rec

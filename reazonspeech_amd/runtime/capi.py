@@ -44,6 +44,8 @@ EXPORTS = [
     "rs_avsr_search_finish", "rs_avsr_generate_state_bytes", "rs_avsr_generate",
     "rs_avsr_search_state_bytes_opts", "rs_avsr_search_begin_opts", "rs_avsr_search_step_opts", "rs_avsr_search_peek_opts",
     "rs_avsr_search_finish_opts", "rs_avsr_generate_state_bytes_opts", "rs_avsr_generate_opts",
+    "rs_avsr_search_state_bytes_scored", "rs_avsr_search_begin_scored", "rs_avsr_search_step_scored", "rs_avsr_search_peek_scored",
+    "rs_avsr_search_finish_scored", "rs_avsr_generate_state_bytes_scored", "rs_avsr_generate_scored",
     "rs_ctc_align_workspace_bytes", "rs_ctc_align", "rs_ctc_find_blank",
     "rs_resample",
     "rs_avsr_logfbank", "rs_avsr_pixels",
@@ -274,6 +276,16 @@ def load():
     lib.rs_avsr_generate_state_bytes_opts.argtypes = [vp, c_int, c_int, c_int, c_int, op]
     lib.rs_avsr_generate_state_bytes_opts.restype = c_size_t
     lib.rs_avsr_generate_opts.argtypes = [vp, vp, vp, c_int, c_int, sp, op, vp, vp, vp, vp, c_size_t, vp]
+    # the _scored forms: the _opts arguments plus step_scores (step, generate) and token_scores, token_lse, beam_indices, steps_run (finish, generate)
+    lib.rs_avsr_search_state_bytes_scored.argtypes = lib.rs_avsr_search_state_bytes_opts.argtypes
+    lib.rs_avsr_search_state_bytes_scored.restype = c_size_t
+    lib.rs_avsr_search_begin_scored.argtypes = lib.rs_avsr_search_begin_opts.argtypes
+    lib.rs_avsr_search_step_scored.argtypes = [vp, vp, c_int, sp, op, vp, c_int, c_int, vp, c_size_t, vp]
+    lib.rs_avsr_search_peek_scored.argtypes = lib.rs_avsr_search_peek_opts.argtypes
+    lib.rs_avsr_search_finish_scored.argtypes = [vp, sp, op, c_int, vp, c_size_t, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rs_avsr_generate_state_bytes_scored.argtypes = lib.rs_avsr_generate_state_bytes_opts.argtypes
+    lib.rs_avsr_generate_state_bytes_scored.restype = c_size_t
+    lib.rs_avsr_generate_scored.argtypes = [vp, vp, vp, c_int, c_int, sp, op, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, vp]
     lib.rs_ctc_align_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
     lib.rs_ctc_align_workspace_bytes.restype = c_size_t
     lib.rs_ctc_align.argtypes = [vp, vp, c_int, vp, c_int, c_int, vp, vp, c_int, c_int, c_int, vp, vp, vp, c_size_t, vp]
