@@ -872,7 +872,7 @@ int launch_attention_hd(rs_ctx* ctx, AttnParams& p, int B, int T, hipStream_t s)
     // algorithmic: ac + bd + pv = 3 * 2*T*T*HD per (b,h)
     const double flops = (double)B * dm.n_heads * 3.0 * 2.0 * T * (double)T * HD;
     const double bytes = (double)B * T * dm.d_model * 2.0 * 4.0;
-    rs_prof_begin(ctx, RS_PROF_ATTN, s, flops, bytes);
+    rs_prof_scope prof(ctx, RS_PROF_ATTN, s, flops, bytes);
     p.trace = HD == 128 ? g_attn_trace : nullptr;
     const bool window = p.att_left >= 0 || p.att_right >= 0;
     // Persistent launch of the staged kernel ($RS_ATTN_PERSIST=1; off): as many workgroups as the chip holds at once, each
@@ -903,9 +903,9 @@ int launch_attention_hd(rs_ctx* ctx, AttnParams& p, int B, int T, hipStream_t s)
             const size_t lds_s = (size_t)NSLOT * S::SLOT + (size_t)NW * S_SCR;
             const int dbg = stream >> 4;
             auto kern = dbg ? relpos_attention_stream_kernel<HD, NW, NSLOT, WPE, true> : relpos_attention_stream_kernel<HD, NW, NSLOT, WPE, false>;
-            if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)kern, (int)lds_s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_ATTN, s); return rc; }
+            if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)kern, (int)lds_s); rc != RS_OK) return rc;
             hipLaunchKernelGGL(kern, dim3(8 * ((n_items + 7) / 8)), dim3(64 * NW), lds_s, s, p, n_groups, dm.n_heads, n_items, dbg);
-            rs_prof_end(ctx, RS_PROF_ATTN, s);
+            prof.end();
             RS_CHECK_LAUNCH(ctx, "relpos_attention (streaming)");
             return RS_OK;
         }
@@ -932,7 +932,7 @@ int launch_attention_hd(rs_ctx* ctx, AttnParams& p, int B, int T, hipStream_t s)
             else if (kbc == 3 && nw2 >= 2) go(relpos_attention_kernel<HD, false, false, 3>, relpos_attention_kernel<HD, false, false, 3, true>, 3);
             else if (kbc == 4 && nw2 >= 2) go(relpos_attention_kernel<HD, false, false, 4>, relpos_attention_kernel<HD, false, false, 4, true>, 4);
             else if (nw2 == 1) go(relpos_attention_kernel<HD, false, false, 2>, relpos_attention_kernel<HD, false, false, 2, true>, 2);
-            rs_prof_end(ctx, RS_PROF_ATTN, s);
+            prof.end();
             if (rc != RS_OK) return rc == RS_EINVAL ? rs_fail(ctx, RS_EINVAL, "attention: $RS_ATTN64 geometry %d,%d is not built", kbc, nwmax) : rc;
             RS_CHECK_LAUNCH(ctx, "relpos_attention (head_dim 64)");
             return RS_OK;
@@ -942,10 +942,10 @@ int launch_attention_hd(rs_ctx* ctx, AttnParams& p, int B, int T, hipStream_t s)
     else if (p.trace) {
         if constexpr (HD == 128) hipLaunchKernelGGL((relpos_attention_kernel<HD, true, false>), grid, block, lds, s, p);
     } else if (persist_grid(grid, lds, 64 * nw)) {
-        if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)relpos_attention_kernel<HD, false, false, 0, true>, (int)lds); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_ATTN, s); return rc; }
+        if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)relpos_attention_kernel<HD, false, false, 0, true>, (int)lds); rc != RS_OK) return rc;
         hipLaunchKernelGGL((relpos_attention_kernel<HD, false, false, 0, true>), dim3(resident), block, lds, s, p);
     } else hipLaunchKernelGGL((relpos_attention_kernel<HD, false, false>), grid, block, lds, s, p);
-    rs_prof_end(ctx, RS_PROF_ATTN, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "relpos_attention");
     return RS_OK;
 }

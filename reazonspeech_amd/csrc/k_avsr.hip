@@ -811,13 +811,13 @@ extern "C" int rs_avsr_encoder_forward(rs_ctx* ctx, const float* input_values, c
     auto blocks1d = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
     if (pixel_values) {
         // ---- video: Conv3d + BN + PReLU, max-pool, ResNet-18 trunk, average pool, projection
-        rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 2.0 * N * pl.H1 * pl.H1 * 64 * 245.0, 0.0);
+        rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, 2.0 * N * pl.H1 * pl.H1 * 64 * 245.0, 0.0);
         hipLaunchKernelGGL(avsr_conv3d_kernel, dim3(pl.H1, T, B), dim3(256), 0, s, pixel_values, T, H, H, k.conv3d_w, k.bn0_a, k.bn0_b, k.prelu0, a0);
         {
             const size_t total = N * pl.H2 * pl.H2 * 64;
             hipLaunchKernelGGL(avsr_maxpool_kernel, blocks1d(total), dim3(256), 0, s, a0, pl.H1, pl.H1, 64, pl.H2, pl.H2, total, x);
         }
-        rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+        prof.end();
         RS_CHECK_LAUNCH(ctx, "avsr video front-end");
         int hw = pl.H2;
         float *cur = x, *o1 = y, *o2 = z;

@@ -202,14 +202,14 @@ int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* en
     const size_t lds = (size_t)2 * cap * sizeof(float);
     rs_arena arena(ws);                                                  // (rs_ctc_align compared the size with the query's)
     uint8_t* dec = align_layout(B, tp_max, c_max, arena);
-    rs_prof_begin(ctx, RS_PROF_DECODE, s, (double)B * tp_max * c_max * (3.0 * S + 2.0), (double)B * tp_max * c_max * (4.0 * S + 1.0));
+    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, (double)B * tp_max * c_max * (3.0 * S + 2.0), (double)B * tp_max * c_max * (4.0 * S + 1.0));
 #define RS_ALIGN_ARGS probs, ld, enc_lens, tp_max, gt, gt_lens, c_max, S, blank, cap, dec, frames, status
     if (c_max <= ALIGN_THREADS) hipLaunchKernelGGL(ctc_align_kernel<1>, dim3(B), dim3(ALIGN_THREADS), lds, s, RS_ALIGN_ARGS);
     else if (c_max <= 2 * ALIGN_THREADS) hipLaunchKernelGGL(ctc_align_kernel<2>, dim3(B), dim3(ALIGN_THREADS), lds, s, RS_ALIGN_ARGS);
     else if (c_max <= 4 * ALIGN_THREADS) hipLaunchKernelGGL(ctc_align_kernel<4>, dim3(B), dim3(ALIGN_THREADS), lds, s, RS_ALIGN_ARGS);
     else hipLaunchKernelGGL(ctc_align_kernel<0>, dim3(B), dim3(ALIGN_THREADS), lds, s, RS_ALIGN_ARGS);
 #undef RS_ALIGN_ARGS
-    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "ctc_align");
     return RS_OK;
 }

@@ -100,10 +100,10 @@ int rs_launch_sub2d_conv0(rs_ctx* ctx, const float* feats, const int32_t* lens1,
     const rs_dims& d = ctx->d;
     const int C = d.sub_channels;
     if (d.n_mels > 128 || 2 * (F1 - 1) + 2 >= d.n_mels + 1) return rs_fail(ctx, RS_EINVAL, "conv2d subsampling: n_mels %d / F1 %d", d.n_mels, F1);
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, (double)Bc * T1 * F1 * C * 18.0, (double)Bc * (t_max * d.n_mels * 4.0 + (double)T1 * F1 * C * 2.0));
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)Bc * T1 * F1 * C * 18.0, (double)Bc * (t_max * d.n_mels * 4.0 + (double)T1 * F1 * C * 2.0));
     hipLaunchKernelGGL(sub2d_conv0_kernel<uint16_t>, dim3(T1, Bc), dim3(256), 0, s, feats, lens1, b0, t_max, d.n_mels, T1, F1, C,
                        ctx->sub_conv0_w, ctx->sub_conv0_b, out);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "sub2d_conv0");
     return RS_OK;
 }
@@ -113,10 +113,10 @@ int rs_launch_sub2d_conv0_f32(rs_ctx* ctx, const float* feats, const int32_t* le
     const rs_dims& d = ctx->d;
     const int C = d.sub_channels;
     if (d.n_mels > 128 || 2 * (F1 - 1) + 2 >= d.n_mels + 1) return rs_fail(ctx, RS_EINVAL, "conv2d subsampling: n_mels %d / F1 %d", d.n_mels, F1);
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, (double)Bc * T1 * F1 * C * 18.0, (double)Bc * (t_max * d.n_mels * 4.0 + (double)T1 * F1 * C * 4.0));
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)Bc * T1 * F1 * C * 18.0, (double)Bc * (t_max * d.n_mels * 4.0 + (double)T1 * F1 * C * 4.0));
     hipLaunchKernelGGL(sub2d_conv0_kernel<float>, dim3(T1, Bc), dim3(256), 0, s, feats, lens1, b0, t_max, d.n_mels, T1, F1, C,
                        ctx->sub_conv0_w, ctx->sub_conv0_b, out);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "sub2d_conv0_f32");
     return RS_OK;
 }
@@ -125,10 +125,10 @@ int rs_launch_im2col3x3s2(rs_ctx* ctx, const uint16_t* in, int Bc, int T1, int F
     const int C = ctx->d.sub_channels;
     if (C % 8) return rs_fail(ctx, RS_EINVAL, "im2col: channels %d must be a multiple of 8", C);
     if ((long long)Bc * T2 > 65535LL) return rs_fail(ctx, RS_EINVAL, "im2col: chunk of %d x %d rows exceeds the grid", Bc, T2);
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, (double)Bc * T2 * F2 * 9.0 * C * 2.0 * 2.0);
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, 0.0, (double)Bc * T2 * F2 * 9.0 * C * 2.0 * 2.0);
     hipLaunchKernelGGL(im2col3x3s2_kernel, dim3(F2, Bc * T2), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), T1, F1, T2, F2, C / 8,
                        reinterpret_cast<uint4*>(out));
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "im2col3x3s2");
     return RS_OK;
 }
@@ -137,19 +137,19 @@ int rs_launch_im2col3x3s2_f32(rs_ctx* ctx, const float* in, int Bc, int T1, int 
     const int C = ctx->d.sub_channels;
     if (C % 4) return rs_fail(ctx, RS_EINVAL, "im2col: channels %d must be a multiple of 4", C);
     if ((long long)Bc * T2 > 65535LL) return rs_fail(ctx, RS_EINVAL, "im2col: chunk of %d x %d rows exceeds the grid", Bc, T2);
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, (double)Bc * T2 * F2 * 9.0 * C * 4.0 * 2.0);
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, 0.0, (double)Bc * T2 * F2 * 9.0 * C * 4.0 * 2.0);
     hipLaunchKernelGGL(im2col3x3s2_kernel, dim3(F2, Bc * T2), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), T1, F1, T2, F2, C / 4,
                        reinterpret_cast<uint4*>(out));
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "im2col3x3s2_f32");
     return RS_OK;
 }
 
 int rs_launch_ctc_softmax(rs_ctx* ctx, float* logits, int M, int V, int ld, int blank, float* blank_out, hipStream_t s) {
     if (M <= 0) return RS_OK;
-    rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, 4.0 * M * V, 8.0 * M * V);
+    rs_prof_scope prof(ctx, RS_PROF_ELEMENTWISE, s, 4.0 * M * V, 8.0 * M * V);
     hipLaunchKernelGGL(ctc_softmax_kernel, dim3((M + 3) / 4), dim3(256), 0, s, logits, M, V, ld, blank, blank_out);
-    rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "ctc_softmax");
     return RS_OK;
 }

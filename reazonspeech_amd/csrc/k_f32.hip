@@ -733,10 +733,10 @@ int rs_launch_gemm_f32(rs_ctx* ctx, const float* A, int lda, const float* W, int
         return rs_fail(ctx, RS_EINVAL, "gemm_f32: row mask without lengths");
     GemmF32 p{A, W, out, bias, residual, mask_lens, lda, ldw, ldc, M, N, K, flags, alpha, mask_rows_per_step, mask_steps, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
     const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT), block(256);
-    rs_prof_begin(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
+    rs_prof_scope prof(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
     if (ctx->gemm_f32_x3) hipLaunchKernelGGL((gemm_f32_kernel<false, false, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, s, p);
-    rs_prof_end(ctx, RS_PROF_GEMM, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "gemm_f32");
     return RS_OK;
 }
@@ -757,7 +757,7 @@ int rs_launch_conv3x3_f32(rs_ctx* ctx, const float* in, int n_img, int H, int Wd
               H, Wd, C, OH, OW, stride, bn_scale, bn_shift, prelu};
     const bool n64 = Cout <= 64;
     const dim3 grid((Cout + (n64 ? 64 : GT) - 1) / (n64 ? 64 : GT), (unsigned)((rows + GT - 1) / GT)), block(256);
-    rs_prof_begin(ctx, RS_PROF_GEMM, s, 2.0 * rows * (double)Cout * K, 4.0 * ((double)n_img * H * Wd * C + (double)Cout * K + 2.0 * rows * Cout));
+    rs_prof_scope prof(ctx, RS_PROF_GEMM, s, 2.0 * rows * (double)Cout * K, 4.0 * ((double)n_img * H * Wd * C + (double)Cout * K + 2.0 * rows * Cout));
     if (ctx->gemm_f32_x3) {
         if (one_by_one) {
             if (n64) hipLaunchKernelGGL((gemm_f32_kernel<false, true, true>), grid, block, 0, s, p);
@@ -770,7 +770,7 @@ int rs_launch_conv3x3_f32(rs_ctx* ctx, const float* in, int n_img, int H, int Wd
         else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, s, p);
     } else if (n64) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, s, p);
-    rs_prof_end(ctx, RS_PROF_GEMM, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "conv3x3_f32");
     return RS_OK;
 }
@@ -783,7 +783,7 @@ int rs_launch_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, con
     if (hd > 256) return rs_fail(ctx, RS_EINVAL, "attention_f32: head_dim %d > 256", hd);
     const dim3 grid((T + 3) / 4, dm.n_heads, B), block(256);
     const float scale = 1.0f / sqrtf((float)hd);
-    rs_prof_begin(ctx, RS_PROF_ATTN, s, (double)B * dm.n_heads * 3.0 * 2.0 * T * (double)T * hd, (double)B * T * dm.d_model * 4.0 * 4.0);
+    rs_prof_scope prof(ctx, RS_PROF_ATTN, s, (double)B * dm.n_heads * 3.0 * 2.0 * T * (double)T * hd, (double)B * T * dm.d_model * 4.0 * 4.0);
 #define RS_ATT_KEYS(NCH)                                                                                                 \
     hipLaunchKernelGGL((attention_f32_keys_kernel<NCH>), grid, block, 0, s, qkv, pos, bias_u, bias_v, lens, out, T, dm.d_model, hd, \
                        dm.att_left, dm.att_right, dm.n_global, scale)
@@ -806,7 +806,7 @@ int rs_launch_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, con
     else RS_ATT_CASE(4);
 #undef RS_ATT_CASE
 #undef RS_ATT_KEYS
-    rs_prof_end(ctx, RS_PROF_ATTN, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "attention_f32");
     return RS_OK;
 }
@@ -816,9 +816,9 @@ int rs_launch_glu_dwconv_f32(rs_ctx* ctx, const float* x, const float* w, const 
     if (B <= 0 || T <= 0) return RS_OK;
     if (k < 1 || !(k & 1)) return rs_fail(ctx, RS_EINVAL, "glu_dwconv_f32: kernel size %d unsupported", k);
     const dim3 grid((d + 255) / 256, T, B), block(256);
-    rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), (double)B * T * d * 12.0);
+    rs_prof_scope prof(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), (double)B * T * d * 12.0);
     hipLaunchKernelGGL(glu_dwconv_silu_f32_kernel, grid, block, 0, s, x, w, b, lens, T, d, k, out);
-    rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "glu_dwconv_silu_f32");
     return RS_OK;
 }
@@ -834,7 +834,7 @@ int rs_launch_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, const float*
     if ((flags & RS_GEMM_RESIDUAL) && !residual) return rs_fail(ctx, RS_EINVAL, "gemm_f32 (skinny): residual flag without a residual");
     GemmF32 p{A, W, out, bias, residual, nullptr, lda, ldw, ldc, M, N, K, flags, 1.0f, 0, 0};
     const dim3 grid((N + 15) / 16), block(64 * SK_WAVES);
-    rs_prof_begin(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
+    rs_prof_scope prof(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
     switch ((M + 15) / 16) {                      // row tiles of 16: only as many as there are rows
         case 1: hipLaunchKernelGGL((gemm_f32_skinny_kernel<1>), grid, block, 0, s, p); break;
         case 2: hipLaunchKernelGGL((gemm_f32_skinny_kernel<2>), grid, block, 0, s, p); break;
@@ -844,7 +844,7 @@ int rs_launch_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, const float*
         case 6: hipLaunchKernelGGL((gemm_f32_skinny_kernel<6>), grid, block, 0, s, p); break;
         default: hipLaunchKernelGGL((gemm_f32_skinny_kernel<8>), grid, block, 0, s, p); break;
     }
-    rs_prof_end(ctx, RS_PROF_GEMM, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "gemm_f32_skinny");
     return RS_OK;
 }

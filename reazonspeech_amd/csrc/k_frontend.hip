@@ -262,7 +262,7 @@ int rs_launch_frontend(rs_ctx* ctx, const float* audio, const int32_t* lens, int
         RS_HIP(ctx, hipMemsetAsync(feats, 0, (size_t)B * t_max * d.n_mels * 4, s));
     }
     const double bytes = (double)B * ((double)t_max * d.hop_length * 4.0 + (double)t_max * d.n_mels * 4.0 * 3.0);
-    rs_prof_begin(ctx, RS_PROF_FRONTEND, s, (double)B * t_max * (5.0 * 512 * 9 + 3 * 257 + 2 * 600), bytes);
+    rs_prof_scope prof(ctx, RS_PROF_FRONTEND, s, (double)B * t_max * (5.0 * 512 * 9 + 3 * 257 + 2 * 600), bytes);
     hipLaunchKernelGGL(logmel_kernel, grid, block, 0, s, p);
     if (d.frontend_kind == 2) {
     } else if (d.frontend_kind == 1)
@@ -271,7 +271,7 @@ int rs_launch_frontend(rs_ctx* ctx, const float* audio, const int32_t* lens, int
     else
         hipLaunchKernelGGL(feat_normalize_kernel, dim3(B), dim3(1024), 0, s, raw, n_frames, t_max, d.n_mels, d.norm_eps,
                            feats);
-    rs_prof_end(ctx, RS_PROF_FRONTEND, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "frontend");
     return RS_OK;
 }

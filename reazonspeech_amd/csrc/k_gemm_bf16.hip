@@ -904,9 +904,8 @@ int rs_launch_gemm(rs_ctx* ctx, const rs_gemm_args& a, hipStream_t s) {
                          (double)a.M * a.N * ((a.flags & RS_GEMM_OUT_F32) ? 4 : ((a.flags & RS_GEMM_GLU) ? 1 : 2)) +
                          ((a.flags & RS_GEMM_RESIDUAL) ? (double)a.M * a.N * 4 : 0.0);   // residual is read once
     ctx->prof_tag[0] = a.M; ctx->prof_tag[1] = a.N; ctx->prof_tag[2] = a.K; ctx->prof_tag[3] = a.flags;
-    rs_prof_begin(ctx, RS_PROF_GEMM, s, flops, bytes);
-    int rc = RS_OK;
-    for (size_t r0 = 0; r0 < (size_t)a.M && rc == RS_OK; r0 += max_rows) {
+    rs_prof_scope prof(ctx, RS_PROF_GEMM, s, flops, bytes);
+    for (size_t r0 = 0; r0 < (size_t)a.M; r0 += max_rows) {
         GemmParams p;
         const size_t rows = (size_t)a.M - r0 < max_rows ? (size_t)a.M - r0 : max_rows;
         p.A = a.A + r0 * a.lda; p.W = a.W;
@@ -927,10 +926,9 @@ int rs_launch_gemm(rs_ctx* ctx, const rs_gemm_args& a, hipStream_t s) {
             p.cv_f_bytes = (unsigned)(2 * a.conv_C * 2);
             p.cv_seg_bytes = (unsigned)((size_t)a.conv_F1 * a.conv_C * 2);
         }
-        rc = launch_rows(ctx, p, bm, s);
+        if (int rc = launch_rows(ctx, p, bm, s); rc != RS_OK) return rc;
     }
-    rs_prof_end(ctx, RS_PROF_GEMM, s);      // paired with rs_prof_begin on every path
-    if (rc != RS_OK) return rc;
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "gemm_smf16");
     return RS_OK;
 }

@@ -249,9 +249,9 @@ int rs_launch_gemm_i8q(rs_ctx* ctx, const float* A, int lda, int group, const fl
     if (!A || !W || !colsum || !wq || !qp || !out) return rs_fail(ctx, RS_EINVAL, "gemm_i8q: null pointer");
     GemmI8 p{A, W, colsum, wq, qp, out, bias, residual, lda, ldw, ldc, M, N, K, group, flags};
     const dim3 grid((N + IBN - 1) / IBN, (M + IBM - 1) / IBM), block(256);
-    rs_prof_begin(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * (double)M * K + (double)N * K + 4.0 * (double)M * N);
+    rs_prof_scope prof(ctx, RS_PROF_GEMM, s, 2.0 * M * (double)N * K, 4.0 * (double)M * K + (double)N * K + 4.0 * (double)M * N);
     hipLaunchKernelGGL(gemm_i8q_kernel, grid, block, 0, s, p);
-    rs_prof_end(ctx, RS_PROF_GEMM, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "gemm_i8q");
     return RS_OK;
 }

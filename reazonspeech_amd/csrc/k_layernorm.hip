@@ -452,13 +452,13 @@ int rs_launch_layernorm(rs_ctx* ctx, const float* x, const float* g, const float
     if (d % 256 || d > 2048) return rs_fail(ctx, RS_EINVAL, "layernorm: d=%d must be a multiple of 256, <= 2048", d);
     const dim3 grid((M + 3) / 4), block(256);
     const double bytes = (double)M * d * (4.0 + (out_bf16 ? 2.0 : 0.0) + (out_f32 ? 4.0 : 0.0));
-    rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, 8.0 * M * d, bytes);
+    rs_prof_scope prof(ctx, RS_PROF_ELEMENTWISE, s, 8.0 * M * d, bytes);
     switch (d / 256) {
 #define LN_CASE(NV) case NV: hipLaunchKernelGGL(layernorm_kernel<NV>, grid, block, 0, s, x, g, b, M, eps, out_bf16, out_f32); break;
         LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
 #undef LN_CASE
     }
-    rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "layernorm");
     return RS_OK;
 }
@@ -469,13 +469,13 @@ int rs_launch_layernorm2(rs_ctx* ctx, const float* x, const float* g1, const flo
     if (d % 256 || d > 2048) return rs_fail(ctx, RS_EINVAL, "layernorm: d=%d must be a multiple of 256, <= 2048", d);
     const dim3 grid((M + 3) / 4), block(256);
     if (!out_f32 && !stats) return rs_fail(ctx, RS_EINVAL, "layernorm2: neither the first norm's rows nor its statistics requested");
-    rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, 16.0 * M * d, (double)M * d * (out_f32 ? 10.0 : 6.0));
+    rs_prof_scope prof(ctx, RS_PROF_ELEMENTWISE, s, 16.0 * M * d, (double)M * d * (out_f32 ? 10.0 : 6.0));
     switch (d / 256) {
 #define LN_CASE(NV) case NV: hipLaunchKernelGGL(layernorm2_kernel<NV>, grid, block, 0, s, x, g1, b1, g2, b2, M, eps, out_f32, out_bf16, stats); break;
         LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
 #undef LN_CASE
     }
-    rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "layernorm2");
     return RS_OK;
 }
@@ -486,7 +486,7 @@ int rs_launch_dwconv_act(rs_ctx* ctx, const uint16_t* x, const float* w, const f
     if (d % 64) return rs_fail(ctx, RS_EINVAL, "dwconv: d=%d must be a multiple of 64", d);
     if (act < 0 || act > 1) return rs_fail(ctx, RS_EINVAL, "dwconv: unknown activation %d", act);
     const dim3 grid((T + 127) / 128, d / 64, B), block(256);
-    rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), (double)B * T * d * 4.0);
+    rs_prof_scope prof(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), (double)B * T * d * 4.0);
 #define RS_DW(KK)                                                                                              \
     case KK:                                                                                                   \
         if (act) hipLaunchKernelGGL((dwconv_act_kernel<KK, 1>), grid, block, 0, s, x, w, b, lens, T, d, out);  \
@@ -495,11 +495,10 @@ int rs_launch_dwconv_act(rs_ctx* ctx, const uint16_t* x, const float* w, const f
     switch (k) {
         RS_DW(7) RS_DW(15) RS_DW(31)
         default:
-            rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
             return rs_fail(ctx, RS_EINVAL, "dwconv: kernel size %d is not built (7, 15, 31)", k);
     }
 #undef RS_DW
-    rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "dwconv_act");
     return RS_OK;
 }
@@ -514,7 +513,7 @@ int rs_launch_glu_dwconv(rs_ctx* ctx, const uint16_t* x, int layout, const float
     const int glu_generic = rs_knob(RS_KNOB_GLU_GENERIC);
     if (layout == 2 && (k == 7 || k == 15 || k == 31) && glu_generic != 1) return rs_launch_dwconv_act(ctx, x, w, b, lens, B, T, d, k, 0, out, s);
     const double bytes = (double)B * T * d * ((layout == 2 ? 2.0 : 4.0) + 2.0);
-    rs_prof_begin(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), bytes);
+    rs_prof_scope prof(ctx, RS_PROF_ELEMENTWISE, s, (double)B * T * d * (2.0 * k + 12.0), bytes);
     if (k == 9 && glu_generic != 1) {
         // register-window fast path (the FastConformer kernel size); 48-frame tiles
         constexpr int R = 6, TTF = 8 * R;
@@ -522,7 +521,7 @@ int rs_launch_glu_dwconv(rs_ctx* ctx, const uint16_t* x, int layout, const float
         const size_t lds = (size_t)(TTF + 9 - 1) * CT * sizeof(float);
 #define RS_GLU_FAST(LY)                                                                                                   \
         do {                                                                                                              \
-            if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)glu_dwconv_silu_fast_kernel<9, R, LY>, (int)lds); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s); return rc; } \
+            if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)glu_dwconv_silu_fast_kernel<9, R, LY>, (int)lds); rc != RS_OK) return rc; \
             hipLaunchKernelGGL((glu_dwconv_silu_fast_kernel<9, R, LY>), grid, block, lds, s, x, w, b, lens, T, d, out);   \
         } while (0)
         if (layout == 0) RS_GLU_FAST(0);
@@ -535,7 +534,7 @@ int rs_launch_glu_dwconv(rs_ctx* ctx, const uint16_t* x, int layout, const float
         const size_t lds = (size_t)(TT + k - 1) * CT * sizeof(float);
         hipLaunchKernelGGL(glu_dwconv_silu_kernel, grid, block, lds, s, x, w, b, lens, T, d, k, layout, out);
     }
-    rs_prof_end(ctx, RS_PROF_ELEMENTWISE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "glu_dwconv_silu");
     return RS_OK;
 }

@@ -1021,31 +1021,29 @@ int ensure_decode_lds(rs_ctx* ctx) {
 
 }  // namespace
 
-// ---- launch helpers for the beam search (k_rnnt_alsd.hip); `st_ptr` points at a DecodeState over hypothesis rows ----
+// ---- launch helpers for the other drivers (declared in k_rnnt_common.h) ----
 int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s) {
     if (int rc = ensure_decode_lds(ctx); rc != RS_OK) return rc;
     launch_lstm_pred(ctx, *reinterpret_cast<const DecodeState*>(st_ptr), rows, rows, narrow_kernels_usable(ctx), s);
     return RS_OK;
 }
 
-// exact f32 joint logits of the rows on alive list (step & 1) -> st.zapprox [rows][64 * ceil(V / 64)]
 int rs_rnnt_launch_joint_logits(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int tp_max, int rows_per_utt,
                                 int step, hipStream_t s) {
     if (int rc = ensure_decode_lds(ctx); rc != RS_OK) return rc;
     const rs_dims& d = ctx->d;
-    const int nct = (d.n_logits + 63) / 64;
+    const int nct = rs_joint_zstride(d) / 64;
     hipLaunchKernelGGL(rnnt_tile_kernel<2>, dim3(joint_grid_x(nct, (rows + 31) / 32), (rows + 31) / 32), dim3(512), TILE_LDS, s,
                        *reinterpret_cast<const DecodeState*>(st_ptr), joint_enc, rows, tp_max, d.pred_layers, d.pred_hidden,
                        d.joint_hidden, d.n_logits, ctx->jout_w, ctx->jout_b, nct, step, rows_per_utt);
     return RS_OK;
 }
 
-// the same with indirect prediction vectors (st.g_off); `rows` = extent of the row space (the alive lists have that stride)
 int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
                                          int rows_per_utt, int step, hipStream_t s) {
     if (int rc = ensure_decode_lds(ctx); rc != RS_OK) return rc;
     const rs_dims& d = ctx->d;
-    const int nct = (d.n_logits + 63) / 64;
+    const int nct = rs_joint_zstride(d) / 64;
     const int rts = (rows_bound + 31) / 32 > 0 ? (rows_bound + 31) / 32 : 1;
     const DecodeState& st = *reinterpret_cast<const DecodeState*>(st_ptr);
     if (st.a_pre)
@@ -1078,13 +1076,12 @@ static void greedy_layout(const rs_ctx* ctx, int B, rs_arena& a, DecodeState& st
     st.a16 = a.take<uint16_t>(B * J); st.anorm = a.take<float>(B);     // screened joint
     st.zapprox = a.take<float>(B * Vpad);
 }
-constexpr size_t GREEDY_SLACK = 1024;
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B) {
     rs_arena a;
     DecodeState st{};
     greedy_layout(ctx, B, a, st);
-    return a.bytes() + GREEDY_SLACK;
+    return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int u_max,
@@ -1093,12 +1090,11 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
-    if (H % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "rnnt: pred_hidden/joint_hidden must be multiples of 128");
-    if (L < 1 || L > 4) return rs_fail(ctx, RS_EINVAL, "rnnt: 1..4 LSTM layers supported");
+    if (int rc = rs_rnnt_check_dims(ctx, "rnnt"); rc != RS_OK) return rc;
     rs_arena arena(workspace);
     DecodeState st{};
     greedy_layout(ctx, B, arena, st);
-    if (workspace_bytes < arena.bytes() + GREEDY_SLACK) return rs_fail(ctx, RS_EWORKSPACE, "rnnt: workspace too small");
+    if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK) return rs_fail(ctx, RS_EWORKSPACE, "rnnt: workspace too small");
     st.joint_act = d.joint_act;
     if (ctx->k2_conv_w) st.unk = ctx->k2 ? rs_k2_unk_id(ctx) : -1;
     const size_t state_bytes = (size_t)L * B * H * 4;
@@ -1111,7 +1107,7 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
     const bool narrow = narrow_kernels_usable(ctx);
     auto lstm_and_pred = [&](int rows_bound) { launch_lstm_pred(ctx, st, B, rows_bound, narrow, s); };
 
-    rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(st.h, 0, 2 * rs_align(state_bytes), s));   // h and c are adjacent
     RS_HIP(ctx, hipMemsetAsync(st.g, 0, (size_t)B * J * 4, s));
     hipLaunchKernelGGL(rnnt_init_kernel, dim3(1), dim3(256), 0, s, st, enc_lens, B, d.blank_id, n_ids);
@@ -1185,7 +1181,7 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
         finished = host_counters[2 + (steps & 1)] == 0;
         alive_bound = host_counters[2 + (steps & 1)];
     }
-    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    prof.end();
     if (rs_knob(RS_KNOB_DECODE_TRACE)) fprintf(stderr, "[decode trace] B=%d T'=%d: %d steps (screen %d, narrow %d, lookahead %d)\n", B, tp_max, steps, (int)screen, (int)narrow, (int)lookahead);
     if (host_counters[1]) return rs_fail(ctx, RS_EOVERFLOW, "rnnt: an utterance emitted more than u_max=%d tokens", u_max);
     if (!finished) return rs_fail(ctx, RS_ESTATE, "rnnt: decode did not finish in %d steps", max_steps);

@@ -19,10 +19,6 @@
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
 
-int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
-int rs_rnnt_launch_joint_logits(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int tp_max, int rows_per_utt,
-                                int step, hipStream_t s);
-
 namespace {
 
 constexpr int MAX_BEAM = 8;
@@ -160,8 +156,7 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             } else {
                 for (int v = lane; v < V; v += 64) sum = sum + rs_expf(zr[v] - m);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) sum = sum + __shfl_xor(sum, off, 64);
+            sum = wave_sum(sum);
             sum = __shfl(sum, 0, 64);
             const float lse = m + rs_logf(sum);
             const float hs = as.score[p][row];
@@ -378,12 +373,11 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, rs_arena& a, DecodeSt
     as.done = a.take<int32_t>(B);
     as.fin_y = a.take<int32_t>((size_t)B * cap); as.fin_al = a.take<int32_t>((size_t)B * cap);
     q.counters = a.take<int32_t>(16);
-    q.zapprox = a.take<float>(rows * (size_t)((d.n_logits + 63) / 64 * 64));
+    q.zapprox = a.take<float>(rows * (size_t)rs_joint_zstride(d));
     as.cap = cap;
     st[0] = st[1] = q;
     st[1].h = h1; st[1].c = c1; st[1].g = g1;
 }
-constexpr size_t ALSD_SLACK = 1024;
 
 }  // namespace
 
@@ -393,7 +387,7 @@ size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int
     DecodeState st[2];
     AlsdState as;
     alsd_layout(ctx, B, beam, cap, a, st, as);
-    return a.bytes() + ALSD_SLACK;
+    return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
@@ -402,8 +396,7 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
-    if (H % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "alsd: pred_hidden/joint_hidden must be multiples of 128");
-    if (L < 1 || L > 4) return rs_fail(ctx, RS_EINVAL, "alsd: 1..4 LSTM layers supported");
+    if (int rc = rs_rnnt_check_dims(ctx, "alsd"); rc != RS_OK) return rc;
     const int W = beam < V - 1 ? beam : V - 1;
     if (W < 1 || W > MAX_BEAM) return rs_fail(ctx, RS_EINVAL, "alsd: beam size must be 1..%d", MAX_BEAM);
     const int max_steps = tp_max + alsd_budget(tp_max, ratio, abs_len);      // >= every utterance's alignment length
@@ -412,19 +405,20 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     DecodeState st[2];
     AlsdState as;
     alsd_layout(ctx, B, W, cap, arena, st, as);
-    if (workspace_bytes < arena.bytes() + ALSD_SLACK)
-        return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, arena.bytes() + ALSD_SLACK);
+    if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     const int rows = B * W;
     float* const hset[2] = {st[0].h, st[1].h}; float* const cset[2] = {st[0].c, st[1].c}; float* const gset[2] = {st[0].g, st[1].g};
     int32_t* const counters = st[0].counters;
     float* const zbuf = st[0].zapprox;
-    const int zstride = (V + 63) / 64 * 64;
+    const int zstride = rs_joint_zstride(d);
+    const auto select = V <= 64 * 48 ? alsd_select_kernel<48> : alsd_select_kernel<0>;   // (48: the logits row fits a lane's registers)
 
-    rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * rs_align((size_t)L * rows * H * 4), s));   // h and c of set 0
     hipLaunchKernelGGL(alsd_init_kernel, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len);
     // start of sequence: blank token from zero state, slot 0 of every utterance (list built by the init kernel)
-    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) return rc;
     RS_CHECK_LAUNCH(ctx, "alsd init");
 
     const int CHUNK = 16;
@@ -434,21 +428,19 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     while (!finished && i <= max_steps) {
         for (int c = 0; c < CHUNK && i <= max_steps; ++c, ++i) {
             const int p = i & 1, pn = p ^ 1;
-            if (int rc = rs_rnnt_launch_joint_logits(ctx, &st[p], joint_enc, rows, tp_max, W, i, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
-            if (V <= 64 * 48) hipLaunchKernelGGL((alsd_select_kernel<48>), dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V,
-                               d.blank_id, i, ratio, abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores);
-            else hipLaunchKernelGGL((alsd_select_kernel<0>), dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V,
-                               d.blank_id, i, ratio, abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores);
+            if (int rc = rs_rnnt_launch_joint_logits(ctx, &st[p], joint_enc, rows, tp_max, W, i, s); rc != RS_OK) return rc;
+            hipLaunchKernelGGL(select, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio, abs_len,
+                               score_norm, merge, out_cap, ids, steps, n_ids, scores);
             hipLaunchKernelGGL(alsd_reorder_kernel, dim3(rows), dim3(256), 0, s, as, pn, W, rows, L, H, J, hset[p], cset[p],
                                gset[p], hset[pn], cset[pn], gset[pn]);
-            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[pn], rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[pn], rows, s); rc != RS_OK) return rc;
         }
         RS_CHECK_LAUNCH(ctx, "alsd step");
         RS_HIP(ctx, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, s));
         RS_HIP(ctx, hipStreamSynchronize(s));
         finished = hc[4] >= B;
     }
-    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    prof.end();
     if (!finished) return rs_fail(ctx, RS_ESTATE, "alsd: %d of %d utterances unfinished after %d alignment steps", B - hc[4], B, max_steps + 1);
     if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "alsd: a hypothesis has more than out_cap=%d labels", out_cap);
     return RS_OK;

@@ -36,9 +36,6 @@
 
 #include "k_rnnt_common.h"
 
-int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
-int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
-                                         int rows_per_utt, int step, hipStream_t s);
 
 namespace {
 
@@ -149,10 +146,7 @@ __global__ __launch_bounds__(256) void beam_act_kernel(DecodeState st, const flo
         t = t < Tp ? t : Tp - 1;
         const float4 a = reinterpret_cast<const float4*>(f + ((size_t)(row / rows_per_utt) * Tp + t) * J)[q];
         const float4 g = reinterpret_cast<const float4*>(st.g + st.g_off[row])[q];
-        float4 r;
-        if (st.joint_act) { r.x = rs_tanhf(a.x + g.x); r.y = rs_tanhf(a.y + g.y); r.z = rs_tanhf(a.z + g.z); r.w = rs_tanhf(a.w + g.w); }
-        else { r.x = fmaxf(a.x + g.x, 0.0f); r.y = fmaxf(a.y + g.y, 0.0f); r.z = fmaxf(a.z + g.z, 0.0f); r.w = fmaxf(a.w + g.w, 0.0f); }
-        reinterpret_cast<float4*>(a_pre + (size_t)row * J)[q] = r;
+        reinterpret_cast<float4*>(a_pre + (size_t)row * J)[q] = rs_joint_act4(a, g, st.joint_act);
     }
 }
 
@@ -650,7 +644,7 @@ BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max,
     bs.max_nodes = (tp_max > 0 ? tp_max : 1) * max_pops + 1;       // a pop adds at most one node
     bs.n_slots = 2 * max_pops + 1;                                   // zero state + survivors (<= max_pops) + evaluations of a frame (<= max_pops)
     bs.slot_floats = 2 * d.pred_layers * d.pred_hidden + d.joint_hidden;
-    p.zstride = (d.n_logits + 63) / 64 * 64;
+    p.zstride = rs_joint_zstride(d);
     int R = (beam + 12 + 3) / 4 * 4;                                 // a frame opens with >= beam survivors, usually a few more
     if (R > 64) R = 64;
     if (R > max_pops) R = max_pops;
@@ -700,7 +694,6 @@ BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max,
     p.rec_lds = (size_t)4 * (p.zstride + 256) * 4;
     return p;
 }
-constexpr size_t BEAM_SLACK = 1024;
 
 int clamp_pops(int beam, int max_pops) { return max_pops > 0 ? max_pops : 16 * beam; }
 
@@ -713,7 +706,7 @@ size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int
     BeamState bs;
     DecodeState st{};
     beam_layout(ctx, B, bm, beam_k, tp_max, clamp_pops(bm, max_pops), a, bs, st);
-    return a.bytes() + BEAM_SLACK;
+    return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
@@ -721,8 +714,7 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
                       void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
-    if (H % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "beam search: pred_hidden/joint_hidden must be multiples of 128");
-    if (L < 1 || L > 4) return rs_fail(ctx, RS_EINVAL, "beam search: 1..4 LSTM layers supported");
+    if (int rc = rs_rnnt_check_dims(ctx, "beam search"); rc != RS_OK) return rc;
     if (V < 2) return rs_fail(ctx, RS_EINVAL, "beam search: vocabulary of %d", V);
     const int bm = beam < V ? beam : V, beam_k = bm < V - 1 ? bm : V - 1;
     const int mp = clamp_pops(bm, max_pops);
@@ -732,8 +724,8 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     BeamState bs;
     DecodeState st{};
     const BeamPlan pl = beam_layout(ctx, B, bm, beam_k, tp_max, mp, arena, bs, st);
-    if (workspace_bytes < arena.bytes() + BEAM_SLACK)
-        return rs_fail(ctx, RS_EWORKSPACE, "beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + BEAM_SLACK);
+    if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     if (pl.step_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: beam %d x max_pops %d needs %zu bytes of LDS (> 150 KB): lower max_pops", bm, mp, pl.step_lds);
     if (pl.rec_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: vocabulary %d exceeds the record kernel's LDS", V);
     unsigned long long* const trace = bs.trace;
@@ -745,7 +737,7 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_step_kernel, (int)pl.step_lds); rc != RS_OK) return rc;
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_first_kernel, (int)pl.step_lds); rc != RS_OK) return rc;
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)record, (int)pl.rec_lds); rc != RS_OK) return rc;
-    rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(bs.t, 0, pl.zero_bytes, s));
     // slot 0 of every utterance: the zero state the search starts from
     RS_HIP(ctx, hipMemset2DAsync(bs.slots, (size_t)bs.n_slots * bs.slot_floats * 4, 0, (size_t)bs.slot_floats * 4, B, s));
@@ -767,12 +759,9 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     while (!finished && it < max_iters) {
         for (int c = 0; c < CHUNK; ++c, ++it) {
             const int step = (int)(it & 1);
-            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, B * bs.KS, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, B * bs.KS, s); rc != RS_OK) return rc;
             hipLaunchKernelGGL(beam_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, joint_enc, a_pre, pl.rows, tp_max, J, rpu, step);
-            if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, pl.rows, joint_rts * 32, tp_max, rpu, step, s); rc != RS_OK) {
-                rs_prof_end(ctx, RS_PROF_DECODE, s);
-                return rc;
-            }
+            if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, pl.rows, joint_rts * 32, tp_max, rpu, step, s); rc != RS_OK) return rc;
             hipLaunchKernelGGL(record, dim3(rec_blocks), dim3(256), pl.rec_lds, s, bs, st, st.zapprox, pl.zstride, pl.rows, rpu, V, d.blank_id,
                                step);
             hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), pl.step_lds, s, bs, st, enc_lens, B, L, H, J, bm, score_norm, out_cap,
@@ -783,7 +772,7 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
         RS_HIP(ctx, hipStreamSynchronize(s));
         finished = hf[0] >= B;
     }
-    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    prof.end();
     if (bs.trace) {                                                  // diagnostic: where the step kernel's workgroups spend their time
         unsigned long long tr[14];
         RS_HIP(ctx, hipMemcpy(tr, trace, sizeof tr, hipMemcpyDeviceToHost));

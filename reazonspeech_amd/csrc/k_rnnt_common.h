@@ -1,10 +1,32 @@
 // k_rnnt_common.h — pieces shared by the decode translation units (k_rnnt.hip: greedy, k_rnnt_alsd.hip / k_rnnt_beam.hip /
-// k_rnnt_mbs.hip: the beam searches).
-// Both are compiled with -ffp-contract=off.
+// k_rnnt_mbs.hip: the beam searches, k_rnnt_scores.hip: token log-probabilities).
+// All are compiled with -ffp-contract=off.
 #pragma once
 #include "rs_common.h"
 
+// ---- launch helpers of k_rnnt.hip for the other drivers; `st_ptr` points at a DecodeState over hypothesis rows ----
+int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
+// exact f32 joint logits of the rows on alive list (step & 1) -> st.zapprox [rows][rs_joint_zstride]
+int rs_rnnt_launch_joint_logits(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int tp_max, int rows_per_utt, int step, hipStream_t s);
+// the same with indirect prediction vectors (st.g_off) or given rows act(f + g) (st.a_pre); `rows` = extent of the row space (alive list stride)
+int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
+                                         int rows_per_utt, int step, hipStream_t s);
+
 namespace {
+
+// ---- host: what every driver sets up the same way -------------------------------------------------
+constexpr size_t RS_DECODE_SLACK = 1024;   // bytes every workspace query adds to its layout
+
+// row pitch (floats) of the exact joint logits: whole 64-column tiles (rnnt_tile_kernel writes n_ctiles * 64 columns)
+inline int rs_joint_zstride(const rs_dims& d) { return (d.n_logits + 63) / 64 * 64; }
+
+// the shapes the LSTM and tile kernels are built for; `what` names the driver in the message
+inline int rs_rnnt_check_dims(rs_ctx* ctx, const char* what) {
+    const rs_dims& d = ctx->d;
+    if (d.pred_hidden % 128 || d.joint_hidden % 128) return rs_fail(ctx, RS_EINVAL, "%s: pred_hidden/joint_hidden must be multiples of 128", what);
+    if (d.pred_layers < 1 || d.pred_layers > 4) return rs_fail(ctx, RS_EINVAL, "%s: 1..4 LSTM layers supported", what);
+    return RS_OK;
+}
 
 constexpr int SPLITK_LSTM = 16;  // K slices of the LSTM gate products
 constexpr int SPLITK_TILE = 8;   // K slices of the joint / prediction projections
@@ -55,6 +77,19 @@ __device__ __forceinline__ float rs_logf(float x) {
 __device__ __forceinline__ float rs_logaddexpf(float a, float b) {
     const float hi = a >= b ? a : b, lo = a >= b ? b : a;
     return hi + rs_logf(1.0f + rs_expf(lo - hi));
+}
+
+// the joint activation of four columns: tanh(f + g) (joint_act 1: ESPnet, Zipformer) or relu(f + g) (0: NeMo)
+__device__ __forceinline__ float4 rs_joint_act4(float4 f, float4 g, int joint_act) {
+    float4 r;
+    if (joint_act) { r.x = rs_tanhf(f.x + g.x); r.y = rs_tanhf(f.y + g.y); r.z = rs_tanhf(f.z + g.z); r.w = rs_tanhf(f.w + g.w); }
+    else { r.x = fmaxf(f.x + g.x, 0.0f); r.y = fmaxf(f.y + g.y, 0.0f); r.z = fmaxf(f.z + g.z, 0.0f); r.w = fmaxf(f.w + g.w, 0.0f); }
+    return r;
+}
+
+// (value desc, index asc): does (oz, ov) come before (bz, bv)?  An index < 0 is an empty entry.
+__device__ __forceinline__ bool rs_before(float oz, int ov, float bz, int bv) {
+    return ov >= 0 && (bv < 0 || oz > bz || (oz == bz && ov < bv));
 }
 
 // Activation rows are gathered by index, so a lane-per-row load (what the MFMA A operand wants:

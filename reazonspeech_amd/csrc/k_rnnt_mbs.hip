@@ -61,9 +61,6 @@
 
 #include <type_traits>
 
-int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
-int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
-                                         int rows_per_utt, int step, hipStream_t s);
 
 namespace {
 
@@ -176,16 +173,8 @@ __global__ __launch_bounds__(256) void mbs_act_kernel(DecodeState st, MbsState m
         const int drow = utt * K + ms.dec[list][row];
         const float4 a = reinterpret_cast<const float4*>(f + ((size_t)utt * Tp + t) * J)[q];
         const float4 g = reinterpret_cast<const float4*>(st.g + (size_t)drow * J)[q];
-        float4 r;
-        if (st.joint_act) { r.x = rs_tanhf(a.x + g.x); r.y = rs_tanhf(a.y + g.y); r.z = rs_tanhf(a.z + g.z); r.w = rs_tanhf(a.w + g.w); }
-        else { r.x = fmaxf(a.x + g.x, 0.0f); r.y = fmaxf(a.y + g.y, 0.0f); r.z = fmaxf(a.z + g.z, 0.0f); r.w = fmaxf(a.w + g.w, 0.0f); }
-        reinterpret_cast<float4*>(a_pre + (size_t)row * J)[q] = r;
+        reinterpret_cast<float4*>(a_pre + (size_t)row * J)[q] = rs_joint_act4(a, g, st.joint_act);
     }
-}
-
-// (value desc, flat index asc): does (oz, ov) come before (bz, bv)?  An index < 0 is an empty entry.
-__device__ __forceinline__ bool mbs_before(float oz, int ov, float bz, int bv) {
-    return ov >= 0 && (bv < 0 || oz > bz || (oz == bz && ov < bv));
 }
 
 // NVR > 0: V <= 256 NVR and a hypothesis's logits row is read ONCE into NVR registers per thread, every load in flight before the
@@ -305,14 +294,14 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
         for (int off = 32; off > 0; off >>= 1) {
             const float oz = __shfl_xor(bz, off, 64);
             const int ov = __shfl_xor(bv, off, 64);
-            if (mbs_before(oz, ov, bz, bv)) { bz = oz; bv = ov; }
+            if (rs_before(oz, ov, bz, bv)) { bz = oz; bv = ov; }
         }
         if (lane == 0) { s_cz[j][wave] = bz; s_cv[j][wave] = bv; }
         __syncthreads();
         bz = s_cz[j][0]; bv = s_cv[j][0];
 #pragma unroll
         for (int w = 1; w < 4; ++w)
-            if (mbs_before(s_cz[j][w], s_cv[j][w], bz, bv)) { bz = s_cz[j][w]; bv = s_cv[j][w]; }
+            if (rs_before(s_cz[j][w], s_cv[j][w], bz, bv)) { bz = s_cz[j][w]; bv = s_cv[j][w]; }
         if (bv < 0) { n_cand = j; break; }                // fewer than K values exist (H V < K); uniform over the workgroup
         if (tid == 0) { s_val[j] = bz; s_idx[j] = bv; }
         if (tv[0] == bv) {                                // the owner pops its head
@@ -469,7 +458,7 @@ float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, rs_ar
     for (int k = 0; k < 2; ++k) { ms.y[k] = a.take<int32_t>(rows * cap); ms.fr[k] = a.take<int32_t>(rows * cap); }
     ms.n_hyp[0] = a.take<int32_t>(B); ms.n_hyp[1] = a.take<int32_t>(B);
     st.counters = a.take<int32_t>(16);
-    st.zapprox = a.take<float>(rows * (size_t)((d.n_logits + 63) / 64 * 64));
+    st.zapprox = a.take<float>(rows * (size_t)rs_joint_zstride(d));
     ms.ctx[0] = ms.ctx[1] = nullptr;
     if (hotwords) { ms.ctx[0] = a.take<int32_t>(rows); ms.ctx[1] = a.take<int32_t>(rows); }       // (last: the plain layout is a prefix)
     ms.cap = cap;
@@ -477,7 +466,6 @@ float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, rs_ar
     st.joint_act = d.joint_act;
     return a_pre;
 }
-constexpr size_t MBS_SLACK = 1024;
 
 }  // namespace
 
@@ -487,7 +475,7 @@ size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_
     DecodeState st{};
     MbsState ms;
     mbs_layout(ctx, B, K, tp_max > 0 ? tp_max : 1, hotwords, a, st, ms);
-    return a.bytes() + MBS_SLACK;
+    return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
@@ -497,7 +485,7 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     const int D = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
     if (!ctx->k2_conv_w || d.pred_layers != 1) return rs_fail(ctx, RS_EINVAL, "modified beam search: the context has no stateless decoder");
-    if (D % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "modified beam search: decoder_dim / joiner_dim must be multiples of 128");
+    if (int rc = rs_rnnt_check_dims(ctx, "modified beam search"); rc != RS_OK) return rc;
     if (K < 1 || K > MBS_MAX_K) return rs_fail(ctx, RS_EINVAL, "modified beam search: max_active_paths must be 1..%d", MBS_MAX_K);
     if ((long long)K * V > 0x7fffffffLL) return rs_fail(ctx, RS_EINVAL, "modified beam search: vocabulary too large");
     const int cap = tp_max > 0 ? tp_max : 1;              // at most one token per frame
@@ -508,42 +496,39 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     MbsHw hw{};
     if (HWF) { hw.g = *hotwords; hw.graph_of = graph_of; }
     float* const a_pre = mbs_layout(ctx, B, K, cap, HWF, arena, st, ms);
-    if (workspace_bytes < arena.bytes() + MBS_SLACK)
-        return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + MBS_SLACK);
+    if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
+        return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     const int rows = B * K;
     float* const zbuf = st.zapprox;
     st.unk = rs_k2_unk_id(ctx);
-    const int zstride = (V + 63) / 64 * 64;
+    const int zstride = rs_joint_zstride(d);
 
-    rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * rs_align((size_t)rows * D * 4), s));                  // h .. c_tmp are adjacent
     if (HWF) hipLaunchKernelGGL((mbs_init_kernel<true>), dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, hw);
     else hipLaunchKernelGGL((mbs_init_kernel<false>), dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, MbsNoHw{});
-    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
     RS_CHECK_LAUNCH(ctx, "modified beam search init");
     const int act_blocks = (int)(((long long)rows * (J / 4) + 255) / 256);
+    // the selection kernel: the logits a lane keeps in registers follow from the vocabulary; the hotword form takes the graphs last
+    auto select_hw = mbs_select_kernel<4, true>;
+    if (V > MBS_THREADS * 4) select_hw = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, true> : mbs_select_kernel<0, true>;
+    auto select = mbs_select_kernel<4, false>;
+    if (V > MBS_THREADS * 4) select = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, false> : mbs_select_kernel<0, false>;
     for (int t = 0; t < tp_max; ++t) {
         hipLaunchKernelGGL(mbs_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, ms, joint_enc, a_pre, rows, tp_max, J, K, t);
-        if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, rows, rows, tp_max, K, t, s); rc != RS_OK) {
-            rs_prof_end(ctx, RS_PROF_DECODE, s);
-            return rc;
-        }
-#define RS_MBS_ARGS st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t, blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores
-        if (HWF) {
-            if (V <= MBS_THREADS * 4) hipLaunchKernelGGL((mbs_select_kernel<4, true>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, hw);
-            else if (V <= MBS_THREADS * 42) hipLaunchKernelGGL((mbs_select_kernel<42, true>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, hw);
-            else hipLaunchKernelGGL((mbs_select_kernel<0, true>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, hw);
-        } else if (V <= MBS_THREADS * 4) hipLaunchKernelGGL((mbs_select_kernel<4, false>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, MbsNoHw{});
-        else if (V <= MBS_THREADS * 42) hipLaunchKernelGGL((mbs_select_kernel<42, false>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, MbsNoHw{});
-        else hipLaunchKernelGGL((mbs_select_kernel<0, false>), dim3(B), dim3(MBS_THREADS), 0, s, RS_MBS_ARGS, MbsNoHw{});
-#undef RS_MBS_ARGS
-        if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; }
+        if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, rows, rows, tp_max, K, t, s); rc != RS_OK) return rc;
+        if (HWF) hipLaunchKernelGGL(select_hw, dim3(B), dim3(MBS_THREADS), 0, s, st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t,
+                                    blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, hw);
+        else hipLaunchKernelGGL(select, dim3(B), dim3(MBS_THREADS), 0, s, st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t,
+                                blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, MbsNoHw{});
+        if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
     }
     RS_CHECK_LAUNCH(ctx, "modified beam search step");
     int32_t hc[4] = {0, 0, 0, 0};
     RS_HIP(ctx, hipMemcpyAsync(hc, st.counters, sizeof hc, hipMemcpyDeviceToHost, s));
     RS_HIP(ctx, hipStreamSynchronize(s));
-    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    prof.end();
     if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "modified beam search: a result has more than out_cap=%d tokens", out_cap);
     return RS_OK;
 }

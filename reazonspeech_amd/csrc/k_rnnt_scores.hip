@@ -25,10 +25,6 @@
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
 
-int rs_rnnt_launch_lstm_pred(rs_ctx* ctx, const void* st_ptr, int rows, hipStream_t s);
-int rs_rnnt_launch_joint_logits_indirect(rs_ctx* ctx, const void* st_ptr, const float* joint_enc, int rows, int rows_bound, int tp_max,
-                                         int rows_per_utt, int step, hipStream_t s);
-
 namespace {
 
 struct ScoreArgs {
@@ -135,13 +131,7 @@ __global__ __launch_bounds__(256) void scores_gather_kernel(ScoreArgs a, DecodeS
     const float4 fv = *reinterpret_cast<const float4*>(f + ((size_t)b * a.tp_max + t) * J + k);
     const float* gr = g_log ? g_log + ((size_t)u * a.B + b) * J : st.g + (size_t)r * J;
     const float4 gv = *reinterpret_cast<const float4*>(gr + k);
-    float4 o;
-    if (st.joint_act) {
-        o.x = rs_tanhf(fv.x + gv.x); o.y = rs_tanhf(fv.y + gv.y); o.z = rs_tanhf(fv.z + gv.z); o.w = rs_tanhf(fv.w + gv.w);
-    } else {
-        o.x = fmaxf(fv.x + gv.x, 0.0f); o.y = fmaxf(fv.y + gv.y, 0.0f); o.z = fmaxf(fv.z + gv.z, 0.0f); o.w = fmaxf(fv.w + gv.w, 0.0f);
-    }
-    *reinterpret_cast<float4*>(a_pre + (size_t)r * J + k) = o;
+    *reinterpret_cast<float4*>(a_pre + (size_t)r * J + k) = rs_joint_act4(fv, gv, st.joint_act);
     if (k == 0) st.alive[(size_t)parity * list_pitch + r] = r;
     if (i == 0) st.counters[2 + parity] = n;
 }
@@ -222,18 +212,17 @@ void scores_layout(const rs_ctx* ctx, int B, int u_cap, size_t R, rs_arena& ar, 
     }
     st.alive = ar.take<int32_t>(2 * R);                                      // [2][R]: the tile kernel reads list (chunk & 1) at pitch R
     l.a_pre = ar.take<float>(R * J);
-    st.zapprox = ar.take<float>(R * (size_t)((d.n_logits + 63) / 64 * 64));
+    st.zapprox = ar.take<float>(R * (size_t)rs_joint_zstride(d));
     st.a_pre = l.a_pre;
     st.joint_act = d.joint_act;
 }
-constexpr size_t SCORES_SLACK = 1024;
 constexpr size_t SCORES_MAX_R = 32 * 65535;                // the tile kernel's grid
 
 size_t scores_bytes(const rs_ctx* ctx, int B, int u_cap, size_t R) {
     rs_arena ar;
     ScoreLayout l;
     scores_layout(ctx, B, u_cap, R, ar, l);
-    return ar.bytes() + SCORES_SLACK;
+    return ar.bytes() + RS_DECODE_SLACK;
 }
 
 }  // namespace
@@ -260,8 +249,8 @@ int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     const bool k2 = ctx->k2_conv_w != nullptr;
-    if (H % 128 || J % 128) return rs_fail(ctx, RS_EINVAL, "token scores: pred_hidden / joint_hidden must be multiples of 128");
-    if (k2 ? L != 1 : (L < 1 || L > 4)) return rs_fail(ctx, RS_EINVAL, "token scores: unsupported prediction network");
+    if (int rc = rs_rnnt_check_dims(ctx, "token scores"); rc != RS_OK) return rc;
+    if (k2 && L != 1) return rs_fail(ctx, RS_EINVAL, "token scores: unsupported prediction network");
     if ((long long)B * u_cap > 0x3fffffffLL) return rs_fail(ctx, RS_EINVAL, "token scores: B x u_cap too large");
     const size_t R = rs_rnnt_token_scores_chunk_rows(ctx, B, u_cap, workspace_bytes);
     if (R == 0)
@@ -274,26 +263,25 @@ int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t
     a.enc_lens = enc_lens; a.ids = ids; a.frames = frames; a.n_ids = n_ids;
     a.B = B; a.u_cap = u_cap; a.tp_max = tp_max; a.V = V; a.blank = d.blank_id; a.steps = steps;
     if (k2) st.unk = rs_k2_unk_id(ctx);
-    const int zstride = (V + 63) / 64 * 64;
+    const int zstride = rs_joint_zstride(d);
 
-    rs_prof_begin(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     int32_t info[4] = {0, 0, 0, 0};
-    auto leave = [&](int rc) { rs_prof_end(ctx, RS_PROF_DECODE, s); return rc; };
     hipLaunchKernelGGL(scores_plan_kernel, dim3(1), dim3(256), 0, s, a);
-    if (hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return leave(rs_fail(ctx, RS_EHIP, "token scores: plan failed: %s", hipGetErrorString(hipGetLastError())));
+    RS_HIP(ctx, hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, s));
+    RS_HIP(ctx, hipStreamSynchronize(s));
     const int n_rows = info[0], longest = info[1];
     if (n_rows < 0 || (long long)n_rows > (long long)B * u_cap || longest < 0 || longest > u_cap)
-        return leave(rs_fail(ctx, RS_ESTATE, "token scores: inconsistent plan"));
+        return rs_fail(ctx, RS_ESTATE, "token scores: inconsistent plan");
 
     if (!k2 && n_rows > 0) {
         const size_t state_bytes = (size_t)L * B * H * 4;
-        if (hipMemsetAsync(st.h, 0, 2 * rs_align(state_bytes), s) != hipSuccess) return leave(rs_fail(ctx, RS_EHIP, "token scores: memset failed"));
+        RS_HIP(ctx, hipMemsetAsync(st.h, 0, 2 * rs_align(state_bytes), s));
         for (int u = 0; u < longest; ++u) {
             DecodeState su = st;
             su.g = l.g_log + (size_t)u * B * J;           // the projection writes row b of step u's slab
             hipLaunchKernelGGL(scores_lstm_step_kernel, dim3(1), dim3(256), 0, s, a, su, u);
-            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &su, B, s); rc != RS_OK) return leave(rc);
+            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &su, B, s); rc != RS_OK) return rc;
         }
     }
     int chunk = 0;
@@ -301,18 +289,18 @@ int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t
         const int n = n_rows - w0 < (int)R ? n_rows - w0 : (int)R;
         if (k2) {
             hipLaunchKernelGGL(scores_k2_context_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, st, w0, n);
-            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, n, s); rc != RS_OK) return leave(rc);
+            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, n, s); rc != RS_OK) return rc;
         }
         const long long n_thr = (long long)n * (J / 4);
         hipLaunchKernelGGL(scores_gather_kernel, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s, a, st, joint_enc,
                            (const float*)(k2 ? nullptr : l.g_log), l.a_pre, J, w0, n, (int)R, chunk & 1);
-        if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, (int)R, n, tp_max, 1, chunk, s); rc != RS_OK) return leave(rc);
+        if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, (int)R, n, tp_max, 1, chunk, s); rc != RS_OK) return rc;
         hipLaunchKernelGGL(rnnt_logp_pick_kernel, dim3((n + 3) / 4), dim3(256), 0, s, a, st.zapprox, zstride, w0, n, logp, top1);
     }
-    if (hipGetLastError() != hipSuccess) return leave(rs_fail(ctx, RS_EHIP, "token scores: a launch failed"));
-    if (hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return leave(rs_fail(ctx, RS_EHIP, "token scores: %s", hipGetErrorString(hipGetLastError())));
-    rs_prof_end(ctx, RS_PROF_DECODE, s);
+    RS_CHECK_LAUNCH(ctx, "token scores");
+    RS_HIP(ctx, hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, s));
+    RS_HIP(ctx, hipStreamSynchronize(s));
+    prof.end();
     if (info[2]) return rs_fail(ctx, RS_EINVAL, "token scores: a count outside 0..u_cap, a frame outside its utterance or an id outside the vocabulary (its slot is NaN)");
     return RS_OK;
 }

@@ -203,10 +203,10 @@ int rs_launch_sub_conv0_dw1(rs_ctx* ctx, const float* feats, const int32_t* lens
     const size_t lds = 0;
     const double flops = (double)B * T2 * F2 * C * 2.0 * (6 * 9 + 9);
     const double bytes = (double)B * t_max * d.n_mels * 4.0 + (double)B * T2 * F2 * C * 2.0;
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, flops, bytes);
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, flops, bytes);
     hipLaunchKernelGGL(sub_conv0_dw1_kernel<uint16_t>, dim3(T2, B), dim3(C), lds, s, feats, lens_stage, B, t_max, d.n_mels, T2,
                        F1, F2, C, ctx->sub_conv0_w, ctx->sub_conv0_b, ctx->sub_dw_w[0], ctx->sub_dw_b[0], out);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "sub_conv0_dw1");
     return RS_OK;
 }
@@ -219,9 +219,9 @@ int rs_launch_sub_dw(rs_ctx* ctx, const uint16_t* in, const float* w, const floa
     const int fpb = 256 / cgs;
     const dim3 grid((f_out + fpb - 1) / fpb, t_out, B), block(cgs * fpb);
     const double bytes = (double)B * C * 2.0 * ((double)t_in * f_in + (double)t_out * f_out);
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, (double)B * t_out * f_out * C * 18.0, bytes);
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)B * t_out * f_out * C * 18.0, bytes);
     hipLaunchKernelGGL(sub_dw_kernel, grid, block, 0, s, in, w, b, lens_out, t_in, f_in, t_out, f_out, C, out);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "sub_dw");
     return RS_OK;
 }
@@ -235,11 +235,11 @@ int rs_launch_sub_conv0_dw1_f32(rs_ctx* ctx, const float* feats, const int32_t* 
     const int F1 = (d.n_mels + 2 - 3) / 2 + 1;
     if (d.n_mels % 4 || 4 * F2 > d.n_mels || 2 * F2 < F1)
         return rs_fail(ctx, RS_EINVAL, "subsampling: n_mels=%d must be a multiple of 4 with 4*F2 <= n_mels", d.n_mels);
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, (double)B * T2 * F2 * C * 2.0 * (6 * 9 + 9),
-                  (double)B * t_max * d.n_mels * 4.0 + (double)B * T2 * F2 * C * 4.0);
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)B * T2 * F2 * C * 2.0 * (6 * 9 + 9),
+                       (double)B * t_max * d.n_mels * 4.0 + (double)B * T2 * F2 * C * 4.0);
     hipLaunchKernelGGL(sub_conv0_dw1_kernel<float>, dim3(T2, B), dim3(C), 0, s, feats, lens_stage, B, t_max, d.n_mels, T2, F1, F2, C,
                        ctx->sub_conv0_w, ctx->sub_conv0_b, ctx->sub_dw_w[0], ctx->sub_dw_b[0], out);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "sub_conv0_dw1_f32");
     return RS_OK;
 }
@@ -247,10 +247,10 @@ int rs_launch_sub_conv0_dw1_f32(rs_ctx* ctx, const float* feats, const int32_t* 
 int rs_launch_sub_dw_f32(rs_ctx* ctx, const float* in, const float* w, const float* b, const int32_t* lens_out, int B, int t_in,
                          int f_in, int t_out, int f_out, float* out, hipStream_t s) {
     const int C = ctx->d.sub_channels;
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, (double)B * t_out * f_out * C * 18.0,
-                  (double)B * C * 4.0 * ((double)t_in * f_in + (double)t_out * f_out));
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)B * t_out * f_out * C * 18.0,
+                       (double)B * C * 4.0 * ((double)t_in * f_in + (double)t_out * f_out));
     hipLaunchKernelGGL(sub_dw_f32_kernel, dim3(f_out, t_out, B), dim3(C), 0, s, in, w, b, lens_out, t_in, f_in, t_out, f_out, C, out);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "sub_dw_f32");
     return RS_OK;
 }

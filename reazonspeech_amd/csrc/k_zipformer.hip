@@ -1556,7 +1556,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     hipLaunchKernelGGL(k2_lens_kernel, dim3((B + 255) / 256), dim3(256), 0, s, n_frames, B, d.n_stacks, d.downsampling[0], d.downsampling[1],
                        d.downsampling[2], d.downsampling[3], d.downsampling[4], d.downsampling[5], d.downsampling[6], d.downsampling[7], lens_all);
     // ---- encoder_embed ------------------------------------------------------------------------------------------------
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
+    rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
     hipLaunchKernelGGL(k2_conv0_kernel, dim3(pl.T1, B), dim3(256), 0, s, feats, t_max, pl.F, c1, k.conv0_w, k.conv0_b, a0);
     const bool conv1_first_form = rs_knob(RS_KNOB_K2_CONV1_OLD) != 0;   // the form other channel counts run
     if (c1 == 8 && c2 == 32 && pl.F2 <= 48 && !conv1_first_form) {
@@ -1572,21 +1572,22 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
     const int n_cus = rs_n_cus(ctx);
     if (conv2_fused) {
         // patches gathered into LDS, weights in registers: no patch matrix in HBM
-        if (int rc2 = rs_ensure_dynamic_lds(ctx, (const void*)k2_conv2_fused_kernel, C2_LDS); rc2 != RS_OK) { rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s); return rc2; }
+        if (int rc2 = rs_ensure_dynamic_lds(ctx, (const void*)k2_conv2_fused_kernel, C2_LDS); rc2 != RS_OK) return rc2;
         const long long n_tiles = (rows3 + 127) / 128;
         hipLaunchKernelGGL(k2_conv2_fused_kernel, dim3((unsigned)(n_tiles < n_cus ? n_tiles : n_cus)), dim3(512), C2_LDS, s, a1, pl.T2, pl.F2, T3, F3, k.conv2.w,
                            k.conv2.ld16, k.conv2.b, a2, rows3);
-        rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+        prof.end();
         RS_CHECK_LAUNCH(ctx, "zipformer encoder_embed convs");
     } else {
     hipLaunchKernelGGL(k2_im2col_kernel, dim3((unsigned)((rows3 + 3) / 4)), dim3(256), 0, s, a1, pl.T2, pl.F2, c2, T3, F3, k.conv2.ld16, rows3, col);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    prof.end();
     RS_CHECK_LAUNCH(ctx, "zipformer encoder_embed convs");
     RS_TRY(lin(k.conv2, col, a2, rows3, RS_GEMM_BIAS | RS_GEMM_SWOOSHR | RS_GEMM_OUT_F32));
     }
-    rs_prof_begin(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
-    hipLaunchKernelGGL(k2_cnx_dw_kernel<10>, dim3((T3 + CNX_TT - 1) / CNX_TT, B), dim3(256), 0, s, a2, lens3, T3, F3, c3, k.cnx_dw_w, k.cnx_dw_b, dwo);
-    rs_prof_end(ctx, RS_PROF_SUBSAMPLE, s);
+    {
+        rs_prof_scope prof_dw(ctx, RS_PROF_SUBSAMPLE, s, 0.0, 0.0);
+        hipLaunchKernelGGL(k2_cnx_dw_kernel<10>, dim3((T3 + CNX_TT - 1) / CNX_TT, B), dim3(256), 0, s, a2, lens3, T3, F3, c3, k.cnx_dw_w, k.cnx_dw_b, dwo);
+    }
     const bool cnx_fused = (ctx->k2_cnx_fused < 0 ? rs_knob(RS_KNOB_K2_CNX_FUSED) : ctx->k2_cnx_fused) != 0;
     if (cnx_fused && c3 == CX_C) {
         // both pointwise convolutions in one launch, the hidden tensor stays on the CU; result (bf16) in place over dwo
@@ -1638,7 +1639,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
                 if (lds > 160 * 1024 - 1024) return rs_fail(ctx, RS_EINVAL, "zipformer: %d frames in stack %d exceed the attention kernel's position table in LDS", Ts, st);
                 if (lds > 64 * 1024) RS_TRY(rs_ensure_dynamic_lds(ctx, (const void*)k2_attn_weights_kernel, (int)lds));
                 if (Ts > k.pos_cap) return rs_fail(ctx, RS_EINVAL, "zipformer: %d frames exceed the registered position tables (%d)", Ts, k.pos_cap);
-                rs_prof_begin(ctx, RS_PROF_ATTN, s, (double)B * H * Ts * (double)Ts * (2.0 * K2_QD + 2.0 * K2_PD + 8.0) * 2.0, (double)B * H * Ts * (double)Tp * 2.0);
+                rs_prof_scope prof(ctx, RS_PROF_ATTN, s, (double)B * H * Ts * (double)Ts * (2.0 * K2_QD + 2.0 * K2_PD + 8.0) * 2.0, (double)B * H * Ts * (double)Tp * 2.0);
                 const bool three_sweeps = rs_knob(RS_KNOB_K2_ATTW_SWEEPS) == 3;
                 const dim3 grid((Ts + 63) / 64, H, B);
 #define RS_K2_ATTW1(NT)                                                                                                                     \
@@ -1651,7 +1652,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
                 else if (Tp <= 320) RS_K2_ATTW1(20);
                 else RS_K2_ATTW1(40);
 #undef RS_K2_ATTW1
-                rs_prof_end(ctx, RS_PROF_ATTN, s);
+                prof.end();
             }
             auto ffn = [&](int f, const float* res, bool emit) -> int {
                 if (int r = lin(L.ff_in[f], xb, big, M, RS_GEMM_BIAS | RS_GEMM_SWOOSHL); r != RS_OK) return r;
@@ -1662,11 +1663,11 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
                 // `av` is shared by the three kinds of branch (row pitches vwp / hidp / dd): the columns that pad the out projection's
                 // K extent to a multiple of 64 are zeroed before every use
                 if (vwp != vw && hipMemsetAsync(av, 0, (size_t)M * vwp * 2, s) != hipSuccess) return rs_fail(ctx, RS_EHIP, "memset failed");
-                rs_prof_begin(ctx, RS_PROF_ATTN, s, (double)B * H * Ts * (double)Ts * 2.0 * 16.0, (double)B * H * Ts * (double)Tp * 2.0);
+                rs_prof_scope prof(ctx, RS_PROF_ATTN, s, (double)B * H * Ts * (double)Ts * 2.0 * 16.0, (double)B * H * Ts * (double)Tp * 2.0);
                 const int C = pad64(H * 16);
                 hipLaunchKernelGGL((k2_vt_kernel<0>), dim3((Tp + 63) / 64, C / 64, B), dim3(256), 0, s, big, vw, vw, lens, Ts, Tp, C, vT);
                 hipLaunchKernelGGL((k2_pv_kernel<1, 0>), dim3((Ts + 127) / 128, 1, B * H), dim3(256), 0, s, W, H, Tp, vT, C, big, vw, 0, lens, Ts, av, vwp);
-                rs_prof_end(ctx, RS_PROF_ATTN, s);
+                prof.end();
                 return lin(L.sa_out[a], av, xs, M, RES, xs, xb);
             };
             auto conv_module = [&](int a) -> int {
@@ -1678,10 +1679,10 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
             // non-linear attention: head 0's weights over tanh-gated values, output gate, out projection
             RS_TRY(lin(L.na_in, xb, big, M, RS_GEMM_BIAS));
             if (hidp != hid) RS_HIP(ctx, hipMemsetAsync(av, 0, (size_t)M * hidp * 2, s));
-            rs_prof_begin(ctx, RS_PROF_ATTN, s, (double)B * Ts * (double)Ts * 2.0 * hid, (double)B * Ts * (double)Tp * 2.0);
+            rs_prof_scope prof(ctx, RS_PROF_ATTN, s, (double)B * Ts * (double)Ts * 2.0 * hid, (double)B * Ts * (double)Tp * 2.0);
             hipLaunchKernelGGL((k2_vt_kernel<1>), dim3((Tp + 63) / 64, hidp / 64, B), dim3(256), 0, s, big, 3 * hid, hid, lens, Ts, Tp, hidp, vT);
             hipLaunchKernelGGL((k2_pv_kernel<4, 1>), dim3((Ts + 127) / 128, (hid + 63) / 64, B), dim3(256), 0, s, W, H, Tp, vT, hidp, big, 3 * hid, hid, lens, Ts, av, hidp);
-            rs_prof_end(ctx, RS_PROF_ATTN, s);
+            prof.end();
             RS_TRY(lin(L.na_out, av, xs, M, RES, xs, xb));
             RS_TRY(self_attn(0));
             RS_TRY(conv_module(0));

@@ -211,10 +211,22 @@ int rs_n_cus(rs_ctx* ctx);
             return rs_fail((ctx), RS_EHIP, "launch %s failed: %s", (what), hipGetErrorString(_e)); \
     } while (0)
 
-// RAII-ish profiling bracket around kernel launches of one class
+// Profiling bracket around the kernel launches of one class: rs_prof_begin records the start event and the class's bookkeeping,
+// rs_prof_end the stop event.  Launchers do not call the two themselves; they open an rs_prof_scope, which ends the bracket
+// exactly once on every way out of its block (RS_HIP, RS_CHECK_LAUNCH and every other early return included).  The stop event
+// belongs right after the bracket's last launch: call end() there, or close the scope's block there, when more follows.
 int rs_prof_class_index(int klass);
 void rs_prof_begin(rs_ctx* ctx, int klass, hipStream_t s, double flops, double bytes);
 void rs_prof_end(rs_ctx* ctx, int klass, hipStream_t s);
+struct rs_prof_scope {
+    rs_prof_scope(rs_ctx* ctx, int klass, hipStream_t s, double flops, double bytes) : ctx(ctx), klass(klass), s(s) { rs_prof_begin(ctx, klass, s, flops, bytes); }
+    rs_prof_scope(const rs_prof_scope&) = delete;
+    rs_prof_scope& operator=(const rs_prof_scope&) = delete;
+    ~rs_prof_scope() { end(); }
+    void end() { if (open) rs_prof_end(ctx, klass, s); open = false; }
+private:
+    rs_ctx* ctx; int klass; hipStream_t s; bool open = true;
+};
 
 // ----------------------------------------------------------------------------------------
 // kernel launchers (one per .hip file); all return RS_OK / RS_E*
