@@ -56,8 +56,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 
 // Two LayerNorms back to back on one read of the row: y = LN(x; g1, b1) is stored as f32 (the residual
 // stream after a layer's output norm), z = LN(y; g2, b2) as bf16 (the next layer's first FFN input).
-// Same arithmetic as two layernorm_kernel launches (y is normalised from registers instead of being
-// re-read), 362 MB instead of 507 MB of traffic per layer boundary at B=256.
+// The same source arithmetic as two layernorm_kernel launches (y is normalised from registers instead of being
+// re-read), 362 MB instead of 507 MB of traffic per layer boundary at B=256.  z has the bits of layernorm_kernel on y; y itself
+// can differ from layernorm_kernel's in the last bit: under -ffp-contract=fast the compiler fuses the products of the first
+// norm's sum of squared deviations into FMAs there and not here (tests/test_gpu_convmod_ops.py holds both to float64).
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm2_kernel(const float* __restrict__ x, const float* __restrict__ g1,
                                                          const float* __restrict__ b1, const float* __restrict__ g2,
@@ -537,4 +539,21 @@ int rs_launch_glu_dwconv(rs_ctx* ctx, const uint16_t* x, int layout, const float
     prof.end();
     RS_CHECK_LAUNCH(ctx, "glu_dwconv_silu");
     return RS_OK;
+}
+
+// Test hooks, deliberately not in rs_asr.h (no ABI change): the two launchers that no public entry reaches with every argument of
+// their own (the SwooshR activation and d % 256 != 0 of dwconv_act; layernorm2 at all), for the operator tests of
+// tests/test_gpu_convmod_ops.py.  They return the launcher's code; the message is read with rs_last_error.
+extern "C" int rs_debug_dwconv_act(rs_ctx* ctx, const uint16_t* x, const float* w, const float* b, const int32_t* lens, int B, int T, int d,
+                                   int k, int act, uint16_t* out, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (!x || !w || !b || !lens || !out) return rs_fail(ctx, RS_EINVAL, "dwconv_act: null pointer");
+    return rs_launch_dwconv_act(ctx, x, w, b, lens, B, T, d, k, act, out, (hipStream_t)stream);
+}
+
+extern "C" int rs_debug_layernorm2(rs_ctx* ctx, const float* x, const float* g1, const float* b1, const float* g2, const float* b2, int M,
+                                   int d, float eps, float* out_f32, uint16_t* out_bf16, float* stats, void* stream) {
+    if (!ctx) return RS_EINVAL;
+    if (!x || !g1 || !b1 || !g2 || !b2 || !out_bf16) return rs_fail(ctx, RS_EINVAL, "layernorm2: null pointer");
+    return rs_launch_layernorm2(ctx, x, g1, b1, g2, b2, M, d, eps, out_f32, out_bf16, stats, (hipStream_t)stream);
 }

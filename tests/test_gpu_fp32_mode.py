@@ -129,10 +129,14 @@ def test_attention_f32(gpu_device, T, lens, window, heads):
     c.close()
 
 
-@pytest.mark.parametrize("T,lens,k", [(19, [19, 14], 9), (70, [70, 33, 1], 9), (50, [50, 20], 31)])
-def test_glu_dwconv_f32(ctx, gpu_device, T, lens, k):
+@pytest.mark.parametrize("T,lens,k,d", [pytest.param(19, [19, 14], 9, 256, id="19-lens0-9"), pytest.param(70, [70, 33, 1], 9, 256, id="70-lens1-9"),
+                                        pytest.param(50, [50, 20], 31, 256, id="50-lens2-31"),
+                                        # d not a multiple of the 256-thread block (the c >= d guard); two channel blocks and a len of 0
+                                        pytest.param(50, [50, 20], 31, 320, id="50-lens3-31-d320"),
+                                        pytest.param(33, [33, 0, 17], 7, 512, id="33-lens4-7-d512")])
+def test_glu_dwconv_f32(ctx, gpu_device, T, lens, k, d):
     g = torch.Generator().manual_seed(T)
-    B, d = len(lens), 256
+    B = len(lens)
     x = torch.randn((B, T, 2 * d), generator=g)
     w = torch.randn((d, k), generator=g) / 3
     b = 0.1 * torch.randn((d,), generator=g)
@@ -141,11 +145,12 @@ def test_glu_dwconv_f32(ctx, gpu_device, T, lens, k):
     u = xd[..., :d] * torch.sigmoid(xd[..., d:]) * (torch.arange(T)[None, :] < lens_t[:, None])[:, :, None]
     z = torch.nn.functional.conv1d(u.transpose(1, 2), w.double()[:, None, :], b.double(), padding=(k - 1) // 2, groups=d).transpose(1, 2)
     ref = torch.nn.functional.silu(z).float()
-    out = torch.zeros((B * T, d), dtype=torch.float32, device=gpu_device)
+    out = torch.full((B * T + 8, d), 7.0, dtype=torch.float32, device=gpu_device)
     ctx.glu_dwconv_f32(x.reshape(B * T, 2 * d).to(gpu_device), w.t().contiguous().to(gpu_device), b.to(gpu_device),
                        lens_t.to(gpu_device), B, T, d, k, out)
     sync()
-    assert (out.cpu().view(B, T, d) - ref).abs().max() <= 2e-5
+    assert (out[:B * T].cpu().view(B, T, d) - ref).abs().max() <= 2e-5
+    assert (out[B * T:] == 7.0).all(), "rows past B * T were written"
 
 
 # ---- end to end --------------------------------------------------------------------------------------------------

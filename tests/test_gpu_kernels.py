@@ -15,6 +15,7 @@ import torch
 from reazonspeech_amd.runtime import capi
 from reazonspeech_amd.runtime.config import TINY, FASTCONFORMER_619M
 from oracle import model as om
+from convmod_ref import conv_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -403,7 +404,7 @@ def test_layernorm(ctx, gpu_device, d):
     ctx.layernorm(dx, gamma.to(gpu_device), beta.to(gpu_device), 1e-5, out_bf16=o16, out_f32=o32)
     sync()
     assert (o32.cpu() - ref).abs().max() <= 2e-5
-    assert (o16.cpu().float() - ref).abs().max() <= 2e-2
+    assert ((o16.cpu().float() - ref).abs() <= 2e-5 + 2.0 ** -7 * ref.abs()).all()        # one bf16 ulp of the output rounding
     # in place (how the encoder applies norm_out to the residual stream)
     ctx.layernorm(dx, gamma.to(gpu_device), beta.to(gpu_device), 1e-5, out_f32=dx)
     sync()
@@ -426,7 +427,7 @@ def test_glu_dwconv_silu(ctx, gpu_device, T, lens):
     ctx.glu_dwconv(bf(x).reshape(B * T, 2 * d).to(gpu_device), w.t().contiguous().to(gpu_device), b.to(gpu_device),
                    lens_t.to(gpu_device), B, T, d, k, out)
     sync()
-    assert (out.cpu().float().view(B, T, d) - ref).abs().max() <= 2e-2
+    assert ((out.cpu().float().view(B, T, d) - ref).abs() <= conv_tol(ref)).all()
     # the other input layouts: value / gate columns interleaved in blocks of 32 (what the pw1 GEMM produces from the
     # loader's row order) and GLU already applied by the GEMM epilogue (bf16 [B*T][d])
     from reazonspeech_amd.runtime.weights import glu_interleave_index
@@ -442,7 +443,7 @@ def test_glu_dwconv_silu(ctx, gpu_device, T, lens):
     ctx.glu_dwconv(bf(ug).reshape(B * T, d).to(gpu_device), w.t().contiguous().to(gpu_device), b.to(gpu_device),
                    lens_t.to(gpu_device), B, T, d, k, out2, layout=capi.GLU_APPLIED)
     sync()
-    assert (out2.cpu().float().view(B, T, d) - ref2).abs().max() <= 2e-2
+    assert ((out2.cpu().float().view(B, T, d) - ref2).abs() <= conv_tol(ref2)).all()
 
 
 @pytest.mark.parametrize("T,lens,window", [(19, [19, 14], None), (138, [138, 97, 5], None), (64, [64, 33], None),
