@@ -119,7 +119,9 @@ __global__ __launch_bounds__(384) void relpos_attention_kernel(AttnParams p) {
     const int lane = tid & 63;
     int b = blockIdx.z, h = blockIdx.y, qg = blockIdx.x;
     if constexpr (PERSIST) { qg = item % p.n_groups; h = (item / p.n_groups) % p.n_heads; b = item / (p.n_groups * p.n_heads); }
-    const int len = p.lens[b];
+    // clamped to T like every other form: key blocks cover rows up to 32 ceil(T / 32) - 1, and `j < len` with a length above T let
+    // the (clamped, repeated) rows T .. len - 1 into the softmax
+    const int len = p.lens[b] < T ? p.lens[b] : T;
     const int i0 = (qg * nw + wave) * 32;
     const int il = lane & 31, hh = lane >> 5;
     const int qi = i0 + il;
@@ -137,6 +139,7 @@ __global__ __launch_bounds__(384) void relpos_attention_kernel(AttnParams p) {
     auto stage_kv = [&](int jc, int nb) {
         // nb * 512 K items <= 8 * blockDim for every launch shape.  Named scalars, unconditional (clamped)
         // loads: an indexed array or a predicated definition is demoted to scratch memory by the compiler.
+        // (nb >= 1: with nb = 0 the clamps below end at item -1, which at head_dim 64 is slot -1 / VH = -1: key rows -32 .. -1)
         const int items = nb * 32 * NCH;
         auto k_src = [&](int it) -> const uint4* {
             int idx = tid + it * (int)blockDim.x;
@@ -209,7 +212,10 @@ __global__ __launch_bounds__(384) void relpos_attention_kernel(AttnParams p) {
     if (wave == 0 && 4 * lane < 2 * HD)                  // bias_s = [u(HD) | v(HD)]
         *reinterpret_cast<float4*>(bias_s + 4 * lane) =
             *reinterpret_cast<const float4*>((4 * lane < HD ? p.bias_u : p.bias_v - HD) + h * HD + 4 * lane);
-    stage_kv(0, n_kblocks < KB_CHUNK ? n_kblocks : KB_CHUNK);
+    // an utterance of length 0 stages one block (rows clamped into the utterance, never read back) rather than none: stage_kv's
+    // index clamps need an item to stop at.  With nb = 0 the V loads of head_dim 64 read the 32 rows BEFORE the utterance: before
+    // the start of qkv for b = 0, or for any b when B * T is small
+    stage_kv(0, n_kblocks < 1 ? 1 : n_kblocks < KB_CHUNK ? n_kblocks : KB_CHUNK);
     stamp(0.0f);                                   // [1] own K/V stores issued and landed
     __syncthreads();
     stamp(0.0f);                                   // [2] workgroup barrier passed
