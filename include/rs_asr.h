@@ -345,7 +345,9 @@ int rs_finalize(rs_ctx* ctx);
  * sample count is at most max_samples (pad included). */
 size_t rs_workspace_bytes(const rs_ctx* ctx, int B, int max_samples);
 
-/* Shape helpers (host arithmetic, no device work). */
+/* Shape helpers (host arithmetic, no device work).  Like every query that returns a size or a frame count, they answer 0 for
+ * a null context and for a context of a family they are not defined for (an AV-HuBERT context), and write no error text:
+ * their context is const. */
 int rs_mel_frames(const rs_ctx* ctx, int n_samples);   /* floor(L / hop) */
 int rs_enc_frames(const rs_ctx* ctx, int n_mel_frames); /* three k3 s2 p1 convs */
 

@@ -42,7 +42,7 @@ struct rs_avsr_layer {
     rs_avsr_attn sa, ca;
     const float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b;
 };
-struct rs_avsr {
+struct rs_avsr : rs_family_state {
     rs_avsr_dims d{};
     const float *audio_w = nullptr, *audio_b = nullptr, *conv3d_w = nullptr, *bn0_a = nullptr, *bn0_b = nullptr, *prelu0 = nullptr;
     rs_avsr_block blocks[4][2] = {};
@@ -643,8 +643,6 @@ AvsrPlan avsr_plan(const rs_avsr& k, int B, int T, rs_arena& a) {
     return p;
 }
 
-void avsr_free(rs_avsr* k) { delete k; }
-
 int launch_attn(rs_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldk, size_t kstride, const float* kmask, int mask_pitch, int rows_per_kb,
                 int Bq, int Tq, int n_keys, int H, int hd, int causal, float* out, int ldo, hipStream_t s) {
     if (Bq <= 0 || Tq <= 0 || n_keys <= 0) return RS_OK;
@@ -691,13 +689,12 @@ extern "C" int rs_avsr_create(rs_ctx** out, int device, const rs_avsr_dims* dims
     if (!out || !dims) return RS_EINVAL;
     *out = nullptr;
     rs_ctx* ctx = new (std::nothrow) rs_ctx();
-    if (!ctx) return RS_EINVAL;
+    rs_avsr* k = ctx ? new (std::nothrow) rs_avsr() : nullptr;
+    if (!k) { delete ctx; return RS_EINVAL; }
     *out = ctx;
     ctx->device = device;
-    rs_avsr* k = new (std::nothrow) rs_avsr();
-    if (!k) return rs_fail(ctx, RS_EINVAL, "out of memory");
-    ctx->avsr = k;
-    ctx->avsr_free = avsr_free;
+    ctx->family = RS_FAM_AVSR;
+    ctx->state.reset(k);
     k->d = *dims;
     const rs_avsr_dims& d = k->d;
     if (d.encoder_layers < 1 || d.decoder_layers < 1 || d.encoder_embed_dim % 32 || d.decoder_embed_dim != d.encoder_embed_dim || d.encoder_ffn_dim % 32 ||
@@ -713,7 +710,7 @@ extern "C" int rs_avsr_create(rs_ctx** out, int device, const rs_avsr_dims* dims
 }
 
 int rs_avsr_finalize_impl(rs_ctx* ctx) {
-    rs_avsr& k = *ctx->avsr;
+    rs_avsr& k = *rs_avsr_of(ctx);
     const rs_avsr_dims& d = k.d;
     const size_t dm = d.encoder_embed_dim, ffn = d.encoder_ffn_dim, dffn = d.decoder_ffn_dim;
     rs_weights r(ctx);
@@ -764,8 +761,8 @@ int rs_avsr_finalize_impl(rs_ctx* ctx) {
 }
 
 extern "C" int rs_avsr_encoder_set_taps(rs_ctx* ctx, float* video, float* fused_ln, float* enc_ln, float* layer_out, const int32_t* layer_ids, int n_layer_ids) {
-    if (!ctx || !ctx->avsr) return RS_EINVAL;
-    rs_avsr& k = *ctx->avsr;
+    RS_GUARD(ctx, rs_avsr_encoder_set_taps);
+    rs_avsr& k = *rs_avsr_of(ctx);
     if (n_layer_ids < 0 || (n_layer_ids > 0 && (!layer_out || !layer_ids))) return rs_fail(ctx, RS_EINVAL, "avsr taps: null pointer");
     for (int i = 0; i < n_layer_ids; ++i)
         if (layer_ids[i] < 0 || layer_ids[i] >= k.d.encoder_layers) return rs_fail(ctx, RS_EINVAL, "avsr taps: layer %d out of range", layer_ids[i]);
@@ -776,20 +773,20 @@ extern "C" int rs_avsr_encoder_set_taps(rs_ctx* ctx, float* video, float* fused_
 }
 
 extern "C" size_t rs_avsr_workspace_bytes(const rs_ctx* ctx, int B, int T) {
-    if (!ctx || !ctx->avsr || B <= 0 || T <= 0) return 0;
+    RS_GUARD_QUERY(ctx, rs_avsr_workspace_bytes, 0);
+    if (B <= 0 || T <= 0) return 0;
     rs_arena a;
-    avsr_plan(*ctx->avsr, B, T, a);
+    avsr_plan(*rs_avsr_of(ctx), B, T, a);
     return a.bytes() + AVSR_SLACK;
 }
 
 extern "C" int rs_avsr_encoder_forward(rs_ctx* ctx, const float* input_values, const float* pixel_values, const float* padding_mask, int B, int T, float* enc_out,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    if (!ctx || !ctx->avsr) return RS_EINVAL;
-    if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_encoder_forward");
+    RS_GUARD(ctx, rs_avsr_encoder_forward);
     if (B <= 0 || T <= 0) return B < 0 || T < 0 ? rs_fail(ctx, RS_EINVAL, "avsr encoder: negative size") : RS_OK;
     if ((!input_values && !pixel_values) || !padding_mask || !enc_out || !workspace)
         return rs_fail(ctx, RS_EINVAL, "avsr encoder: null pointer (one of input_values / pixel_values may be NULL: that modality's FEATURES are zeros, modeling_avhubert.py:172-177)");
-    rs_avsr& k = *ctx->avsr;
+    rs_avsr& k = *rs_avsr_of(ctx);
     const rs_avsr_dims& d = k.d;
     hipStream_t s = (hipStream_t)stream;
     rs_arena arena(workspace);
@@ -929,17 +926,17 @@ AvsrDecPlan avsr_dec_plan(const rs_avsr& k, int B, int T, int beams, int max_len
 }  // namespace
 
 extern "C" size_t rs_avsr_decoder_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
-    if (!ctx || !ctx->avsr || B <= 0 || T <= 0 || beams <= 0 || max_len <= 0) return 0;
+    RS_GUARD_QUERY(ctx, rs_avsr_decoder_state_bytes, 0);
+    if (B <= 0 || T <= 0 || beams <= 0 || max_len <= 0) return 0;
     rs_arena a;
-    avsr_dec_plan(*ctx->avsr, B, T, beams, max_len, a);
+    avsr_dec_plan(*rs_avsr_of(ctx), B, T, beams, max_len, a);
     return a.bytes() + AVSR_DEC_SLACK;
 }
 
 extern "C" int rs_avsr_decoder_begin(rs_ctx* ctx, const float* enc, int B, int T, int beams, int max_len, void* state, size_t state_bytes, void* stream) {
-    if (!ctx || !ctx->avsr) return RS_EINVAL;
-    if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_decoder_begin");
+    RS_GUARD(ctx, rs_avsr_decoder_begin);
     if (B <= 0 || T <= 0 || beams <= 0 || max_len <= 0 || !enc || !state) return rs_fail(ctx, RS_EINVAL, "avsr decoder: bad argument");
-    rs_avsr& k = *ctx->avsr;
+    rs_avsr& k = *rs_avsr_of(ctx);
     const rs_avsr_dims& d = k.d;
     if (max_len > d.max_positions) return rs_fail(ctx, RS_EINVAL, "avsr decoder: %d positions exceed max_target_positions %d", max_len, d.max_positions);
     rs_arena arena(state);
@@ -960,11 +957,10 @@ extern "C" int rs_avsr_decoder_begin(rs_ctx* ctx, const float* enc, int B, int T
 
 extern "C" int rs_avsr_decoder_step(rs_ctx* ctx, const int32_t* tokens, const int32_t* src_rows, int step, const float* padding_mask, int B, int T, int beams,
                                     int max_len, float* logits, void* state, size_t state_bytes, void* stream) {
-    if (!ctx || !ctx->avsr) return RS_EINVAL;
-    if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_decoder_step");
+    RS_GUARD(ctx, rs_avsr_decoder_step);
     if (B <= 0 || T <= 0 || beams <= 0 || max_len <= 0 || step < 0 || step >= max_len || !tokens || !padding_mask || !logits || !state)
         return rs_fail(ctx, RS_EINVAL, "avsr decoder step: bad argument (step %d of %d)", step, max_len);
-    rs_avsr& k = *ctx->avsr;
+    rs_avsr& k = *rs_avsr_of(ctx);
     const rs_avsr_dims& d = k.d;
     rs_arena arena(state);
     const AvsrDecPlan pl = avsr_dec_plan(k, B, T, beams, max_len, arena);
@@ -1017,4 +1013,5 @@ extern "C" int rs_avsr_decoder_step(rs_ctx* ctx, const int32_t* tokens, const in
 }
 
 // the dimensions of an avsr context for the other translation units (k_avsr_search.hip); nullptr for another family's context
-const rs_avsr_dims* rs_avsr_dims_of(const rs_ctx* ctx) { return ctx && ctx->avsr ? &ctx->avsr->d : nullptr; }
+rs_avsr* rs_avsr_of(const rs_ctx* ctx) { return ctx && ctx->family == RS_FAM_AVSR ? static_cast<rs_avsr*>(ctx->state.get()) : nullptr; }
+const rs_avsr_dims* rs_avsr_dims_of(const rs_ctx* ctx) { return rs_avsr_of(ctx) ? &rs_avsr_of(ctx)->d : nullptr; }

@@ -572,8 +572,7 @@ OptArgs opt_args(const Opts& op, const SearchPtrs& p) {      // (go2 / marks are
 
 // the arguments of a search call -> its options.  vocab 0: a call that touches the front of the state only (rows, peek, finish)
 int check_search_args(rs_ctx* ctx, const rs_avsr_search* sp, const rs_avsr_search_opts* opts, int B, int vocab, const void* state, const char* what, Opts* op) {
-    const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
-    if (!d) return rs_fail(ctx, RS_EINVAL, "%s: defined for an avsr context (rs_avsr_create) only", what);
+    const rs_avsr_dims* d = rs_avsr_dims_of(ctx);        // (the entry's guard: an avsr context)
     if (!sp || !state) return rs_fail(ctx, RS_EINVAL, "%s: null pointer", what);
     if (sp->beams < 1 || sp->beams > MAXK) return rs_fail(ctx, RS_EINVAL, "%s: beams must be 1..%d, got %d", what, MAXK, sp->beams);
     if (sp->greedy && sp->beams != 1) return rs_fail(ctx, RS_EINVAL, "%s: greedy search has one row per clip, got beams %d", what, sp->beams);
@@ -614,7 +613,7 @@ bool opts_ok_for_bytes(const rs_avsr_search_opts* o, int beams) {
 
 // ---- the entry points: every family (plain, _opts, _scored) is one implementation with the options and the recording as arguments ----
 size_t search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts, bool rec) {
-    if (!rs_avsr_dims_of(ctx) || B <= 0 || beams < 1 || beams > MAXK || max_len < 2 || vocab < 4 || !opts_ok_for_bytes(opts, beams)) return 0;
+    if (B <= 0 || beams < 1 || beams > MAXK || max_len < 2 || vocab < 4 || !opts_ok_for_bytes(opts, beams)) return 0;
     Opts op;
     op.rec = rec;
     if (opts) op.o = *opts;
@@ -623,7 +622,6 @@ size_t search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len, int 
 
 int search_begin(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, bool rec, int B, int vocab, void* state, size_t state_bytes,
                  void* stream) {
-    if (!ctx) return RS_EINVAL;
     SearchPtrs p;
     Opts op;
     op.rec = rec;
@@ -638,7 +636,6 @@ int search_begin(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search
 // step_scores (rec only): f32[max_new_tokens][B * beams][Vp] or null
 int search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, bool rec, float* step_scores, int B,
                 int vocab, void* state, size_t state_bytes, void* stream) {
-    if (!ctx) return RS_EINVAL;
     SearchPtrs p;
     Opts op;
     op.rec = rec;
@@ -673,7 +670,6 @@ int search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search
 
 int search_peek(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, bool rec, int B, void* state, size_t state_bytes, int step,
                 int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
-    if (!ctx) return RS_EINVAL;
     SearchPtrs p;
     Opts op;
     op.rec = rec;
@@ -700,7 +696,6 @@ bool scored_out_ok(const rs_avsr_search* search, const ScoredOut& so) { return s
 
 int search_finish(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, const ScoredOut* so, int B, void* state, size_t state_bytes,
                   int32_t* sequences, int32_t* lengths, float* scores, void* stream) {
-    if (!ctx) return RS_EINVAL;
     SearchPtrs p;
     Opts op;
     op.rec = so != nullptr;
@@ -722,43 +717,52 @@ int search_finish(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_searc
 }  // namespace
 
 extern "C" size_t rs_avsr_search_state_bytes_opts(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts) {
+    RS_GUARD_QUERY(ctx, rs_avsr_search_state_bytes_opts, 0);
     return search_state_bytes(ctx, B, beams, max_len, vocab, opts, false);
 }
 extern "C" size_t rs_avsr_search_state_bytes_scored(const rs_ctx* ctx, int B, int beams, int max_len, int vocab, const rs_avsr_search_opts* opts) {
+    RS_GUARD_QUERY(ctx, rs_avsr_search_state_bytes_scored, 0);
     return search_state_bytes(ctx, B, beams, max_len, vocab, opts, true);
 }
 extern "C" size_t rs_avsr_search_state_bytes(const rs_ctx* ctx, int B, int beams, int max_len) {
+    RS_GUARD_QUERY(ctx, rs_avsr_search_state_bytes, 0);
     return rs_avsr_search_state_bytes_opts(ctx, B, beams, max_len, 4, nullptr);
 }
 
 extern "C" int rs_avsr_search_begin_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
                                          size_t state_bytes, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_begin_opts);
     return search_begin(ctx, search, opts, false, B, vocab, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_search_begin_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, int vocab, void* state,
                                            size_t state_bytes, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_begin_scored);
     return search_begin(ctx, search, opts, true, B, vocab, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_search_begin(rs_ctx* ctx, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_begin);
     return rs_avsr_search_begin_opts(ctx, search, nullptr, B, vocab, state, state_bytes, stream);
 }
 
 extern "C" int rs_avsr_search_step_opts(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B,
                                         int vocab, void* state, size_t state_bytes, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_step_opts);
     return search_step(ctx, logits, step, search, opts, false, nullptr, B, vocab, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_search_step_scored(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, const rs_avsr_search_opts* opts,
                                           float* step_scores, int B, int vocab, void* state, size_t state_bytes, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_step_scored);
     return search_step(ctx, logits, step, search, opts, true, step_scores, B, vocab, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_search_step(rs_ctx* ctx, const float* logits, int step, const rs_avsr_search* search, int B, int vocab, void* state, size_t state_bytes,
                                    void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_step);
     return rs_avsr_search_step_opts(ctx, logits, step, search, nullptr, B, vocab, state, state_bytes, stream);
 }
 
 extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, const int32_t** tokens,
                                    const int32_t** src_rows) {
-    if (!ctx) return RS_EINVAL;
+    RS_GUARD(ctx, rs_avsr_search_rows);
     SearchPtrs p;
     Opts op;
     const int rc = check_search(ctx, search, nullptr, B, 0, state, state_bytes, "rs_avsr_search_rows", &p, &op);
@@ -770,30 +774,36 @@ extern "C" int rs_avsr_search_rows(rs_ctx* ctx, const rs_avsr_search* search, in
 
 extern "C" int rs_avsr_search_peek_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                         int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_peek_opts);
     return search_peek(ctx, search, opts, false, B, state, state_bytes, step, tokens, src_rows, run_scores, fin_scores, goes_on_out, stream);
 }
 extern "C" int rs_avsr_search_peek_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                           int step, int32_t* tokens, int32_t* src_rows, float* run_scores, float* fin_scores, int32_t* goes_on_out,
                                           void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_peek_scored);
     return search_peek(ctx, search, opts, true, B, state, state_bytes, step, tokens, src_rows, run_scores, fin_scores, goes_on_out, stream);
 }
 extern "C" int rs_avsr_search_peek(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int step, int32_t* tokens, int32_t* src_rows,
                                    float* run_scores, float* fin_scores, int32_t* goes_on_out, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_peek);
     return rs_avsr_search_peek_opts(ctx, search, nullptr, B, state, state_bytes, step, tokens, src_rows, run_scores, fin_scores, goes_on_out, stream);
 }
 
 extern "C" int rs_avsr_search_finish_opts(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                           int32_t* sequences, int32_t* lengths, float* scores, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_finish_opts);
     return search_finish(ctx, search, opts, nullptr, B, state, state_bytes, sequences, lengths, scores, stream);
 }
 extern "C" int rs_avsr_search_finish_scored(rs_ctx* ctx, const rs_avsr_search* search, const rs_avsr_search_opts* opts, int B, void* state, size_t state_bytes,
                                             int32_t* sequences, int32_t* lengths, float* scores, float* token_scores, float* token_lse, int32_t* beam_indices,
                                             int32_t* steps_run, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_finish_scored);
     const ScoredOut so{token_scores, token_lse, beam_indices, steps_run};
     return search_finish(ctx, search, opts, &so, B, state, state_bytes, sequences, lengths, scores, stream);
 }
 extern "C" int rs_avsr_search_finish(rs_ctx* ctx, const rs_avsr_search* search, int B, void* state, size_t state_bytes, int32_t* sequences, int32_t* lengths,
                                      float* scores, void* stream) {
+    RS_GUARD(ctx, rs_avsr_search_finish);
     return rs_avsr_search_finish_opts(ctx, search, nullptr, B, state, state_bytes, sequences, lengths, scores, stream);
 }
 
@@ -823,7 +833,7 @@ struct StopWatch {              // pinned words the go[] entries are copied to, 
 };
 
 size_t generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts, bool rec) {
-    if (!rs_avsr_dims_of(ctx) || B <= 0 || T <= 0 || beams < 1 || beams > MAXK || max_len < 2 || !opts_ok_for_bytes(opts, beams)) return 0;
+    if (B <= 0 || T <= 0 || beams < 1 || beams > MAXK || max_len < 2 || !opts_ok_for_bytes(opts, beams)) return 0;
     Opts op;
     op.rec = rec;
     if (opts) op.o = *opts;
@@ -834,12 +844,15 @@ size_t generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_
 }  // namespace
 
 extern "C" size_t rs_avsr_generate_state_bytes_opts(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts) {
+    RS_GUARD_QUERY(ctx, rs_avsr_generate_state_bytes_opts, 0);
     return generate_state_bytes(ctx, B, T, beams, max_len, opts, false);
 }
 extern "C" size_t rs_avsr_generate_state_bytes_scored(const rs_ctx* ctx, int B, int T, int beams, int max_len, const rs_avsr_search_opts* opts) {
+    RS_GUARD_QUERY(ctx, rs_avsr_generate_state_bytes_scored, 0);
     return generate_state_bytes(ctx, B, T, beams, max_len, opts, true);
 }
 extern "C" size_t rs_avsr_generate_state_bytes(const rs_ctx* ctx, int B, int T, int beams, int max_len) {
+    RS_GUARD_QUERY(ctx, rs_avsr_generate_state_bytes, 0);
     return rs_avsr_generate_state_bytes_opts(ctx, B, T, beams, max_len, nullptr);
 }
 
@@ -847,10 +860,7 @@ namespace {
 // so null: nothing is recorded (the plain and _opts forms)
 int generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search, const rs_avsr_search_opts* opts,
              const ScoredOut* so, float* step_scores, int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream) {
-    if (!ctx) return RS_EINVAL;
     const rs_avsr_dims* d = rs_avsr_dims_of(ctx);
-    if (!d) return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: defined for an avsr context (rs_avsr_create) only");
-    if (!ctx->finalized) return rs_fail(ctx, RS_ESTATE, "rs_finalize must precede rs_avsr_generate");
     if (!search || !enc || !padding_mask || !sequences || !lengths || !state || T <= 0 || (so && !scored_out_ok(search, *so)))
         return rs_fail(ctx, RS_EINVAL, "rs_avsr_generate: bad argument");
     const bool rec = so != nullptr;
@@ -900,16 +910,19 @@ int generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, in
 extern "C" int rs_avsr_generate_opts(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
                                      const rs_avsr_search_opts* opts, int32_t* sequences, int32_t* lengths, float* scores, void* state, size_t state_bytes,
                                      void* stream) {
+    RS_GUARD(ctx, rs_avsr_generate_opts);
     return generate(ctx, enc, padding_mask, B, T, search, opts, nullptr, nullptr, sequences, lengths, scores, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_generate_scored(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search,
                                        const rs_avsr_search_opts* opts, float* step_scores, int32_t* sequences, int32_t* lengths, float* scores,
                                        float* token_scores, float* token_lse, int32_t* beam_indices, int32_t* steps_run, void* state, size_t state_bytes,
                                        void* stream) {
+    RS_GUARD(ctx, rs_avsr_generate_scored);
     const ScoredOut so{token_scores, token_lse, beam_indices, steps_run};
     return generate(ctx, enc, padding_mask, B, T, search, opts, &so, step_scores, sequences, lengths, scores, state, state_bytes, stream);
 }
 extern "C" int rs_avsr_generate(rs_ctx* ctx, const float* enc, const float* padding_mask, int B, int T, const rs_avsr_search* search, int32_t* sequences,
                                 int32_t* lengths, float* scores, void* state, size_t state_bytes, void* stream) {
+    RS_GUARD(ctx, rs_avsr_generate);
     return rs_avsr_generate_opts(ctx, enc, padding_mask, B, T, search, nullptr, sequences, lengths, scores, state, state_bytes, stream);
 }

@@ -98,11 +98,12 @@ __global__ __launch_bounds__(256) void ctc_softmax_kernel(float* __restrict__ z,
 int rs_launch_sub2d_conv0(rs_ctx* ctx, const float* feats, const int32_t* lens1, int b0, int Bc, int t_max, int T1, int F1,
                           uint16_t* out, hipStream_t s) {
     const rs_dims& d = ctx->d;
+    const rs_conformer& cf = *rs_conformer_of(ctx);
     const int C = d.sub_channels;
     if (d.n_mels > 128 || 2 * (F1 - 1) + 2 >= d.n_mels + 1) return rs_fail(ctx, RS_EINVAL, "conv2d subsampling: n_mels %d / F1 %d", d.n_mels, F1);
     rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)Bc * T1 * F1 * C * 18.0, (double)Bc * (t_max * d.n_mels * 4.0 + (double)T1 * F1 * C * 2.0));
     hipLaunchKernelGGL(sub2d_conv0_kernel<uint16_t>, dim3(T1, Bc), dim3(256), 0, s, feats, lens1, b0, t_max, d.n_mels, T1, F1, C,
-                       ctx->sub_conv0_w, ctx->sub_conv0_b, out);
+                       cf.sub_conv0_w, cf.sub_conv0_b, out);
     prof.end();
     RS_CHECK_LAUNCH(ctx, "sub2d_conv0");
     return RS_OK;
@@ -111,11 +112,12 @@ int rs_launch_sub2d_conv0(rs_ctx* ctx, const float* feats, const int32_t* lens1,
 int rs_launch_sub2d_conv0_f32(rs_ctx* ctx, const float* feats, const int32_t* lens1, int b0, int Bc, int t_max, int T1, int F1,
                               float* out, hipStream_t s) {
     const rs_dims& d = ctx->d;
+    const rs_conformer& cf = *rs_conformer_of(ctx);
     const int C = d.sub_channels;
     if (d.n_mels > 128 || 2 * (F1 - 1) + 2 >= d.n_mels + 1) return rs_fail(ctx, RS_EINVAL, "conv2d subsampling: n_mels %d / F1 %d", d.n_mels, F1);
     rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)Bc * T1 * F1 * C * 18.0, (double)Bc * (t_max * d.n_mels * 4.0 + (double)T1 * F1 * C * 4.0));
     hipLaunchKernelGGL(sub2d_conv0_kernel<float>, dim3(T1, Bc), dim3(256), 0, s, feats, lens1, b0, t_max, d.n_mels, T1, F1, C,
-                       ctx->sub_conv0_w, ctx->sub_conv0_b, out);
+                       cf.sub_conv0_w, cf.sub_conv0_b, out);
     prof.end();
     RS_CHECK_LAUNCH(ctx, "sub2d_conv0_f32");
     return RS_OK;

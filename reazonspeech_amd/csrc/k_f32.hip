@@ -1,9 +1,10 @@
 // k_f32.hip — the float32 PARITY MODE of the encoder (rs_set_option "precision_f32").
 //
 // The reference runs this model in float32 with no autocast (pkg/nemo-asr/src/transcribe.py:26-28, :48-53).  The
-// throughput mode of this library feeds bf16 operands to the matrix cores; this file is the same encoder with float32
-// weights, float32 activations and float32 arithmetic end to end, so that "greedy token ids identical to the float32
-// reference" is a statement about the whole path and not only about the decode loop:
+// throughput mode of this library feeds bf16 operands to the matrix cores; these are the kernels of the same encoder with
+// float32 weights, float32 activations and float32 arithmetic end to end (the call sequence sits next to its bf16 twin in
+// k_conformer.hip), so that "greedy token ids identical to the float32 reference" is a statement about the whole path and
+// not only about the decode loop:
 //
 //   gemm_f32_kernel        every dense contraction on v_mfma_f32_16x16x4_f32 (an exact f32 fma chain; 157 TF/s peak), one
 //                          fixed summation order per output element (ascending 16-blocks, inside a block k = e + 4 kk),
@@ -18,11 +19,6 @@
 #include <stdlib.h>
 
 #include "rs_common.h"
-
-int rs_launch_sub_conv0_dw1_f32(rs_ctx* ctx, const float* feats, const int32_t* lens_stage, int B, int t_max, int T2, int F2,
-                                float* out, hipStream_t s);
-int rs_launch_sub_dw_f32(rs_ctx* ctx, const float* in, const float* w, const float* b, const int32_t* lens_out, int B, int t_in,
-                         int f_in, int t_out, int f_out, float* out, hipStream_t s);
 
 namespace {
 
@@ -670,53 +666,6 @@ __global__ __launch_bounds__(256) void glu_dwconv_silu_f32_kernel(const float* _
     out[((size_t)b * T + t) * d + c] = silu_exact(acc);
 }
 
-struct EncPlanF32 {
-    int T[5], F[5];
-    int32_t* lens;
-    float *sa, *col, *sb, *x, *hn, *big, *ctxb, *posp, *ctc;   // ctc: nullptr without a CTC head
-    int chunk;       // Conv2dSubsampling: utterances per pass of conv0 / patch gather / dense-conv GEMM
-};
-constexpr size_t ENC_F32_SLACK = 256;
-
-EncPlanF32 plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
-    const rs_dims& d = ctx->d;
-    EncPlanF32 p{};
-    p.T[0] = t_max; p.F[0] = d.n_mels;
-    for (int s = 1; s <= d.sub_stages; ++s) { p.T[s] = rs_conv_len(p.T[s - 1], d.sub_kind); p.F[s] = rs_conv_len(p.F[s - 1], d.sub_kind); }
-    const size_t C = d.sub_channels, dm = d.d_model;
-    const size_t Tp = p.T[d.sub_stages] > 0 ? p.T[d.sub_stages] : 1, M = (size_t)B * Tp;
-    size_t widest = (size_t)d.ff_dim;
-    if (3 * dm > widest) widest = 3 * dm;
-    p.lens = a.take<int32_t>((size_t)4 * B);
-    p.chunk = B;
-    if (d.sub_kind == 1) {
-        // the pieces of rs_api.hip's plan_encoder with float32 elements: conv0 output and 3x3 patches of ONE chunk of utterances, the
-        // dense conv's output of the whole batch.  Each chunked buffer stays within 1 GiB and is reserved by rs_sub_chunk_rule's
-        // bound, and the chunk is the smaller of the two rules' so that both reserves cover it.  CONDITION for the chunk to be the
-        // patch matrix's alone, as it was before the conv0 buffer had a rule of its own: T1 F1 <= 9 T2 F2.  It holds for 80 mels
-        // (F1 39, F2 19, T1 <= 4 T2: 39 T1 <= 156 T2 < 171 T2); a front end of very few features (F1 3, F2 1 at T1 4) would run
-        // more, smaller passes than the patch rule asks for, with the same results.
-        const size_t T1 = p.T[1] > 0 ? p.T[1] : 1, T2 = p.T[2] > 0 ? p.T[2] : 1;
-        const rs_sub_chunk col = rs_sub_chunk_rule(T2 * p.F[2] * 9 * C * 4, (size_t)1 << 30, T2, B);
-        const rs_sub_chunk sa = rs_sub_chunk_rule(T1 * p.F[1] * C * 4, (size_t)1 << 30, T2, B);
-        p.chunk = std::min(col.chunk, sa.chunk);
-        p.sa = a.take<float>(sa.reserve / 4);
-        p.col = a.take<float>(col.reserve / 4);
-        p.sb = a.take<float>((size_t)B * T2 * p.F[2] * C);
-    } else {
-        const size_t sub_elems = (size_t)B * p.T[2] * p.F[2] * C;
-        p.sa = a.take<float>(sub_elems);
-        p.sb = a.take<float>(sub_elems);
-    }
-    p.x = a.take<float>(M * dm);
-    p.hn = a.take<float>(M * dm);
-    p.big = a.take<float>(M * widest);
-    p.ctxb = a.take<float>(M * dm);
-    p.posp = a.take<float>((2 * Tp) * dm);
-    p.ctc = d.ctc_vocab > 0 ? a.take<float>(M * (size_t)rs_ctc_pad(d.ctc_vocab)) : nullptr;
-    return p;
-}
-
 }  // namespace
 
 int rs_launch_gemm_f32(rs_ctx* ctx, const float* A, int lda, const float* W, int ldw, float* out, int ldc, int M, int N, int K,
@@ -779,8 +728,8 @@ int rs_launch_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, con
                             const int32_t* lens, int B, int T, float* out, hipStream_t s) {
     if (B <= 0 || T <= 0) return RS_OK;
     const rs_dims& dm = ctx->d;
-    const int hd = dm.d_model / dm.n_heads;
-    if (hd > 256) return rs_fail(ctx, RS_EINVAL, "attention_f32: head_dim %d > 256", hd);
+    const int hd = dm.n_heads > 0 ? dm.d_model / dm.n_heads : 0;
+    if (hd < 1 || hd > 256) return rs_fail(ctx, RS_EINVAL, "attention_f32: head_dim %d (1 .. 256)", hd);
     const dim3 grid((T + 3) / 4, dm.n_heads, B), block(256);
     const float scale = 1.0f / sqrtf((float)hd);
     rs_prof_scope prof(ctx, RS_PROF_ATTN, s, (double)B * dm.n_heads * 3.0 * 2.0 * T * (double)T * hd, (double)B * T * dm.d_model * 4.0 * 4.0);
@@ -867,108 +816,3 @@ extern "C" int rs_debug_gemm_f32_skinny(rs_ctx* ctx, const float* A, int lda, co
     return rs_launch_gemm_f32_skinny(ctx, A, lda, W, ldw, out, ldc, M, N, K, flags, bias, residual, (hipStream_t)stream);
 }
 
-size_t rs_encoder_f32_workspace_bytes(const rs_ctx* ctx, int B, int t_max) {
-    rs_arena a;
-    plan_f32(ctx, B, t_max, a);
-    return a.bytes() + ENC_F32_SLACK;
-}
-
-// The float32 encoder: the call sequence of rs_encoder_forward (rs_api.hip) with float32 operands everywhere and no
-// fusion that moves a rounding (there is none to move: nothing is rounded below float32).
-int rs_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out,
-                           float* joint_enc, int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    const rs_dims& d = ctx->d;
-    const rs_f32_weights& w = ctx->f32;
-    rs_arena arena(workspace);
-    const EncPlanF32 pl = plan_f32(ctx, B, t_max, arena);
-    if (workspace_bytes < arena.bytes() + ENC_F32_SLACK)
-        return rs_fail(ctx, RS_EWORKSPACE, "encoder (float32 mode): workspace %zu < %zu", workspace_bytes, arena.bytes() + ENC_F32_SLACK);
-    int32_t* const lens_stage = pl.lens;
-    float *const sa = pl.sa, *const sb = pl.sb, *const x = pl.x, *const hn = pl.hn, *const big = pl.big, *const ctxb = pl.ctxb, *const posp = pl.posp;
-    const int C = d.sub_channels, dm = d.d_model, ff = d.ff_dim, S = d.sub_stages;
-    const int Tp = pl.T[S], M = B * Tp;
-    int rc;
-#define RS_TRY(call) do { rc = (call); if (rc != RS_OK) return rc; } while (0)
-    auto gemm = [&](const float* A, int lda, const float* W, int K, float* out, int ldc, int Mr, int N, int flags, const float* bias,
-                    float alpha, const float* res) -> int {
-        return rs_launch_gemm_f32(ctx, A, lda, W, K, out, ldc, Mr, N, K, flags, bias, alpha, res, nullptr, 0, 0, s);
-    };
-    // ---- subsampling
-    RS_TRY(rs_launch_enc_lens(ctx, n_frames, B, lens_stage, s));
-    if (Tp <= 0) return rs_fail(ctx, RS_EINVAL, "encoder (float32 mode): %d feature frames are too few for the subsampling", t_max);
-    if (d.sub_kind == 1) {
-        // ESPnet Conv2dSubsampling in float32: conv0 -> 3x3 patches -> the dense conv as one exact-f32 GEMM per chunk of utterances
-        float* const col = pl.col;
-        const int T1 = pl.T[1], F1 = pl.F[1], T2 = pl.T[2], F2 = pl.F[2];
-        for (int b0 = 0; b0 < B; b0 += pl.chunk) {
-            const int bc = B - b0 < pl.chunk ? B - b0 : pl.chunk;
-            RS_TRY(rs_launch_sub2d_conv0_f32(ctx, feats, lens_stage, b0, bc, t_max, T1, F1, sa, s));
-            RS_TRY(rs_launch_im2col3x3s2_f32(ctx, sa, bc, T1, F1, T2, F2, col, s));
-            RS_TRY(rs_launch_gemm_f32(ctx, col, 9 * C, w.sub_conv1_w, 9 * C, sb + (size_t)b0 * T2 * F2 * C, C, bc * T2 * F2, C, 9 * C,
-                                      RS_GEMM_BIAS | RS_GEMM_RELU | RS_GEMM_ROWMASK, ctx->sub_conv1_b, 1.0f, nullptr,
-                                      lens_stage + B + b0, F2, T2, s));
-        }
-    } else
-    RS_TRY(rs_launch_sub_conv0_dw1_f32(ctx, feats, lens_stage, B, t_max, pl.T[2], pl.F[2], sa, s));
-    for (int st = 2; st <= S && d.sub_kind == 0; ++st) {
-        if (st > 2)
-            RS_TRY(rs_launch_sub_dw_f32(ctx, sb, ctx->sub_dw_w[st - 2], ctx->sub_dw_b[st - 2], lens_stage + (st - 1) * B, B,
-                                        pl.T[st - 1], pl.F[st - 1], pl.T[st], pl.F[st], sa, s));
-        RS_TRY(rs_launch_gemm_f32(ctx, sa, C, w.sub_pw_w[st - 2], C, sb, C, B * pl.T[st] * pl.F[st], C, C,
-                                  RS_GEMM_BIAS | RS_GEMM_RELU | RS_GEMM_ROWMASK, ctx->sub_pw_b[st - 2], 1.0f, nullptr,
-                                  lens_stage + (st - 1) * B, pl.F[st], pl.T[st], s));
-    }
-    {
-        const int K = C * pl.F[S];
-        RS_TRY(gemm(sb, K, w.sub_out_w, K, x, dm, M, dm, RS_GEMM_BIAS, ctx->sub_out_b, d.xscaling ? sqrtf((float)dm) : 1.0f, nullptr));
-    }
-    const int32_t* lens = lens_stage + (S - 1) * B;
-    RS_HIP(ctx, hipMemcpyAsync(enc_lens, lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    if (ctx->tap_sub) RS_HIP(ctx, hipMemcpyAsync(ctx->tap_sub, x, (size_t)M * dm * 4, hipMemcpyDeviceToDevice, s));
-    // ---- position rows for this T'
-    const int tcap = (int)((w.pos_table_bytes / ((size_t)dm * 4) + 1) / 2);
-    if (Tp > tcap) return rs_fail(ctx, RS_EINVAL, "encoder (float32 mode): T'=%d exceeds the registered pos.table.f32 capacity %d", Tp, tcap);
-    const float* pos_slice = w.pos_table + (size_t)(tcap - Tp) * dm;
-    const int npos = 2 * Tp - 1;
-    const int RES = RS_GEMM_BIAS | RS_GEMM_RESIDUAL;
-    for (int i = 0; i < d.n_layers; ++i) {
-        const rs_layer_w& L = ctx->layers[i];
-        const rs_layer_w32& L32 = w.layers[i];
-        // 1/2 FFN
-        RS_TRY(rs_launch_layernorm(ctx, x, L.ln_ff1_g, L.ln_ff1_b, M, dm, d.ln_eps, nullptr, hn, s));
-        RS_TRY(gemm(hn, dm, L32.ff1_w1, dm, big, ff, M, ff, RS_GEMM_BIAS | RS_GEMM_SILU, L.ff1_b1, 1.0f, nullptr));
-        RS_TRY(gemm(big, ff, L32.ff1_w2, ff, x, dm, M, dm, RES, L.ff1_b2, 0.5f, x));
-        // rel-pos MHSA
-        RS_TRY(rs_launch_layernorm(ctx, x, L.ln_att_g, L.ln_att_b, M, dm, d.ln_eps, nullptr, hn, s));
-        RS_TRY(gemm(hn, dm, L32.qkv_w, dm, big, 3 * dm, M, 3 * dm, RS_GEMM_BIAS, L.qkv_b, 1.0f, nullptr));
-        RS_TRY(gemm(pos_slice, dm, L32.pos_w, dm, posp, dm, npos, dm, 0, nullptr, 1.0f, nullptr));
-        RS_TRY(rs_launch_attention_f32(ctx, big, posp, L.bias_u, L.bias_v, lens, B, Tp, ctxb, s));
-        RS_TRY(gemm(ctxb, dm, L32.out_w, dm, x, dm, M, dm, RES, L.out_b, 1.0f, x));
-        // conv module (pw1 in NeMo's own row order: values | gates)
-        RS_TRY(rs_launch_layernorm(ctx, x, L.ln_conv_g, L.ln_conv_b, M, dm, d.ln_eps, nullptr, hn, s));
-        RS_TRY(gemm(hn, dm, L32.pw1_w, dm, big, 2 * dm, M, 2 * dm, RS_GEMM_BIAS, L32.pw1_b, 1.0f, nullptr));
-        RS_TRY(rs_launch_glu_dwconv_f32(ctx, big, L.dw_w, L.dw_b, lens, B, Tp, dm, d.conv_kernel, ctxb, s));
-        RS_TRY(gemm(ctxb, dm, L32.pw2_w, dm, x, dm, M, dm, RES, L.pw2_b, 1.0f, x));
-        // 1/2 FFN
-        RS_TRY(rs_launch_layernorm(ctx, x, L.ln_ff2_g, L.ln_ff2_b, M, dm, d.ln_eps, nullptr, hn, s));
-        RS_TRY(gemm(hn, dm, L32.ff2_w1, dm, big, ff, M, ff, RS_GEMM_BIAS | RS_GEMM_SILU, L.ff2_b1, 1.0f, nullptr));
-        RS_TRY(gemm(big, ff, L32.ff2_w2, ff, x, dm, M, dm, RES, L.ff2_b2, 0.5f, x));
-        // output norm, in place (a wave holds its whole row in registers before it stores)
-        RS_TRY(rs_launch_layernorm(ctx, x, L.ln_out_g, L.ln_out_b, M, dm, d.ln_eps, nullptr, x, s));
-        for (size_t k = 0; k < ctx->tap_ids.size(); ++k)
-            if (ctx->tap_ids[k] == i)
-                RS_HIP(ctx, hipMemcpyAsync(ctx->tap_layers + k * (size_t)M * dm, x, (size_t)M * dm * 4, hipMemcpyDeviceToDevice, s));
-    }
-    // ESPnet: the encoder's after_norm on top of the last block's norm_final
-    if (d.final_norm) RS_TRY(rs_launch_layernorm(ctx, x, ctx->final_norm_g, ctx->final_norm_b, M, dm, d.ln_eps, nullptr, x, s));
-    if (enc_out) RS_HIP(ctx, hipMemcpyAsync(enc_out, x, (size_t)M * dm * 4, hipMemcpyDeviceToDevice, s));
-    RS_TRY(gemm(x, dm, w.jenc_w, dm, joint_enc, d.joint_hidden, M, d.joint_hidden, RS_GEMM_BIAS, ctx->jenc_b, 1.0f, nullptr));
-    if (d.ctc_vocab > 0 && (ctx->ctc_probs || ctx->ctc_blank)) {
-        const int Vp = rs_ctc_pad(d.ctc_vocab);
-        float* z = ctx->ctc_probs ? ctx->ctc_probs : pl.ctc;
-        RS_TRY(gemm(x, dm, w.ctc_w, dm, z, Vp, M, Vp, RS_GEMM_BIAS, ctx->ctc_b, 1.0f, nullptr));
-        RS_TRY(rs_launch_ctc_softmax(ctx, z, M, d.ctc_vocab, Vp, d.blank_id, ctx->ctc_blank, s));
-    }
-#undef RS_TRY
-    return RS_OK;
-}

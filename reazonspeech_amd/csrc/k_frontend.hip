@@ -265,10 +265,11 @@ int rs_launch_frontend(rs_ctx* ctx, const float* audio, const int32_t* lens, int
     rs_prof_scope prof(ctx, RS_PROF_FRONTEND, s, (double)B * t_max * (5.0 * 512 * 9 + 3 * 257 + 2 * 600), bytes);
     hipLaunchKernelGGL(logmel_kernel, grid, block, 0, s, p);
     if (d.frontend_kind == 2) {
-    } else if (d.frontend_kind == 1)
+    } else if (d.frontend_kind == 1) {            // (rs_create only: a Conformer context)
+        const rs_conformer& cf = *rs_conformer_of(ctx);
         hipLaunchKernelGGL(feat_mvn_kernel, dim3((t_max * d.n_mels + 255) / 256, B), dim3(256), 0, s, raw, n_frames, t_max, d.n_mels,
-                           ctx->fe_mvn_mean, ctx->fe_mvn_istd, feats);
-    else
+                           cf.fe_mvn_mean, cf.fe_mvn_istd, feats);
+    } else
         hipLaunchKernelGGL(feat_normalize_kernel, dim3(B), dim3(1024), 0, s, raw, n_frames, t_max, d.n_mels, d.norm_eps,
                            feats);
     prof.end();

@@ -259,7 +259,7 @@ int rs_launch_gemm_i8q(rs_ctx* ctx, const float* A, int lda, int group, const fl
 extern "C" int rs_gemm_i8q(rs_ctx* ctx, const float* A, int lda, const int32_t* lens, int group, const int8_t* W, int ldw, const int32_t* colsum,
                            const float* wq, float* out, int ldc, int M, int N, int K, int flags, const float* bias, const float* residual, float* qp,
                            void* stream) {
-    if (!ctx) return RS_EINVAL;
+    RS_GUARD(ctx, rs_gemm_i8q);
     if (M < 0 || N < 0) return rs_fail(ctx, RS_EINVAL, "gemm_i8q: negative size");
     if (M == 0 || N == 0) return RS_OK;
     if (group <= 0 || M % group) return rs_fail(ctx, RS_EINVAL, "gemm_i8q: M (%d) must be a whole number of groups of %d rows", M, group);

@@ -1096,7 +1096,7 @@ int rs_rnnt_greedy_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_
     greedy_layout(ctx, B, arena, st);
     if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK) return rs_fail(ctx, RS_EWORKSPACE, "rnnt: workspace too small");
     st.joint_act = d.joint_act;
-    if (ctx->k2_conv_w) st.unk = ctx->k2 ? rs_k2_unk_id(ctx) : -1;
+    if (ctx->k2_conv_w) st.unk = rs_k2_unk_id(ctx);
     const size_t state_bytes = (size_t)L * B * H * 4;
     const int nct = (V + 63) / 64, Vpad = (V + 15) / 16 * 16;
     // the screened joint keeps a row's logits (<= 48 x 64) and a K slice (<= 8 blocks of 16) in registers, J / 32 <= 20 weight fragments

@@ -195,6 +195,7 @@ int rs_launch_enc_lens(rs_ctx* ctx, const int32_t* n_frames, int B, int32_t* len
 int rs_launch_sub_conv0_dw1(rs_ctx* ctx, const float* feats, const int32_t* lens_stage, int B, int t_max, int T2,
                             int F2, uint16_t* out, hipStream_t s) {
     const rs_dims& d = ctx->d;
+    const rs_conformer& cf = *rs_conformer_of(ctx);
     const int C = d.sub_channels;
     if (C > 256 || (C % 64)) return rs_fail(ctx, RS_EINVAL, "subsampling: channels %d unsupported (<=256, %%64)", C);
     const int F1 = (d.n_mels + 2 - 3) / 2 + 1;
@@ -205,7 +206,7 @@ int rs_launch_sub_conv0_dw1(rs_ctx* ctx, const float* feats, const int32_t* lens
     const double bytes = (double)B * t_max * d.n_mels * 4.0 + (double)B * T2 * F2 * C * 2.0;
     rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, flops, bytes);
     hipLaunchKernelGGL(sub_conv0_dw1_kernel<uint16_t>, dim3(T2, B), dim3(C), lds, s, feats, lens_stage, B, t_max, d.n_mels, T2,
-                       F1, F2, C, ctx->sub_conv0_w, ctx->sub_conv0_b, ctx->sub_dw_w[0], ctx->sub_dw_b[0], out);
+                       F1, F2, C, cf.sub_conv0_w, cf.sub_conv0_b, cf.sub_dw_w[0], cf.sub_dw_b[0], out);
     prof.end();
     RS_CHECK_LAUNCH(ctx, "sub_conv0_dw1");
     return RS_OK;
@@ -230,6 +231,7 @@ int rs_launch_sub_dw(rs_ctx* ctx, const uint16_t* in, const float* w, const floa
 int rs_launch_sub_conv0_dw1_f32(rs_ctx* ctx, const float* feats, const int32_t* lens_stage, int B, int t_max, int T2, int F2,
                                 float* out, hipStream_t s) {
     const rs_dims& d = ctx->d;
+    const rs_conformer& cf = *rs_conformer_of(ctx);
     const int C = d.sub_channels;
     if (C > 256 || (C % 64)) return rs_fail(ctx, RS_EINVAL, "subsampling: channels %d unsupported (<=256, %%64)", C);
     const int F1 = (d.n_mels + 2 - 3) / 2 + 1;
@@ -238,7 +240,7 @@ int rs_launch_sub_conv0_dw1_f32(rs_ctx* ctx, const float* feats, const int32_t* 
     rs_prof_scope prof(ctx, RS_PROF_SUBSAMPLE, s, (double)B * T2 * F2 * C * 2.0 * (6 * 9 + 9),
                        (double)B * t_max * d.n_mels * 4.0 + (double)B * T2 * F2 * C * 4.0);
     hipLaunchKernelGGL(sub_conv0_dw1_kernel<float>, dim3(T2, B), dim3(C), 0, s, feats, lens_stage, B, t_max, d.n_mels, T2, F1, F2, C,
-                       ctx->sub_conv0_w, ctx->sub_conv0_b, ctx->sub_dw_w[0], ctx->sub_dw_b[0], out);
+                       cf.sub_conv0_w, cf.sub_conv0_b, cf.sub_dw_w[0], cf.sub_dw_b[0], out);
     prof.end();
     RS_CHECK_LAUNCH(ctx, "sub_conv0_dw1_f32");
     return RS_OK;

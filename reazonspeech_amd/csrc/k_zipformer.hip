@@ -58,7 +58,7 @@ struct rs_k2_layer {
     const float *pos_proj, *cm_dw_w[2], *cm_dw_b[2], *norm_bias, *norm_scale, *bypass, *bypass_mid;
 };
 
-struct rs_k2 {
+struct rs_k2 : rs_family_state {
     rs_k2_dims d{};
     std::vector<std::vector<rs_k2_layer>> stacks;
     rs_k2_linear conv2, cnx_pw1, cnx_pw2, emb_out, jenc;     // (ctx->jenc_w / jenc_b repeat jenc.w / jenc.b for the shared decode)
@@ -1210,7 +1210,7 @@ struct K2Plan : K2Geom {
 constexpr size_t K2_SLACK = 256;
 
 K2Plan k2_plan(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
-    const rs_k2& k = *ctx->k2;
+    const rs_k2& k = *rs_k2_of(ctx);
     const rs_k2_dims& d = k.d;
     K2Plan p{};
     static_cast<K2Geom&>(p) = k2_geom(d, t_max);
@@ -1258,7 +1258,7 @@ struct K2PlanF32 : K2Geom {
 };
 
 K2PlanF32 k2_plan_f32(const rs_ctx* ctx, int B, int t_max, rs_arena& a) {
-    const rs_k2& k = *ctx->k2;
+    const rs_k2& k = *rs_k2_of(ctx);
     const rs_k2_dims& d = k.d;
     K2PlanF32 p{};
     static_cast<K2Geom&>(p) = k2_geom(d, t_max);
@@ -1352,21 +1352,18 @@ K2Pieces k2_pieces(const rs_k2_dims& d, float* const* stackout) {
     return pc;
 }
 
-void k2_free(rs_k2* k) { delete k; }
-
 }  // namespace
 
 extern "C" int rs_k2_create(rs_ctx** out, int device, const rs_k2_dims* dims) {
     if (!out || !dims) return RS_EINVAL;
     *out = nullptr;
     rs_ctx* ctx = new (std::nothrow) rs_ctx();
-    if (!ctx) return RS_EINVAL;
+    rs_k2* k = ctx ? new (std::nothrow) rs_k2() : nullptr;
+    if (!k) { delete ctx; return RS_EINVAL; }
     *out = ctx;
     ctx->device = device;
-    rs_k2* k = new (std::nothrow) rs_k2();
-    if (!k) return rs_fail(ctx, RS_EINVAL, "out of memory");
-    ctx->k2 = k;
-    ctx->k2_free = k2_free;
+    ctx->family = RS_FAM_ZIPFORMER;
+    ctx->state.reset(k);
     k->d = *dims;
     const rs_k2_dims& d = k->d;
     if (d.n_stacks < 1 || d.n_stacks > 8) return rs_fail(ctx, RS_EINVAL, "zipformer: 1..8 stacks");
@@ -1401,14 +1398,14 @@ extern "C" int rs_k2_create(rs_ctx** out, int device, const rs_k2_dims* dims) {
 }
 
 extern "C" int rs_k2_encoder_set_taps(rs_ctx* ctx, float* embed_out, float* stack_out) {
-    if (!ctx || !ctx->k2) return RS_EINVAL;
-    ctx->k2->tap_embed = embed_out;
-    ctx->k2->tap_stacks = stack_out;
+    RS_GUARD(ctx, rs_k2_encoder_set_taps);
+    rs_k2_of(ctx)->tap_embed = embed_out;
+    rs_k2_of(ctx)->tap_stacks = stack_out;
     return RS_OK;
 }
 
 int rs_k2_finalize_impl(rs_ctx* ctx) {
-    rs_k2& k = *ctx->k2;
+    rs_k2& k = *rs_k2_of(ctx);
     const rs_k2_dims& d = k.d;
     K2Readers r(ctx);
     rs_weights& w = r.w16;
@@ -1503,7 +1500,8 @@ int rs_k2_finalize_impl(rs_ctx* ctx) {
     return RS_OK;
 }
 
-int rs_k2_unk_id(const rs_ctx* ctx) { return ctx->k2 ? ctx->k2->d.unk_id : -1; }
+rs_k2* rs_k2_of(const rs_ctx* ctx) { return ctx && ctx->family == RS_FAM_ZIPFORMER ? static_cast<rs_k2*>(ctx->state.get()) : nullptr; }
+int rs_k2_unk_id(const rs_ctx* ctx) { return rs_k2_of(ctx) ? rs_k2_of(ctx)->d.unk_id : -1; }
 
 int rs_k2_enc_frames_impl(const rs_ctx* ctx, int n_feat) {
     (void)ctx;
@@ -1523,7 +1521,7 @@ static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int3
 
 int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out, float* joint_enc,
                                int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    rs_k2& k = *ctx->k2;
+    rs_k2& k = *rs_k2_of(ctx);
     const rs_k2_dims& d = k.d;
     if (t_max < 9) return rs_fail(ctx, RS_EINVAL, "zipformer: %d feature frames are too few for encoder_embed (9 are needed)", t_max);
     if (ctx->precision_f32 || ctx->precision_i8) return rs_k2_encoder_forward_f32(ctx, feats, n_frames, B, t_max, enc_out, joint_enc, enc_lens, workspace, workspace_bytes, s);
@@ -1721,7 +1719,7 @@ int rs_k2_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n
 // recipe "fp32" is its line-by-line counterpart).
 static int rs_k2_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out, float* joint_enc,
                                      int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    rs_k2& k = *ctx->k2;
+    rs_k2& k = *rs_k2_of(ctx);
     const rs_k2_dims& d = k.d;
     rs_arena arena(workspace);
     const K2PlanF32 pl = k2_plan_f32(ctx, B, t_max, arena);

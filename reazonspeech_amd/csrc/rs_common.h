@@ -3,12 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/rs_asr.h"
 #include "rs_arena.h"
+#include "rs_family.h"
 #include "rs_knobs.h"
 #include "rs_tensors.h"
 
@@ -99,23 +101,13 @@ struct rs_f32_weights {
     size_t pos_table_bytes = 0;
 };
 
-struct rs_k2;                       // the Zipformer family's resolved weights and dimensions (k_zipformer.hip)
-struct rs_avsr;                     // the AV-HuBERT family's (k_avsr.hip)
+// A family's own state: resolved weights, dimensions, taps.  The context owns exactly one, made by its create function.
+struct rs_family_state { virtual ~rs_family_state() = default; };
 
-struct rs_ctx {
-    int device = 0;
-    rs_k2* k2 = nullptr;            // non-null: a context made by rs_k2_create (reazonspeech.k2.asr); the stage entry points dispatch on it
-    void (*k2_free)(rs_k2*) = nullptr;
-    rs_avsr* avsr = nullptr;        // non-null: a context made by rs_avsr_create (reazonspeech.avsr); only the rs_avsr_* stage entry points apply
-    void (*avsr_free)(rs_avsr*) = nullptr;
-    rs_dims d{};
+// The Conformer family (rs_create: NeMo and ESPnet, told apart by rs_dims.frontend_kind / sub_kind / final_norm / ctc_vocab);
+// filled by k_conformer.hip.  The Zipformer family's rs_k2 lives in k_zipformer.hip, the AV-HuBERT family's rs_avsr in k_avsr.hip.
+struct rs_conformer : rs_family_state {
     int head_dim = 0, sub_freq = 0;
-    bool finalized = false;
-    std::string err;
-    rs_tensor_table tensors;        // rs_set_tensor: name -> (pointer, bytes); read through rs_weights (below) by every rs_finalize
-    // resolved weights
-    const float *fe_window = nullptr, *fe_fb_w = nullptr, *fe_twiddle = nullptr;
-    const int32_t* fe_fb_idx = nullptr;
     const float *sub_conv0_w = nullptr, *sub_conv0_b = nullptr;
     const float *sub_dw_w[4] = {}, *sub_dw_b[4] = {};
     const uint16_t* sub_pw_w[4] = {};
@@ -123,7 +115,6 @@ struct rs_ctx {
     const uint16_t* sub_out_w = nullptr;
     const float* sub_out_b = nullptr;
     std::vector<rs_layer_w> layers;
-    // ESPnet family (rs_dims.frontend_kind / sub_kind / final_norm / ctc_vocab)
     const float *fe_mvn_mean = nullptr, *fe_mvn_istd = nullptr;
     const uint16_t* sub_conv1_w = nullptr;
     const float* sub_conv1_b = nullptr;
@@ -131,36 +122,54 @@ struct rs_ctx {
     const uint16_t* ctc_w = nullptr;
     const float* ctc_b = nullptr;
     float *ctc_probs = nullptr, *ctc_blank = nullptr;     // rs_encoder_set_ctc_out
+    const uint16_t* pos_table = nullptr;                  // "pos.table": bf16 [2*Tcap-1][d]
+    size_t pos_table_bytes = 0;
+    rs_f32_weights f32;
+    // parity taps (rs_encoder_set_taps): copies of the residual stream taken inside rs_encoder_forward
+    float* tap_sub = nullptr;
+    float* tap_layers = nullptr;
+    std::vector<int> tap_ids;
+    // options (rs_set_option)
+    int defer_out_norm = 1;         // 1 = a layer's output norm is applied by the next layer's first residual GEMM (f32 rows not stored); bit-identical to 0
+    int fuse_glu = 1;               // conv module: 1 = GLU in the pw1 GEMM epilogue (every batch size: one rounding point, batch-invariant);
+                                    // 0 = plain pw1 product, GLU in the depthwise kernel ($RS_FUSE_GLU; the layout tests set the option)
+};
+struct rs_k2;
+struct rs_avsr;
+
+struct rs_ctx {
+    int device = 0;
+    rs_family family = RS_FAM_CONFORMER;            // set once by rs_create / rs_k2_create / rs_avsr_create
+    std::unique_ptr<rs_family_state> state;         // that family's own state: read through rs_conformer_of / rs_k2_of / rs_avsr_of
+    rs_dims d{};
+    bool finalized = false;
+    std::string err;
+    rs_tensor_table tensors;        // rs_set_tensor: name -> (pointer, bytes); read through rs_weights (below) by every rs_finalize
+    // front-end tables
+    const float *fe_window = nullptr, *fe_fb_w = nullptr, *fe_twiddle = nullptr;
+    const int32_t* fe_fb_idx = nullptr;
+    // decoder and joint
     const uint16_t* jenc_w = nullptr;
     const float* jenc_b = nullptr;
     const float* lstm_w4[8] = {};   // optional "pred.lstm{l}.w4": fragment-major with rows permuted to (unit group, gate, unit)
-    const float* k2_conv_w = nullptr;   // stateless decoder (Zipformer family): grouped Conv1d over the last two tokens, f32 [D][4][2]
+    const float* k2_conv_w = nullptr;   // stateless decoder: grouped Conv1d over the last two tokens, f32 [D][4][2]
     const float *embed = nullptr, *lstm_w[8] = {}, *lstm_b[8] = {}, *jpred_w = nullptr, *jpred_b = nullptr,
                 *jout_w = nullptr, *jout_b = nullptr;
     // screened joint (optional tensors joint.out.w16 / .wrm / .bpad / .wmax; k_rnnt.hip)
     const uint16_t* jout_w16 = nullptr;
     const float *jout_wrm = nullptr, *jout_bpad = nullptr, *jout_wmax = nullptr;
+    // options (rs_set_option)
     bool decode_screen = true;
     bool decode_narrow = true;      // narrow-tile LSTM / projection kernels (k_rnnt.hip)
-    bool gemm_f32_x3 = false;       // rs_launch_gemm_f32 / rs_launch_conv3x3_f32 multiply with three bf16 terms per float32 product (k_f32.hip X3; avsr only)
-    int k2_conv2_fused = -1;        // Zipformer conv2 with its patches gathered into LDS: -1 = the table's RS_K2_CONV2_FUSED (default 1); rs_set_option("k2_conv2_fused")
-    int k2_cnx_fused = -1;          // Zipformer ConvNeXt pointwise pair as one kernel: -1 = the table's RS_K2_CNX_FUSED (default 1); rs_set_option("k2_cnx_fused")
-    // position table cache: the caller registers "pos_table.<T>" tensors (bf16 [2T-1][d])
-    // options (rs_set_option)
+    bool gemm_f32_x3 = false;       // rs_launch_gemm_f32 / rs_launch_conv3x3_f32 multiply with three bf16 terms per float32 product (k_f32.hip X3)
+    int k2_conv2_fused = -1;        // conv2 with its patches gathered into LDS: -1 = the table's RS_K2_CONV2_FUSED (default 1); rs_set_option("k2_conv2_fused")
+    int k2_cnx_fused = -1;          // ConvNeXt pointwise pair as one kernel: -1 = the table's RS_K2_CNX_FUSED (default 1); rs_set_option("k2_cnx_fused")
     int n_cus = 0;                  // compute units of the device (rs_n_cus: queried on first use)
-    int defer_out_norm = 1;         // 1 = a layer's output norm is applied by the next layer's first residual GEMM (f32 rows not stored); bit-identical to 0
-    int fuse_glu = 1;               // conv module: 1 = GLU in the pw1 GEMM epilogue (every batch size: one rounding point, batch-invariant);
-                                    // 0 = plain pw1 product, GLU in the depthwise kernel ($RS_FUSE_GLU; the layout tests set the option)
     bool has_f32 = false;           // the "*.f32" tensors of the float32 parity mode are registered (all or none)
-    int precision_f32 = 0;          // rs_set_option("precision_f32"): 1 = rs_encoder_forward runs k_f32.hip's float32 encoder
-    bool has_i8 = false;            // Zipformer: at least one quantized Linear ("<name>.i8") is registered
-    int precision_i8 = 0;           // rs_set_option("precision_i8") (Zipformer only): the float32 encoder with its quantized Linears ("*.i8") on k_int8.hip
-    rs_f32_weights f32;
+    int precision_f32 = 0;          // rs_set_option("precision_f32"): 1 = rs_encoder_forward runs the float32 encoder
+    bool has_i8 = false;            // at least one quantized Linear ("<name>.i8") is registered
+    int precision_i8 = 0;           // rs_set_option("precision_i8"): the float32 encoder with its quantized Linears ("*.i8") on k_int8.hip
     bool env_read = false;          // the table's context defaults were applied (once, by the first rs_finalize; rs_set_option wins afterwards)
-    // parity taps (rs_encoder_set_taps): copies of the residual stream taken inside rs_encoder_forward
-    float* tap_sub = nullptr;
-    float* tap_layers = nullptr;
-    std::vector<int> tap_ids;
     // k_gemm_bf16.hip, register-resident weight form ($RS_GEMM_BREG): fragment-major copies of registered GEMM weights (made on first
     // use, owned by the context) and a scratch for operands that are not registered tensors (re-shuffled on every launch)
     std::unordered_map<const void*, void*> wfm;
@@ -172,12 +181,33 @@ struct rs_ctx {
     int32_t prof_tag[4] = {0, 0, 0, 0};   // (M, N, K, flags) of the launch about to be bracketed (set by the GEMM launcher)
 };
 
+// A context's family state as its own type; nullptr for a context of another family (and for a null context).
+inline rs_conformer* rs_conformer_of(const rs_ctx* ctx) {
+    return ctx && ctx->family == RS_FAM_CONFORMER ? static_cast<rs_conformer*>(ctx->state.get()) : nullptr;
+}
+rs_k2* rs_k2_of(const rs_ctx* ctx);       // k_zipformer.hip
+rs_avsr* rs_avsr_of(const rs_ctx* ctx);   // k_avsr.hip
+
 // Opt-in for more than 64 KiB of dynamic LDS, once per (device, kernel): the attribute is per device and the
 // first launch of a kernel can come from any thread (the decode worker and the encoder thread both start
 // kernels), so the bookkeeping is a mutex-guarded set keyed by the context's device — not a function-local flag.
 int rs_ensure_dynamic_lds(rs_ctx* ctx, const void* func, int bytes);
 
 int rs_fail(rs_ctx* ctx, int code, const char* fmt, ...);
+
+// The family guard (rs_family.h), first statement of every exported function that takes a context.  RS_GUARD returns the refusal's
+// code with its text in the context; RS_GUARD_QUERY is for the size and frame-count queries, which return `zero` and write nothing.
+inline int rs_guard(rs_ctx* ctx, rs_entry e) {
+    char msg[512];
+    const int rc = rs_family_guard(e, ctx != nullptr, ctx ? ctx->family : RS_FAM_CONFORMER, ctx && ctx->finalized, msg, sizeof msg);
+    if (rc != RS_OK && ctx) ctx->err = msg;
+    return rc;
+}
+inline bool rs_guard_query(const rs_ctx* ctx, rs_entry e) {
+    return rs_family_guard(e, ctx != nullptr, ctx ? ctx->family : RS_FAM_CONFORMER, ctx && ctx->finalized, nullptr, 0) == RS_OK;
+}
+#define RS_GUARD(ctx, entry) do { if (const int _g = rs_guard((ctx), RS_ENTRY_##entry); _g != RS_OK) return _g; } while (0)
+#define RS_GUARD_QUERY(ctx, entry, zero) do { if (!rs_guard_query((ctx), RS_ENTRY_##entry)) return zero; } while (0)
 
 // The registered tensors as typed pointers (rs_tensors.h's sticky reader): the first failing get() is kept, every later one does
 // nothing and leaves its output alone; a finalize calls fail() where it needs the pointers to be good.
@@ -286,9 +316,10 @@ int rs_launch_glu_dwconv_f32(rs_ctx* ctx, const float* x, const float* w, const 
 int rs_launch_i8_range(rs_ctx* ctx, const float* A, int lda, const int32_t* lens, int group, int n_groups, int K, float* qp, hipStream_t s);
 int rs_launch_gemm_i8q(rs_ctx* ctx, const float* A, int lda, int group, const float* qp, const int8_t* W, int ldw, const int32_t* colsum,
                        const float* wq, float* out, int ldc, int M, int N, int K, int flags, const float* bias, const float* residual, hipStream_t s);
-size_t rs_encoder_f32_workspace_bytes(const rs_ctx* ctx, int B, int t_max);
-int rs_encoder_forward_f32(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out,
-                           float* joint_enc, int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s);
+int rs_launch_sub_conv0_dw1_f32(rs_ctx* ctx, const float* feats, const int32_t* lens_stage, int B, int t_max, int T2, int F2,
+                                float* out, hipStream_t s);
+int rs_launch_sub_dw_f32(rs_ctx* ctx, const float* in, const float* w, const float* b, const int32_t* lens_out, int B, int t_in,
+                         int f_in, int t_out, int f_out, float* out, hipStream_t s);
 int rs_launch_enc_lens(rs_ctx* ctx, const int32_t* n_frames, int B, int32_t* lens_out, hipStream_t s);
 // ESPnet family (k_espnet.hip)
 int rs_launch_sub2d_conv0(rs_ctx* ctx, const float* feats, const int32_t* lens1, int b0, int Bc, int t_max, int T1, int F1,
@@ -300,7 +331,11 @@ int rs_launch_sub2d_conv0_f32(rs_ctx* ctx, const float* feats, const int32_t* le
 int rs_launch_im2col3x3s2_f32(rs_ctx* ctx, const float* in, int Bc, int T1, int F1, int T2, int F2, float* out, hipStream_t s);
 // rows of the registered CTC head ("ctc.w" / "ctc.b") and row pitch of the posteriors: the vocabulary padded to a multiple of 4
 static inline int rs_ctc_pad(int v) { return (v + 3) / 4 * 4; }
-// Zipformer family (k_zipformer.hip): the entry points of rs_api.hip dispatch to these when ctx->k2 is set
+// the families' parts of the shared entry points (k_conformer.hip, k_zipformer.hip, k_avsr.hip)
+int rs_conformer_finalize_impl(rs_ctx* ctx);
+size_t rs_conformer_workspace_bytes_impl(const rs_ctx* ctx, int B, int t_max);
+int rs_conformer_encoder_forward_impl(rs_ctx* ctx, const float* feats, const int32_t* n_frames, int B, int t_max, float* enc_out, float* joint_enc,
+                                      int32_t* enc_lens, void* workspace, size_t workspace_bytes, hipStream_t s);
 int rs_avsr_finalize_impl(rs_ctx* ctx);
 const rs_avsr_dims* rs_avsr_dims_of(const rs_ctx* ctx);   // k_avsr.hip: nullptr unless an avsr context
 int rs_k2_finalize_impl(rs_ctx* ctx);
