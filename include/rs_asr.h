@@ -620,10 +620,44 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
                          float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- hotwords (contextual biasing) in the ALSD beam search — added within ABI 7 ---------------------
+ * gives the LSTM transducers (the NeMo family: FastConformer-RNNT, whose checkpoint ships `strategy: alsd`) what
+ * rs_rnnt_mbs_hotwords gives the Zipformer family.  [UPSTREAM] NeMo's align_length_sync_decoding has no hotword rule: the
+ * semantics are this project's.  The graph (rs_hotwords, graph_of), `step` and `Finalize` are the ones stated above for
+ * rs_rnnt_mbs_hotwords; the search is rs_rnnt_alsd with these additions for an utterance b whose graph_of[b] >= 0:
+ *   every hypothesis carries a context_state, a node of its utterance's graph; the start hypothesis stands at the graph's root.
+ *   expansion of a hypothesis with score hs and state s: the `beam` best non-blank tokens are picked by raw logit as in
+ *   rs_rnnt_alsd.  The blank candidate is unchanged: hs + (z[blank] - lse), state s.  A label candidate v takes
+ *   (delta, s') = step(s, v); its score is (hs + (z[v] - lse)) + delta, in that float32 order, its state s'.
+ *   selection of the `beam` best candidates RANKS THE BOOSTED SCORES, ties as in rs_rnnt_alsd (the lower candidate index first).
+ *   This differs from rs_rnnt_mbs_hotwords on purpose: there the bonus is added after the selection, here it is part of the
+ *   ranking, so a phrase continuation inside its hypothesis's top `beam` can overtake.  Recombination is unchanged: equal label
+ *   sequences have equal states by construction, and the first occurrence's state stays.
+ *   a hypothesis recorded as finished (a blank taken at the last frame) is recorded with sc + (-node_score(state)) (Finalize),
+ *   sc its score after recombination; the normalised score compared with the best so far is computed from that value.  The
+ *   "nothing finished: the best of the beam" exit applies the same Finalize to every beam entry before comparing.
+ *   scores[b] = the winner's score including its net bonus.  A new hypothesis's state is its candidate's state.
+ * An utterance without a graph inside a hotword call yields the bits of rs_rnnt_alsd.  All numbers float32 in the order
+ * csrc/k_rnnt_alsd.hip states and tests/alsd_hotwords_checker.c restates (bit for bit); scores that are multiples of 0.5 make
+ * every graph quantity exact.  The walk on the device is the one of rs_rnnt_mbs_hotwords (csrc/k_rnnt_hotwords.h): counted loops
+ * only, an index outside the table is the root and is never dereferenced; validate a table with rs_hotwords_check before upload.
+ * rs_rnnt_alsd_hotwords with hw == NULL, n_graphs == 0 or graph_of == NULL launches the plain kernels of rs_rnnt_alsd (the same
+ * bits); otherwise the hotword form of the selection kernel runs: still six launches per alignment step, no further host round
+ * trip.  Workspace: rs_rnnt_alsd_hotwords_workspace_bytes, the plain layout plus one state per hypothesis row (0 for invalid
+ * arguments or a context that is not finalized).  Errors as rs_rnnt_alsd, and RS_EINVAL for negative counts or null arrays;
+ * RS_EINVAL for a Zipformer or AV-HuBERT context.  rs_rnnt_token_scores on the result reports the model's unmodified
+ * distribution (no bonus). */
+size_t rs_rnnt_alsd_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio,
+                                             int max_target_abs);
+int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
+                          double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids,
+                          int32_t* steps, int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- token log-probabilities of a finished transducer search — added within ABI 7 ----------------
  * gives what NeMo's Hypothesis.token_confidence (preserve_token_confidence, method max_prob), sherpa-onnx's per-token log-probs
  * and ESPnet's scored hypotheses give: how sure the model was of every token it emitted.  A teacher-forced pass over the OUTPUT
- * of any search of this header (rs_rnnt_greedy, rs_rnnt_alsd, rs_rnnt_beam, rs_rnnt_mbs / _hotwords); it runs after the search,
+ * of any search of this header (rs_rnnt_greedy, rs_rnnt_alsd / _hotwords, rs_rnnt_beam, rs_rnnt_mbs / _hotwords); it runs after the search,
  * shares none of its kernels' state and leaves ids / frames / n_ids as they are.  For token u of utterance b, emitted at frame t:
  *     logp[b][u] = z[id] - logsumexp(z),   z = W_out . act(f[b][t] + g(y_<u)) + b_out
  * with g(y_<u) the prediction network's output after the start context and the first u labels: the model's unmodified

@@ -16,8 +16,25 @@
 //        buffers), each new row's parent row, and the work lists of the next step
 //   alsd_reorder_kernel   new row <- parent row's prediction-network state (h, c, g), ping-pong
 //   LSTM x L + joint.pred over the rows that took a token (rnnt_lstm4 / rnnt_pred16 or the wide variants)
+//
+// HOTWORDS (rs_rnnt_alsd_hotwords; the graph, `step` and `Finalize` are stated in include/rs_asr.h, the walk is k_rnnt_hotwords.h,
+// shared with the modified beam search).  NeMo's ALSD has no hotword rule; this one is the project's.  Every hypothesis row carries
+// a node of its utterance's graph (AlsdHw.ctx, ping-pong like the records; the start hypothesis stands at the root).  Phase 1: the
+// W best non-blank tokens are picked by raw logit as in the plain form; the blank candidate keeps score and state; a label
+// candidate v takes (delta, s') = step(s, v), its score is (hs + (z[v] - lse)) + delta, its state s' — lane 0 of the hypothesis's
+// wave walks the graph, at most W counted walks, the states live in LDS next to c_tok.  Phase 2 RANKS THE BOOSTED SCORES (the
+// modified beam search adds its bonus after the selection; here a phrase continuation inside its hypothesis's top W can overtake);
+// recombination is unchanged (equal label sequences have equal states; the first occurrence's stays).  A hypothesis recorded as
+// finished is recorded with sc + (-node_score[state]) (Finalize), sc its score after recombination, and its normalised score is
+// computed from that value; the "nothing finished" exit does the same to every beam entry before comparing.  Phase 3 writes the
+// new row's state.  It is the hotword form of alsd_init_kernel / alsd_select_kernel (template parameter HW): no further launch,
+// no host round trip.  The plain instantiations are the ones launched when no utterance of the call has a graph; inside the
+// hotword form a workgroup whose utterance has none takes the plain statements.  Restated by tests/alsd_hotwords_checker.c.
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
+#include "k_rnnt_hotwords.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -42,11 +59,18 @@ struct AlsdState {
     int cap;
 };
 
+struct AlsdNoHw {};      // the kernel argument of the plain form
+struct AlsdHw {          // hotwords: the graphs of the call and the node each hypothesis row stands at
+    RnntHw t;
+    int32_t* ctx[2];     // [rows], ping-pong like AlsdState's records
+};
+
 // label budget of an utterance with T frames (oracle/alsd.py: a float is a multiple of T, an int is absolute)
 __host__ __device__ inline int alsd_budget(int T, double ratio, int abs_len) { return abs_len >= 0 ? abs_len : (int)(ratio * (double)T); }
 
+template <bool HW>
 __global__ void alsd_init_kernel(DecodeState st, AlsdState as, const int32_t* __restrict__ enc_lens, int B, int W, int blank,
-                                 double ratio, int abs_len) {
+                                 double ratio, int abs_len, std::conditional_t<HW, AlsdHw, AlsdNoHw> hw) {
     // single workgroup: the start hypothesis of every utterance and the first work lists, in row order
     __shared__ int n_alive_s;
     if (threadIdx.x == 0) n_alive_s = 0;
@@ -55,6 +79,7 @@ __global__ void alsd_init_kernel(DecodeState st, AlsdState as, const int32_t* __
         const int row = b * W;
         as.len[0][row] = 0; as.score[0][row] = 0.0f; as.n_hyp[0][b] = 1;
         as.fin_n[b] = -1; as.fin_norm[b] = 0.0f; as.fin_score[b] = 0.0f; as.done[b] = 0;
+        if constexpr (HW) { const int r = hw_root(hw.t, b); hw.ctx[0][row] = r < 0 ? 0 : r; }
         st.token[row] = blank; st.tcur[row] = 0; st.act[b] = row;
         const int T = enc_lens[b];
         if (T > 0 && T + alsd_budget(T, ratio, abs_len) > 0) st.alive[atomicAdd(&n_alive_s, 1)] = row;
@@ -70,11 +95,12 @@ __device__ __forceinline__ int cand_len(int parent_len, int tok) { return parent
 // NVR > 0: the logits row of a hypothesis is read ONCE into NVR registers per lane (V <= 64 NVR), every load in flight before the
 // first comparison; the scan for the maximum / the W best and the exp-sum then walk the registers in the same ascending order as
 // the two memory passes of the NVR = 0 form — identical arithmetic, one memory round trip instead of two chains of 47.
-template <int NVR>
+// HW: the hotword form (see the head of this file); the plain form is the same text without the `if constexpr (HW)` statements.
+template <int NVR, bool HW>
 __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
     DecodeState st, AlsdState as, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int B, int W,
     int V, int blank, int i, double ratio, int abs_len, int score_norm, int merge, int out_cap, int32_t* __restrict__ ids,
-    int32_t* __restrict__ steps, int32_t* __restrict__ n_ids, float* __restrict__ scores) {
+    int32_t* __restrict__ steps, int32_t* __restrict__ n_ids, float* __restrict__ scores, std::conditional_t<HW, AlsdHw, AlsdNoHw> hw) {
     const int b = blockIdx.x;
     if (as.done[b]) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -88,6 +114,9 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
     __shared__ float c_score[MAX_CAND];
     __shared__ int c_tok[MAX_CAND];
     __shared__ int c_ok[MAX_CAND];
+    __shared__ int c_state[HW ? MAX_CAND : 1];   // hotwords: the context state of each candidate
+    int root = -1;                               // hotwords: the root of the utterance's graph, -1 = it has none
+    if constexpr (HW) root = hw_root(hw.t, b);
     __shared__ int s_sel[MAX_BEAM];        // selected candidate of beam position j
     __shared__ float s_score[MAX_BEAM];    // its score after recombination
     __shared__ int s_keep[MAX_BEAM];       // beam position written to new slot k
@@ -162,6 +191,11 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             const float hs = as.score[p][row];
             const int base = wave * (W + 1);
             if (lane == 0) { c_score[base] = hs + (zr[blank] - lse); c_tok[base] = -1; c_ok[base] = 1; s_live = 1; }
+            int hstate = 0;                                                  // hotwords: the node this hypothesis stands at
+            if constexpr (HW) {
+                if (root >= 0) hstate = hw.ctx[p][row];
+                if (lane == 0) c_state[base] = hstate;                       // the blank keeps it
+            }
             for (int j = 0; j < W; ++j) {
                 float bz = tz[0];
                 int bv = tv[0];
@@ -172,7 +206,15 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
                     if (ov >= 0 && (bv < 0 || oz > bz || (oz == bz && ov < bv))) { bz = oz; bv = ov; }
                 }
                 if (bv < 0) break;
-                if (lane == 0) { c_score[base + 1 + j] = hs + (bz - lse); c_tok[base + 1 + j] = bv; c_ok[base + 1 + j] = 1; }
+                if (lane == 0) {
+                    float cs = hs + (bz - lse);
+                    if constexpr (HW) {
+                        int nx = 0;
+                        if (root >= 0) { const float delta = hw_step(hw.t.g, root, hstate, bv, &nx); cs = cs + delta; }
+                        c_state[base + 1 + j] = nx;
+                    }
+                    c_score[base + 1 + j] = cs; c_tok[base + 1 + j] = bv; c_ok[base + 1 + j] = 1;
+                }
                 if (tv[0] == bv) {                                           // the owner pops its head
 #pragma unroll
                     for (int k = 0; k + 1 < MAX_BEAM; ++k) { tz[k] = tz[k + 1]; tv[k] = tv[k + 1]; }
@@ -194,7 +236,10 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
                 for (int s = 0; s < n_cur; ++s) {
                     const int row = b * W + s;
                     const int n = as.len[p][row];
-                    const float sc = as.score[p][row];
+                    float sc = as.score[p][row];
+                    if constexpr (HW) {
+                        if (root >= 0) sc = sc + (-hw.t.g.node_score[hw_node(hw.t.g, hw.ctx[p][row], root)]);      // Finalize
+                    }
                     const float norm = score_norm ? sc / (float)(n + 1) : sc;
                     if (src_n < 0 || norm > bn) {
                         src_n = n; src_score = sc; bn = norm;
@@ -278,6 +323,9 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             float sc = c_score[c];
 #pragma unroll
             for (int j = 0; j < MAX_BEAM; ++j) if (j < n_sel && sel[j] == c) sc = ssc[j];
+            if constexpr (HW) {
+                if (root >= 0) sc = sc + (-hw.t.g.node_score[hw_node(hw.t.g, c_state[c], root)]);                  // Finalize
+            }
             const float norm = score_norm ? sc / (float)(n + 1) : sc;
             if (fn < 0 || norm > fnorm) {
                 fn = n; fnorm = norm; fscore = sc;
@@ -320,6 +368,7 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             as.len[pn][row] = nn;
             as.score[pn][row] = s_score[wave];
             as.parent[row] = prow;
+            if constexpr (HW) hw.ctx[pn][row] = root >= 0 ? c_state[c] : 0;
             const int tn = (i + 1) - nn;
             st.tcur[row] = tn;
             if (i + 1 < n_steps && tn <= T - 1) {
@@ -351,7 +400,7 @@ __global__ __launch_bounds__(256) void alsd_reorder_kernel(AlsdState as, int pn,
 
 // the search's layout: two ping-pong sets of the prediction-network state (st[k].h / .c / .g; everything else of st[0] and st[1] is
 // shared) and the hypothesis store
-void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, rs_arena& a, DecodeState st[2], AlsdState& as) {
+void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, rs_arena& a, DecodeState st[2], AlsdState& as, int32_t* hw_ctx[2]) {
     const rs_dims& d = ctx->d;
     const size_t rows = (size_t)B * W, state = (size_t)d.pred_layers * rows * d.pred_hidden, J = d.joint_hidden;
     DecodeState q{};
@@ -374,6 +423,8 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, rs_arena& a, DecodeSt
     as.fin_y = a.take<int32_t>((size_t)B * cap); as.fin_al = a.take<int32_t>((size_t)B * cap);
     q.counters = a.take<int32_t>(16);
     q.zapprox = a.take<float>(rows * (size_t)rs_joint_zstride(d));
+    hw_ctx[0] = hw_ctx[1] = nullptr;
+    if (hotwords) { hw_ctx[0] = a.take<int32_t>(rows); hw_ctx[1] = a.take<int32_t>(rows); }       // (last: the plain layout is a prefix)
     as.cap = cap;
     st[0] = st[1] = q;
     st[1].h = h1; st[1].c = c1; st[1].g = g1;
@@ -381,18 +432,20 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, rs_arena& a, DecodeSt
 
 }  // namespace
 
-size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap) {
+size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords) {
     if (B <= 0 || beam <= 0 || cap <= 0) return 0;
     rs_arena a;
     DecodeState st[2];
     AlsdState as;
-    alsd_layout(ctx, B, beam, cap, a, st, as);
+    int32_t* hw_ctx[2];
+    alsd_layout(ctx, B, beam, cap, hotwords, a, st, as, hw_ctx);
     return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
-                      float* scores, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
+                      hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
@@ -404,7 +457,10 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     rs_arena arena(workspace);
     DecodeState st[2];
     AlsdState as;
-    alsd_layout(ctx, B, W, cap, arena, st, as);
+    const bool HWF = hotwords != nullptr && graph_of != nullptr && hotwords->n_graphs > 0;      // else: the plain kernels, today's bits
+    AlsdHw hw{};
+    if (HWF) { hw.t.g = *hotwords; hw.t.graph_of = graph_of; }
+    alsd_layout(ctx, B, W, cap, HWF, arena, st, as, hw.ctx);
     if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
         return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     const int rows = B * W;
@@ -412,11 +468,13 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     int32_t* const counters = st[0].counters;
     float* const zbuf = st[0].zapprox;
     const int zstride = rs_joint_zstride(d);
-    const auto select = V <= 64 * 48 ? alsd_select_kernel<48> : alsd_select_kernel<0>;   // (48: the logits row fits a lane's registers)
+    const auto select = V <= 64 * 48 ? alsd_select_kernel<48, false> : alsd_select_kernel<0, false>;   // (48: the logits row fits a lane's registers)
+    const auto select_hw = V <= 64 * 48 ? alsd_select_kernel<48, true> : alsd_select_kernel<0, true>;  // the hotword form takes the graphs last
 
     rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * rs_align((size_t)L * rows * H * 4), s));   // h and c of set 0
-    hipLaunchKernelGGL(alsd_init_kernel, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len);
+    if (HWF) hipLaunchKernelGGL(alsd_init_kernel<true>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, hw);
+    else hipLaunchKernelGGL(alsd_init_kernel<false>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, AlsdNoHw{});
     // start of sequence: blank token from zero state, slot 0 of every utterance (list built by the init kernel)
     if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) return rc;
     RS_CHECK_LAUNCH(ctx, "alsd init");
@@ -429,8 +487,10 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
         for (int c = 0; c < CHUNK && i <= max_steps; ++c, ++i) {
             const int p = i & 1, pn = p ^ 1;
             if (int rc = rs_rnnt_launch_joint_logits(ctx, &st[p], joint_enc, rows, tp_max, W, i, s); rc != RS_OK) return rc;
-            hipLaunchKernelGGL(select, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio, abs_len,
-                               score_norm, merge, out_cap, ids, steps, n_ids, scores);
+            if (HWF) hipLaunchKernelGGL(select_hw, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio,
+                                        abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores, hw);
+            else hipLaunchKernelGGL(select, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio, abs_len,
+                                    score_norm, merge, out_cap, ids, steps, n_ids, scores, AlsdNoHw{});
             hipLaunchKernelGGL(alsd_reorder_kernel, dim3(rows), dim3(256), 0, s, as, pn, W, rows, L, H, J, hset[p], cset[p],
                                gset[p], hset[pn], cset[pn], gset[pn]);
             if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[pn], rows, s); rc != RS_OK) return rc;

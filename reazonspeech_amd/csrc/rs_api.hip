@@ -12,7 +12,7 @@
 #include "rs_common.h"
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B);
-size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap);
+size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords);
 size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords);
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
                      int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
@@ -23,7 +23,8 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
                       void* workspace, size_t workspace_bytes, hipStream_t s);
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
-                      float* scores, void* workspace, size_t workspace_bytes, hipStream_t s);
+                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
+                      hipStream_t s);
 size_t rs_rnnt_token_scores_workspace_bytes_impl(const rs_ctx* ctx, int B, int u_cap);
 int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
                               const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
@@ -344,13 +345,20 @@ size_t rs_rnnt_alsd_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_m
     RS_GUARD_QUERY(ctx, rs_rnnt_alsd_workspace_bytes, 0);
     if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
     const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs));
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), false);
 }
 
-int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
-                 double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
-                 int32_t* n_ids, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
-    RS_GUARD(ctx, rs_rnnt_alsd);
+size_t rs_rnnt_alsd_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_alsd_hotwords_workspace_bytes, 0);
+    if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
+    const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), true);
+}
+
+// the argument checks and the dispatch of rs_rnnt_alsd and rs_rnnt_alsd_hotwords (hw == nullptr: the plain kernels)
+static int alsd_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double max_target_ratio,
+                     int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids, float* scores,
+                     const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes, void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0) return rs_fail(ctx, RS_EINVAL, "alsd: negative size");
     if (max_target_abs < 0 && !(max_target_ratio >= 0.0 && max_target_ratio <= 64.0))
         return rs_fail(ctx, RS_EINVAL, "alsd: max_target_ratio must be in [0, 64]");
@@ -363,7 +371,36 @@ int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
     }
     return rs_rnnt_alsd_impl(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs,
                              (flags & RS_ALSD_SCORE_NORM) != 0, (flags & RS_ALSD_MERGE) != 0, out_cap, ids, steps, n_ids, scores,
-                             workspace, workspace_bytes, (hipStream_t)stream);
+                             hw, hw ? graph_of : nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
+                 double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
+                 int32_t* n_ids, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_alsd);
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+                     nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
+                          double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
+                          int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_alsd_hotwords);
+    if (hw && (hw->n_nodes < 0 || hw->n_children < 0 || hw->n_graphs < 0 || hw->max_level < 0))
+        return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: negative count");
+    if (hw && graph_of && hw->n_graphs > 0) {
+        if (hw->n_nodes < hw->n_graphs || hw->n_children < 0 || hw->max_level < 0)
+            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)", hw->n_nodes,
+                           hw->n_children, hw->n_graphs, hw->max_level);
+        if (!hw->child_begin || !hw->fail || !hw->output || !hw->is_end || !hw->level || !hw->token_score || !hw->node_score ||
+            !hw->output_score || !hw->graph_root || (hw->n_children > 0 && (!hw->child_tok || !hw->child_node)))
+            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: null array");
+    } else {
+        hw = nullptr;                                     // no graph in this call: today's kernels, today's bits
+    }
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+                     hw, graph_of, workspace, workspace_bytes, stream);
 }
 
 size_t rs_rnnt_beam_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops) {

@@ -60,7 +60,7 @@ SYNTHETIC_ENV = "REAZONSPEECH_AMD_SYNTHETIC"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, decoding=None, beam_size=None,
-               precision="bf16", synthetic=False, resample="host", token_scores=False):
+               precision="bf16", synthetic=False, resample="host", token_scores=False, hotwords_file="", hotwords_score=1.5, hotwords=None):
     """Load the ReazonSpeech FastConformer-RNNT model onto a ROCm GPU.
 
     Args:
@@ -95,6 +95,14 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         the device right after the search (rs_rnnt_token_scores), valid with every `precision` and `decoding`; with
         `raw_hypothesis`, `Hypothesis.token_confidence` = exp(log-probability) like NeMo's `max_prob` method.  Off (default):
         today's objects.  Stored as `model.token_scores`, may be changed later.
+      hotwords_file (str), hotwords_score (float), hotwords: contextual biasing of the ALSD beam search, with the keyword names and
+        defaults of the k2 package ("" / 1.5 / None): a file with one phrase per line (an optional trailing ` :2.0` is that phrase's
+        own score), and / or `hotwords` = the same as a string of phrases separated by `/` or a list (strings, or sequences of token
+        ids).  Phrases are tokenised with the model's SentencePiece vocabulary, both as a word start and as the word reads in the
+        middle of a sentence (runtime/nemo_hotwords.py); one the vocabulary cannot spell is skipped with a warning.  The search
+        adds the score per matched token to hypotheses that spell a phrase out, inside its ranking, and takes it back when the
+        match breaks off (include/rs_asr.h rs_rnnt_alsd_hotwords).  The graph is built and uploaded once, here;
+        `transcribe(..., hotwords=...)` replaces it per call.  Non-empty hotwords with a decoding other than "alsd" raise ValueError.
       pos_cap (int): encoder frames (80 ms each) the resident relative-position tables cover at load time
         (default 1024, about 82 s); longer utterances grow the tables on first use.
 
@@ -108,6 +116,11 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     from ...runtime.resample import check_mode
 
     check_mode(resample)
+    from ...runtime import nemo_hotwords
+    if hotwords_file and not os.path.isfile(hotwords_file):
+        raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
+    if decoding is not None:               # (a checkpoint's own strategy is only known once it is read: checked again below)
+        nemo_hotwords.check_keywords(str(decoding), hotwords_file, hotwords_score, hotwords)
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if str(device).startswith("cpu"):
@@ -141,10 +154,17 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         cfg = cfg.with_(beam_size=int(beam_size))
     cfg.validate()
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-    return AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, **kw)
+    has_hotwords = nemo_hotwords.check_keywords(cfg.decoding, hotwords_file, hotwords_score, hotwords)
+    model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, **kw)
+    model.hotwords_score = float(hotwords_score)
+    if has_hotwords:
+        model.hotwords = nemo_hotwords.model_graph(model, hotwords, hotwords_file)     # the model's graph (None = nothing left to bias)
+        if model.hotwords is not None:
+            model.hotword_set((model.hotwords,))                                       # checked and uploaded once, at load
+    return model
 
 
-def transcribe_batch(model, audios, config=None, distributed=False):
+def transcribe_batch(model, audios, config=None, distributed=False, hotwords=None):
     """Transcribe a list of AudioData in one batched pass.
 
     Each utterance is processed exactly as `transcribe()` would process it alone
@@ -155,11 +175,23 @@ def transcribe_batch(model, audios, config=None, distributed=False):
     length-balanced shard on its own GPU and gets every result back, in the caller's order, through the
     path's one collective (an RCCL all_gather of the hypotheses).
 
+    `hotwords`: None (the model's, if any: `load_model(hotwords=...)`), one string of phrases separated by `/` for all audios, or
+    a list with one entry per audio (None / a string / a list of phrases) INSTEAD OF the model's: every utterance is biased by
+    its own graph inside the one batch.  Needs `decoding="alsd"` (ValueError otherwise).  Without hotwords every result is what
+    it was.
+
     Returns:
       list[TranscribeResult]
     """
     if config is None:
         config = TranscribeConfig()
+    from ...runtime import nemo_hotwords
+    graphs = nemo_hotwords.per_audio(model, hotwords, len(audios))
+    return _transcribe_graphs(model, audios, config, distributed, graphs)
+
+
+def _transcribe_graphs(model, audios, config, distributed, graphs):
+    """`transcribe_batch` with the hotwords resolved: `graphs` = None, or one HotwordGraph / None per audio"""
     # 16 kHz mono float32 waveforms (transcribe.py:44 minus the padding, which the kernel applies)
     waves = [np.ascontiguousarray(w, dtype=np.float32) for w in norm_batch(model, audios, norm_audio)]
     if config.verbose:
@@ -190,21 +222,27 @@ def transcribe_batch(model, audios, config=None, distributed=False):
         raise ValueError("token_scores is on: the distributed path does not gather token log-probabilities (transcribe_batch(distributed=False) "
                          "on each rank, or load the model without token_scores)")
     if distributed:
-        to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves))
+        to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves, hotwords=graphs))
     else:
-        model.transcribe_waveforms(waves, on_batch=to_results)
+        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs)
     return results
 
 
-def transcribe(model, audio, config=None):
+def transcribe(model, audio, config=None, hotwords=None):
     """Inference of one utterance (transcribe.py:30-60).
 
     Args:
         model: what `load_model()` returned
         audio (AudioData): audio to transcribe
         config (TranscribeConfig): additional settings
+        hotwords: phrases to favour in this call INSTEAD OF the model's: a string of phrases separated by `/`, or a list of
+            phrases, each with an optional ` :score`; None = the model's hotwords, if any (needs `decoding="alsd"`)
 
     Returns:
         TranscribeResult
     """
-    return transcribe_batch(model, [audio], config)[0]
+    if config is None:
+        config = TranscribeConfig()
+    from ...runtime import nemo_hotwords
+    graphs = nemo_hotwords.per_audio(model, hotwords, 1, single=True)
+    return _transcribe_graphs(model, [audio], config, False, graphs)[0]

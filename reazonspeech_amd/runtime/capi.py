@@ -34,6 +34,7 @@ EXPORTS = [
     "rs_rnnt_alsd", "rs_rnnt_alsd_workspace_bytes", "rs_rnnt_beam", "rs_rnnt_beam_workspace_bytes", "rs_host_stage_rows",
     "rs_rnnt_mbs", "rs_rnnt_mbs_workspace_bytes",
     "rs_rnnt_mbs_hotwords", "rs_rnnt_mbs_hotwords_workspace_bytes", "rs_hotwords_check",
+    "rs_rnnt_alsd_hotwords", "rs_rnnt_alsd_hotwords_workspace_bytes",
     "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
@@ -227,6 +228,10 @@ def load():
     lib.rs_rnnt_alsd_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_alsd.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp, vp,
                                  c_size_t, vp]
+    lib.rs_rnnt_alsd_hotwords_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
+    lib.rs_rnnt_alsd_hotwords_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_alsd_hotwords.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp,
+                                          POINTER(RsHotwords), vp, vp, c_size_t, vp]
     lib.rs_profile_enable.argtypes = [vp, c_int]
     lib.rs_profile_reset.argtypes = [vp]
     lib.rs_profile_read.argtypes = [vp, c_int, POINTER(c_double), POINTER(c_int64), POINTER(c_double),
@@ -476,6 +481,25 @@ class Context:
         self.check(self.lib.rs_rnnt_alsd(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags,
                                          ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores), _ptr(ws),
                                          ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def alsd_hotwords_workspace_bytes(self, B, beam, tp_max, max_target_len):
+        ratio, abs_len = self._alsd_budget(max_target_len)
+        n = self.lib.rs_rnnt_alsd_hotwords_workspace_bytes(self._h, B, beam, tp_max, ratio, abs_len)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_alsd_hotwords_workspace_bytes: invalid arguments (a finalized Conformer context, B > 0, beam > 0)")
+        return n
+
+    def rnnt_alsd_hotwords(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores,
+                           hotwords, graph_of, ws, stream):
+        """rnnt_alsd with contextual biasing: `hotwords` = an RsHotwords of device pointers (None = no graph: rs_rnnt_alsd's kernels),
+        `graph_of` int32 [B] on the device (-1 = the utterance has no graph)"""
+        assert steps.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
+        ratio, abs_len = self._alsd_budget(max_target_len)
+        flags = (ALSD_SCORE_NORM if score_norm else 0) | (ALSD_MERGE if merge else 0)
+        self.check(self.lib.rs_rnnt_alsd_hotwords(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags,
+                                                  ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores),
+                                                  byref(hotwords) if hotwords is not None else None, _ptr(graph_of), _ptr(ws),
+                                                  ws.numel() * ws.element_size(), c_void_p(stream)))
 
     def beam_workspace_bytes(self, B, beam, tp_max, max_pops=0):
         n = self.lib.rs_rnnt_beam_workspace_bytes(self._h, B, beam, tp_max, max_pops)

@@ -61,7 +61,7 @@ class _Buffers:
         self.n_ids = torch.zeros((B,), dtype=i32, device=dev)
         self.scores = torch.zeros((B,), dtype=f32, device=dev)
         self.pops = torch.zeros((B,), dtype=i32, device=dev)     # "beam": prediction-network evaluations per utterance
-        # hotwords (Zipformer family, modified beam search): each utterance's graph in the batch's `hw_set` (-1 = none); `stage` /
+        # hotwords (modified beam search, ALSD): each utterance's graph in the batch's `hw_set` (-1 = none); `stage` /
         # `fill_host` set both, `hw_set` None = the batch has no graph and the plain search runs
         self.graph_of = torch.full((B,), -1, dtype=i32, device=dev)
         self.h_graph_of = torch.full((B,), -1, dtype=i32).pin_memory()
@@ -204,6 +204,8 @@ class AsrModel:
             self.pad_left, self.pad_right = int(pad_samples[0]), int(pad_samples[1])
         self._bufs = {}
         self._hw_sets = {}              # (graph keys) -> _HotwordSet
+        self.hotwords = None            # the model's own HotwordGraph (nemo: load_model(hotwords=...)); None = no hotwords
+        self.hotwords_score = 1.5
         self._dec_lanes = []            # [(context, stream)] of the decode lanes beyond what was needed so far
         self._streams = None
         self._streams_prio = None
@@ -434,6 +436,14 @@ class AsrModel:
             ctx.rnnt_mbs(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
                          buf.ids, buf.frames, buf.n_ids, buf.scores, buf.ws_alsd, stream)
             return
+        if cfg.decoding == "alsd" and hw is not None:      # ALSD with hotwords: the batch has at least one graph (csrc/k_rnnt_alsd.hip, HW form)
+            n = ctx.alsd_hotwords_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len)
+            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
+                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            ctx.rnnt_alsd_hotwords(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len,
+                                   cfg.beam_score_norm, False, buf.ids, buf.frames, buf.n_ids, buf.scores, hw.struct, buf.graph_of,
+                                   buf.ws_alsd, stream)
+            return
         if cfg.decoding != "alsd":
             ctx.rnnt_greedy(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, buf.u_max, buf.ids, buf.frames, buf.n_ids,
                             ws, stream)
@@ -629,7 +639,7 @@ class AsrModel:
         with torch.cuda.device(self.device):
             return _Buffers(self, B, (max(int(l_max), 1) + 63) // 64 * 64)
 
-    # ---- hotwords (Zipformer family, modified beam search) ----------------------------------------------------------------------
+    # ---- hotwords (Zipformer family: modified beam search; NeMo family: ALSD) ---------------------------------------------------
     def hotword_set(self, graphs):
         """the device table of a tuple of distinct HotwordGraph: built, checked (rs_hotwords_check) and uploaded once, then
         found again by content"""
@@ -651,8 +661,10 @@ class AsrModel:
             raise ValueError(f"hotwords: {len(hotwords)} entries for {n} utterances")
         if all(g is None for g in hotwords):
             return None
-        if self.cfg.decoding != "modified_beam_search":
-            raise ValueError("hotwords need decoding_method='modified_beam_search'")
+        if self.cfg.decoding not in ("modified_beam_search", "alsd"):      # greedy has no hypotheses to bias; "beam" has no hotword form
+            if getattr(self.cfg, "family", "") == "k2":
+                raise ValueError("hotwords need decoding_method='modified_beam_search'")
+            raise ValueError(f"hotwords need decoding='alsd', not {self.cfg.decoding!r}")
         distinct, index = [], {}
         for g in hotwords:
             if g is not None and g.key not in index:
@@ -862,7 +874,7 @@ class AsrModel:
         batch i+2 / i+3 while the GPU works on the batches before them, H2D on the encoder stream, hypotheses copied back
         by the decode workers: no drain between batches.  Results come back in the caller's order.
 
-        `hotwords` (Zipformer family, modified beam search): None, or one HotwordGraph (runtime/k2_hotwords.py) or None per
+        `hotwords` (modified beam search or ALSD): None, or one HotwordGraph (runtime/k2_hotwords.py) or None per
         utterance.  The distinct graphs of the call become one device table (`hotword_set`) and every utterance's graph index
         travels with it through sorting and grouping; a batch without any graph runs the plain search."""
         n = len(waveforms)

@@ -1,5 +1,6 @@
 """Tokenizers: the reference reads `model.tokenizer.ids_to_text` of NeMo's SentencePiece
-wrapper (pkg/nemo-asr/src/decode.py:41,47).  Two implementations with that one method:
+wrapper (pkg/nemo-asr/src/decode.py:41,47).  Two implementations with that one method (and `text_to_ids`, the
+way back, which hotwords need):
 
   SentencePieceTokenizer   wraps a `tokenizer.model` taken from a .nemo archive
   SyntheticTokenizer       a seeded vocabulary for synthetic-weight runs (no checkpoint here)
@@ -20,6 +21,26 @@ class SentencePieceTokenizer:
 
     def ids_to_tokens(self, ids):
         return [self._sp.id_to_piece(int(i)) for i in ids]
+
+    def text_to_ids(self, text):
+        """the readings of `text` as token ids, for hotwords (runtime/nemo_hotwords.py): (a) what SentencePiece's own encode gives,
+        and, whenever it differs, (b) the reading the word has in the middle of a Japanese sentence, where no U+2581 precedes it:
+        a first piece that is exactly U+2581 is dropped, a first piece U+2581 + X becomes X when X is a piece.  [] when the
+        vocabulary cannot spell the text (encode gives <unk>) or the text is empty."""
+        ids = [int(i) for i in self._sp.encode(text)]
+        unk = self._sp.unk_id()
+        if not ids or any(i == unk for i in ids):
+            return []
+        out = [tuple(ids)]
+        first = self._sp.id_to_piece(ids[0])
+        if first == _WS:
+            if len(ids) > 1:
+                out.append(tuple(ids[1:]))
+        elif first.startswith(_WS):
+            x = self._sp.piece_to_id(first[len(_WS):])
+            if x != unk and self._sp.id_to_piece(x) == first[len(_WS):]:
+                out.append((int(x),) + tuple(ids[1:]))
+        return out
 
 
 class SyntheticTokenizer:
@@ -45,6 +66,25 @@ class SyntheticTokenizer:
                 pieces.append(p)
         self.pieces = pieces
         self.vocab_size = vocab_size
+
+    def text_to_ids(self, text):
+        """the reading of `text` as token ids, for hotwords: greedy longest match over the pieces (white space -> U+2581);
+        [] when a character matches no piece or the text is empty.  One reading: a list of one tuple."""
+        if getattr(self, "_index", None) is None:
+            self._index = {p: i for i, p in reversed(list(enumerate(self.pieces)))}
+            self._longest = max(len(p) for p in self.pieces)
+        text = "".join(_WS if c.isspace() else c for c in text.strip())
+        ids, k = [], 0
+        while k < len(text):
+            for n in range(min(self._longest, len(text) - k), 0, -1):
+                i = self._index.get(text[k:k + n])
+                if i is not None:
+                    ids.append(i)
+                    k += n
+                    break
+            else:
+                return []
+        return [tuple(ids)] if ids else []
 
     def ids_to_tokens(self, ids):
         return [self.pieces[int(i)] for i in ids]
