@@ -654,6 +654,72 @@ int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* en
                           int32_t* steps, int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- n-gram language model (shallow fusion) in the ALSD beam search — added within ABI 7 -------------
+ * gives the NeMo family what `decoding.beam.ngram_lm_model` / `ngram_lm_alpha` give upstream: a backoff n-gram model, trained on
+ * the user's own text, whose log-probability of every label expansion enters the ranking.  [UPSTREAM, not vendored, UNVERIFIED]
+ * NeMo's align_length_sync_decoding is believed to add ngram_lm_alpha * lm_score to each of a hypothesis's top-k expansions after
+ * the top-k pick (NeMo is not available to this project); that is the slot rs_rnnt_alsd_hotwords already ranks in, and the rule
+ * below is stated for it.  No end-of-sentence term: upstream ALSD adds none, and the search never emits `</s>`.
+ *
+ * rs_ngram: one model as flat arrays, natural logarithms (each value = float32(log10 value x ln 10), the product in float64):
+ *   child_begin i32[n_nodes + 1]   CSR over a forward trie of token ids; node 0 is the root (the empty context)
+ *   child_tok / child_node i32[n_children]   token (strictly ascending within a node) and node of each child
+ *   root_child i32[n_logits]       node of the unigram of token v, -1 = none (most walks end here: one load, not a bisection)
+ *   logp / backoff f32[n_nodes]    of the node's n-gram; backoff 0 where the file gives none
+ *   suffix i32[n_nodes]            node of the longest proper suffix of the node's words that the model has; the root's is the root
+ *   level i32[n_nodes]             n-gram length; root 0
+ *   start                          node of `<s>` if the model has it (a level-1 node in no child list: no token reaches it), else 0
+ *   order                          the model's order, 1..8;   unk_logp = `<unk>`'s log-probability (or the model's lowest unigram's)
+ * rs_rnnt_alsd_lm reads DEVICE pointers; rs_ngram_host is the same layout with HOST pointers, for rs_ngram_check.
+ *   step(state s, token v) -> (lp, next), float32, no contraction:
+ *     n = s; acc = 0; c = none
+ *     repeat at most order + 1 times:
+ *         c = (n == root) ? root_child[v] : child(n, v)             (bisection, at most 32 steps)
+ *         if c found or n == root: stop
+ *         acc = acc + backoff[n]; n = suffix[n]
+ *     found:      lp = acc + logp[c];   next = level[c] < order ? c : suffix[c]
+ *     not found:  lp = acc + unk_logp;  next = root
+ *   in the search (rs_rnnt_alsd / rs_rnnt_alsd_hotwords with these additions): every hypothesis row carries an LM state; the start
+ *   hypothesis stands at `start`.  The blank candidate is unchanged and keeps the state.  A label candidate v of a hypothesis with
+ *   score hs and state s: cs = hs + (z[v] - lse); with a hotword graph on that utterance cs = cs + delta exactly as in
+ *   rs_rnnt_alsd_hotwords; then (lp, s') = step(s, v) and cs = cs + (lm_alpha * lp), the product rounded first; its LM state is s'.
+ *   Selection ranks these scores, ties as in rs_rnnt_alsd.  Recombination is unchanged (the state is a function of the label
+ *   sequence alone) and the first occurrence's state stays.  scores[b] includes the LM terms; rs_rnnt_token_scores keeps reporting
+ *   the model's unmodified distribution.
+ * All numbers float32 in the order csrc/k_rnnt_alsd.hip / csrc/k_rnnt_ngram.h state and tests/alsd_lm_checker.c restates (bit for
+ * bit).  Every walk on the device is a counted loop (order + 1 backoff steps, 32 bisection steps); a node or child index outside
+ * the table is replaced by the root before it is used and a token outside root_child counts as not found: a corrupt table can give
+ * a wrong score and nothing else.  rs_ngram_check (pure host code, no context) validates a table before upload: counts and index
+ * ranges, children strictly ascending, level[child] = level[parent] + 1, level[suffix[n]] < level[n] for every node but the root,
+ * every root_child entry a level-1 child of the root on that token, `start` the root or a level-1 node, every value finite;
+ * RS_EINVAL with the reason in msg (msg_bytes, may be NULL).
+ * rs_rnnt_alsd_lm with lm == NULL, n_nodes == 0 or lm_alpha == 0 is rs_rnnt_alsd_hotwords (the same kernels, the same bits; with
+ * hw == NULL as well that is rs_rnnt_alsd); otherwise the LM form of the selection kernel runs, candidate j's walk on lane j of
+ * its hypothesis's wave: still six launches per alignment step, no further host round trip.  Workspace:
+ * rs_rnnt_alsd_lm_workspace_bytes, the hotword layout plus one LM state per hypothesis row, twice (0 for invalid arguments or a
+ * context that is not finalized).  Errors as rs_rnnt_alsd_hotwords, and RS_EINVAL, before anything is enqueued, for negative counts
+ * or null arrays, a non-finite or negative lm_alpha, lm->n_logits different from the context's, `order` outside 1..8, `start`
+ * outside the nodes; RS_EINVAL for a Zipformer or AV-HuBERT context. */
+typedef struct rs_ngram {
+    const int32_t* child_begin;
+    const int32_t* child_tok;
+    const int32_t* child_node;
+    const int32_t* root_child;
+    const float* logp;
+    const float* backoff;
+    const int32_t* suffix;
+    const int32_t* level;
+    int32_t n_nodes, n_children, n_logits, order, start;
+    float unk_logp;
+} rs_ngram;
+typedef rs_ngram rs_ngram_host;
+int rs_ngram_check(const rs_ngram_host* table, char* msg, size_t msg_bytes);
+size_t rs_rnnt_alsd_lm_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs);
+int rs_rnnt_alsd_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
+                    double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
+                    int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
+                    float lm_alpha, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- token log-probabilities of a finished transducer search — added within ABI 7 ----------------
  * gives what NeMo's Hypothesis.token_confidence (preserve_token_confidence, method max_prob), sherpa-onnx's per-token log-probs
  * and ESPnet's scored hypotheses give: how sure the model was of every token it emitted.  A teacher-forced pass over the OUTPUT

@@ -30,9 +30,20 @@
 // new row's state.  It is the hotword form of alsd_init_kernel / alsd_select_kernel (template parameter HW): no further launch,
 // no host round trip.  The plain instantiations are the ones launched when no utterance of the call has a graph; inside the
 // hotword form a workgroup whose utterance has none takes the plain statements.  Restated by tests/alsd_hotwords_checker.c.
+//
+// N-GRAM LM (rs_rnnt_alsd_lm; the table and `step` are stated in include/rs_asr.h, the walk is k_rnnt_ngram.h).  Every hypothesis
+// row carries an LM state (AlsdHwLm.lmctx, ping-pong; the start hypothesis stands at `start`).  A label candidate's score is
+// ((hs + (z[v] - lse)) [+ delta]) + (alpha * lp), the product rounded first, its state the step's next state; the blank keeps score
+// and state.  An LM walk usually backs off through every level (a hotword walk usually ends at the first node), so the W walks of a
+// hypothesis run SIDE BY SIDE: the W picks are made as in the plain form, lane j keeps pick j in registers, and after the last pick
+// lane j computes candidate j whole — score, hotword step if the utterance has a graph, LM step — and writes it to LDS (c_lm next
+// to c_state).  The LM form is the template parameter LM of alsd_init_kernel / alsd_select_kernel; it is compiled with HW on and
+// carries the call's graphs, or none (graph_of == nullptr: every utterance takes the no-graph statements).  Restated by
+// tests/alsd_lm_checker.c.
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
 #include "k_rnnt_hotwords.h"
+#include "k_rnnt_ngram.h"
 
 #include <type_traits>
 
@@ -65,12 +76,26 @@ struct AlsdHw {          // hotwords: the graphs of the call and the node each h
     int32_t* ctx[2];     // [rows], ping-pong like AlsdState's records
 };
 
+struct AlsdHwLm : AlsdHw {   // n-gram LM: the model, its weight and the LM state of each hypothesis row (the graphs may be absent)
+    rs_ngram g;
+    float alpha;
+    int32_t* lmctx[2];   // [rows], ping-pong
+};
+template <bool HW, bool LM>
+using AlsdArg = std::conditional_t<LM, AlsdHwLm, std::conditional_t<HW, AlsdHw, AlsdNoHw>>;
+// root of utterance b's graph; the LM form may carry no graphs at all
+template <bool LM, class A>
+__device__ __forceinline__ int alsd_root(const A& hw, int b) {
+    if constexpr (LM) { if (hw.t.graph_of == nullptr) return -1; }
+    return hw_root(hw.t, b);
+}
+
 // label budget of an utterance with T frames (oracle/alsd.py: a float is a multiple of T, an int is absolute)
 __host__ __device__ inline int alsd_budget(int T, double ratio, int abs_len) { return abs_len >= 0 ? abs_len : (int)(ratio * (double)T); }
 
-template <bool HW>
+template <bool HW, bool LM = false>
 __global__ void alsd_init_kernel(DecodeState st, AlsdState as, const int32_t* __restrict__ enc_lens, int B, int W, int blank,
-                                 double ratio, int abs_len, std::conditional_t<HW, AlsdHw, AlsdNoHw> hw) {
+                                 double ratio, int abs_len, AlsdArg<HW, LM> hw) {
     // single workgroup: the start hypothesis of every utterance and the first work lists, in row order
     __shared__ int n_alive_s;
     if (threadIdx.x == 0) n_alive_s = 0;
@@ -79,7 +104,8 @@ __global__ void alsd_init_kernel(DecodeState st, AlsdState as, const int32_t* __
         const int row = b * W;
         as.len[0][row] = 0; as.score[0][row] = 0.0f; as.n_hyp[0][b] = 1;
         as.fin_n[b] = -1; as.fin_norm[b] = 0.0f; as.fin_score[b] = 0.0f; as.done[b] = 0;
-        if constexpr (HW) { const int r = hw_root(hw.t, b); hw.ctx[0][row] = r < 0 ? 0 : r; }
+        if constexpr (HW) { const int r = alsd_root<LM>(hw, b); hw.ctx[0][row] = r < 0 ? 0 : r; }
+        if constexpr (LM) hw.lmctx[0][row] = lm_node(hw.g, hw.g.start);
         st.token[row] = blank; st.tcur[row] = 0; st.act[b] = row;
         const int T = enc_lens[b];
         if (T > 0 && T + alsd_budget(T, ratio, abs_len) > 0) st.alive[atomicAdd(&n_alive_s, 1)] = row;
@@ -96,11 +122,13 @@ __device__ __forceinline__ int cand_len(int parent_len, int tok) { return parent
 // first comparison; the scan for the maximum / the W best and the exp-sum then walk the registers in the same ascending order as
 // the two memory passes of the NVR = 0 form — identical arithmetic, one memory round trip instead of two chains of 47.
 // HW: the hotword form (see the head of this file); the plain form is the same text without the `if constexpr (HW)` statements.
-template <int NVR, bool HW>
+// LM: the n-gram form (HW on as well); the other forms are the same text without the `if constexpr (LM)` statements.
+template <int NVR, bool HW, bool LM = false>
 __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
     DecodeState st, AlsdState as, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int B, int W,
     int V, int blank, int i, double ratio, int abs_len, int score_norm, int merge, int out_cap, int32_t* __restrict__ ids,
-    int32_t* __restrict__ steps, int32_t* __restrict__ n_ids, float* __restrict__ scores, std::conditional_t<HW, AlsdHw, AlsdNoHw> hw) {
+    int32_t* __restrict__ steps, int32_t* __restrict__ n_ids, float* __restrict__ scores, AlsdArg<HW, LM> hw) {
+    static_assert(HW || !LM, "the LM form is compiled with the hotword statements");
     const int b = blockIdx.x;
     if (as.done[b]) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -116,7 +144,8 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
     __shared__ int c_ok[MAX_CAND];
     __shared__ int c_state[HW ? MAX_CAND : 1];   // hotwords: the context state of each candidate
     int root = -1;                               // hotwords: the root of the utterance's graph, -1 = it has none
-    if constexpr (HW) root = hw_root(hw.t, b);
+    if constexpr (HW) root = alsd_root<LM>(hw, b);
+    __shared__ int c_lm[LM ? MAX_CAND : 1];      // n-gram LM: the LM state of each candidate
     __shared__ int s_sel[MAX_BEAM];        // selected candidate of beam position j
     __shared__ float s_score[MAX_BEAM];    // its score after recombination
     __shared__ int s_keep[MAX_BEAM];       // beam position written to new slot k
@@ -196,6 +225,12 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
                 if (root >= 0) hstate = hw.ctx[p][row];
                 if (lane == 0) c_state[base] = hstate;                       // the blank keeps it
             }
+            [[maybe_unused]] int lstate = 0, n_pick = 0, mv = -1;            // n-gram LM: the row's state; lane j keeps pick j
+            [[maybe_unused]] float mz = 0.0f;
+            if constexpr (LM) {
+                lstate = hw.lmctx[p][row];
+                if (lane == 0) c_lm[base] = lstate;                          // the blank keeps it
+            }
             for (int j = 0; j < W; ++j) {
                 float bz = tz[0];
                 int bv = tv[0];
@@ -206,7 +241,10 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
                     if (ov >= 0 && (bv < 0 || oz > bz || (oz == bz && ov < bv))) { bz = oz; bv = ov; }
                 }
                 if (bv < 0) break;
-                if (lane == 0) {
+                if constexpr (LM) {
+                    if (lane == j) { mz = bz; mv = bv; }
+                    n_pick = j + 1;
+                } else if (lane == 0) {
                     float cs = hs + (bz - lse);
                     if constexpr (HW) {
                         int nx = 0;
@@ -219,6 +257,17 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
 #pragma unroll
                     for (int k = 0; k + 1 < MAX_BEAM; ++k) { tz[k] = tz[k + 1]; tv[k] = tv[k + 1]; }
                     tz[MAX_BEAM - 1] = -INFINITY; tv[MAX_BEAM - 1] = -1;
+                }
+            }
+            if constexpr (LM) {
+                if (lane < n_pick) {                                         // candidate `lane`, whole: W walks side by side
+                    float cs = hs + (mz - lse);
+                    int nx = 0, ln = 0;
+                    if (root >= 0) { const float delta = hw_step(hw.t.g, root, hstate, mv, &nx); cs = cs + delta; }
+                    const float lp = lm_step(hw.g, lstate, mv, &ln);
+                    cs = cs + (hw.alpha * lp);
+                    c_state[base + 1 + lane] = nx; c_lm[base + 1 + lane] = ln;
+                    c_score[base + 1 + lane] = cs; c_tok[base + 1 + lane] = mv; c_ok[base + 1 + lane] = 1;
                 }
             }
         }
@@ -369,6 +418,7 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             as.score[pn][row] = s_score[wave];
             as.parent[row] = prow;
             if constexpr (HW) hw.ctx[pn][row] = root >= 0 ? c_state[c] : 0;
+            if constexpr (LM) hw.lmctx[pn][row] = c_lm[c];
             const int tn = (i + 1) - nn;
             st.tcur[row] = tn;
             if (i + 1 < n_steps && tn <= T - 1) {
@@ -400,7 +450,8 @@ __global__ __launch_bounds__(256) void alsd_reorder_kernel(AlsdState as, int pn,
 
 // the search's layout: two ping-pong sets of the prediction-network state (st[k].h / .c / .g; everything else of st[0] and st[1] is
 // shared) and the hypothesis store
-void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, rs_arena& a, DecodeState st[2], AlsdState& as, int32_t* hw_ctx[2]) {
+void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, bool lm, rs_arena& a, DecodeState st[2], AlsdState& as, int32_t* hw_ctx[2],
+                 int32_t* lm_ctx[2]) {
     const rs_dims& d = ctx->d;
     const size_t rows = (size_t)B * W, state = (size_t)d.pred_layers * rows * d.pred_hidden, J = d.joint_hidden;
     DecodeState q{};
@@ -425,6 +476,8 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, rs_are
     q.zapprox = a.take<float>(rows * (size_t)rs_joint_zstride(d));
     hw_ctx[0] = hw_ctx[1] = nullptr;
     if (hotwords) { hw_ctx[0] = a.take<int32_t>(rows); hw_ctx[1] = a.take<int32_t>(rows); }       // (last: the plain layout is a prefix)
+    lm_ctx[0] = lm_ctx[1] = nullptr;
+    if (lm) { lm_ctx[0] = a.take<int32_t>(rows); lm_ctx[1] = a.take<int32_t>(rows); }             // (after them: the hotword layout is a prefix)
     as.cap = cap;
     st[0] = st[1] = q;
     st[1].h = h1; st[1].c = c1; st[1].g = g1;
@@ -432,20 +485,20 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, rs_are
 
 }  // namespace
 
-size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords) {
+size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm) {
     if (B <= 0 || beam <= 0 || cap <= 0) return 0;
     rs_arena a;
     DecodeState st[2];
     AlsdState as;
-    int32_t* hw_ctx[2];
-    alsd_layout(ctx, B, beam, cap, hotwords, a, st, as, hw_ctx);
+    int32_t *hw_ctx[2], *lm_ctx[2];
+    alsd_layout(ctx, B, beam, cap, hotwords || lm, lm, a, st, as, hw_ctx, lm_ctx);
     return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
-                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
-                      hipStream_t s) {
+                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
+                      void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
@@ -458,9 +511,12 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     DecodeState st[2];
     AlsdState as;
     const bool HWF = hotwords != nullptr && graph_of != nullptr && hotwords->n_graphs > 0;      // else: the plain kernels, today's bits
-    AlsdHw hw{};
+    const bool LMF = ngram != nullptr && ngram->n_nodes > 0 && lm_alpha != 0.0f;                // else: the forms above, today's bits
+    AlsdHwLm hw{};
     if (HWF) { hw.t.g = *hotwords; hw.t.graph_of = graph_of; }
-    alsd_layout(ctx, B, W, cap, HWF, arena, st, as, hw.ctx);
+    if (LMF) { hw.g = *ngram; hw.alpha = lm_alpha; }
+    alsd_layout(ctx, B, W, cap, HWF || LMF, LMF, arena, st, as, hw.ctx, hw.lmctx);
+    const AlsdHw& hw_only = hw;                                                                 // the hotword form's argument
     if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
         return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     const int rows = B * W;
@@ -470,10 +526,12 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     const int zstride = rs_joint_zstride(d);
     const auto select = V <= 64 * 48 ? alsd_select_kernel<48, false> : alsd_select_kernel<0, false>;   // (48: the logits row fits a lane's registers)
     const auto select_hw = V <= 64 * 48 ? alsd_select_kernel<48, true> : alsd_select_kernel<0, true>;  // the hotword form takes the graphs last
+    const auto select_lm = V <= 64 * 48 ? alsd_select_kernel<48, true, true> : alsd_select_kernel<0, true, true>;   // the LM form: graphs and model
 
     rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * rs_align((size_t)L * rows * H * 4), s));   // h and c of set 0
-    if (HWF) hipLaunchKernelGGL(alsd_init_kernel<true>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, hw);
+    if (LMF) hipLaunchKernelGGL((alsd_init_kernel<true, true>), dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, hw);
+    else if (HWF) hipLaunchKernelGGL(alsd_init_kernel<true>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, hw_only);
     else hipLaunchKernelGGL(alsd_init_kernel<false>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, AlsdNoHw{});
     // start of sequence: blank token from zero state, slot 0 of every utterance (list built by the init kernel)
     if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) return rc;
@@ -487,8 +545,10 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
         for (int c = 0; c < CHUNK && i <= max_steps; ++c, ++i) {
             const int p = i & 1, pn = p ^ 1;
             if (int rc = rs_rnnt_launch_joint_logits(ctx, &st[p], joint_enc, rows, tp_max, W, i, s); rc != RS_OK) return rc;
-            if (HWF) hipLaunchKernelGGL(select_hw, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio,
+            if (LMF) hipLaunchKernelGGL(select_lm, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio,
                                         abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores, hw);
+            else if (HWF) hipLaunchKernelGGL(select_hw, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio,
+                                             abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores, hw_only);
             else hipLaunchKernelGGL(select, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio, abs_len,
                                     score_norm, merge, out_cap, ids, steps, n_ids, scores, AlsdNoHw{});
             hipLaunchKernelGGL(alsd_reorder_kernel, dim3(rows), dim3(256), 0, s, as, pn, W, rows, L, H, J, hset[p], cset[p],

@@ -1,6 +1,7 @@
 // rs_api.hip — the C ABI of librs_asr.so (include/rs_asr.h): context lifecycle, weight registry, the family guard (rs_family.h) at
 // every entry and the dispatch to the family that serves it, argument checks, profiling readers and the single-operator hooks.
 // The families' own finalize, workspace plans and encoder call sequences live in k_conformer.hip, k_zipformer.hip and k_avsr.hip.
+#include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -10,9 +11,10 @@
 #include <utility>
 
 #include "rs_common.h"
+#include "rs_ngram_check.h"
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B);
-size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords);
+size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm);
 size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords);
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
                      int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
@@ -23,8 +25,8 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
                       void* workspace, size_t workspace_bytes, hipStream_t s);
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
-                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
-                      hipStream_t s);
+                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
+                      void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_token_scores_workspace_bytes_impl(const rs_ctx* ctx, int B, int u_cap);
 int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
                               const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
@@ -345,20 +347,29 @@ size_t rs_rnnt_alsd_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_m
     RS_GUARD_QUERY(ctx, rs_rnnt_alsd_workspace_bytes, 0);
     if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
     const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), false);
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), false, false);
 }
 
 size_t rs_rnnt_alsd_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
     RS_GUARD_QUERY(ctx, rs_rnnt_alsd_hotwords_workspace_bytes, 0);
     if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
     const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), true);
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), true, false);
 }
 
-// the argument checks and the dispatch of rs_rnnt_alsd and rs_rnnt_alsd_hotwords (hw == nullptr: the plain kernels)
+size_t rs_rnnt_alsd_lm_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_alsd_lm_workspace_bytes, 0);
+    if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
+    const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), true, true);
+}
+
+// the argument checks and the dispatch of rs_rnnt_alsd, rs_rnnt_alsd_hotwords and rs_rnnt_alsd_lm (hw == nullptr, lm == nullptr: the
+// plain kernels)
 static int alsd_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double max_target_ratio,
                      int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids, float* scores,
-                     const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes, void* stream) {
+                     const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
+                     void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0) return rs_fail(ctx, RS_EINVAL, "alsd: negative size");
     if (max_target_abs < 0 && !(max_target_ratio >= 0.0 && max_target_ratio <= 64.0))
         return rs_fail(ctx, RS_EINVAL, "alsd: max_target_ratio must be in [0, 64]");
@@ -371,7 +382,7 @@ static int alsd_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     }
     return rs_rnnt_alsd_impl(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs,
                              (flags & RS_ALSD_SCORE_NORM) != 0, (flags & RS_ALSD_MERGE) != 0, out_cap, ids, steps, n_ids, scores,
-                             hw, hw ? graph_of : nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+                             hw, hw ? graph_of : nullptr, lm, lm_alpha, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
@@ -379,7 +390,25 @@ int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
                  int32_t* n_ids, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd);
     return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
-                     nullptr, nullptr, workspace, workspace_bytes, stream);
+                     nullptr, nullptr, nullptr, 0.0f, workspace, workspace_bytes, stream);
+}
+
+// the table checks of rs_rnnt_alsd_hotwords and rs_rnnt_alsd_lm: RS_OK and *hw the table to search with (nullptr: no graph in this call)
+static int alsd_hotwords_arg(rs_ctx* ctx, const rs_hotwords** hw, const int32_t* graph_of) {
+    const rs_hotwords* t = *hw;
+    if (t && (t->n_nodes < 0 || t->n_children < 0 || t->n_graphs < 0 || t->max_level < 0))
+        return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: negative count");
+    if (t && graph_of && t->n_graphs > 0) {
+        if (t->n_nodes < t->n_graphs || t->n_children < 0 || t->max_level < 0)
+            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)", t->n_nodes,
+                           t->n_children, t->n_graphs, t->max_level);
+        if (!t->child_begin || !t->fail || !t->output || !t->is_end || !t->level || !t->token_score || !t->node_score ||
+            !t->output_score || !t->graph_root || (t->n_children > 0 && (!t->child_tok || !t->child_node)))
+            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: null array");
+    } else {
+        *hw = nullptr;                                    // no graph in this call: today's kernels, today's bits
+    }
+    return RS_OK;
 }
 
 int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
@@ -387,20 +416,35 @@ int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* en
                           int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace,
                           size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd_hotwords);
-    if (hw && (hw->n_nodes < 0 || hw->n_children < 0 || hw->n_graphs < 0 || hw->max_level < 0))
-        return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: negative count");
-    if (hw && graph_of && hw->n_graphs > 0) {
-        if (hw->n_nodes < hw->n_graphs || hw->n_children < 0 || hw->max_level < 0)
-            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)", hw->n_nodes,
-                           hw->n_children, hw->n_graphs, hw->max_level);
-        if (!hw->child_begin || !hw->fail || !hw->output || !hw->is_end || !hw->level || !hw->token_score || !hw->node_score ||
-            !hw->output_score || !hw->graph_root || (hw->n_children > 0 && (!hw->child_tok || !hw->child_node)))
-            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: null array");
+    if (int rc = alsd_hotwords_arg(ctx, &hw, graph_of); rc != RS_OK) return rc;
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+                     hw, graph_of, nullptr, 0.0f, workspace, workspace_bytes, stream);
+}
+
+int rs_ngram_check(const rs_ngram_host* table, char* msg, size_t msg_bytes) { return rs_ngram_check_table(table, msg, msg_bytes); }
+
+int rs_rnnt_alsd_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
+                    double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
+                    int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
+                    float lm_alpha, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_alsd_lm);
+    if (int rc = alsd_hotwords_arg(ctx, &hw, graph_of); rc != RS_OK) return rc;
+    if (!(lm_alpha >= 0.0f) || !isfinite(lm_alpha)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: lm_alpha must be a finite number >= 0");
+    if (lm && (lm->n_nodes < 0 || lm->n_children < 0 || lm->n_logits < 0)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: negative count");
+    if (lm && lm->n_nodes > 0 && lm_alpha != 0.0f) {
+        if (lm->n_logits != ctx->d.n_logits)
+            return rs_fail(ctx, RS_EINVAL, "alsd: lm: the table is built for %d logits, the context has %d", lm->n_logits, ctx->d.n_logits);
+        if (lm->order < 1 || lm->order > RS_NGRAM_MAX_ORDER) return rs_fail(ctx, RS_EINVAL, "alsd: lm: order %d outside 1..%d", lm->order, (int)RS_NGRAM_MAX_ORDER);
+        if (lm->start < 0 || lm->start >= lm->n_nodes) return rs_fail(ctx, RS_EINVAL, "alsd: lm: start %d outside the %d nodes", lm->start, lm->n_nodes);
+        if (!isfinite(lm->unk_logp)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: unk_logp is not finite");
+        if (!lm->child_begin || !lm->root_child || !lm->logp || !lm->backoff || !lm->suffix || !lm->level ||
+            (lm->n_children > 0 && (!lm->child_tok || !lm->child_node)))
+            return rs_fail(ctx, RS_EINVAL, "alsd: lm: null array");
     } else {
-        hw = nullptr;                                     // no graph in this call: today's kernels, today's bits
+        lm = nullptr;                                     // no model in this call: rs_rnnt_alsd_hotwords, the same kernels and bits
     }
     return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
-                     hw, graph_of, workspace, workspace_bytes, stream);
+                     hw, graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
 }
 
 size_t rs_rnnt_beam_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops) {

@@ -47,6 +47,8 @@ enum { RS_ANYTIME = 0, RS_FINAL = 1 };
     /* FINAL also for the size: with all-zero arguments (tests/test_gpu_family_guards.py) a query of an ANYTIME row must answer > 0 */ \
     X(rs_rnnt_alsd_hotwords_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                             \
     X(rs_rnnt_alsd_hotwords, C, FINAL, RS_HINT_LSTM_ONLY)                                                                             \
+    X(rs_rnnt_alsd_lm_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                                   \
+    X(rs_rnnt_alsd_lm, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                   \
     X(rs_rnnt_beam_workspace_bytes, C, ANYTIME, RS_HINT_LSTM_ONLY)                                                                    \
     X(rs_rnnt_beam, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                      \
     X(rs_rnnt_mbs_workspace_bytes, Z, ANYTIME, RS_HINT_MBS)                                                                           \

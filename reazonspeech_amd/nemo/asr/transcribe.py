@@ -60,7 +60,8 @@ SYNTHETIC_ENV = "REAZONSPEECH_AMD_SYNTHETIC"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, decoding=None, beam_size=None,
-               precision="bf16", synthetic=False, resample="host", token_scores=False, hotwords_file="", hotwords_score=1.5, hotwords=None):
+               precision="bf16", synthetic=False, resample="host", token_scores=False, hotwords_file="", hotwords_score=1.5, hotwords=None,
+               ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="nemo"):
     """Load the ReazonSpeech FastConformer-RNNT model onto a ROCm GPU.
 
     Args:
@@ -103,6 +104,17 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         adds the score per matched token to hypotheses that spell a phrase out, inside its ranking, and takes it back when the
         match breaks off (include/rs_asr.h rs_rnnt_alsd_hotwords).  The graph is built and uploaded once, here;
         `transcribe(..., hotwords=...)` replaces it per call.  Non-empty hotwords with a decoding other than "alsd" raise ValueError.
+      ngram_lm_model (str or NgramLm), ngram_lm_alpha (float), ngram_lm_tokens (str): shallow fusion of a backoff n-gram language
+        model into the ALSD beam search, with NeMo's keyword names (`decoding.beam.ngram_lm_model` / `ngram_lm_alpha`): an ARPA text
+        file (`.gz` allowed; a KenLM binary raises ValueError: only ARPA text is read) or an `NgramLm` built by
+        runtime/ngram_lm.py.  Every label expansion's score gets `ngram_lm_alpha` x the LM's natural-log probability of the token
+        after the hypothesis's labels, inside the ranking (include/rs_asr.h rs_rnnt_alsd_lm); no end-of-sentence term.
+        `ngram_lm_tokens` says how a word of the file names a token: "nemo" (default) = one character chr(id + 100), which is
+        [UPSTREAM, UNVERIFIED] believed to be what NeMo's train_kenlm.py writes for BPE models; "pieces" = the vocabulary's piece
+        strings; "ids" = decimal ids.  Checked before anything is loaded: FileNotFoundError for a missing file, ValueError for an
+        alpha that is no finite number >= 0, an unknown `ngram_lm_tokens`, or an LM with a decoding other than "alsd".  Stored as
+        `model.ngram_lm` and `model.ngram_lm_alpha`, both may be set later; alpha 0 = the search without the LM.  The
+        `decoding.beam.ngram_lm_model` key of a checkpoint's yaml is NOT read (it is a path of the training machine).
       pos_cap (int): encoder frames (80 ms each) the resident relative-position tables cover at load time
         (default 1024, about 82 s); longer utterances grow the tables on first use.
 
@@ -121,6 +133,10 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
     if decoding is not None:               # (a checkpoint's own strategy is only known once it is read: checked again below)
         nemo_hotwords.check_keywords(str(decoding), hotwords_file, hotwords_score, hotwords)
+    from ...runtime import ngram_lm
+    has_lm = ngram_lm.check_keywords(None if decoding is None else str(decoding), ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+    if has_lm and isinstance(ngram_lm_model, (str, os.PathLike)) and not os.path.isfile(ngram_lm_model):
+        raise FileNotFoundError(f"ngram_lm_model {str(ngram_lm_model)!r} does not exist")
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if str(device).startswith("cpu"):
@@ -155,12 +171,17 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     cfg.validate()
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
     has_hotwords = nemo_hotwords.check_keywords(cfg.decoding, hotwords_file, hotwords_score, hotwords)
+    ngram_lm.check_keywords(cfg.decoding, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)      # the checkpoint's own strategy is known now
     model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, **kw)
     model.hotwords_score = float(hotwords_score)
     if has_hotwords:
         model.hotwords = nemo_hotwords.model_graph(model, hotwords, hotwords_file)     # the model's graph (None = nothing left to bias)
         if model.hotwords is not None:
             model.hotword_set((model.hotwords,))                                       # checked and uploaded once, at load
+    model.ngram_lm_alpha = float(ngram_lm_alpha)
+    if has_lm:
+        model.ngram_lm = ngram_lm.model_lm(model, ngram_lm_model, ngram_lm_tokens)
+        model.ngram_set(model.ngram_lm)                                                # checked and uploaded once, at load
     return model
 
 
@@ -180,6 +201,10 @@ def transcribe_batch(model, audios, config=None, distributed=False, hotwords=Non
     its own graph inside the one batch.  Needs `decoding="alsd"` (ValueError otherwise).  Without hotwords every result is what
     it was.
 
+    A model loaded with an n-gram LM (`load_model(ngram_lm_model=...)`) decodes every batch with `model.ngram_lm` at
+    `model.ngram_lm_alpha`; both may be set between calls (alpha 0 = without the LM).  `transcribe(..., ngram_lm_alpha=)` takes
+    the weight per call.
+
     Returns:
       list[TranscribeResult]
     """
@@ -190,8 +215,11 @@ def transcribe_batch(model, audios, config=None, distributed=False, hotwords=Non
     return _transcribe_graphs(model, audios, config, distributed, graphs)
 
 
-def _transcribe_graphs(model, audios, config, distributed, graphs):
-    """`transcribe_batch` with the hotwords resolved: `graphs` = None, or one HotwordGraph / None per audio"""
+def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alpha=None):
+    """`transcribe_batch` with the hotwords resolved: `graphs` = None, or one HotwordGraph / None per audio; `ngram_lm_alpha`: the
+    n-gram LM's weight in this call (None = the model's value, 0 = without the LM; a value with no LM loaded raises ValueError)"""
+    from ...runtime import ngram_lm
+    lm = ngram_lm.call_alpha(model, ngram_lm_alpha)
     # 16 kHz mono float32 waveforms (transcribe.py:44 minus the padding, which the kernel applies)
     waves = [np.ascontiguousarray(w, dtype=np.float32) for w in norm_batch(model, audios, norm_audio)]
     if config.verbose:
@@ -222,13 +250,18 @@ def _transcribe_graphs(model, audios, config, distributed, graphs):
         raise ValueError("token_scores is on: the distributed path does not gather token log-probabilities (transcribe_batch(distributed=False) "
                          "on each rank, or load the model without token_scores)")
     if distributed:
-        to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves, hotwords=graphs))
+        to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves, hotwords=graphs, **_lm_kw(lm)))
     else:
-        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs)
+        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs, **_lm_kw(lm))
     return results
 
 
-def transcribe(model, audio, config=None, hotwords=None):
+def _lm_kw(lm):
+    """the `ngram_lm` keyword of the runtime for a resolved (NgramLm or None, alpha): (None, 0) runs the call without an LM"""
+    return {"ngram_lm": lm}
+
+
+def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None):
     """Inference of one utterance (transcribe.py:30-60).
 
     Args:
@@ -237,6 +270,8 @@ def transcribe(model, audio, config=None, hotwords=None):
         config (TranscribeConfig): additional settings
         hotwords: phrases to favour in this call INSTEAD OF the model's: a string of phrases separated by `/`, or a list of
             phrases, each with an optional ` :score`; None = the model's hotwords, if any (needs `decoding="alsd"`)
+        ngram_lm_alpha: the weight of the model's n-gram LM in this call: None = `model.ngram_lm_alpha`, 0 = this call without the
+            LM; a value when no LM is loaded raises ValueError
 
     Returns:
         TranscribeResult
@@ -245,4 +280,4 @@ def transcribe(model, audio, config=None, hotwords=None):
         config = TranscribeConfig()
     from ...runtime import nemo_hotwords
     graphs = nemo_hotwords.per_audio(model, hotwords, 1, single=True)
-    return _transcribe_graphs(model, [audio], config, False, graphs)[0]
+    return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha)[0]

@@ -35,6 +35,7 @@ EXPORTS = [
     "rs_rnnt_mbs", "rs_rnnt_mbs_workspace_bytes",
     "rs_rnnt_mbs_hotwords", "rs_rnnt_mbs_hotwords_workspace_bytes", "rs_hotwords_check",
     "rs_rnnt_alsd_hotwords", "rs_rnnt_alsd_hotwords_workspace_bytes",
+    "rs_rnnt_alsd_lm", "rs_rnnt_alsd_lm_workspace_bytes", "rs_ngram_check",
     "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
@@ -79,6 +80,33 @@ def hotwords_check(table):
     rc = lib.rs_hotwords_check(byref(t), msg, len(msg))
     if rc != RS_OK:
         raise RsError(rc, msg.value.decode() or "rs_hotwords_check failed")
+
+
+NGRAM_ARRAYS = ("child_begin", "child_tok", "child_node", "root_child", "logp", "backoff", "suffix", "level")   # `struct rs_ngram`, in its order
+NGRAM_FLOATS = ("logp", "backoff")
+
+
+class RsNgram(Structure):
+    """mirror of `struct rs_ngram` (device pointers) / `rs_ngram_host` (host pointers)"""
+    _fields_ = [(name, c_void_p) for name in NGRAM_ARRAYS] + [("n_nodes", c_int32), ("n_children", c_int32), ("n_logits", c_int32),
+                                                             ("order", c_int32), ("start", c_int32), ("unk_logp", c_float)]
+
+
+def ngram_check(arrays, start, order, unk_logp):
+    """rs_ngram_check on a host table: `arrays` = dict of numpy arrays (NGRAM_ARRAYS: int32, logp / backoff float32).  Pure host
+    code.  Raises RsError(RS_EINVAL, reason) for a table the search must not be given."""
+    import numpy as np
+    lib = load()
+    keep = {k: np.ascontiguousarray(arrays[k], dtype=np.float32 if k in NGRAM_FLOATS else np.int32) for k in NGRAM_ARRAYS}
+    t = RsNgram(*[c_void_p(keep[k].ctypes.data) for k in NGRAM_ARRAYS], len(keep["logp"]), len(keep["child_tok"]),
+                len(keep["root_child"]), int(order), int(start), float(unk_logp))
+    if len(keep["child_begin"]) != t.n_nodes + 1 or any(len(keep[k]) != t.n_nodes for k in ("backoff", "suffix", "level")) \
+            or len(keep["child_node"]) != t.n_children:
+        raise RsError(RS_EINVAL, "ngram: the arrays of the table disagree in length")
+    msg = ctypes.create_string_buffer(256)
+    rc = lib.rs_ngram_check(byref(t), msg, len(msg))
+    if rc != RS_OK:
+        raise RsError(rc, msg.value.decode() or "rs_ngram_check failed")
 
 
 class RsDims(Structure):
@@ -232,6 +260,11 @@ def load():
     lib.rs_rnnt_alsd_hotwords_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_alsd_hotwords.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp,
                                           POINTER(RsHotwords), vp, vp, c_size_t, vp]
+    lib.rs_rnnt_alsd_lm_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
+    lib.rs_rnnt_alsd_lm_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_alsd_lm.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp,
+                                    POINTER(RsHotwords), vp, POINTER(RsNgram), c_float, vp, c_size_t, vp]
+    lib.rs_ngram_check.argtypes = [POINTER(RsNgram), c_char_p, c_size_t]
     lib.rs_profile_enable.argtypes = [vp, c_int]
     lib.rs_profile_reset.argtypes = [vp]
     lib.rs_profile_read.argtypes = [vp, c_int, POINTER(c_double), POINTER(c_int64), POINTER(c_double),
@@ -500,6 +533,26 @@ class Context:
                                                   ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores),
                                                   byref(hotwords) if hotwords is not None else None, _ptr(graph_of), _ptr(ws),
                                                   ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def alsd_lm_workspace_bytes(self, B, beam, tp_max, max_target_len):
+        ratio, abs_len = self._alsd_budget(max_target_len)
+        n = self.lib.rs_rnnt_alsd_lm_workspace_bytes(self._h, B, beam, tp_max, ratio, abs_len)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_alsd_lm_workspace_bytes: invalid arguments (a finalized Conformer context, B > 0, beam > 0)")
+        return n
+
+    def rnnt_alsd_lm(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores,
+                     hotwords, graph_of, lm, lm_alpha, ws, stream):
+        """rnnt_alsd_hotwords with an n-gram LM in the ranking: `lm` = an RsNgram of device pointers (None, or lm_alpha 0 = no model:
+        rs_rnnt_alsd_hotwords' kernels), `lm_alpha` its weight"""
+        assert steps.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
+        ratio, abs_len = self._alsd_budget(max_target_len)
+        flags = (ALSD_SCORE_NORM if score_norm else 0) | (ALSD_MERGE if merge else 0)
+        self.check(self.lib.rs_rnnt_alsd_lm(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags,
+                                            ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores),
+                                            byref(hotwords) if hotwords is not None else None, _ptr(graph_of),
+                                            byref(lm) if lm is not None else None, float(lm_alpha), _ptr(ws),
+                                            ws.numel() * ws.element_size(), c_void_p(stream)))
 
     def beam_workspace_bytes(self, B, beam, tp_max, max_pops=0):
         n = self.lib.rs_rnnt_beam_workspace_bytes(self._h, B, beam, tp_max, max_pops)

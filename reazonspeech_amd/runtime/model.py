@@ -66,6 +66,7 @@ class _Buffers:
         self.graph_of = torch.full((B,), -1, dtype=i32, device=dev)
         self.h_graph_of = torch.full((B,), -1, dtype=i32).pin_memory()
         self.hw_set = None
+        self.lm = None                  # n-gram LM of the batch (ALSD): (_NgramSet, alpha) or None; `stage` / `fill_host` set it
         self.ws_alsd = None              # beam-search scratch (grows with beam and alignment length): on first use
         self.score_bufs = None           # token scores (`AsrModel.score`): (workspace, logp, top1), on first use
         self.ws = torch.empty((ctx.workspace_bytes(B, self.l_pad),), dtype=torch.uint8, device=dev)
@@ -119,6 +120,7 @@ class _BufView:
         self.frames = cut(base.frames, B, self.u_max)
         self.n_ids, self.scores, self.pops = base.n_ids, base.scores, base.pops
         self.graph_of, self.h_graph_of, self.hw_set = base.graph_of, base.h_graph_of, None
+        self.lm = None
         self.ws, self.ws_dec = base.ws, base.ws_dec
         self.h_audio, self.h_lens = cut(base.h_audio, B, l_max), base.h_lens
         self.h_out = None
@@ -156,6 +158,17 @@ class _HotwordSet:
         self.dev = {k: torch.from_numpy(table[k]).to(device) for k in capi.HOTWORD_ARRAYS}
         self.struct = capi.RsHotwords(*[self.dev[k].data_ptr() if self.dev[k].numel() else None for k in capi.HOTWORD_ARRAYS],
                                       len(table["fail"]), len(table["child_tok"]), len(graphs), int(table["max_level"]))
+
+
+class _NgramSet:
+    """an n-gram LM on the device (runtime/ngram_lm.py: NgramLm), checked by rs_ngram_check before the upload"""
+
+    def __init__(self, lm, device):
+        capi.ngram_check(lm.arrays, lm.start, lm.order, lm.unk_logp)      # raises RsError(RS_EINVAL): nothing is uploaded with a bad table
+        self.key = lm.key
+        self.dev = {k: torch.from_numpy(lm.arrays[k]).to(device) for k in capi.NGRAM_ARRAYS}
+        self.struct = capi.RsNgram(*[self.dev[k].data_ptr() if self.dev[k].numel() else None for k in capi.NGRAM_ARRAYS],
+                                   lm.n_nodes, lm.n_children, lm.n_logits, lm.order, lm.start, float(lm.unk_logp))
 
 
 class AsrModel:
@@ -206,6 +219,9 @@ class AsrModel:
         self._hw_sets = {}              # (graph keys) -> _HotwordSet
         self.hotwords = None            # the model's own HotwordGraph (nemo: load_model(hotwords=...)); None = no hotwords
         self.hotwords_score = 1.5
+        self.ngram_lm = None            # the model's NgramLm (nemo: load_model(ngram_lm_model=...)); None = no LM fusion
+        self.ngram_lm_alpha = 0.0       # its weight in the ALSD ranking; both may be set later
+        self._lm_sets = {}              # NgramLm.key -> _NgramSet
         self._dec_lanes = []            # [(context, stream)] of the decode lanes beyond what was needed so far
         self._streams = None
         self._streams_prio = None
@@ -436,6 +452,15 @@ class AsrModel:
             ctx.rnnt_mbs(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
                          buf.ids, buf.frames, buf.n_ids, buf.scores, buf.ws_alsd, stream)
             return
+        lm = getattr(buf, "lm", None)
+        if cfg.decoding == "alsd" and lm is not None:      # ALSD with an n-gram LM, with or without graphs in the batch (csrc/k_rnnt_alsd.hip, LM form)
+            n = ctx.alsd_lm_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len)
+            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
+                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            ctx.rnnt_alsd_lm(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len, cfg.beam_score_norm,
+                             False, buf.ids, buf.frames, buf.n_ids, buf.scores, hw.struct if hw is not None else None,
+                             buf.graph_of if hw is not None else None, lm[0].struct, lm[1], buf.ws_alsd, stream)
+            return
         if cfg.decoding == "alsd" and hw is not None:      # ALSD with hotwords: the batch has at least one graph (csrc/k_rnnt_alsd.hip, HW form)
             n = ctx.alsd_hotwords_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len)
             if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
@@ -653,6 +678,30 @@ class AsrModel:
         self._hw_sets[key] = hs                           # most recently used last
         return hs
 
+    # ---- n-gram LM (NeMo family: ALSD) ----------------------------------------------------------------------------------------------
+    def ngram_set(self, lm):
+        """the device table of an NgramLm: checked (rs_ngram_check) and uploaded once, then found again by content"""
+        ns = self._lm_sets.pop(lm.key, None)
+        if ns is None:
+            if len(self._lm_sets) >= 2:
+                self._lm_sets.pop(next(iter(self._lm_sets)))
+            with torch.cuda.device(self.device):
+                ns = _NgramSet(lm, self.device)
+        self._lm_sets[lm.key] = ns
+        return ns
+
+    def lm_plan(self, ngram_lm=None):
+        """`ngram_lm`: None = the model's own (`self.ngram_lm`, `self.ngram_lm_alpha`), or (NgramLm or None, alpha) for this call
+        -> (device table, alpha), or None when the call runs without an LM (no model, or alpha 0)"""
+        lm, alpha = (self.ngram_lm, self.ngram_lm_alpha) if ngram_lm is None else ngram_lm
+        if lm is None or not alpha:
+            return None
+        if not (np.isfinite(alpha) and alpha > 0):
+            raise ValueError(f"ngram_lm_alpha must be a finite number >= 0, not {alpha!r}")
+        if self.cfg.decoding != "alsd":
+            raise ValueError(f"an n-gram LM needs decoding='alsd', not {self.cfg.decoding!r}")
+        return self.ngram_set(lm), float(alpha)
+
     def graph_plan(self, hotwords, n):
         """`hotwords`: None, or one HotwordGraph / None per utterance -> (device set, [graph index per utterance, -1 = none]) or None"""
         if hotwords is None:
@@ -688,7 +737,7 @@ class AsrModel:
         buf.hw_set = hw
         return True
 
-    def fill_host(self, waveforms: Sequence[np.ndarray], buf, hotwords=None, members=None):
+    def fill_host(self, waveforms: Sequence[np.ndarray], buf, hotwords=None, members=None, lm=None):
         """copy host waveforms (16 kHz mono float32, un-padded) into the buffer set's pinned staging buffers; the tail of
         every row is zeroed (the kernels mask by length, this only keeps the padding deterministic).  Returns the view of
         `buf` narrowed to this batch's longest utterance."""
@@ -701,11 +750,14 @@ class AsrModel:
         capi.host_stage_rows(view.h_audio, view.l_max, waveforms, buf.h_lens)
         # `hotwords`: the call's `graph_plan`, `members`: this batch's positions in it (the H2D copy is run_pipelined's)
         self._set_graphs(view, hotwords, members)
+        view.lm = lm                             # the call's `lm_plan`
         return view
 
-    def stage(self, waveforms: Sequence[np.ndarray], l_max: Optional[int] = None, buf: Optional[_Buffers] = None, hotwords=None) -> _Buffers:
+    def stage(self, waveforms: Sequence[np.ndarray], l_max: Optional[int] = None, buf: Optional[_Buffers] = None, hotwords=None,
+              ngram_lm=None) -> _Buffers:
         """copy host waveforms (16 kHz mono float32, un-padded) into a pinned buffer and on to HBM; `hotwords`: the call's
-        `graph_plan` (every utterance of it is in this batch), None = no hotwords"""
+        `graph_plan` (every utterance of it is in this batch), None = no hotwords; `ngram_lm`: as `lm_plan` takes it (None = the
+        model's own LM, if it has one)"""
         B = len(waveforms)
         longest = max((len(w) for w in waveforms), default=0)
         l_max = max(int(l_max or 0), longest, 1)
@@ -726,6 +778,7 @@ class AsrModel:
             buf.lens.copy_(buf.h_lens, non_blocking=True)
             if self._set_graphs(buf, hotwords):
                 buf.graph_of.copy_(buf.h_graph_of, non_blocking=True)
+            buf.lm = self.lm_plan(ngram_lm)
         return buf
 
     RESAMPLE_CHUNK = 1 << 28        # float32 samples (1 GiB) one rs_resample launch takes in, and at most writes
@@ -825,7 +878,7 @@ class AsrModel:
             res.token_logprobs = [lp[b, :n[b]].tolist() for b in range(buf.B)]
         return res
 
-    def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None) -> DecodedBatch:
+    def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None, ngram_lm=None) -> DecodedBatch:
         """SPMD form of `transcribe_waveforms` for one process per GPU (`torch.distributed` initialised, RCCL):
         every rank passes the same list, decodes its length-balanced shard on its own GPU and receives all
         hypotheses (ids, frames, encoder lengths and — beam search — scores) in the caller's order after the path's one
@@ -840,7 +893,7 @@ class AsrModel:
             # `batch`: the chunk size of the dealing plan (ragged input is dealt as length-sorted chunks, balanced over the
             # ranks: runtime/dist.py shard_balanced) — this rank's batches are exactly its chunks
             res = self.transcribe_waveforms([waveforms[i] for i in indices], max_batch=min(max_batch, batch),
-                                            hotwords=None if hotwords is None else [hotwords[i] for i in indices])
+                                            hotwords=None if hotwords is None else [hotwords[i] for i in indices], ngram_lm=ngram_lm)
             return res.ids, res.frames, res.enc_lens, res.scores
 
         ids, frames, enc_lens, scores = rdist.sharded_decode([len(w) for w in waveforms], run_local, max_batch=max_batch)
@@ -861,7 +914,7 @@ class AsrModel:
                 self._pool_sets = [_Buffers(self, B, l_max) for _ in range(n_sets)]
         return self._pool_sets[:n_sets]
 
-    def transcribe_waveforms(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, on_batch=None, hotwords=None) -> DecodedBatch:
+    def transcribe_waveforms(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, on_batch=None, hotwords=None, ngram_lm=None) -> DecodedBatch:
         """host float32 waveforms -> token ids / frames (the batched boundary).
 
         `on_batch(indices, decoded)`: called once per batch, in batch order, as soon as that batch's hypotheses are on
@@ -876,14 +929,18 @@ class AsrModel:
 
         `hotwords` (modified beam search or ALSD): None, or one HotwordGraph (runtime/k2_hotwords.py) or None per
         utterance.  The distinct graphs of the call become one device table (`hotword_set`) and every utterance's graph index
-        travels with it through sorting and grouping; a batch without any graph runs the plain search."""
+        travels with it through sorting and grouping; a batch without any graph runs the plain search.
+
+        `ngram_lm` (ALSD): None = the model's own n-gram LM and weight (`self.ngram_lm`, `self.ngram_lm_alpha`), or
+        (NgramLm or None, alpha) for this call; alpha 0 or no model = the search without an LM (`lm_plan`)."""
         n = len(waveforms)
         if n == 0:
             return DecodedBatch([], [], [])
         waveforms = [np.asarray(w, dtype=np.float32) for w in waveforms]
         plan = self.graph_plan(hotwords, n)
+        lm = self.lm_plan(ngram_lm)
         if n <= max_batch:
-            buf = self.stage(waveforms, hotwords=plan)
+            buf = self.stage(waveforms, hotwords=plan, ngram_lm=ngram_lm)
             self.run_device(buf)
             res = self.collect(buf)
             if on_batch is not None:
@@ -902,7 +959,7 @@ class AsrModel:
         pool = self._pool(max_batch, l_max, n_sets)
 
         def fill(i, buf):
-            return self.fill_host([waveforms[k] for k in groups[i]], buf, hotwords=plan, members=groups[i])
+            return self.fill_host([waveforms[k] for k in groups[i]], buf, hotwords=plan, members=groups[i], lm=lm)
 
         # `on_batch` runs on its own thread, in batch order: a decode lane that ran the caller's post-processing itself
         # would start its next batch that much later (ids -> text is ~25 ms of Python per 256 utterances)
