@@ -578,7 +578,7 @@ int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, in
  *   tokens, timestamps AND context state of the one added first stay.  After the utterance's last frame every hypothesis of the
  *   final set gets log_prob += -node_score(context_state); then the winner is chosen, by the rule and tie rule of rs_rnnt_mbs.
  *   scores[b] = the winner's log_prob after that.  An utterance without a graph is searched exactly as by rs_rnnt_mbs.
- * All numbers float32 in the order csrc/k_rnnt_mbs.hip states and tests/k2_hotwords_checker.c restates (bit for bit); scores that
+ * All numbers float32 in the order csrc/k_rnnt_mbs.hip states and tests/k2_mbs_checker.c restates (bit for bit); scores that
  * are multiples of 0.5 make every graph quantity exact.
  *
  * rs_hotwords: the graphs of a call as flat arrays, all graphs concatenated (node and child indices are global):
@@ -638,7 +638,7 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
  *   "nothing finished: the best of the beam" exit applies the same Finalize to every beam entry before comparing.
  *   scores[b] = the winner's score including its net bonus.  A new hypothesis's state is its candidate's state.
  * An utterance without a graph inside a hotword call yields the bits of rs_rnnt_alsd.  All numbers float32 in the order
- * csrc/k_rnnt_alsd.hip states and tests/alsd_hotwords_checker.c restates (bit for bit); scores that are multiples of 0.5 make
+ * csrc/k_rnnt_alsd.hip states and tests/alsd_checker.c restates (bit for bit); scores that are multiples of 0.5 make
  * every graph quantity exact.  The walk on the device is the one of rs_rnnt_mbs_hotwords (csrc/k_rnnt_hotwords.h): counted loops
  * only, an index outside the table is the root and is never dereferenced; validate a table with rs_hotwords_check before upload.
  * rs_rnnt_alsd_hotwords with hw == NULL, n_graphs == 0 or graph_of == NULL launches the plain kernels of rs_rnnt_alsd (the same
@@ -686,7 +686,7 @@ int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* en
  *   Selection ranks these scores, ties as in rs_rnnt_alsd.  Recombination is unchanged (the state is a function of the label
  *   sequence alone) and the first occurrence's state stays.  scores[b] includes the LM terms; rs_rnnt_token_scores keeps reporting
  *   the model's unmodified distribution.
- * All numbers float32 in the order csrc/k_rnnt_alsd.hip / csrc/k_rnnt_ngram.h state and tests/alsd_lm_checker.c restates (bit for
+ * All numbers float32 in the order csrc/k_rnnt_alsd.hip / csrc/k_rnnt_ngram.h state and tests/alsd_checker.c restates (bit for
  * bit).  Every walk on the device is a counted loop (order + 1 backoff steps, 32 bisection steps); a node or child index outside
  * the table is replaced by the root before it is used and a token outside root_child counts as not found: a corrupt table can give
  * a wrong score and nothing else.  rs_ngram_check (pure host code, no context) validates a table before upload: counts and index

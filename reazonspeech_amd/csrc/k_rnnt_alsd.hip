@@ -29,7 +29,7 @@
 // computed from that value; the "nothing finished" exit does the same to every beam entry before comparing.  Phase 3 writes the
 // new row's state.  It is the hotword form of alsd_init_kernel / alsd_select_kernel (template parameter HW): no further launch,
 // no host round trip.  The plain instantiations are the ones launched when no utterance of the call has a graph; inside the
-// hotword form a workgroup whose utterance has none takes the plain statements.  Restated by tests/alsd_hotwords_checker.c.
+// hotword form a workgroup whose utterance has none takes the plain statements.  Restated by tests/alsd_checker.c.
 //
 // N-GRAM LM (rs_rnnt_alsd_lm; the table and `step` are stated in include/rs_asr.h, the walk is k_rnnt_ngram.h).  Every hypothesis
 // row carries an LM state (AlsdHwLm.lmctx, ping-pong; the start hypothesis stands at `start`).  A label candidate's score is
@@ -39,7 +39,7 @@
 // lane j computes candidate j whole — score, hotword step if the utterance has a graph, LM step — and writes it to LDS (c_lm next
 // to c_state).  The LM form is the template parameter LM of alsd_init_kernel / alsd_select_kernel; it is compiled with HW on and
 // carries the call's graphs, or none (graph_of == nullptr: every utterance takes the no-graph statements).  Restated by
-// tests/alsd_lm_checker.c.
+// tests/alsd_checker.c.
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
 #include "k_rnnt_hotwords.h"
@@ -527,41 +527,44 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     const auto select = V <= 64 * 48 ? alsd_select_kernel<48, false> : alsd_select_kernel<0, false>;   // (48: the logits row fits a lane's registers)
     const auto select_hw = V <= 64 * 48 ? alsd_select_kernel<48, true> : alsd_select_kernel<0, true>;  // the hotword form takes the graphs last
     const auto select_lm = V <= 64 * 48 ? alsd_select_kernel<48, true, true> : alsd_select_kernel<0, true, true>;   // the LM form: graphs and model
+    const auto init_lm = alsd_init_kernel<true, true>;
+    const auto init_hw = alsd_init_kernel<true>;
+    const auto init = alsd_init_kernel<false>;
 
-    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-    RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * rs_align((size_t)L * rows * H * 4), s));   // h and c of set 0
-    if (LMF) hipLaunchKernelGGL((alsd_init_kernel<true, true>), dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, hw);
-    else if (HWF) hipLaunchKernelGGL(alsd_init_kernel<true>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, hw_only);
-    else hipLaunchKernelGGL(alsd_init_kernel<false>, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, AlsdNoHw{});
-    // start of sequence: blank token from zero state, slot 0 of every utterance (list built by the init kernel)
-    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) return rc;
-    RS_CHECK_LAUNCH(ctx, "alsd init");
+    // the search, written once: `init_k` and `select_k` are the form's kernels, `tables` their last argument (graphs, model, or nothing)
+    auto search = [&](auto init_k, auto select_k, const auto& tables) -> int {
+        rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+        RS_HIP(ctx, hipMemsetAsync(hset[0], 0, 2 * rs_align((size_t)L * rows * H * 4), s));   // h and c of set 0
+        hipLaunchKernelGGL(init_k, dim3(1), dim3(256), 0, s, st[0], as, enc_lens, B, W, d.blank_id, ratio, abs_len, tables);
+        // start of sequence: blank token from zero state, slot 0 of every utterance (list built by the init kernel)
+        if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[0], rows, s); rc != RS_OK) return rc;
+        RS_CHECK_LAUNCH(ctx, "alsd init");
 
-    const int CHUNK = 16;
-    int32_t hc[8] = {0};
-    bool finished = false;
-    int i = 0;
-    while (!finished && i <= max_steps) {
-        for (int c = 0; c < CHUNK && i <= max_steps; ++c, ++i) {
-            const int p = i & 1, pn = p ^ 1;
-            if (int rc = rs_rnnt_launch_joint_logits(ctx, &st[p], joint_enc, rows, tp_max, W, i, s); rc != RS_OK) return rc;
-            if (LMF) hipLaunchKernelGGL(select_lm, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio,
-                                        abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores, hw);
-            else if (HWF) hipLaunchKernelGGL(select_hw, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio,
-                                             abs_len, score_norm, merge, out_cap, ids, steps, n_ids, scores, hw_only);
-            else hipLaunchKernelGGL(select, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio, abs_len,
-                                    score_norm, merge, out_cap, ids, steps, n_ids, scores, AlsdNoHw{});
-            hipLaunchKernelGGL(alsd_reorder_kernel, dim3(rows), dim3(256), 0, s, as, pn, W, rows, L, H, J, hset[p], cset[p],
-                               gset[p], hset[pn], cset[pn], gset[pn]);
-            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[pn], rows, s); rc != RS_OK) return rc;
+        const int CHUNK = 16;
+        int32_t hc[8] = {0};
+        bool finished = false;
+        int i = 0;
+        while (!finished && i <= max_steps) {
+            for (int c = 0; c < CHUNK && i <= max_steps; ++c, ++i) {
+                const int p = i & 1, pn = p ^ 1;
+                if (int rc = rs_rnnt_launch_joint_logits(ctx, &st[p], joint_enc, rows, tp_max, W, i, s); rc != RS_OK) return rc;
+                hipLaunchKernelGGL(select_k, dim3(B), dim3(64 * W), 0, s, st[p], as, zbuf, zstride, enc_lens, B, W, V, d.blank_id, i, ratio, abs_len,
+                                   score_norm, merge, out_cap, ids, steps, n_ids, scores, tables);
+                hipLaunchKernelGGL(alsd_reorder_kernel, dim3(rows), dim3(256), 0, s, as, pn, W, rows, L, H, J, hset[p], cset[p],
+                                   gset[p], hset[pn], cset[pn], gset[pn]);
+                if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st[pn], rows, s); rc != RS_OK) return rc;
+            }
+            RS_CHECK_LAUNCH(ctx, "alsd step");
+            RS_HIP(ctx, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, s));
+            RS_HIP(ctx, hipStreamSynchronize(s));
+            finished = hc[4] >= B;
         }
-        RS_CHECK_LAUNCH(ctx, "alsd step");
-        RS_HIP(ctx, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, s));
-        RS_HIP(ctx, hipStreamSynchronize(s));
-        finished = hc[4] >= B;
-    }
-    prof.end();
-    if (!finished) return rs_fail(ctx, RS_ESTATE, "alsd: %d of %d utterances unfinished after %d alignment steps", B - hc[4], B, max_steps + 1);
-    if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "alsd: a hypothesis has more than out_cap=%d labels", out_cap);
-    return RS_OK;
+        prof.end();
+        if (!finished) return rs_fail(ctx, RS_ESTATE, "alsd: %d of %d utterances unfinished after %d alignment steps", B - hc[4], B, max_steps + 1);
+        if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "alsd: a hypothesis has more than out_cap=%d labels", out_cap);
+        return RS_OK;
+    };
+    if (LMF) return search(init_lm, select_lm, hw);
+    if (HWF) return search(init_hw, select_hw, hw_only);
+    return search(init, select, AlsdNoHw{});
 }

@@ -43,7 +43,7 @@
 // (delta, state') = step(parent's state, v), log_prob = lp[h][v] + delta; one that appends nothing keeps its parent's state.  The
 // merge adds log_probs with their bonuses inside; tokens, timestamps AND state of the entry added first stay.  At the utterance's
 // last frame every entry of the new set gets log_prob = log_prob + (-node_score[state]) (Finalize) BEFORE the winner is chosen;
-// scores[b] is the winner's log_prob after that.  Float32 order of one step, restated by tests/k2_hotwords_checker.c:
+// scores[b] is the winner's log_prob after that.  Float32 order of one step, restated by tests/k2_mbs_checker.c:
 //   child hit:  score = token_score[n];       otherwise:  score = node_score[n] - node_score[state]
 //   non-strict exit (output_score[n] != 0):  delta = (score + out) - node_score[n];     otherwise:  delta = score + output_score[n]
 // It is the hotword form of mbs_select_kernel (template parameter HW): no further launch, no host round trip.  The plain
@@ -451,32 +451,36 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     st.unk = rs_k2_unk_id(ctx);
     const int zstride = rs_joint_zstride(d);
 
-    rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-    RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * rs_align((size_t)rows * D * 4), s));                  // h .. c_tmp are adjacent
-    if (HWF) hipLaunchKernelGGL((mbs_init_kernel<true>), dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, hw);
-    else hipLaunchKernelGGL((mbs_init_kernel<false>), dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, MbsNoHw{});
-    if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
-    RS_CHECK_LAUNCH(ctx, "modified beam search init");
-    const int act_blocks = (int)(((long long)rows * (J / 4) + 255) / 256);
+    const auto init_hw = mbs_init_kernel<true>;
+    const auto init = mbs_init_kernel<false>;
     // the selection kernel: the logits a lane keeps in registers follow from the vocabulary; the hotword form takes the graphs last
     auto select_hw = mbs_select_kernel<4, true>;
     if (V > MBS_THREADS * 4) select_hw = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, true> : mbs_select_kernel<0, true>;
     auto select = mbs_select_kernel<4, false>;
     if (V > MBS_THREADS * 4) select = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, false> : mbs_select_kernel<0, false>;
-    for (int t = 0; t < tp_max; ++t) {
-        hipLaunchKernelGGL(mbs_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, ms, joint_enc, a_pre, rows, tp_max, J, K, t);
-        if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, rows, rows, tp_max, K, t, s); rc != RS_OK) return rc;
-        if (HWF) hipLaunchKernelGGL(select_hw, dim3(B), dim3(MBS_THREADS), 0, s, st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t,
-                                    blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, hw);
-        else hipLaunchKernelGGL(select, dim3(B), dim3(MBS_THREADS), 0, s, st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t,
-                                blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, MbsNoHw{});
+    // the search, written once: `init_k` and `select_k` are the form's kernels, `tables` their last argument (the graphs, or nothing)
+    auto search = [&](auto init_k, auto select_k, const auto& tables) -> int {
+        rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
+        RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * rs_align((size_t)rows * D * 4), s));                  // h .. c_tmp are adjacent
+        hipLaunchKernelGGL(init_k, dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, tables);
         if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
-    }
-    RS_CHECK_LAUNCH(ctx, "modified beam search step");
-    int32_t hc[4] = {0, 0, 0, 0};
-    RS_HIP(ctx, hipMemcpyAsync(hc, st.counters, sizeof hc, hipMemcpyDeviceToHost, s));
-    RS_HIP(ctx, hipStreamSynchronize(s));
-    prof.end();
-    if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "modified beam search: a result has more than out_cap=%d tokens", out_cap);
-    return RS_OK;
+        RS_CHECK_LAUNCH(ctx, "modified beam search init");
+        const int act_blocks = (int)(((long long)rows * (J / 4) + 255) / 256);
+        for (int t = 0; t < tp_max; ++t) {
+            hipLaunchKernelGGL(mbs_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, ms, joint_enc, a_pre, rows, tp_max, J, K, t);
+            if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, rows, rows, tp_max, K, t, s); rc != RS_OK) return rc;
+            hipLaunchKernelGGL(select_k, dim3(B), dim3(MBS_THREADS), 0, s, st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t,
+                               blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, tables);
+            if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
+        }
+        RS_CHECK_LAUNCH(ctx, "modified beam search step");
+        int32_t hc[4] = {0, 0, 0, 0};
+        RS_HIP(ctx, hipMemcpyAsync(hc, st.counters, sizeof hc, hipMemcpyDeviceToHost, s));
+        RS_HIP(ctx, hipStreamSynchronize(s));
+        prof.end();
+        if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "modified beam search: a result has more than out_cap=%d tokens", out_cap);
+        return RS_OK;
+    };
+    if (HWF) return search(init_hw, select_hw, hw);
+    return search(init, select, MbsNoHw{});
 }

@@ -343,25 +343,27 @@ static int alsd_steps(int tp_max, double ratio, int abs_len) {
     return tp_max + budget > 0 ? tp_max + budget : 1;
 }
 
-size_t rs_rnnt_alsd_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
-    RS_GUARD_QUERY(ctx, rs_rnnt_alsd_workspace_bytes, 0);
+// the three workspace queries of ALSD (each entry keeps its own family guard): room for the hotword states and / or the LM states
+static size_t alsd_workspace(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs, bool hotwords,
+                             bool lm) {
     if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
     const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), false, false);
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), hotwords, lm);
+}
+
+size_t rs_rnnt_alsd_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_alsd_workspace_bytes, 0);
+    return alsd_workspace(ctx, B, beam, tp_max, max_target_ratio, max_target_abs, false, false);
 }
 
 size_t rs_rnnt_alsd_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
     RS_GUARD_QUERY(ctx, rs_rnnt_alsd_hotwords_workspace_bytes, 0);
-    if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
-    const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), true, false);
+    return alsd_workspace(ctx, B, beam, tp_max, max_target_ratio, max_target_abs, true, false);
 }
 
 size_t rs_rnnt_alsd_lm_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
     RS_GUARD_QUERY(ctx, rs_rnnt_alsd_lm_workspace_bytes, 0);
-    if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
-    const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), true, true);
+    return alsd_workspace(ctx, B, beam, tp_max, max_target_ratio, max_target_abs, true, true);
 }
 
 // the argument checks and the dispatch of rs_rnnt_alsd, rs_rnnt_alsd_hotwords and rs_rnnt_alsd_lm (hw == nullptr, lm == nullptr: the
@@ -393,20 +395,21 @@ int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
                      nullptr, nullptr, nullptr, 0.0f, workspace, workspace_bytes, stream);
 }
 
-// the table checks of rs_rnnt_alsd_hotwords and rs_rnnt_alsd_lm: RS_OK and *hw the table to search with (nullptr: no graph in this call)
-static int alsd_hotwords_arg(rs_ctx* ctx, const rs_hotwords** hw, const int32_t* graph_of) {
+// the device hotword table of a search entry (`search` = the prefix of its messages): RS_OK and *hw the table to search with
+// (nullptr: no graph in this call).  `any_table`: negative counts are refused on a table nobody points at, too (the ALSD entries).
+static int hotwords_arg(rs_ctx* ctx, const char* search, bool any_table, const rs_hotwords** hw, const int32_t* graph_of) {
     const rs_hotwords* t = *hw;
-    if (t && (t->n_nodes < 0 || t->n_children < 0 || t->n_graphs < 0 || t->max_level < 0))
-        return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: negative count");
+    if (any_table && t && (t->n_nodes < 0 || t->n_children < 0 || t->n_graphs < 0 || t->max_level < 0))
+        return rs_fail(ctx, RS_EINVAL, "%s: hotwords: negative count", search);
     if (t && graph_of && t->n_graphs > 0) {
         if (t->n_nodes < t->n_graphs || t->n_children < 0 || t->max_level < 0)
-            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)", t->n_nodes,
+            return rs_fail(ctx, RS_EINVAL, "%s: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)", search, t->n_nodes,
                            t->n_children, t->n_graphs, t->max_level);
         if (!t->child_begin || !t->fail || !t->output || !t->is_end || !t->level || !t->token_score || !t->node_score ||
             !t->output_score || !t->graph_root || (t->n_children > 0 && (!t->child_tok || !t->child_node)))
-            return rs_fail(ctx, RS_EINVAL, "alsd: hotwords: null array");
+            return rs_fail(ctx, RS_EINVAL, "%s: hotwords: null array", search);
     } else {
-        *hw = nullptr;                                    // no graph in this call: today's kernels, today's bits
+        *hw = nullptr;                                    // no graph in this call: the plain kernels, the plain bits
     }
     return RS_OK;
 }
@@ -416,7 +419,7 @@ int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* en
                           int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace,
                           size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd_hotwords);
-    if (int rc = alsd_hotwords_arg(ctx, &hw, graph_of); rc != RS_OK) return rc;
+    if (int rc = hotwords_arg(ctx, "alsd", true, &hw, graph_of); rc != RS_OK) return rc;
     return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
                      hw, graph_of, nullptr, 0.0f, workspace, workspace_bytes, stream);
 }
@@ -428,7 +431,7 @@ int rs_rnnt_alsd_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens
                     int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
                     float lm_alpha, void* workspace, size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd_lm);
-    if (int rc = alsd_hotwords_arg(ctx, &hw, graph_of); rc != RS_OK) return rc;
+    if (int rc = hotwords_arg(ctx, "alsd", true, &hw, graph_of); rc != RS_OK) return rc;
     if (!(lm_alpha >= 0.0f) || !isfinite(lm_alpha)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: lm_alpha must be a finite number >= 0");
     if (lm && (lm->n_nodes < 0 || lm->n_children < 0 || lm->n_logits < 0)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: negative count");
     if (lm && lm->n_nodes > 0 && lm_alpha != 0.0f) {
@@ -549,16 +552,7 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
         RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * 4, (hipStream_t)stream));
         return RS_OK;
     }
-    if (hw && graph_of && hw->n_graphs > 0) {
-        if (hw->n_nodes < hw->n_graphs || hw->n_children < 0 || hw->max_level < 0)
-            return rs_fail(ctx, RS_EINVAL, "modified beam search: hotwords: bad counts (%d nodes, %d children, %d graphs, max_level %d)",
-                           hw->n_nodes, hw->n_children, hw->n_graphs, hw->max_level);
-        if (!hw->child_begin || !hw->fail || !hw->output || !hw->is_end || !hw->level || !hw->token_score || !hw->node_score ||
-            !hw->output_score || !hw->graph_root || (hw->n_children > 0 && (!hw->child_tok || !hw->child_node)))
-            return rs_fail(ctx, RS_EINVAL, "modified beam search: hotwords: null array");
-    } else {
-        hw = nullptr;                                     // no graph in this call: today's kernels, today's bits
-    }
+    if (int rc = hotwords_arg(ctx, "modified beam search", false, &hw, graph_of); rc != RS_OK) return rc;
     return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
                             out_cap, ids, frames, n_ids, scores, hw, hw ? graph_of : nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }

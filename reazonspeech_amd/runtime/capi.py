@@ -240,30 +240,24 @@ def load():
     lib.rs_rnnt_beam_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_beam.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_beam.restype = c_int
-    lib.rs_rnnt_mbs_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
-    lib.rs_rnnt_mbs_workspace_bytes.restype = c_size_t
-    lib.rs_rnnt_mbs.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp, vp, c_size_t, vp]
-    lib.rs_rnnt_mbs_hotwords_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
-    lib.rs_rnnt_mbs_hotwords_workspace_bytes.restype = c_size_t
-    lib.rs_rnnt_mbs_hotwords.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp, POINTER(RsHotwords), vp, vp,
-                                         c_size_t, vp]
+    # the searches with variants: one prefix (up to `scores`) and one tail (workspace, its size, stream); a variant adds its tables between
+    tail, hw_args = [vp, c_size_t, vp], [POINTER(RsHotwords), vp]
+    mbs = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp]
+    lib.rs_rnnt_mbs.argtypes = mbs + tail
+    lib.rs_rnnt_mbs_hotwords.argtypes = mbs + hw_args + tail
+    for fn in (lib.rs_rnnt_mbs_workspace_bytes, lib.rs_rnnt_mbs_hotwords_workspace_bytes):
+        fn.argtypes, fn.restype = [vp, c_int, c_int, c_int, c_int], c_size_t
     lib.rs_hotwords_check.argtypes = [POINTER(RsHotwords), c_char_p, c_size_t]
     lib.rs_rnnt_token_scores_workspace_bytes.argtypes = [vp, c_int, c_int]
     lib.rs_rnnt_token_scores_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_token_scores.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, vp, c_int, c_int, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_token_scores.restype = c_int
-    lib.rs_rnnt_alsd_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
-    lib.rs_rnnt_alsd_workspace_bytes.restype = c_size_t
-    lib.rs_rnnt_alsd.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp, vp,
-                                 c_size_t, vp]
-    lib.rs_rnnt_alsd_hotwords_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
-    lib.rs_rnnt_alsd_hotwords_workspace_bytes.restype = c_size_t
-    lib.rs_rnnt_alsd_hotwords.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp,
-                                          POINTER(RsHotwords), vp, vp, c_size_t, vp]
-    lib.rs_rnnt_alsd_lm_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int]
-    lib.rs_rnnt_alsd_lm_workspace_bytes.restype = c_size_t
-    lib.rs_rnnt_alsd_lm.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp,
-                                    POINTER(RsHotwords), vp, POINTER(RsNgram), c_float, vp, c_size_t, vp]
+    alsd = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp]
+    lib.rs_rnnt_alsd.argtypes = alsd + tail
+    lib.rs_rnnt_alsd_hotwords.argtypes = alsd + hw_args + tail
+    lib.rs_rnnt_alsd_lm.argtypes = alsd + hw_args + [POINTER(RsNgram), c_float] + tail
+    for fn in (lib.rs_rnnt_alsd_workspace_bytes, lib.rs_rnnt_alsd_hotwords_workspace_bytes, lib.rs_rnnt_alsd_lm_workspace_bytes):
+        fn.argtypes, fn.restype = [vp, c_int, c_int, c_int, c_double, c_int], c_size_t
     lib.rs_ngram_check.argtypes = [POINTER(RsNgram), c_char_p, c_size_t]
     lib.rs_profile_enable.argtypes = [vp, c_int]
     lib.rs_profile_reset.argtypes = [vp]
@@ -499,60 +493,34 @@ class Context:
             return float(max_target_len), -1
         return 0.0, int(max_target_len)
 
-    def alsd_workspace_bytes(self, B, beam, tp_max, max_target_len):
+    def alsd_workspace_bytes(self, B, beam, tp_max, max_target_len, *, hotwords=False, lm=False):
+        """the workspace of `rnnt_alsd` called with a hotword set (`hotwords`) and / or an n-gram LM (`lm`), from the entry's own query"""
         ratio, abs_len = self._alsd_budget(max_target_len)
-        n = self.lib.rs_rnnt_alsd_workspace_bytes(self._h, B, beam, tp_max, ratio, abs_len)
+        name = "rs_rnnt_alsd_lm_workspace_bytes" if lm else "rs_rnnt_alsd_hotwords_workspace_bytes" if hotwords else "rs_rnnt_alsd_workspace_bytes"
+        n = getattr(self.lib, name)(self._h, B, beam, tp_max, ratio, abs_len)
         if n == 0:
-            raise RuntimeError("rs_rnnt_alsd_workspace_bytes: invalid arguments")
+            raise RuntimeError(f"{name}: invalid arguments" + (" (a finalized Conformer context, B > 0, beam > 0)" if lm or hotwords else ""))
         return n
 
     def rnnt_alsd(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, ids, steps, n_ids,
-                  scores, ws, stream):
-        """ids / steps int32 [B][out_cap], n_ids int32 [B], scores float32 [B]"""
-        ratio, abs_len = self._alsd_budget(max_target_len)
-        flags = (ALSD_SCORE_NORM if score_norm else 0) | (ALSD_MERGE if merge else 0)
-        self.check(self.lib.rs_rnnt_alsd(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags,
-                                         ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores), _ptr(ws),
-                                         ws.numel() * ws.element_size(), c_void_p(stream)))
-
-    def alsd_hotwords_workspace_bytes(self, B, beam, tp_max, max_target_len):
-        ratio, abs_len = self._alsd_budget(max_target_len)
-        n = self.lib.rs_rnnt_alsd_hotwords_workspace_bytes(self._h, B, beam, tp_max, ratio, abs_len)
-        if n == 0:
-            raise RuntimeError("rs_rnnt_alsd_hotwords_workspace_bytes: invalid arguments (a finalized Conformer context, B > 0, beam > 0)")
-        return n
-
-    def rnnt_alsd_hotwords(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores,
-                           hotwords, graph_of, ws, stream):
-        """rnnt_alsd with contextual biasing: `hotwords` = an RsHotwords of device pointers (None = no graph: rs_rnnt_alsd's kernels),
-        `graph_of` int32 [B] on the device (-1 = the utterance has no graph)"""
+                  scores, ws, stream, *, hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
+        """ids / steps int32 [B][out_cap], n_ids int32 [B], scores float32 [B].
+        Contextual biasing: `hotwords` = an RsHotwords of device pointers, `graph_of` int32 [B] on the device (-1 = the utterance has
+        no graph).  N-gram LM in the ranking: `lm` = an RsNgram of device pointers, `lm_alpha` its weight (0 = no model).
+        The call goes to the narrowest entry that takes what was passed: rs_rnnt_alsd_lm, rs_rnnt_alsd_hotwords or rs_rnnt_alsd."""
         assert steps.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
         ratio, abs_len = self._alsd_budget(max_target_len)
         flags = (ALSD_SCORE_NORM if score_norm else 0) | (ALSD_MERGE if merge else 0)
-        self.check(self.lib.rs_rnnt_alsd_hotwords(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags,
-                                                  ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores),
-                                                  byref(hotwords) if hotwords is not None else None, _ptr(graph_of), _ptr(ws),
-                                                  ws.numel() * ws.element_size(), c_void_p(stream)))
-
-    def alsd_lm_workspace_bytes(self, B, beam, tp_max, max_target_len):
-        ratio, abs_len = self._alsd_budget(max_target_len)
-        n = self.lib.rs_rnnt_alsd_lm_workspace_bytes(self._h, B, beam, tp_max, ratio, abs_len)
-        if n == 0:
-            raise RuntimeError("rs_rnnt_alsd_lm_workspace_bytes: invalid arguments (a finalized Conformer context, B > 0, beam > 0)")
-        return n
-
-    def rnnt_alsd_lm(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores,
-                     hotwords, graph_of, lm, lm_alpha, ws, stream):
-        """rnnt_alsd_hotwords with an n-gram LM in the ranking: `lm` = an RsNgram of device pointers (None, or lm_alpha 0 = no model:
-        rs_rnnt_alsd_hotwords' kernels), `lm_alpha` its weight"""
-        assert steps.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
-        ratio, abs_len = self._alsd_budget(max_target_len)
-        flags = (ALSD_SCORE_NORM if score_norm else 0) | (ALSD_MERGE if merge else 0)
-        self.check(self.lib.rs_rnnt_alsd_lm(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags,
-                                            ids.shape[1], _ptr(ids), _ptr(steps), _ptr(n_ids), _ptr(scores),
-                                            byref(hotwords) if hotwords is not None else None, _ptr(graph_of),
-                                            byref(lm) if lm is not None else None, float(lm_alpha), _ptr(ws),
-                                            ws.numel() * ws.element_size(), c_void_p(stream)))
+        head = (self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags, ids.shape[1], _ptr(ids), _ptr(steps),
+                _ptr(n_ids), _ptr(scores))
+        tail = (_ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream))
+        hw = (byref(hotwords) if hotwords is not None else None, _ptr(graph_of))
+        if lm is not None or lm_alpha:
+            self.check(self.lib.rs_rnnt_alsd_lm(*head, *hw, byref(lm) if lm is not None else None, float(lm_alpha), *tail))
+        elif hotwords is not None or graph_of is not None:
+            self.check(self.lib.rs_rnnt_alsd_hotwords(*head, *hw, *tail))
+        else:
+            self.check(self.lib.rs_rnnt_alsd(*head, *tail))
 
     def beam_workspace_bytes(self, B, beam, tp_max, max_pops=0):
         n = self.lib.rs_rnnt_beam_workspace_bytes(self._h, B, beam, tp_max, max_pops)
@@ -568,36 +536,28 @@ class Context:
                                          int(max_pops), ids.shape[1], _ptr(ids), _ptr(frames) if frames is not None else None, _ptr(n_ids), _ptr(scores), _ptr(pops), _ptr(ws),
                                          ws.numel() * ws.element_size(), c_void_p(stream)))
 
-    def mbs_workspace_bytes(self, B, max_active_paths, tp_max, out_cap):
-        n = self.lib.rs_rnnt_mbs_workspace_bytes(self._h, B, max_active_paths, tp_max, out_cap)
+    def mbs_workspace_bytes(self, B, max_active_paths, tp_max, out_cap, *, hotwords=False):
+        """the workspace of `rnnt_mbs`, called with a hotword set when `hotwords`, from the entry's own query"""
+        name = "rs_rnnt_mbs_hotwords_workspace_bytes" if hotwords else "rs_rnnt_mbs_workspace_bytes"
+        n = getattr(self.lib, name)(self._h, B, max_active_paths, tp_max, out_cap)
         if n == 0:
-            raise RuntimeError("rs_rnnt_mbs_workspace_bytes: invalid arguments (a Zipformer context, max_active_paths 1..8)")
+            raise RuntimeError(f"{name}: invalid arguments (a Zipformer context, max_active_paths 1..8)")
         return n
 
     def rnnt_mbs(self, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, length_norm, ids, frames, n_ids, scores, ws,
-                 stream):
+                 stream, *, hotwords=None, graph_of=None):
         """sherpa-onnx's modified_beam_search (Zipformer contexts): ids / frames int32 [B][out_cap], n_ids int32 [B], scores
-        float32 [B] (log_prob of the winner, not normalised)"""
-        assert frames.shape == ids.shape
-        self.check(self.lib.rs_rnnt_mbs(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
-                                        MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids), _ptr(frames), _ptr(n_ids),
-                                        _ptr(scores), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
-
-    def mbs_hotwords_workspace_bytes(self, B, max_active_paths, tp_max, out_cap):
-        n = self.lib.rs_rnnt_mbs_hotwords_workspace_bytes(self._h, B, max_active_paths, tp_max, out_cap)
-        if n == 0:
-            raise RuntimeError("rs_rnnt_mbs_hotwords_workspace_bytes: invalid arguments (a Zipformer context, max_active_paths 1..8)")
-        return n
-
-    def rnnt_mbs_hotwords(self, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, length_norm, ids, frames, n_ids, scores,
-                          hotwords, graph_of, ws, stream):
-        """rnnt_mbs with contextual biasing: `hotwords` = an RsHotwords of device pointers (None = no graph: rs_rnnt_mbs itself),
-        `graph_of` int32 [B] on the device (-1 = the utterance has no graph)"""
+        float32 [B] (log_prob of the winner, not normalised).
+        Contextual biasing: `hotwords` = an RsHotwords of device pointers, `graph_of` int32 [B] on the device (-1 = the utterance has
+        no graph); either one passed: rs_rnnt_mbs_hotwords, else rs_rnnt_mbs."""
         assert frames.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
-        self.check(self.lib.rs_rnnt_mbs_hotwords(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths),
-                                                 float(blank_penalty), MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids),
-                                                 _ptr(frames), _ptr(n_ids), _ptr(scores), byref(hotwords) if hotwords is not None else None,
-                                                 _ptr(graph_of), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
+        head = (self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
+                MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids), _ptr(frames), _ptr(n_ids), _ptr(scores))
+        tail = (_ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream))
+        if hotwords is not None or graph_of is not None:
+            self.check(self.lib.rs_rnnt_mbs_hotwords(*head, byref(hotwords) if hotwords is not None else None, _ptr(graph_of), *tail))
+        else:
+            self.check(self.lib.rs_rnnt_mbs(*head, *tail))
 
     def token_scores_workspace_bytes(self, B, u_cap):
         """the MINIMUM workspace of `rnnt_token_scores` (32 rows per chunk); a larger one makes fewer chunks, same bits"""

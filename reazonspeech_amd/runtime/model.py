@@ -423,6 +423,12 @@ class AsrModel:
         B, u_cap = buf.B, buf.ids.shape[1]
         return buf.score_bufs[1][:B * u_cap].view(B, u_cap)
 
+    def _search_ws(self, buf, n):
+        """the buffer set's workspace of the beam searches, grown to `n` bytes"""
+        if buf.ws_alsd is None or buf.ws_alsd.numel() < n:       # (a narrowed view may have sized it for a shorter batch)
+            buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        return buf.ws_alsd
+
     def decode(self, ctx, buf: _Buffers, ws, stream, max_pops=None, decoding=None):
         """stage 3 on `stream`: the checkpoint's decoding strategy (cfg.decoding).  Greedy fills buf.ids / buf.frames
         (emission frames); ALSD fills buf.ids / buf.frames (alignment steps i = frame + labels before) / buf.scores; the
@@ -430,54 +436,26 @@ class AsrModel:
         cfg = self.cfg
         if max_pops is not None or decoding is not None:     # per-call overrides (the caller's retry policy): never written into self.cfg
             cfg = cfg.with_(**({"beam_max_pops": int(max_pops)} if max_pops is not None else {}), **({"decoding": decoding} if decoding is not None else {}))
+        hw = getattr(buf, "hw_set", None)                  # the batch has at least one graph; graph_of goes with a hotword set only
+        hot = dict(hotwords=hw.struct, graph_of=buf.graph_of) if hw is not None else {}
         if cfg.decoding == "beam":
-            n = ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops)
-            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
-                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            sws = self._search_ws(buf, ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops))
             ctx.rnnt_beam(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops,
-                          buf.ids, buf.n_ids, buf.scores, buf.pops, buf.ws_alsd, stream, frames=buf.frames)
-            return
-        hw = getattr(buf, "hw_set", None)
-        if cfg.decoding == "modified_beam_search" and hw is not None:     # ... with hotwords: the batch has at least one graph
-            n = ctx.mbs_hotwords_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1])
-            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
-                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
-            ctx.rnnt_mbs_hotwords(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
-                                  buf.ids, buf.frames, buf.n_ids, buf.scores, hw.struct, buf.graph_of, buf.ws_alsd, stream)
-            return
-        if cfg.decoding == "modified_beam_search":    # Zipformer family: sherpa-onnx's second method (csrc/k_rnnt_mbs.hip)
-            n = ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1])
-            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
-                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
+                          buf.ids, buf.n_ids, buf.scores, buf.pops, sws, stream, frames=buf.frames)
+        elif cfg.decoding == "modified_beam_search":      # Zipformer family: sherpa-onnx's second method (csrc/k_rnnt_mbs.hip)
+            sws = self._search_ws(buf, ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1], hotwords=hw is not None))
             ctx.rnnt_mbs(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
-                         buf.ids, buf.frames, buf.n_ids, buf.scores, buf.ws_alsd, stream)
-            return
-        lm = getattr(buf, "lm", None)
-        if cfg.decoding == "alsd" and lm is not None:      # ALSD with an n-gram LM, with or without graphs in the batch (csrc/k_rnnt_alsd.hip, LM form)
-            n = ctx.alsd_lm_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len)
-            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
-                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
-            ctx.rnnt_alsd_lm(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len, cfg.beam_score_norm,
-                             False, buf.ids, buf.frames, buf.n_ids, buf.scores, hw.struct if hw is not None else None,
-                             buf.graph_of if hw is not None else None, lm[0].struct, lm[1], buf.ws_alsd, stream)
-            return
-        if cfg.decoding == "alsd" and hw is not None:      # ALSD with hotwords: the batch has at least one graph (csrc/k_rnnt_alsd.hip, HW form)
-            n = ctx.alsd_hotwords_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len)
-            if buf.ws_alsd is None or buf.ws_alsd.numel() < n:
-                buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
-            ctx.rnnt_alsd_hotwords(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len,
-                                   cfg.beam_score_norm, False, buf.ids, buf.frames, buf.n_ids, buf.scores, hw.struct, buf.graph_of,
-                                   buf.ws_alsd, stream)
-            return
-        if cfg.decoding != "alsd":
+                         buf.ids, buf.frames, buf.n_ids, buf.scores, sws, stream, **hot)
+        elif cfg.decoding == "alsd":                       # with an n-gram LM and / or graphs in the batch: the LM / HW forms of csrc/k_rnnt_alsd.hip
+            lm = getattr(buf, "lm", None)
+            fused = dict(lm=lm[0].struct, lm_alpha=lm[1]) if lm is not None else {}
+            sws = self._search_ws(buf, ctx.alsd_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len,
+                                                                hotwords=hw is not None, lm=lm is not None))
+            ctx.rnnt_alsd(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len, cfg.beam_score_norm,
+                          False, buf.ids, buf.frames, buf.n_ids, buf.scores, sws, stream, **hot, **fused)
+        else:
             ctx.rnnt_greedy(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, buf.u_max, buf.ids, buf.frames, buf.n_ids,
                             ws, stream)
-            return
-        n = ctx.alsd_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len)
-        if buf.ws_alsd is None or buf.ws_alsd.numel() < n:       # (a narrowed view may have sized it for a shorter batch)
-            buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
-        ctx.rnnt_alsd(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len,
-                      cfg.beam_score_norm, False, buf.ids, buf.frames, buf.n_ids, buf.scores, buf.ws_alsd, stream)
 
     # ------------------------------------------------------------------------------------------
     def run_encoder(self, buf: _Buffers, stream, ctx=None):

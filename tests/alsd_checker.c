@@ -1,9 +1,35 @@
 /*
- * alsd_lm_checker.c — CPU restatement of rs_rnnt_alsd_lm (reazonspeech_amd/csrc/k_rnnt_alsd.hip): the ALSD beam search with hotwords
- * AND an n-gram language model in its ranking, in the device's float32 evaluation order.  TEST INFRASTRUCTURE, built by
- * tests/ngram_lm_ref.py with the flags tests/alsd_hotwords_ref.py uses and linked against the oracle library.  The search is
- * tests/alsd_hotwords_checker.c's, decision for decision (see there for the hotword rules), plus the rule of include/rs_asr.h
- * (rs_rnnt_alsd_lm):
+ * alsd_checker.c — CPU restatement of the ALSD beam search of reazonspeech_amd/csrc/k_rnnt_alsd.hip in the device's float32 evaluation
+ * order: rs_rnnt_alsd, with hotwords (contextual biasing: rs_rnnt_alsd_hotwords) and with an n-gram language model in its ranking
+ * (rs_rnnt_alsd_lm).  The one ALSD checker of the tests.  TEST INFRASTRUCTURE, built by tests/checker_lib.py with the flags of
+ * oracle/build.py and linked against the oracle library (oracle/rnnt_alsd.c, oracle/rnnt_greedy.c), whose search this file repeats
+ * decision for decision (log-softmax reduction rs_oracle_lse, expansion, selection, recombination, finished hypotheses: see
+ * oracle/rnnt_alsd.c) and extends by the context rules and the LM rule of include/rs_asr.h.
+ *
+ * Hotwords.  The graph arrives as the flat table the device reads (all graphs concatenated; graph_of[b] = -1: the utterance has none
+ * and is searched exactly as by oracle/rnnt_alsd.c).  For an utterance with a graph:
+ *   every hypothesis carries a node (`state`); the start hypothesis stands at the root
+ *   expansion of a hypothesis (score hs, state s): the W best non-blank tokens by raw logit, as in the plain search;
+ *     blank:    score = hs + (z[blank] - lse),            state = s
+ *     label v:  (delta, s') = step(s, v),  score = (hs + (z[v] - lse)) + delta,  state = s'
+ *   step(state, v):
+ *     state has a child n on v:  score = token_score[n]
+ *     else: n = fail[state]; while n has no child on v and n is not the root: n = fail[n]; n = its child on v if any;
+ *           score = node_score[n] - node_score[state]
+ *     output_score[n] != 0:  out = is_end[n] ? node_score[n] : output[n] >= 0 ? node_score[output[n]] : node_score[n];
+ *                            delta = (score + out) - node_score[n]; next = root                        (the non-strict exit)
+ *     else:                  delta = score + output_score[n]; next = n
+ *   selection ranks the boosted scores (score desc, expansion order asc); recombination as in the plain search, the first
+ *   occurrence's state stays
+ *   a hypothesis recorded as finished (a blank taken at the last frame): sc = its score after recombination,
+ *     recorded score = sc + (-node_score[state]) (Finalize), normalised score from that value
+ *   nothing finished: the same Finalize on every beam entry before the best is chosen
+ * Hotword counters per utterance (how the batch exercised the graph), hw_counters[b][0..5]: [0] child hits, [1] fail transitions
+ * (steps that left `state` through its fail link), [2] non-strict exits, [3] Finalize applications with a non-zero delta,
+ * [4] recombinations, [5] recombinations whose two states differed (the specification says: never).  finalize[b] = the Finalize
+ * delta inside scores[b].
+ *
+ * Language model (lm_nodes == 0 or alpha == 0: no LM term at all, the search above bit for bit):
  *   every hypothesis carries an LM state (a node of the model's trie); the start hypothesis stands at `start`
  *   the blank candidate keeps score and state
  *   label v of a hypothesis (score hs, LM state s):  cs = hs + (z[v] - lse);  with a graph: cs = cs + delta;
@@ -12,7 +38,6 @@
  *     root; acc = acc + backoff[n]; n = suffix[n].   found: lp = acc + logp[c], next = level[c] < order ? c : suffix[c];
  *     not found: lp = acc + unk_logp, next = root
  *   selection ranks these scores; recombination is unchanged, the first occurrence's state stays
- * lm_nodes == 0 or alpha == 0: no LM term at all (the search of tests/alsd_hotwords_checker.c, bit for bit).
  * LM counters per utterance, lm_counters[b][0..13]: [0..8] hits by the level of the node found (index 0 unused), [9] backoffs (links
  * followed), [10] unk (nothing found at the root), [11] full_order_pops (next = suffix), [12] recombinations; [13] recombinations
  * whose two LM states differed (the specification says: never).
@@ -152,7 +177,7 @@ static void pred_step(const float* x, const hyp_t* p, hyp_t* q, int L, int H, in
 
 /* beam_* (may be NULL): the beam as the search left it — beam_n [B], beam_len / beam_state [B][8], beam_score [B][8],
  * beam_y [B][8][out_cap].  Returns 0, -1 for a bad beam size, -5 when a result did not fit out_cap (it is truncated). */
-int rs_alsd_lm_checker(const float* f, const int32_t* enc_lens, int B, int Tp, int J, int H, int L, int V, int blank,
+int rs_alsd_checker(const float* f, const int32_t* enc_lens, int B, int Tp, int J, int H, int L, int V, int blank,
                              const float* embed, const float* const* lstm_w, const float* const* lstm_b, const float* Wp,
                              const float* bp, const float* Wo, const float* bo, int beam, const int32_t* u_max, int score_norm,
                              int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids, float* scores,

@@ -1,42 +1,31 @@
-"""Helpers of the ALSD hotword tests (tests/test_alsd_hotwords_host.py, tests/test_gpu_alsd_hotwords.py).  TEST INFRASTRUCTURE.
+"""Helpers of the ALSD hotword and LM tests (tests/test_alsd_hotwords_host.py, tests/test_alsd_lm_host.py and their GPU tests).
+TEST INFRASTRUCTURE.
 
-  hw_checker(...)        tests/alsd_hotwords_checker.c through ctypes: the device's float32 order with hotwords, and its counters
+  alsd_checker(...)      tests/alsd_checker.c through ctypes: the device's float32 order with hotwords and LM, and its counters
   hw_float64(...)        oracle/alsd.py's search plus the context rules of include/rs_asr.h (rs_rnnt_alsd_hotwords), in float64,
                          over the pointer graph of tests/k2_hotwords_ref.py (ContextGraph)
   toy_batch / toy_graphs the ragged toy-geometry batch of the GPU test and three phrase lists cut from the plain search's results
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import torch
 
-import k2_hotwords_ref as KR
+import checker_lib
 import k2_mbs_ref as R
-from oracle import alsd as oalsd, build as obuild, greedy as og
+from oracle import alsd as oalsd, greedy as og
 from reazonspeech_amd.runtime import k2_hotwords
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "alsd_hotwords_checker.c")
 MAX_BEAM = 8
 COUNTERS = ("child_hits", "fail_transitions", "exits", "finalized", "recombinations", "state_mismatches")
-EMPTY_TABLE = KR.EMPTY_TABLE
-_lib = None
+LM_COUNTERS = 14
+EMPTY_TABLE = R.EMPTY_TABLE
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        og.lib()
-        out = os.path.join(os.path.dirname(R._out_path()), "alsd_hotwords_checker.so")
-        deps = [SRC, obuild.OUT, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE,
-                                   "-o", out, SRC, obuild.OUT, "-Wl,-rpath," + obuild.HERE, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_alsd_hotwords_checker.restype = ctypes.c_int
-    return _lib
+    L = checker_lib.load("alsd_checker.c")
+    L.rs_alsd_checker.restype = ctypes.c_int
+    return L
 
 
 def table_of(phrase_lists):
@@ -44,11 +33,13 @@ def table_of(phrase_lists):
     return k2_hotwords.concat([k2_hotwords.build_graph(p) for p in phrase_lists])
 
 
-def hw_checker(cfg, sd, f, enc_lens, table=None, graph_of=None, beam=4, max_target_len=2.0, score_norm=True, merge=False, out_cap=None,
-               inject=None, dims=None):
-    """as oracle.greedy.rnnt_alsd, with the flat table of the call's graphs (None = no graph) and graph_of int [B] (-1 = none).
-    -> per utterance a dict: ids, steps, score, score_bits, the COUNTERS, finalize (the Finalize delta inside the score) and beam =
-    [(labels, score, state)] as the search left it.
+def alsd_checker(cfg, sd, f, enc_lens, table=None, graph_of=None, lm=None, alpha=0.0, beam=4, max_target_len=2.0, score_norm=True,
+                 merge=False, out_cap=None, inject=None, dims=None):
+    """as oracle.greedy.rnnt_alsd, with the flat table of the call's graphs (None = no graph), graph_of int [B] (-1 = none), and an
+    NgramLm with its weight (None / 0 = no LM).
+    -> per utterance a dict: ids, steps, score, score_bits, the COUNTERS, finalize (the Finalize delta inside the score), hits
+    [order + 1] (by level), backoffs, unk, full_order_pops, lm_mismatches, and beam = [(labels, score, hotword state, LM state)] as the
+    search left it.
     inject [Tp][V][V] with dims = (V, blank): logits by (frame, last label + 1) instead of the networks (cfg, sd, f unused)."""
     L = lib()
     enc_lens = np.ascontiguousarray(enc_lens, dtype=np.int32)
@@ -86,20 +77,33 @@ def hw_checker(cfg, sd, f, enc_lens, table=None, graph_of=None, beam=4, max_targ
     counters, fin = np.zeros((B, len(COUNTERS)), np.int32), np.zeros((B,), np.float32)
     beam_n, beam_len, beam_state = np.zeros((B,), np.int32), np.zeros((B, MAX_BEAM), np.int32), np.zeros((B, MAX_BEAM), np.int32)
     beam_score, beam_y = np.zeros((B, MAX_BEAM), np.float32), np.zeros((B, MAX_BEAM, out_cap), np.int32)
-    rc = L.rs_alsd_hotwords_checker(
+    lmc, beam_lm = np.zeros((B, LM_COUNTERS), np.int32), np.zeros((B, MAX_BEAM), np.int32)
+    if lm is not None:
+        assert lm.n_logits == V, (lm.n_logits, V)
+        a = lm.arrays
+        lm_args = (ip(a["child_begin"]), ip(a["child_tok"]), ip(a["child_node"]), ip(a["root_child"]), fp(a["logp"]), fp(a["backoff"]),
+                   ip(a["suffix"]), ip(a["level"]), lm.n_nodes, lm.order, lm.start, ctypes.c_float(float(lm.unk_logp)))
+    else:
+        lm_args = (None,) * 8 + (0, 1, 0, ctypes.c_float(0.0))
+    rc = L.rs_alsd_checker(
         net[0], ip(enc_lens), B, Tp, J, H, NL, V, blank, net[1], net[2], net[3], net[4], net[5], net[6], net[7], int(beam), ip(u_max),
         int(bool(score_norm)), int(bool(merge)), int(out_cap), ip(ids), ip(steps), ip(n_ids), fp(scores),
         ip(tab["child_begin"]), ip(tab["child_tok"]), ip(tab["child_node"]), ip(tab["fail"]), ip(tab["output"]), ip(tab["is_end"]),
         fp(tab["token_score"]), fp(tab["node_score"]), fp(tab["output_score"]), ip(tab["graph_root"]), len(tab["graph_root"]),
-        ip(graph_of), ip(counters), fp(fin), inj, ip(beam_n), ip(beam_len), ip(beam_state), fp(beam_score), ip(beam_y))
+        ip(graph_of), ip(counters), fp(fin), inj, ip(beam_n), ip(beam_len), ip(beam_state), fp(beam_score), ip(beam_y),
+        *lm_args, ctypes.c_float(float(alpha)), ip(lmc), ip(beam_lm))
     if rc != 0:
-        raise RuntimeError(f"alsd hotwords checker failed ({rc}; -5 = more than out_cap={out_cap} labels)")
+        raise RuntimeError(f"alsd checker failed ({rc}; -5 = more than out_cap={out_cap} labels)")
     out = []
     for b in range(B):
         d = dict(ids=ids[b, :n_ids[b]].tolist(), steps=steps[b, :n_ids[b]].tolist(), score=float(scores[b]),
                  score_bits=int(scores[b:b + 1].view(np.int32)[0]), finalize=float(fin[b]),
-                 beam=[(beam_y[b, k, :beam_len[b, k]].tolist(), float(beam_score[b, k]), int(beam_state[b, k])) for k in range(beam_n[b])])
+                 beam=[(beam_y[b, k, :beam_len[b, k]].tolist(), float(beam_score[b, k]), int(beam_state[b, k]), int(beam_lm[b, k]))
+                       for k in range(beam_n[b])],
+                 hits=lmc[b, :9].tolist(), backoffs=int(lmc[b, 9]), unk=int(lmc[b, 10]), full_order_pops=int(lmc[b, 11]),
+                 lm_mismatches=int(lmc[b, 13]))
         d.update({name: int(counters[b, i]) for i, name in enumerate(COUNTERS)})
+        assert d["recombinations"] == lmc[b, 12]             # counted once among the hotword counters, once among the LM's
         out.append(d)
     return out
 
@@ -170,7 +174,7 @@ def toy_batch(cfg, seed=7, B=7, Tp=21):
 
 
 def toy_graphs(plain):
-    """Three phrase lists [(token ids, score)] chosen from the PLAIN search's results `plain` (hw_checker without a table at beam
+    """Three phrase lists [(token ids, score)] chosen from the PLAIN search's results `plain` (alsd_checker without a table at beam
     4), so that the graphs are met by what the search proposes; every score is a multiple of 0.5:
       A  cut from the winners: per utterance the winner's first three labels, the labels of its best beam entry that differs, and
          the winner's last two labels followed by one that does not come (a match still pending at the end: Finalize)
@@ -182,7 +186,7 @@ def toy_graphs(plain):
         if len(r["ids"]) >= 2:
             a.append((tuple(r["ids"][:3]), 2.0))
             a.append((tuple(r["ids"][-2:]) + (r["ids"][0],), 2.0))
-        others = [y for y, _, _ in r["beam"] if y != r["ids"] and len(y) >= 1]
+        others = [y for y, *_ in r["beam"] if y != r["ids"] and len(y) >= 1]
         if others:
             a.append((tuple(others[0]), 2.0))
     a = [p for p in a if not (p in seen or seen.add(p))]

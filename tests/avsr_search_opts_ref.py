@@ -9,19 +9,13 @@ TEST INFRASTRUCTURE.
   CASES          the option cases of tests/golden/make_avsr_search_opts_golden.py
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from oracle import build as obuild
-
 import avsr_search_ref as sr
+import checker_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "avsr_search_opts_checker.c")
 NEG = np.float32(-1.0e9)
-_lib = None
 
 NEUTRAL = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, early_stopping=False, num_return_sequences=1)
 
@@ -56,18 +50,11 @@ def with_neutral(opts):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(os.path.dirname(sr._out_path()), "avsr_search_opts_checker.so")
-        deps = [SRC, sr.SRC, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE, "-I", HERE,
-                                   "-o", out, SRC, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_avsr_checker_opts_greedy_step.restype = ctypes.c_int
-        _lib.rs_avsr_checker_opts_beam_step.restype = ctypes.c_int
-        _lib.rs_avsr_checker_opts_logp.restype = None
-    return _lib
+    L = checker_lib.load("avsr_search_opts_checker.c", link_oracle=False, includes=("avsr_search_checker.c",))
+    L.rs_avsr_checker_opts_greedy_step.restype = ctypes.c_int
+    L.rs_avsr_checker_opts_beam_step.restype = ctypes.c_int
+    L.rs_avsr_checker_opts_logp.restype = None
+    return L
 
 
 class OptsChecker(sr.Checker):

@@ -6,43 +6,19 @@
   eos_recipe     the synthetic weights of tests/golden/make_avsr_eos_golden.py: AVSR_TINY whose decoder is biased towards eos
 """
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from oracle import build as obuild
+import checker_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "avsr_search_checker.c")
 MAX_K = 8
-_lib = None
-
-
-def _out_path():
-    for d in (os.path.join(HERE, "_build"), os.path.join(tempfile.gettempdir(), f"rs_avsr_search_{os.getuid()}")):
-        try:
-            os.makedirs(d, exist_ok=True)
-            if os.access(d, os.W_OK):
-                return os.path.join(d, "avsr_search_checker.so")
-        except OSError:
-            continue
-    raise RuntimeError("no writable directory for the checker library")
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = _out_path()
-        deps = [SRC, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE,
-                                   "-o", out, SRC, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_avsr_checker_greedy_step.restype = ctypes.c_int
-        _lib.rs_avsr_checker_beam_step.restype = ctypes.c_int
-    return _lib
+    L = checker_lib.load("avsr_search_checker.c", link_oracle=False)
+    L.rs_avsr_checker_greedy_step.restype = ctypes.c_int
+    L.rs_avsr_checker_beam_step.restype = ctypes.c_int
+    return L
 
 
 def _fp(a):

@@ -9,33 +9,22 @@ TEST INFRASTRUCTURE.
 import ctypes
 import hashlib
 import os
-import subprocess
 
 import numpy as np
 
-from oracle import build as obuild
-
 import avsr_search_ref as sr
 import avsr_search_opts_ref as so
+import checker_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "avsr_token_scores_checker.c")
 GOLDEN_CASES = {"beam": ("beam", {}), "greedy": ("greedy", {}), "combined": ("beam", so.CASES["combined"][2]), "nret3": ("beam", so.CASES["nret3"][2])}
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(os.path.dirname(sr._out_path()), "avsr_token_scores_checker.so")
-        deps = [SRC, so.SRC, sr.SRC, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE, "-I", HERE,
-                                   "-o", out, SRC, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_avsr_checker_scored_greedy_step.restype = ctypes.c_int
-        _lib.rs_avsr_checker_scored_beam_step.restype = ctypes.c_int
-    return _lib
+    L = checker_lib.load("avsr_token_scores_checker.c", link_oracle=False, includes=("avsr_search_opts_checker.c", "avsr_search_checker.c"))
+    L.rs_avsr_checker_scored_greedy_step.restype = ctypes.c_int
+    L.rs_avsr_checker_scored_beam_step.restype = ctypes.c_int
+    return L
 
 
 def golden():

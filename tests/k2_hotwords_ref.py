@@ -6,23 +6,14 @@
   flat_step / FlatView   a numpy walker over the flat table the device reads (strict and non-strict; the product builds only the
                          non-strict walk, in the kernel)
   hw_float64(...)        k2_mbs_ref.mbs_float64 plus the context rules, in float64
-  hw_checker(...)        tests/k2_hotwords_checker.c through ctypes: the device's float32 order with hotwords, and its counters
+The C checker with hotwords is k2_mbs_ref.mbs_checker (tests/k2_mbs_checker.c), given a table and graph_of.
 """
-import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 import k2_mbs_ref as R
-from oracle import build as obuild, greedy as og
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "k2_hotwords_checker.c")
-MAX_K = 8
-_lib = None
 
 
 # ---- the graph, with pointers ------------------------------------------------------------------------------------------------
@@ -211,78 +202,7 @@ def hw_float64(cfg, sd, f, graph, K=4, blank_penalty=0.0, length_norm=True, logi
                 final_gap=top[0] - top[1] if len(top) > 1 else math.inf)
 
 
-# ---- the C checker ---------------------------------------------------------------------------------------------------------------
-def lib():
-    global _lib
-    if _lib is None:
-        og.lib()
-        out = os.path.join(os.path.dirname(R._out_path()), "k2_hotwords_checker.so")
-        deps = [SRC, obuild.OUT, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE,
-                                   "-o", out, SRC, obuild.OUT, "-Wl,-rpath," + obuild.HERE, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_k2_hotwords_checker.restype = ctypes.c_int
-    return _lib
-
-
-EMPTY_TABLE = dict(child_begin=np.zeros(1, np.int32), child_tok=np.zeros(0, np.int32), child_node=np.zeros(0, np.int32),
-                   fail=np.zeros(0, np.int32), output=np.zeros(0, np.int32), is_end=np.zeros(0, np.int32), level=np.zeros(0, np.int32),
-                   token_score=np.zeros(0, np.float32), node_score=np.zeros(0, np.float32), output_score=np.zeros(0, np.float32),
-                   graph_root=np.zeros(0, np.int32), max_level=0)
-
-
-def hw_checker(cfg, sd, f, enc_lens, table=None, graph_of=None, K=4, blank_penalty=0.0, length_norm=True, out_cap=None, workers=None):
-    """as k2_mbs_ref.mbs_checker, with the flat table of the call's graphs (None = no graph) and graph_of int [B] (-1 = none).
-    Per utterance additionally: child_hits, fail_transitions, exits (non-strict), finalize (the sum of the Finalize deltas)."""
-    L = lib()
-    og.lib().rs_oracle_set_joint_act(1)
-    a = R.k2_arrays(sd)
-    f = np.ascontiguousarray(f, dtype=np.float32)
-    B, Tp, J = f.shape
-    enc_lens = np.ascontiguousarray(enc_lens, dtype=np.int32)
-    table = table if table is not None else EMPTY_TABLE
-    tab = {k: np.ascontiguousarray(v, dtype=np.float32 if k.endswith("_score") else np.int32) for k, v in table.items() if k != "max_level"}
-    graph_of = np.ascontiguousarray(graph_of if graph_of is not None else np.full(B, -1), dtype=np.int32)
-    assert len(graph_of) == B
-    if out_cap is None:
-        out_cap = max(Tp, 1)
-    ids, frames = np.zeros((B, out_cap), np.int32), np.zeros((B, out_cap), np.int32)
-    n_ids, merges, fin_n = np.zeros((B,), np.int32), np.zeros((B,), np.int32), np.zeros((B,), np.int32)
-    scores = np.zeros((B,), np.float32)
-    fin_len, fin_lp = np.zeros((B, MAX_K), np.int32), np.zeros((B, MAX_K), np.float32)
-    fin_y = np.zeros((B, MAX_K, out_cap), np.int32)
-    counters, fin_total = np.zeros((B, 3), np.int32), np.zeros((B,), np.float32)
-    fp, ip = og._fp, og._ip
-
-    def rows(b0, b1):
-        return L.rs_k2_hotwords_checker(
-            fp(f[b0:b1]), ip(enc_lens[b0:b1]), b1 - b0, Tp, J, cfg.decoder_dim, cfg.vocab_size, cfg.blank_id, cfg.unk_id, fp(a["embed"]),
-            fp(a["conv_w"]), fp(a["wp"]), fp(a["bp"]), fp(a["wo"]), fp(a["bo"]), int(K), ctypes.c_float(blank_penalty),
-            int(bool(length_norm)), int(out_cap), ip(ids[b0:b1]), ip(frames[b0:b1]), ip(n_ids[b0:b1]), fp(scores[b0:b1]),
-            ip(merges[b0:b1]), ip(fin_n[b0:b1]), ip(fin_len[b0:b1]), fp(fin_lp[b0:b1]), ip(fin_y[b0:b1]),
-            ip(tab["child_begin"]), ip(tab["child_tok"]), ip(tab["child_node"]), ip(tab["fail"]), ip(tab["output"]), ip(tab["is_end"]),
-            fp(tab["token_score"]), fp(tab["node_score"]), fp(tab["output_score"]), ip(tab["graph_root"]), len(tab["graph_root"]),
-            ip(graph_of[b0:b1]), ip(counters[b0:b1]), fp(fin_total[b0:b1]))
-
-    if workers is None:
-        workers = min(16, os.cpu_count() or 1)
-    if B > 1 and workers > 1:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(workers, B)) as pool:
-            rc = min(pool.map(lambda b: rows(b, b + 1), range(B)))
-    else:
-        rc = rows(0, B) if B else 0
-    if rc != 0:
-        raise RuntimeError(f"k2 hotwords checker failed ({rc}; -5 = more than out_cap={out_cap} tokens)")
-    out = []
-    for b in range(B):
-        final = [(fin_y[b, k, :fin_len[b, k]].tolist(), float(fin_lp[b, k])) for k in range(fin_n[b])]
-        out.append(dict(ids=ids[b, :n_ids[b]].tolist(), frames=frames[b, :n_ids[b]].tolist(), score=float(scores[b]),
-                        score_bits=int(scores[b:b + 1].view(np.int32)[0]), merges=int(merges[b]), final=final,
-                        child_hits=int(counters[b, 0]), fail_transitions=int(counters[b, 1]), exits=int(counters[b, 2]),
-                        finalize=float(fin_total[b])))
-    return out
+EMPTY_TABLE = R.EMPTY_TABLE
 
 
 # ---- the graphs of the toy-geometry tests ---------------------------------------------------------------------------------------

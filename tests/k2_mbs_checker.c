@@ -1,13 +1,14 @@
 /*
- * k2_mbs_checker.c — CPU restatement of reazonspeech_amd/csrc/k_rnnt_mbs.hip (rs_rnnt_mbs): sherpa-onnx's modified_beam_search
- * over icefall's stateless decoder and tanh joiner, in the device's float32 evaluation order.  TEST INFRASTRUCTURE, built by
- * tests/k2_mbs_ref.py with the flags of oracle/build.py and linked against the oracle library, whose routines compute the decoder
+ * k2_mbs_checker.c — CPU restatement of reazonspeech_amd/csrc/k_rnnt_mbs.hip (rs_rnnt_mbs, rs_rnnt_mbs_hotwords): sherpa-onnx's
+ * modified_beam_search over icefall's stateless decoder and tanh joiner, without and with hotwords (contextual biasing), in the
+ * device's float32 evaluation order.  The one modified-beam-search checker of the tests.  TEST INFRASTRUCTURE, built by
+ * tests/checker_lib.py with the flags of oracle/build.py and linked against the oracle library, whose routines compute the decoder
  * (rs_oracle_k2_decoder), decoder_proj (rs_oracle_dot) and the joint logits (rs_oracle_joint_argmax with logits_out; the caller
  * sets the joint activation to tanh) — this file holds the search only.
  *
- * [UPSTREAM, not vendored; PARITY UNPINNED] OfflineTransducerModifiedBeamSearchDecoder::Decode without LM / hotwords,
- * Hypotheses::Add, GetMostProbable(length_norm).  Per utterance: one starting hypothesis ys = [-1, blank], log_prob 0; per frame
- * t, for the H <= K hypotheses of the set: logits[h] (blank logit - blank_penalty when the penalty is > 0),
+ * [UPSTREAM, not vendored; PARITY UNPINNED] OfflineTransducerModifiedBeamSearchDecoder::Decode without LM, Hypotheses::Add,
+ * GetMostProbable(length_norm).  Per utterance: one starting hypothesis ys = [-1, blank], log_prob 0; per frame t, for the H <= K
+ * hypotheses of the set: logits[h] (blank logit - blank_penalty when the penalty is > 0),
  * lp[h][v] = ((logits[h][v] - max) - log(sum)) + log_prob[h]; the K largest of the H V values (equal values: the lower flat
  * index h V + v first) in descending order: copy h, append v / t unless v is the blank or <unk>, log_prob = lp[h][v]; a
  * hypothesis whose token sequence equals one already in the new set is merged into it (rs_logaddexpf(old, new), first
@@ -21,6 +22,22 @@
  *   wave w   : lanes l = 0..63 hold s_(64 w + l); for off = 32, 16, 8, 4, 2, 1: every lane l takes s_l + s_(l xor off); lane 0
  *              is the wave's sum
  *   sum      = ((wave0 + wave1) + wave2) + wave3
+ *
+ * Hotwords.  [UPSTREAM, not vendored; PARITY UNPINNED] ContextGraph::ForwardOneStep(strict_mode = false) and Finalize as Decode uses
+ * them; the specification is in include/rs_asr.h (rs_rnnt_mbs_hotwords).  The graph arrives as the flat table the device reads (all
+ * graphs concatenated; graph_of[b] = -1, or no table: the utterance has none and none of the statements below runs for it).  Every
+ * hypothesis carries a node; the K best are selected WITHOUT bonus; each selected candidate that appends a label v walks once,
+ * before the merge:
+ *   state has a child n on v:  score = token_score[n]
+ *   else: n = fail[state]; while n has no child on v and n is not the root: n = fail[n]; n = its child on v if any;
+ *         score = node_score[n] - node_score[state]
+ *   output_score[n] != 0:  out = is_end[n] ? node_score[n] : output[n] >= 0 ? node_score[output[n]] : node_score[n];
+ *                          delta = (score + out) - node_score[n]; next = root                        (the non-strict exit)
+ *   else:                  delta = score + output_score[n]; next = n
+ *   log_prob = lp + delta.  A merged candidate adds its log_prob (bonus inside) by rs_logaddexpf; the first entry's state stays.
+ * After the last frame: log_prob = log_prob + (-node_score[state]) for every entry of the final set, then the winner.
+ * Counters per utterance (how the batch exercised the graph): child hits, fail transitions (steps that left `state` through its
+ * fail link), non-strict exits, and the sum of the Finalize deltas over the final set.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +55,7 @@ typedef struct {
     int n;          /* tokens after the context */
     int t0, t1;     /* the last two entries of ys */
     float lp;
+    int ctx;        /* node of the context graph */
     int32_t* y;     /* [cap] */
     int32_t* fr;    /* [cap] */
     float* g;       /* [J] decoder_proj(decoder(t0, t1)) */
@@ -62,6 +80,43 @@ static float lse_sum(const float* x, int V, float m) {
     return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
+typedef struct {
+    const int32_t *child_begin, *child_tok, *child_node, *fail, *output, *is_end;
+    const float *token_score, *node_score, *output_score;
+} hw_table;
+
+static int hw_child(const hw_table* g, int n, int tok) {
+    for (int c = g->child_begin[n]; c < g->child_begin[n + 1]; ++c)
+        if (g->child_tok[c] == tok) return g->child_node[c];
+    return -1;
+}
+
+/* counters: [0] child hits, [1] fail transitions, [2] non-strict exits */
+static float hw_step(const hw_table* g, int root, int state, int tok, int* next, int32_t* counters) {
+    int n = hw_child(g, state, tok);
+    float score;
+    if (n >= 0) {
+        score = g->token_score[n];
+        counters[0] += 1;
+    } else {
+        n = g->fail[state];
+        while (hw_child(g, n, tok) < 0 && n != root) n = g->fail[n];
+        const int c = hw_child(g, n, tok);
+        if (c >= 0) n = c;
+        score = g->node_score[n] - g->node_score[state];
+        if (state != root) counters[1] += 1;
+    }
+    if (g->output_score[n] != 0.0f) {
+        const int o = g->output[n];
+        const float out = g->is_end[n] ? g->node_score[n] : (o >= 0 ? g->node_score[o] : g->node_score[n]);
+        *next = root;
+        counters[2] += 1;
+        return (score + out) - g->node_score[n];
+    }
+    *next = n;
+    return score + g->output_score[n];
+}
+
 static void hyp_alloc(hyp_t* h, int cap, int J) {
     h->y = (int32_t*)malloc(sizeof(int32_t) * cap);
     h->fr = (int32_t*)malloc(sizeof(int32_t) * cap);
@@ -74,7 +129,12 @@ static void hyp_free(hyp_t* h) { free(h->y); free(h->fr); free(h->g); }
 int rs_k2_mbs_checker(const float* f, const int32_t* enc_lens, int B, int Tp, int J, int D, int V, int blank, int unk,
                       const float* embed, const float* conv_w, const float* Wp, const float* bp, const float* Wo, const float* bo,
                       int K, float blank_penalty, int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids,
-                      float* scores, int32_t* merges, int32_t* final_n, int32_t* final_len, float* final_lp, int32_t* final_y) {
+                      float* scores, int32_t* merges, int32_t* final_n, int32_t* final_len, float* final_lp, int32_t* final_y,
+                      const int32_t* child_begin, const int32_t* child_tok, const int32_t* child_node, const int32_t* hw_fail,
+                      const int32_t* hw_output, const int32_t* is_end, const float* token_score, const float* node_score,
+                      const float* output_score, const int32_t* graph_root, int n_graphs, const int32_t* graph_of,
+                      int32_t* hw_counters /* [B][3] */, float* finalize_total /* [B] */) {
+    const hw_table G = {child_begin, child_tok, child_node, hw_fail, hw_output, is_end, token_score, node_score, output_score};
     if (K < 1 || K > MBS_MAX_K) return -1;
     int overflow = 0;
     const int cap = Tp > 0 ? Tp : 1;
@@ -85,6 +145,11 @@ int rs_k2_mbs_checker(const float* f, const int32_t* enc_lens, int B, int Tp, in
     for (int b = 0; b < B; ++b) {
         int cur = 0, H = 1, n_merge = 0;
         const int T = enc_lens[b];
+        const int gi = graph_of ? graph_of[b] : -1;
+        const int root = (gi >= 0 && gi < n_graphs) ? graph_root[gi] : -1;
+        hw_counters[3 * b] = hw_counters[3 * b + 1] = hw_counters[3 * b + 2] = 0;
+        finalize_total[b] = 0.0f;
+        set[0][0].ctx = root < 0 ? 0 : root;
         {
             hyp_t* h0 = &set[0][0];
             h0->n = 0; h0->t0 = -1; h0->t1 = blank; h0->lp = 0.0f;
@@ -116,12 +181,26 @@ int rs_k2_mbs_checker(const float* f, const int32_t* enc_lens, int B, int Tp, in
                 }
                 sel[n_cand++] = best;
             }
+            /* hotwords: every candidate walks before any merge */
+            float clp[MBS_MAX_K];
+            int cctx[MBS_MAX_K];
+            for (int j = 0; j < n_cand; ++j) {
+                const int h = sel[j] / V, v = sel[j] - h * V;
+                clp[j] = lpv[sel[j]];
+                cctx[j] = old[h].ctx;
+                if (root >= 0 && v != blank && v != unk) {
+                    int nx = root;
+                    const float delta = hw_step(&G, root, old[h].ctx, v, &nx, hw_counters + 3 * b);
+                    clp[j] = clp[j] + delta;
+                    cctx[j] = nx;
+                }
+            }
             int nn = 0;
             for (int j = 0; j < n_cand; ++j) {
                 const int h = sel[j] / V, v = sel[j] - h * V;
                 const int tok = (v != blank && v != unk) ? v : -1;
                 const int n = old[h].n + (tok >= 0 ? 1 : 0);
-                const float lp = lpv[sel[j]];
+                const float lp = clp[j];
                 int merged = 0;
                 for (int e = 0; e < nn && !merged; ++e) {
                     if (nw[e].n != n) continue;
@@ -136,7 +215,7 @@ int rs_k2_mbs_checker(const float* f, const int32_t* enc_lens, int B, int Tp, in
                 hyp_t* d = &nw[nn++];
                 memcpy(d->y, old[h].y, sizeof(int32_t) * old[h].n);
                 memcpy(d->fr, old[h].fr, sizeof(int32_t) * old[h].n);
-                d->n = n; d->lp = lp; d->t0 = old[h].t0; d->t1 = old[h].t1;
+                d->n = n; d->lp = lp; d->t0 = old[h].t0; d->t1 = old[h].t1; d->ctx = cctx[j];
                 if (tok >= 0) {
                     d->y[n - 1] = tok; d->fr[n - 1] = t;
                     d->t0 = old[h].t1; d->t1 = tok;
@@ -149,7 +228,14 @@ int rs_k2_mbs_checker(const float* f, const int32_t* enc_lens, int B, int Tp, in
             cur ^= 1;
             H = nn;
         }
-        const hyp_t* fin = set[cur];
+        hyp_t* fin = set[cur];
+        if (root >= 0 && T > 0)
+            for (int k = 0; k < H; ++k) {                    /* Finalize */
+                const float delta = -node_score[fin[k].ctx];
+                fin[k].lp = fin[k].lp + delta;
+                finalize_total[b] = finalize_total[b] + delta;
+                fin[k].ctx = root;
+            }
         int win = 0;
         float win_norm = 0.0f;
         for (int k = 0; k < H; ++k) {

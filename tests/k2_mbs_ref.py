@@ -1,51 +1,33 @@
 """Helpers of the modified-beam-search tests (tests/test_k2_mbs_host.py, tests/test_gpu_k2_mbs.py).  TEST INFRASTRUCTURE.
 
-  mbs_checker(...)   tests/k2_mbs_checker.c through ctypes: the search of csrc/k_rnnt_mbs.hip restated in the device's float32 order.
-                     Compiled here with the flags of oracle/build.py and linked against the oracle library, whose decoder, projection
-                     and joint-logit routines it calls.
+  mbs_checker(...)   tests/k2_mbs_checker.c through ctypes: the search of csrc/k_rnnt_mbs.hip restated in the device's float32 order,
+                     without or with hotwords, and its counters.  Built by tests/checker_lib.py and linked against the oracle
+                     library, whose decoder, projection and joint-logit routines it calls.
   mbs_float64(...)   a readable torch-float64 restatement of the algorithm (include/rs_asr.h, rs_rnnt_mbs) with Python-float
                      log_prob like upstream; also reports how close the search came to a tie.
 """
 import ctypes
 import math
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import torch
 
-from oracle import build as obuild, greedy as og, zipformer as oz
+import checker_lib
+from oracle import greedy as og, zipformer as oz
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "k2_mbs_checker.c")
 MAX_K = 8
-_lib = None
-
-
-def _out_path():
-    for d in (os.path.join(HERE, "_build"), os.path.join(tempfile.gettempdir(), f"rs_k2_mbs_{os.getuid()}")):
-        try:
-            os.makedirs(d, exist_ok=True)
-            if os.access(d, os.W_OK):
-                return os.path.join(d, "k2_mbs_checker.so")
-        except OSError:
-            continue
-    raise RuntimeError("no writable directory for the checker library")
+# the flat hotword table (reazonspeech_amd.runtime.k2_hotwords.concat) of no graph at all
+EMPTY_TABLE = dict(child_begin=np.zeros(1, np.int32), child_tok=np.zeros(0, np.int32), child_node=np.zeros(0, np.int32),
+                   fail=np.zeros(0, np.int32), output=np.zeros(0, np.int32), is_end=np.zeros(0, np.int32), level=np.zeros(0, np.int32),
+                   token_score=np.zeros(0, np.float32), node_score=np.zeros(0, np.float32), output_score=np.zeros(0, np.float32),
+                   graph_root=np.zeros(0, np.int32), max_level=0)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        og.lib()                                             # builds oracle/librs_oracle.so when stale, and loads it
-        out = _out_path()
-        deps = [SRC, obuild.OUT, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE,
-                                   "-o", out, SRC, obuild.OUT, "-Wl,-rpath," + obuild.HERE, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_k2_mbs_checker.restype = ctypes.c_int
-    return _lib
+    L = checker_lib.load("k2_mbs_checker.c")
+    L.rs_k2_mbs_checker.restype = ctypes.c_int
+    return L
 
 
 def k2_arrays(sd):
@@ -54,16 +36,21 @@ def k2_arrays(sd):
                 bp=c("joiner.decoder_proj.bias"), wo=c("joiner.output_linear.weight"), bo=c("joiner.output_linear.bias"))
 
 
-def mbs_checker(cfg, sd, f, enc_lens, K=4, blank_penalty=0.0, length_norm=True, out_cap=None, workers=None):
-    """f float32 [B, Tp, J] (numpy) = joiner.encoder_proj(encoder output), enc_lens int [B] -> per utterance a dict(ids, frames,
-    score (float32 log_prob of the winner), merges, final = [(tokens, float32 log_prob)] of the last set in the order of entry).
-    Utterances are independent: rows run on `workers` threads."""
+def mbs_checker(cfg, sd, f, enc_lens, table=None, graph_of=None, K=4, blank_penalty=0.0, length_norm=True, out_cap=None, workers=None):
+    """f float32 [B, Tp, J] (numpy) = joiner.encoder_proj(encoder output), enc_lens int [B], the flat table of the call's graphs
+    (None = no graph) and graph_of int [B] (-1 = none) -> per utterance a dict(ids, frames, score (float32 log_prob of the winner),
+    score_bits, merges, final = [(tokens, float32 log_prob)] of the last set in the order of entry, child_hits, fail_transitions,
+    exits (non-strict), finalize (the sum of the Finalize deltas)).  Utterances are independent: rows run on `workers` threads."""
     L = lib()
     og.lib().rs_oracle_set_joint_act(1)                      # the Zipformer joiner is tanh (as oracle/k2_greedy.c sets it)
     a = k2_arrays(sd)
     f = np.ascontiguousarray(f, dtype=np.float32)
     B, Tp, J = f.shape
     enc_lens = np.ascontiguousarray(enc_lens, dtype=np.int32)
+    table = table if table is not None else EMPTY_TABLE
+    tab = {k: np.ascontiguousarray(v, dtype=np.float32 if k.endswith("_score") else np.int32) for k, v in table.items() if k != "max_level"}
+    graph_of = np.ascontiguousarray(graph_of if graph_of is not None else np.full(B, -1), dtype=np.int32)
+    assert len(graph_of) == B
     if out_cap is None:
         out_cap = max(Tp, 1)
     ids, frames = np.zeros((B, out_cap), np.int32), np.zeros((B, out_cap), np.int32)
@@ -71,14 +58,18 @@ def mbs_checker(cfg, sd, f, enc_lens, K=4, blank_penalty=0.0, length_norm=True, 
     scores = np.zeros((B,), np.float32)
     fin_len, fin_lp = np.zeros((B, MAX_K), np.int32), np.zeros((B, MAX_K), np.float32)
     fin_y = np.zeros((B, MAX_K, out_cap), np.int32)
+    counters, fin_total = np.zeros((B, 3), np.int32), np.zeros((B,), np.float32)
     fp, ip = og._fp, og._ip
 
     def rows(b0, b1):
-        return L.rs_k2_mbs_checker(fp(f[b0:b1]), ip(enc_lens[b0:b1]), b1 - b0, Tp, J, cfg.decoder_dim, cfg.vocab_size, cfg.blank_id,
-                                   cfg.unk_id, fp(a["embed"]), fp(a["conv_w"]), fp(a["wp"]), fp(a["bp"]), fp(a["wo"]), fp(a["bo"]),
-                                   int(K), ctypes.c_float(blank_penalty), int(bool(length_norm)), int(out_cap), ip(ids[b0:b1]),
-                                   ip(frames[b0:b1]), ip(n_ids[b0:b1]), fp(scores[b0:b1]), ip(merges[b0:b1]), ip(fin_n[b0:b1]),
-                                   ip(fin_len[b0:b1]), fp(fin_lp[b0:b1]), ip(fin_y[b0:b1]))
+        return L.rs_k2_mbs_checker(
+            fp(f[b0:b1]), ip(enc_lens[b0:b1]), b1 - b0, Tp, J, cfg.decoder_dim, cfg.vocab_size, cfg.blank_id, cfg.unk_id, fp(a["embed"]),
+            fp(a["conv_w"]), fp(a["wp"]), fp(a["bp"]), fp(a["wo"]), fp(a["bo"]), int(K), ctypes.c_float(blank_penalty),
+            int(bool(length_norm)), int(out_cap), ip(ids[b0:b1]), ip(frames[b0:b1]), ip(n_ids[b0:b1]), fp(scores[b0:b1]),
+            ip(merges[b0:b1]), ip(fin_n[b0:b1]), ip(fin_len[b0:b1]), fp(fin_lp[b0:b1]), ip(fin_y[b0:b1]),
+            ip(tab["child_begin"]), ip(tab["child_tok"]), ip(tab["child_node"]), ip(tab["fail"]), ip(tab["output"]), ip(tab["is_end"]),
+            fp(tab["token_score"]), fp(tab["node_score"]), fp(tab["output_score"]), ip(tab["graph_root"]), len(tab["graph_root"]),
+            ip(graph_of[b0:b1]), ip(counters[b0:b1]), fp(fin_total[b0:b1]))
 
     if workers is None:
         workers = min(16, os.cpu_count() or 1)
@@ -94,7 +85,9 @@ def mbs_checker(cfg, sd, f, enc_lens, K=4, blank_penalty=0.0, length_norm=True, 
     for b in range(B):
         final = [(fin_y[b, k, :fin_len[b, k]].tolist(), float(fin_lp[b, k])) for k in range(fin_n[b])]
         out.append(dict(ids=ids[b, :n_ids[b]].tolist(), frames=frames[b, :n_ids[b]].tolist(), score=float(scores[b]),
-                        score_bits=int(scores[b:b + 1].view(np.int32)[0]), merges=int(merges[b]), final=final))
+                        score_bits=int(scores[b:b + 1].view(np.int32)[0]), merges=int(merges[b]), final=final,
+                        child_hits=int(counters[b, 0]), fail_transitions=int(counters[b, 1]), exits=int(counters[b, 2]),
+                        finalize=float(fin_total[b])))
     return out
 
 

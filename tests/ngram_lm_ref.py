@@ -4,30 +4,22 @@ TEST INFRASTRUCTURE.
   write_arpa(path, entries, ...)  an ARPA file from {(words...): (log10 p, log10 backoff or None)}
   ArpaDict                        the textbook dictionary implementation of ARPA backoff, float64
   step(lm, state, tok)            include/rs_asr.h's `step` over the flat arrays of an NgramLm, in float32
-  lm_checker(...)                 tests/alsd_lm_checker.c through ctypes: the device's float32 order with hotwords and LM, its counters
+  (the C checker with an LM is alsd_hotwords_ref.alsd_checker, tests/alsd_checker.c, given lm and alpha)
   lm_float64(...)                 oracle/alsd.py's search plus the hotword rules plus the LM rule, in float64
   toy_lm(plain, cfg)              an order-3 LM cut from the plain search's results; random_lm(...) a large synthetic one"""
-import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import torch
 
-import alsd_hotwords_ref as AR
-import k2_mbs_ref as R
-from oracle import alsd as oalsd, build as obuild, greedy as og
+from oracle import alsd as oalsd
 from reazonspeech_amd.runtime import ngram_lm as NL
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "alsd_lm_checker.c")
 TOY_ARPA = os.path.join(HERE, "golden", "toy_3gram.arpa")
-MAX_BEAM = 8
-LM_COUNTERS = 14
 BOS = NL.BOS
 LN10 = math.log(10.0)
-_lib = None
 
 
 # ---- ARPA text -------------------------------------------------------------------------------------------------------------------
@@ -108,92 +100,6 @@ def walk(lm, tokens, state=None):
     return s
 
 
-# ---- the C checker -----------------------------------------------------------------------------------------------------------------
-def lib():
-    global _lib
-    if _lib is None:
-        og.lib()
-        out = os.path.join(os.path.dirname(R._out_path()), "alsd_lm_checker.so")
-        deps = [SRC, obuild.OUT, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE,
-                                   "-o", out, SRC, obuild.OUT, "-Wl,-rpath," + obuild.HERE, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_alsd_lm_checker.restype = ctypes.c_int
-    return _lib
-
-
-def lm_checker(cfg, sd, f, enc_lens, lm=None, alpha=0.0, table=None, graph_of=None, beam=4, max_target_len=2.0, score_norm=True,
-               merge=False, out_cap=None, inject=None, dims=None):
-    """as AR.hw_checker, with an NgramLm and its weight (None / 0 = no LM).  -> per utterance a dict: ids, steps, score, score_bits,
-    the hotword COUNTERS, hits [order + 1] (by level), backoffs, unk, full_order_pops, recombinations, lm_mismatches, and beam =
-    [(labels, score, hotword state, LM state)]"""
-    L = lib()
-    enc_lens = np.ascontiguousarray(enc_lens, dtype=np.int32)
-    B = len(enc_lens)
-    PF = ctypes.POINTER(ctypes.c_float)
-    fp, ip = og._fp, og._ip
-    if inject is None:
-        arr = og.decoder_arrays(cfg, sd)
-        f = np.ascontiguousarray(f, dtype=np.float32)
-        assert f.shape[0] == B
-        _, Tp, J = f.shape
-        H, NL_, V, blank = cfg.pred_hidden, cfg.pred_layers, cfg.n_logits, cfg.blank_id
-        wl = (PF * NL_)(*[fp(w) for w in arr["lstm_w"]])
-        bl = (PF * NL_)(*[fp(b) for b in arr["lstm_b"]])
-        net = (fp(f), fp(arr["embed"]), wl, bl, fp(arr["Wp"]), fp(arr["bp"]), fp(arr["Wo"]), fp(arr["bo"]))
-        og.lib().rs_oracle_set_joint_act(0)
-        inj = None
-    else:
-        inject = np.ascontiguousarray(inject, dtype=np.float32)
-        V, blank = dims
-        Tp = inject.shape[0]
-        assert inject.shape == (Tp, V, V)
-        J, H, NL_ = 1, 1, 1
-        net = (None,) * 8
-        inj = fp(inject)
-    u_max = og.alsd_budget(enc_lens, max_target_len)
-    if out_cap is None:
-        out_cap = max(1, int((enc_lens + u_max).max())) if B else 1
-    table = table if table is not None else AR.EMPTY_TABLE
-    tab = {k: np.ascontiguousarray(v, dtype=np.float32 if k.endswith("_score") else np.int32) for k, v in table.items() if k != "max_level"}
-    graph_of = np.ascontiguousarray(graph_of if graph_of is not None else np.full(B, -1), dtype=np.int32)
-    assert len(graph_of) == B
-    ids, steps = np.zeros((B, out_cap), np.int32), np.zeros((B, out_cap), np.int32)
-    n_ids, scores = np.zeros((B,), np.int32), np.zeros((B,), np.float32)
-    counters, fin = np.zeros((B, len(AR.COUNTERS)), np.int32), np.zeros((B,), np.float32)
-    beam_n, beam_len, beam_state = np.zeros((B,), np.int32), np.zeros((B, MAX_BEAM), np.int32), np.zeros((B, MAX_BEAM), np.int32)
-    beam_score, beam_y = np.zeros((B, MAX_BEAM), np.float32), np.zeros((B, MAX_BEAM, out_cap), np.int32)
-    lmc, beam_lm = np.zeros((B, LM_COUNTERS), np.int32), np.zeros((B, MAX_BEAM), np.int32)
-    if lm is not None:
-        assert lm.n_logits == V, (lm.n_logits, V)
-        a = lm.arrays
-        lm_args = (ip(a["child_begin"]), ip(a["child_tok"]), ip(a["child_node"]), ip(a["root_child"]), fp(a["logp"]), fp(a["backoff"]),
-                   ip(a["suffix"]), ip(a["level"]), lm.n_nodes, lm.order, lm.start, ctypes.c_float(float(lm.unk_logp)))
-    else:
-        lm_args = (None,) * 8 + (0, 1, 0, ctypes.c_float(0.0))
-    rc = L.rs_alsd_lm_checker(
-        net[0], ip(enc_lens), B, Tp, J, H, NL_, V, blank, net[1], net[2], net[3], net[4], net[5], net[6], net[7], int(beam), ip(u_max),
-        int(bool(score_norm)), int(bool(merge)), int(out_cap), ip(ids), ip(steps), ip(n_ids), fp(scores),
-        ip(tab["child_begin"]), ip(tab["child_tok"]), ip(tab["child_node"]), ip(tab["fail"]), ip(tab["output"]), ip(tab["is_end"]),
-        fp(tab["token_score"]), fp(tab["node_score"]), fp(tab["output_score"]), ip(tab["graph_root"]), len(tab["graph_root"]),
-        ip(graph_of), ip(counters), fp(fin), inj, ip(beam_n), ip(beam_len), ip(beam_state), fp(beam_score), ip(beam_y),
-        *lm_args, ctypes.c_float(float(alpha)), ip(lmc), ip(beam_lm))
-    if rc != 0:
-        raise RuntimeError(f"alsd lm checker failed ({rc}; -5 = more than out_cap={out_cap} labels)")
-    out = []
-    for b in range(B):
-        d = dict(ids=ids[b, :n_ids[b]].tolist(), steps=steps[b, :n_ids[b]].tolist(), score=float(scores[b]),
-                 score_bits=int(scores[b:b + 1].view(np.int32)[0]), finalize=float(fin[b]),
-                 beam=[(beam_y[b, k, :beam_len[b, k]].tolist(), float(beam_score[b, k]), int(beam_state[b, k]), int(beam_lm[b, k]))
-                       for k in range(beam_n[b])],
-                 hits=lmc[b, :9].tolist(), backoffs=int(lmc[b, 9]), unk=int(lmc[b, 10]), full_order_pops=int(lmc[b, 11]),
-                 recombinations=int(lmc[b, 12]), lm_mismatches=int(lmc[b, 13]))
-        d.update({name: int(counters[b, i]) for i, name in enumerate(AR.COUNTERS) if name != "recombinations"})
-        out.append(d)
-    return out
-
-
 def totals(rows, order):
     """the LM counters of a batch, summed: {hits: [level 1..order], backoffs, unk, full_order_pops, recombinations}"""
     return dict(hits=[sum(r["hits"][k] for r in rows) for k in range(1, order + 1)], backoffs=sum(r["backoffs"] for r in rows),
@@ -258,7 +164,7 @@ def lm_float64(cfg, sd, f, t_len, graph=None, arpa=None, alpha=0.0, bos=False, b
 
 # ---- fixtures --------------------------------------------------------------------------------------------------------------------
 def toy_lm(plain, cfg, skip=5):
-    """an order-3 model cut from the PLAIN search's results `plain` (AR.hw_checker at beam 4), so that the search meets it at every
+    """an order-3 model cut from the PLAIN search's results `plain` (AR.alsd_checker at beam 4), so that the search meets it at every
     level; every log10 value is a multiple of 1/8.  Unigrams for every token but those with id % skip == skip - 1 (a candidate
     without one is an unknown word); `<s>` and the bigram `<s>` + each winner's first label; the bigrams and trigrams of the
     winners' labels and of the best beam entry that differs, prefix-closed as a file is
@@ -269,7 +175,7 @@ def toy_lm(plain, cfg, skip=5):
     seqs = []
     for r in plain:
         seqs.append(r["ids"])
-        seqs += [y for y, _, _ in r["beam"] if y != r["ids"]][:1]
+        seqs += [y for y, *_ in r["beam"] if y != r["ids"]][:1]
     for y in seqs:
         y = [t for t in y]
         if y and (y[0],) in ent:

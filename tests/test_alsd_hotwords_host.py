@@ -1,7 +1,7 @@
 """CPU: hotwords (contextual biasing) of the NeMo family's ALSD beam search (rs_rnnt_alsd_hotwords, csrc/k_rnnt_alsd.hip; the
 semantics are stated in include/rs_asr.h).  What needs no GPU:
 
-  * the C checker (tests/alsd_hotwords_checker.c) with an empty table, or with graph_of all -1, IS oracle/rnnt_alsd.c, bit for bit
+  * the C checker (tests/alsd_checker.c) with an empty table, or with graph_of all -1, IS oracle/rnnt_alsd.c, bit for bit
   * the checker against a float64 Python restatement of the same rules on the toy geometry (the tolerance of
     tests/test_oracle_alsd.py for the plain pair)
   * hand-built cases on a five-entry vocabulary with injected logits: a boosted continuation overtakes in the ranking, an
@@ -36,7 +36,7 @@ def toy():
     sd = synthetic_state_dict(TINY, 0)
     f, lens = AR.toy_batch(TINY, seed=TOY_SEED)
     f, lens = f.numpy(), lens.numpy()
-    plain = AR.hw_checker(TINY, sd, f, lens, beam=4)
+    plain = AR.alsd_checker(TINY, sd, f, lens, beam=4)
     graphs = AR.toy_graphs(plain)
     return sd, f, lens, graphs, AR.table_of(graphs)
 
@@ -49,8 +49,8 @@ def test_checker_without_graph_is_the_plain_oracle(toy, beam, max_target_len, no
     assert lens[2] == 0 and lens.max() == f.shape[1]
     ref = og.rnnt_alsd(TINY, sd, f, lens, beam=beam, max_target_len=max_target_len, score_norm=norm, recombine="merge" if merge else "upstream")
     kw = dict(beam=beam, max_target_len=max_target_len, score_norm=norm, merge=merge)
-    for got in (AR.hw_checker(TINY, sd, f, lens, **kw),                                           # an empty table
-                AR.hw_checker(TINY, sd, f, lens, table, [-1] * len(lens), **kw)):                 # a table nobody points at
+    for got in (AR.alsd_checker(TINY, sd, f, lens, **kw),                                           # an empty table
+                AR.alsd_checker(TINY, sd, f, lens, table, [-1] * len(lens), **kw)):                 # a table nobody points at
         for b, (g, r) in enumerate(zip(got, ref)):
             assert g["ids"] == r[0] and g["steps"] == r[1], b
             assert AR.same_bits(g["score"], r[2]), (b, g["score"], r[2])
@@ -66,8 +66,8 @@ def test_checker_matches_float64_restatement(toy, beam, mode, norm):
     import torch
     sd, f, lens, graphs, table = toy
     rows, graph_of = [0, 1, 3, 6], [0, 1, 2, 0]
-    got = AR.hw_checker(TINY, sd, f[rows], lens[rows], table, graph_of, beam=beam, max_target_len=1.0, score_norm=norm, merge=mode == "merge")
-    plain = AR.hw_checker(TINY, sd, f[rows], lens[rows], beam=beam, max_target_len=1.0, score_norm=norm, merge=mode == "merge")
+    got = AR.alsd_checker(TINY, sd, f[rows], lens[rows], table, graph_of, beam=beam, max_target_len=1.0, score_norm=norm, merge=mode == "merge")
+    plain = AR.alsd_checker(TINY, sd, f[rows], lens[rows], beam=beam, max_target_len=1.0, score_norm=norm, merge=mode == "merge")
     n_tok = 0
     for k, b in enumerate(rows):
         graph = KR.ContextGraph(graphs[graph_of[k]])
@@ -98,7 +98,7 @@ def lsm(row):
 
 def run(z, T, phrases, beam, budget, norm=False, merge=False):
     table = AR.table_of([phrases]) if phrases else None
-    return AR.hw_checker(None, None, None, [T], table, [0] if phrases else None, beam=beam, max_target_len=int(budget), score_norm=norm,
+    return AR.alsd_checker(None, None, None, [T], table, [0] if phrases else None, beam=beam, max_target_len=int(budget), score_norm=norm,
                          merge=merge, inject=z, dims=(V, BLANK))[0]
 
 
@@ -174,8 +174,8 @@ def test_toy_fixture_exercises_the_graph(toy, beam, max_target_len, norm, merge)
     sd, f, lens, graphs, table = toy
     assert all(s * 2 == int(s * 2) for g in graphs for _, s in g)
     kw = dict(beam=beam, max_target_len=max_target_len, score_norm=norm, merge=merge)
-    hot = AR.hw_checker(TINY, sd, f, lens, table, AR.TOY_GRAPH_OF, **kw)
-    plain = AR.hw_checker(TINY, sd, f, lens, **kw)
+    hot = AR.alsd_checker(TINY, sd, f, lens, table, AR.TOY_GRAPH_OF, **kw)
+    plain = AR.alsd_checker(TINY, sd, f, lens, **kw)
     total = {k: sum(h[k] for h in hot) for k in AR.COUNTERS}
     assert all(total[k] > 0 for k in AR.COUNTERS[:4]) and total["state_mismatches"] == 0, f"re-choose the inputs: {total}"
     for b, g in enumerate(AR.TOY_GRAPH_OF):

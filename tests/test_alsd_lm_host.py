@@ -1,8 +1,8 @@
 """CPU: n-gram LM shallow fusion in the NeMo family's ALSD beam search (rs_rnnt_alsd_lm, csrc/k_rnnt_alsd.hip; the rule is stated in
 include/rs_asr.h).  What needs no GPU:
 
-  * the C checker (tests/alsd_lm_checker.c) with no LM, or with alpha 0, IS tests/alsd_hotwords_checker.c, bit for bit, with and
-    without graphs
+  * the C checker (tests/alsd_checker.c) with no LM, or with alpha 0, returns what tests/alsd_hotwords_checker.c returned before
+    this file absorbed it (tests/golden/alsd_hotwords_checker_pins.json), bit for bit, with and without graphs
   * the checker against a float64 Python restatement of the same rules on the toy geometry (labels, steps; scores with the tolerance
     tests/test_alsd_hotwords_host.py holds for its pair)
   * hand-built cases on a five-entry vocabulary with injected logits: an LM term overtakes inside a hypothesis's top `beam` (and
@@ -11,6 +11,7 @@ include/rs_asr.h).  What needs no GPU:
   * the keywords of the nemo package, the export list and the family rows"""
 import ctypes
 import inspect
+import json
 import math
 import os
 import re
@@ -40,26 +41,35 @@ def toy():
     sd = synthetic_state_dict(TINY, 0)
     f, lens = AR.toy_batch(TINY, seed=TOY_SEED)
     f, lens = f.numpy(), lens.numpy()
-    plain = AR.hw_checker(TINY, sd, f, lens, beam=4)
+    plain = AR.alsd_checker(TINY, sd, f, lens, beam=4)
     graphs = AR.toy_graphs(plain)
     ent = NR.toy_lm(plain, TINY)
     return sd, f, lens, graphs, AR.table_of(graphs), ent, NL.build(ent, TINY.vocab_size, TINY.blank_id)
 
 
 # ---- without an LM the checker is the hotword checker ----------------------------------------------------------------------------------
+with open(os.path.join(ROOT, "tests", "golden", "alsd_hotwords_checker_pins.json")) as _fh:
+    PINS = {(c["beam"], c["max_target_len"], c["score_norm"], c["merge"], c["graphs"]): c["rows"] for c in json.load(_fh)["cases"]}
+
+
 @pytest.mark.parametrize("beam,max_target_len,norm,merge", [(1, 1.0, False, False), (2, 1.0, True, True), (4, 2.0, True, False),
                                                             (4, 7, False, True), (8, 0.5, True, False)])
 def test_checker_without_lm_is_the_hotword_checker(toy, beam, max_target_len, norm, merge):
+    """the hotword checker is the one deleted from the tree: its results on these inputs are the pins (floats as bit patterns)"""
     sd, f, lens, _, table, _, lm = toy
     kw = dict(beam=beam, max_target_len=max_target_len, score_norm=norm, merge=merge)
     for tab, gof in ((None, None), (table, AR.TOY_GRAPH_OF)):
-        ref = AR.hw_checker(TINY, sd, f, lens, tab, gof, **kw)
-        for got in (NR.lm_checker(TINY, sd, f, lens, None, 0.7, tab, gof, **kw),              # no model
-                    NR.lm_checker(TINY, sd, f, lens, lm, 0.0, tab, gof, **kw)):               # alpha 0
+        ref = PINS[(beam, max_target_len, norm, merge, tab is not None)]
+        runs = [AR.alsd_checker(TINY, sd, f, lens, tab, gof, None, 0.7, **kw),                    # no model
+                AR.alsd_checker(TINY, sd, f, lens, tab, gof, lm, 0.0, **kw)]                      # alpha 0
+        if tab is None:
+            runs.append(AR.alsd_checker(TINY, sd, f, lens, **kw))                                 # no graph or LM argument at all
+        for got in runs:
+            assert len(got) == len(ref)
             for b, (g, r) in enumerate(zip(got, ref)):
-                assert g["ids"] == r["ids"] and g["steps"] == r["steps"] and g["score_bits"] == r["score_bits"], (b, g["score"], r["score"])
-                assert g["finalize"] == r["finalize"] and [e[:3] for e in g["beam"]] == r["beam"]
-                assert all(g[k] == r[k] for k in AR.COUNTERS if k != "recombinations") and g["recombinations"] == r["recombinations"]
+                assert g["ids"] == r["ids"] and g["steps"] == r["steps"] and g["score_bits"] == r["score_bits"], (b, g["score"])
+                assert AR.bits(g["finalize"]) == r["finalize_bits"] and [[y, AR.bits(sc), st] for y, sc, st, _ in g["beam"]] == r["beam"]
+                assert all(g[k] == r[k] for k in AR.COUNTERS)
                 assert sum(g["hits"]) == g["backoffs"] == g["unk"] == g["full_order_pops"] == 0
         assert sum(len(r["ids"]) for r in ref) > 20
 
@@ -74,8 +84,8 @@ def test_checker_matches_float64_restatement(toy, beam, mode, norm, hot):
     sd, f, lens, graphs, table, ent, lm = toy
     rows, graph_of = [0, 1, 3, 6], [0, 1, 2, 0]
     kw = dict(beam=beam, max_target_len=1.0, score_norm=norm, merge=mode == "merge")
-    got = NR.lm_checker(TINY, sd, f[rows], lens[rows], lm, TOY_ALPHA, table if hot else None, graph_of if hot else None, **kw)
-    plain = AR.hw_checker(TINY, sd, f[rows], lens[rows], table if hot else None, graph_of if hot else None, **kw)
+    got = AR.alsd_checker(TINY, sd, f[rows], lens[rows], table if hot else None, graph_of if hot else None, lm, TOY_ALPHA, **kw)
+    plain = AR.alsd_checker(TINY, sd, f[rows], lens[rows], table if hot else None, graph_of if hot else None, **kw)
     arpa = NR.ArpaDict(ent, 3, min(p for k, (p, _) in ent.items() if len(k) == 1 and k != (BOS,)))
     n_tok = 0
     for k, b in enumerate(rows):
@@ -112,8 +122,8 @@ def model(ent, unk=None):
 
 def run(z, T, lm, alpha, beam, budget, phrases=None, norm=False, merge=False):
     table = AR.table_of([phrases]) if phrases else None
-    return NR.lm_checker(None, None, None, [T], lm, alpha, table, [0] if phrases else None, beam=beam, max_target_len=int(budget),
-                         score_norm=norm, merge=merge, inject=z, dims=(V, BLANK))[0]
+    return AR.alsd_checker(None, None, None, [T], table, [0] if phrases else None, lm, alpha, beam=beam, max_target_len=int(budget),
+                           score_norm=norm, merge=merge, inject=z, dims=(V, BLANK))[0]
 
 
 def test_an_lm_term_overtakes_inside_the_top_beam_and_only_there():
@@ -218,9 +228,9 @@ def test_toy_fixture_exercises_the_model(toy, beam, max_target_len, norm, merge)
     assert lm.order == 3 and lm.start != 0 and any(lm.arrays["root_child"][:TINY.vocab_size] < 0)
     capi.ngram_check(lm.arrays, lm.start, lm.order, lm.unk_logp)
     kw = dict(beam=beam, max_target_len=max_target_len, score_norm=norm, merge=merge)
-    plain = AR.hw_checker(TINY, sd, f, lens, **kw)
+    plain = AR.alsd_checker(TINY, sd, f, lens, **kw)
     for tab, gof in ((None, None), (table, AR.TOY_GRAPH_OF)):
-        got = NR.lm_checker(TINY, sd, f, lens, lm, TOY_ALPHA, tab, gof, **kw)
+        got = AR.alsd_checker(TINY, sd, f, lens, tab, gof, lm, TOY_ALPHA, **kw)
         t = NR.totals(got, lm.order)
         if beam == 1:                                          # one hypothesis per utterance: nothing to recombine with
             t["recombinations"] = 1

@@ -1,5 +1,5 @@
 """-m gpu: hotwords in the ALSD beam search on the device (rs_rnnt_alsd_hotwords, csrc/k_rnnt_alsd.hip) against its C checker
-(tests/alsd_hotwords_checker.c, itself held to oracle/rnnt_alsd.c and a float64 restatement in tests/test_alsd_hotwords_host.py):
+(tests/alsd_checker.c, itself held to oracle/rnnt_alsd.c and a float64 restatement in tests/test_alsd_hotwords_host.py):
 labels, alignment steps and score BITS.
 
   toy geometry      7 ragged rows (one without frames, one of full length), three graphs plus "none" spread over them; beams
@@ -48,11 +48,11 @@ def device_search(model, f, lens, beam, hw=None, graph_of=None, max_target_len=2
         model.ctx.rnnt_alsd(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, ws, stream)
     else:
         gof = None if graph_of is None else torch.as_tensor(np.asarray(graph_of), dtype=torch.int32).to(dev)
-        n = model.ctx.alsd_hotwords_workspace_bytes(B, beam, Tp, max_target_len)
+        n = model.ctx.alsd_workspace_bytes(B, beam, Tp, max_target_len, hotwords=True)
         assert n >= model.ctx.alsd_workspace_bytes(B, beam, Tp, max_target_len) + 2 * 4 * B * min(beam, model.cfg.n_logits - 1)
         ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-        model.ctx.rnnt_alsd_hotwords(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores,
-                                     hw.struct if hw is not None else None, gof, ws, stream)
+        model.ctx.rnnt_alsd(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, ws, stream,
+                            hotwords=hw.struct if hw is not None else None, graph_of=gof)
     torch.cuda.synchronize()
     n = n_ids.cpu().numpy()
     bits = scores.cpu().numpy().view(np.int32)
@@ -63,7 +63,7 @@ def check(model, sd, f, lens, graphs, graph_of, **kw):
     """device == checker, bits; -> (device rows, checker rows)"""
     hw = _HotwordSet(graphs, model.device)
     got = device_search(model, f, lens, hw=hw, graph_of=graph_of, **kw)
-    want = AR.hw_checker(model.cfg, sd, np.asarray(f), np.asarray(lens, np.int32), kh.concat(graphs), graph_of, **kw)
+    want = AR.alsd_checker(model.cfg, sd, np.asarray(f), np.asarray(lens, np.int32), kh.concat(graphs), graph_of, **kw)
     for b, (g, w) in enumerate(zip(got, want)):
         assert g[0] == w["ids"] and g[1] == w["steps"], (kw, b, g[:2], w["ids"], w["steps"])
         assert g[2] == w["score_bits"], (kw, b, g[2], w["score_bits"], w["score"])
@@ -83,7 +83,7 @@ def toy(tiny):
     f, lens = AR.toy_batch(TINY, seed=TOY_SEED)
     f, lens = f.numpy(), lens.numpy()
     assert len(lens) == 7 and f.shape[1] == 21 and lens[2] == 0 and lens[5] == 21
-    graphs = [kh.build_graph(p) for p in AR.toy_graphs(AR.hw_checker(TINY, sd, f, lens, beam=4))]
+    graphs = [kh.build_graph(p) for p in AR.toy_graphs(AR.alsd_checker(TINY, sd, f, lens, beam=4))]
     return f, lens, graphs
 
 
@@ -117,8 +117,8 @@ def test_bit_exact_at_619m_geometry(gpu_device):
     f = (torch.randn((B, Tp, cfg.joint_hidden), generator=g) * (0.8 + 0.4 * torch.rand((B, 1, 1), generator=g))).numpy()
     lens = torch.randint(3, Tp + 1, (B,), generator=g, dtype=torch.int32).numpy()
     lens[2] = Tp
-    plain = AR.hw_checker(cfg, sd, f[2:3], lens[2:3], beam=4, max_target_len=1.0)      # labels the search proposes: one row is enough
-    seen = sorted({t for r in plain for y, _, _ in r["beam"] + [(r["ids"], 0, 0)] for t in y})
+    plain = AR.alsd_checker(cfg, sd, f[2:3], lens[2:3], beam=4, max_target_len=1.0)      # labels the search proposes: one row is enough
+    seen = sorted({t for r in plain for y, *_ in r["beam"] + [(r["ids"], 0, 0)] for t in y})
     assert len(seen) >= 2
     rng = np.random.default_rng(4)
     firsts = np.unique(np.concatenate([rng.choice(cfg.vocab_size, size=400 - len(seen), replace=False), seen]))
@@ -146,9 +146,9 @@ def test_bit_exact_wide_vocabulary_form(gpu_device):
     B, Tp = 3, 8
     f = (torch.randn((B, Tp, cfg.joint_hidden), generator=g) * 0.9).numpy()
     lens = np.asarray([8, 5, 7], np.int32)
-    plain = AR.hw_checker(cfg, sd, f, lens, beam=2, max_target_len=1.0)
+    plain = AR.alsd_checker(cfg, sd, f, lens, beam=2, max_target_len=1.0)
     phrases = [(tuple(r["ids"][:2]), 2.0) for r in plain if len(r["ids"]) >= 2]
-    phrases += [(tuple(y[-2:]) + (7,), 1.5) for r in plain for y, _, _ in r["beam"] if len(y) >= 2]
+    phrases += [(tuple(y[-2:]) + (7,), 1.5) for r in plain for y, *_ in r["beam"] if len(y) >= 2]
     assert phrases, "the fixture must emit labels"
     got, want = check(model, sd, f, lens, [kh.build_graph(phrases)], [0, -1, 0], beam=2, max_target_len=1.0)
     print("wide vocabulary:", {k: sum(w[k] for w in want) for k in AR.COUNTERS})
@@ -209,7 +209,7 @@ def test_through_the_nemo_package(gpu_device):
     torch.cuda.synchronize()
     got = model.collect(buf)
     model.token_scores = False
-    want = AR.hw_checker(TINY, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), kh.concat([model.hotwords]), [0] * 9,
+    want = AR.alsd_checker(TINY, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), kh.concat([model.hotwords]), [0] * 9,
                          beam=4, max_target_len=TINY.alsd_max_target_len)
     assert got.ids == [w["ids"] for w in want] and got.frames == [[i - u for u, i in enumerate(w["steps"])] for w in want]
     assert [np.float32(s) for s in got.scores] == [np.float32(w["score"]) for w in want]
@@ -262,10 +262,10 @@ def test_errors(tiny, toy):
     k2 = capi.Context(ZIPFORMER_TINY, 0)
     try:
         with pytest.raises(RuntimeError):
-            k2.alsd_hotwords_workspace_bytes(2, 4, 10, 1.0)
+            k2.alsd_workspace_bytes(2, 4, 10, 1.0, hotwords=True)
         with pytest.raises(capi.RsError, match="not defined for a Zipformer context") as e:
-            k2.rnnt_alsd_hotwords(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 1.0, True, False, z(2, 20), z(2, 20),
-                                  z(2), torch.zeros((2,), device=dev), hw.struct, z(2), torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0)
+            k2.rnnt_alsd(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 1.0, True, False, z(2, 20), z(2, 20),
+                         z(2), torch.zeros((2,), device=dev), torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0, hotwords=hw.struct, graph_of=z(2))
         assert e.value.code == capi.RS_EINVAL
     finally:
         k2.close()

@@ -1,5 +1,5 @@
 """-m gpu: n-gram LM shallow fusion in the ALSD beam search on the device (rs_rnnt_alsd_lm, csrc/k_rnnt_alsd.hip, k_rnnt_ngram.h)
-against its C checker (tests/alsd_lm_checker.c, itself held to tests/alsd_hotwords_checker.c and a float64 restatement in
+against its C checker (tests/alsd_checker.c, itself held to its predecessor's recorded results and a float64 restatement in
 tests/test_alsd_lm_host.py): labels, alignment steps and score BITS.
 
   toy geometry      7 ragged rows (one without frames, one of full length); beams 1 / 2 / 4 / 8, and once each: merge on, score
@@ -56,14 +56,14 @@ def device_search(model, f, lens, beam, lm=None, alpha=0.0, hw=None, graph_of=No
         ws = torch.empty((model.ctx.alsd_workspace_bytes(B, beam, Tp, max_target_len),), dtype=torch.uint8, device=dev)
         model.ctx.rnnt_alsd(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, ws, stream)
     elif entry == "hotwords":
-        ws = torch.empty((model.ctx.alsd_hotwords_workspace_bytes(B, beam, Tp, max_target_len),), dtype=torch.uint8, device=dev)
-        model.ctx.rnnt_alsd_hotwords(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, hws, gof, ws, stream)
+        ws = torch.empty((model.ctx.alsd_workspace_bytes(B, beam, Tp, max_target_len, hotwords=True),), dtype=torch.uint8, device=dev)
+        model.ctx.rnnt_alsd(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, ws, stream, hotwords=hws, graph_of=gof)
     else:
-        n = model.ctx.alsd_lm_workspace_bytes(B, beam, Tp, max_target_len)
-        assert n >= model.ctx.alsd_hotwords_workspace_bytes(B, beam, Tp, max_target_len) + 2 * 4 * B * min(beam, model.cfg.n_logits - 1)
+        n = model.ctx.alsd_workspace_bytes(B, beam, Tp, max_target_len, hotwords=True, lm=True)
+        assert n >= model.ctx.alsd_workspace_bytes(B, beam, Tp, max_target_len, hotwords=True) + 2 * 4 * B * min(beam, model.cfg.n_logits - 1)
         ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-        model.ctx.rnnt_alsd_lm(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, hws, gof,
-                               lm.struct if lm is not None else None, alpha, ws, stream)
+        model.ctx.rnnt_alsd(f, lens, B, Tp, beam, max_target_len, score_norm, merge, ids, steps, n_ids, scores, ws, stream, hotwords=hws,
+                            graph_of=gof, lm=lm.struct if lm is not None else None, lm_alpha=alpha)
     torch.cuda.synchronize()
     n = n_ids.cpu().numpy()
     bits = scores.cpu().numpy().view(np.int32)
@@ -74,8 +74,8 @@ def check(model, sd, f, lens, lm, alpha, graphs=None, graph_of=None, **kw):
     """device == checker, bits; -> (device rows, checker rows)"""
     hw = _HotwordSet(graphs, model.device) if graphs else None
     got = device_search(model, f, lens, lm=_NgramSet(lm, model.device), alpha=alpha, hw=hw, graph_of=graph_of if graphs else None, **kw)
-    want = NR.lm_checker(model.cfg, sd, np.asarray(f), np.asarray(lens, np.int32), lm, alpha, kh.concat(graphs) if graphs else None,
-                         graph_of if graphs else None, **kw)
+    want = AR.alsd_checker(model.cfg, sd, np.asarray(f), np.asarray(lens, np.int32), kh.concat(graphs) if graphs else None,
+                           graph_of if graphs else None, lm, alpha, **kw)
     for b, (g, w) in enumerate(zip(got, want)):
         assert g[0] == w["ids"] and g[1] == w["steps"], (kw, b, g[:2], w["ids"], w["steps"])
         assert g[2] == w["score_bits"], (kw, b, g[2], w["score_bits"], w["score"])
@@ -95,7 +95,7 @@ def toy(tiny):
     f, lens = AR.toy_batch(TINY, seed=TOY_SEED)
     f, lens = f.numpy(), lens.numpy()
     assert len(lens) == 7 and f.shape[1] == 21 and lens[2] == 0 and lens[5] == 21
-    plain = AR.hw_checker(TINY, sd, f, lens, beam=4)
+    plain = AR.alsd_checker(TINY, sd, f, lens, beam=4)
     graphs = [kh.build_graph(p) for p in AR.toy_graphs(plain)]
     return f, lens, graphs, NL.build(NR.toy_lm(plain, TINY), TINY.vocab_size, TINY.blank_id)
 
@@ -133,8 +133,8 @@ def test_bit_exact_at_619m_geometry(gpu_device):
     f = (torch.randn((B, Tp, cfg.joint_hidden), generator=g) * (0.8 + 0.4 * torch.rand((B, 1, 1), generator=g))).numpy()
     lens = torch.randint(3, Tp + 1, (B,), generator=g, dtype=torch.int32).numpy()
     lens[2] = Tp
-    plain = AR.hw_checker(cfg, sd, f, lens, beam=4, max_target_len=1.0)                # the label sequences the search proposes
-    seqs = [y for r in plain for y, _, _ in r["beam"] + [(r["ids"], 0, 0)] if y]
+    plain = AR.alsd_checker(cfg, sd, f, lens, beam=4, max_target_len=1.0)                # the label sequences the search proposes
+    seqs = [y for r in plain for y, *_ in r["beam"] + [(r["ids"], 0, 0)] if y]
     seen = sorted({t for y in seqs for t in y})
     assert len(seen) >= 2
     lm = NL.build(NR.random_lm(cfg, seqs, n_high=3000, order=4), cfg.vocab_size, cfg.blank_id)
@@ -160,8 +160,8 @@ def test_bit_exact_wide_vocabulary_form(gpu_device):
     B, Tp = 3, 8
     f = (torch.randn((B, Tp, cfg.joint_hidden), generator=g) * 0.9).numpy()
     lens = np.asarray([8, 5, 7], np.int32)
-    plain = AR.hw_checker(cfg, sd, f, lens, beam=2, max_target_len=1.0)
-    seqs = [y for r in plain for y, _, _ in r["beam"] + [(r["ids"], 0, 0)] if y]
+    plain = AR.alsd_checker(cfg, sd, f, lens, beam=2, max_target_len=1.0)
+    seqs = [y for r in plain for y, *_ in r["beam"] + [(r["ids"], 0, 0)] if y]
     assert seqs, "the fixture must emit labels"
     lm = NL.build(NR.random_lm(cfg, seqs, n_high=500, order=3, seed=9), cfg.vocab_size, cfg.blank_id)
     got, want = check(model, sd, f, lens, lm, 0.6, beam=2, max_target_len=1.0)
@@ -242,8 +242,8 @@ def test_through_the_nemo_package(gpu_device, tmp_path):
     torch.cuda.synchronize()
     got = model.collect(buf)
     model.token_scores = False
-    want = NR.lm_checker(TINY, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), model.ngram_lm, 0.6,
-                         beam=4, max_target_len=TINY.alsd_max_target_len)
+    want = AR.alsd_checker(TINY, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), lm=model.ngram_lm, alpha=0.6,
+                           beam=4, max_target_len=TINY.alsd_max_target_len)
     assert got.ids == [w["ids"] for w in want] and got.frames == [[i - u for u, i in enumerate(w["steps"])] for w in want]
     assert [np.float32(s) for s in got.scores] == [np.float32(w["score"]) for w in want]
     assert [model.tokenizer.ids_to_text(ids) for ids in got.ids] == text(res) and got.ids != dec.ids
@@ -267,10 +267,10 @@ def test_errors(tiny, toy):
     k2 = capi.Context(ZIPFORMER_TINY, 0)
     try:
         with pytest.raises(RuntimeError):
-            k2.alsd_lm_workspace_bytes(2, 4, 10, 1.0)
+            k2.alsd_workspace_bytes(2, 4, 10, 1.0, lm=True)
         with pytest.raises(capi.RsError, match="not defined for a Zipformer context") as e:
-            k2.rnnt_alsd_lm(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 1.0, True, False, z(2, 20), z(2, 20),
-                            z(2), torch.zeros((2,), device=dev), None, None, ns.struct, 0.5, torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0)
+            k2.rnnt_alsd(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 1.0, True, False, z(2, 20), z(2, 20),
+                         z(2), torch.zeros((2,), device=dev), torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0, lm=ns.struct, lm_alpha=0.5)
         assert e.value.code == capi.RS_EINVAL
     finally:
         k2.close()

@@ -1,5 +1,5 @@
 """-m gpu: hotwords in the modified beam search on the device (rs_rnnt_mbs_hotwords, csrc/k_rnnt_mbs.hip) against its C checker
-(tests/k2_hotwords_checker.c): ids, frames and the float32 score of every utterance BIT FOR BIT, given the device's own
+(tests/k2_mbs_checker.c): ids, frames and the float32 score of every utterance BIT FOR BIT, given the device's own
 joiner.encoder_proj output.
 
   toy geometry (V = 97)      K = 1, 2, 4, 8; 7 ragged utterances with a zero-frame row; three graphs + "none" spread over the rows
@@ -67,9 +67,9 @@ def device_search(am, f, lens, K, hw=None, graph_of=None, blank_penalty=0.0, len
         am.ctx.rnnt_mbs(f, lens, B, Tp, K, blank_penalty, length_norm, ids, frames, n_ids, scores, ws, stream)
     else:
         gof = None if graph_of is None else torch.as_tensor(np.asarray(graph_of), dtype=torch.int32).to(dev)
-        ws = torch.empty((am.ctx.mbs_hotwords_workspace_bytes(B, K, Tp, out_cap),), dtype=torch.uint8, device=dev)
-        am.ctx.rnnt_mbs_hotwords(f, lens, B, Tp, K, blank_penalty, length_norm, ids, frames, n_ids, scores,
-                                 hw.struct if hw is not None else None, gof, ws, stream)
+        ws = torch.empty((am.ctx.mbs_workspace_bytes(B, K, Tp, out_cap, hotwords=True),), dtype=torch.uint8, device=dev)
+        am.ctx.rnnt_mbs(f, lens, B, Tp, K, blank_penalty, length_norm, ids, frames, n_ids, scores, ws, stream,
+                        hotwords=hw.struct if hw is not None else None, graph_of=gof)
     torch.cuda.synchronize()
     n = n_ids.cpu().numpy()
     bits = scores.cpu().numpy().view(np.int32)
@@ -80,7 +80,7 @@ def check(cfg, sd, am, f, lens, graphs, graph_of, **kw):
     """device == checker, bits; -> (device rows, checker rows)"""
     hw = _HotwordSet(graphs, am.device)
     got = device_search(am, f, lens, hw=hw, graph_of=graph_of, **kw)
-    want = H.hw_checker(cfg, sd, f.cpu().numpy(), np.asarray(lens, np.int32), kh.concat(graphs), graph_of, **kw)
+    want = R.mbs_checker(cfg, sd, f.cpu().numpy(), np.asarray(lens, np.int32), kh.concat(graphs), graph_of, **kw)
     for b, (g, w) in enumerate(zip(got, want)):
         assert g[0] == w["ids"] and g[1] == w["frames"], (kw, b, g[:2], w["ids"], w["frames"])
         assert g[2] == w["score_bits"], (kw, b, g[2], w["score_bits"], w["score"])
@@ -211,7 +211,7 @@ def test_through_k2model_and_the_transcribe_functions(tiny, toy):
     am.run_device(buf)
     torch.cuda.synchronize()
     got = am.collect(buf)
-    want = H.hw_checker(cfg, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), kh.concat([model.hotwords]), [0] * 9, K=4)
+    want = R.mbs_checker(cfg, sd, buf.joint_enc.cpu().numpy(), np.asarray(got.enc_lens, np.int32), kh.concat([model.hotwords]), [0] * 9, K=4)
     assert got.ids == [w["ids"] for w in want] and got.frames == [w["frames"] for w in want]
     assert [np.float32(s) for s in got.scores] == [np.float32(w["score"]) for w in want]
     assert ["".join(model.symbol(i) for i in ids) for ids in got.ids] == text(res)
@@ -241,13 +241,13 @@ def test_errors(tiny, toy):
     sd = synthetic_state_dict(TINY, 0)
     nemo = AsrModel(TINY, sd, SyntheticTokenizer(TINY.vocab_size), device="cuda:0")
     with pytest.raises(RuntimeError):
-        nemo.ctx.mbs_hotwords_workspace_bytes(2, 4, 10, 10)
+        nemo.ctx.mbs_workspace_bytes(2, 4, 10, 10, hotwords=True)
     dev = nemo.device
     z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)          # noqa: E731
     hw = _HotwordSet(graphs, dev)
     with pytest.raises(capi.RsError, match="Zipformer") as e:
-        nemo.ctx.rnnt_mbs_hotwords(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 0.0, True, z(2, 10), z(2, 10),
-                                   z(2), torch.zeros((2,), device=dev), hw.struct, z(2), torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0)
+        nemo.ctx.rnnt_mbs(torch.zeros((2, 10, TINY.joint_hidden), device=dev), z(2) + 10, 2, 10, 4, 0.0, True, z(2, 10), z(2, 10),
+                          z(2), torch.zeros((2,), device=dev), torch.empty((1 << 20,), dtype=torch.uint8, device=dev), 0, hotwords=hw.struct, graph_of=z(2))
     assert e.value.code == capi.RS_EINVAL
     # a table that fails the check never reaches the device: _HotwordSet raises before it uploads anything
     bad = kh.build_graph([((5, 6, 7), 2.0), ((6, 7), 1.5)])

@@ -1,14 +1,16 @@
 """CPU: hotwords (contextual biasing) of the Zipformer family's modified beam search (rs_rnnt_mbs_hotwords, csrc/k_rnnt_mbs.hip;
 runtime/k2_hotwords.py) — the graph against upstream's own unit-test tables, the product's flat builder against an independent
-pointer restatement, rs_hotwords_check, the C checker with hotwords (tests/k2_hotwords_checker.c) against the plain checker and
-against a float64 restatement, hand-built cases for every context rule of the search, and parsing / argument checking.
+pointer restatement, rs_hotwords_check, the C checker (tests/k2_mbs_checker.c) without graphs against what the plain checker returned
+before the hotword one absorbed it (tests/golden/k2_mbs_checker_pins.json) and with graphs against a float64 restatement, hand-built cases for every context rule of the search, and parsing / argument checking.
 
 The agreement rule of the checker test is the one of tests/test_k2_mbs_host.py (LINE = 2e-4 on the gaps the float64 run reports;
 a row below it may differ from the first such frame on).  The bonuses do not move it: with scores that are multiples of 0.5 every
 graph quantity is exact in float32 and float64 alike, so the two searches still part only at near-ties of the log-softmax values.
 At most 1 row in 8 may use the excuse (there: 3 of 24)."""
 import ctypes
+import json
 import math
+import os
 import types
 import warnings
 
@@ -163,14 +165,40 @@ def bits(rows):
     return [(r["ids"], r["frames"], r["score_bits"]) for r in rows]
 
 
+# The plain checker is the one the hotword checker replaced: its results on the toy batch (floats as bit patterns), by keywords.
+# The checker is deterministic, its input here is not: the toy batch is the float32 oracle's encoder projection, and torch's CPU
+# kernels differ by a few ulp from one machine to another (seen: the same tokens and frames, scores 2 - 8 ulp apart).  So tokens,
+# frames and merge counts are held exactly and scores within LINE / 2, the tolerance of the float64 test below.
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "k2_mbs_checker_pins.json")) as _fh:
+    PINS = {tuple(sorted(c["kw"].items())): c["rows"] for c in json.load(_fh)["cases"]}
+
+
+def pinned(**kw):
+    return PINS[tuple(sorted(kw.items()))]
+
+
+def f32(pattern):
+    return float(np.asarray([pattern], np.int32).view(np.float32)[0])
+
+
+def assert_equals_pins(rows, want):
+    assert len(rows) == len(want)
+    for b, (r, w) in enumerate(zip(rows, want)):
+        assert (r["ids"], r["frames"], r["merges"]) == (w["ids"], w["frames"], w["merges"]), b
+        assert abs(r["score"] - f32(w["score_bits"])) < LINE / 2, (b, r["score"], f32(w["score_bits"]))
+        assert [y for y, _ in r["final"]] == [y for y, _ in w["final"]], b
+        assert all(abs(lp - f32(p)) < LINE / 2 for (_, lp), (_, p) in zip(r["final"], w["final"])), b
+
+
 @pytest.mark.parametrize("K", [1, 2, 4, 8])
 def test_checker_without_a_graph_is_the_plain_checker(toy, K):
-    want = R.mbs_checker(toy.cfg, toy.sd, toy.f, toy.el, K=K)
-    assert bits(H.hw_checker(toy.cfg, toy.sd, toy.f, toy.el, None, None, K=K)) == bits(want)
-    got = H.hw_checker(toy.cfg, toy.sd, toy.f, toy.el, toy.table, [-1] * 6, K=K)       # graphs in the call, none used
+    want = R.mbs_checker(toy.cfg, toy.sd, toy.f, toy.el, K=K)                          # no graph argument at all
+    assert_equals_pins(want, pinned(K=K))
+    assert bits(R.mbs_checker(toy.cfg, toy.sd, toy.f, toy.el, None, None, K=K)) == bits(want)
+    got = R.mbs_checker(toy.cfg, toy.sd, toy.f, toy.el, toy.table, [-1] * 6, K=K)      # graphs in the call, none used
     assert bits(got) == bits(want)
     assert all(r["child_hits"] == r["fail_transitions"] == r["exits"] == 0 and r["finalize"] == 0.0 for r in got)
-    assert [r["final"] for r in got] == [r["final"] for r in want]
+    assert [r["final"] for r in got] == [r["final"] for r in want] and [r["merges"] for r in got] == [r["merges"] for r in want]
 
 
 def test_checker_with_graphs_equals_the_float64_restatement(toy):
@@ -179,8 +207,9 @@ def test_checker_with_graphs_equals_the_float64_restatement(toy):
     totals = dict(child_hits=0, fail_transitions=0, exits=0)
     finalized = differs = 0
     for kw in (dict(K=4), dict(K=2, blank_penalty=1.5), dict(K=8, length_norm=False)):
-        chk = H.hw_checker(toy.cfg, toy.sd, toy.f, toy.el, toy.table, toy.graph_of, **kw)
+        chk = R.mbs_checker(toy.cfg, toy.sd, toy.f, toy.el, toy.table, toy.graph_of, **kw)
         plain = R.mbs_checker(toy.cfg, toy.sd, toy.f, toy.el, **kw)
+        assert_equals_pins(plain, pinned(**kw))
         for b, g in enumerate(toy.graph_of):
             ref = H.hw_float64(toy.cfg, toy.sd, toy.f[b, :toy.el[b]], graphs[g] if g >= 0 else None, **kw)
             got = chk[b]

@@ -7,43 +7,18 @@
   pack / unpack         ragged per-utterance lists <-> the [B][u_cap] arrays of the C ABI
 """
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import torch
 
-from oracle import build as obuild, greedy as og, zipformer as oz
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "token_scores_checker.c")
-_lib = None
-
-
-def _out_path():
-    for d in (os.path.join(HERE, "_build"), os.path.join(tempfile.gettempdir(), f"rs_token_scores_{os.getuid()}")):
-        try:
-            os.makedirs(d, exist_ok=True)
-            if os.access(d, os.W_OK):
-                return os.path.join(d, "token_scores_checker.so")
-        except OSError:
-            continue
-    raise RuntimeError("no writable directory for the checker library")
+import checker_lib
+from oracle import greedy as og, zipformer as oz
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        og.lib()                                             # builds oracle/librs_oracle.so when stale, and loads it
-        out = _out_path()
-        deps = [SRC, obuild.OUT, os.path.join(obuild.HERE, "rnnt_math.h")]
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-            subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", obuild.HERE,
-                                   "-o", out, SRC, obuild.OUT, "-Wl,-rpath," + obuild.HERE, "-lm"])
-        _lib = ctypes.CDLL(out)
-        _lib.rs_token_scores_checker.restype = ctypes.c_int
-    return _lib
+    L = checker_lib.load("token_scores_checker.c")
+    L.rs_token_scores_checker.restype = ctypes.c_int
+    return L
 
 
 def is_k2(cfg):
