@@ -641,7 +641,11 @@ __global__ __launch_bounds__(256) void rnnt_prep_kernel(DecodeState st, const fl
         *reinterpret_cast<u16x4_t*>(st.a16 + (size_t)slot * J + k) = pack_bf16x4(a0, a1, a2, a3);
     }
     ss = wave_sum(ss);
-    if (lane == 0) st.anorm[slot] = sqrtf(ss) * 1.0001f;        // any summation order is fine: the bound has slack
+    // any summation order is fine: the bound has slack.  The floor covers the squares that UNDERFLOW: an element below 2^-60 has a
+    // square below 2^-120, which float32 holds with few bits or not at all (ss = 0 for |a_k| < 2^-75, for |a_k| < 2^-63 where
+    // subnormals are flushed); such elements add at most J * 2^-120 to ||a||^2, so ||a|| <= sqrt(ss) + sqrt(J) * 2^-60, and
+    // sqrt(J) <= 2^5 on the screened path (J <= 640).  Larger elements have normal squares: relative error 2^-24 each.
+    if (lane == 0) st.anorm[slot] = sqrtf(ss) * 1.0001f + 0x1p-55f;
 }
 
 // screening GEMM of the joint (see "screened joint" below):
@@ -705,7 +709,7 @@ __global__ __launch_bounds__(256) void rnnt_screen_kernel(DecodeState st, const 
 // restricted to the columns that can possibly win:
 //   1. rnnt_screen_kernel a = relu(f[b][t_b] + g[b]) per alive row (bf16 tile in LDS, ||a||_2), then
 //                         z~ = bf16(a) . bf16(W_o)^T + b_o   (bf16 MFMA, f32 accumulate: 1/16 of the f32 MFMA cost)
-//   2. rnnt_verify_kernel per row: m = max z~; every column with z~_v >= m - 2 eps is a candidate, where
+//   2. rnnt_verify_kernel per row: m = max z~; every column with m - z~_v <= 2 eps + 2^-21 |m| (screen_margin below) is a candidate, where
 //        |z~_v - z_v| <= eps = 2^-7 * 1.25 * ||a|| * max_v ||w_v||
 //      (bf16 rounding of both operands is <= 2^-8 relative each, the products are exact in f32, Cauchy-Schwarz bounds
 //      sum |a_k w_vk|, the factor 1.25 covers the f32 accumulation error of both sums).  The true argmax of the exact
@@ -717,6 +721,31 @@ __global__ __launch_bounds__(256) void rnnt_screen_kernel(DecodeState st, const 
 // (NCH == 0: any V — the approximate logits are scanned from memory twice and the candidates are evaluated in batches of up to
 //  VER_CAP; the Zipformer family's 10 720 symbols.)  The error bound does not depend on the activation: a = act(f + g) is
 //  computed exactly (ReLU, or the shared tanh polynomial) and only then rounded for the screening product.
+//
+// What the candidate test has to cover beyond eps.  eps bounds |t_v - s_v|, the two DOT PRODUCTS (t_v = bf16 MFMA sum, s_v = the
+// exact-order float32 chain).  The values that are compared carry one more rounding each: z~_v = fl(t_v + b_v) in
+// rnnt_screen_kernel and z_v = fl(s_v + b_v) in verify_evaluate, each within 2^-24 of its own magnitude.  With u the true argmax
+// and c the column of m = max z~:
+//     z~_u >= z_u - eps - d_u >= z_c - eps - d_u >= m - 2 eps - d_u - d_c,     d_x <= 2^-24 (|z_x| + |z~_x|).
+// All four magnitudes are within 3 eps (+ the d's) of |m|, so d_u + d_c <= 2^-22 |m| (1 + 2^-22) + 3 * 2^-22 eps.  The margin
+//     2 eps + 2^-21 |m|
+// has twice that in its second term; the 2^-22-relative remainder on eps, the roundings of the margin's own three products and
+// its sum (2^-24 relative each) and the rounding of fl(m - z~_v) (2^-24 relative: a column with m - z~_v <= margin * (1 - 2^-23)
+// always passes) disappear in the pads wmax already carries (2^-10, runtime/weights.py screen_tensors) and anorm (1e-4).
+// The test is  fl(m - z~_v) <= margin,  NOT  z~_v >= fl(m - margin):  when ||a|| is small and a bias is large, 2 eps is below
+// half an ulp of m, fl(m - 2 eps) == m, and a column whose exact logit TIES the maximum was never evaluated (one-hot
+// a = 8.75e-6, w = 0.054, both biases 8: z~ = 8 + ulp against 8, exact logits 8 and 8, the lower index lost;
+// tests/test_gpu_decode_edges.py test_small_activation_rows).  ||a|| itself: see the floor in rnnt_prep_kernel — with
+// anorm = 0 (two elements of 2^-80) the margin was zero and the bf16 order of two columns decided.
+// (Products a_k w_vk that underflow themselves, |a_k w_vk| < 2^-126, add an absolute error below J * 2^-126 per logit; the
+// floor's share of the margin, 2^-61 max ||w_v||, covers it for every output layer with a row norm above 2^-55.)
+__device__ __forceinline__ float screen_margin(float m, float wmax, float anorm) {
+    return 0x1p-21f * fabsf(m) + 0.01953125f * wmax * anorm;     // 2^-21 |m| + 2 * 2^-7 * 1.25 * max ||w_v|| * ||a||
+}
+__device__ __forceinline__ bool screen_candidate(float m, float z, float margin) {
+    return m - z <= margin;                                      // -inf padding: m - z = +inf never passes
+}
+
 constexpr int VER_CAP = 1024;
 
 // exact float32 logits of the candidate columns cand_s[0 .. n_cand) of one row (a_s = its exact act(f + g) in LDS), one wave:
@@ -834,8 +863,8 @@ __global__ __launch_bounds__(256) void rnnt_verify_kernel(DecodeState st, const 
     const int tc = t < Tp ? t : Tp - 1;
     float* a_s = reinterpret_cast<float*>(ver_smem) + wave * J;
     verify_act_row(st, f + ((size_t)b * Tp + tc) * J, st.g + (size_t)b * J, a_s, J, lane, 64);
-    // 2 eps = 2 * 2^-7 * 1.25 * ||a|| * max_v ||w_v||  (wmax[0] holds the largest row norm of W_o, rounded up)
-    const float thr = m - 0.01953125f * wmax[0] * st.anorm[slot];
+    // (wmax[0] holds the largest row norm of W_o, rounded up)
+    const float margin = screen_margin(m, wmax[0], st.anorm[slot]);
     // candidate columns, ascending, compacted into LDS (the unrolled part stays tiny: the exact evaluation exists once in
     // the instruction stream)
     int* cand_s = reinterpret_cast<int*>(ver_smem + 4 * J * 4) + wave * CAND_ROWS;
@@ -845,7 +874,7 @@ __global__ __launch_bounds__(256) void rnnt_verify_kernel(DecodeState st, const 
     if constexpr (NCH > 0) {
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            const bool is = zr[c] >= thr;                         // -inf padding never passes (thr is finite)
+            const bool is = screen_candidate(m, zr[c], margin);
             const unsigned long long mask = __ballot(is);
             if (is) cand_s[n_cand + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = c * 64 + lane;
             n_cand += __builtin_popcountll(mask);
@@ -855,7 +884,7 @@ __global__ __launch_bounds__(256) void rnnt_verify_kernel(DecodeState st, const 
         verify_evaluate(cand_s, n_cand, a_s, Wrm, bo, J, lane, best, best_idx);
     } else {
         for (int c = 0; c < nchunk; ++c) {
-            const bool is = c * 64 + lane < V && z[c * 64 + lane] >= thr;
+            const bool is = c * 64 + lane < V && screen_candidate(m, z[c * 64 + lane], margin);
             const unsigned long long mask = __ballot(is);
             if (is) cand_s[n_cand + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = c * 64 + lane;
             n_cand += __builtin_popcountll(mask);
@@ -910,11 +939,11 @@ __global__ __launch_bounds__(256) void rnnt_verify_wide_kernel(DecodeState st, c
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float thr = m - 0.01953125f * wmax[0] * st.anorm[slot];
+    const float margin = screen_margin(m, wmax[0], st.anorm[slot]);
     int n_cand = 0;
 #pragma unroll
     for (int c = 0; c < NCHW; ++c) {
-        const bool is = zr[c] >= thr;
+        const bool is = screen_candidate(m, zr[c], margin);
         const unsigned long long mask = __ballot(is);
         if (is) cand_s[n_cand + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = (wave * NCHW + c) * 64 + lane;
         n_cand += __builtin_popcountll(mask);
