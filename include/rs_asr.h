@@ -620,6 +620,40 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
                          float* scores, const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- n-gram language model shallow fusion in the modified beam search — added within ABI 7 (probe the symbols) ----------------
+ * [UPSTREAM, not vendored, UNVERIFIED] icefall's modified_beam_search_lm_shallow_fusion / modified_beam_search_ngram_rescoring
+ * add an n-gram LM's score to a hypothesis after the top-K pick of a frame; the slot below is believed to be theirs and has not
+ * been compared with them.  sherpa-onnx's own `lm=` / `lm_scale=` is a neural LM and is not this.
+ * The model is an rs_ngram and the step is `step` of rs_ngram, both stated with rs_rnnt_alsd_lm below, unchanged.  The search is
+ * rs_rnnt_mbs / rs_rnnt_mbs_hotwords with these additions:
+ *   every hypothesis row carries an LM state; the starting hypothesis stands at lm.start (an index outside the nodes counts as
+ *   the root).  Steps 1 - 4 are unchanged: the K best of the H x V values are selected WITHOUT the LM term and without any
+ *   hotword bonus.  The LM therefore re-ranks only among the K survivors of a frame and acts on later frames through log_prob; it
+ *   cannot rescue a candidate that was not selected.  THIS DIFFERS FROM rs_rnnt_alsd_lm ON PURPOSE: there the LM term is part of
+ *   the value the pruning ranks, here it is added after the selection.
+ *   Step 5, before the merge: a selected candidate that appends a label v (neither the blank nor <unk>) from a parent with LM
+ *   state s is scored, float32, no contraction, in this order:
+ *       lp = lp[h][v];   with a graph: lp = lp + delta (as rs_rnnt_mbs_hotwords);   (l, s') = step(s, v);
+ *       log_prob = lp + (lm_alpha * l)        the product is rounded first
+ *   and its LM state is s'.  A candidate that appends nothing (blank or <unk>) keeps its score and state and makes no walk.
+ *   The merge is unchanged: rs_logaddexpf of the log_probs with their terms inside; tokens, timestamps, context state and LM
+ *   state of the entry added first stay (equal token sequences have equal LM states anyway).  No end-of-sentence term.  The
+ *   hotword Finalize at the last frame is unchanged and is applied to the LM-inclusive score before the winner is chosen.
+ *   scores[b] includes the LM terms; rs_rnnt_token_scores keeps reporting the model's unmodified distribution.
+ * rs_rnnt_mbs_lm with lm == NULL, lm->n_nodes == 0 or lm_alpha == 0 is rs_rnnt_mbs_hotwords (the same kernels, the same bits;
+ * with no graphs as well, rs_rnnt_mbs).  Otherwise the LM form of the selection kernel runs, which carries the call's graphs or
+ * none: still five launches per frame, nothing waits for the host, one synchronisation at the end.  Workspace:
+ * rs_rnnt_mbs_lm_workspace_bytes, the hotword layout plus one LM state per hypothesis row, twice (0 for invalid arguments or a
+ * context that is not finalized).  Errors as rs_rnnt_mbs_hotwords, and RS_EINVAL before anything is enqueued for an lm_alpha
+ * that is negative or not finite, lm->n_logits other than the context's, order outside 1..8, start outside the nodes, negative
+ * counts or null arrays. */
+struct rs_ngram;
+size_t rs_rnnt_mbs_lm_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap);
+int rs_rnnt_mbs_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                   float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                   const rs_hotwords* hw, const int32_t* graph_of, const struct rs_ngram* lm, float lm_alpha, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ---- hotwords (contextual biasing) in the ALSD beam search — added within ABI 7 ---------------------
  * gives the LSTM transducers (the NeMo family: FastConformer-RNNT, whose checkpoint ships `strategy: alsd`) what
  * rs_rnnt_mbs_hotwords gives the Zipformer family.  [UPSTREAM] NeMo's align_length_sync_decoding has no hotword rule: the

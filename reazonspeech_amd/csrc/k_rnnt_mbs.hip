@@ -4,7 +4,7 @@
 // `max_active_paths` is the constructor's other offline transducer method).
 //
 // [UPSTREAM, not vendored, PARITY UNPINNED like the greedy search] OfflineTransducerModifiedBeamSearchDecoder::Decode without
-// LM, Hypotheses::Add, GetMostProbable(length_norm = true); hotwords (ContextGraph) are the second half of this comment.  The
+// LM, Hypotheses::Add, GetMostProbable(length_norm = true); hotwords (ContextGraph) and the n-gram LM follow below.  The
 // algorithm, as built here:
 //   * per utterance one starting hypothesis ys = [-1, blank] (context_size = 2 entries), log_prob = 0, no timestamps;
 //   * for every encoder frame t < enc_lens[b], with H <= K live hypotheses (K = max_active_paths):
@@ -56,9 +56,25 @@
 // a bisection halves an interval of < 2^31 entries, 32 steps), and a node or child index outside the table is replaced by the root
 // before it is used — a corrupt table can give a wrong bonus, nothing else.  rs_hotwords_check (rs_api.hip) refuses such tables
 // on the host before upload.  The walk itself (hw_root, hw_node, hw_child, hw_step) is k_rnnt_hotwords.h.
+//
+// N-GRAM LM (rs_rnnt_mbs_lm; the table and `step` are stated in include/rs_asr.h, the walk is k_rnnt_ngram.h, shared with ALSD).
+// [UPSTREAM, not vendored, UNVERIFIED] the slot is believed to be icefall's modified_beam_search_lm_shallow_fusion: the LM term is
+// added to a candidate AFTER the top-K pick, not inside it (ALSD's LM form ranks with it, on purpose: see the header).  Every
+// hypothesis row carries an LM state (MbsState.lmctx, ping-pong; the starting hypothesis stands at `start`).  Step 4 is untouched.
+// In step 5, before the merge, a selected candidate that appends a label v: lp = lp[h][v]; with a graph lp = lp + delta;
+// (l, s') = step(s, v); log_prob = lp + (alpha * l), the product rounded first; state s'.  One that appends nothing keeps score and
+// state and makes no walk.  The merge keeps the first entry's LM state too; Finalize applies to the LM-inclusive score; no
+// end-of-sentence term.  An LM walk usually backs off through every level (a hotword walk usually ends at its first node), so the at
+// most 8 walks of a frame do not run one after another on all lanes: lane j < n_cand of wave 0 computes candidate j whole — hotword
+// step if the utterance has a graph, LM step, score — and the three results are broadcast by __shfl, so everything below (merge,
+// decoder rows, winner) stays uniform.  What this saves over one lane doing all walks has not been measured.  The LM form is the
+// template parameter LM of mbs_init_kernel / mbs_select_kernel; it is compiled with HW on and carries the call's graphs or none
+// (graph_of == nullptr: every utterance takes the no-graph statements).  The plain and hotword instantiations are the same text
+// without the `if constexpr (LM)` statements and are the ones launched when the call has no model (lm == NULL, no nodes, alpha 0).
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
 #include "k_rnnt_hotwords.h"
+#include "k_rnnt_ngram.h"
 
 #include <type_traits>
 
@@ -80,16 +96,29 @@ struct MbsState {
     int32_t* fr[2];      // [rows][cap] frame of each token
     int32_t* n_hyp[2];   // [B]
     int32_t* ctx[2];     // [rows] hotwords: node of the context graph the hypothesis stands at (nullptr without hotwords)
+    int32_t* lmctx[2];   // [rows] n-gram LM: the LM state of the hypothesis (nullptr without an LM)
     int cap;
 };
 
 // the graphs of a call and the walk over them: k_rnnt_hotwords.h (shared with the ALSD search)
 using MbsNoHw = RnntNoHw;
 using MbsHw = RnntHw;
+struct MbsHwLm : MbsHw { // n-gram LM: the model and its weight next to the graphs, which may be absent (graph_of == nullptr)
+    rs_ngram lm;
+    float alpha;
+};
+template <bool HW, bool LM>
+using MbsArg = std::conditional_t<LM, MbsHwLm, std::conditional_t<HW, MbsHw, MbsNoHw>>;
+// root of utterance b's graph; the LM form may carry no graphs at all
+template <bool LM, class A>
+__device__ __forceinline__ int mbs_root(const A& hw, int b) {
+    if constexpr (LM) { if (hw.graph_of == nullptr) return -1; }
+    return hw_root(hw, b);
+}
 
-template <bool HW>
+template <bool HW, bool LM = false>
 __global__ void mbs_init_kernel(DecodeState st, MbsState ms, const int32_t* __restrict__ enc_lens, int B, int K, int blank,
-                                int32_t* __restrict__ n_ids, float* __restrict__ scores, std::conditional_t<HW, MbsHw, MbsNoHw> hw) {
+                                int32_t* __restrict__ n_ids, float* __restrict__ scores, MbsArg<HW, LM> hw) {
     // single workgroup: the starting hypothesis of every utterance, its decoder row and the first work lists
     __shared__ int n_alive_s;
     if (threadIdx.x == 0) n_alive_s = 0;
@@ -98,7 +127,8 @@ __global__ void mbs_init_kernel(DecodeState st, MbsState ms, const int32_t* __re
         const int row = b * K;
         ms.len[0][row] = 0; ms.score[0][row] = 0.0f; ms.last0[0][row] = -1; ms.last1[0][row] = blank; ms.dec[0][row] = 0;
         ms.n_hyp[0][b] = 1;
-        if constexpr (HW) { const int r = hw_root(hw, b); ms.ctx[0][row] = r < 0 ? 0 : r; }
+        if constexpr (HW) { const int r = mbs_root<LM>(hw, b); ms.ctx[0][row] = r < 0 ? 0 : r; }
+        if constexpr (LM) ms.lmctx[0][row] = lm_node(hw.lm, hw.lm.start);
         st.token2[row] = -1; st.token[row] = blank; st.act[b] = row;
         n_ids[b] = 0; scores[b] = 0.0f;                  // the result of an utterance without frames
         if (enc_lens[b] > 0) st.alive[atomicAdd(&n_alive_s, 1)] = row;
@@ -128,11 +158,13 @@ __global__ __launch_bounds__(256) void mbs_act_kernel(DecodeState st, MbsState m
 // NVR > 0: V <= 256 NVR and a hypothesis's logits row is read ONCE into NVR registers per thread, every load in flight before the
 // first comparison; maximum, exp-sum and the running top-K then walk the registers.  NVR = 0: any V, three passes over memory,
 // the same arithmetic in the same order.
-template <int NVR, bool HW>
+// HW: the hotword form; LM: the n-gram form (HW on as well).  The other forms are the same text without the `if constexpr` statements.
+template <int NVR, bool HW, bool LM = false>
 __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
     DecodeState st, MbsState ms, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int rows, int K,
     int V, int blank, int unk, int t, float blank_penalty, int length_norm, int out_cap, int32_t* __restrict__ ids,
-    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores, std::conditional_t<HW, MbsHw, MbsNoHw> hw) {
+    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores, MbsArg<HW, LM> hw) {
+    static_assert(HW || !LM, "the LM form is compiled with the hotword statements");
     const int b = blockIdx.x;
     const int T = enc_lens[b];
     if (t >= T) return;                                   // skipped, not masked
@@ -151,7 +183,8 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
     __shared__ int s_nnew;
     __shared__ int s_ctx[HW ? MBS_MAX_K : 1];             // hotwords: the context state of each entry of the new set
     int root = -1;                                        // hotwords: the root of the utterance's graph, -1 = it has none
-    if constexpr (HW) root = hw_root(hw, b);
+    if constexpr (HW) root = mbs_root<LM>(hw, b);
+    __shared__ int s_lm[LM ? MBS_MAX_K : 1];              // n-gram LM: the LM state of each entry of the new set
 
     // ---- steps 3 + 4a: every thread's K best of its own columns over all H rows (sorted: value desc, flat index asc; a thread
     // meets its flat indices in ascending order, so a later equal value never displaces an earlier one) ----
@@ -281,7 +314,40 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
         }
         // hotwords: one walk per candidate that appends a label, before the merge; the others keep their parent's state
         int cctx[HW ? MBS_MAX_K : 1];
-        if constexpr (HW) {
+        [[maybe_unused]] int clm[LM ? MBS_MAX_K : 1];
+        if constexpr (LM) {
+            // n-gram LM: an LM walk usually backs off through every level, so the walks run side by side: lane j computes candidate j
+            // whole — the hotword step if the utterance has a graph, the LM step, the score — and the three results are broadcast
+            float msc = 0.0f;
+            int mctx = 0, mlm = 0;
+            if (lane < n_cand) {
+                const int c = s_idx[lane];
+                const int h = c / V, v = c - h * V;
+                const int prow = b * K + h;
+                msc = s_val[lane];
+                if (root >= 0) mctx = ms.ctx[p][prow];
+                mlm = ms.lmctx[p][prow];
+                if (v != blank && v != unk) {
+                    if (root >= 0) {
+                        int nx = root;
+                        const float delta = hw_step(hw.g, root, mctx, v, &nx);
+                        msc = msc + delta;
+                        mctx = nx;
+                    }
+                    int ln = 0;
+                    const float l = lm_step(hw.lm, mlm, v, &ln);
+                    msc = msc + (hw.alpha * l);
+                    mlm = ln;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < MBS_MAX_K; ++j) {
+                const float bsc = __shfl(msc, j, 64);
+                cctx[j] = __shfl(mctx, j, 64);
+                clm[j] = __shfl(mlm, j, 64);
+                if (j < n_cand) csc[j] = bsc;
+            }
+        } else if constexpr (HW) {
 #pragma unroll
             for (int j = 0; j < MBS_MAX_K; ++j) {
                 cctx[j] = 0;
@@ -337,6 +403,7 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
                 if (root >= 0 && t == T - 1) sc = sc + (-hw.g.node_score[hw_node(hw.g, cctx[j], root)]);      // Finalize
                 if (lane == 0) s_ctx[nk] = cctx[j];
             }
+            if constexpr (LM) { if (lane == 0) s_lm[nk] = clm[j]; }
             if (lane == 0) { s_prow[nk] = cprow[j]; s_tok[nk] = ctok[j]; s_score[nk] = sc; s_dec[nk] = d; }
             const int n = cplen[j] + (ctok[j] >= 0 ? 1 : 0);
             const float norm = length_norm ? sc / (float)(n + MBS_CONTEXT) : sc;
@@ -382,6 +449,7 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
             ms.len[pn][row] = nn; ms.score[pn][row] = s_score[k];
             ms.last0[pn][row] = l0; ms.last1[pn][row] = l1; ms.dec[pn][row] = s_dec[k];
             if constexpr (HW) ms.ctx[pn][row] = s_ctx[k];
+            if constexpr (LM) ms.lmctx[pn][row] = s_lm[k];
             const int pos = atomicAdd(&st.counters[2 + pn], 1);
             st.alive[(size_t)pn * rows + pos] = row;
         }
@@ -389,7 +457,7 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
 }
 
 // the search's layout (h .. c_tmp adjacent: one memset clears the four); -> DecodeState.a_pre, writable (mbs_act_kernel fills it)
-float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, rs_arena& a, DecodeState& st, MbsState& ms) {
+float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, bool lm, rs_arena& a, DecodeState& st, MbsState& ms) {
     const rs_dims& d = ctx->d;
     const size_t rows = (size_t)B * K, state = rows * d.pred_hidden;
     st.h = a.take<float>(state); st.c = a.take<float>(state);                // (the projection kernel's state commit copies
@@ -408,7 +476,9 @@ float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, rs_ar
     st.counters = a.take<int32_t>(16);
     st.zapprox = a.take<float>(rows * (size_t)rs_joint_zstride(d));
     ms.ctx[0] = ms.ctx[1] = nullptr;
-    if (hotwords) { ms.ctx[0] = a.take<int32_t>(rows); ms.ctx[1] = a.take<int32_t>(rows); }       // (last: the plain layout is a prefix)
+    if (hotwords) { ms.ctx[0] = a.take<int32_t>(rows); ms.ctx[1] = a.take<int32_t>(rows); }       // (after the plain layout: it is a prefix)
+    ms.lmctx[0] = ms.lmctx[1] = nullptr;
+    if (lm) { ms.lmctx[0] = a.take<int32_t>(rows); ms.lmctx[1] = a.take<int32_t>(rows); }         // (last: the hotword layout is a prefix)
     ms.cap = cap;
     st.a_pre = a_pre;
     st.joint_act = d.joint_act;
@@ -417,18 +487,18 @@ float* mbs_layout(const rs_ctx* ctx, int B, int K, int cap, bool hotwords, rs_ar
 
 }  // namespace
 
-size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords) {
+size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords, bool lm) {
     if (B <= 0 || K <= 0 || K > MBS_MAX_K || tp_max < 0) return 0;
     rs_arena a;
     DecodeState st{};
     MbsState ms;
-    mbs_layout(ctx, B, K, tp_max > 0 ? tp_max : 1, hotwords, a, st, ms);
+    mbs_layout(ctx, B, K, tp_max > 0 ? tp_max : 1, hotwords || lm, lm, a, st, ms);
     return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
                      int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
-                     const int32_t* graph_of, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                     const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int D = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
@@ -441,9 +511,12 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     DecodeState st{};
     MbsState ms;
     const bool HWF = hotwords != nullptr && graph_of != nullptr && hotwords->n_graphs > 0;      // else: the plain kernels, today's bits
-    MbsHw hw{};
+    const bool LMF = ngram != nullptr && ngram->n_nodes > 0 && lm_alpha != 0.0f;                // else: the forms above, today's bits
+    MbsHwLm hwlm{};
+    MbsHw& hw = hwlm;                                     // the hotword form takes the base: the graphs alone
     if (HWF) { hw.g = *hotwords; hw.graph_of = graph_of; }
-    float* const a_pre = mbs_layout(ctx, B, K, cap, HWF, arena, st, ms);
+    if (LMF) { hwlm.lm = *ngram; hwlm.alpha = lm_alpha; }
+    float* const a_pre = mbs_layout(ctx, B, K, cap, HWF || LMF, LMF, arena, st, ms);
     if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
         return rs_fail(ctx, RS_EWORKSPACE, "modified beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     const int rows = B * K;
@@ -458,6 +531,9 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     if (V > MBS_THREADS * 4) select_hw = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, true> : mbs_select_kernel<0, true>;
     auto select = mbs_select_kernel<4, false>;
     if (V > MBS_THREADS * 4) select = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, false> : mbs_select_kernel<0, false>;
+    const auto init_lm = mbs_init_kernel<true, true>;     // the LM form: the model, and the call's graphs or none
+    auto select_lm = mbs_select_kernel<4, true, true>;
+    if (V > MBS_THREADS * 4) select_lm = V <= MBS_THREADS * 42 ? mbs_select_kernel<42, true, true> : mbs_select_kernel<0, true, true>;
     // the search, written once: `init_k` and `select_k` are the form's kernels, `tables` their last argument (the graphs, or nothing)
     auto search = [&](auto init_k, auto select_k, const auto& tables) -> int {
         rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
@@ -481,6 +557,7 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
         if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "modified beam search: a result has more than out_cap=%d tokens", out_cap);
         return RS_OK;
     };
+    if (LMF) return search(init_lm, select_lm, hwlm);
     if (HWF) return search(init_hw, select_hw, hw);
     return search(init, select, MbsNoHw{});
 }

@@ -1,6 +1,6 @@
 // k_rnnt_ngram.h — the device walk over a backoff n-gram language model (include/rs_asr.h: rs_ngram), for the searches that fuse an
-// LM into their ranking: ALSD today (k_rnnt_alsd.hip, rs_rnnt_alsd_lm).  It holds the walk only and includes nothing of a search, so
-// that another search can compile the same text and get the same bits.
+// LM into their scores: ALSD (k_rnnt_alsd.hip, rs_rnnt_alsd_lm) and the modified beam search (k_rnnt_mbs.hip, rs_rnnt_mbs_lm).  It
+// holds the walk only and includes nothing of a search: both compile the same text, so a step gives both the same bits.
 //
 // The model is read-only flat arrays: a forward trie over token ids with sorted child lists (a child is found by bisection), a link
 // from every node to the longest proper suffix of its words that the model has, and the backoff weight paid on that link.  Most

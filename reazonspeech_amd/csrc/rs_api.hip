@@ -15,10 +15,10 @@
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B);
 size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm);
-size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords);
+size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords, bool lm);
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
                      int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
-                     const int32_t* graph_of, void* workspace, size_t workspace_bytes, hipStream_t s);
+                     const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops);
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
                       int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
@@ -426,26 +426,34 @@ int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* en
 
 int rs_ngram_check(const rs_ngram_host* table, char* msg, size_t msg_bytes) { return rs_ngram_check_table(table, msg, msg_bytes); }
 
+// the device n-gram table of a search entry (`search` = the prefix of its messages): RS_OK and *lm the table to search with
+// (nullptr: no model in this call)
+static int ngram_arg(rs_ctx* ctx, const char* search, const rs_ngram** table, float lm_alpha) {
+    const rs_ngram* lm = *table;
+    if (!(lm_alpha >= 0.0f) || !isfinite(lm_alpha)) return rs_fail(ctx, RS_EINVAL, "%s: lm: lm_alpha must be a finite number >= 0", search);
+    if (lm && (lm->n_nodes < 0 || lm->n_children < 0 || lm->n_logits < 0)) return rs_fail(ctx, RS_EINVAL, "%s: lm: negative count", search);
+    if (lm && lm->n_nodes > 0 && lm_alpha != 0.0f) {
+        if (lm->n_logits != ctx->d.n_logits)
+            return rs_fail(ctx, RS_EINVAL, "%s: lm: the table is built for %d logits, the context has %d", search, lm->n_logits, ctx->d.n_logits);
+        if (lm->order < 1 || lm->order > RS_NGRAM_MAX_ORDER) return rs_fail(ctx, RS_EINVAL, "%s: lm: order %d outside 1..%d", search, lm->order, (int)RS_NGRAM_MAX_ORDER);
+        if (lm->start < 0 || lm->start >= lm->n_nodes) return rs_fail(ctx, RS_EINVAL, "%s: lm: start %d outside the %d nodes", search, lm->start, lm->n_nodes);
+        if (!isfinite(lm->unk_logp)) return rs_fail(ctx, RS_EINVAL, "%s: lm: unk_logp is not finite", search);
+        if (!lm->child_begin || !lm->root_child || !lm->logp || !lm->backoff || !lm->suffix || !lm->level ||
+            (lm->n_children > 0 && (!lm->child_tok || !lm->child_node)))
+            return rs_fail(ctx, RS_EINVAL, "%s: lm: null array", search);
+    } else {
+        *table = nullptr;                                 // no model in this call: the entry without one, the same kernels and bits
+    }
+    return RS_OK;
+}
+
 int rs_rnnt_alsd_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
                     double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
                     int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
                     float lm_alpha, void* workspace, size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd_lm);
     if (int rc = hotwords_arg(ctx, "alsd", true, &hw, graph_of); rc != RS_OK) return rc;
-    if (!(lm_alpha >= 0.0f) || !isfinite(lm_alpha)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: lm_alpha must be a finite number >= 0");
-    if (lm && (lm->n_nodes < 0 || lm->n_children < 0 || lm->n_logits < 0)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: negative count");
-    if (lm && lm->n_nodes > 0 && lm_alpha != 0.0f) {
-        if (lm->n_logits != ctx->d.n_logits)
-            return rs_fail(ctx, RS_EINVAL, "alsd: lm: the table is built for %d logits, the context has %d", lm->n_logits, ctx->d.n_logits);
-        if (lm->order < 1 || lm->order > RS_NGRAM_MAX_ORDER) return rs_fail(ctx, RS_EINVAL, "alsd: lm: order %d outside 1..%d", lm->order, (int)RS_NGRAM_MAX_ORDER);
-        if (lm->start < 0 || lm->start >= lm->n_nodes) return rs_fail(ctx, RS_EINVAL, "alsd: lm: start %d outside the %d nodes", lm->start, lm->n_nodes);
-        if (!isfinite(lm->unk_logp)) return rs_fail(ctx, RS_EINVAL, "alsd: lm: unk_logp is not finite");
-        if (!lm->child_begin || !lm->root_child || !lm->logp || !lm->backoff || !lm->suffix || !lm->level ||
-            (lm->n_children > 0 && (!lm->child_tok || !lm->child_node)))
-            return rs_fail(ctx, RS_EINVAL, "alsd: lm: null array");
-    } else {
-        lm = nullptr;                                     // no model in this call: rs_rnnt_alsd_hotwords, the same kernels and bits
-    }
+    if (int rc = ngram_arg(ctx, "alsd", &lm, lm_alpha); rc != RS_OK) return rc;
     return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
                      hw, graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
 }
@@ -477,7 +485,7 @@ int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
 size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
     RS_GUARD_QUERY(ctx, rs_rnnt_mbs_workspace_bytes, 0);
     if (B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0) return 0;
-    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, false);
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, false, false);
 }
 
 int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
@@ -491,7 +499,13 @@ int rs_rnnt_mbs(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, in
 size_t rs_rnnt_mbs_hotwords_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
     RS_GUARD_QUERY(ctx, rs_rnnt_mbs_hotwords_workspace_bytes, 0);
     if (B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0) return 0;
-    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, true);
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, true, false);
+}
+
+size_t rs_rnnt_mbs_lm_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_mbs_lm_workspace_bytes, 0);
+    if (B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0) return 0;
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, true, true);
 }
 
 // pure host code: is `t` (HOST pointers) a table the device walk may be given?  (The walk is safe on any table; a table that
@@ -538,10 +552,11 @@ int rs_hotwords_check(const rs_hotwords_host* t, char* msg, size_t msg_bytes) {
     return RS_OK;
 }
 
-int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
-                         float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
-                         const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes, void* stream) {
-    RS_GUARD(ctx, rs_rnnt_mbs_hotwords);
+// the argument checks and the dispatch of rs_rnnt_mbs, rs_rnnt_mbs_hotwords and rs_rnnt_mbs_lm (lm == nullptr: no model)
+static int mbs_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                    float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                    const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
+                    void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0) return rs_fail(ctx, RS_EINVAL, "modified beam search: negative size");
     if (max_active_paths < 1 || max_active_paths > 8) return rs_fail(ctx, RS_EINVAL, "modified beam search: max_active_paths must be 1..8, got %d", max_active_paths);
     if (!(blank_penalty >= 0.0f)) return rs_fail(ctx, RS_EINVAL, "modified beam search: blank_penalty must be >= 0");
@@ -554,7 +569,26 @@ int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
     }
     if (int rc = hotwords_arg(ctx, "modified beam search", false, &hw, graph_of); rc != RS_OK) return rc;
     return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
-                            out_cap, ids, frames, n_ids, scores, hw, hw ? graph_of : nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+                            out_cap, ids, frames, n_ids, scores, hw, hw ? graph_of : nullptr, lm, lm_alpha, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+
+int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                         float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                         const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_mbs_hotwords);
+    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, hw,
+                    graph_of, nullptr, 0.0f, workspace, workspace_bytes, stream);
+}
+
+int rs_rnnt_mbs_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                   float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                   const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_mbs_lm);
+    if (int rc = ngram_arg(ctx, "modified beam search", &lm, lm_alpha); rc != RS_OK) return rc;     // before anything is enqueued
+    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, hw,
+                    graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
 }
 
 // ---- token log-probabilities of a finished search (k_rnnt_scores.hip) ----

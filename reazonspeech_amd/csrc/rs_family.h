@@ -55,6 +55,9 @@ enum { RS_ANYTIME = 0, RS_FINAL = 1 };
     X(rs_rnnt_mbs, Z, FINAL, RS_HINT_MBS)                                                                                             \
     X(rs_rnnt_mbs_hotwords_workspace_bytes, Z, ANYTIME, RS_HINT_MBS)                                                                  \
     X(rs_rnnt_mbs_hotwords, Z, FINAL, RS_HINT_MBS)                                                                                    \
+    /* FINAL also for the size, as rs_rnnt_alsd_hotwords_workspace_bytes above */                                                     \
+    X(rs_rnnt_mbs_lm_workspace_bytes, Z, FINAL, RS_HINT_MBS)                                                                          \
+    X(rs_rnnt_mbs_lm, Z, FINAL, RS_HINT_MBS)                                                                                          \
     X(rs_rnnt_token_scores_workspace_bytes, CZ, FINAL, RS_HINT_TRANSDUCER)                                                            \
     /* ANYTIME: tests/test_gpu_token_scores.py pins RS_EINVAL for a context that is not finalized; the entry tests that itself */     \
     X(rs_rnnt_token_scores, CZ, ANYTIME, RS_HINT_TRANSDUCER)                                                                          \

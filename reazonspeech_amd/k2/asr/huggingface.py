@@ -58,7 +58,7 @@ def resolve_checkpoint(language, precision, checkpoint=None):
 
 def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
                decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host", hotwords_file="",
-               hotwords_score=1.5, hotwords=None, token_scores=False):
+               hotwords_score=1.5, hotwords=None, token_scores=False, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -86,7 +86,7 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
       decoding_method (str), max_active_paths (int), blank_penalty (float): the keywords of
         `sherpa_onnx.OfflineRecognizer.from_transducer` with its defaults.  "greedy_search" is what the reference passes (:81);
         "modified_beam_search" keeps `max_active_paths` (1..8, default 4) hypotheses per utterance (rs_rnnt_mbs,
-        csrc/k_rnnt_mbs.hip: no LM).  Valid with every `precision` / `compute`; anything else raises ValueError.
+        csrc/k_rnnt_mbs.hip).  Valid with every `precision` / `compute`; anything else raises ValueError.
       hotwords_file (str), hotwords_score (float): sherpa-onnx's contextual biasing, its names and defaults ("" / 1.5): a file with one
         phrase per line (blank lines ignored, an optional trailing ` :<float>` = the phrase's own score), every character looked up
         in tokens.txt; a phrase with a character that is no token is skipped with a warning.  The modified beam search then adds
@@ -94,6 +94,15 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
         (rs_rnnt_mbs_hotwords, runtime/k2_hotwords.py).  `hotwords` = the same as an in-memory list (strings, or sequences of token
         ids).  The graph is built and uploaded once, here; `create_stream(hotwords=...)` / `transcribe(..., hotwords=...)` replace it
         per utterance.  With "greedy_search" non-empty hotwords raise ValueError, as upstream refuses them.
+      ngram_lm_model (str or NgramLm), ngram_lm_alpha (float), ngram_lm_tokens (str): shallow fusion of a backoff n-gram language
+        model of the user's own text into the modified beam search, the slot of icefall's modified_beam_search_lm_shallow_fusion
+        ([UPSTREAM, UNVERIFIED]; sherpa-onnx's `lm=` is a neural LM and is not offered): an ARPA text file (`.gz` allowed; a KenLM
+        binary raises ValueError) or an `NgramLm` built by runtime/ngram_lm.py.  A candidate that survives a frame's top-K selection
+        and appends a token gets `ngram_lm_alpha` x the LM's natural-log probability of that token after the hypothesis's tokens
+        (include/rs_asr.h rs_rnnt_mbs_lm); no end-of-sentence term.  `ngram_lm_tokens`: "pieces" (default) = the words of the file
+        are the symbols of tokens.txt as written there, "ids" = decimal ids; "nemo" and anything else raise ValueError, as do an
+        alpha that is no finite number >= 0 and an LM with "greedy_search".  Stored as `model.ngram_lm` / `model.ngram_lm_alpha`,
+        both may be set later; `transcribe(..., ngram_lm_alpha=)` takes a weight for one call.
       resample (str): where `transcribe` / `transcribe_batch` normalise input at another rate than 16 kHz or with several channels
         (`norm_audio`): "host" (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count)
         group of a call (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`;
@@ -114,11 +123,15 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     from ...runtime.resample import check_mode
     check_mode(resample)
     from .model import search_config
-    search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords)
+    search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
+                  ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+    if isinstance(ngram_lm_model, (str, os.PathLike)) and ngram_lm_model and not os.path.isfile(ngram_lm_model):
+        raise FileNotFoundError(f"ngram_lm_model {str(ngram_lm_model)!r} does not exist")
     if hotwords_file and not os.path.isfile(hotwords_file):
         raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
     search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample,
-                  hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords, token_scores=token_scores)
+                  hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords, token_scores=token_scores,
+                  ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):

@@ -12,7 +12,7 @@ import re
 
 import numpy as np
 
-from ...runtime import k2_hotwords
+from ...runtime import k2_hotwords, ngram_lm as ngram
 from ...runtime.model import AsrModel
 
 _BYTE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
@@ -68,10 +68,11 @@ DECODING_METHODS = ("greedy_search", "modified_beam_search")      # sherpa-onnx'
 
 
 def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, hotwords_file="", hotwords_score=1.5,
-                  hotwords=None):
+                  hotwords=None, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
     """`cfg` with the search sherpa_onnx.OfflineRecognizer.from_transducer's keywords ask for (its names and defaults);
     ValueError for anything it does not have or this package does not run.  Needs no GPU.  The hotwords keywords are checked
-    here (upstream refuses them with greedy_search too); the graph itself is the model's, not the configuration's."""
+    here (upstream refuses them with greedy_search too); the graph itself is the model's, not the configuration's.  So are the
+    n-gram LM keywords (runtime/ngram_lm.py: k2_check_keywords): an LM with greedy_search raises."""
     has_hotwords = bool(hotwords_file) or (hotwords is not None and len(hotwords) > 0)
     if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
         raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
@@ -79,6 +80,7 @@ def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blan
         raise ValueError("hotwords need decoding_method='modified_beam_search' (greedy_search has no hypotheses to bias)")
     if decoding_method not in DECODING_METHODS:
         raise ValueError(f"decoding_method must be 'greedy_search' or 'modified_beam_search', not {decoding_method!r}")
+    ngram.k2_check_keywords(decoding_method, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
     if not float(blank_penalty) >= 0.0:
         raise ValueError(f"blank_penalty must be >= 0, not {blank_penalty!r}")
     if decoding_method == "greedy_search":
@@ -100,8 +102,15 @@ def stream_graphs(model_graph, streams):
 class K2Model:
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
                  decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host",
-                 hotwords_file="", hotwords_score=1.5, hotwords=None, token_scores=False):
-        """token_scores: `stream.result.token_log_probs` (and `.token_ids`) are filled: the log-probability of every token under the
+                 hotwords_file="", hotwords_score=1.5, hotwords=None, token_scores=False, ngram_lm_model=None, ngram_lm_alpha=0.0,
+                 ngram_lm_tokens="pieces"):
+        """ngram_lm_model / ngram_lm_alpha / ngram_lm_tokens: shallow fusion of a backoff n-gram language model into the modified beam
+        search (include/rs_asr.h rs_rnnt_mbs_lm: the LM term is added to the K survivors of a frame, after the selection): an ARPA
+        text file (`.gz` allowed) or an `NgramLm` of runtime/ngram_lm.py, its weight, and how a word of the file names a token:
+        "pieces" (default) = the symbols of tokens.txt as written there, "ids" = decimal ids; "nemo" raises ValueError.  Stored as
+        `model.ngram_lm` / `model.ngram_lm_alpha`, both settable; alpha 0 = the search without the LM.  With greedy_search an LM
+        raises ValueError.  The table is checked (rs_ngram_check) and uploaded once, here.
+        token_scores: `stream.result.token_log_probs` (and `.token_ids`) are filled: the log-probability of every token under the
         model's own distribution (no blank penalty, no hotword bonus), computed on the device right after the search
         (rs_rnnt_token_scores); valid with every precision and decoding method.  Stored as `model.token_scores`, may be changed later.
         hotwords_file / hotwords_score: sherpa-onnx's keywords and defaults (contextual biasing of the modified beam search:
@@ -121,7 +130,8 @@ class K2Model:
         pos_cap: rows of relative positions the resident position tables start with (|rel| < pos_cap; None = the runtime's default);
         a longer utterance grows them (AsrModel.ensure_pos_cap), so this only moves the first growth"""
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
-        cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords)
+        cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
+                            ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
         self.cfg = cfg
         self.tokens = list(tokens)
         self.hotwords_score = float(hotwords_score)
@@ -132,6 +142,9 @@ class K2Model:
         self.device = self.am.device
         if self.hotwords is not None:
             self.am.hotword_set((self.hotwords,))         # checked and uploaded once, at load
+        self.ngram_lm_alpha = ngram_lm_alpha
+        if ngram.k2_has_lm(ngram_lm_model):
+            self.ngram_lm = ngram.k2_model_lm(cfg, self.tokens, ngram_lm_model, ngram_lm_tokens)
 
     def hotword_graph(self, hotwords, hotwords_file=""):
         """a hotwords argument (a string of phrases separated by `/`, or a list; each phrase with an optional ` :score`) -> its
@@ -164,6 +177,26 @@ class K2Model:
     def token_scores(self, value):
         self.am.token_scores = bool(value)
 
+    # the model's n-gram LM (an NgramLm, None = no fusion) and its weight: the runtime model's, settable
+    @property
+    def ngram_lm(self):
+        return self.am.ngram_lm
+
+    @ngram_lm.setter
+    def ngram_lm(self, lm):
+        if lm is not None:
+            lm = ngram.k2_model_lm(self.cfg, self.tokens, lm)
+            self.am.ngram_set(lm)                         # checked (rs_ngram_check) and uploaded once, found again by NgramLm.key
+        self.am.ngram_lm = lm
+
+    @property
+    def ngram_lm_alpha(self):
+        return self.am.ngram_lm_alpha
+
+    @ngram_lm_alpha.setter
+    def ngram_lm_alpha(self, alpha):
+        self.am.ngram_lm_alpha = ngram.check_alpha(alpha)
+
     # ---- sherpa-onnx's surface ------------------------------------------------------------------------------------------
     def create_stream(self, hotwords=None):
         """hotwords: sherpa-onnx's per-stream hotwords — a string of phrases separated by `/` (or a list), each with an optional
@@ -173,11 +206,13 @@ class K2Model:
     def decode_stream(self, stream):
         self.decode_streams([stream])
 
-    def decode_streams(self, streams):
+    def decode_streams(self, streams, ngram_lm_alpha=None):
+        """ngram_lm_alpha: the weight of the model's n-gram LM in this call (None = `model.ngram_lm_alpha`, 0 = without the LM)"""
+        lm = None if ngram_lm_alpha is None else ngram.k2_call_alpha(self, ngram_lm_alpha)
         for st in streams:
             if st.sample_rate != self.cfg.sample_rate:
                 raise ValueError(f"sample rate {st.sample_rate}: the model expects {self.cfg.sample_rate} Hz (sherpa-onnx resamples; resample with norm_audio first)")
-        res = self.am.transcribe_waveforms([st.samples for st in streams], hotwords=stream_graphs(self.hotwords, streams))
+        res = self.am.transcribe_waveforms([st.samples for st in streams], hotwords=stream_graphs(self.hotwords, streams), ngram_lm=lm)
         for k, (st, ids, frames) in enumerate(zip(streams, res.ids, res.frames)):
             st.result = self.convert(ids, frames, res.token_logprobs[k] if res.token_logprobs is not None else None)
 

@@ -70,7 +70,7 @@ def _streams(model, audios, hotwords):
     return streams
 
 
-def transcribe(model, audio, config=None, hotwords=None):
+def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None):
     """Inference audio data using the K2 model (transcribe.py:10-45).
 
     Args:
@@ -79,6 +79,8 @@ def transcribe(model, audio, config=None, hotwords=None):
         config (TranscribeConfig): Additional settings
         hotwords: phrases to favour in this call INSTEAD OF the model's (`create_stream(hotwords=...)`): a string of phrases
             separated by `/`, or a list of phrases, each with an optional ` :score`; None = the model's hotwords, if any
+        ngram_lm_alpha: the weight of the model's n-gram LM in this call: None = `model.ngram_lm_alpha`, 0 = this call without the
+            LM; a value while the model has no LM raises ValueError
 
     Returns:
         TranscribeResult
@@ -90,7 +92,10 @@ def transcribe(model, audio, config=None, hotwords=None):
         config = TranscribeConfig()
     audio = _prepare_batch(model, [audio])[0]
     stream = _streams(model, [audio], None if hotwords is None else [hotwords])[0]
-    model.decode_stream(stream)
+    if ngram_lm_alpha is None:
+        model.decode_stream(stream)                       # (the reference's call)
+    else:
+        model.decode_streams([stream], ngram_lm_alpha=ngram_lm_alpha)
     return _result(stream)
 
 
@@ -99,7 +104,8 @@ def transcribe_batch(model, audios, config=None, hotwords=None):
     `transcribe` (every kernel masks by the utterance's own length).  The search (greedy or modified beam search) is the one the
     model was built with (`load_model(decoding_method=...)`).  `hotwords`: None (the model's, if any), one string of phrases
     separated by `/` for all audios, or a list with one entry per audio (None / a string / a list of phrases): every utterance is
-    biased by its own graph inside the one batch."""
+    biased by its own graph inside the one batch.  A model loaded with an n-gram LM decodes every batch with `model.ngram_lm` at
+    `model.ngram_lm_alpha`; the per-call weight is on `transcribe` only."""
     streams = _streams(model, _prepare_batch(model, audios), hotwords)
     model.decode_streams(streams)
     return [_result(st) for st in streams]

@@ -36,6 +36,7 @@ EXPORTS = [
     "rs_rnnt_mbs_hotwords", "rs_rnnt_mbs_hotwords_workspace_bytes", "rs_hotwords_check",
     "rs_rnnt_alsd_hotwords", "rs_rnnt_alsd_hotwords_workspace_bytes",
     "rs_rnnt_alsd_lm", "rs_rnnt_alsd_lm_workspace_bytes", "rs_ngram_check",
+    "rs_rnnt_mbs_lm", "rs_rnnt_mbs_lm_workspace_bytes",
     "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
@@ -245,7 +246,8 @@ def load():
     mbs = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp]
     lib.rs_rnnt_mbs.argtypes = mbs + tail
     lib.rs_rnnt_mbs_hotwords.argtypes = mbs + hw_args + tail
-    for fn in (lib.rs_rnnt_mbs_workspace_bytes, lib.rs_rnnt_mbs_hotwords_workspace_bytes):
+    lib.rs_rnnt_mbs_lm.argtypes = mbs + hw_args + [POINTER(RsNgram), c_float] + tail
+    for fn in (lib.rs_rnnt_mbs_workspace_bytes, lib.rs_rnnt_mbs_hotwords_workspace_bytes, lib.rs_rnnt_mbs_lm_workspace_bytes):
         fn.argtypes, fn.restype = [vp, c_int, c_int, c_int, c_int], c_size_t
     lib.rs_hotwords_check.argtypes = [POINTER(RsHotwords), c_char_p, c_size_t]
     lib.rs_rnnt_token_scores_workspace_bytes.argtypes = [vp, c_int, c_int]
@@ -536,26 +538,30 @@ class Context:
                                          int(max_pops), ids.shape[1], _ptr(ids), _ptr(frames) if frames is not None else None, _ptr(n_ids), _ptr(scores), _ptr(pops), _ptr(ws),
                                          ws.numel() * ws.element_size(), c_void_p(stream)))
 
-    def mbs_workspace_bytes(self, B, max_active_paths, tp_max, out_cap, *, hotwords=False):
-        """the workspace of `rnnt_mbs`, called with a hotword set when `hotwords`, from the entry's own query"""
-        name = "rs_rnnt_mbs_hotwords_workspace_bytes" if hotwords else "rs_rnnt_mbs_workspace_bytes"
+    def mbs_workspace_bytes(self, B, max_active_paths, tp_max, out_cap, *, hotwords=False, lm=False):
+        """the workspace of `rnnt_mbs` called with a hotword set (`hotwords`) and / or an n-gram LM (`lm`), from the entry's own query"""
+        name = "rs_rnnt_mbs_lm_workspace_bytes" if lm else "rs_rnnt_mbs_hotwords_workspace_bytes" if hotwords else "rs_rnnt_mbs_workspace_bytes"
         n = getattr(self.lib, name)(self._h, B, max_active_paths, tp_max, out_cap)
         if n == 0:
-            raise RuntimeError(f"{name}: invalid arguments (a Zipformer context, max_active_paths 1..8)")
+            raise RuntimeError(f"{name}: invalid arguments (a {'finalized ' if lm else ''}Zipformer context, max_active_paths 1..8)")
         return n
 
     def rnnt_mbs(self, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, length_norm, ids, frames, n_ids, scores, ws,
-                 stream, *, hotwords=None, graph_of=None):
+                 stream, *, hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
         """sherpa-onnx's modified_beam_search (Zipformer contexts): ids / frames int32 [B][out_cap], n_ids int32 [B], scores
         float32 [B] (log_prob of the winner, not normalised).
         Contextual biasing: `hotwords` = an RsHotwords of device pointers, `graph_of` int32 [B] on the device (-1 = the utterance has
-        no graph); either one passed: rs_rnnt_mbs_hotwords, else rs_rnnt_mbs."""
+        no graph).  N-gram LM after the selection: `lm` = an RsNgram of device pointers, `lm_alpha` its weight (0 = no model).
+        The call goes to the narrowest entry that takes what was passed: rs_rnnt_mbs_lm, rs_rnnt_mbs_hotwords or rs_rnnt_mbs."""
         assert frames.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
         head = (self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
                 MBS_LENGTH_NORM if length_norm else 0, ids.shape[1], _ptr(ids), _ptr(frames), _ptr(n_ids), _ptr(scores))
         tail = (_ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream))
-        if hotwords is not None or graph_of is not None:
-            self.check(self.lib.rs_rnnt_mbs_hotwords(*head, byref(hotwords) if hotwords is not None else None, _ptr(graph_of), *tail))
+        hw = (byref(hotwords) if hotwords is not None else None, _ptr(graph_of))
+        if lm is not None or lm_alpha:
+            self.check(self.lib.rs_rnnt_mbs_lm(*head, *hw, byref(lm) if lm is not None else None, float(lm_alpha), *tail))
+        elif hotwords is not None or graph_of is not None:
+            self.check(self.lib.rs_rnnt_mbs_hotwords(*head, *hw, *tail))
         else:
             self.check(self.lib.rs_rnnt_mbs(*head, *tail))
 

@@ -66,7 +66,7 @@ class _Buffers:
         self.graph_of = torch.full((B,), -1, dtype=i32, device=dev)
         self.h_graph_of = torch.full((B,), -1, dtype=i32).pin_memory()
         self.hw_set = None
-        self.lm = None                  # n-gram LM of the batch (ALSD): (_NgramSet, alpha) or None; `stage` / `fill_host` set it
+        self.lm = None                  # n-gram LM of the batch (ALSD, modified beam search): (_NgramSet, alpha) or None; `stage` / `fill_host` set it
         self.ws_alsd = None              # beam-search scratch (grows with beam and alignment length): on first use
         self.score_bufs = None           # token scores (`AsrModel.score`): (workspace, logp, top1), on first use
         self.ws = torch.empty((ctx.workspace_bytes(B, self.l_pad),), dtype=torch.uint8, device=dev)
@@ -219,8 +219,8 @@ class AsrModel:
         self._hw_sets = {}              # (graph keys) -> _HotwordSet
         self.hotwords = None            # the model's own HotwordGraph (nemo: load_model(hotwords=...)); None = no hotwords
         self.hotwords_score = 1.5
-        self.ngram_lm = None            # the model's NgramLm (nemo: load_model(ngram_lm_model=...)); None = no LM fusion
-        self.ngram_lm_alpha = 0.0       # its weight in the ALSD ranking; both may be set later
+        self.ngram_lm = None            # the model's NgramLm (nemo, k2: load_model(ngram_lm_model=...)); None = no LM fusion
+        self.ngram_lm_alpha = 0.0       # its weight in the search (ALSD, modified beam search); both may be set later
         self._lm_sets = {}              # NgramLm.key -> _NgramSet
         self._dec_lanes = []            # [(context, stream)] of the decode lanes beyond what was needed so far
         self._streams = None
@@ -438,17 +438,18 @@ class AsrModel:
             cfg = cfg.with_(**({"beam_max_pops": int(max_pops)} if max_pops is not None else {}), **({"decoding": decoding} if decoding is not None else {}))
         hw = getattr(buf, "hw_set", None)                  # the batch has at least one graph; graph_of goes with a hotword set only
         hot = dict(hotwords=hw.struct, graph_of=buf.graph_of) if hw is not None else {}
+        lm = getattr(buf, "lm", None)                      # with an n-gram LM and / or graphs in the batch: the LM / HW forms of the search
+        fused = dict(lm=lm[0].struct, lm_alpha=lm[1]) if lm is not None else {}
         if cfg.decoding == "beam":
             sws = self._search_ws(buf, ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops))
             ctx.rnnt_beam(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops,
                           buf.ids, buf.n_ids, buf.scores, buf.pops, sws, stream, frames=buf.frames)
         elif cfg.decoding == "modified_beam_search":      # Zipformer family: sherpa-onnx's second method (csrc/k_rnnt_mbs.hip)
-            sws = self._search_ws(buf, ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1], hotwords=hw is not None))
+            sws = self._search_ws(buf, ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1], hotwords=hw is not None,
+                                                               lm=lm is not None))
             ctx.rnnt_mbs(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
-                         buf.ids, buf.frames, buf.n_ids, buf.scores, sws, stream, **hot)
-        elif cfg.decoding == "alsd":                       # with an n-gram LM and / or graphs in the batch: the LM / HW forms of csrc/k_rnnt_alsd.hip
-            lm = getattr(buf, "lm", None)
-            fused = dict(lm=lm[0].struct, lm_alpha=lm[1]) if lm is not None else {}
+                         buf.ids, buf.frames, buf.n_ids, buf.scores, sws, stream, **hot, **fused)
+        elif cfg.decoding == "alsd":
             sws = self._search_ws(buf, ctx.alsd_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len,
                                                                 hotwords=hw is not None, lm=lm is not None))
             ctx.rnnt_alsd(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len, cfg.beam_score_norm,
@@ -656,7 +657,7 @@ class AsrModel:
         self._hw_sets[key] = hs                           # most recently used last
         return hs
 
-    # ---- n-gram LM (NeMo family: ALSD) ----------------------------------------------------------------------------------------------
+    # ---- n-gram LM (ALSD, modified beam search) -----------------------------------------------------------------------------------------
     def ngram_set(self, lm):
         """the device table of an NgramLm: checked (rs_ngram_check) and uploaded once, then found again by content"""
         ns = self._lm_sets.pop(lm.key, None)
@@ -676,6 +677,10 @@ class AsrModel:
             return None
         if not (np.isfinite(alpha) and alpha > 0):
             raise ValueError(f"ngram_lm_alpha must be a finite number >= 0, not {alpha!r}")
+        if self.cfg.decoding == "modified_beam_search":  # (the k2 package; its greedy_search is refused in its own words)
+            return self.ngram_set(lm), float(alpha)
+        if getattr(self.cfg, "family", None) == "k2":
+            raise ValueError(f"an n-gram LM needs decoding_method='modified_beam_search', not {self.cfg.decoding!r}")
         if self.cfg.decoding != "alsd":
             raise ValueError(f"an n-gram LM needs decoding='alsd', not {self.cfg.decoding!r}")
         return self.ngram_set(lm), float(alpha)
@@ -909,7 +914,7 @@ class AsrModel:
         utterance.  The distinct graphs of the call become one device table (`hotword_set`) and every utterance's graph index
         travels with it through sorting and grouping; a batch without any graph runs the plain search.
 
-        `ngram_lm` (ALSD): None = the model's own n-gram LM and weight (`self.ngram_lm`, `self.ngram_lm_alpha`), or
+        `ngram_lm` (ALSD, modified beam search): None = the model's own n-gram LM and weight (`self.ngram_lm`, `self.ngram_lm_alpha`), or
         (NgramLm or None, alpha) for this call; alpha 0 or no model = the search without an LM (`lm_plan`)."""
         n = len(waveforms)
         if n == 0:

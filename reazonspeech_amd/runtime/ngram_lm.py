@@ -1,5 +1,5 @@
-"""N-gram language models for shallow fusion in the ALSD beam search (rs_rnnt_alsd_lm, csrc/k_rnnt_alsd.hip; the rule is stated in
-include/rs_asr.h): ARPA text -> the flat arrays the device walks (csrc/k_rnnt_ngram.h).  Needs no GPU and nothing beyond numpy.
+"""N-gram language models for shallow fusion in the transducer beam searches — ALSD (rs_rnnt_alsd_lm, csrc/k_rnnt_alsd.hip) and the
+k2 package's modified beam search (rs_rnnt_mbs_lm, csrc/k_rnnt_mbs.hip); the rules are stated in include/rs_asr.h: ARPA text -> the flat arrays the device walks (csrc/k_rnnt_ngram.h).  Needs no GPU and nothing beyond numpy.
 
   read_arpa(path, vocab_size, blank_id, ngram_lm_tokens=, pieces=) -> Ngrams     the file's n-grams over token ids
   build(ngrams, vocab_size, blank_id) -> NgramLm                                 the flat table (natural logarithms, float32)
@@ -13,7 +13,8 @@ How a "word" of the file names a token (`ngram_lm_tokens`):
   "nemo"    one character, chr(id + 100).  [UPSTREAM, not vendored, UNVERIFIED] believed to be what NeMo's
             scripts/asr_language_modeling/ngram_lm/train_kenlm.py writes for BPE models (TOKEN_OFFSET = 100) and what the beam
             search's compute_ngram_score looks up; NeMo is not available to this project, so the encoding is an assumption.
-  "pieces"  the vocabulary's piece strings (tokenizer.ids_to_tokens)
+  "pieces"  the vocabulary's piece strings (tokenizer.ids_to_tokens; k2: the symbols of tokens.txt as written there, which is what an
+            icefall token-level LM is trained on — the k2 package's default)
   "ids"     decimal ids
 `<s>`, `</s>` and `<unk>` are special in all three.  N-grams that contain `</s>` (the search never emits it), that have `<s>`
 anywhere but first, or that hold a word which maps to no id below vocab_size or to the blank are dropped; ONE warning gives the
@@ -313,4 +314,67 @@ def call_alpha(model, ngram_lm_alpha):
         return None, 0.0
     if model.cfg.decoding != "alsd":
         raise ValueError(f"an n-gram LM needs decoding='alsd', not {model.cfg.decoding!r}")
+    return lm, alpha
+
+
+# ---- the keywords of the k2 package -----------------------------------------------------------------------------------------------
+K2_TOKEN_MODES = ("pieces", "ids")
+K2_NEEDS_MBS = "an n-gram LM needs decoding_method='modified_beam_search'"
+
+
+def k2_check_tokens(ngram_lm_tokens):
+    if ngram_lm_tokens == "nemo":
+        raise ValueError("ngram_lm_tokens='nemo' is the NeMo package's word encoding; the k2 package reads 'pieces' (the symbols of tokens.txt) or 'ids'")
+    if ngram_lm_tokens not in K2_TOKEN_MODES:
+        raise ValueError(f"ngram_lm_tokens must be one of {K2_TOKEN_MODES}, not {ngram_lm_tokens!r}")
+    return ngram_lm_tokens
+
+
+def k2_has_lm(ngram_lm_model):
+    return ngram_lm_model is not None and not (isinstance(ngram_lm_model, str) and not ngram_lm_model)
+
+
+def k2_check_keywords(decoding_method, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
+    """the LM keywords of the k2 `load_model` / `K2Model`, checked before anything is loaded -> True when there is an LM.  ValueError
+    for an alpha that is no finite number >= 0, the "nemo" or an unknown token encoding, and an LM with greedy_search (it has no
+    hypotheses to re-rank)."""
+    check_alpha(ngram_lm_alpha)
+    k2_check_tokens(ngram_lm_tokens)
+    has = k2_has_lm(ngram_lm_model)
+    if has and decoding_method != "modified_beam_search":
+        raise ValueError(f"{K2_NEEDS_MBS}, not {decoding_method!r}")
+    return has
+
+
+def k2_model_lm(cfg, tokens, ngram_lm_model, ngram_lm_tokens="pieces"):
+    """`ngram_lm_model` (a path or an NgramLm) -> the NgramLm a k2 model with configuration `cfg` and tokens.txt symbols `tokens`
+    decodes with; the table's n_logits must be the model's"""
+    if cfg.decoding != "modified_beam_search":
+        raise ValueError(f"{K2_NEEDS_MBS}, not {cfg.decoding!r}")
+    if isinstance(ngram_lm_model, NgramLm):
+        if ngram_lm_model.n_logits != cfg.n_logits:
+            raise ValueError(f"the n-gram LM was built for {ngram_lm_model.n_logits} logits, the model has {cfg.n_logits}")
+        return ngram_lm_model
+    k2_check_tokens(ngram_lm_tokens)
+    pieces = None
+    if ngram_lm_tokens == "pieces":
+        # the file's `<unk>` is the model's unknown-word entry, never a token of an n-gram: tokens.txt's own <unk> symbol names no id here
+        pieces = [None if i == cfg.unk_id else p for i, p in enumerate(list(tokens)[:cfg.vocab_size])]
+    return load(ngram_lm_model, cfg.vocab_size, cfg.blank_id, ngram_lm_tokens, pieces, cfg.n_logits)
+
+
+def k2_call_alpha(model, ngram_lm_alpha):
+    """the `ngram_lm_alpha` of the k2 `transcribe` -> (NgramLm or None, alpha) of this call: None = the model's value, 0 = this call
+    without the LM; a value with no LM loaded raises ValueError"""
+    lm = getattr(model, "ngram_lm", None)
+    if ngram_lm_alpha is None:
+        alpha = check_alpha(getattr(model, "ngram_lm_alpha", 0.0), "model.ngram_lm_alpha")
+    else:
+        alpha = check_alpha(ngram_lm_alpha)
+        if lm is None and alpha > 0:
+            raise ValueError("ngram_lm_alpha given, but the model has no n-gram LM (load_model(ngram_lm_model=...))")
+    if lm is None or alpha == 0.0:
+        return None, 0.0
+    if model.cfg.decoding != "modified_beam_search":
+        raise ValueError(f"{K2_NEEDS_MBS}, not {model.cfg.decoding!r}")
     return lm, alpha
