@@ -522,6 +522,32 @@ int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
                  int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- n-best lists from the default beam search — added within ABI 7 (probe the symbols) ------------------------------------------
+ * replaces: `nbest=` of espnet2's Speech2Text, i.e. BeamSearchTransducer's `sort_nbest(kept_hyps)[:nbest]` at the end of the search,
+ * which rs_rnnt_beam runs with nbest = 1.  The search is rs_rnnt_beam; what changes is what is read back after the last frame, inside
+ * the step kernel — no further launch, no host round trip.
+ * RANKING RULE, upstream's restated exactly.  The candidates are ALL hypotheses kept after the last frame — the survivors, at least
+ * `beam` of them, in the kept list's order (ascending by score, ties in the order they were kept: oracle/espnet_beam.c).  They are
+ * sorted by norm = score / len(yseq) with RS_BEAM_SCORE_NORM (yseq counts the leading blank; one float32 division), else by
+ * norm = score, DESCENDING AND STABLE IN THE ORDER OF THE KEPT LIST, as Python's sorted(..., reverse=True) is: rank r is the first
+ * maximum among those not yet ranked.  EQUAL LABEL SEQUENCES ARE NOT REMOVED, because upstream does not remove them (the same
+ * labels reached along two alignments are two hypotheses of the kept list).  Entry 0 is bit for bit what rs_rnnt_beam returns.
+ *   nbest             1..8 and <= beam (after the clamp to the vocabulary)
+ *   ids / frames i32[B][nbest][out_cap]   labels (no leading blank) and the frame each was appended at (frames may be NULL), per entry
+ *   n_ids i32[B][nbest]                   label count of each entry; an entry past n_hyps[b] has n_ids = 0 and is not otherwise specified
+ *   scores f32[B][nbest]                  score (log-probability) of each entry, not normalised
+ *   norm_scores f32[B][nbest]             the norm the entries are ranked by, descending
+ *   n_hyps i32[B]                         nbest; 1 for an utterance without frames (its kept list is the start hypothesis: no labels,
+ *                                         score 0); 0 for an utterance that overflowed max_pops
+ * Workspace: rs_rnnt_beam_nbest_workspace_bytes (that of rs_rnnt_beam: the lists live in the outputs; 0 for invalid arguments or a
+ * context that is not finalized).  Errors as rs_rnnt_beam; RS_EINVAL before anything is enqueued for nbest outside 1..8 or above the
+ * beam; RS_EOVERFLOW if a frame needed more than max_pops pops or any returned entry has more than out_cap labels (that entry
+ * returns n_ids = 0).  Restated by tests/espnet_beam_nbest_checker.c, which the lists equal bit for bit. */
+size_t rs_rnnt_beam_nbest_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, int nbest);
+int rs_rnnt_beam_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags,
+                       int max_pops, int nbest, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                       float* norm_scores, int32_t* n_hyps, int32_t* pops, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- sherpa-onnx's modified_beam_search (Zipformer family) ---------------------------------------
  * replaces: the search inside sherpa_onnx.OfflineRecognizer.from_transducer(..., decoding_method="modified_beam_search",
  * max_active_paths=K) — the second offline transducer method of the constructor the reference builds its recognizer with
@@ -654,6 +680,32 @@ int rs_rnnt_mbs_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens,
                    const rs_hotwords* hw, const int32_t* graph_of, const struct rs_ngram* lm, float lm_alpha, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- n-best lists from the modified beam search — added within ABI 7 (probe the symbols) ----------------------------------------
+ * The project's addition: sherpa-onnx returns one hypothesis per stream and has no n-best option.  The search is rs_rnnt_mbs_lm
+ * (hw, graph_of and lm may each be NULL, lm_alpha may be 0: then the hotword or the plain form runs, as there); what changes is what
+ * is read from the last set, inside the selection kernel of the utterance's last frame — no further launch, no host round trip.
+ * RANKING RULE.  The candidates are the hypotheses of the set the last frame leaves, after merging and after the hotword Finalize,
+ * in the order in which they entered that set.  Each has norm = log_prob / len(ys) with RS_MBS_LENGTH_NORM (len counts the 2
+ * context entries, one float32 division) and norm = log_prob without it.  Rank r holds the candidate with the greatest norm among
+ * those not yet ranked; EQUAL NORMS: THE ONE THAT ENTERED THE LAST SET FIRST — rs_rnnt_mbs's rule and tie rule applied down the
+ * list, so entry 0 is bit for bit what rs_rnnt_mbs / _hotwords / _lm return for the same arguments.  Equal token sequences cannot
+ * occur twice: the set merged them.
+ *   nbest             1..8 and <= max_active_paths
+ *   ids / frames i32[B][nbest][out_cap]   tokens (without the context) and the encoder frame of each, per entry
+ *   n_ids i32[B][nbest]                   token count of each entry; an entry past n_hyps[b] has n_ids = 0 and is not otherwise specified
+ *   scores f32[B][nbest]                  log_prob of each entry, not normalised, after Finalize (what scores[b] of rs_rnnt_mbs_lm carries)
+ *   norm_scores f32[B][nbest]             the norm the entries are ranked by, descending
+ *   n_hyps i32[B]                         min(nbest, size of the last set); 0 for an utterance without frames
+ * Workspace: rs_rnnt_mbs_nbest_workspace_bytes (the layout of rs_rnnt_mbs_lm: the lists live in the outputs; 0 for invalid arguments
+ * or a context that is not finalized).  Errors as rs_rnnt_mbs_lm; RS_EINVAL before anything is enqueued for nbest outside 1..8 or
+ * above max_active_paths; RS_EOVERFLOW if any returned entry has more than out_cap tokens.  Restated by
+ * tests/k2_mbs_nbest_checker.c, which the lists equal bit for bit. */
+size_t rs_rnnt_mbs_nbest_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap, int nbest);
+int rs_rnnt_mbs_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                      float blank_penalty, int flags, int nbest, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids,
+                      float* scores, float* norm_scores, int32_t* n_hyps, const rs_hotwords* hw, const int32_t* graph_of,
+                      const struct rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- hotwords (contextual biasing) in the ALSD beam search — added within ABI 7 ---------------------
  * gives the LSTM transducers (the NeMo family: FastConformer-RNNT, whose checkpoint ships `strategy: alsd`) what
  * rs_rnnt_mbs_hotwords gives the Zipformer family.  [UPSTREAM] NeMo's align_length_sync_decoding has no hotword rule: the
@@ -753,6 +805,40 @@ int rs_rnnt_alsd_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens
                     double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
                     int32_t* n_ids, float* scores, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
                     float lm_alpha, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- n-best lists from the ALSD beam search — added within ABI 7 (probe the symbols) ---------------------------------------------
+ * replaces: NeMo's beam decoding with `return_best_hypothesis=False` (NBestHypotheses), i.e. `sort_nbest(final)` at the end of
+ * align_length_sync_decoding, with equal label sequences removed.  The search is rs_rnnt_alsd_lm (hw, graph_of and lm may each be
+ * NULL, lm_alpha may be 0: then the hotword or the plain form runs, as there); in place of the single best finished hypothesis the
+ * selection kernel keeps `nbest` ranked ones per utterance during the search — no further launch, no host round trip.
+ * RANKING RULE.  Entry condition, score and norm are exactly rs_rnnt_alsd's: a blank taken at the utterance's last frame finishes a
+ * hypothesis; its score is read after this step's recombination; under hotwords the value is sc + (-node_score(state)) (Finalize);
+ * norm = sc / (n + 1) with RS_ALSD_SCORE_NORM (n labels; one float32 division), else norm = sc.  A candidate ENTERS BELOW EVERY
+ * ENTRY WHOSE NORM IS >= ITS OWN, so the earlier-finished one wins ties, as rs_rnnt_alsd's strict `>` does; a full list drops its
+ * last entry.  THE LIST HOLDS EACH LABEL SEQUENCE AT MOST ONCE: equal sequences can only finish in the same alignment step
+ * (i = T - 1 + n), which happens when RS_ALSD_MERGE is off and recombined duplicates stay in the beam; of those the one with the
+ * greater norm is kept, and the one considered first (the lower beam slot) on a tie.  The list is therefore NeMo's
+ * sort_nbest(final)[:nbest] with duplicates removed, and entry 0 is bit for bit what rs_rnnt_alsd / _hotwords / _lm return.
+ * When nothing finished (alignment budget spent, or no frames), the list is the beam's entries under the same ranking and
+ * de-duplication, each after Finalize — rs_rnnt_alsd's exit already ranks them.
+ *   nbest             1..8 and <= beam (after the clamp to the vocabulary)
+ *   ids / steps i32[B][nbest][out_cap]    labels and the alignment step of each, per entry
+ *   n_ids i32[B][nbest]                   label count of each entry; an entry past n_hyps[b] has n_ids = 0 and is not otherwise specified
+ *   scores f32[B][nbest]                  the score of each entry, not normalised, after Finalize (what scores[b] of rs_rnnt_alsd_lm carries)
+ *   norm_scores f32[B][nbest]             the norm the entries are ranked by, descending
+ *   n_hyps i32[B]                         entries valid for utterance b, 1..nbest (an utterance without frames: 1, the empty start hypothesis)
+ * Labels move at most once per insertion: a slot table with an order array (the ranks hold slot numbers); one wave does the insert
+ * with the label copy spread over its lanes.  Workspace: rs_rnnt_alsd_nbest_workspace_bytes (the layout of rs_rnnt_alsd_lm plus
+ * 8 label slots per utterance; 0 for invalid arguments or a context that is not finalized).  Errors as rs_rnnt_alsd_lm; RS_EINVAL
+ * before anything is enqueued for nbest outside 1..8 or above the beam; RS_EOVERFLOW if any returned entry has more than out_cap
+ * labels.  Restated by tests/alsd_nbest_checker.c, which the lists equal bit for bit. */
+size_t rs_rnnt_alsd_nbest_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs,
+                                          int nbest);
+int rs_rnnt_alsd_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
+                       double max_target_ratio, int max_target_abs, int flags, int nbest, int out_cap, int32_t* ids, int32_t* steps,
+                       int32_t* n_ids, float* scores, float* norm_scores, int32_t* n_hyps, const rs_hotwords* hw,
+                       const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* ---- token log-probabilities of a finished transducer search — added within ABI 7 ----------------
  * gives what NeMo's Hypothesis.token_confidence (preserve_token_confidence, method max_prob), sherpa-onnx's per-token log-probs

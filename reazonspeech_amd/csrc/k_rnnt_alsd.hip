@@ -68,7 +68,100 @@ struct AlsdState {
     int32_t* fin_al;     // [B][cap]
     int32_t* done;       // [B]
     int cap;
+    // n-best (rs_rnnt_alsd_nbest, nbest >= 1; otherwise nbest == 0 and every pointer below is null): the ranked list of finished
+    // hypotheses that stands in place of the single fin_* record.  A slot table with an order array: labels live in slots and are
+    // written once per insertion, the ranks only move slot numbers.
+    int nbest;
+    int32_t* nb_n;       // [B] entries in the list
+    int32_t* nb_slot;    // [B][MAX_BEAM] slot of rank r
+    float* nb_norm;      // [B][MAX_BEAM] by rank
+    float* nb_score;     // [B][MAX_BEAM] by rank
+    int32_t* nb_len;     // [B][MAX_BEAM] by rank
+    int32_t* nb_y;       // [B][MAX_BEAM][cap] by slot
+    int32_t* nb_al;      // [B][MAX_BEAM][cap] by slot
+    float* out_norm;     // [B][nbest] the caller's norm_scores
+    int32_t* out_nhyps;  // [B] the caller's n_hyps
 };
+
+// ---- the ranked list in registers of wave 0 (every lane holds the same values): ranks 0 .. n - 1, best first -------------------
+// RULE (include/rs_asr.h rs_rnnt_alsd_nbest): a candidate enters below every entry whose norm is >= its own (earlier-finished wins
+// ties, as the single record's strict `>` does); the list holds a label sequence at most once — equal sequences can only finish in the
+// same alignment step (i = T - 1 + n), so a candidate is compared with the entries that entered in THIS step only (`src`: their beam
+// row, whose labels are still in as.y[p]); of two equal ones the greater norm stays, the first on a tie; a full list drops its tail.
+struct AlsdList {
+    int n;
+    int slot[MAX_BEAM], len[MAX_BEAM], src[MAX_BEAM];
+    float norm[MAX_BEAM], score[MAX_BEAM];
+};
+
+__device__ __forceinline__ void alsd_list_load(const AlsdState& as, int b, AlsdList& l) {
+    l.n = as.nb_n[b];
+#pragma unroll
+    for (int r = 0; r < MAX_BEAM; ++r) {
+        const bool in = r < l.n;
+        l.slot[r] = in ? as.nb_slot[b * MAX_BEAM + r] : 0; l.len[r] = in ? as.nb_len[b * MAX_BEAM + r] : 0; l.src[r] = -1;
+        l.norm[r] = in ? as.nb_norm[b * MAX_BEAM + r] : 0.0f; l.score[r] = in ? as.nb_score[b * MAX_BEAM + r] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ void alsd_list_store(const AlsdState& as, int b, const AlsdList& l) {      // one lane
+    as.nb_n[b] = l.n;
+#pragma unroll
+    for (int r = 0; r < MAX_BEAM; ++r)
+        if (r < l.n) {
+            as.nb_slot[b * MAX_BEAM + r] = l.slot[r]; as.nb_len[b * MAX_BEAM + r] = l.len[r];
+            as.nb_norm[b * MAX_BEAM + r] = l.norm[r]; as.nb_score[b * MAX_BEAM + r] = l.score[r];
+        }
+}
+
+// offer beam row `row` of set p (n labels, score sc after Finalize, norm) to the list; one wave, the label copy spread over its lanes
+__device__ __forceinline__ void alsd_list_offer(const AlsdState& as, int b, int p, AlsdList& l, int row, int n, float sc, float norm, int lane) {
+    const int cap = as.cap;
+    const int32_t* ry = as.y[p] + (size_t)row * cap;
+    int dupr = -1;
+#pragma unroll
+    for (int r = 0; r < MAX_BEAM; ++r) {
+        if (r >= l.n || dupr >= 0 || l.src[r] < 0 || l.len[r] != n) continue;      // (uniform over the wave)
+        const int32_t* oy = as.y[p] + (size_t)l.src[r] * cap;
+        bool differ = false;
+        for (int q = lane; q < n; q += 64) differ = differ || (ry[q] != oy[q]);
+        if (__ballot(differ) == 0ull) dupr = r;
+    }
+    int slot = -1;
+    if (dupr >= 0) {                                       // the same labels finished earlier in this step
+        float dn = 0.0f;
+#pragma unroll
+        for (int r = 0; r < MAX_BEAM; ++r) if (r == dupr) { dn = l.norm[r]; slot = l.slot[r]; }
+        if (!(norm > dn)) return;                          // the first one stays on a tie
+#pragma unroll
+        for (int r = 0; r + 1 < MAX_BEAM; ++r)
+            if (r >= dupr) { l.slot[r] = l.slot[r + 1]; l.len[r] = l.len[r + 1]; l.src[r] = l.src[r + 1]; l.norm[r] = l.norm[r + 1]; l.score[r] = l.score[r + 1]; }
+        l.n -= 1;
+    }
+    int pos = 0;
+#pragma unroll
+    for (int r = 0; r < MAX_BEAM; ++r) pos += (r < l.n && l.norm[r] >= norm) ? 1 : 0;
+    if (pos >= as.nbest) return;                           // a full list of better entries
+    if (slot < 0) {
+        if (l.n == as.nbest) {                             // the tail leaves; its slot takes the newcomer
+#pragma unroll
+            for (int r = 0; r < MAX_BEAM; ++r) if (r == l.n - 1) slot = l.slot[r];
+            l.n -= 1;
+        } else {
+            slot = l.n;                                    // (slots 0 .. n - 1 are the ones in use: a slot is only ever freed to be refilled)
+        }
+    }
+#pragma unroll
+    for (int r = MAX_BEAM - 1; r >= 1; --r)
+        if (r > pos && r <= l.n) { l.slot[r] = l.slot[r - 1]; l.len[r] = l.len[r - 1]; l.src[r] = l.src[r - 1]; l.norm[r] = l.norm[r - 1]; l.score[r] = l.score[r - 1]; }
+#pragma unroll
+    for (int r = 0; r < MAX_BEAM; ++r) if (r == pos) { l.slot[r] = slot; l.len[r] = n; l.src[r] = row; l.norm[r] = norm; l.score[r] = sc; }
+    l.n += 1;
+    int32_t* dy = as.nb_y + ((size_t)b * MAX_BEAM + slot) * cap;
+    int32_t* dal = as.nb_al + ((size_t)b * MAX_BEAM + slot) * cap;
+    const int32_t* ral = as.al[p] + (size_t)row * cap;
+    for (int q = lane; q < n; q += 64) { dy[q] = ry[q]; dal[q] = ral[q]; }
+}
 
 struct AlsdNoHw {};      // the kernel argument of the plain form
 struct AlsdHw {          // hotwords: the graphs of the call and the node each hypothesis row stands at
@@ -104,6 +197,7 @@ __global__ void alsd_init_kernel(DecodeState st, AlsdState as, const int32_t* __
         const int row = b * W;
         as.len[0][row] = 0; as.score[0][row] = 0.0f; as.n_hyp[0][b] = 1;
         as.fin_n[b] = -1; as.fin_norm[b] = 0.0f; as.fin_score[b] = 0.0f; as.done[b] = 0;
+        if (as.nbest > 0) as.nb_n[b] = 0;
         if constexpr (HW) { const int r = alsd_root<LM>(hw, b); hw.ctx[0][row] = r < 0 ? 0 : r; }
         if constexpr (LM) hw.lmctx[0][row] = lm_node(hw.g, hw.g.start);
         st.token[row] = blank; st.tcur[row] = 0; st.act[b] = row;
@@ -123,7 +217,9 @@ __device__ __forceinline__ int cand_len(int parent_len, int tok) { return parent
 // the two memory passes of the NVR = 0 form — identical arithmetic, one memory round trip instead of two chains of 47.
 // HW: the hotword form (see the head of this file); the plain form is the same text without the `if constexpr (HW)` statements.
 // LM: the n-gram form (HW on as well); the other forms are the same text without the `if constexpr (LM)` statements.
-template <int NVR, bool HW, bool LM = false>
+// NB: the n-best form (rs_rnnt_alsd_nbest): the ranked list in place of the fin_* record.  A template parameter, not a run-time
+// branch: the list's registers in the other forms cost the old entries 1.5 % (95.8 against 94.4 ms per 256 x 10 s batch).
+template <int NVR, bool HW, bool LM = false, bool NB = false>
 __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
     DecodeState st, AlsdState as, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int B, int W,
     int V, int blank, int i, double ratio, int abs_len, int score_norm, int merge, int out_cap, int32_t* __restrict__ ids,
@@ -276,6 +372,41 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
 
     if (!s_live) {
         // ---- the search of this utterance is over (alignment budget spent, or every hypothesis is past the last frame)
+        if constexpr (NB) {
+          if (wave == 0) {
+            // the ranked list; nothing finished: the beam's entries under the same ranking and de-duplication
+            AlsdList l;
+            alsd_list_load(as, b, l);
+            if (l.n == 0) {
+                for (int s = 0; s < n_cur; ++s) {
+                    const int row = b * W + s;
+                    const int n = as.len[p][row];
+                    float sc = as.score[p][row];
+                    if constexpr (HW) {
+                        if (root >= 0) sc = sc + (-hw.t.g.node_score[hw_node(hw.t.g, hw.ctx[p][row], root)]);      // Finalize
+                    }
+                    const float norm = score_norm ? sc / (float)(n + 1) : sc;
+                    alsd_list_offer(as, b, p, l, row, n, sc, norm, lane);
+                }
+            }
+            const int nbest = as.nbest;
+            for (int r = 0; r < nbest; ++r) {
+                const size_t e = (size_t)b * nbest + r;
+                if (r >= l.n) { if (lane == 0) n_ids[e] = 0; continue; }
+                int slot = 0, n = 0;
+                float sc = 0.0f, norm = 0.0f;
+#pragma unroll
+                for (int k = 0; k < MAX_BEAM; ++k) if (k == r) { slot = l.slot[k]; n = l.len[k]; sc = l.score[k]; norm = l.norm[k]; }
+                if (n > out_cap) { n = out_cap; if (lane == 0) st.counters[1] = 1; }
+                const int32_t* sy = as.nb_y + ((size_t)b * MAX_BEAM + slot) * cap;       // (a lane reads back the positions it wrote)
+                const int32_t* sal = as.nb_al + ((size_t)b * MAX_BEAM + slot) * cap;
+                for (int q = lane; q < n; q += 64) { ids[e * out_cap + q] = sy[q]; steps[e * out_cap + q] = sal[q]; }
+                if (lane == 0) { n_ids[e] = n; scores[e] = sc; as.out_norm[e] = norm; }
+            }
+            if (lane == 0) { as.out_nhyps[b] = l.n; as.done[b] = 1; atomicAdd(&st.counters[4], 1); }
+          }
+          return;
+        }
         if (wave == 0) {
             int src_n = as.fin_n[b];
             float src_score = as.fin_score[b];
@@ -361,6 +492,8 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             }
         }
         // finished hypotheses: a blank taken at the last frame; the score is read after recombination
+        [[maybe_unused]] AlsdList nl;
+        if constexpr (NB) alsd_list_load(as, b, nl);
         int fn = as.fin_n[b];
         float fnorm = as.fin_norm[b], fscore = as.fin_score[b];
         for (int s = 0; s < n_cur; ++s) {
@@ -376,6 +509,7 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
                 if (root >= 0) sc = sc + (-hw.t.g.node_score[hw_node(hw.t.g, c_state[c], root)]);                  // Finalize
             }
             const float norm = score_norm ? sc / (float)(n + 1) : sc;
+            if constexpr (NB) { alsd_list_offer(as, b, p, nl, row, n, sc, norm, lane); continue; }      // the list in place of the record
             if (fn < 0 || norm > fnorm) {
                 fn = n; fnorm = norm; fscore = sc;
                 for (int q = lane; q < n; q += 64) {
@@ -385,6 +519,7 @@ __global__ __launch_bounds__(64 * MAX_BEAM) void alsd_select_kernel(
             }
         }
         if (lane == 0) { as.fin_n[b] = fn; as.fin_norm[b] = fnorm; as.fin_score[b] = fscore; }
+        if constexpr (NB) { if (lane == 0) alsd_list_store(as, b, nl); }
         // the new beam, in selection order ("merge" drops the duplicates)
         int nk = 0;
 #pragma unroll
@@ -450,8 +585,8 @@ __global__ __launch_bounds__(256) void alsd_reorder_kernel(AlsdState as, int pn,
 
 // the search's layout: two ping-pong sets of the prediction-network state (st[k].h / .c / .g; everything else of st[0] and st[1] is
 // shared) and the hypothesis store
-void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, bool lm, rs_arena& a, DecodeState st[2], AlsdState& as, int32_t* hw_ctx[2],
-                 int32_t* lm_ctx[2]) {
+void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, bool lm, int nbest, rs_arena& a, DecodeState st[2], AlsdState& as,
+                 int32_t* hw_ctx[2], int32_t* lm_ctx[2]) {
     const rs_dims& d = ctx->d;
     const size_t rows = (size_t)B * W, state = (size_t)d.pred_layers * rows * d.pred_hidden, J = d.joint_hidden;
     DecodeState q{};
@@ -478,6 +613,15 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, bool l
     if (hotwords) { hw_ctx[0] = a.take<int32_t>(rows); hw_ctx[1] = a.take<int32_t>(rows); }       // (last: the plain layout is a prefix)
     lm_ctx[0] = lm_ctx[1] = nullptr;
     if (lm) { lm_ctx[0] = a.take<int32_t>(rows); lm_ctx[1] = a.take<int32_t>(rows); }             // (after them: the hotword layout is a prefix)
+    as.nbest = nbest;                                                                             // (last of all: every other layout is a prefix)
+    as.nb_n = as.nb_slot = as.nb_len = as.nb_y = as.nb_al = as.out_nhyps = nullptr;
+    as.nb_norm = as.nb_score = as.out_norm = nullptr;
+    if (nbest > 0) {
+        const size_t e = (size_t)B * MAX_BEAM;
+        as.nb_n = a.take<int32_t>(B); as.nb_slot = a.take<int32_t>(e); as.nb_len = a.take<int32_t>(e);
+        as.nb_norm = a.take<float>(e); as.nb_score = a.take<float>(e);
+        as.nb_y = a.take<int32_t>(e * cap); as.nb_al = a.take<int32_t>(e * cap);
+    }
     as.cap = cap;
     st[0] = st[1] = q;
     st[1].h = h1; st[1].c = c1; st[1].g = g1;
@@ -485,20 +629,20 @@ void alsd_layout(const rs_ctx* ctx, int B, int W, int cap, bool hotwords, bool l
 
 }  // namespace
 
-size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm) {
+size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm, int nbest) {
     if (B <= 0 || beam <= 0 || cap <= 0) return 0;
     rs_arena a;
     DecodeState st[2];
     AlsdState as;
     int32_t *hw_ctx[2], *lm_ctx[2];
-    alsd_layout(ctx, B, beam, cap, hotwords || lm, lm, a, st, as, hw_ctx, lm_ctx);
+    alsd_layout(ctx, B, beam, cap, hotwords || lm, lm, nbest, a, st, as, hw_ctx, lm_ctx);
     return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
-                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
-                      void* workspace, size_t workspace_bytes, hipStream_t s) {
+                      float* scores, int nbest, float* norm_scores, int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of,
+                      const rs_ngram* ngram, float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
@@ -515,7 +659,8 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     AlsdHwLm hw{};
     if (HWF) { hw.t.g = *hotwords; hw.t.graph_of = graph_of; }
     if (LMF) { hw.g = *ngram; hw.alpha = lm_alpha; }
-    alsd_layout(ctx, B, W, cap, HWF || LMF, LMF, arena, st, as, hw.ctx, hw.lmctx);
+    alsd_layout(ctx, B, W, cap, HWF || LMF, LMF, nbest, arena, st, as, hw.ctx, hw.lmctx);
+    as.out_norm = norm_scores; as.out_nhyps = n_hyps;
     const AlsdHw& hw_only = hw;                                                                 // the hotword form's argument
     if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
         return rs_fail(ctx, RS_EWORKSPACE, "alsd: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
@@ -527,6 +672,10 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     const auto select = V <= 64 * 48 ? alsd_select_kernel<48, false> : alsd_select_kernel<0, false>;   // (48: the logits row fits a lane's registers)
     const auto select_hw = V <= 64 * 48 ? alsd_select_kernel<48, true> : alsd_select_kernel<0, true>;  // the hotword form takes the graphs last
     const auto select_lm = V <= 64 * 48 ? alsd_select_kernel<48, true, true> : alsd_select_kernel<0, true, true>;   // the LM form: graphs and model
+    // the n-best forms of the three (rs_rnnt_alsd_nbest)
+    const auto select_nb = V <= 64 * 48 ? alsd_select_kernel<48, false, false, true> : alsd_select_kernel<0, false, false, true>;
+    const auto select_hw_nb = V <= 64 * 48 ? alsd_select_kernel<48, true, false, true> : alsd_select_kernel<0, true, false, true>;
+    const auto select_lm_nb = V <= 64 * 48 ? alsd_select_kernel<48, true, true, true> : alsd_select_kernel<0, true, true, true>;
     const auto init_lm = alsd_init_kernel<true, true>;
     const auto init_hw = alsd_init_kernel<true>;
     const auto init = alsd_init_kernel<false>;
@@ -564,6 +713,11 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
         if (hc[1]) return rs_fail(ctx, RS_EOVERFLOW, "alsd: a hypothesis has more than out_cap=%d labels", out_cap);
         return RS_OK;
     };
+    if (nbest > 0) {
+        if (LMF) return search(init_lm, select_lm_nb, hw);
+        if (HWF) return search(init_hw, select_hw_nb, hw_only);
+        return search(init, select_nb, AlsdNoHw{});
+    }
     if (LMF) return search(init_lm, select_lm, hw);
     if (HWF) return search(init_hw, select_hw, hw_only);
     return search(init, select, AlsdNoHw{});

@@ -94,7 +94,8 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // grid ceil(B / 256)
 __global__ __launch_bounds__(256) void beam_init_kernel(BeamState bs, const int32_t* __restrict__ enc_lens, int B, int blank,
                                                         int32_t* __restrict__ n_ids, float* __restrict__ scores,
-                                                        int32_t* __restrict__ pops) {
+                                                        int32_t* __restrict__ pops, int nbest, float* __restrict__ norm_scores,
+                                                        int32_t* __restrict__ n_hyps) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     bs.t[b] = 0; bs.nk[b] = 0; bs.npop[b] = 0; bs.pops[b] = 0; bs.ninit[b] = 0; bs.nb[b] = 0; bs.nrec[b] = bs.R; bs.npark[b] = 0;
@@ -106,8 +107,14 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamState bs, const int3
     bs.h_score[h0] = 0.0f; bs.h_node[h0] = -1; bs.h_tok[h0] = blank; bs.h_slot[h0] = 0; bs.h_len[h0] = 1; bs.h_alive[h0] = 1;
     bs.h_rec[h0] = -1;
     bs.nh[b] = 1;
-    n_ids[b] = 0; scores[b] = 0.0f; pops[b] = 0;
     const int fin = enc_lens[b] <= 0;            // nothing to search: the empty hypothesis, score 0
+    pops[b] = 0;
+    if (nbest > 0) {                             // rs_rnnt_beam_nbest: [B][nbest] lists; without frames the kept list is the start hypothesis alone
+        for (int r = 0; r < nbest; ++r) { n_ids[(size_t)b * nbest + r] = 0; scores[(size_t)b * nbest + r] = 0.0f; norm_scores[(size_t)b * nbest + r] = 0.0f; }
+        n_hyps[b] = fin;
+    } else {
+        n_ids[b] = 0; scores[b] = 0.0f;
+    }
     bs.done[b] = fin;
     if (fin) atomicAdd(&bs.flags[0], 1);
 }
@@ -438,7 +445,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
                                                         int L, int H, int J, int beam, int score_norm, int out_cap, int iter,
                                                         int32_t* __restrict__ ids, int32_t* __restrict__ frames,
                                                         int32_t* __restrict__ n_ids, float* __restrict__ scores,
-                                                        int32_t* __restrict__ pops) {
+                                                        int32_t* __restrict__ pops, int nbest, float* __restrict__ norm_scores,
+                                                        int32_t* __restrict__ n_hyps) {
     extern __shared__ __attribute__((aligned(16))) char beam_smem[];
     const int MP = bs.max_pops, R = bs.R, KS = bs.KS, RP = bs.RP, RF = bs.rec_floats, K = bs.beam_k;
     float* lsc = reinterpret_cast<float*>(beam_smem);
@@ -605,8 +613,51 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
         BEAM_MARK(5)
         return;
     }
-    // ---- last frame: the first maximum of score / len(yseq) (or of score) over the survivors in their order ----
     int dummy;
+    if (nbest > 0) {
+        // ---- last frame, rs_rnnt_beam_nbest: upstream's sort_nbest(kept_hyps)[:nbest] — the survivors in their order, sorted by
+        // score / len(yseq) (or by score) descending and stable: rank r is the first maximum among those not yet ranked (rank 0 is
+        // the winner below).  Equal label sequences stay.  Thread r then reads entry r back through the label trie. ----
+        __shared__ int s_pick[8];
+        __shared__ float s_pnorm[8];
+        int nh_out = 0;
+        par ^= 1;
+        for (int r = 0; r < nbest; ++r, par ^= 1) {
+            list_argmax_count<false>(lsc, lrec, n_good, ks, 0, 1, &sc, par, hm, bi, dummy);
+            if (bi < 0) break;                                       // (nbest <= beam <= survivors: does not happen)
+            if (tid == 0) { s_pick[r] = bi; s_pnorm[r] = hm; lsc[bi] = __int_as_float(0x7fc00000); }
+            ++nh_out;
+            lds_barrier();
+        }
+        if (tid < nh_out) {
+            const int pick = s_pick[tid];
+            const size_t e = (size_t)b * nbest + tid;
+            const int n = sl[pick] - 1;
+            scores[e] = __int_as_float(used[pick]);
+            norm_scores[e] = s_pnorm[tid];
+            if (n > out_cap) { n_ids[e] = 0; bs.flags[1] = 1; }
+            else {
+                int node = sn[pick];
+                for (int q = n - 1; q >= 0; --q) {
+                    const int2 nd = bs.nodes[(size_t)b * bs.max_nodes + node];
+                    ids[e * out_cap + q] = nd.y;
+                    if (frames) frames[e * out_cap + q] = bs.node_frame[(size_t)b * bs.max_nodes + node];
+                    node = nd.x;
+                }
+                n_ids[e] = n;
+            }
+        }
+        if (tid == 0) {
+            n_hyps[b] = nh_out;
+            pops[b] = bs.pops[b] + pops_add;
+            bs.done[b] = 1;
+            __threadfence();                                         // (the entries above are other threads' stores; the host reads after the stream ends)
+            atomicAdd(&bs.flags[0], 1);
+        }
+        BEAM_MARK(6)
+        return;
+    }
+    // ---- last frame: the first maximum of score / len(yseq) (or of score) over the survivors in their order ----
     list_argmax_count<false>(lsc, lrec, n_good, ks, 0, 1, &sc, par ^ 1, hm, bi, dummy);
     if (tid == 0) {
         const int n = sl[bi] - 1;
@@ -710,8 +761,8 @@ size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int
 }
 
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
-                      int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
-                      void* workspace, size_t workspace_bytes, hipStream_t s) {
+                      int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, int nbest,
+                      float* norm_scores, int32_t* n_hyps, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (int rc = rs_rnnt_check_dims(ctx, "beam search"); rc != RS_OK) return rc;
@@ -741,7 +792,8 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     RS_HIP(ctx, hipMemsetAsync(bs.t, 0, pl.zero_bytes, s));
     // slot 0 of every utterance: the zero state the search starts from
     RS_HIP(ctx, hipMemset2DAsync(bs.slots, (size_t)bs.n_slots * bs.slot_floats * 4, 0, (size_t)bs.slot_floats * 4, B, s));
-    hipLaunchKernelGGL(beam_init_kernel, dim3((B + 255) / 256), dim3(256), 0, s, bs, enc_lens, B, d.blank_id, n_ids, scores, pops);
+    hipLaunchKernelGGL(beam_init_kernel, dim3((B + 255) / 256), dim3(256), 0, s, bs, enc_lens, B, d.blank_id, n_ids, scores, pops, nbest,
+                       norm_scores, n_hyps);
     hipLaunchKernelGGL(beam_first_kernel, dim3(B), dim3(256), pl.step_lds, s, bs, st, B, L, H, J);
     RS_CHECK_LAUNCH(ctx, "beam init");
 
@@ -765,7 +817,7 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
             hipLaunchKernelGGL(record, dim3(rec_blocks), dim3(256), pl.rec_lds, s, bs, st, st.zapprox, pl.zstride, pl.rows, rpu, V, d.blank_id,
                                step);
             hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), pl.step_lds, s, bs, st, enc_lens, B, L, H, J, bm, score_norm, out_cap,
-                               step, ids, frames, n_ids, scores, pops);
+                               step, ids, frames, n_ids, scores, pops, nbest, norm_scores, n_hyps);
         }
         RS_CHECK_LAUNCH(ctx, "beam step");
         RS_HIP(ctx, hipMemcpyAsync(hf, bs.flags, sizeof hf, hipMemcpyDeviceToHost, s));

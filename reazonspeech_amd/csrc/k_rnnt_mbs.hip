@@ -130,7 +130,7 @@ __global__ void mbs_init_kernel(DecodeState st, MbsState ms, const int32_t* __re
         if constexpr (HW) { const int r = mbs_root<LM>(hw, b); ms.ctx[0][row] = r < 0 ? 0 : r; }
         if constexpr (LM) ms.lmctx[0][row] = lm_node(hw.lm, hw.lm.start);
         st.token2[row] = -1; st.token[row] = blank; st.act[b] = row;
-        n_ids[b] = 0; scores[b] = 0.0f;                  // the result of an utterance without frames
+        if (n_ids != nullptr) { n_ids[b] = 0; scores[b] = 0.0f; }   // the result of an utterance without frames (rs_rnnt_mbs_nbest: the caller clears its lists)
         if (enc_lens[b] > 0) st.alive[atomicAdd(&n_alive_s, 1)] = row;
     }
     __syncthreads();
@@ -159,11 +159,16 @@ __global__ __launch_bounds__(256) void mbs_act_kernel(DecodeState st, MbsState m
 // first comparison; maximum, exp-sum and the running top-K then walk the registers.  NVR = 0: any V, three passes over memory,
 // the same arithmetic in the same order.
 // HW: the hotword form; LM: the n-gram form (HW on as well).  The other forms are the same text without the `if constexpr` statements.
+// nbest == 0: the one result, as ever (ids / frames [B][out_cap], n_ids / scores [B]).  nbest >= 1 (rs_rnnt_mbs_nbest; a uniform
+// run-time branch at the utterance's last frame, no further launch): the entries of the last set ranked by the winner's rule applied
+// down the list — the greatest norm first, of equal norms the one that entered the set first — into ids / frames
+// [B][nbest][out_cap], n_ids / scores / norm_scores [B][nbest], n_hyps [B].
 template <int NVR, bool HW, bool LM = false>
 __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
     DecodeState st, MbsState ms, const float* __restrict__ zbuf, int zstride, const int32_t* __restrict__ enc_lens, int rows, int K,
     int V, int blank, int unk, int t, float blank_penalty, int length_norm, int out_cap, int32_t* __restrict__ ids,
-    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores, MbsArg<HW, LM> hw) {
+    int32_t* __restrict__ frames, int32_t* __restrict__ n_ids, float* __restrict__ scores, int nbest, float* __restrict__ norm_scores,
+    int32_t* __restrict__ n_hyps, MbsArg<HW, LM> hw) {
     static_assert(HW || !LM, "the LM form is compiled with the hotword statements");
     const int b = blockIdx.x;
     const int T = enc_lens[b];
@@ -392,6 +397,11 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
         int nk = 0;
         int win = -1, win_n = 0;
         float win_norm = 0.0f, win_score = 0.0f;
+        float enorm[MBS_MAX_K], esc[MBS_MAX_K];           // n-best: norm, score and length of the entries, by candidate
+        int en[MBS_MAX_K];
+        unsigned left = 0;                                // n-best: the entries not yet ranked
+#pragma unroll
+        for (int j = 0; j < MBS_MAX_K; ++j) { enorm[j] = 0.0f; esc[j] = 0.0f; en[j] = 0; }
 #pragma unroll
         for (int j = 0; j < MBS_MAX_K; ++j) {
             if (j >= n_cand || ((dup >> j) & 1u)) continue;
@@ -408,10 +418,37 @@ __global__ __launch_bounds__(MBS_THREADS) void mbs_select_kernel(
             const int n = cplen[j] + (ctok[j] >= 0 ? 1 : 0);
             const float norm = length_norm ? sc / (float)(n + MBS_CONTEXT) : sc;
             if (win < 0 || norm > win_norm) { win = j; win_n = n; win_norm = norm; win_score = sc; }
+            if (nbest > 0 && t == T - 1) { enorm[j] = norm; esc[j] = sc; en[j] = n; left |= 1u << j; }      // (only the list reads them)
             ++nk;
         }
         if (lane == 0) { s_nnew = nk; ms.n_hyp[pn][b] = nk; }
-        if (t == T - 1 && win >= 0) {                     // the utterance's last frame: the result
+        if (t == T - 1 && win >= 0 && nbest > 0) {        // the utterance's last frame: the ranked list (rank 0 is the winner below)
+            int nh = 0;
+            for (int r = 0; r < nbest; ++r) {
+                int pick = -1;
+                float pnorm = 0.0f;
+#pragma unroll
+                for (int j = 0; j < MBS_MAX_K; ++j)
+                    if (((left >> j) & 1u) && (pick < 0 || enorm[j] > pnorm)) { pick = j; pnorm = enorm[j]; }
+                if (pick < 0) break;                      // the last set is smaller than nbest
+                left &= ~(1u << pick);
+                int wprow = 0, wtok = -1, wplen = 0, n = 0;
+                float wsc = 0.0f;
+#pragma unroll
+                for (int j = 0; j < MBS_MAX_K; ++j)
+                    if (j == pick) { wprow = cprow[j]; wtok = ctok[j]; wplen = cplen[j]; n = en[j]; wsc = esc[j]; }
+                if (n > out_cap) { n = out_cap; if (lane == 0) st.counters[1] = 1; }
+                const size_t e = (size_t)b * nbest + r;
+                const int32_t *py = ms.y[p] + (size_t)wprow * cap, *pf = ms.fr[p] + (size_t)wprow * cap;
+                for (int q = lane; q < n; q += 64) {
+                    ids[e * out_cap + q] = q < wplen ? py[q] : wtok;
+                    frames[e * out_cap + q] = q < wplen ? pf[q] : t;
+                }
+                if (lane == 0) { n_ids[e] = n; scores[e] = wsc; norm_scores[e] = pnorm; }
+                ++nh;
+            }
+            if (lane == 0) n_hyps[b] = nh;
+        } else if (t == T - 1 && win >= 0) {              // the utterance's last frame: the result
             int wprow = 0, wtok = -1, wplen = 0;
 #pragma unroll
             for (int j = 0; j < MBS_MAX_K; ++j) if (j == win) { wprow = cprow[j]; wtok = ctok[j]; wplen = cplen[j]; }
@@ -497,8 +534,9 @@ size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_
 }
 
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
-                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
-                     const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int nbest, float* norm_scores,
+                     int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
+                     void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int D = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (B <= 0) return RS_OK;
@@ -538,7 +576,14 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
     auto search = [&](auto init_k, auto select_k, const auto& tables) -> int {
         rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
         RS_HIP(ctx, hipMemsetAsync(st.h, 0, 4 * rs_align((size_t)rows * D * 4), s));                  // h .. c_tmp are adjacent
-        hipLaunchKernelGGL(init_k, dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, n_ids, scores, tables);
+        if (nbest > 0) {                                  // the lists: an entry that is not written has no labels, an utterance without frames no entry
+            RS_HIP(ctx, hipMemsetAsync(n_ids, 0, (size_t)B * nbest * 4, s));
+            RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * nbest * 4, s));
+            RS_HIP(ctx, hipMemsetAsync(norm_scores, 0, (size_t)B * nbest * 4, s));
+            RS_HIP(ctx, hipMemsetAsync(n_hyps, 0, (size_t)B * 4, s));
+        }
+        hipLaunchKernelGGL(init_k, dim3(1), dim3(256), 0, s, st, ms, enc_lens, B, K, d.blank_id, nbest > 0 ? nullptr : n_ids,
+                           nbest > 0 ? nullptr : scores, tables);
         if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
         RS_CHECK_LAUNCH(ctx, "modified beam search init");
         const int act_blocks = (int)(((long long)rows * (J / 4) + 255) / 256);
@@ -546,7 +591,7 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
             hipLaunchKernelGGL(mbs_act_kernel, dim3(act_blocks), dim3(256), 0, s, st, ms, joint_enc, a_pre, rows, tp_max, J, K, t);
             if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, rows, rows, tp_max, K, t, s); rc != RS_OK) return rc;
             hipLaunchKernelGGL(select_k, dim3(B), dim3(MBS_THREADS), 0, s, st, ms, zbuf, zstride, enc_lens, rows, K, V, d.blank_id, st.unk, t,
-                               blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, tables);
+                               blank_penalty, length_norm, out_cap, ids, frames, n_ids, scores, nbest, norm_scores, n_hyps, tables);
             if (int rc = rs_rnnt_launch_lstm_pred(ctx, &st, rows, s); rc != RS_OK) return rc;
         }
         RS_CHECK_LAUNCH(ctx, "modified beam search step");

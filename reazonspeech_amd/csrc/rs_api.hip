@@ -14,18 +14,19 @@
 #include "rs_ngram_check.h"
 
 size_t rs_rnnt_workspace_bytes(const rs_ctx* ctx, int B);
-size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm);
+size_t rs_rnnt_alsd_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int cap, bool hotwords, bool lm, int nbest);
 size_t rs_rnnt_mbs_workspace_bytes_impl(const rs_ctx* ctx, int B, int K, int tp_max, bool hotwords, bool lm);
 int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int K, float blank_penalty,
-                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, const rs_hotwords* hotwords,
-                     const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s);
+                     int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int nbest, float* norm_scores,
+                     int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
+                     void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops);
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
-                      int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops,
-                      void* workspace, size_t workspace_bytes, hipStream_t s);
+                      int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, int nbest,
+                      float* norm_scores, int32_t* n_hyps, void* workspace, size_t workspace_bytes, hipStream_t s);
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
-                      float* scores, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
+                      float* scores, int nbest, float* norm_scores, int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
                       void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_token_scores_workspace_bytes_impl(const rs_ctx* ctx, int B, int u_cap);
 int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
@@ -345,10 +346,10 @@ static int alsd_steps(int tp_max, double ratio, int abs_len) {
 
 // the three workspace queries of ALSD (each entry keeps its own family guard): room for the hotword states and / or the LM states
 static size_t alsd_workspace(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs, bool hotwords,
-                             bool lm) {
+                             bool lm, int nbest = 0) {
     if (B <= 0 || beam <= 0 || tp_max < 0 || (max_target_abs < 0 && !(max_target_ratio >= 0.0))) return 0;
     const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;
-    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), hotwords, lm);
+    return rs_rnnt_alsd_workspace_bytes_impl(ctx, B, W, alsd_steps(tp_max, max_target_ratio, max_target_abs), hotwords, lm, nbest);
 }
 
 size_t rs_rnnt_alsd_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs) {
@@ -366,32 +367,39 @@ size_t rs_rnnt_alsd_lm_workspace_bytes(const rs_ctx* ctx, int B, int beam, int t
     return alsd_workspace(ctx, B, beam, tp_max, max_target_ratio, max_target_abs, true, true);
 }
 
-// the argument checks and the dispatch of rs_rnnt_alsd, rs_rnnt_alsd_hotwords and rs_rnnt_alsd_lm (hw == nullptr, lm == nullptr: the
-// plain kernels)
+// the argument checks and the dispatch of rs_rnnt_alsd, rs_rnnt_alsd_hotwords, rs_rnnt_alsd_lm (hw == nullptr, lm == nullptr: the
+// plain kernels) and rs_rnnt_alsd_nbest (nbest >= 1: ids / steps [B][nbest][out_cap], n_ids / scores / norm_scores [B][nbest],
+// n_hyps [B]; the others pass nbest = 0 and no lists: the one result)
 static int alsd_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double max_target_ratio,
-                     int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids, float* scores,
-                     const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
+                     int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids, float* scores, int nbest,
+                     float* norm_scores, int32_t* n_hyps, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
                      void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0) return rs_fail(ctx, RS_EINVAL, "alsd: negative size");
     if (max_target_abs < 0 && !(max_target_ratio >= 0.0 && max_target_ratio <= 64.0))
         return rs_fail(ctx, RS_EINVAL, "alsd: max_target_ratio must be in [0, 64]");
     if (B == 0) return RS_OK;
     if (!joint_enc || !enc_lens || !ids || !steps || !n_ids || !scores || !workspace) return rs_fail(ctx, RS_EINVAL, "alsd: null pointer");
-    if (tp_max == 0) {
-        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, (size_t)B * 4, (hipStream_t)stream));
-        RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * 4, (hipStream_t)stream));
+    if (nbest > 0 && (!norm_scores || !n_hyps)) return rs_fail(ctx, RS_EINVAL, "alsd: null pointer");
+    if (tp_max == 0) {                                    // no frames anywhere: the start hypothesis, empty, score 0
+        const size_t entries = (size_t)B * (nbest > 0 ? nbest : 1);
+        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, entries * 4, (hipStream_t)stream));
+        RS_HIP(ctx, hipMemsetAsync(scores, 0, entries * 4, (hipStream_t)stream));
+        if (nbest > 0) {
+            RS_HIP(ctx, hipMemsetAsync(norm_scores, 0, entries * 4, (hipStream_t)stream));
+            RS_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)n_hyps, 1, (size_t)B, (hipStream_t)stream));
+        }
         return RS_OK;
     }
     return rs_rnnt_alsd_impl(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs,
                              (flags & RS_ALSD_SCORE_NORM) != 0, (flags & RS_ALSD_MERGE) != 0, out_cap, ids, steps, n_ids, scores,
-                             hw, hw ? graph_of : nullptr, lm, lm_alpha, workspace, workspace_bytes, (hipStream_t)stream);
+                             nbest, norm_scores, n_hyps, hw, hw ? graph_of : nullptr, lm, lm_alpha, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int rs_rnnt_alsd(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam,
                  double max_target_ratio, int max_target_abs, int flags, int out_cap, int32_t* ids, int32_t* steps,
                  int32_t* n_ids, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd);
-    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores, 0, nullptr, nullptr,
                      nullptr, nullptr, nullptr, 0.0f, workspace, workspace_bytes, stream);
 }
 
@@ -420,7 +428,7 @@ int rs_rnnt_alsd_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* en
                           size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_alsd_hotwords);
     if (int rc = hotwords_arg(ctx, "alsd", true, &hw, graph_of); rc != RS_OK) return rc;
-    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores, 0, nullptr, nullptr,
                      hw, graph_of, nullptr, 0.0f, workspace, workspace_bytes, stream);
 }
 
@@ -454,8 +462,29 @@ int rs_rnnt_alsd_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens
     RS_GUARD(ctx, rs_rnnt_alsd_lm);
     if (int rc = hotwords_arg(ctx, "alsd", true, &hw, graph_of); rc != RS_OK) return rc;
     if (int rc = ngram_arg(ctx, "alsd", &lm, lm_alpha); rc != RS_OK) return rc;
-    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores, 0, nullptr, nullptr,
                      hw, graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
+}
+
+// ---- n-best lists of ALSD: the same dispatch with the lists as outputs ----
+size_t rs_rnnt_alsd_nbest_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, double max_target_ratio, int max_target_abs, int nbest) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_alsd_nbest_workspace_bytes, 0);
+    if (nbest < 1 || nbest > 8 || nbest > beam) return 0;
+    return alsd_workspace(ctx, B, beam, tp_max, max_target_ratio, max_target_abs, true, true, nbest);      // the LM form's layout plus the list
+}
+
+int rs_rnnt_alsd_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double max_target_ratio,
+                       int max_target_abs, int flags, int nbest, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids, float* scores,
+                       float* norm_scores, int32_t* n_hyps, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
+                       float lm_alpha, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_alsd_nbest);
+    if (nbest < 1 || nbest > 8) return rs_fail(ctx, RS_EINVAL, "alsd: nbest must be 1..8, got %d", nbest);      // before anything is enqueued
+    const int W = beam < ctx->d.n_logits - 1 ? beam : ctx->d.n_logits - 1;                                       // (the search clamps the beam)
+    if (nbest > W) return rs_fail(ctx, RS_EINVAL, "alsd: nbest %d is above the beam %d", nbest, W);
+    if (int rc = hotwords_arg(ctx, "alsd", true, &hw, graph_of); rc != RS_OK) return rc;
+    if (int rc = ngram_arg(ctx, "alsd", &lm, lm_alpha); rc != RS_OK) return rc;
+    return alsd_call(ctx, joint_enc, enc_lens, B, tp_max, beam, max_target_ratio, max_target_abs, flags, out_cap, ids, steps, n_ids, scores,
+                     nbest, norm_scores, n_hyps, hw, graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
 }
 
 size_t rs_rnnt_beam_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops) {
@@ -464,22 +493,56 @@ size_t rs_rnnt_beam_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_m
     return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops);
 }
 
-int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
-                 int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, void* workspace,
-                 size_t workspace_bytes, void* stream) {
-    RS_GUARD(ctx, rs_rnnt_beam);
+// the argument checks and the dispatch of rs_rnnt_beam and rs_rnnt_beam_nbest (nbest >= 1: ids / frames [B][nbest][out_cap], n_ids /
+// scores / norm_scores [B][nbest], n_hyps [B]; rs_rnnt_beam passes nbest = 0 and no lists: the one result)
+static int beam_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
+                     int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, int nbest, float* norm_scores,
+                     int32_t* n_hyps, void* workspace, size_t workspace_bytes, void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0 || max_pops < 0) return rs_fail(ctx, RS_EINVAL, "beam search: negative size");
     if (beam < 1) return rs_fail(ctx, RS_EINVAL, "beam search: beam size must be >= 1");
     if (B == 0) return RS_OK;
     if (!joint_enc || !enc_lens || !ids || !n_ids || !scores || !pops || !workspace) return rs_fail(ctx, RS_EINVAL, "beam search: null pointer");
-    if (tp_max == 0) {
-        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, (size_t)B * 4, (hipStream_t)stream));
-        RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * 4, (hipStream_t)stream));
+    if (nbest > 0 && (!norm_scores || !n_hyps)) return rs_fail(ctx, RS_EINVAL, "beam search: null pointer");
+    if (tp_max == 0) {                                    // no frames anywhere: the start hypothesis, empty, score 0
+        const size_t entries = (size_t)B * (nbest > 0 ? nbest : 1);
+        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, entries * 4, (hipStream_t)stream));
+        RS_HIP(ctx, hipMemsetAsync(scores, 0, entries * 4, (hipStream_t)stream));
         RS_HIP(ctx, hipMemsetAsync(pops, 0, (size_t)B * 4, (hipStream_t)stream));
+        if (nbest > 0) {
+            RS_HIP(ctx, hipMemsetAsync(norm_scores, 0, entries * 4, (hipStream_t)stream));
+            RS_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)n_hyps, 1, (size_t)B, (hipStream_t)stream));
+        }
         return RS_OK;
     }
     return rs_rnnt_beam_impl(ctx, joint_enc, enc_lens, B, tp_max, beam, (flags & RS_BEAM_SCORE_NORM) != 0, max_pops, out_cap, ids,
-                             frames, n_ids, scores, pops, workspace, workspace_bytes, (hipStream_t)stream);
+                             frames, n_ids, scores, pops, nbest, norm_scores, n_hyps, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
+                 int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_beam);
+    return beam_call(ctx, joint_enc, enc_lens, B, tp_max, beam, flags, max_pops, out_cap, ids, frames, n_ids, scores, pops, 0, nullptr,
+                     nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---- n-best lists of the default beam search: the same dispatch with the lists as outputs ----
+size_t rs_rnnt_beam_nbest_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, int nbest) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_beam_nbest_workspace_bytes, 0);
+    if (B <= 0 || beam <= 0 || tp_max < 0 || max_pops < 0 || ctx->d.n_logits < 2 || nbest < 1 || nbest > 8 || nbest > beam) return 0;
+    return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops);         // the lists live in the outputs
+}
+
+int rs_rnnt_beam_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
+                       int nbest, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, float* norm_scores,
+                       int32_t* n_hyps, int32_t* pops, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_beam_nbest);
+    if (nbest < 1 || nbest > 8) return rs_fail(ctx, RS_EINVAL, "beam search: nbest must be 1..8, got %d", nbest);      // before anything is enqueued
+    if (beam < 1) return rs_fail(ctx, RS_EINVAL, "beam search: beam size must be >= 1");
+    const int bm = beam < ctx->d.n_logits ? beam : ctx->d.n_logits;                    // (the search clamps the beam to the vocabulary)
+    if (nbest > bm) return rs_fail(ctx, RS_EINVAL, "beam search: nbest %d is above the beam %d", nbest, bm);
+    return beam_call(ctx, joint_enc, enc_lens, B, tp_max, beam, flags, max_pops, out_cap, ids, frames, n_ids, scores, pops, nbest,
+                     norm_scores, n_hyps, workspace, workspace_bytes, stream);
 }
 
 size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {
@@ -552,33 +615,41 @@ int rs_hotwords_check(const rs_hotwords_host* t, char* msg, size_t msg_bytes) {
     return RS_OK;
 }
 
-// the argument checks and the dispatch of rs_rnnt_mbs, rs_rnnt_mbs_hotwords and rs_rnnt_mbs_lm (lm == nullptr: no model)
+// the argument checks and the dispatch of rs_rnnt_mbs, rs_rnnt_mbs_hotwords, rs_rnnt_mbs_lm (lm == nullptr: no model) and
+// rs_rnnt_mbs_nbest (nbest >= 1: ids / frames [B][nbest][out_cap], n_ids / scores / norm_scores [B][nbest], n_hyps [B]; the others
+// pass nbest = 0 and no lists: the one result)
 static int mbs_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
-                    float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
-                    const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
-                    void* stream) {
+                    float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int nbest,
+                    float* norm_scores, int32_t* n_hyps, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha,
+                    void* workspace, size_t workspace_bytes, void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0) return rs_fail(ctx, RS_EINVAL, "modified beam search: negative size");
     if (max_active_paths < 1 || max_active_paths > 8) return rs_fail(ctx, RS_EINVAL, "modified beam search: max_active_paths must be 1..8, got %d", max_active_paths);
     if (!(blank_penalty >= 0.0f)) return rs_fail(ctx, RS_EINVAL, "modified beam search: blank_penalty must be >= 0");
     if (B == 0) return RS_OK;
     if (!joint_enc || !enc_lens || !ids || !frames || !n_ids || !scores || !workspace) return rs_fail(ctx, RS_EINVAL, "modified beam search: null pointer");
+    if (nbest > 0 && (!norm_scores || !n_hyps)) return rs_fail(ctx, RS_EINVAL, "modified beam search: null pointer");
     if (tp_max == 0) {
-        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, (size_t)B * 4, (hipStream_t)stream));
-        RS_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)B * 4, (hipStream_t)stream));
+        const size_t entries = (size_t)B * (nbest > 0 ? nbest : 1);
+        RS_HIP(ctx, hipMemsetAsync(n_ids, 0, entries * 4, (hipStream_t)stream));
+        RS_HIP(ctx, hipMemsetAsync(scores, 0, entries * 4, (hipStream_t)stream));
+        if (nbest > 0) {
+            RS_HIP(ctx, hipMemsetAsync(norm_scores, 0, entries * 4, (hipStream_t)stream));
+            RS_HIP(ctx, hipMemsetAsync(n_hyps, 0, (size_t)B * 4, (hipStream_t)stream));
+        }
         return RS_OK;
     }
     if (int rc = hotwords_arg(ctx, "modified beam search", false, &hw, graph_of); rc != RS_OK) return rc;
     return rs_rnnt_mbs_impl(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, (flags & RS_MBS_LENGTH_NORM) != 0,
-                            out_cap, ids, frames, n_ids, scores, hw, hw ? graph_of : nullptr, lm, lm_alpha, workspace, workspace_bytes,
-                            (hipStream_t)stream);
+                            out_cap, ids, frames, n_ids, scores, nbest, norm_scores, n_hyps, hw, hw ? graph_of : nullptr, lm, lm_alpha,
+                            workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int rs_rnnt_mbs_hotwords(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
                          float blank_penalty, int flags, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
                          const rs_hotwords* hw, const int32_t* graph_of, void* workspace, size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_mbs_hotwords);
-    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, hw,
-                    graph_of, nullptr, 0.0f, workspace, workspace_bytes, stream);
+    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, 0,
+                    nullptr, nullptr, hw, graph_of, nullptr, 0.0f, workspace, workspace_bytes, stream);
 }
 
 int rs_rnnt_mbs_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
@@ -587,8 +658,28 @@ int rs_rnnt_mbs_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens,
                    size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_mbs_lm);
     if (int rc = ngram_arg(ctx, "modified beam search", &lm, lm_alpha); rc != RS_OK) return rc;     // before anything is enqueued
-    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, hw,
-                    graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
+    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, 0,
+                    nullptr, nullptr, hw, graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
+}
+
+// ---- n-best lists of the modified beam search: the same dispatch with the lists as outputs ----
+size_t rs_rnnt_mbs_nbest_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap, int nbest) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_mbs_nbest_workspace_bytes, 0);
+    if (B <= 0 || max_active_paths < 1 || max_active_paths > 8 || tp_max < 0 || out_cap < 0 || nbest < 1 || nbest > max_active_paths) return 0;
+    return rs_rnnt_mbs_workspace_bytes_impl(ctx, B, max_active_paths, tp_max, true, true);       // the lists live in the outputs: the LM form's layout
+}
+
+int rs_rnnt_mbs_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int max_active_paths,
+                      float blank_penalty, int flags, int nbest, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                      float* norm_scores, int32_t* n_hyps, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm,
+                      float lm_alpha, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_mbs_nbest);
+    if (nbest < 1 || nbest > 8) return rs_fail(ctx, RS_EINVAL, "modified beam search: nbest must be 1..8, got %d", nbest);      // before anything is enqueued
+    if (nbest > max_active_paths)
+        return rs_fail(ctx, RS_EINVAL, "modified beam search: nbest %d is above max_active_paths %d", nbest, max_active_paths);
+    if (int rc = ngram_arg(ctx, "modified beam search", &lm, lm_alpha); rc != RS_OK) return rc;
+    return mbs_call(ctx, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, flags, out_cap, ids, frames, n_ids, scores, nbest,
+                    norm_scores, n_hyps, hw, graph_of, lm, lm_alpha, workspace, workspace_bytes, stream);
 }
 
 // ---- token log-probabilities of a finished search (k_rnnt_scores.hip) ----

@@ -49,8 +49,12 @@ enum { RS_ANYTIME = 0, RS_FINAL = 1 };
     X(rs_rnnt_alsd_hotwords, C, FINAL, RS_HINT_LSTM_ONLY)                                                                             \
     X(rs_rnnt_alsd_lm_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                                   \
     X(rs_rnnt_alsd_lm, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                   \
+    X(rs_rnnt_alsd_nbest_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                                \
+    X(rs_rnnt_alsd_nbest, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                \
     X(rs_rnnt_beam_workspace_bytes, C, ANYTIME, RS_HINT_LSTM_ONLY)                                                                    \
     X(rs_rnnt_beam, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                      \
+    X(rs_rnnt_beam_nbest_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                                \
+    X(rs_rnnt_beam_nbest, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                \
     X(rs_rnnt_mbs_workspace_bytes, Z, ANYTIME, RS_HINT_MBS)                                                                           \
     X(rs_rnnt_mbs, Z, FINAL, RS_HINT_MBS)                                                                                             \
     X(rs_rnnt_mbs_hotwords_workspace_bytes, Z, ANYTIME, RS_HINT_MBS)                                                                  \
@@ -58,6 +62,8 @@ enum { RS_ANYTIME = 0, RS_FINAL = 1 };
     /* FINAL also for the size, as rs_rnnt_alsd_hotwords_workspace_bytes above */                                                     \
     X(rs_rnnt_mbs_lm_workspace_bytes, Z, FINAL, RS_HINT_MBS)                                                                          \
     X(rs_rnnt_mbs_lm, Z, FINAL, RS_HINT_MBS)                                                                                          \
+    X(rs_rnnt_mbs_nbest_workspace_bytes, Z, FINAL, RS_HINT_MBS)                                                                       \
+    X(rs_rnnt_mbs_nbest, Z, FINAL, RS_HINT_MBS)                                                                                       \
     X(rs_rnnt_token_scores_workspace_bytes, CZ, FINAL, RS_HINT_TRANSDUCER)                                                            \
     /* ANYTIME: tests/test_gpu_token_scores.py pins RS_EINVAL for a context that is not finalized; the entry tests that itself */     \
     X(rs_rnnt_token_scores, CZ, ANYTIME, RS_HINT_TRANSDUCER)                                                                          \

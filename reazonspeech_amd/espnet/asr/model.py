@@ -55,19 +55,53 @@ class _ScoredHypothesis:
         self.yseq, self.token_logprobs = list(yseq), list(token_logprobs)
 
 
+class _NBestHypothesis:
+    """4th element of an n-best entry of a model loaded with `nbest=N`: [UPSTREAM] the fields of espnet2's transducer Hypothesis a
+    caller of Speech2Text reads — `yseq` (the ids; upstream's leading blank is not repeated here) and `score` (the hypothesis's
+    log-probability, not normalised; NaN for the one entry of a window the greedy search decoded, which keeps no score) — plus `norm_score` (score / len(yseq) counting that blank: what sort_nbest ranks by) and,
+    with `token_scores` on, `token_logprobs` for entry 0 (None for the other entries)"""
+
+    def __init__(self, yseq, score, norm_score, token_logprobs=None):
+        self.yseq, self.score, self.norm_score = list(yseq), float(score), float(norm_score)
+        self.token_logprobs = None if token_logprobs is None else list(token_logprobs)
+
+
+def check_nbest(nbest, beam_size):
+    """the `nbest=` keyword of load_model / EspnetModel (upstream's Speech2Text(nbest=)): None or 1 with any search, 2..8 with the
+    beam search and not above beam_size; ValueError with the reason otherwise.  -> the count the search is run with (0 = off)"""
+    if nbest is None:
+        return 0
+    if not (isinstance(nbest, int) and not isinstance(nbest, bool) and 1 <= nbest <= 8):
+        raise ValueError(f"nbest must be an integer in 1..8, not {nbest!r}")
+    beam = 1 if beam_size is None else int(beam_size)
+    if beam <= 1:
+        if nbest > 1:
+            raise ValueError(f"nbest={nbest} needs the beam search (beam_size > 1): greedy_search keeps one hypothesis")
+        return 0
+    if nbest > beam:
+        raise ValueError(f"nbest={nbest} is above beam_size={beam}")
+    return nbest
+
+
 class EspnetModel:
     def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host",
-                 resample="host", token_scores=False):
-        """token_scores: the searches are followed by rs_rnnt_token_scores on the device; `recognize_batch_scored` and the 4th element
+                 resample="host", token_scores=False, nbest=None):
+        """nbest: upstream's `Speech2Text(nbest=N)`: `model(speech)` returns the N best hypotheses of the beam search — upstream's
+        `sort_nbest(kept_hyps)[:nbest]`, ranked on the device (include/rs_asr.h rs_rnnt_beam_nbest) — as N tuples (text, tokens, ids,
+        hyp) with `hyp.score` set; `recognize_batch(..., nbest=)` gives the same per window.  None (default): one tuple, as ever.
+        N above beam_size, or N > 1 with beam_size <= 1, raises ValueError.  Stored as `model.nbest`.
+        token_scores: the searches are followed by rs_rnnt_token_scores on the device; `recognize_batch_scored` and the 4th element
         of `model(speech)`'s n-best entry carry the log-probability of every token.  Stored as `model.token_scores`."""
         assert cfg.espnet and len(token_list) == cfg.vocab_size
         self.segmentation = segmentation
+        n_best = check_nbest(nbest, beam_size)
         if beam_size is not None and int(beam_size) > 1:
             cfg = cfg.with_(decoding="beam", beam_size=int(beam_size), beam_score_norm=True, beam_max_pops=int(max_pops))
         self.beam_size = cfg.beam_size if cfg.decoding == "beam" else 1
         self.cfg = cfg
         self.token_list = list(token_list)
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision, resample=resample, token_scores=token_scores)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision, resample=resample, token_scores=token_scores,
+                           nbest=n_best)
         self.device = self.am.device
         self.dtype = "float32"
         self._last_enc = self._last_ctc = None
@@ -75,9 +109,12 @@ class EspnetModel:
 
     # ---- the reference's call forms -------------------------------------------------------------------------------
     def __call__(self, speech):
-        """Speech2Text.__call__: n-best list of (text, tokens, token ids, hypothesis); here nbest = 1 (upstream's default)"""
+        """Speech2Text.__call__: n-best list of (text, tokens, token ids, hypothesis): one entry (upstream's default), or
+        `model.nbest` of them from a model loaded with `nbest=N`"""
         wav = np.asarray(speech.detach().cpu().numpy() if isinstance(speech, torch.Tensor) else speech, dtype=np.float32).reshape(-1)
         res = self._search([wav])
+        if res.nbest is not None:
+            return self._nbest_entries(res, 0)
         ids = res.ids[0]
         tokens = [self.token_list[i] for i in ids]
         hyp = _ScoredHypothesis(ids, res.token_logprobs[0]) if res.token_logprobs is not None else None
@@ -92,11 +129,29 @@ class EspnetModel:
     def ids_to_text(self, ids):
         return self.tokens2text([self.token_list[i] for i in ids])
 
-    def recognize_batch(self, waves, isolate_overflow=False):
+    def _nbest_entries(self, res, b):
+        """window b of a search that ran with lists -> [(text, tokens, ids, hyp)], best first; a window the greedy fall-back decoded
+        has the one entry"""
+        out = []
+        for r, (ids, _, score, norm) in enumerate(res.nbest[b]):
+            tokens = [self.token_list[i] for i in ids]
+            lp = res.token_logprobs[b] if res.token_logprobs is not None and r == 0 else None
+            out.append((self.tokens2text(tokens), tokens, ids, _NBestHypothesis(ids, score, norm, lp)))
+        return out
+
+    @property
+    def nbest(self):
+        return self.am.nbest
+
+    def recognize_batch(self, waves, isolate_overflow=False, nbest=None):
         """padded like the reference pads each window (np.pad(samples, PADDING), transcribe.py:69) -> [text].
-        `isolate_overflow`: see `_search`."""
-        res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves], isolate_overflow=isolate_overflow)
-        return [self.ids_to_text(ids) for ids in res.ids]
+        `isolate_overflow`: see `_search`.  `nbest=N`: per window the list of `model(speech)` instead — N tuples (text, tokens, ids,
+        hyp), best first (one where the greedy fall-back decoded the window)."""
+        padded = [np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves]
+        if nbest is None:
+            return [self.ids_to_text(ids) for ids in self._search(padded, isolate_overflow=isolate_overflow).ids]
+        res = self._search(padded, isolate_overflow=isolate_overflow, nbest=check_nbest(nbest, self.beam_size) or 1)
+        return [self._nbest_entries(res, b) for b in range(len(padded))]
 
     def recognize_batch_scored(self, waves, isolate_overflow=False):
         """`recognize_batch` of a model with `token_scores` on -> ([text], [(token ids, log-probabilities)])"""
@@ -113,7 +168,7 @@ class EspnetModel:
     def token_scores(self, value):
         self.am.token_scores = bool(value)
 
-    def _search(self, waves, max_batch=256, isolate_overflow=False):
+    def _search(self, waves, max_batch=256, isolate_overflow=False, nbest=None):
         """the transducer search over a batch of (padded) windows.  Upstream's default beam search has no bound on the
         prediction-network evaluations a frame may take; the device search has one (`max_pops`, which sizes its workspace)
         and reports RS_EOVERFLOW instead of truncating.  The front end and the encoder run ONCE per batch; a decode that hits
@@ -124,16 +179,24 @@ class EspnetModel:
         `isolate_overflow` (default off: a chunk that still overflows turns greedy as a whole): the windows of such a chunk are
         decoded again one by one, each with the retry ladder above, so that only the window that overflows turns greedy and its
         chunk-mates keep the beam search's result — what a caller that pools unrelated windows into one chunk needs to return
-        what the window-by-window path returns."""
+        what the window-by-window path returns.
+
+        `nbest`: entries per window for this call (None = `model.nbest`).  With lists on, `DecodedBatch.nbest` holds every window's;
+        the retry ladder is the same, and a window the greedy fall-back decoded has a list of one (score NaN: the greedy search
+        keeps none) and `degraded`."""
         from ...runtime.capi import RsError, RS_EOVERFLOW
         from ...runtime.model import DecodedBatch
         am = self.am
+        n_best = am.nbest if nbest is None else nbest
         if am.cfg.decoding != "beam":
-            return am.transcribe_waveforms(waves)
+            res = am.transcribe_waveforms(waves)
+            if n_best:                                    # (nbest = 1 with the greedy search: the one hypothesis as a list)
+                res.nbest = [[(ids, fr, float("nan"), float("nan"))] for ids, fr in zip(res.ids, res.frames)]
+            return res
         bound = am.cfg.beam_max_pops or 16 * am.cfg.beam_size
-        out = DecodedBatch([], [], [], [], [], [] if am.token_scores else None)
+        out = DecodedBatch([], [], [], [], [], token_logprobs=[] if am.token_scores else None, nbest=[] if n_best else None)
         for lo in range(0, len(waves), max_batch):
-            buf = am.stage([np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]])
+            buf = am.stage([np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]], nbest=n_best)
             with torch.cuda.device(am.device):
                 stream = torch.cuda.current_stream().cuda_stream
                 am.run_encoder(buf, stream)
@@ -148,9 +211,11 @@ class EspnetModel:
                             raise
                 if used is None and isolate_overflow and buf.B > 1:
                     for w in waves[lo:lo + max_batch]:
-                        one = self._search([w], max_batch=1)
+                        one = self._search([w], max_batch=1, nbest=n_best)
                         out.ids += one.ids; out.frames += one.frames; out.enc_lens += one.enc_lens
                         out.scores += one.scores; out.degraded += one.degraded
+                        if out.nbest is not None:
+                            out.nbest += one.nbest
                         if out.token_logprobs is not None:
                             out.token_logprobs += one.token_logprobs
                     continue
@@ -167,6 +232,8 @@ class EspnetModel:
             out.degraded += [used != "beam"] * buf.B
             if out.token_logprobs is not None:
                 out.token_logprobs += res.token_logprobs
+            if out.nbest is not None:                     # (the greedy fall-back ran without lists: its one hypothesis each)
+                out.nbest += res.nbest if res.nbest is not None else [[(ids, fr, float("nan"), float("nan"))] for ids, fr in zip(res.ids, res.frames)]
         return out
 
     # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option

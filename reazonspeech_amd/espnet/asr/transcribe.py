@@ -23,7 +23,7 @@ CHECKPOINT_ENV = "REAZONSPEECH_ESPNET_CHECKPOINT"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False,
-               segmentation="host", resample="host", token_scores=False):
+               segmentation="host", resample="host", token_scores=False, nbest=None):
     """Load the ReazonSpeech ESPnet model onto a ROCm GPU (transcribe.py:12-32).
 
     Args:
@@ -55,13 +55,22 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         confidence = exp(mean); the pieces of a long recording are concatenated in order.  Valid with every `precision` and
         `beam_size`.  Off (default): today's objects.  Stored as `model.token_scores`, may be changed later.
 
+      nbest (int): upstream's `Speech2Text(nbest=N)`, 1..8 and at most `beam_size`: `model(speech)` returns the N best hypotheses of
+        the default beam search as N tuples (text, tokens, ids, hyp) with `hyp.score` set — upstream's `sort_nbest(kept_hyps)[:nbest]`,
+        ranked on the device (include/rs_asr.h rs_rnnt_beam_nbest) — and `model.recognize_batch(..., nbest=N)` the same per window.
+        `transcribe` / `transcribe_batch` keep returning the best hypothesis.  None (default): one tuple, as ever.  A window that the
+        greedy fall-back decodes (see `max_pops`), and every window of a greedy model asked for nbest = 1, returns a list of ONE
+        whose `hyp.score` and `hyp.norm_score` are NaN — the greedy search keeps no score; test with `math.isnan` before sorting.  N above the
+        beam, or N > 1 with the greedy search, raises ValueError.
+
     The reference downloads `reazon-research/reazonspeech-espnet-v2` through espnet_model_zoo (:27-31), which an offline box
     cannot do: give `checkpoint=` / the environment variable.  Without a checkpoint this RAISES; seeded synthetic weights of
     the architecture (timings valid, transcripts meaningless) are loaded only on request — `config=`, `synthetic=True` or
     $REAZONSPEECH_AMD_SYNTHETIC=1 — and a warning says so."""
     from ...runtime.config import ESPNET_CONFORMER_120M
     from ...runtime.weights_espnet import synthetic_state_dict_espnet
-    from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES
+    from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES, check_nbest
+    check_nbest(nbest, beam_size if beam_size is not None else (1 if config is not None or synthetic else 20))     # argument errors first
     from ...runtime.resample import check_mode
     if segmentation not in SEGMENTATION_MODES:
         raise ValueError(f"segmentation must be one of {SEGMENTATION_MODES}, got {segmentation!r}")
@@ -78,7 +87,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
             raise FileNotFoundError(f"checkpoint {checkpoint!r} does not exist")
         cfg, sd, tokens = read_espnet(checkpoint)
         return EspnetModel(cfg, sd, tokens, device=device, beam_size=20 if beam_size is None else beam_size, max_pops=max_pops,
-                           precision=precision, segmentation=segmentation, resample=resample, token_scores=token_scores)
+                           precision=precision, segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest)
     cfg = config or ESPNET_CONFORMER_120M
     if config is None:
         if not (synthetic or os.environ.get("REAZONSPEECH_AMD_SYNTHETIC", "0") not in ("", "0")):
@@ -89,7 +98,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
               "(`synthetic=True` / $REAZONSPEECH_AMD_SYNTHETIC): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
     return EspnetModel(cfg, synthetic_state_dict_espnet(cfg, seed), synthetic_token_list(cfg.vocab_size, seed), device=device,
                        beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision,
-                       segmentation=segmentation, resample=resample, token_scores=token_scores)
+                       segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest)
 
 
 def _windows(model, waveform, window):

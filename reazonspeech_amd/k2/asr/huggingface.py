@@ -58,7 +58,7 @@ def resolve_checkpoint(language, precision, checkpoint=None):
 
 def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
                decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host", hotwords_file="",
-               hotwords_score=1.5, hotwords=None, token_scores=False, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
+               hotwords_score=1.5, hotwords=None, token_scores=False, nbest=0, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -103,6 +103,11 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
         are the symbols of tokens.txt as written there, "ids" = decimal ids; "nemo" and anything else raise ValueError, as do an
         alpha that is no finite number >= 0 and an LM with "greedy_search".  Stored as `model.ngram_lm` / `model.ngram_lm_alpha`,
         both may be set later; `transcribe(..., ngram_lm_alpha=)` takes a weight for one call.
+      nbest (int): this project's addition — sherpa-onnx returns one hypothesis per stream.  N in 1..8 with "modified_beam_search"
+        makes `stream.result.nbest` (and `transcribe(...).nbest`) the N best hypotheses of the search's last set, ranked on the
+        device by the rule that picks the winner (include/rs_asr.h rs_rnnt_mbs_nbest): results with tokens / timestamps / text /
+        log_prob; entry 0 is the result itself; fewer than N when the last set is smaller.  0 (default) = off, today's objects.
+        N above `max_active_paths`, or N > 1 with "greedy_search", raises ValueError.  Stored as `model.nbest`, may be set later.
       resample (str): where `transcribe` / `transcribe_batch` normalise input at another rate than 16 kHz or with several channels
         (`norm_audio`): "host" (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count)
         group of a call (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`;
@@ -124,14 +129,14 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     check_mode(resample)
     from .model import search_config
     search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
-                  ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+                  ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, nbest)
     if isinstance(ngram_lm_model, (str, os.PathLike)) and ngram_lm_model and not os.path.isfile(ngram_lm_model):
         raise FileNotFoundError(f"ngram_lm_model {str(ngram_lm_model)!r} does not exist")
     if hotwords_file and not os.path.isfile(hotwords_file):
         raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
     search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample,
                   hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords, token_scores=token_scores,
-                  ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens)
+                  ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens, nbest=nbest)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):

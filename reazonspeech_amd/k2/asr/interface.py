@@ -46,6 +46,23 @@ class ScoredTranscribeResult(TranscribeResult):
     subword_logprobs: List[float] = field(default_factory=list)
 
 
+@dataclass
+class NBestTranscribeResult(TranscribeResult):
+    """What `transcribe()` returns from a model loaded with `nbest=N` (this project's addition; sherpa-onnx has no n-best): the
+    result as ever, plus `nbest` — the N best hypotheses of the modified beam search's last set as results of this same type,
+    ranked by `norm_log_prob` (log_prob / len(ys) as sherpa-onnx normalises it), entry 0 equal to the result itself, fewer than N
+    when the last set is smaller.  `log_prob` is the hypothesis's total log-probability with hotword and LM terms inside.  The
+    token fields are those of ScoredTranscribeResult: filled for the result and entry 0 when the model also has `token_scores=True`,
+    None for every other entry (and for all of them with `token_scores` off)."""
+    log_prob: Optional[float] = None
+    norm_log_prob: Optional[float] = None
+    nbest: List["NBestTranscribeResult"] = field(default_factory=list)
+    token_ids: Optional[List[int]] = None
+    token_logprobs: Optional[List[float]] = None
+    confidence: Optional[float] = None
+    subword_logprobs: Optional[List[float]] = None
+
+
 def mean_confidence(logprobs):
     """exp(mean(logprobs)), None for an empty list"""
     return float(np.exp(np.mean(np.asarray(logprobs, np.float64)))) if len(logprobs) else None

@@ -19,8 +19,12 @@ _BYTE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
 
 
 class _Result:
-    def __init__(self, tokens, timestamps, text, token_ids=None, token_log_probs=None):
+    def __init__(self, tokens, timestamps, text, token_ids=None, token_log_probs=None, log_prob=None, norm_log_prob=None, nbest=None):
         self.tokens, self.timestamps, self.text = tokens, timestamps, text
+        # n-best (this project's addition: sherpa-onnx returns one hypothesis): `nbest` = the ranked results of the last set, each
+        # with tokens / timestamps / text / log_prob (the hypothesis's total log-probability, hotword and LM terms inside) and
+        # norm_log_prob (what they are ranked by); entry 0 is this result.  None unless the model was loaded with nbest=N.
+        self.log_prob, self.norm_log_prob, self.nbest = log_prob, norm_log_prob, nbest
         # token_scores: the ids behind `tokens` and the log-probability of each ([UPSTREAM] sherpa-onnx keeps per-token log-probs in
         # its hypotheses); None with the option off
         self.token_ids, self.token_log_probs = token_ids, token_log_probs
@@ -68,11 +72,16 @@ DECODING_METHODS = ("greedy_search", "modified_beam_search")      # sherpa-onnx'
 
 
 def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, hotwords_file="", hotwords_score=1.5,
-                  hotwords=None, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
+                  hotwords=None, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces", nbest=0):
     """`cfg` with the search sherpa_onnx.OfflineRecognizer.from_transducer's keywords ask for (its names and defaults);
     ValueError for anything it does not have or this package does not run.  Needs no GPU.  The hotwords keywords are checked
     here (upstream refuses them with greedy_search too); the graph itself is the model's, not the configuration's.  So are the
-    n-gram LM keywords (runtime/ngram_lm.py: k2_check_keywords): an LM with greedy_search raises."""
+    n-gram LM keywords (runtime/ngram_lm.py: k2_check_keywords): an LM with greedy_search raises.  `nbest` (this project's
+    addition, 0 = off) must be an integer in 0..8, at most max_active_paths, and above 1 needs the modified beam search."""
+    if not (isinstance(nbest, int) and not isinstance(nbest, bool) and 0 <= nbest <= 8):
+        raise ValueError(f"nbest must be an integer in 0..8, not {nbest!r}")
+    if nbest > 1 and decoding_method == "greedy_search":
+        raise ValueError(f"nbest={nbest} needs decoding_method='modified_beam_search' (greedy_search keeps one hypothesis)")
     has_hotwords = bool(hotwords_file) or (hotwords is not None and len(hotwords) > 0)
     if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
         raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
@@ -89,6 +98,8 @@ def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blan
         return cfg.with_(decoding="greedy_batch", beam_size=1, blank_penalty=0.0)
     if not (isinstance(max_active_paths, int) and 1 <= max_active_paths <= 8):
         raise ValueError(f"max_active_paths must be an integer in 1..8, not {max_active_paths!r}")
+    if nbest > max_active_paths:
+        raise ValueError(f"nbest={nbest} is above max_active_paths={max_active_paths}: the search keeps no more hypotheses than that")
     return cfg.with_(decoding="modified_beam_search", beam_size=int(max_active_paths), blank_penalty=float(blank_penalty))
 
 
@@ -103,8 +114,14 @@ class K2Model:
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
                  decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host",
                  hotwords_file="", hotwords_score=1.5, hotwords=None, token_scores=False, ngram_lm_model=None, ngram_lm_alpha=0.0,
-                 ngram_lm_tokens="pieces"):
-        """ngram_lm_model / ngram_lm_alpha / ngram_lm_tokens: shallow fusion of a backoff n-gram language model into the modified beam
+                 ngram_lm_tokens="pieces", nbest=0):
+        """nbest: this project's addition (sherpa-onnx returns one hypothesis per stream): N >= 1 with the modified beam search makes
+        `stream.result.nbest` the N best hypotheses of the search's last set, ranked on the device by log_prob / len(ys) as the
+        winner is chosen (include/rs_asr.h rs_rnnt_mbs_nbest) — results with tokens / timestamps / text / log_prob / norm_log_prob,
+        entry 0 the result itself, fewer than N when the last set is smaller.  0 (default): `result.nbest` is None.  N above
+        max_active_paths, or N > 1 with greedy_search, raises ValueError.  With token_scores, entry 0 carries the token
+        log-probabilities and the other entries None.
+        ngram_lm_model / ngram_lm_alpha / ngram_lm_tokens: shallow fusion of a backoff n-gram language model into the modified beam
         search (include/rs_asr.h rs_rnnt_mbs_lm: the LM term is added to the K survivors of a frame, after the selection): an ARPA
         text file (`.gz` allowed) or an `NgramLm` of runtime/ngram_lm.py, its weight, and how a word of the file names a token:
         "pieces" (default) = the symbols of tokens.txt as written there, "ids" = decimal ids; "nemo" raises ValueError.  Stored as
@@ -131,14 +148,15 @@ class K2Model:
         a longer utterance grows them (AsrModel.ensure_pos_cap), so this only moves the first growth"""
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
         cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
-                            ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+                            ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, nbest)
         self.cfg = cfg
         self.tokens = list(tokens)
         self.hotwords_score = float(hotwords_score)
         self.hotwords = self.hotword_graph(hotwords, hotwords_file)       # the model's graph (None = no hotwords)
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded
         cap = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, token_scores=token_scores, **cap)
+        self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, token_scores=token_scores,
+                           nbest=nbest if cfg.decoding == "modified_beam_search" else 0, **cap)
         self.device = self.am.device
         if self.hotwords is not None:
             self.am.hotword_set((self.hotwords,))         # checked and uploaded once, at load
@@ -197,6 +215,15 @@ class K2Model:
     def ngram_lm_alpha(self, alpha):
         self.am.ngram_lm_alpha = ngram.check_alpha(alpha)
 
+    # entries of `stream.result.nbest` (0 = off): the runtime model's option, settable
+    @property
+    def nbest(self):
+        return self.am.nbest
+
+    @nbest.setter
+    def nbest(self, n):
+        self.am.nbest = self.am.nbest_plan(n)
+
     # ---- sherpa-onnx's surface ------------------------------------------------------------------------------------------
     def create_stream(self, hotwords=None):
         """hotwords: sherpa-onnx's per-stream hotwords — a string of phrases separated by `/` (or a list), each with an optional
@@ -215,6 +242,11 @@ class K2Model:
         res = self.am.transcribe_waveforms([st.samples for st in streams], hotwords=stream_graphs(self.hotwords, streams), ngram_lm=lm)
         for k, (st, ids, frames) in enumerate(zip(streams, res.ids, res.frames)):
             st.result = self.convert(ids, frames, res.token_logprobs[k] if res.token_logprobs is not None else None)
+            if res.nbest is not None:                     # the ranked list; entry 0 is the result itself
+                entries = [self.convert(y, fr) for y, fr, _, _ in res.nbest[k][1:]]
+                for r, (_, _, lp, norm) in zip([st.result] + entries, res.nbest[k]):
+                    r.log_prob, r.norm_log_prob = lp, norm
+                st.result.nbest = ([st.result] + entries) if res.nbest[k] else []
 
     # ---- result conversion ------------------------------------------------------------------------------------------------
     def symbol(self, i):

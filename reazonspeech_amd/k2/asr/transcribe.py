@@ -3,7 +3,7 @@ silence on both sides, warn above TOO_LONG_SECONDS, decode one stream, pair toke
 import warnings
 
 from ...runtime.resample import norm_batch
-from .interface import AudioData, TranscribeConfig, TranscribeResult, ScoredTranscribeResult, Subword, mean_confidence
+from .interface import AudioData, TranscribeConfig, TranscribeResult, ScoredTranscribeResult, NBestTranscribeResult, Subword, mean_confidence
 from .audio import pad_audio, norm_audio, SAMPLERATE
 
 PAD_SECONDS = 0.9
@@ -33,7 +33,22 @@ def _pad_and_warn(audio):
     return audio
 
 
+def _entry(r):
+    """one result of `stream.result.nbest` -> NBestTranscribeResult without its own list"""
+    subwords = [Subword(token=t, seconds=s) for t, s in zip(r.tokens, r.timestamps)]
+    lp = r.token_log_probs
+    scored = {} if lp is None else dict(token_ids=list(r.token_ids), token_logprobs=list(lp), confidence=mean_confidence(lp), subword_logprobs=list(lp))
+    return NBestTranscribeResult(r.text, subwords, log_prob=r.log_prob, norm_log_prob=r.norm_log_prob, **scored)
+
+
 def _result(stream):
+    if getattr(stream.result, "nbest", None) is not None:     # a model loaded with nbest=N: entry 0 is the result itself
+        entries = [_entry(r) for r in stream.result.nbest]
+        if not entries:                                        # no frames: no hypothesis was ranked
+            return NBestTranscribeResult(stream.result.text, [])
+        head = _entry(stream.result.nbest[0])
+        head.nbest = entries
+        return head
     subwords = [Subword(token=t, seconds=s) for t, s in zip(stream.result.tokens, stream.result.timestamps)]
     lp = getattr(stream.result, "token_log_probs", None)
     if lp is not None:                   # a model loaded with token_scores=True

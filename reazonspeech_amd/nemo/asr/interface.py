@@ -60,6 +60,32 @@ class ScoredTranscribeResult(TranscribeResult):
     segment_confidence: List[float] = field(default_factory=list)
 
 
+@dataclass
+class NBestTranscribeResult(TranscribeResult):
+    """What `transcribe()` returns from a model loaded with `nbest=N` and the ALSD search (additive; NeMo's beam decoding with
+    `return_best_hypothesis=False`): the result as ever, plus `nbest` — the N best finished hypotheses as results of this same type,
+    ranked on the device by `norm_score` (score / (labels + 1) with the search's score normalisation; include/rs_asr.h
+    rs_rnnt_alsd_nbest), equal label sequences kept once, entry 0 equal to the result itself in text, subwords, segments and score.
+    `score` is the hypothesis's log-probability with hotword and LM terms inside.  The token fields are those of
+    ScoredTranscribeResult: filled for entry 0 when the model also has `token_scores=True`, None for every other entry.  With
+    `raw_hypothesis`, `hypothesis` is an NBestHypotheses whose `n_best_hypotheses` are the entries' Hypothesis objects."""
+    score: Optional[float] = None
+    norm_score: Optional[float] = None
+    nbest: List["NBestTranscribeResult"] = field(default_factory=list)
+    token_ids: Optional[List[int]] = None
+    token_logprobs: Optional[List[float]] = None
+    confidence: Optional[float] = None
+    subword_logprobs: Optional[List[float]] = None
+    segment_confidence: Optional[List[float]] = None
+
+
+class NBestHypotheses:
+    """[UPSTREAM] NeMo's NBestHypotheses: what `raw_hypothesis` carries when the lists are on"""
+
+    def __init__(self, n_best_hypotheses):
+        self.n_best_hypotheses = list(n_best_hypotheses)
+
+
 def mean_confidence(logprobs):
     """exp(mean(logprobs)), None for an empty list"""
     return float(np.exp(np.mean(np.asarray(logprobs, np.float64)))) if len(logprobs) else None

@@ -60,7 +60,7 @@ SYNTHETIC_ENV = "REAZONSPEECH_AMD_SYNTHETIC"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, decoding=None, beam_size=None,
-               precision="bf16", synthetic=False, resample="host", token_scores=False, hotwords_file="", hotwords_score=1.5, hotwords=None,
+               precision="bf16", synthetic=False, resample="host", token_scores=False, nbest=0, hotwords_file="", hotwords_score=1.5, hotwords=None,
                ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="nemo"):
     """Load the ReazonSpeech FastConformer-RNNT model onto a ROCm GPU.
 
@@ -91,6 +91,11 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         "device" = one HIP launch per (rate, channel count) group of a `transcribe_batch` call (`AsrModel.resample_batch`,
         rs_resample) with the host path's Kaiser filter — float32 rounding apart from the host path's result without soxr.
         Stored as `model.resample`, may be changed later.  Anything else raises ValueError.
+      nbest (int): N in 1..8, at most `beam_size`, with `decoding="alsd"`: every result is an `NBestTranscribeResult` (interface.py)
+        whose `nbest` holds the N best finished hypotheses — NeMo's `return_best_hypothesis=False`: `sort_nbest(final)` with equal
+        label sequences kept once, ranked inside the search's selection kernel (rs_rnnt_alsd_nbest); entry 0 is the result itself;
+        with `raw_hypothesis`, `hypothesis.n_best_hypotheses`.  0 (default): today's objects.  N above the beam, or N > 1 with a
+        greedy decoding, raises ValueError.  Stored as `model.nbest`; `transcribe(..., nbest=N)` takes a count for one call.
       token_scores (bool): every result is a `ScoredTranscribeResult` (interface.py): the log-probability of every emitted token
         under the model's own distribution, per subword, and confidences per segment and utterance (exp of the mean) — computed on
         the device right after the search (rs_rnnt_token_scores), valid with every `precision` and `decoding`; with
@@ -172,7 +177,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
     has_hotwords = nemo_hotwords.check_keywords(cfg.decoding, hotwords_file, hotwords_score, hotwords)
     ngram_lm.check_keywords(cfg.decoding, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)      # the checkpoint's own strategy is known now
-    model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, **kw)
+    model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, nbest=nbest, **kw)
     model.hotwords_score = float(hotwords_score)
     if has_hotwords:
         model.hotwords = nemo_hotwords.model_graph(model, hotwords, hotwords_file)     # the model's graph (None = nothing left to bias)
@@ -215,7 +220,14 @@ def transcribe_batch(model, audios, config=None, distributed=False, hotwords=Non
     return _transcribe_graphs(model, audios, config, distributed, graphs)
 
 
-def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alpha=None):
+def _nbest_result(ret, score, norm):
+    """a decoded hypothesis as an NBestTranscribeResult (the token fields only where `decode_hypothesis` scored it)"""
+    from .interface import NBestTranscribeResult
+    scored = {k: getattr(ret, k) for k in ("token_ids", "token_logprobs", "confidence", "subword_logprobs", "segment_confidence") if hasattr(ret, k)}
+    return NBestTranscribeResult(ret.text, ret.subwords, ret.segments, ret.hypothesis, score=score, norm_score=norm, **scored)
+
+
+def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alpha=None, nbest=None):
     """`transcribe_batch` with the hotwords resolved: `graphs` = None, or one HotwordGraph / None per audio; `ngram_lm_alpha`: the
     n-gram LM's weight in this call (None = the model's value, 0 = without the LM; a value with no LM loaded raises ValueError)"""
     from ...runtime import ngram_lm
@@ -244,6 +256,21 @@ def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alph
             ret = decode_hypothesis(model, hyp, lp)
             if config.raw_hypothesis:
                 ret.hypothesis = hyp
+            if decoded.nbest is not None:                 # the ranked list: entry 0 is the result itself
+                from .interface import NBestHypotheses
+                entries, hyps = [], []
+                for r, (y, fr, score, norm) in enumerate(decoded.nbest[k]):
+                    h = hyp if r == 0 else Hypothesis.from_alsd(y, [f + idx for idx, f in enumerate(fr)], model.cfg.blank_id)
+                    h.score = score
+                    e = _nbest_result(ret if r == 0 else decode_hypothesis(model, h), score, norm)
+                    entries.append(e)
+                    hyps.append(h)
+                ret = _nbest_result(ret, decoded.nbest[k][0][2], decoded.nbest[k][0][3]) if entries else _nbest_result(ret, None, None)
+                ret.nbest = entries
+                if config.raw_hypothesis:
+                    ret.hypothesis = NBestHypotheses(hyps)
+                    for e, h in zip(entries, hyps):
+                        e.hypothesis = h
             results[i] = ret
 
     if distributed and getattr(model, "token_scores", False):
@@ -252,7 +279,7 @@ def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alph
     if distributed:
         to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves, hotwords=graphs, **_lm_kw(lm)))
     else:
-        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs, **_lm_kw(lm))
+        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs, nbest=nbest, **_lm_kw(lm))
     return results
 
 
@@ -261,7 +288,7 @@ def _lm_kw(lm):
     return {"ngram_lm": lm}
 
 
-def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None):
+def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nbest=None):
     """Inference of one utterance (transcribe.py:30-60).
 
     Args:
@@ -272,6 +299,9 @@ def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None):
             phrases, each with an optional ` :score`; None = the model's hotwords, if any (needs `decoding="alsd"`)
         ngram_lm_alpha: the weight of the model's n-gram LM in this call: None = `model.ngram_lm_alpha`, 0 = this call without the
             LM; a value when no LM is loaded raises ValueError
+        nbest: entries of the n-best list in this call: None = `model.nbest`, 0 = without the list, N = the N best finished
+            hypotheses (`NBestTranscribeResult.nbest`; needs `decoding="alsd"` and N <= beam_size, ValueError otherwise).
+            `transcribe_batch` decodes with `model.nbest`.
 
     Returns:
         TranscribeResult
@@ -280,4 +310,4 @@ def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None):
         config = TranscribeConfig()
     from ...runtime import nemo_hotwords
     graphs = nemo_hotwords.per_audio(model, hotwords, 1, single=True)
-    return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha)[0]
+    return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha, nbest)[0]

@@ -37,6 +37,9 @@ EXPORTS = [
     "rs_rnnt_alsd_hotwords", "rs_rnnt_alsd_hotwords_workspace_bytes",
     "rs_rnnt_alsd_lm", "rs_rnnt_alsd_lm_workspace_bytes", "rs_ngram_check",
     "rs_rnnt_mbs_lm", "rs_rnnt_mbs_lm_workspace_bytes",
+    "rs_rnnt_mbs_nbest", "rs_rnnt_mbs_nbest_workspace_bytes",
+    "rs_rnnt_beam_nbest", "rs_rnnt_beam_nbest_workspace_bytes",
+    "rs_rnnt_alsd_nbest", "rs_rnnt_alsd_nbest_workspace_bytes",
     "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
@@ -241,6 +244,10 @@ def load():
     lib.rs_rnnt_beam_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_beam.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_beam.restype = c_int
+    lib.rs_rnnt_beam_nbest_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int, c_int]
+    lib.rs_rnnt_beam_nbest_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_beam_nbest.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, vp]
+    lib.rs_rnnt_beam_nbest.restype = c_int
     # the searches with variants: one prefix (up to `scores`) and one tail (workspace, its size, stream); a variant adds its tables between
     tail, hw_args = [vp, c_size_t, vp], [POINTER(RsHotwords), vp]
     mbs = [vp, vp, vp, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp, vp]
@@ -249,6 +256,11 @@ def load():
     lib.rs_rnnt_mbs_lm.argtypes = mbs + hw_args + [POINTER(RsNgram), c_float] + tail
     for fn in (lib.rs_rnnt_mbs_workspace_bytes, lib.rs_rnnt_mbs_hotwords_workspace_bytes, lib.rs_rnnt_mbs_lm_workspace_bytes):
         fn.argtypes, fn.restype = [vp, c_int, c_int, c_int, c_int], c_size_t
+    # the n-best entry: `nbest` before out_cap, norm_scores and n_hyps after scores, then the most general tables
+    lib.rs_rnnt_mbs_nbest.argtypes = mbs[:8] + [c_int] + mbs[8:] + [vp, vp] + hw_args + [POINTER(RsNgram), c_float] + tail
+    lib.rs_rnnt_mbs_nbest.restype = c_int
+    lib.rs_rnnt_mbs_nbest_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int, c_int]
+    lib.rs_rnnt_mbs_nbest_workspace_bytes.restype = c_size_t
     lib.rs_hotwords_check.argtypes = [POINTER(RsHotwords), c_char_p, c_size_t]
     lib.rs_rnnt_token_scores_workspace_bytes.argtypes = [vp, c_int, c_int]
     lib.rs_rnnt_token_scores_workspace_bytes.restype = c_size_t
@@ -260,6 +272,10 @@ def load():
     lib.rs_rnnt_alsd_lm.argtypes = alsd + hw_args + [POINTER(RsNgram), c_float] + tail
     for fn in (lib.rs_rnnt_alsd_workspace_bytes, lib.rs_rnnt_alsd_hotwords_workspace_bytes, lib.rs_rnnt_alsd_lm_workspace_bytes):
         fn.argtypes, fn.restype = [vp, c_int, c_int, c_int, c_double, c_int], c_size_t
+    lib.rs_rnnt_alsd_nbest.argtypes = alsd[:9] + [c_int] + alsd[9:] + [vp, vp] + hw_args + [POINTER(RsNgram), c_float] + tail
+    lib.rs_rnnt_alsd_nbest.restype = c_int
+    lib.rs_rnnt_alsd_nbest_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int, c_int]
+    lib.rs_rnnt_alsd_nbest_workspace_bytes.restype = c_size_t
     lib.rs_ngram_check.argtypes = [POINTER(RsNgram), c_char_p, c_size_t]
     lib.rs_profile_enable.argtypes = [vp, c_int]
     lib.rs_profile_reset.argtypes = [vp]
@@ -504,6 +520,28 @@ class Context:
             raise RuntimeError(f"{name}: invalid arguments" + (" (a finalized Conformer context, B > 0, beam > 0)" if lm or hotwords else ""))
         return n
 
+    def alsd_nbest_workspace_bytes(self, B, beam, tp_max, max_target_len, nbest):
+        """the workspace of `rnnt_alsd_nbest`, from the entry's own query"""
+        ratio, abs_len = self._alsd_budget(max_target_len)
+        n = self.lib.rs_rnnt_alsd_nbest_workspace_bytes(self._h, B, beam, tp_max, ratio, abs_len, nbest)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_alsd_nbest_workspace_bytes: invalid arguments (a finalized Conformer context, B > 0, nbest 1..8 and <= beam)")
+        return n
+
+    def rnnt_alsd_nbest(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, nbest, ids, steps, n_ids, scores,
+                        norm_scores, n_hyps, ws, stream, *, hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
+        """rs_rnnt_alsd_nbest: ALSD with the `nbest` best finished hypotheses per utterance, ranked during the search — ids / steps int32
+        [B][nbest][out_cap], n_ids int32 [B][nbest], scores / norm_scores float32 [B][nbest], n_hyps int32 [B].  Tables as `rnnt_alsd`;
+        all of them may be absent."""
+        assert ids.dim() == 3 and ids.shape[:2] == (B, nbest) and steps.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
+        assert n_ids.numel() >= B * nbest and scores.numel() >= B * nbest and norm_scores.numel() >= B * nbest and n_hyps.numel() >= B
+        ratio, abs_len = self._alsd_budget(max_target_len)
+        flags = (ALSD_SCORE_NORM if score_norm else 0) | (ALSD_MERGE if merge else 0)
+        self.check(self.lib.rs_rnnt_alsd_nbest(
+            self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, ratio, abs_len, flags, int(nbest), ids.shape[2], _ptr(ids), _ptr(steps),
+            _ptr(n_ids), _ptr(scores), _ptr(norm_scores), _ptr(n_hyps), byref(hotwords) if hotwords is not None else None, _ptr(graph_of),
+            byref(lm) if lm is not None else None, float(lm_alpha), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
+
     def rnnt_alsd(self, joint_enc, enc_lens, B, tp_max, beam, max_target_len, score_norm, merge, ids, steps, n_ids,
                   scores, ws, stream, *, hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
         """ids / steps int32 [B][out_cap], n_ids int32 [B], scores float32 [B].
@@ -538,6 +576,22 @@ class Context:
                                          int(max_pops), ids.shape[1], _ptr(ids), _ptr(frames) if frames is not None else None, _ptr(n_ids), _ptr(scores), _ptr(pops), _ptr(ws),
                                          ws.numel() * ws.element_size(), c_void_p(stream)))
 
+    def beam_nbest_workspace_bytes(self, B, beam, tp_max, max_pops, nbest):
+        n = self.lib.rs_rnnt_beam_nbest_workspace_bytes(self._h, B, beam, tp_max, max_pops, nbest)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_beam_nbest_workspace_bytes: invalid arguments (a finalized Conformer context, nbest 1..8 and <= beam)")
+        return n
+
+    def rnnt_beam_nbest(self, joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, nbest, ids, n_ids, scores, norm_scores, n_hyps,
+                        pops, ws, stream, frames=None):
+        """rs_rnnt_beam_nbest: ESPnet's default beam search with upstream's `sort_nbest(kept_hyps)[:nbest]` — ids (and frames,
+        optional) int32 [B][nbest][out_cap], n_ids int32 [B][nbest], scores / norm_scores float32 [B][nbest], n_hyps / pops int32 [B]"""
+        assert ids.dim() == 3 and ids.shape[:2] == (B, nbest) and (frames is None or frames.shape == ids.shape)
+        assert n_ids.numel() >= B * nbest and scores.numel() >= B * nbest and norm_scores.numel() >= B * nbest and n_hyps.numel() >= B
+        self.check(self.lib.rs_rnnt_beam_nbest(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, 1 if score_norm else 0, int(max_pops),
+                                               int(nbest), ids.shape[2], _ptr(ids), _ptr(frames), _ptr(n_ids), _ptr(scores), _ptr(norm_scores),
+                                               _ptr(n_hyps), _ptr(pops), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
+
     def mbs_workspace_bytes(self, B, max_active_paths, tp_max, out_cap, *, hotwords=False, lm=False):
         """the workspace of `rnnt_mbs` called with a hotword set (`hotwords`) and / or an n-gram LM (`lm`), from the entry's own query"""
         name = "rs_rnnt_mbs_lm_workspace_bytes" if lm else "rs_rnnt_mbs_hotwords_workspace_bytes" if hotwords else "rs_rnnt_mbs_workspace_bytes"
@@ -564,6 +618,27 @@ class Context:
             self.check(self.lib.rs_rnnt_mbs_hotwords(*head, *hw, *tail))
         else:
             self.check(self.lib.rs_rnnt_mbs(*head, *tail))
+
+    def mbs_nbest_workspace_bytes(self, B, max_active_paths, tp_max, out_cap, nbest):
+        """the workspace of `rnnt_mbs_nbest`, from the entry's own query"""
+        n = self.lib.rs_rnnt_mbs_nbest_workspace_bytes(self._h, B, max_active_paths, tp_max, out_cap, nbest)
+        if n == 0:
+            raise RuntimeError("rs_rnnt_mbs_nbest_workspace_bytes: invalid arguments (a finalized Zipformer context, max_active_paths 1..8, "
+                               "nbest 1..max_active_paths)")
+        return n
+
+    def rnnt_mbs_nbest(self, joint_enc, enc_lens, B, tp_max, max_active_paths, blank_penalty, length_norm, nbest, ids, frames, n_ids,
+                       scores, norm_scores, n_hyps, ws, stream, *, hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
+        """rs_rnnt_mbs_nbest: the modified beam search with the `nbest` best hypotheses of the last set per utterance — ids / frames
+        int32 [B][nbest][out_cap], n_ids int32 [B][nbest], scores / norm_scores float32 [B][nbest] (log_prob, and the value the
+        entries are ranked by), n_hyps int32 [B] (valid entries).  Tables as `rnnt_mbs`; all of them may be absent."""
+        assert ids.dim() == 3 and ids.shape[:2] == (B, nbest) and frames.shape == ids.shape and (graph_of is None or graph_of.numel() >= B)
+        assert n_ids.numel() >= B * nbest and scores.numel() >= B * nbest and norm_scores.numel() >= B * nbest and n_hyps.numel() >= B
+        self.check(self.lib.rs_rnnt_mbs_nbest(
+            self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, int(max_active_paths), float(blank_penalty),
+            MBS_LENGTH_NORM if length_norm else 0, int(nbest), ids.shape[2], _ptr(ids), _ptr(frames), _ptr(n_ids), _ptr(scores),
+            _ptr(norm_scores), _ptr(n_hyps), byref(hotwords) if hotwords is not None else None, _ptr(graph_of),
+            byref(lm) if lm is not None else None, float(lm_alpha), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))
 
     def token_scores_workspace_bytes(self, B, u_cap):
         """the MINIMUM workspace of `rnnt_token_scores` (32 rows per chunk); a larger one makes fewer chunks, same bits"""

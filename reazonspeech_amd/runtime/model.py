@@ -30,6 +30,9 @@ class DecodedBatch:
     enc_lens: List[int]
     scores: Optional[List[float]] = None
     degraded: Optional[List[bool]] = None     # per utterance: the requested search overflowed its bound and a weaker one was used (espnet `_search`)
+    # n-best (`AsrModel.nbest` / `decode(nbest=)`): per utterance the ranked list [(ids, frames, score, norm_score)], entry 0 = the
+    # hypothesis above; None when not asked for
+    nbest: Optional[List[list]] = None
     token_logprobs: Optional[List[List[float]]] = None   # `AsrModel.token_scores`: log-probability of every id under the model's own distribution
 
 
@@ -69,6 +72,10 @@ class _Buffers:
         self.lm = None                  # n-gram LM of the batch (ALSD, modified beam search): (_NgramSet, alpha) or None; `stage` / `fill_host` set it
         self.ws_alsd = None              # beam-search scratch (grows with beam and alignment length): on first use
         self.score_bufs = None           # token scores (`AsrModel.score`): (workspace, logp, top1), on first use
+        self.nbest_bufs = None           # n-best lists (`AsrModel.decode`): ids, frames, n_ids, scores, norm_scores, n_hyps, on first use
+        self.want_nbest = 0              # entries asked for per utterance (`stage` / `fill_host` set it; 0 = the one hypothesis)
+        self.nbest_n = 0                 # entries the last `decode` wrote per utterance (0 = it ran without lists)
+        self.h_nbest = None              # the lists on the host (a pipeline worker copied them back)
         self.ws = torch.empty((ctx.workspace_bytes(B, self.l_pad),), dtype=torch.uint8, device=dev)
         # the decoder of batch i overlaps the encoder of batch i+1 in the pipelined path: own scratch
         self.ws_dec = torch.empty((ctx.workspace_bytes(B, 16),), dtype=torch.uint8, device=dev)
@@ -124,10 +131,19 @@ class _BufView:
         self.ws, self.ws_dec = base.ws, base.ws_dec
         self.h_audio, self.h_lens = cut(base.h_audio, B, l_max), base.h_lens
         self.h_out = None
+        self.want_nbest, self.nbest_n, self.h_nbest = 0, 0, None
         self.step = -1
 
     def narrow(self, l_max):
         return self.base.narrow(l_max)
+
+    @property
+    def nbest_bufs(self):
+        return self.base.nbest_bufs
+
+    @nbest_bufs.setter
+    def nbest_bufs(self, v):
+        self.base.nbest_bufs = v
 
     @property
     def score_bufs(self):
@@ -175,8 +191,13 @@ class AsrModel:
     HOTWORD_SETS = 8        # graph sets kept on the device (least recently used dropped)
 
     def __init__(self, cfg: ModelConfig, state_dict, tokenizer, device="cuda", pos_cap: int = DEFAULT_POS_CAP,
-                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host", token_scores: bool = False):
-        """token_scores: every decode is followed by `score` (rs_rnnt_token_scores, csrc/k_rnnt_scores.hip) on the same stream and
+                 pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host", token_scores: bool = False,
+                 nbest: int = 0):
+        """nbest: 0 (default) = every search returns its one hypothesis; N >= 1 = the search also returns its N best hypotheses per
+        utterance, ranked on the device (`DecodedBatch.nbest`; include/rs_asr.h rs_rnnt_mbs_nbest / rs_rnnt_beam_nbest state the
+        ranking, rs_rnnt_alsd_nbest too).  Built for every beam search; N above the beam, or N > 1 with a
+        greedy search, raises ValueError (`nbest_plan`).  May be changed later.
+        token_scores: every decode is followed by `score` (rs_rnnt_token_scores, csrc/k_rnnt_scores.hip) on the same stream and
         `DecodedBatch.token_logprobs` is filled; off (default): nothing runs and nothing is allocated.  May be changed later.
         resample: where the packages' `norm_audio` work (resample to 16 kHz, average the channels) is done for input at another
         rate or with several channels: "host" (default) = scipy / soxr per utterance as before, "device" = `resample_batch`.
@@ -187,6 +208,8 @@ class AsrModel:
         from .resample import check_mode
         self.resample = check_mode(resample)
         self.token_scores = bool(token_scores)
+        self.cfg = cfg
+        self.nbest = self.nbest_plan(nbest)     # (an impossible count is refused before anything is loaded)
         self._resample_tables = {}      # rate -> the plan's table on the device
         if precision not in ("bf16", "fp32", "fp32x3", "int8"):
             raise ValueError(f"precision must be 'bf16', 'fp32', 'fp32x3' or 'int8', not {precision!r}")
@@ -429,26 +452,89 @@ class AsrModel:
             buf.ws_alsd = torch.empty((n,), dtype=torch.uint8, device=self.device)
         return buf.ws_alsd
 
-    def decode(self, ctx, buf: _Buffers, ws, stream, max_pops=None, decoding=None):
+    def nbest_plan(self, nbest=None, decoding=None):
+        """`nbest`: None = the model's own (`self.nbest`), or the entries per utterance for this call -> the count the search is run
+        with, 0 = the one hypothesis as ever.  ValueError with the reason for a count the model's search cannot give."""
+        n = getattr(self, "nbest", 0) if nbest is None else nbest
+        if n is None or (isinstance(n, int) and not isinstance(n, bool) and n == 0):
+            return 0
+        if not (isinstance(n, int) and not isinstance(n, bool) and 1 <= n <= 8):
+            raise ValueError(f"nbest must be an integer in 1..8, not {n!r}")
+        decoding = decoding or self.cfg.decoding
+        if decoding not in ("alsd", "beam", "modified_beam_search"):
+            if n > 1:
+                raise ValueError(f"nbest={n} needs a beam search: the greedy search ({decoding!r}) keeps one hypothesis")
+            return 0
+        if n > self.cfg.beam_size:
+            raise ValueError(f"nbest={n} is above the beam ({self.cfg.beam_size}): the search keeps no more hypotheses than that")
+        return n
+
+    def _nbest_bufs(self, buf, n):
+        """the buffer set's n-best outputs for `n` entries per utterance at the batch's label capacity, allocated on first use"""
+        B, u_cap = buf.B, buf.ids.shape[1]
+        nb = buf.nbest_bufs
+        if nb is None or tuple(nb["ids"].shape) != (B, n, u_cap):
+            dev, i32, f32 = self.device, torch.int32, torch.float32
+            nb = dict(ids=torch.zeros((B, n, u_cap), dtype=i32, device=dev), frames=torch.zeros((B, n, u_cap), dtype=i32, device=dev),
+                      n_ids=torch.zeros((B, n), dtype=i32, device=dev), scores=torch.zeros((B, n), dtype=f32, device=dev),
+                      norm_scores=torch.zeros((B, n), dtype=f32, device=dev), n_hyps=torch.zeros((B,), dtype=i32, device=dev))
+            buf.nbest_bufs = nb
+        return nb
+
+    def _nbest_head(self, buf, nb, stream):
+        """entry 0 of every list into buf.ids / frames / n_ids / scores, on `stream`: the search's one result, where `score`,
+        `collect` and the pipeline's copies read it"""
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device)):
+            buf.ids.copy_(nb["ids"][:, 0]); buf.frames.copy_(nb["frames"][:, 0])
+            buf.n_ids.copy_(nb["n_ids"][:, 0]); buf.scores.copy_(nb["scores"][:, 0])
+
+    def decode(self, ctx, buf: _Buffers, ws, stream, max_pops=None, decoding=None, nbest=None):
         """stage 3 on `stream`: the checkpoint's decoding strategy (cfg.decoding).  Greedy fills buf.ids / buf.frames
         (emission frames); ALSD fills buf.ids / buf.frames (alignment steps i = frame + labels before) / buf.scores; the
-        modified beam search of the Zipformer family fills buf.ids / buf.frames (frames) / buf.scores.  All synchronise the stream."""
+        modified beam search of the Zipformer family fills buf.ids / buf.frames (frames) / buf.scores.  All synchronise the stream.
+        `nbest`: entries per utterance of the ranked list the search also leaves in the buffer set's `nbest_bufs` (`collect` reads
+        them into `DecodedBatch.nbest`); None = what the batch was staged with (`buf.want_nbest`), 0 = none.  Entry 0 is copied into
+        buf.ids / frames / n_ids / scores, so everything after the search reads what it reads without lists."""
         cfg = self.cfg
+        n_best = self.nbest_plan(nbest, decoding) if nbest is not None else getattr(buf, "want_nbest", 0)
+        buf.nbest_n = 0
         if max_pops is not None or decoding is not None:     # per-call overrides (the caller's retry policy): never written into self.cfg
             cfg = cfg.with_(**({"beam_max_pops": int(max_pops)} if max_pops is not None else {}), **({"decoding": decoding} if decoding is not None else {}))
         hw = getattr(buf, "hw_set", None)                  # the batch has at least one graph; graph_of goes with a hotword set only
         hot = dict(hotwords=hw.struct, graph_of=buf.graph_of) if hw is not None else {}
         lm = getattr(buf, "lm", None)                      # with an n-gram LM and / or graphs in the batch: the LM / HW forms of the search
         fused = dict(lm=lm[0].struct, lm_alpha=lm[1]) if lm is not None else {}
-        if cfg.decoding == "beam":
+        if cfg.decoding == "beam" and n_best:             # ... with upstream's sort_nbest(kept_hyps)[:nbest] (rs_rnnt_beam_nbest: the same kernels)
+            nb = self._nbest_bufs(buf, n_best)
+            sws = self._search_ws(buf, ctx.beam_nbest_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops, n_best))
+            ctx.rnnt_beam_nbest(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops, n_best,
+                                nb["ids"], nb["n_ids"], nb["scores"], nb["norm_scores"], nb["n_hyps"], buf.pops, sws, stream, frames=nb["frames"])
+            self._nbest_head(buf, nb, stream)
+            buf.nbest_n = n_best
+        elif cfg.decoding == "beam":
             sws = self._search_ws(buf, ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops))
             ctx.rnnt_beam(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops,
                           buf.ids, buf.n_ids, buf.scores, buf.pops, sws, stream, frames=buf.frames)
+        elif cfg.decoding == "modified_beam_search" and n_best:      # ... with its ranked list (rs_rnnt_mbs_nbest: the same kernels)
+            nb = self._nbest_bufs(buf, n_best)
+            sws = self._search_ws(buf, ctx.mbs_nbest_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1], n_best))
+            ctx.rnnt_mbs_nbest(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm, n_best,
+                               nb["ids"], nb["frames"], nb["n_ids"], nb["scores"], nb["norm_scores"], nb["n_hyps"], sws, stream, **hot, **fused)
+            self._nbest_head(buf, nb, stream)
+            buf.nbest_n = n_best
         elif cfg.decoding == "modified_beam_search":      # Zipformer family: sherpa-onnx's second method (csrc/k_rnnt_mbs.hip)
             sws = self._search_ws(buf, ctx.mbs_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1], hotwords=hw is not None,
                                                                lm=lm is not None))
             ctx.rnnt_mbs(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.blank_penalty, cfg.mbs_length_norm,
                          buf.ids, buf.frames, buf.n_ids, buf.scores, sws, stream, **hot, **fused)
+        elif cfg.decoding == "alsd" and n_best:           # ... with the ranked list of finished hypotheses (rs_rnnt_alsd_nbest: the same kernels)
+            nb = self._nbest_bufs(buf, n_best)
+            sws = self._search_ws(buf, ctx.alsd_nbest_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len, n_best))
+            ctx.rnnt_alsd_nbest(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.alsd_max_target_len, cfg.beam_score_norm,
+                                False, n_best, nb["ids"], nb["frames"], nb["n_ids"], nb["scores"], nb["norm_scores"], nb["n_hyps"], sws, stream,
+                                **hot, **fused)
+            self._nbest_head(buf, nb, stream)
+            buf.nbest_n = n_best
         elif cfg.decoding == "alsd":
             sws = self._search_ws(buf, ctx.alsd_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.alsd_max_target_len,
                                                                 hotwords=hw is not None, lm=lm is not None))
@@ -560,6 +646,7 @@ class AsrModel:
                                                  buf.scores.cpu() if self.cfg.has_scores else None)
                                     if self.token_scores:
                                         buf.h_out = buf.h_out + (self.score_view(buf).cpu(),)
+                                    buf.h_nbest = {k: t.cpu() for k, t in buf.nbest_bufs.items()} if buf.nbest_n else None
                             if after_decode is not None:
                                 if i > 0:
                                     hooked[i - 1].wait()
@@ -720,7 +807,7 @@ class AsrModel:
         buf.hw_set = hw
         return True
 
-    def fill_host(self, waveforms: Sequence[np.ndarray], buf, hotwords=None, members=None, lm=None):
+    def fill_host(self, waveforms: Sequence[np.ndarray], buf, hotwords=None, members=None, lm=None, nbest=0):
         """copy host waveforms (16 kHz mono float32, un-padded) into the buffer set's pinned staging buffers; the tail of
         every row is zeroed (the kernels mask by length, this only keeps the padding deterministic).  Returns the view of
         `buf` narrowed to this batch's longest utterance."""
@@ -734,13 +821,14 @@ class AsrModel:
         # `hotwords`: the call's `graph_plan`, `members`: this batch's positions in it (the H2D copy is run_pipelined's)
         self._set_graphs(view, hotwords, members)
         view.lm = lm                             # the call's `lm_plan`
+        view.want_nbest = nbest                  # the call's `nbest_plan`
         return view
 
     def stage(self, waveforms: Sequence[np.ndarray], l_max: Optional[int] = None, buf: Optional[_Buffers] = None, hotwords=None,
-              ngram_lm=None) -> _Buffers:
+              ngram_lm=None, nbest=None) -> _Buffers:
         """copy host waveforms (16 kHz mono float32, un-padded) into a pinned buffer and on to HBM; `hotwords`: the call's
         `graph_plan` (every utterance of it is in this batch), None = no hotwords; `ngram_lm`: as `lm_plan` takes it (None = the
-        model's own LM, if it has one)"""
+        model's own LM, if it has one); `nbest`: as `nbest_plan` takes it (None = the model's own count)"""
         B = len(waveforms)
         longest = max((len(w) for w in waveforms), default=0)
         l_max = max(int(l_max or 0), longest, 1)
@@ -762,6 +850,7 @@ class AsrModel:
             if self._set_graphs(buf, hotwords):
                 buf.graph_of.copy_(buf.h_graph_of, non_blocking=True)
             buf.lm = self.lm_plan(ngram_lm)
+            buf.want_nbest = self.nbest_plan(nbest)
         return buf
 
     RESAMPLE_CHUNK = 1 << 28        # float32 samples (1 GiB) one rs_resample launch takes in, and at most writes
@@ -840,6 +929,7 @@ class AsrModel:
         pipeline worker already copied back (buf.h_out), otherwise they are fetched here; `decoding`: the search that
         produced them when it was overridden for the call (see `decode`)"""
         decoding = decoding or self.cfg.decoding
+        from_worker = host is not None
         if host is None:
             host = (buf.n_ids.cpu(), buf.ids.cpu(), buf.frames.cpu(), buf.enc_lens.cpu(),
                     buf.scores.cpu() if decoding in ("alsd", "beam", "modified_beam_search") else None)
@@ -859,7 +949,25 @@ class AsrModel:
         if len(host) > 5:
             lp = host[5].numpy()
             res.token_logprobs = [lp[b, :n[b]].tolist() for b in range(buf.B)]
+        if getattr(buf, "nbest_n", 0):
+            nb = buf.h_nbest if from_worker and buf.h_nbest is not None else {k: t.cpu() for k, t in buf.nbest_bufs.items()}
+            res.nbest = self.nbest_lists({k: t.numpy() for k, t in nb.items()}, buf.B, decoding)
         return res
+
+    @staticmethod
+    def nbest_lists(nb, B, decoding):
+        """the host copies of a buffer set's n-best outputs -> per utterance [(ids, frames, score, norm_score)], best first"""
+        out = []
+        for b in range(B):
+            rows = []
+            for r in range(int(nb["n_hyps"][b])):
+                m = int(nb["n_ids"][b, r])
+                fr = nb["frames"][b, r, :m]
+                if decoding == "alsd":           # alignment step i = frame + labels emitted before
+                    fr = fr - np.arange(m, dtype=fr.dtype)
+                rows.append((nb["ids"][b, r, :m].tolist(), fr.tolist(), float(nb["scores"][b, r]), float(nb["norm_scores"][b, r])))
+            out.append(rows)
+        return out
 
     def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None, ngram_lm=None) -> DecodedBatch:
         """SPMD form of `transcribe_waveforms` for one process per GPU (`torch.distributed` initialised, RCCL):
@@ -871,6 +979,9 @@ class AsrModel:
         if self.token_scores:
             raise ValueError("token_scores is on: transcribe_waveforms_sharded does not gather token log-probabilities; "
                              "use transcribe_waveforms on each rank, or turn token_scores off")
+        if self.nbest:
+            raise ValueError("nbest is on: transcribe_waveforms_sharded does not gather n-best lists; use transcribe_waveforms on each "
+                             "rank, or set nbest to 0")
 
         def run_local(indices, batch):
             # `batch`: the chunk size of the dealing plan (ragged input is dealt as length-sorted chunks, balanced over the
@@ -897,7 +1008,8 @@ class AsrModel:
                 self._pool_sets = [_Buffers(self, B, l_max) for _ in range(n_sets)]
         return self._pool_sets[:n_sets]
 
-    def transcribe_waveforms(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, on_batch=None, hotwords=None, ngram_lm=None) -> DecodedBatch:
+    def transcribe_waveforms(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, on_batch=None, hotwords=None, ngram_lm=None,
+                             nbest=None) -> DecodedBatch:
         """host float32 waveforms -> token ids / frames (the batched boundary).
 
         `on_batch(indices, decoded)`: called once per batch, in batch order, as soon as that batch's hypotheses are on
@@ -915,15 +1027,19 @@ class AsrModel:
         travels with it through sorting and grouping; a batch without any graph runs the plain search.
 
         `ngram_lm` (ALSD, modified beam search): None = the model's own n-gram LM and weight (`self.ngram_lm`, `self.ngram_lm_alpha`), or
-        (NgramLm or None, alpha) for this call; alpha 0 or no model = the search without an LM (`lm_plan`)."""
+        (NgramLm or None, alpha) for this call; alpha 0 or no model = the search without an LM (`lm_plan`).
+
+        `nbest`: None = the model's own count (`self.nbest`), or the entries per utterance for this call (0 = none): the result's
+        `nbest` then holds every utterance's ranked list (`nbest_plan`: ValueError for a count the search cannot give)."""
         n = len(waveforms)
+        n_best = self.nbest_plan(nbest)
         if n == 0:
-            return DecodedBatch([], [], [])
+            return DecodedBatch([], [], [], nbest=[] if n_best else None)
         waveforms = [np.asarray(w, dtype=np.float32) for w in waveforms]
         plan = self.graph_plan(hotwords, n)
         lm = self.lm_plan(ngram_lm)
         if n <= max_batch:
-            buf = self.stage(waveforms, hotwords=plan, ngram_lm=ngram_lm)
+            buf = self.stage(waveforms, hotwords=plan, ngram_lm=ngram_lm, nbest=n_best)
             self.run_device(buf)
             res = self.collect(buf)
             if on_batch is not None:
@@ -932,6 +1048,7 @@ class AsrModel:
         order = sorted(range(n), key=lambda i: (len(waveforms[i]), i))
         ids, frames, enc_lens, scores = [None] * n, [None] * n, [None] * n, [None] * n
         logprobs = [None] * n if self.token_scores else None
+        lists = [None] * n if n_best else None
         groups = [order[i:i + max_batch] for i in range(0, n, max_batch)]
         # longest batch first: what is left after the last encoder is one decode, and the shortest batch's is the shortest
         # (a ragged list's drain shrinks from the longest batch's decode to the shortest's)
@@ -942,7 +1059,7 @@ class AsrModel:
         pool = self._pool(max_batch, l_max, n_sets)
 
         def fill(i, buf):
-            return self.fill_host([waveforms[k] for k in groups[i]], buf, hotwords=plan, members=groups[i], lm=lm)
+            return self.fill_host([waveforms[k] for k in groups[i]], buf, hotwords=plan, members=groups[i], lm=lm, nbest=n_best)
 
         # `on_batch` runs on its own thread, in batch order: a decode lane that ran the caller's post-processing itself
         # would start its next batch that much later (ids -> text is ~25 ms of Python per 256 utterances)
@@ -968,11 +1085,14 @@ class AsrModel:
                 scores[i] = res.scores[k] if res.scores is not None else None
                 if logprobs is not None:
                     logprobs[i] = res.token_logprobs[k]
+                if lists is not None:
+                    lists[i] = res.nbest[k]
             if post_q is not None:
                 m = len(group)
                 post_q.put((group, DecodedBatch(res.ids[:m], res.frames[:m], res.enc_lens[:m],
                                                 res.scores[:m] if res.scores is not None else None,
-                                                token_logprobs=res.token_logprobs[:m] if logprobs is not None else None)))
+                                                token_logprobs=res.token_logprobs[:m] if logprobs is not None else None,
+                                                nbest=res.nbest[:m] if lists is not None else None)))
 
         post = None
         if post_q is not None:
@@ -996,4 +1116,4 @@ class AsrModel:
                 gc.enable()
         if post_err:
             raise post_err[0]
-        return DecodedBatch(ids, frames, enc_lens, scores if self.cfg.has_scores else None, token_logprobs=logprobs)
+        return DecodedBatch(ids, frames, enc_lens, scores if self.cfg.has_scores else None, token_logprobs=logprobs, nbest=lists)
