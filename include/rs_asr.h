@@ -873,6 +873,41 @@ int rs_rnnt_token_scores(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
                          const int32_t* frames, const int32_t* n_ids, int u_cap, int flags, float* logp, int32_t* top1,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- forced alignment and transcript likelihood on the transducer lattice — added within ABI 7 ----
+ * answers what the reference's corpus tools ask of a model (pkg/_v1/src/align.py, pkg/espnet-oneseg: align a known text to the
+ * audio, keep or drop the utterance by its score) for the families without a CTC head: here is a text, how well does it fit this
+ * audio, and when was each token spoken?  The transducer lattice of Graves 2012.  For utterance b, T = min(enc_lens[b], tp_max),
+ * labels y_1..y_U (U = n_ids[b]), g(u) the prediction network's output after the start context and the first u labels (u = 0..U),
+ *     z(t,u) = W_out . act(f[b][t] + g(u)) + b_out,   lb(t,u) = z[blank] - lse(z),   ly(t,u) = z[y_(u+1)] - lse(z)   (u < U)
+ * in the float32 order of rs_rnnt_token_scores: ly(t,u) is, bit for bit, what that entry returns for token u placed at frame t.
+ *   no flag (NeMo, ESPnet)    a(0,0) = 0;  a(t,u) = lae(a(t-1,u) + lb(t-1,u), a(t,u-1) + ly(t,u-1));  loglik = a(T-1,U) + lb(T-1,U)
+ *   RS_ALIGN_ONE_PER_FRAME    a(t,u) = lae(a(t-1,u) + lb(t-1,u), a(t-1,u-1) + ly(t-1,u-1)) over t = 0..T;  loglik = a(T,U): a label
+ *                             also advances the frame, as every Zipformer search of this header moves; feasible only for U <= T
+ *   lae(a, b)                 m = max(a, b); -inf when m is -inf, else m + log(exp(a - m) + exp(b - m)) (the searches' exp and
+ *                             log); a is the blank term; a predecessor outside the lattice contributes -inf
+ *   loglik f32[B]             log P(text | audio), the sum over all alignments
+ *   best f32[B]               the same recursion with max in place of lae: the Viterbi score; ties go to the blank predecessor
+ *   frames i32[B][u_cap]      frame at which label u + 1 is emitted on that path: non-decreasing, strictly increasing with the flag
+ *   logp f32[B][u_cap]        ly(frames[b][u], u)
+ * Rows that are no error: T = 0 and U = 0 give loglik = best = 0; an infeasible row (T = 0 with U > 0, or U > T with the flag)
+ * gives loglik = best = -inf, frames -1 and logp NaN.  Slots at u >= n_ids[b] are left untouched.
+ * u_cap (the row pitch of ids, frames and logp) is at most RS_ALIGN_U_CAP_MAX.
+ * Workspace: rs_rnnt_align_workspace_bytes(ctx, B, tp_max, u_cap) is the MINIMUM (0 for invalid arguments); it holds the whole
+ * lattice (two floats and a back-pointer bit per cell of B x tp_max x (u_cap + 1)) and 32 lattice rows of joint logits per
+ * chunk; every further 32 rows per chunk cost what they cost rs_rnnt_token_scores.  Same bits whatever the chunk and whatever
+ * else is in the batch; stated in csrc/k_rnnt_align.hip and restated serially by tests/rnnt_align_checker.c.
+ * Synchronises the stream internally (twice).  RS_EINVAL — before anything is enqueued — for an AV-HuBERT or unfinalised context,
+ * a null pointer, a negative size, an unknown flag, u_cap above the bound or a workspace below the minimum.  The kernels check
+ * every count against u_cap and every id against the vocabulary before they index anything, and the blank id is no label: a bad
+ * entry makes its row's loglik / best / logp NaN and its frames -1, the call returns RS_EINVAL after the sync and the other rows
+ * keep their bits; nothing is read or written out of range. */
+enum { RS_ALIGN_ONE_PER_FRAME = 1 };
+#define RS_ALIGN_U_CAP_MAX 2047
+size_t rs_rnnt_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int u_cap);
+int rs_rnnt_align(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                  const int32_t* n_ids, int u_cap, int flags, float* loglik, float* best, int32_t* frames, float* logp,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC segmentation of a batch (ESPnet family: time stamps of a recognised text) ------------------
  * Replaces: ctc_segmentation.ctc_segmentation(config, lpz, ground_truth_mat) of the third-party aligner the reference calls
  * once per window (pkg/espnet-asr/src/ctc.py:60-75), for the default CtcSegmentationParameters — the only ones the reference

@@ -19,13 +19,14 @@ LIB = os.path.join(LIBDIR, "librs_asr.so")
 ARCH = "gfx950"
 
 SOURCES = ["rs_api.hip", "k_conformer.hip", "k_gemm_bf16.hip", "k_layernorm.hip", "k_attention.hip", "k_frontend.hip",
-           "k_subsample.hip", "k_rnnt.hip", "k_rnnt_alsd.hip", "k_rnnt_beam.hip", "k_rnnt_mbs.hip", "k_rnnt_scores.hip", "k_f32.hip", "k_espnet.hip", "k_zipformer.hip", "k_avsr.hip",
+           "k_subsample.hip", "k_rnnt.hip", "k_rnnt_alsd.hip", "k_rnnt_beam.hip", "k_rnnt_mbs.hip", "k_rnnt_scores.hip", "k_rnnt_align.hip", "k_f32.hip", "k_espnet.hip", "k_zipformer.hip", "k_avsr.hip",
            "k_int8.hip", "k_avsr_search.hip", "k_ctc_align.hip", "k_ctc_blank.hip", "k_resample.hip", "k_avsr_features.hip"]
 EXTRA = {"k_rnnt.hip": ["-ffp-contract=off"],
          "k_rnnt_alsd.hip": ["-ffp-contract=off"],
          "k_rnnt_beam.hip": ["-ffp-contract=off"],
          "k_rnnt_mbs.hip": ["-ffp-contract=off"],
          "k_rnnt_scores.hip": ["-ffp-contract=off"],
+         "k_rnnt_align.hip": ["-ffp-contract=off"],
          "k_int8.hip": ["-ffp-contract=off"],
          "k_avsr_search.hip": ["-ffp-contract=off"],
          "k_ctc_align.hip": ["-ffp-contract=off"],

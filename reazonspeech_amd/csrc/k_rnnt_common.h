@@ -1,5 +1,5 @@
 // k_rnnt_common.h — pieces shared by the decode translation units (k_rnnt.hip: greedy, k_rnnt_alsd.hip / k_rnnt_beam.hip /
-// k_rnnt_mbs.hip: the beam searches, k_rnnt_scores.hip: token log-probabilities).
+// k_rnnt_mbs.hip: the beam searches, k_rnnt_scores.hip: token log-probabilities, k_rnnt_align.hip: forced alignment).
 // All are compiled with -ffp-contract=off.
 #pragma once
 #include "rs_common.h"

@@ -29,6 +29,10 @@ int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
                       float* scores, int nbest, float* norm_scores, int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
                       void* workspace, size_t workspace_bytes, hipStream_t s);
 size_t rs_rnnt_token_scores_workspace_bytes_impl(const rs_ctx* ctx, int B, int u_cap);
+size_t rs_rnnt_align_workspace_bytes_impl(const rs_ctx* ctx, int B, int tp_max, int u_cap);
+int rs_rnnt_align_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                       const int32_t* n_ids, int u_cap, int one_per_frame, float* loglik, float* best, int32_t* frames, float* logp,
+                       void* workspace, size_t workspace_bytes, hipStream_t s);
 int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
                               const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
                               void* workspace, size_t workspace_bytes, hipStream_t s);
@@ -705,6 +709,31 @@ int rs_rnnt_token_scores(rs_ctx* ctx, const float* joint_enc, const int32_t* enc
     if (tp_max == 0) return RS_OK;                         // no frames: no utterance has a token
     return rs_rnnt_token_scores_impl(ctx, joint_enc, enc_lens, B, tp_max, ids, frames, n_ids, u_cap, (flags & RS_SCORES_FRAMES_ARE_STEPS) != 0,
                                      logp, top1, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- forced alignment and transcript likelihood on the transducer lattice (k_rnnt_align.hip) ----
+size_t rs_rnnt_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int u_cap) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_align_workspace_bytes, 0);
+    if (!token_scores_ctx_ok(ctx) || B <= 0 || tp_max < 0 || u_cap < 0 || u_cap > RS_ALIGN_U_CAP_MAX) return 0;
+    return rs_rnnt_align_workspace_bytes_impl(ctx, B, tp_max, u_cap);
+}
+
+int rs_rnnt_align(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                  const int32_t* n_ids, int u_cap, int flags, float* loglik, float* best, int32_t* frames, float* logp, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_align);
+    if (!token_scores_ctx_ok(ctx)) return rs_fail(ctx, RS_EINVAL, "align: the context is not finalized");
+    if (B < 0 || tp_max < 0 || u_cap < 0) return rs_fail(ctx, RS_EINVAL, "align: negative size");
+    if (flags & ~RS_ALIGN_ONE_PER_FRAME) return rs_fail(ctx, RS_EINVAL, "align: unknown flag %d", flags);
+    if (u_cap > RS_ALIGN_U_CAP_MAX) return rs_fail(ctx, RS_EINVAL, "align: u_cap %d is above %d", u_cap, RS_ALIGN_U_CAP_MAX);
+    if (B == 0) return RS_OK;
+    if (!joint_enc || !enc_lens || !ids || !n_ids || !loglik || !best || !frames || !logp || !workspace)
+        return rs_fail(ctx, RS_EINVAL, "align: null pointer");
+    const size_t least = rs_rnnt_align_workspace_bytes_impl(ctx, B, tp_max, u_cap);
+    if (least == 0) return rs_fail(ctx, RS_EINVAL, "align: B x tp_max x (u_cap + 1) is too large");
+    if (workspace_bytes < least) return rs_fail(ctx, RS_EINVAL, "align: workspace %zu < %zu", workspace_bytes, least);
+    return rs_rnnt_align_impl(ctx, joint_enc, enc_lens, B, tp_max, ids, n_ids, u_cap, (flags & RS_ALIGN_ONE_PER_FRAME) != 0, loglik, best,
+                              frames, logp, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t rs_ctc_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int c_max, int S) {

@@ -44,6 +44,21 @@ class ScoredTranscribeResult(TranscribeResult):
     confidence: Optional[float] = None
 
 
+@dataclass
+class AlignedTranscribeResult(ScoredTranscribeResult):
+    """What `align_text()` returns (additive): the given text placed on the audio by the transducer lattice (include/rs_asr.h
+    rs_rnnt_align).  The result fields are built from (token ids, Viterbi frames) the way `transcribe` builds them from a search;
+    `token_logprobs[i]` = log-probability of `token_ids[i]` at its frame; `log_likelihood` = log P(text | audio) summed over ALL
+    alignments; `alignment_log_prob` = the best alignment's own score (<= log_likelihood); `norm_log_likelihood` =
+    log_likelihood / max(len(token_ids), 1); `feasible` False (scores -inf, no times) when the text has no alignment on this
+    audio: no frames, or more tokens than frames for a model that emits one token per frame."""
+    token_seconds: List[float] = field(default_factory=list)     # frame x the encoder's stride, minus the padding `transcribe` adds
+    log_likelihood: float = float("-inf")
+    alignment_log_prob: float = float("-inf")
+    norm_log_likelihood: float = float("-inf")
+    feasible: bool = False
+
+
 def mean_confidence(logprobs):
     """exp(mean(logprobs)), None for an empty list"""
     return float(np.exp(np.mean(np.asarray(logprobs, np.float64)))) if len(logprobs) else None

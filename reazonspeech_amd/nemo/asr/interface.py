@@ -61,6 +61,20 @@ class ScoredTranscribeResult(TranscribeResult):
 
 
 @dataclass
+class AlignedTranscribeResult(ScoredTranscribeResult):
+    """What `align_text()` returns (additive): the given text placed on the audio by the transducer lattice (include/rs_asr.h
+    rs_rnnt_align).  The result fields are built from (token ids, Viterbi frames) the way `transcribe` builds them from a search;
+    `token_logprobs[i]` = log-probability of `token_ids[i]` at its frame; `log_likelihood` = log P(text | audio) summed over ALL
+    alignments; `alignment_log_prob` = the best alignment's own score (<= log_likelihood); `norm_log_likelihood` =
+    log_likelihood / max(len(token_ids), 1); `feasible` False (scores -inf, no times) when the text has no alignment on this
+    audio: no frames, or more tokens than frames for a model that emits one token per frame."""
+    log_likelihood: float = float("-inf")
+    alignment_log_prob: float = float("-inf")
+    norm_log_likelihood: float = float("-inf")
+    feasible: bool = False
+
+
+@dataclass
 class NBestTranscribeResult(TranscribeResult):
     """What `transcribe()` returns from a model loaded with `nbest=N` and the ALSD search (additive; NeMo's beam decoding with
     `return_best_hypothesis=False`): the result as ever, plus `nbest` — the N best finished hypotheses as results of this same type,

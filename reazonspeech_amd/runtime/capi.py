@@ -23,6 +23,8 @@ GLU_HALVES, GLU_BLOCK32, GLU_APPLIED = 0, 1, 2
 ALSD_SCORE_NORM, ALSD_MERGE = 1, 2
 MBS_LENGTH_NORM = 1
 SCORES_FRAMES_ARE_STEPS = 1
+ALIGN_ONE_PER_FRAME = 1
+ALIGN_U_CAP_MAX = 2047
 PROF_GEMM, PROF_ATTN, PROF_FRONTEND, PROF_DECODE, PROF_ELEMENTWISE, PROF_SUBSAMPLE = 1, 2, 4, 8, 16, 32
 
 # every symbol include/rs_asr.h declares (tests/test_capi_exports.py checks the .so exports them)
@@ -40,7 +42,7 @@ EXPORTS = [
     "rs_rnnt_mbs_nbest", "rs_rnnt_mbs_nbest_workspace_bytes",
     "rs_rnnt_beam_nbest", "rs_rnnt_beam_nbest_workspace_bytes",
     "rs_rnnt_alsd_nbest", "rs_rnnt_alsd_nbest_workspace_bytes",
-    "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes",
+    "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes", "rs_rnnt_align", "rs_rnnt_align_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
     "rs_k2_create", "rs_k2_encoder_set_taps",
@@ -266,6 +268,10 @@ def load():
     lib.rs_rnnt_token_scores_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_token_scores.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, vp, c_int, c_int, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_token_scores.restype = c_int
+    lib.rs_rnnt_align_workspace_bytes.argtypes = [vp, c_int, c_int, c_int]
+    lib.rs_rnnt_align_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_align.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, vp, c_size_t, vp]
+    lib.rs_rnnt_align.restype = c_int
     alsd = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp]
     lib.rs_rnnt_alsd.argtypes = alsd + tail
     lib.rs_rnnt_alsd_hotwords.argtypes = alsd + hw_args + tail
@@ -657,6 +663,24 @@ class Context:
                                                  ids.shape[1], SCORES_FRAMES_ARE_STEPS if frames_are_steps else 0, _ptr(logp), _ptr(top1),
                                                  _ptr(ws), ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes),
                                                  c_void_p(stream)))
+
+    def align_workspace_bytes(self, B, tp_max, u_cap):
+        """the MINIMUM workspace of `rnnt_align` (the whole lattice, 32 rows per chunk); a larger one makes fewer chunks, same bits"""
+        n = self.lib.rs_rnnt_align_workspace_bytes(self._h, int(B), int(tp_max), int(u_cap))
+        if n == 0:
+            raise RuntimeError(f"rs_rnnt_align_workspace_bytes: invalid arguments (a finalized transducer context, B > 0, tp_max >= 0, "
+                               f"0 <= u_cap <= {ALIGN_U_CAP_MAX}, B x tp_max x (u_cap + 1) < 2^30)")
+        return n
+
+    def rnnt_align(self, joint_enc, enc_lens, B, tp_max, ids, n_ids, loglik, best, frames, logp, ws, stream, one_per_frame=False,
+                   ws_bytes=None):
+        """forced alignment and likelihood of given transcripts on the transducer lattice (include/rs_asr.h rs_rnnt_align): ids int32
+        [B][u_cap], n_ids int32 [B]; loglik / best float32 [B], frames int32 / logp float32 [B][u_cap]; one_per_frame: a label also
+        advances the frame (the Zipformer searches)"""
+        assert frames.shape == ids.shape and logp.shape == ids.shape and loglik.numel() >= B and best.numel() >= B
+        self.check(self.lib.rs_rnnt_align(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, _ptr(ids), _ptr(n_ids), ids.shape[1],
+                                          ALIGN_ONE_PER_FRAME if one_per_frame else 0, _ptr(loglik), _ptr(best), _ptr(frames), _ptr(logp),
+                                          _ptr(ws), ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes), c_void_p(stream)))
 
     def ctc_align_workspace_bytes(self, B, tp_max, c_max, S):
         n = self.lib.rs_ctc_align_workspace_bytes(self._h, int(B), int(tp_max), int(c_max), int(S))

@@ -36,6 +36,19 @@ class DecodedBatch:
     token_logprobs: Optional[List[List[float]]] = None   # `AsrModel.token_scores`: log-probability of every id under the model's own distribution
 
 
+@dataclass
+class AlignedBatch:
+    """host-side result of `AsrModel.align_waveforms`: per utterance the frame and the log-probability of every given label on the
+    best alignment, log P(text | audio) summed over all alignments, the best alignment's own score, and whether the text has an
+    alignment at all (an infeasible one: -inf scores, frames -1, NaN log-probabilities)"""
+    frames: List[List[int]]
+    token_logprobs: List[List[float]]
+    log_likelihood: List[float]
+    alignment_log_prob: List[float]
+    enc_lens: List[int]
+    feasible: List[bool]
+
+
 def alsd_label_budget(t_frames: int, max_target_len) -> int:
     """labels a hypothesis may emit beyond the frames (oracle/alsd.py: float = multiple of T', int = absolute)"""
     return int(max_target_len * t_frames) if isinstance(max_target_len, float) else int(max_target_len)
@@ -967,6 +980,67 @@ class AsrModel:
                     fr = fr - np.arange(m, dtype=fr.dtype)
                 rows.append((nb["ids"][b, r, :m].tolist(), fr.tolist(), float(nb["scores"][b, r]), float(nb["norm_scores"][b, r])))
             out.append(rows)
+        return out
+
+    ALIGN_MAX_CELLS = 0x3fffffff      # B x tp_max x (u_cap + 1) one rs_rnnt_align call takes (include/rs_asr.h); a larger batch is halved
+    ALIGN_CHUNK_ROWS = 16384    # lattice rows whose logits `align_waveforms` asks room for at once; fewer rows, more chunks, same bits
+
+    def align_waveforms(self, waveforms: Sequence[np.ndarray], label_rows: Sequence[Sequence[int]], max_batch: int = 256,
+                        one_per_frame: Optional[bool] = None) -> AlignedBatch:
+        """host float32 waveforms and the token ids of their known texts -> the forced alignment and the likelihood of every text
+        (rs_rnnt_align, csrc/k_rnnt_align.hip): front-end and encoder as `transcribe_waveforms` runs them, then the transducer
+        lattice of (audio, text) instead of a search.  `one_per_frame`: a label also advances the frame; None = the topology the
+        model's own searches move in (`cfg.max_symbols == 1`: the Zipformer family).  Up to `max_batch` utterances run as one
+        batch, sorted by length (a batch whose lattice is beyond one call's bound is halved); a row's bits do not depend on its
+        batch.  Results come back in the caller's order."""
+        n = len(waveforms)
+        if len(label_rows) != n:
+            raise ValueError(f"align_waveforms: {n} waveforms but {len(label_rows)} texts")
+        one = bool(self.cfg.max_symbols == 1 if one_per_frame is None else one_per_frame)
+        labels = [[int(i) for i in row] for row in label_rows]
+        longest = max((len(r) for r in labels), default=0)
+        if longest > capi.ALIGN_U_CAP_MAX:
+            raise ValueError(f"align_waveforms: a text of {longest} tokens; at most {capi.ALIGN_U_CAP_MAX} are supported (window the audio)")
+        out = AlignedBatch([None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n)
+        waveforms = [np.asarray(w, dtype=np.float32) for w in waveforms]
+        order = sorted(range(n), key=lambda i: (len(waveforms[i]), i))
+        cfg = self.cfg
+        hidden = getattr(cfg, "decoder_dim", None) or cfg.pred_hidden
+        per_row = 4 * (2 * cfg.joint_hidden + (cfg.n_logits + 63) // 64 * 64 + 2 * hidden + 16)
+        groups = [order[g0:g0 + max_batch] for g0 in range(0, n, max_batch)]
+        while groups:
+            group = groups.pop(0)
+            B = len(group)
+            buf = self.stage([waveforms[i] for i in group])
+            u_cap = max(max(len(labels[i]) for i in group), 1)
+            if B * buf.tp_max * (u_cap + 1) > self.ALIGN_MAX_CELLS:          # the lattice of the batch is beyond the entry's bound
+                if B == 1:
+                    raise ValueError(f"align_waveforms: {buf.tp_max} frames x {u_cap} tokens is more than one call aligns (window the audio)")
+                groups[:0] = [group[:B // 2], group[B // 2:]]
+                continue
+            ids = np.zeros((B, u_cap), np.int32)
+            for k, i in enumerate(group):
+                ids[k, :len(labels[i])] = labels[i]
+            n_ids = np.asarray([len(labels[i]) for i in group], np.int32)
+            with torch.cuda.device(self.device):
+                dev = self.device
+                stream = torch.cuda.current_stream().cuda_stream
+                self.run_encoder(buf, stream)
+                ids_d, n_d = torch.from_numpy(ids).to(dev), torch.from_numpy(n_ids).to(dev)
+                loglik, best = torch.empty((B,), device=dev), torch.empty((B,), device=dev)
+                frames = torch.full((B, u_cap), -1, dtype=torch.int32, device=dev)
+                logp = torch.full((B, u_cap), float("nan"), device=dev)
+                rows = min(self.ALIGN_CHUNK_ROWS, B * buf.tp_max * (u_cap + 1))
+                ws = torch.empty((self.ctx.align_workspace_bytes(B, buf.tp_max, u_cap) + (rows + 31) // 32 * 32 * per_row,),
+                                 dtype=torch.uint8, device=dev)
+                self.ctx.rnnt_align(buf.joint_enc, buf.enc_lens, B, buf.tp_max, ids_d, n_d, loglik, best, frames, logp, ws, stream,
+                                    one_per_frame=one)
+                loglik, best, frames, logp, el = (t.cpu().numpy() for t in (loglik, best, frames, logp, buf.enc_lens))
+            for k, i in enumerate(group):
+                m = int(n_ids[k])
+                out.frames[i], out.token_logprobs[i] = frames[k, :m].tolist(), logp[k, :m].tolist()
+                out.log_likelihood[i], out.alignment_log_prob[i] = float(loglik[k]), float(best[k])
+                out.enc_lens[i], out.feasible[i] = int(el[k]), bool(np.isfinite(loglik[k]))
         return out
 
     def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None, ngram_lm=None) -> DecodedBatch:
