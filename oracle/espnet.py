@@ -16,22 +16,23 @@ import torch.nn.functional as F
 from . import model as om
 
 
-def frontend(cfg, sd, audio: torch.Tensor, lengths: torch.Tensor):
+def frontend(cfg, sd, audio: torch.Tensor, lengths: torch.Tensor, dtype=torch.float32):
     """audio f32[B, Lmax], lengths i64[B] -> (features f32[B, Tmax, n_mels], n_frames i64[B]).
 
     [UPSTREAM] espnet2 DefaultFrontend: Stft (torch.stft, n_fft, hop, win_length, periodic Hann, center=True, reflect
     padding, onesided) -> power -> LogMel (librosa Slaney filters `melmat` [n_freq, n_mels], log(clamp(x, 1e-10))) with frames
     past 1 + L // hop zeroed, then GlobalMVN ((x - mean) / std) with the padding zeroed again.  Each utterance is transformed
-    on its own samples (reflect padding looks at the utterance's last samples, not at the batch padding)."""
+    on its own samples (reflect padding looks at the utterance's last samples, not at the batch padding).  `dtype`: the type of all
+    arithmetic (torch.float64: the same float32 parameters, window and audio in double precision)."""
     B = audio.shape[0]
-    window = torch.hann_window(cfg.win_length, periodic=True, dtype=torch.float32)
-    melmat = sd["frontend.logmel.melmat"].to(torch.float32)
-    mean, std = sd["normalize.mean"].to(torch.float32), sd["normalize.std"].to(torch.float32).clamp_min(cfg.norm_eps)
+    window = torch.hann_window(cfg.win_length, periodic=True, dtype=torch.float32).to(dtype)
+    melmat = sd["frontend.logmel.melmat"].to(dtype)
+    mean, std = sd["normalize.mean"].to(dtype), sd["normalize.std"].to(dtype).clamp_min(cfg.norm_eps)
     n = 1 + lengths // cfg.hop_length
     Tmax = int(n.max())
-    out = torch.zeros((B, Tmax, cfg.n_mels), dtype=torch.float32)
+    out = torch.zeros((B, Tmax, cfg.n_mels), dtype=dtype)
     for b in range(B):
-        x = audio[b, :int(lengths[b])].to(torch.float32)
+        x = audio[b, :int(lengths[b])].to(dtype)
         st = torch.stft(x, cfg.n_fft, hop_length=cfg.hop_length, win_length=cfg.win_length, window=window, center=True,
                         pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
         power = st.real ** 2 + st.imag ** 2                          # [n_freq, frames]

@@ -33,9 +33,10 @@ def _rb(x: torch.Tensor, recipe: str) -> torch.Tensor:
 # F1-F4: log-mel front-end
 # --------------------------------------------------------------------------------------
 
-def frontend(cfg, sd, audio: torch.Tensor, lengths: torch.Tensor):
+def frontend(cfg, sd, audio: torch.Tensor, lengths: torch.Tensor, dtype=torch.float32):
     """audio f32[B, Lmax] (already zero padded like pad_audio), lengths i64[B]
-    -> (features f32[B, Tmax, n_mels], n_frames i64[B]).
+    -> (features f32[B, Tmax, n_mels], n_frames i64[B]).  `dtype`: the type of all arithmetic (torch.float64: the same float32
+    parameters and audio in double precision, the yardstick of what float32 costs here).
 
     [UPSTREAM] AudioToMelSpectrogramPreprocessor / FilterbankFeatures.forward:
     pre-emphasis (HF feature_extraction_parakeet.py:252-260), torch.stft(n_fft, hop,
@@ -47,15 +48,15 @@ def frontend(cfg, sd, audio: torch.Tensor, lengths: torch.Tensor):
     B, Lmax = audio.shape
     t = torch.arange(Lmax)[None, :]
     valid = t < lengths[:, None]
-    x = audio.to(torch.float32)
+    x = audio.to(dtype)
     if cfg.preemph:
         x = torch.cat([x[:, :1], x[:, 1:] - cfg.preemph * x[:, :-1]], dim=1)
     x = x.masked_fill(~valid, 0.0)
-    window = sd["preprocessor.featurizer.window"].to(torch.float32)
+    window = sd["preprocessor.featurizer.window"].to(dtype)
     stft = torch.stft(x, cfg.n_fft, hop_length=cfg.hop_length, win_length=cfg.win_length,
                       window=window, center=True, pad_mode="constant", return_complex=True)
     power = stft.real ** 2 + stft.imag ** 2                      # [B, 257, frames]
-    fb = sd["preprocessor.featurizer.fb"].to(torch.float32).reshape(cfg.n_mels, -1)
+    fb = sd["preprocessor.featurizer.fb"].to(dtype).reshape(cfg.n_mels, -1)
     mel = torch.log(fb @ power + cfg.log_guard).permute(0, 2, 1)  # [B, frames, n_mels]
     n = (lengths + (cfg.n_fft // 2) * 2 - cfg.n_fft) // cfg.hop_length
     Tmax = int(n.max())

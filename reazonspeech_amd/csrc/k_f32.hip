@@ -10,6 +10,9 @@
 //                          fixed summation order per output element (ascending 16-blocks, inside a block k = e + 4 kk),
 //                          independent of M and of the tile position: batch-invariant like the bf16 family
 //   attention_f32_kernel   rel-pos attention, one wave per query row, float32 scores / softmax / PV
+//                          (the forms that run: attention_f32_mfma_kernel for full attention, attention_f32_keys_kernel<4 / 8 / 0>
+//                          for limited context; this first form stays behind RS_ATTN_F32_OLD and for a head_dim that is no
+//                          multiple of 4)
 //   glu_dwconv_silu_f32    conv-module middle with IEEE exp / divide
 //   (LayerNorm: k_layernorm.hip's kernels already compute and can store float32; subsampling: the float32 instantiations
 //    of k_subsample.hip)
@@ -427,8 +430,16 @@ __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restr
 // it makes per key (profiles/r06_05_f32_*_before.txt: 34 % of the NeMo float32 mode, 70 % of the ESPnet one).  Here a lane owns keys
 // lane, lane + 64, .. and computes the whole head_dim dot products of ITS keys (ascending e, one fma chain per term; the wave's query
 // vectors q + u, q + v sit in LDS and are read as broadcasts), so a query costs two wave reductions in total (maximum, denominator);
-// the P.V sum then walks the keys with the probability read from its lane (v_readlane) and the value row read coalesced.  Scores live
-// in registers: T <= 64 NCH (NCH = 4 / 8); longer inputs (long-form windows) take the kernel above.  Same mask semantics.
+// the P.V sum then walks the keys with the probability read from its lane (v_readlane) and the value row read coalesced.  Same mask
+// semantics.
+//   NCH = 4 / 8   the scores live in registers: T <= 64 NCH
+//   NCH = 0       any T (limited-context attention in a buffer of more than 512 frames): the keys are walked 64 at a time twice
+//                 (maximum; then exp / denominator / P.V with the scores computed again by the same code)
+// ONE body serves all three, so every number is formed the same way whatever the buffer's length: a lane's score by the same two fma
+// chains, its share of the denominator by adding its keys' terms in ascending chunks (the chunks past the length that NCH = 4 / 8 also
+// add are exact zeros) before the one wave_sum, the P.V sum over ascending keys with masked keys skipped.  An utterance therefore has
+// the same bits alone in a short buffer and inside a long one (tests/test_gpu_attention_edges.py
+// test_f32_limited_context_across_the_512_seam, tests/test_gpu_conformer_lengths.py section 4).
 template <int NCH>
 __global__ __launch_bounds__(256) void attention_f32_keys_kernel(const float* __restrict__ qkv, const float* __restrict__ pos,
                                                                  const float* __restrict__ bias_u, const float* __restrict__ bias_v,
@@ -457,43 +468,28 @@ __global__ __launch_bounds__(256) void attention_f32_keys_kernel(const float* __
     const float4* qv4 = reinterpret_cast<const float4*>(qs[wave][1]);
     const bool window = att_left >= 0 || att_right >= 0;
     const int left = att_left >= 0 ? att_left : T, right = att_right >= 0 ? att_right : T;
-    float sc[NCH];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int j = lane + 64 * c;
+    auto score = [&](int j) -> float {                     // -inf for a key this query does not see
         bool vis = j < len;
         if (vis && window) vis = ((i - j) <= left && (j - i) <= right) || i < n_global || j < n_global;
-        sc[c] = -INFINITY;
-        if (vis) {
-            const float4* kr = reinterpret_cast<const float4*>(base + (size_t)j * ld + d);
-            const float4* pr = reinterpret_cast<const float4*>(pos + (size_t)(j - i + T - 1) * d + h * hd);
-            float ac = 0.0f, bd = 0.0f;
-            for (int e4 = 0; e4 < hd / 4; ++e4) {
-                const float4 kv = kr[e4], pv = pr[e4], a = qu4[e4], g = qv4[e4];
-                ac = fmaf(a.x, kv.x, ac); ac = fmaf(a.y, kv.y, ac); ac = fmaf(a.z, kv.z, ac); ac = fmaf(a.w, kv.w, ac);
-                bd = fmaf(g.x, pv.x, bd); bd = fmaf(g.y, pv.y, bd); bd = fmaf(g.z, pv.z, bd); bd = fmaf(g.w, pv.w, bd);
-            }
-            sc[c] = (ac + bd) * scale;
-            mx = fmaxf(mx, sc[c]);
+        if (!vis) return -INFINITY;
+        const float4* kr = reinterpret_cast<const float4*>(base + (size_t)j * ld + d);
+        const float4* pr = reinterpret_cast<const float4*>(pos + (size_t)(j - i + T - 1) * d + h * hd);
+        float ac = 0.0f, bd = 0.0f;
+        for (int e4 = 0; e4 < hd / 4; ++e4) {
+            const float4 kv = kr[e4], pv = pr[e4], a = qu4[e4], g = qv4[e4];
+            ac = fmaf(a.x, kv.x, ac); ac = fmaf(a.y, kv.y, ac); ac = fmaf(a.z, kv.z, ac); ac = fmaf(a.w, kv.w, ac);
+            bd = fmaf(g.x, pv.x, bd); bd = fmaf(g.y, pv.y, bd); bd = fmaf(g.z, pv.z, bd); bd = fmaf(g.w, pv.w, bd);
         }
-    }
-    mx = wave_max(mx);
-    float den = 0.0f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        sc[c] = sc[c] > -INFINITY ? expf(sc[c] - mx) : 0.0f;
-        den += sc[c];
-    }
-    den = wave_sum(den);
-    // P.V: this lane's output elements e = lane, lane + 64, ..; keys in ascending order
+        return (ac + bd) * scale;
+    };
+    // P.V of one chunk of 64 keys: this lane's output elements e = lane, lane + 64, ..; keys in ascending order
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     const float* vbase = base + 2 * d;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
+    auto pv_chunk = [&](int c, float pj) {
+        if (!__any(pj != 0.0f)) return;                    // a chunk wholly outside the window (or past the length): nothing to add
         const int jn = len - 64 * c < 64 ? len - 64 * c : 64;
         for (int jj = 0; jj < jn; ++jj) {
-            const float p = __shfl(sc[c], jj, 64);
+            const float p = __shfl(pj, jj, 64);
             if (p != 0.0f) {                               // (wave-uniform: masked keys contribute nothing)
                 const float* vr = vbase + (size_t)(64 * c + jj) * ld;
 #pragma unroll
@@ -501,7 +497,35 @@ __global__ __launch_bounds__(256) void attention_f32_keys_kernel(const float* __
                     if (lane + 64 * v < hd) acc[v] = fmaf(p, vr[lane + 64 * v], acc[v]);
             }
         }
+    };
+    float mx = -INFINITY, den = 0.0f;
+    if constexpr (NCH > 0) {
+        float sc[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            sc[c] = score(lane + 64 * c);
+            mx = fmaxf(mx, sc[c]);
+        }
+        mx = wave_max(mx);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            sc[c] = sc[c] > -INFINITY ? expf(sc[c] - mx) : 0.0f;
+            den += sc[c];
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) pv_chunk(c, sc[c]);
+    } else {
+        const int nch = (len + 63) / 64;
+        for (int c = 0; c < nch; ++c) mx = fmaxf(mx, score(lane + 64 * c));
+        mx = wave_max(mx);
+        for (int c = 0; c < nch; ++c) {
+            const float sj = score(lane + 64 * c);
+            const float pj = sj > -INFINITY ? expf(sj - mx) : 0.0f;
+            den += pj;
+            pv_chunk(c, pj);
+        }
     }
+    den = wave_sum(den);
 #pragma unroll
     for (int v = 0; v < 4; ++v)
         if (lane + 64 * v < hd) orow[lane + 64 * v] = den > 0.0f ? acc[v] / den : 0.0f;
@@ -746,9 +770,11 @@ int rs_launch_attention_f32(rs_ctx* ctx, const float* qkv, const float* pos, con
         if (hd == 128) hipLaunchKernelGGL((attention_f32_mfma_kernel<128>), grid16, block, 0, s, qkv, pos, bias_u, bias_v, lens, out, T, dm.d_model, scale);
         else hipLaunchKernelGGL((attention_f32_mfma_kernel<64>), grid16, block, 0, s, qkv, pos, bias_u, bias_v, lens, out, T, dm.d_model, scale);
     } else
-    if (!one_wave_per_key_sum && T <= 512 && hd % 4 == 0) {
+    if (!one_wave_per_key_sum && hd % 4 == 0) {
+        // scores in registers up to 512 keys, computed twice above (NCH = 0): one body, the same bits whatever the buffer's length
         if (T <= 256) RS_ATT_KEYS(4);
-        else RS_ATT_KEYS(8);
+        else if (T <= 512) RS_ATT_KEYS(8);
+        else RS_ATT_KEYS(0);
     } else
     if (hd <= 64) RS_ATT_CASE(1);
     else if (hd <= 128) RS_ATT_CASE(2);

@@ -16,7 +16,9 @@ mask, a window edge, a global-token count or a position index off by one, u and 
   attention_f32_mfma_kernel<128 / 64>                 float32, full attention                                     test_f32_mfma
   attention_f32_keys_kernel<4>                        float32, T <= 256: windowed, or full + RS_ATTN_F32_KEYS     test_f32_keys
   attention_f32_keys_kernel<8>                        the same at 256 < T <= 512                                  test_f32_keys
-  attention_f32_kernel<1 / 2>                         RS_ATTN_F32_OLD at T = 65; windowed at T = 513 (head_dim 64 / 128)   test_f32_first_form
+  attention_f32_keys_kernel<0>                        float32, windowed at T > 512 (scores computed twice; the bits of <4 / 8>)   test_f32_keys_long,
+                                                                                                                  test_f32_limited_context_across_the_512_seam
+  attention_f32_kernel<1 / 2>                         RS_ATTN_F32_OLD at T = 65 (head_dim 64 / 128)               test_f32_first_form
   attention_f32_kernel<4>                             head_dim 256: no Context has it (TINY's d_model 256 would need one head, and the
                                                       bf16 attention the Context also sets up builds 128 and 64 only); not reached
   relpos_attention_kernel<128,1,0>  (TRACE)           the phase-timestamp debug hook of scripts/attn_trace.py; not a production form, not run here
@@ -234,16 +236,21 @@ def test_f32_keys(contexts, gpu_device, dh, T):
 
 @pytest.mark.parametrize("dh", [128, 64])
 def test_f32_first_form(contexts, gpu_device, dh):
-    """one wave per query row: under RS_ATTN_F32_OLD at T = 65 (full and limited context), and as limited-context attention runs
-    above T = 512 — the production path of long recordings in the float32 mode"""
+    """one wave per query row: under RS_ATTN_F32_OLD at T = 65 (full and limited context)"""
     for window in (ar.FULL, W1):
         case = f32_case(dh, 65, window, 64, overlong=True)
         c = contexts(dh, window)
         with switches(c.lib, RS_ATTN_F32_OLD=1):
             got = run(c, case, gpu_device, f32=True)
         check(f"f32 first form<{dh // 64}>", case, window, got, f32=True)
+
+
+@pytest.mark.parametrize("dh", [128, 64])
+def test_f32_keys_long(contexts, gpu_device, dh):
+    """limited-context attention above T = 512 — the production path of long recordings in the float32 mode:
+    attention_f32_keys_kernel<0>, the keys walked 64 at a time with the scores computed twice"""
     case = f32_case(dh, 513, W1, 64)
-    check(f"f32 first form<{dh // 64}>", case, W1, run(contexts(dh, W1), case, gpu_device, f32=True), f32=True)
+    check(f"f32 keys<0> windowed, head_dim {dh}", case, W1, run(contexts(dh, W1), case, gpu_device, f32=True), f32=True)
 
 
 # ---- the content of the padding is never read into a result -------------------------------------------------------------------------
@@ -292,15 +299,15 @@ def test_batch_invariance(contexts, gpu_device, dh):
 
 @pytest.mark.parametrize("dh", [128, 64])
 def test_f32_limited_context_across_the_512_seam(contexts, gpu_device, dh):
-    """T <= 512 takes attention_f32_keys_kernel, T > 512 attention_f32_kernel: other summation orders, so an utterance's bits may
-    change with its batch's padded length across that seam; both sides are held to the float32 tolerance"""
+    """T <= 512 takes attention_f32_keys_kernel<4 / 8> (scores in registers), T > 512 attention_f32_keys_kernel<0> (scores computed twice):
+    one kernel body, the same summation orders, so an utterance's values do not change with its batch's padded length across that seam; both sides are
+    held to the float32 tolerance"""
     for T in (512, 513):
         big, inside, alone = in_and_out(contexts, gpu_device, dh, 300, T, W1, True)
         check(f"f32 limited context at T={T}, head_dim {dh}", big, W1, inside, f32=True)
         small = big.alone(1, 300)
         check(f"f32 keys<8> windowed, head_dim {dh}", small, W1, alone, f32=True)
-        if T == 512:                         # the same kernel on both sides: the invariance holds
-            assert same_values(inside[1, :300], alone[0]), f"f32 keys<8> windowed, head_dim {dh}: n=300 alone != inside T=512"
+        assert same_values(inside[1, :300], alone[0]), f"f32 keys windowed, head_dim {dh}: n=300 alone != inside T={T}"
         differ = int((inside[1, :300] != alone[0]).sum())
         print(f"head_dim {dh}: n=300 alone vs inside T={T}: {differ} of {alone.numel()} elements differ, by at most "
               f"{float((inside[1, :300] - alone[0]).abs().max()):.3g}")
