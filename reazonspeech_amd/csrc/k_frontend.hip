@@ -49,12 +49,29 @@ __device__ __forceinline__ float fetch_sample(const float* __restrict__ a, int i
 // The 512-point transform (two real frames per complex FFT, 8 x 8 x 8 in registers, wave-private LDS): k_fft512.h.
 // Everything a wave touches in LDS is its own, so the steps are separated by wave-level fences, not workgroup
 // barriers; the twiddles are staged once per workgroup.
+//
+// LEAN = false is the first form: every frame pair reads the filterbank (fb_idx, fb_w) from global memory inside the mel chain,
+// and the staged span is sized for the largest hop.  LEAN = true keeps the transform, the staging rule and the mel chain as they
+// are (same fmaf order, same logf: same bits) and changes where the operands wait:
+//   - the filterbank is staged once per workgroup into LDS, tap-major with a row pitch of n_mels + 1 (the coalesced copy from
+//     [mel][FB_MAXW] writes a column: pitch 81 spreads it over the banks; the mel stage reads along a row);
+//   - a lane's items of the mel stage (frame of the pair, mel bin) are the same for every pair, so their first bin and tap count
+//     are looked up once, and the tap loop runs to the wave's largest count with a select — a uniform trip count the compiler
+//     unrolls, so the LDS reads of several taps are in flight together instead of one dependent global load per tap;
+//   - the window sits in eight registers per lane (sample n = lane + 64 k), not in LDS;
+//   - the span is dynamic LDS sized by the actual hop: 49 792 bytes per workgroup at hop 160 / 80 mels, three workgroups per
+//     CU as before (the first form: 47 232), and its samples are asked for from HBM together, not one wait per element.
+constexpr int MEL_PASSES = 4;        // 2 * n_mels <= 256 items over 64 lanes
+template <bool LEAN>
 __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
     __shared__ float2 buf[WAVES][FFT512_BUF];
     __shared__ float pw[WAVES][2][NBIN + 3];
     __shared__ float2 tw[NFFT / 2];
-    __shared__ float ys[SPAN_MAX];
-    __shared__ float win_s[NFFT];
+    __shared__ float ys_first[LEAN ? 1 : SPAN_MAX];
+    __shared__ float win_first[LEAN ? 1 : NFFT];
+    extern __shared__ float lean_lds[];              // LEAN: ys[span] | fbw_s[FB_MAXW][n_mels + 1]
+    float* const ys = LEAN ? lean_lds : ys_first;
+    float* const win_s = win_first;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int len = p.lens[b];
@@ -73,9 +90,30 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
     const int f0 = blockIdx.x * WAVES * FRAMES_PER_WAVE;
     const int i_base = p.kind == 2 ? f0 * p.hop + p.hop / 2 - p.win_length / 2 : f0 * p.hop - NFFT / 2 + centre_off;
     const int span = (WAVES * FRAMES_PER_WAVE - 1) * p.hop + NFFT;
-    for (int idx = threadIdx.x; idx < span; idx += blockDim.x) {
+    const int fb_pitch = p.n_mels + 1;
+    float* const fbw_s = lean_lds + span;
+    float wreg[8];                                    // LEAN: the window at n = lane + 64 k, zero beyond its length
+    int it_m[MEL_PASSES], it_k0[MEL_PASSES], it_cnt[MEL_PASSES];     // LEAN: this lane's mel items (idx = lane + 64 q)
+    int cnt_max = 0;
+    if constexpr (LEAN) {                             // (the tables are in L2: asked for before the samples, they arrive under them)
+#pragma unroll 5
+        for (int e = threadIdx.x; e < p.n_mels * FB_MAXW; e += blockDim.x)       // fb_w[m][j] -> fbw_s[j][m]
+            fbw_s[(e % FB_MAXW) * fb_pitch + e / FB_MAXW] = p.fb_w[e];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wreg[k] = lane + 64 * k < p.win_length ? p.window[lane + 64 * k] : 0.0f;
+#pragma unroll
+        for (int q = 0; q < MEL_PASSES; ++q) {
+            const int idx = lane + 64 * q;
+            const bool on = idx < 2 * p.n_mels;
+            const int m = on ? idx - (idx >= p.n_mels ? p.n_mels : 0) : 0;
+            it_m[q] = m;
+            it_k0[q] = on ? p.fb_idx[2 * m] : 0;
+            it_cnt[q] = on ? min(p.fb_idx[2 * m + 1], FB_MAXW) : 0;
+            cnt_max = max(cnt_max, it_cnt[q]);
+        }
+    }
+    auto padded_index = [&](int idx) -> int {           // element idx of the span -> index in the padded signal after the edge rule
         int i = i_base + idx;
-        float y = 0.0f;
         if (p.kind == 1 && Lp > 1) {                      // torch.stft(pad_mode="reflect"): x[-k] = x[k], x[L-1+k] = x[L-1-k]
             i = i < 0 ? -i : i;
             i = i >= Lp ? 2 * (Lp - 1) - i : i;
@@ -85,6 +123,41 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
             for (int bounce = 0; bounce < 8 && (i < 0 || i >= Lp); ++bounce) i = i < 0 ? -i - 1 : 2 * Lp - 1 - i;
             i = i < 0 ? 0 : (i >= Lp ? Lp - 1 : i);
         }
+        return i;
+    };
+    if constexpr (LEAN) {
+        // The samples come from HBM for the first time.  A loop of "load, load, store" waits for memory once per element and
+        // thread (a dozen times per workgroup); here the loads of STAGE_CHUNK elements per thread are issued together — from a
+        // clamped address, without a branch around them — and the edge rule picks value or zero afterwards.
+        constexpr int STAGE_CHUNK = 12;                   // 12 * 256 = 3072 elements: the whole span at hop 160
+        for (int base = 0; base < span; base += STAGE_CHUNK * 64 * WAVES) {
+            float r0[STAGE_CHUNK], r1[STAGE_CHUNK];
+#pragma unroll
+            for (int k = 0; k < STAGE_CHUNK; ++k) {
+                const int j = padded_index(base + k * 64 * WAVES + (int)threadIdx.x) - p.pad_left;
+                r0[k] = 0.0f; r1[k] = 0.0f;
+                if (len > 0) {                            // (uniform; a[0] need not exist for an empty utterance)
+                    r0[k] = a[min(max(j, 0), len - 1)];
+                    if (p.kind != 2) r1[k] = a[min(max(j - 1, 0), len - 1)];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < STAGE_CHUNK; ++k) {
+                const int idx = base + k * 64 * WAVES + (int)threadIdx.x;
+                const int i = padded_index(idx), j = i - p.pad_left;
+                float y = 0.0f;
+                if (i >= 0 && i < Lp) {
+                    const float x0 = (j >= 0 && j < len) ? r0[k] : 0.0f;
+                    if (p.kind == 2) y = x0;
+                    else y = i >= 1 ? x0 - p.preemph * ((j - 1 >= 0 && j - 1 < len) ? r1[k] : 0.0f) : x0;
+                }
+                if (idx < span) ys[idx] = y;
+            }
+        }
+    } else
+    for (int idx = threadIdx.x; idx < span; idx += blockDim.x) {
+        int i = padded_index(idx);
+        float y = 0.0f;
         if (i >= 0 && i < Lp) {
             const float x0 = fetch_sample(a, i, p.pad_left, len);
             if (p.kind == 2) y = x0;                      // DC removal and pre-emphasis are per FRAME (below)
@@ -92,7 +165,12 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
         }
         ys[idx] = y;
     }
-    for (int idx = threadIdx.x; idx < NFFT; idx += blockDim.x) win_s[idx] = idx < p.win_length ? p.window[idx] : 0.0f;
+    if constexpr (LEAN) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt_max = max(cnt_max, __shfl_xor(cnt_max, off, 64));
+        cnt_max = __builtin_amdgcn_readfirstlane(cnt_max);
+    } else
+        for (int idx = threadIdx.x; idx < NFFT; idx += blockDim.x) win_s[idx] = idx < p.win_length ? p.window[idx] : 0.0f;
     __syncthreads();
     const int frame_base = (blockIdx.x * WAVES + wave) * FRAMES_PER_WAVE;
     auto wave_sync = [&]() { fft512_wave_sync(); };
@@ -100,6 +178,10 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
     auto sample = [&](int t, int n) -> float {
         if (t >= n_valid || t >= p.t_max) return 0.0f;
         return ys[(t - f0) * p.hop + n] * win_s[n];
+    };
+    auto sample_lean = [&](int t, int k) -> float {      // the same product with the window from its register
+        if (t >= n_valid || t >= p.t_max) return 0.0f;
+        return ys[(t - f0) * p.hop + lane + 64 * k] * wreg[k];
     };
     // kaldi: (x[n] - mean) - preemph (x[n - 1] - mean), the first sample against itself; mean over the frame's win_length samples
     auto frame_mean = [&](int t) -> float {
@@ -114,6 +196,13 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
         const float cur = fr[n] - mean, prev = fr[n > 0 ? n - 1 : 0] - mean;
         return (cur - p.preemph * prev) * win_s[n];
     };
+    auto sample_kaldi_lean = [&](int t, int k, float mean) -> float {
+        const int n = lane + 64 * k;
+        if (t >= n_valid || t >= p.t_max || n >= p.win_length) return 0.0f;
+        const float* fr = ys + (t - f0) * p.hop;
+        const float cur = fr[n] - mean, prev = fr[n > 0 ? n - 1 : 0] - mean;
+        return (cur - p.preemph * prev) * wreg[k];
+    };
 
     for (int fi = 0; fi < FRAMES_PER_WAVE; fi += 2) {
         const int t = frame_base + fi;
@@ -122,7 +211,16 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
         // ---- step 1: two frames, samples n = lane + 64 k.  A circular shift of the FFT input only changes the phase,
         // so the 400 samples sit at n = 0 .. 399 directly.
         float2 v[8];
-        if (p.kind == 2) {
+        if constexpr (LEAN) {
+            if (p.kind == 2) {
+                const float m0 = frame_mean(t), m1 = frame_mean(t + 1);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = make_float2(sample_kaldi_lean(t, k, m0), sample_kaldi_lean(t + 1, k, m1));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = make_float2(sample_lean(t, k), sample_lean(t + 1, k));
+            }
+        } else if (p.kind == 2) {
             const float m0 = frame_mean(t), m1 = frame_mean(t + 1);
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = make_float2(sample_kaldi(t, lane + 64 * k, m0), sample_kaldi(t + 1, lane + 64 * k, m1));
@@ -134,6 +232,24 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_kernel(FrontParams p) {
         // ---- split the two spectra, power of bins 0..256
         fft512_split_power(z, pw[wave][0], pw[wave][1], lane);
         // ---- banded mel filterbank + log: lane -> (frame of the pair, mel bin)
+        if constexpr (LEAN) {
+#pragma unroll
+            for (int q = 0; q < MEL_PASSES; ++q) {
+                if (64 * q >= 2 * p.n_mels) break;            // (uniform)
+                const int idx = lane + 64 * q;
+                const int f = idx >= p.n_mels, m = it_m[q], k0 = it_k0[q], cnt = it_cnt[q];
+                const float* pwr = pw[wave][f];
+                const float* wcol = fbw_s + m;
+                float acc = 0.0f;
+#pragma unroll 6
+                for (int j = 0; j < cnt_max; ++j) {           // taps past this item's count are read (clamped) and not taken
+                    const float next = fmaf(wcol[j * fb_pitch], pwr[min(k0 + j, NBIN - 1)], acc);
+                    acc = j < cnt ? next : acc;
+                }
+                if (idx < 2 * p.n_mels && t + f < n_valid && t + f < p.t_max)
+                    p.raw[((size_t)b * p.t_max + t + f) * p.n_mels + m] = p.kind >= 1 ? logf(fmaxf(acc, p.log_guard)) : logf(acc + p.log_guard);
+            }
+        } else
         for (int idx = lane; idx < 2 * p.n_mels; idx += 64) {
             const int f = idx >= p.n_mels, m = idx - f * p.n_mels;
             if (t + f < n_valid && t + f < p.t_max) {
@@ -263,7 +379,12 @@ int rs_launch_frontend(rs_ctx* ctx, const float* audio, const int32_t* lens, int
     }
     const double bytes = (double)B * ((double)t_max * d.hop_length * 4.0 + (double)t_max * d.n_mels * 4.0 * 3.0);
     rs_prof_scope prof(ctx, RS_PROF_FRONTEND, s, (double)B * t_max * (5.0 * 512 * 9 + 3 * 257 + 2 * 600), bytes);
-    hipLaunchKernelGGL(logmel_kernel, grid, block, 0, s, p);
+    if (rs_knob(RS_KNOB_LOGMEL_OLD))
+        hipLaunchKernelGGL(logmel_kernel<false>, grid, block, 0, s, p);
+    else {
+        const size_t lds = ((size_t)(fpb - 1) * d.hop_length + NFFT + (size_t)FB_MAXW * (d.n_mels + 1)) * sizeof(float);
+        hipLaunchKernelGGL(logmel_kernel<true>, grid, block, lds, s, p);
+    }
     if (d.frontend_kind == 2) {
     } else if (d.frontend_kind == 1) {            // (rs_create only: a Conformer context)
         const rs_conformer& cf = *rs_conformer_of(ctx);

@@ -42,6 +42,9 @@
     X(BEAM_SPEC, "RS_BEAM_SPEC", INT, 3, "beam search: evaluations asked for per iteration (1 .. 8; sizes the workspace too)")         \
     X(BEAM_TRACE, "RS_BEAM_TRACE", PRESENT, 0, "beam search: phase timing of the step kernel")                                        \
     X(BEAM_RECORD_LDS, "RS_BEAM_RECORD_LDS", PRESENT, 0, "beam search: the any-vocabulary record kernel on a small vocabulary")       \
+    X(LOGMEL_OLD, "RS_LOGMEL_OLD", PRESENT, 0, "log-mel: the first form (16 frames per workgroup, filterbank read from global memory)") \
+    X(SUB_CONV0_OLD, "RS_SUB_CONV0_OLD", PRESENT, 0, "conv0 + dw1: the first form (a workgroup per output row, every odd conv0 row twice)") \
+    X(SUB_DW_OLD, "RS_SUB_DW_OLD", PRESENT, 0, "bf16 depthwise stage: the first form (a thread per output bin, every input row read by two rows)") \
     X(AVSR_POSCONV_OLD, "RS_AVSR_POSCONV_OLD", PRESENT, 0, "AV-HuBERT positional convolution: the VALU form")                         \
     X(K2_CONV1_OLD, "RS_K2_CONV1_OLD", PRESENT, 0, "Zipformer conv1: the VALU form (the one other channel counts run)")               \
     X(K2_ATTW_SWEEPS, "RS_K2_ATTW_SWEEPS", INT, 1, "Zipformer attention weights: 3 = the three-sweep kernel")                         \
