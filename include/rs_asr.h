@@ -840,6 +840,46 @@ int rs_rnnt_alsd_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_l
                        const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---- hotwords and n-gram LM fusion in the default beam search — added within ABI 7 (probe the symbols) ---------------------------
+ * gives the espnet package what rs_rnnt_alsd_hotwords / _lm give nemo and rs_rnnt_mbs_hotwords / _lm give k2: contextual biasing
+ * from a phrase list (rs_hotwords, stated with rs_rnnt_mbs_hotwords) and shallow fusion of a backoff n-gram model (rs_ngram, stated
+ * with rs_rnnt_alsd_lm), with the tables, `step` and `finalize` of those entries unchanged.
+ * [UPSTREAM, not vendored, UNVERIFIED] espnet2 BeamSearchTransducer.default_beam_search with an LM: `beam_logp, beam_idx =
+ * logp[1:].topk(beam_k)` is taken first, then every label extension k it opens gets `score + beam_logp + lm_weight * lm_scores[k + 1]`
+ * — the slot the reference closes with lm_weight = 0.  (ESPnet cannot run here: the rule is restated from its source text.)  The
+ * hotword rule is this project's own: ESPnet's transducer search has none.
+ * The search is rs_rnnt_beam with these additions.  Every hypothesis carries an LM state and — for an utterance b with
+ * graph_of[b] >= 0 — a context state; both are functions of its label sequence alone.  The start hypothesis [blank] stands at
+ * lm->start and at its graph's root.  Popping a hypothesis with score hs, LM state s and context state c:
+ *   - the record of its joint row is unchanged: the beam_k best labels are picked by raw logit WITHOUT any term;
+ *   - the blank extension is unchanged: kept with hs + logp(blank), states s and c;
+ *   - a label extension v is scored in float32 without contraction, in this order:
+ *         sc = hs + logp(v);   with a graph: (delta, c') = step(c, v), sc = sc + delta;
+ *         with an LM: (lp, s') = step(s, v), sc = sc + (lm_alpha * lp), the product rounded first;
+ *     and enters the open list with sc, s', c'.  The open list ranks sc: the terms decide the pop order and the end-of-frame test
+ *     (`beam` kept scores strictly above the open list's maximum).
+ * After the last frame the survivors keep the kept list's order (ascending by score BEFORE Finalize, ties in kept order); each gets
+ * sc = sc + (-node_score(c)) (Finalize: a phrase left open gives its bonus back); only then norm = sc / len(yseq) (or sc) is formed
+ * and the winner / the n-best ranking is today's.  scores and norm_scores carry the values after Finalize, the LM terms inside.
+ * There is no end-of-sentence term.  rs_rnnt_token_scores keeps reporting the model's unmodified distribution.
+ *   nbest             0: the outputs of rs_rnnt_beam (ids / frames [B][out_cap], n_ids / scores [B]; norm_scores and n_hyps may be
+ *                     NULL);   1..8 and <= beam: the lists and the ranking of rs_rnnt_beam_nbest
+ *   hw, graph_of, lm, lm_alpha   as rs_rnnt_alsd_lm takes them (DEVICE pointers)
+ * With hw == NULL, hw->n_graphs == 0 or graph_of == NULL, AND lm == NULL, lm->n_nodes == 0 or lm_alpha == 0, the plain kernels run:
+ * the instantiation and the bits of rs_rnnt_beam / rs_rnnt_beam_nbest.  An utterance without a graph inside a hotword call gets the
+ * bits of the plain search.  Positive bonuses let an extension outscore its parent, so a frame can need more pops than the plain
+ * search: RS_EOVERFLOW stays the answer.
+ * Errors as rs_rnnt_beam; RS_EINVAL before anything is enqueued for a Zipformer or AV-HuBERT context, a negative or non-finite
+ * lm_alpha, lm->n_logits other than the context's, order outside 1..8, start outside the nodes, negative counts or null arrays in
+ * either table, nbest outside 0..8 or above the beam.  Workspace: rs_rnnt_beam_lm_workspace_bytes (the layout of rs_rnnt_beam plus a
+ * context state and an LM state per open-list and kept entry; 0 for invalid arguments or a context that is not finalized).
+ * Restated in all its forms by tests/espnet_beam_lm_checker.c, which the results equal bit for bit. */
+size_t rs_rnnt_beam_lm_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, int nbest);
+int rs_rnnt_beam_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags,
+                    int max_pops, int nbest, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores,
+                    float* norm_scores, int32_t* n_hyps, int32_t* pops, const rs_hotwords* hw, const int32_t* graph_of,
+                    const rs_ngram* lm, float lm_alpha, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- token log-probabilities of a finished transducer search — added within ABI 7 ----------------
  * gives what NeMo's Hypothesis.token_confidence (preserve_token_confidence, method max_prob), sherpa-onnx's per-token log-probs
  * and ESPnet's scored hypotheses give: how sure the model was of every token it emitted.  A teacher-forced pass over the OUTPUT

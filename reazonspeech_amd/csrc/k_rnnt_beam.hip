@@ -34,7 +34,11 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include <type_traits>
+
 #include "k_rnnt_common.h"
+#include "k_rnnt_hotwords.h"
+#include "k_rnnt_ngram.h"
 
 
 namespace {
@@ -85,6 +89,34 @@ __device__ __forceinline__ void beam_fail(const BeamState& bs, int b) {   // one
     bs.done[b] = 1;
     bs.flags[1] = 1;
     atomicAdd(&bs.flags[0], 1);
+}
+
+// ---- the forms <HW, LM> of the step kernel (rs_rnnt_beam_lm; include/rs_asr.h states the rule).  Every hypothesis carries a context
+// state (a node of its utterance's graph) and an LM state; both are functions of its label sequence alone.  They travel with the
+// ENTRIES the search already keeps, not with the label trie: an open-list entry holds the states of its whole sequence (written by the
+// lane that opened it, or by the frame's end for a survivor), a kept entry those of the hypothesis it is the blank extension of.  A
+// launch loads the kept entries' and the frame-start hypotheses' states into LDS beside their nodes; a label extension popped in a
+// later launch reads its own from global memory next to h_tok, which that pop reads anyway.  The plain form carries none of this:
+// `if constexpr` removes every statement, the argument is empty and the LDS footprint is today's.
+struct BeamNoHw {};      // the kernel argument of the plain form
+struct BeamHw {          // hotwords: the graphs of the call and the node each entry stands at
+    RnntHw t;
+    int32_t* h_ctx;      // [B][max_h]    open list
+    int32_t* k_ctx;      // [B][max_pops] kept list
+};
+struct BeamHwLm : BeamHw {   // n-gram LM: the model, its weight and each entry's LM state (the graphs may be absent)
+    rs_ngram g;
+    float alpha;
+    int32_t* h_lm;       // [B][max_h]
+    int32_t* k_lm;       // [B][max_pops]
+};
+template <bool HW, bool LM>
+using BeamArg = std::conditional_t<LM, BeamHwLm, std::conditional_t<HW, BeamHw, BeamNoHw>>;
+// root of utterance b's graph; the LM form may carry no graphs at all
+template <bool LM, class A>
+__device__ __forceinline__ int beam_root(const A& tb, int b) {
+    if constexpr (LM) { if (tb.t.graph_of == nullptr) return -1; }
+    return hw_root(tb.t, b);
 }
 
 // LDS-only barrier: waits for this wave's LDS traffic, not for its global stores (a __syncthreads() also drains vmcnt, which
@@ -417,15 +449,21 @@ __device__ __forceinline__ void schedule_evals(const BeamState& bs, const Decode
     }
 }
 
-// the first iteration's request: the start hypothesis; grid B, block 256, dynamic LDS like beam_step_kernel
-__global__ __launch_bounds__(256) void beam_first_kernel(BeamState bs, DecodeState st, int B, int L, int H, int J) {
+// the first iteration's request: the start hypothesis (HW / LM: standing at its graph's root and at the model's start state); grid B,
+// block 256, dynamic LDS like beam_step_kernel
+template <bool HW, bool LM>
+__global__ __launch_bounds__(256) void beam_first_kernel(BeamState bs, DecodeState st, int B, int L, int H, int J, BeamArg<HW, LM> tb) {
     extern __shared__ __attribute__((aligned(16))) char beam_smem[];
     float* lsc = reinterpret_cast<float*>(beam_smem);
     short* lrec = reinterpret_cast<short*>(lsc + bs.max_h);
     __shared__ ArgmaxScratch sc;
     const int b = blockIdx.x;
     if (bs.done[b]) return;
-    if (threadIdx.x == 0) { lsc[0] = 0.0f; lrec[0] = -1; sc.cnt[0] = 0; sc.cnt[1] = 0; }
+    if (threadIdx.x == 0) {
+        lsc[0] = 0.0f; lrec[0] = -1; sc.cnt[0] = 0; sc.cnt[1] = 0;
+        if constexpr (HW) { const int r = beam_root<LM>(tb, b); tb.h_ctx[(size_t)b * bs.max_h] = r < 0 ? 0 : r; }
+        if constexpr (LM) tb.h_lm[(size_t)b * bs.max_h] = lm_node(tb.g, tb.g.start);
+    }
     __syncthreads();
     schedule_evals(bs, st, b, B, L, H, J, lsc, lrec, 1, 0, 0, bs.nfree[b], bs.nrec[b], &sc, 0, 0);
 }
@@ -440,13 +478,16 @@ __global__ __launch_bounds__(256) void beam_first_kernel(BeamState bs, DecodeSta
 
 // grid B, block 256.  Dynamic LDS: open-list scores [max_h] f32 + records [max_h] i16, kept score / node / slot / len
 // [max_pops] each, frame-start hypotheses' node / len [max_pops] each, slot marks [n_slots], records [RP * rec_floats], their
-// slots [RP]
+// slots [RP]; HW: the kept entries' and the frame-start hypotheses' context states [max_pops] each; LM: their LM states likewise.
+// HW: the hotword form, LM: the n-gram form (HW on as well; see BeamArg above); the plain form is the same text without the
+// `if constexpr` statements.
+template <bool HW, bool LM>
 __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeState st, const int32_t* __restrict__ enc_lens, int B,
                                                         int L, int H, int J, int beam, int score_norm, int out_cap, int iter,
                                                         int32_t* __restrict__ ids, int32_t* __restrict__ frames,
                                                         int32_t* __restrict__ n_ids, float* __restrict__ scores,
                                                         int32_t* __restrict__ pops, int nbest, float* __restrict__ norm_scores,
-                                                        int32_t* __restrict__ n_hyps) {
+                                                        int32_t* __restrict__ n_hyps, BeamArg<HW, LM> tb) {
     extern __shared__ __attribute__((aligned(16))) char beam_smem[];
     const int MP = bs.max_pops, R = bs.R, KS = bs.KS, RP = bs.RP, RF = bs.rec_floats, K = bs.beam_k;
     float* lsc = reinterpret_cast<float*>(beam_smem);
@@ -460,6 +501,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
     int* used = sl + MP;
     float* recs = reinterpret_cast<float*>(used + bs.n_slots);
     int* rslot = reinterpret_cast<int*>(recs + (size_t)RP * RF);
+    [[maybe_unused]] int* kcx = rslot + RP;                          // HW: context state of kept entry i, of frame-start hypothesis i
+    [[maybe_unused]] int* scx = kcx + MP;
+    [[maybe_unused]] int* klm = scx + MP;                            // LM: their LM states
+    [[maybe_unused]] int* slm = klm + MP;
     __shared__ ArgmaxScratch sc;
     __shared__ int s_nfree;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -473,6 +518,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
     int nh = bs.nh[b], nk = bs.nk[b], npop = bs.npop[b], nnode = bs.nnode[b], pops_add = 0;
     const int nfree = bs.nfree[b];
     const int list = (iter + 1) & 1;
+    [[maybe_unused]] int root = -1;                                  // of this utterance's graph; -1: it has none
+    if constexpr (HW) root = beam_root<LM>(tb, b);
 
     // ---- this launch's view of the utterance, in LDS ----
     for (int i = tid; i < nh; i += 256) {
@@ -481,6 +528,14 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
     }
     for (int i = tid; i < nk; i += 256) { ks[i] = bs.k_score[kb + i]; kn[i] = bs.k_node[kb + i]; ksl[i] = bs.k_slot[kb + i]; kl[i] = bs.k_len[kb + i]; }
     for (int i = tid; i < ninit; i += 256) { sn[i] = bs.h_node[hb + i]; sl[i] = bs.h_len[hb + i]; }
+    if constexpr (HW) {
+        for (int i = tid; i < nk; i += 256) kcx[i] = tb.k_ctx[kb + i];
+        for (int i = tid; i < ninit; i += 256) scx[i] = tb.h_ctx[hb + i];
+    }
+    if constexpr (LM) {
+        for (int i = tid; i < nk; i += 256) klm[i] = tb.k_lm[kb + i];
+        for (int i = tid; i < ninit; i += 256) slm[i] = tb.h_lm[hb + i];
+    }
     {   // the records of this frame: the batch [0, nbatch) and what was asked for since [R, nrec)
         const float* src = bs.rec + ((size_t)b * RP) * RF;
         for (int i = tid; i < nbatch * RF; i += 256) recs[i] = src[i];
@@ -511,6 +566,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
     bool have = false;
     float e_score = 0.0f, hm;
     int e_node = 0, e_len = 0, e_own = 0, e_row = 0, bi, n_good, par = 0;
+    [[maybe_unused]] int e_ctx = 0, e_lm = 0;                        // the popped hypothesis's states
     for (;; par ^= 1) {
         if (have) {                                                  // ---- apply one pop: blank extension + label extensions ----
             const float* rc = recs + (size_t)e_row * RF;
@@ -519,12 +575,26 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
                 const float sc_b = e_score + rc[0];
                 ks[nk] = sc_b; kn[nk] = e_node; ksl[nk] = e_own; kl[nk] = e_len;
                 bs.k_score[kb + nk] = sc_b; bs.k_node[kb + nk] = e_node; bs.k_slot[kb + nk] = e_own; bs.k_len[kb + nk] = e_len;
+                if constexpr (HW) { kcx[nk] = e_ctx; tb.k_ctx[kb + nk] = e_ctx; }       // the blank extension keeps both states
+                if constexpr (LM) { klm[nk] = e_lm; tb.k_lm[kb + nk] = e_lm; }
             }
-            if (tid < n_lab) {
-                const float sc_c = e_score + rc[2 + tid];
+            if (tid < n_lab) {                                       // HW / LM: lane j walks extension j, the walks side by side
+                float sc_c = e_score + rc[2 + tid];
+                const int tok = __float_as_int(rc[2 + K + tid]);
                 const size_t o = hb + nh + tid;
+                if constexpr (HW) {
+                    int nx = 0;
+                    if (root >= 0) { const float delta = hw_step(tb.t.g, root, e_ctx, tok, &nx); sc_c = sc_c + delta; }
+                    tb.h_ctx[o] = nx;
+                }
+                if constexpr (LM) {
+                    int ln = 0;
+                    const float lp = lm_step(tb.g, e_lm, tok, &ln);
+                    sc_c = sc_c + (tb.alpha * lp);
+                    tb.h_lm[o] = ln;
+                }
                 lsc[nh + tid] = sc_c; lrec[nh + tid] = -1;
-                bs.h_score[o] = sc_c; bs.h_node[o] = e_node; bs.h_tok[o] = __float_as_int(rc[2 + K + tid]); bs.h_slot[o] = e_own;
+                bs.h_score[o] = sc_c; bs.h_node[o] = e_node; bs.h_tok[o] = tok; bs.h_slot[o] = e_own;
                 bs.h_len[o] = e_len + 1; bs.h_alive[o] = 1; bs.h_rec[o] = -1;
             }
             nh += n_lab; nk += 1; npop += 1; pops_add += 1;
@@ -538,10 +608,15 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
         const int rp = lrec[bi];
         if (rp < 0) break;                                           // it needs an evaluation
         // ---- its record at this frame is here: pop it now ----
-        if (bi < ninit) { e_node = sn[bi]; e_len = sl[bi]; }
-        else {                                                       // a label extension (opened in an earlier launch): it enters the trie
+        if (bi < ninit) {
+            e_node = sn[bi]; e_len = sl[bi];
+            if constexpr (HW) e_ctx = scx[bi];
+            if constexpr (LM) e_lm = slm[bi];
+        } else {                                                       // a label extension (opened in an earlier launch): it enters the trie
             const int tok = bs.h_tok[hb + bi], parent = bs.h_node[hb + bi];
             e_len = bs.h_len[hb + bi];
+            if constexpr (HW) e_ctx = tb.h_ctx[hb + bi];             // (hw_step / lm_step make a state valid before they use it)
+            if constexpr (LM) e_lm = tb.h_lm[hb + bi];
             if (nnode >= bs.max_nodes) { if (tid == 0) beam_fail(bs, b); return; }
             if (tid == 0) { bs.nodes[(size_t)b * bs.max_nodes + nnode] = make_int2(parent, tok); bs.node_frame[(size_t)b * bs.max_nodes + nnode] = t; }
             e_node = nnode++;
@@ -581,14 +656,20 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState bs, DecodeStat
         }
         const int slot = ksl[i];
         if (last) {                                                  // by position: what the read-back below needs
-            lsc[rank] = score_norm ? si / (float)kl[i] : si;
-            sn[rank] = kn[i]; sl[rank] = kl[i]; used[rank] = __float_as_int(si);
+            float fs = si;
+            if constexpr (HW) {                                      // Finalize: a phrase left open gives its bonus back, before the norm
+                if (root >= 0) fs = si + (-tb.t.g.node_score[hw_node(tb.t.g, kcx[i], root)]);
+            }
+            lsc[rank] = score_norm ? fs / (float)kl[i] : fs;
+            sn[rank] = kn[i]; sl[rank] = kl[i]; used[rank] = __float_as_int(fs);
         } else {
             used[slot] = 1;
             bs.h_score[hb + rank] = si;
             bs.h_node[hb + rank] = kn[i]; bs.h_tok[hb + rank] = -1; bs.h_slot[hb + rank] = slot;
             bs.h_len[hb + rank] = kl[i]; bs.h_alive[hb + rank] = 1;
             bs.h_rec[hb + rank] = desc < R ? desc : -1;
+            if constexpr (HW) tb.h_ctx[hb + rank] = kcx[i];
+            if constexpr (LM) tb.h_lm[hb + rank] = klm[i];
             if (desc < R) {
                 const int row = b * rpu + desc;
                 bs.rec_slot[(size_t)b * RP + desc] = slot;
@@ -686,8 +767,10 @@ struct BeamPlan {                                                    // extents 
     float* a_pre;                                                    // DecodeState.a_pre, writable (beam_act_kernel fills it)
 };
 
-// the search's layout: fills the pointers and extents of `bs` and the decode state `st` of its prediction-network / joint launches
-BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max, int max_pops, rs_arena& a, BeamState& bs, DecodeState& st) {
+// the search's layout: fills the pointers and extents of `bs` and the decode state `st` of its prediction-network / joint launches;
+// `hw` / `lm`: the state arrays of the hotword / LM form (tb.h_ctx, tb.k_ctx / tb.h_lm, tb.k_lm) and their LDS, after everything else
+BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max, int max_pops, bool hw, bool lm, rs_arena& a, BeamState& bs,
+                     DecodeState& st, BeamHwLm& tb) {
     const rs_dims& d = ctx->d;
     BeamPlan p;
     bs.max_pops = max_pops; bs.beam_k = beam_k;
@@ -743,6 +826,8 @@ BeamPlan beam_layout(const rs_ctx* ctx, int B, int beam, int beam_k, int tp_max,
     p.step_lds = (size_t)bs.max_h * 4 + (size_t)(bs.max_h + 1) / 2 * 4 + (size_t)max_pops * 4 * 6 + (size_t)bs.n_slots * 4 +
                  (size_t)bs.RP * bs.rec_floats * 4 + (size_t)bs.RP * 4;
     p.rec_lds = (size_t)4 * (p.zstride + 256) * 4;
+    if (hw) { tb.h_ctx = a.take<int32_t>(nB * bs.max_h); tb.k_ctx = a.take<int32_t>(nB * max_pops); p.step_lds += (size_t)max_pops * 4 * 2; }
+    if (lm) { tb.h_lm = a.take<int32_t>(nB * bs.max_h); tb.k_lm = a.take<int32_t>(nB * max_pops); p.step_lds += (size_t)max_pops * 4 * 2; }
     return p;
 }
 
@@ -750,19 +835,21 @@ int clamp_pops(int beam, int max_pops) { return max_pops > 0 ? max_pops : 16 * b
 
 }  // namespace
 
-size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops) {
+size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, bool hotwords, bool lm) {
     const int V = ctx->d.n_logits;
     const int bm = beam < V ? beam : V, beam_k = bm < V - 1 ? bm : V - 1;
     rs_arena a;
     BeamState bs;
     DecodeState st{};
-    beam_layout(ctx, B, bm, beam_k, tp_max, clamp_pops(bm, max_pops), a, bs, st);
+    BeamHwLm tb{};
+    beam_layout(ctx, B, bm, beam_k, tp_max, clamp_pops(bm, max_pops), hotwords || lm, lm, a, bs, st, tb);
     return a.bytes() + RS_DECODE_SLACK;
 }
 
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
                       int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, int nbest,
-                      float* norm_scores, int32_t* n_hyps, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                      float* norm_scores, int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram,
+                      float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     if (int rc = rs_rnnt_check_dims(ctx, "beam search"); rc != RS_OK) return rc;
@@ -774,7 +861,13 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     rs_arena arena(workspace);
     BeamState bs;
     DecodeState st{};
-    const BeamPlan pl = beam_layout(ctx, B, bm, beam_k, tp_max, mp, arena, bs, st);
+    const bool HWF = hotwords != nullptr && graph_of != nullptr && hotwords->n_graphs > 0;      // else: the plain kernels, today's bits
+    const bool LMF = ngram != nullptr && ngram->n_nodes > 0 && lm_alpha != 0.0f;                // else: the forms above, today's bits
+    BeamHwLm tb{};
+    if (HWF) { tb.t.g = *hotwords; tb.t.graph_of = graph_of; }
+    if (LMF) { tb.g = *ngram; tb.alpha = lm_alpha; }
+    const BeamHw& tb_hw = tb;                                                                   // the hotword form's argument
+    const BeamPlan pl = beam_layout(ctx, B, bm, beam_k, tp_max, mp, HWF || LMF, LMF, arena, bs, st, tb);
     if (workspace_bytes < arena.bytes() + RS_DECODE_SLACK)
         return rs_fail(ctx, RS_EWORKSPACE, "beam search: workspace %zu < %zu", workspace_bytes, arena.bytes() + RS_DECODE_SLACK);
     if (pl.step_lds > 150 * 1024) return rs_fail(ctx, RS_EINVAL, "beam search: beam %d x max_pops %d needs %zu bytes of LDS (> 150 KB): lower max_pops", bm, mp, pl.step_lds);
@@ -785,16 +878,18 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
 
     const bool rec_lds = rs_knob(RS_KNOB_BEAM_RECORD_LDS) != 0;     // test hook: the any-vocabulary variant on a small one
     auto record = rec_lds ? beam_record_kernel<0> : V <= 64 * 16 ? beam_record_kernel<16> : V <= 64 * 48 ? beam_record_kernel<48> : beam_record_kernel<0>;
-    if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_step_kernel, (int)pl.step_lds); rc != RS_OK) return rc;
-    if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)beam_first_kernel, (int)pl.step_lds); rc != RS_OK) return rc;
     if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)record, (int)pl.rec_lds); rc != RS_OK) return rc;
+    // the search, written once: `first_k` and `step_k` are the form's kernels, `tables` their last argument (graphs, model, or nothing)
+    auto search = [&](auto first_k, auto step_k, const auto& tables) -> int {
+    if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)step_k, (int)pl.step_lds); rc != RS_OK) return rc;
+    if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)first_k, (int)pl.step_lds); rc != RS_OK) return rc;
     rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
     RS_HIP(ctx, hipMemsetAsync(bs.t, 0, pl.zero_bytes, s));
     // slot 0 of every utterance: the zero state the search starts from
     RS_HIP(ctx, hipMemset2DAsync(bs.slots, (size_t)bs.n_slots * bs.slot_floats * 4, 0, (size_t)bs.slot_floats * 4, B, s));
     hipLaunchKernelGGL(beam_init_kernel, dim3((B + 255) / 256), dim3(256), 0, s, bs, enc_lens, B, d.blank_id, n_ids, scores, pops, nbest,
                        norm_scores, n_hyps);
-    hipLaunchKernelGGL(beam_first_kernel, dim3(B), dim3(256), pl.step_lds, s, bs, st, B, L, H, J);
+    hipLaunchKernelGGL(first_k, dim3(B), dim3(256), pl.step_lds, s, bs, st, B, L, H, J, tables);
     RS_CHECK_LAUNCH(ctx, "beam init");
 
     const int CHUNK = 32;
@@ -816,8 +911,8 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
             if (int rc = rs_rnnt_launch_joint_logits_indirect(ctx, &st, joint_enc, pl.rows, joint_rts * 32, tp_max, rpu, step, s); rc != RS_OK) return rc;
             hipLaunchKernelGGL(record, dim3(rec_blocks), dim3(256), pl.rec_lds, s, bs, st, st.zapprox, pl.zstride, pl.rows, rpu, V, d.blank_id,
                                step);
-            hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), pl.step_lds, s, bs, st, enc_lens, B, L, H, J, bm, score_norm, out_cap,
-                               step, ids, frames, n_ids, scores, pops, nbest, norm_scores, n_hyps);
+            hipLaunchKernelGGL(step_k, dim3(B), dim3(256), pl.step_lds, s, bs, st, enc_lens, B, L, H, J, bm, score_norm, out_cap,
+                               step, ids, frames, n_ids, scores, pops, nbest, norm_scores, n_hyps, tables);
         }
         RS_CHECK_LAUNCH(ctx, "beam step");
         RS_HIP(ctx, hipMemcpyAsync(hf, bs.flags, sizeof hf, hipMemcpyDeviceToHost, s));
@@ -838,4 +933,8 @@ int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_le
     if (!finished) return rs_fail(ctx, RS_ESTATE, "beam search: %d of %d utterances unfinished after %lld iterations", B - hf[0], B, it);
     if (hf[1]) return rs_fail(ctx, RS_EOVERFLOW, "beam search: a frame needed more than max_pops=%d prediction-network evaluations, or a result has more than out_cap=%d labels", mp, out_cap);
     return RS_OK;
+    };
+    if (LMF) return search(beam_first_kernel<true, true>, beam_step_kernel<true, true>, tb);
+    if (HWF) return search(beam_first_kernel<true, false>, beam_step_kernel<true, false>, tb_hw);
+    return search(beam_first_kernel<false, false>, beam_step_kernel<false, false>, BeamNoHw{});
 }

@@ -20,10 +20,11 @@ int rs_rnnt_mbs_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
                      int length_norm, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int nbest, float* norm_scores,
                      int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
                      void* workspace, size_t workspace_bytes, hipStream_t s);
-size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops);
+size_t rs_rnnt_beam_workspace_bytes_impl(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, bool hotwords, bool lm);
 int rs_rnnt_beam_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int score_norm,
                       int max_pops, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, int nbest,
-                      float* norm_scores, int32_t* n_hyps, void* workspace, size_t workspace_bytes, hipStream_t s);
+                      float* norm_scores, int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram,
+                      float lm_alpha, void* workspace, size_t workspace_bytes, hipStream_t s);
 int rs_rnnt_alsd_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, double ratio,
                       int abs_len, int score_norm, int merge, int out_cap, int32_t* ids, int32_t* steps, int32_t* n_ids,
                       float* scores, int nbest, float* norm_scores, int32_t* n_hyps, const rs_hotwords* hotwords, const int32_t* graph_of, const rs_ngram* ngram, float lm_alpha,
@@ -494,14 +495,17 @@ int rs_rnnt_alsd_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_l
 size_t rs_rnnt_beam_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops) {
     RS_GUARD_QUERY(ctx, rs_rnnt_beam_workspace_bytes, 0);
     if (B <= 0 || beam <= 0 || tp_max < 0 || max_pops < 0 || ctx->d.n_logits < 2) return 0;
-    return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops);
+    return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops, false, false);
 }
 
-// the argument checks and the dispatch of rs_rnnt_beam and rs_rnnt_beam_nbest (nbest >= 1: ids / frames [B][nbest][out_cap], n_ids /
-// scores / norm_scores [B][nbest], n_hyps [B]; rs_rnnt_beam passes nbest = 0 and no lists: the one result)
+// the argument checks and the dispatch of rs_rnnt_beam, rs_rnnt_beam_nbest and rs_rnnt_beam_lm (nbest >= 1: ids / frames
+// [B][nbest][out_cap], n_ids / scores / norm_scores [B][nbest], n_hyps [B]; nbest = 0 and no lists: the one result; hw == nullptr and
+// lm == nullptr: the plain kernels).  The callers have checked `nbest` against the beam, and the tables they take with hotwords_arg /
+// ngram_arg below.
 static int beam_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
                      int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, int32_t* pops, int nbest, float* norm_scores,
-                     int32_t* n_hyps, void* workspace, size_t workspace_bytes, void* stream) {
+                     int32_t* n_hyps, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace,
+                     size_t workspace_bytes, void* stream) {
     if (B < 0 || tp_max < 0 || out_cap < 0 || max_pops < 0) return rs_fail(ctx, RS_EINVAL, "beam search: negative size");
     if (beam < 1) return rs_fail(ctx, RS_EINVAL, "beam search: beam size must be >= 1");
     if (B == 0) return RS_OK;
@@ -519,7 +523,8 @@ static int beam_call(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_len
         return RS_OK;
     }
     return rs_rnnt_beam_impl(ctx, joint_enc, enc_lens, B, tp_max, beam, (flags & RS_BEAM_SCORE_NORM) != 0, max_pops, out_cap, ids,
-                             frames, n_ids, scores, pops, nbest, norm_scores, n_hyps, workspace, workspace_bytes, (hipStream_t)stream);
+                             frames, n_ids, scores, pops, nbest, norm_scores, n_hyps, hw, hw ? graph_of : nullptr, lm, lm_alpha, workspace,
+                             workspace_bytes, (hipStream_t)stream);
 }
 
 int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
@@ -527,14 +532,14 @@ int rs_rnnt_beam(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, i
                  size_t workspace_bytes, void* stream) {
     RS_GUARD(ctx, rs_rnnt_beam);
     return beam_call(ctx, joint_enc, enc_lens, B, tp_max, beam, flags, max_pops, out_cap, ids, frames, n_ids, scores, pops, 0, nullptr,
-                     nullptr, workspace, workspace_bytes, stream);
+                     nullptr, nullptr, nullptr, nullptr, 0.0f, workspace, workspace_bytes, stream);
 }
 
 // ---- n-best lists of the default beam search: the same dispatch with the lists as outputs ----
 size_t rs_rnnt_beam_nbest_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, int nbest) {
     RS_GUARD_QUERY(ctx, rs_rnnt_beam_nbest_workspace_bytes, 0);
     if (B <= 0 || beam <= 0 || tp_max < 0 || max_pops < 0 || ctx->d.n_logits < 2 || nbest < 1 || nbest > 8 || nbest > beam) return 0;
-    return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops);         // the lists live in the outputs
+    return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops, false, false);         // the lists live in the outputs
 }
 
 int rs_rnnt_beam_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
@@ -546,7 +551,31 @@ int rs_rnnt_beam_nbest(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_l
     const int bm = beam < ctx->d.n_logits ? beam : ctx->d.n_logits;                    // (the search clamps the beam to the vocabulary)
     if (nbest > bm) return rs_fail(ctx, RS_EINVAL, "beam search: nbest %d is above the beam %d", nbest, bm);
     return beam_call(ctx, joint_enc, enc_lens, B, tp_max, beam, flags, max_pops, out_cap, ids, frames, n_ids, scores, pops, nbest,
-                     norm_scores, n_hyps, workspace, workspace_bytes, stream);
+                     norm_scores, n_hyps, nullptr, nullptr, nullptr, 0.0f, workspace, workspace_bytes, stream);
+}
+
+// ---- hotwords and an n-gram LM in the default beam search: the same dispatch with the tables; nbest = 0: the one result of
+// rs_rnnt_beam, nbest >= 1: the lists of rs_rnnt_beam_nbest ----
+size_t rs_rnnt_beam_lm_workspace_bytes(const rs_ctx* ctx, int B, int beam, int tp_max, int max_pops, int nbest) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_beam_lm_workspace_bytes, 0);
+    if (B <= 0 || beam <= 0 || tp_max < 0 || max_pops < 0 || ctx->d.n_logits < 2 || nbest < 0 || nbest > 8 || nbest > beam) return 0;
+    return rs_rnnt_beam_workspace_bytes_impl(ctx, B, beam, tp_max, max_pops, true, true);     // the LM form's layout: room for both states
+}
+
+int rs_rnnt_beam_lm(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, int beam, int flags, int max_pops,
+                    int nbest, int out_cap, int32_t* ids, int32_t* frames, int32_t* n_ids, float* scores, float* norm_scores, int32_t* n_hyps,
+                    int32_t* pops, const rs_hotwords* hw, const int32_t* graph_of, const rs_ngram* lm, float lm_alpha, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_beam_lm);
+    if (nbest < 0 || nbest > 8) return rs_fail(ctx, RS_EINVAL, "beam search: nbest must be 0..8, got %d", nbest);      // before anything is enqueued
+    if (beam < 1) return rs_fail(ctx, RS_EINVAL, "beam search: beam size must be >= 1");
+    const int bm = beam < ctx->d.n_logits ? beam : ctx->d.n_logits;                    // (the search clamps the beam to the vocabulary)
+    if (nbest > bm) return rs_fail(ctx, RS_EINVAL, "beam search: nbest %d is above the beam %d", nbest, bm);
+    if (int rc = hotwords_arg(ctx, "beam search", true, &hw, graph_of); rc != RS_OK) return rc;
+    if (int rc = ngram_arg(ctx, "beam search", &lm, lm_alpha); rc != RS_OK) return rc;
+    return beam_call(ctx, joint_enc, enc_lens, B, tp_max, beam, flags, max_pops, out_cap, ids, frames, n_ids, scores, pops, nbest,
+                     nbest > 0 ? norm_scores : nullptr, nbest > 0 ? n_hyps : nullptr, hw, graph_of, lm, lm_alpha, workspace, workspace_bytes,
+                     stream);
 }
 
 size_t rs_rnnt_mbs_workspace_bytes(const rs_ctx* ctx, int B, int max_active_paths, int tp_max, int out_cap) {

@@ -55,6 +55,8 @@ enum { RS_ANYTIME = 0, RS_FINAL = 1 };
     X(rs_rnnt_beam, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                      \
     X(rs_rnnt_beam_nbest_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                                \
     X(rs_rnnt_beam_nbest, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                \
+    X(rs_rnnt_beam_lm_workspace_bytes, C, FINAL, RS_HINT_LSTM_ONLY)                                                                   \
+    X(rs_rnnt_beam_lm, C, FINAL, RS_HINT_LSTM_ONLY)                                                                                   \
     X(rs_rnnt_mbs_workspace_bytes, Z, ANYTIME, RS_HINT_MBS)                                                                           \
     X(rs_rnnt_mbs, Z, FINAL, RS_HINT_MBS)                                                                                             \
     X(rs_rnnt_mbs_hotwords_workspace_bytes, Z, ANYTIME, RS_HINT_MBS)                                                                  \

@@ -14,6 +14,7 @@ beam search with score normalisation (k_rnnt_beam.hip) — the reference's setti
 import numpy as np
 import torch
 
+from ...runtime import k2_hotwords, ngram_lm as ngram
 from ...runtime.model import AsrModel
 
 PADDING = (16000, 8000)          # transcribe.py:10
@@ -83,10 +84,81 @@ def check_nbest(nbest, beam_size):
     return nbest
 
 
+NGRAM_TOKEN_MODES = ("pieces", "ids")
+NEEDS_BEAM = "need the beam search (beam_size > 1): greedy_search has no hypotheses to"
+_SPACE = "\ue000"              # stands for '<space>' while a phrase is encoded (runtime/k2_hotwords.py encode drops real whitespace)
+
+
+def has_lm(ngram_lm_model):
+    return ngram_lm_model is not None and not (isinstance(ngram_lm_model, str) and not ngram_lm_model)
+
+
+def check_fusion_keywords(beam_size, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces", hotwords_file="", hotwords_score=1.5):
+    """the hotword and n-gram LM keywords of load_model / EspnetModel, checked before anything is loaded: ValueError for an alpha or
+    a hotwords_score that is no finite number (alpha >= 0), an unknown token encoding, and — as the k2 package refuses them with
+    greedy_search — an LM or a hotwords file with beam_size <= 1.  Needs no GPU."""
+    ngram.check_alpha(ngram_lm_alpha)
+    if ngram_lm_tokens not in NGRAM_TOKEN_MODES:
+        raise ValueError(f"ngram_lm_tokens must be one of {NGRAM_TOKEN_MODES}, not {ngram_lm_tokens!r} ('pieces' = the symbols of token_list)")
+    if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
+        raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
+    greedy = beam_size is None or int(beam_size) <= 1
+    if greedy and has_lm(ngram_lm_model):
+        raise ValueError(f"an n-gram LM {NEEDS_BEAM.replace('need', 'needs', 1)} re-rank")
+    if greedy and hotwords_file:
+        raise ValueError(f"hotwords {NEEDS_BEAM} bias")
+
+
+def lm_pieces(token_list, blank_id):
+    """the word of an ARPA file that names token i with ngram_lm_tokens="pieces": the symbol of token_list as written there,
+    '<space>' included.  '<blank>', '<unk>' and '<sos/eos>' name no token of an n-gram: the file's `<unk>` is the model's unknown-word
+    entry, `<s>` its start state, and the search appends none of the three to a hypothesis."""
+    special = {"<unk>", "<sos/eos>"}
+    return [None if (i == blank_id or p in special) else p for i, p in enumerate(token_list)]
+
+
+def model_lm(cfg, token_list, ngram_lm_model, ngram_lm_tokens="pieces"):
+    """`ngram_lm_model` (a path to ARPA text, `.gz` allowed, or an NgramLm) -> the NgramLm a model with configuration `cfg` and
+    `token_list` decodes with; the table's n_logits must be the model's.  A KenLM binary is refused by the reader."""
+    if isinstance(ngram_lm_model, ngram.NgramLm):
+        if ngram_lm_model.n_logits != cfg.n_logits:
+            raise ValueError(f"the n-gram LM was built for {ngram_lm_model.n_logits} logits, the model has {cfg.n_logits}")
+        return ngram_lm_model
+    if ngram_lm_tokens not in NGRAM_TOKEN_MODES:
+        raise ValueError(f"ngram_lm_tokens must be one of {NGRAM_TOKEN_MODES}, not {ngram_lm_tokens!r} ('pieces' = the symbols of token_list)")
+    pieces = lm_pieces(token_list, cfg.blank_id) if ngram_lm_tokens == "pieces" else None
+    return ngram.load(ngram_lm_model, cfg.vocab_size, cfg.blank_id, ngram_lm_tokens, pieces, cfg.n_logits)
+
+
+def encode_phrases(phrases, token_list, blank_id, hotwords_score=k2_hotwords.DEFAULT_SCORE):
+    """[(phrase, own score)] (runtime/k2_hotwords.py parse_hotwords) -> [(token ids, score)] against an ESPnet character token list:
+    one token per character; whitespace is '<space>' when the list has it and is dropped otherwise; a phrase with a character
+    outside the list is skipped with the warning the k2 package gives"""
+    tokens = list(token_list)
+    unk_id = tokens.index("<unk>") if "<unk>" in tokens else -1
+    if "<space>" in tokens:
+        tokens[tokens.index("<space>")] = _SPACE
+        phrases = [("".join(_SPACE if c.isspace() else c for c in body.strip()) if isinstance(body, str) else body, own) for body, own in phrases]
+    return k2_hotwords.encode(phrases, tokens, blank_id, unk_id, hotwords_score)
+
+
 class EspnetModel:
+    hotwords = None                 # the model's HotwordGraph (None = no hotwords)
+    hotwords_score = k2_hotwords.DEFAULT_SCORE
+
     def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host",
-                 resample="host", token_scores=False, nbest=None):
-        """nbest: upstream's `Speech2Text(nbest=N)`: `model(speech)` returns the N best hypotheses of the beam search — upstream's
+                 resample="host", token_scores=False, nbest=None, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces",
+                 hotwords_file="", hotwords_score=1.5):
+        """ngram_lm_model / ngram_lm_alpha / ngram_lm_tokens: shallow fusion of a backoff n-gram language model into the default beam
+        search ([UPSTREAM] the `lm_weight * lm_scores` slot of default_beam_search, which the reference closes with lm_weight = 0;
+        include/rs_asr.h rs_rnnt_beam_lm): an ARPA text file (`.gz` allowed) or an `NgramLm` of runtime/ngram_lm.py, its weight, and
+        how a word of the file names a token: "pieces" (default) = the symbols of token_list, '<space>' included, "ids" = decimal
+        ids.  Stored as `model.ngram_lm` / `model.ngram_lm_alpha`, both settable; alpha 0 = the search without the LM.
+        hotwords_file / hotwords_score: contextual biasing from a phrase list (runtime/k2_hotwords.py for the file format: one phrase
+        per line with an optional ` :score`; include/rs_asr.h rs_rnnt_beam_lm for what a hotword does); phrases are encoded per
+        character against token_list.  The model's graph is `model.hotwords`; `model(speech, hotwords=...)` and
+        `recognize_batch(..., hotwords=...)` take a call's own.  Both need beam_size > 1: with the greedy search they raise ValueError.
+        nbest: upstream's `Speech2Text(nbest=N)`: `model(speech)` returns the N best hypotheses of the beam search — upstream's
         `sort_nbest(kept_hyps)[:nbest]`, ranked on the device (include/rs_asr.h rs_rnnt_beam_nbest) — as N tuples (text, tokens, ids,
         hyp) with `hyp.score` set; `recognize_batch(..., nbest=)` gives the same per window.  None (default): one tuple, as ever.
         N above beam_size, or N > 1 with beam_size <= 1, raises ValueError.  Stored as `model.nbest`.
@@ -95,6 +167,7 @@ class EspnetModel:
         assert cfg.espnet and len(token_list) == cfg.vocab_size
         self.segmentation = segmentation
         n_best = check_nbest(nbest, beam_size)
+        check_fusion_keywords(beam_size, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, hotwords_file, hotwords_score)
         if beam_size is not None and int(beam_size) > 1:
             cfg = cfg.with_(decoding="beam", beam_size=int(beam_size), beam_score_norm=True, beam_max_pops=int(max_pops))
         self.beam_size = cfg.beam_size if cfg.decoding == "beam" else 1
@@ -106,13 +179,90 @@ class EspnetModel:
         self.dtype = "float32"
         self._last_enc = self._last_ctc = None
         self.asr_model = _AsrModelView(self)
+        self.hotwords_score = float(hotwords_score)
+        self.hotwords = self.hotword_graph(None, hotwords_file)          # the model's graph (None = no hotwords)
+        if self.hotwords is not None:
+            self.am.hotword_set((self.hotwords,))         # checked (rs_hotwords_check) and uploaded once, at load
+        self.ngram_lm_alpha = ngram_lm_alpha
+        if has_lm(ngram_lm_model):
+            self.ngram_lm = model_lm(cfg, self.token_list, ngram_lm_model, ngram_lm_tokens)
+
+    # ---- hotwords and the n-gram LM ------------------------------------------------------------------------------------
+    def hotword_graph(self, hotwords, hotwords_file=""):
+        """a hotwords argument (a string of phrases separated by `/`, or a list; each phrase with an optional ` :score`; or a
+        HotwordGraph) -> its HotwordGraph, None for nothing; phrases without a score of their own take the model's hotwords_score"""
+        if isinstance(hotwords, k2_hotwords.HotwordGraph):
+            graph = hotwords
+        else:
+            phrases = (k2_hotwords.read_hotwords_file(hotwords_file) if hotwords_file else []) + k2_hotwords.parse_hotwords(hotwords)
+            graph = k2_hotwords.build_graph(encode_phrases(phrases, self.token_list, self.cfg.blank_id, self.hotwords_score))
+        if graph is not None and self.cfg.decoding != "beam":
+            raise ValueError(f"hotwords {NEEDS_BEAM} bias")
+        return graph
+
+    def call_graphs(self, hotwords, n):
+        """the `hotwords=` of a call over n windows -> one HotwordGraph or None per window, or None when no window has one.  None =
+        the model's graph for every window; a string (phrases separated by `/`) or a HotwordGraph = that one for every window,
+        INSTEAD OF the model's; a list = one entry per window, each a string, a list of phrases, a HotwordGraph or None (= the
+        model's)."""
+        if hotwords is None:
+            graphs = [self.hotwords] * n
+        elif isinstance(hotwords, (str, k2_hotwords.HotwordGraph)):
+            graphs = [self.hotword_graph(hotwords)] * n
+        else:
+            if len(hotwords) != n:
+                raise ValueError(f"hotwords: {len(hotwords)} entries for {n} windows (a list has one entry per window; one spec for all is a string)")
+            made = {}
+            graphs = []
+            for h in hotwords:
+                if h is None:
+                    graphs.append(self.hotwords)
+                    continue
+                key = h if isinstance(h, str) else id(h)
+                if key not in made:
+                    made[key] = self.hotword_graph(h)
+                graphs.append(made[key])
+        return graphs if any(g is not None for g in graphs) else None
+
+    def call_lm(self, ngram_lm_alpha):
+        """the `ngram_lm_alpha=` of a call -> what AsrModel.stage takes: None = the model's LM at the model's weight, else (NgramLm or
+        None, alpha); 0 = this call without the LM; a value with no LM loaded raises ValueError"""
+        if ngram_lm_alpha is None:
+            return None
+        alpha = ngram.check_alpha(ngram_lm_alpha)
+        if self.ngram_lm is None and alpha > 0:
+            raise ValueError("ngram_lm_alpha given, but the model has no n-gram LM (load_model(ngram_lm_model=...))")
+        return self.ngram_lm, alpha
+
+    # the model's n-gram LM (an NgramLm, None = no fusion) and its weight: the runtime model's, settable
+    @property
+    def ngram_lm(self):
+        return self.am.ngram_lm
+
+    @ngram_lm.setter
+    def ngram_lm(self, lm):
+        if lm is not None:
+            if self.cfg.decoding != "beam":
+                raise ValueError(f"an n-gram LM {NEEDS_BEAM.replace('need', 'needs', 1)} re-rank")
+            lm = model_lm(self.cfg, self.token_list, lm)
+            self.am.ngram_set(lm)                         # checked (rs_ngram_check) and uploaded once, found again by NgramLm.key
+        self.am.ngram_lm = lm
+
+    @property
+    def ngram_lm_alpha(self):
+        return self.am.ngram_lm_alpha
+
+    @ngram_lm_alpha.setter
+    def ngram_lm_alpha(self, alpha):
+        self.am.ngram_lm_alpha = ngram.check_alpha(alpha)
 
     # ---- the reference's call forms -------------------------------------------------------------------------------
-    def __call__(self, speech):
+    def __call__(self, speech, hotwords=None, ngram_lm_alpha=None):
         """Speech2Text.__call__: n-best list of (text, tokens, token ids, hypothesis): one entry (upstream's default), or
-        `model.nbest` of them from a model loaded with `nbest=N`"""
+        `model.nbest` of them from a model loaded with `nbest=N`.  `hotwords`: this call's phrases instead of the model's (a string of
+        phrases separated by `/`, a list of phrases, or a HotwordGraph); `ngram_lm_alpha`: the LM's weight in this call (None = `model.ngram_lm_alpha`, 0 = without the LM)."""
         wav = np.asarray(speech.detach().cpu().numpy() if isinstance(speech, torch.Tensor) else speech, dtype=np.float32).reshape(-1)
-        res = self._search([wav])
+        res = self._search([wav], hotwords=self.call_graphs(None if hotwords is None else [hotwords], 1), ngram_lm=self.call_lm(ngram_lm_alpha))
         if res.nbest is not None:
             return self._nbest_entries(res, 0)
         ids = res.ids[0]
@@ -143,19 +293,23 @@ class EspnetModel:
     def nbest(self):
         return self.am.nbest
 
-    def recognize_batch(self, waves, isolate_overflow=False, nbest=None):
+    def recognize_batch(self, waves, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm_alpha=None):
         """padded like the reference pads each window (np.pad(samples, PADDING), transcribe.py:69) -> [text].
         `isolate_overflow`: see `_search`.  `nbest=N`: per window the list of `model(speech)` instead — N tuples (text, tokens, ids,
-        hyp), best first (one where the greedy fall-back decoded the window)."""
+        hyp), best first (one where the greedy fall-back decoded the window).  `hotwords`: one spec for every window (a string) or
+        a list with one entry per window (see `call_graphs`); `ngram_lm_alpha`: the LM's weight in this call (0 = without the LM)."""
         padded = [np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves]
+        fused = dict(hotwords=self.call_graphs(hotwords, len(padded)), ngram_lm=self.call_lm(ngram_lm_alpha))
         if nbest is None:
-            return [self.ids_to_text(ids) for ids in self._search(padded, isolate_overflow=isolate_overflow).ids]
-        res = self._search(padded, isolate_overflow=isolate_overflow, nbest=check_nbest(nbest, self.beam_size) or 1)
+            return [self.ids_to_text(ids) for ids in self._search(padded, isolate_overflow=isolate_overflow, **fused).ids]
+        res = self._search(padded, isolate_overflow=isolate_overflow, nbest=check_nbest(nbest, self.beam_size) or 1, **fused)
         return [self._nbest_entries(res, b) for b in range(len(padded))]
 
-    def recognize_batch_scored(self, waves, isolate_overflow=False):
-        """`recognize_batch` of a model with `token_scores` on -> ([text], [(token ids, log-probabilities)])"""
-        res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves], isolate_overflow=isolate_overflow)
+    def recognize_batch_scored(self, waves, isolate_overflow=False, hotwords=None, ngram_lm_alpha=None):
+        """`recognize_batch` of a model with `token_scores` on -> ([text], [(token ids, log-probabilities)]); the log-probabilities
+        are the model's own, without hotword bonus or LM term"""
+        res = self._search([np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves], isolate_overflow=isolate_overflow,
+                           hotwords=self.call_graphs(hotwords, len(waves)), ngram_lm=self.call_lm(ngram_lm_alpha))
         if res.token_logprobs is None:
             raise ValueError("recognize_batch_scored needs token_scores=True")
         return [self.ids_to_text(ids) for ids in res.ids], list(zip(res.ids, res.token_logprobs))
@@ -168,7 +322,7 @@ class EspnetModel:
     def token_scores(self, value):
         self.am.token_scores = bool(value)
 
-    def _search(self, waves, max_batch=256, isolate_overflow=False, nbest=None):
+    def _search(self, waves, max_batch=256, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm=None):
         """the transducer search over a batch of (padded) windows.  Upstream's default beam search has no bound on the
         prediction-network evaluations a frame may take; the device search has one (`max_pops`, which sizes its workspace)
         and reports RS_EOVERFLOW instead of truncating.  The front end and the encoder run ONCE per batch; a decode that hits
@@ -183,7 +337,11 @@ class EspnetModel:
 
         `nbest`: entries per window for this call (None = `model.nbest`).  With lists on, `DecodedBatch.nbest` holds every window's;
         the retry ladder is the same, and a window the greedy fall-back decoded has a list of one (score NaN: the greedy search
-        keeps none) and `degraded`."""
+        keeps none) and `degraded`.
+
+        `hotwords`: None, or one HotwordGraph / None per window (`call_graphs`); `ngram_lm`: None = the model's LM and weight, or
+        (NgramLm or None, alpha) for this call (`call_lm`).  Positive bonuses can make a frame take more pops: the ladder is the same,
+        and the greedy fall-back runs without either and stays flagged `degraded`."""
         from ...runtime.capi import RsError, RS_EOVERFLOW
         from ...runtime.model import DecodedBatch
         am = self.am
@@ -196,7 +354,9 @@ class EspnetModel:
         bound = am.cfg.beam_max_pops or 16 * am.cfg.beam_size
         out = DecodedBatch([], [], [], [], [], token_logprobs=[] if am.token_scores else None, nbest=[] if n_best else None)
         for lo in range(0, len(waves), max_batch):
-            buf = am.stage([np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]], nbest=n_best)
+            graphs = None if hotwords is None else list(hotwords[lo:lo + max_batch])
+            buf = am.stage([np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]], nbest=n_best,
+                           hotwords=am.graph_plan(graphs, len(graphs)) if graphs is not None else None, ngram_lm=ngram_lm)
             with torch.cuda.device(am.device):
                 stream = torch.cuda.current_stream().cuda_stream
                 am.run_encoder(buf, stream)
@@ -210,8 +370,8 @@ class EspnetModel:
                         if e.code != RS_EOVERFLOW:
                             raise
                 if used is None and isolate_overflow and buf.B > 1:
-                    for w in waves[lo:lo + max_batch]:
-                        one = self._search([w], max_batch=1, nbest=n_best)
+                    for k, w in enumerate(waves[lo:lo + max_batch]):
+                        one = self._search([w], max_batch=1, nbest=n_best, hotwords=None if graphs is None else [graphs[k]], ngram_lm=ngram_lm)
                         out.ids += one.ids; out.frames += one.frames; out.enc_lens += one.enc_lens
                         out.scores += one.scores; out.degraded += one.degraded
                         if out.nbest is not None:

@@ -23,7 +23,8 @@ CHECKPOINT_ENV = "REAZONSPEECH_ESPNET_CHECKPOINT"
 
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False,
-               segmentation="host", resample="host", token_scores=False, nbest=None):
+               segmentation="host", resample="host", token_scores=False, nbest=None, ngram_lm_model=None, ngram_lm_alpha=0.0,
+               ngram_lm_tokens="pieces", hotwords_file="", hotwords_score=1.5):
     """Load the ReazonSpeech ESPnet model onto a ROCm GPU (transcribe.py:12-32).
 
     Args:
@@ -63,14 +64,31 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         whose `hyp.score` and `hyp.norm_score` are NaN — the greedy search keeps no score; test with `math.isnan` before sorting.  N above the
         beam, or N > 1 with the greedy search, raises ValueError.
 
+      ngram_lm_model (str or NgramLm), ngram_lm_alpha (float), ngram_lm_tokens (str): shallow fusion of a backoff n-gram language
+        model trained on the user's own text into the default beam search — [UPSTREAM] the `lm_weight * lm_scores` slot of
+        default_beam_search, which the reference closes with lm_weight = 0 (include/rs_asr.h rs_rnnt_beam_lm).  An ARPA text file
+        (`.gz` allowed; a KenLM binary is refused) or an `NgramLm`; its weight (0 = off; `model.ngram_lm_alpha` is settable); how a
+        word of the file names a token: "pieces" (default) = the symbols of token_list, '<space>' included, "ids" = decimal ids.
+        `<s>` is the start state; there is no end-of-sentence term.
+      hotwords_file (str), hotwords_score (float): contextual biasing from a phrase list, one phrase per line with an optional
+        ` :score` (runtime/k2_hotwords.py); a phrase is encoded per character against token_list (whitespace is '<space>' when the
+        list has it, dropped otherwise; a phrase with a character outside the list is skipped with a warning).  `model(speech,
+        hotwords=...)`, `recognize_batch`, `transcribe` and `transcribe_batch` take a call's own phrases.
+        Both need `beam_size > 1`: with the greedy search they raise ValueError.  A bonus can make a frame take more pops than
+        `max_pops` allows: the retry ladder is the one described there, and the greedy fall-back runs without either.
+
     The reference downloads `reazon-research/reazonspeech-espnet-v2` through espnet_model_zoo (:27-31), which an offline box
     cannot do: give `checkpoint=` / the environment variable.  Without a checkpoint this RAISES; seeded synthetic weights of
     the architecture (timings valid, transcripts meaningless) are loaded only on request — `config=`, `synthetic=True` or
     $REAZONSPEECH_AMD_SYNTHETIC=1 — and a warning says so."""
     from ...runtime.config import ESPNET_CONFORMER_120M
     from ...runtime.weights_espnet import synthetic_state_dict_espnet
-    from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES, check_nbest
-    check_nbest(nbest, beam_size if beam_size is not None else (1 if config is not None or synthetic else 20))     # argument errors first
+    from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES, check_nbest, check_fusion_keywords
+    beam_known = beam_size if beam_size is not None else (1 if config is not None or synthetic else 20)
+    check_nbest(nbest, beam_known)                        # argument errors first
+    check_fusion_keywords(beam_known, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, hotwords_file, hotwords_score)
+    fusion = dict(ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens, hotwords_file=hotwords_file,
+                  hotwords_score=hotwords_score)
     from ...runtime.resample import check_mode
     if segmentation not in SEGMENTATION_MODES:
         raise ValueError(f"segmentation must be one of {SEGMENTATION_MODES}, got {segmentation!r}")
@@ -87,7 +105,8 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
             raise FileNotFoundError(f"checkpoint {checkpoint!r} does not exist")
         cfg, sd, tokens = read_espnet(checkpoint)
         return EspnetModel(cfg, sd, tokens, device=device, beam_size=20 if beam_size is None else beam_size, max_pops=max_pops,
-                           precision=precision, segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest)
+                           precision=precision, segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest,
+                           **fusion)
     cfg = config or ESPNET_CONFORMER_120M
     if config is None:
         if not (synthetic or os.environ.get("REAZONSPEECH_AMD_SYNTHETIC", "0") not in ("", "0")):
@@ -98,7 +117,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
               "(`synthetic=True` / $REAZONSPEECH_AMD_SYNTHETIC): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
     return EspnetModel(cfg, synthetic_state_dict_espnet(cfg, seed), synthetic_token_list(cfg.vocab_size, seed), device=device,
                        beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision,
-                       segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest)
+                       segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest, **fusion)
 
 
 def _windows(model, waveform, window):
@@ -152,13 +171,33 @@ def plan_windows(lengths, window, find_cuts):
     return pieces
 
 
-def transcribe(model, audio, config=None):
+def _fused(hotwords, ngram_lm_alpha):
+    """the keywords a recogniser call gets: only those that were given, so that a model without them is called as ever"""
+    return {k: v for k, v in (("hotwords", hotwords), ("ngram_lm_alpha", ngram_lm_alpha)) if v is not None}
+
+
+def per_recording(hotwords, n):
+    """`hotwords=` of transcribe_batch -> one spec per recording: a string (phrases separated by `/`) or a HotwordGraph is every
+    recording's; a list has one entry per recording (a string, a list of phrases, a HotwordGraph, or None = the model's own)"""
+    if hotwords is None:
+        return None
+    if isinstance(hotwords, str) or not hasattr(hotwords, "__len__"):
+        return [hotwords] * n
+    if len(hotwords) != n:
+        raise ValueError(f"hotwords: {len(hotwords)} entries for {n} recordings (a list has one entry per recording; one spec for all is a string)")
+    return list(hotwords)
+
+
+def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None):
     """Interface function to transcribe audio data (transcribe.py:34-82).
 
     Args:
       model (EspnetModel): what `load_model()` returned
       audio (AudioData): Audio to transcribe
       config (TranscribeConfig): Additional settings
+      hotwords: this recording's phrases (a string of phrases separated by `/`, a list of phrases, or a HotwordGraph) instead of
+        the model's; they apply to every 20 s window cut from it
+      ngram_lm_alpha (float): the weight of the model's n-gram LM in this call (None = `model.ngram_lm_alpha`, 0 = without the LM)
 
     Returns:
       TranscribeResult
@@ -173,8 +212,11 @@ def transcribe(model, audio, config=None):
     total = len(audio.waveform)
     texts, segments = [], []
     scored = [] if getattr(model, "token_scores", False) else None
+    if hotwords is not None and not isinstance(hotwords, str) and hasattr(model, "hotword_graph"):
+        hotwords = model.hotword_graph(hotwords)           # a list is ONE recording's phrases: built once, shared by its windows
+    fused = _fused(hotwords, ngram_lm_alpha)
     for offset, samples in _windows(model, audio.waveform, int(WINDOW_SECONDS * rate)):
-        best = model(np.pad(samples, PADDING, mode="constant"))[0]           # nbest[0] = (text, tokens, ids, hypothesis)
+        best = model(np.pad(samples, PADDING, mode="constant"), **fused)[0]           # nbest[0] = (text, tokens, ids, hypothesis)
         text = best[0]
         texts.append(text)
         if scored is not None:
@@ -187,8 +229,12 @@ def transcribe(model, audio, config=None):
     return make_result("".join(texts), segments, scored)
 
 
-def transcribe_batch(model, audios, config=None):
+def transcribe_batch(model, audios, config=None, hotwords=None, ngram_lm_alpha=None):
     """Additive: many utterances recognised as one batch on the device.
+
+    `hotwords`: one spec for every recording (a string) or a list with one entry per recording (`per_recording`); a recording's
+    hotwords apply to every window cut from it, also on the pooled long-form path.  `ngram_lm_alpha`: the weight of the model's
+    n-gram LM in this call (0 = without the LM).
 
     `model.segmentation == "host"`: SHORT utterances (each at most one 20 s window) are recognised as one batch and segmented
     one by one on the host; an utterance longer than a window goes through `transcribe` on its own.
@@ -202,26 +248,28 @@ def transcribe_batch(model, audios, config=None):
         config = TranscribeConfig(verbose=False)
     norm = [AudioData(w, SAMPLERATE) for w in norm_batch(model, audios, norm_audio)]
     window = int(WINDOW_SECONDS * 16000)
+    hotwords = per_recording(hotwords, len(norm))
     if getattr(model, "segmentation", "host") == "device":
-        return _transcribe_pooled(model, norm, window)
+        return _transcribe_pooled(model, norm, window, hotwords, ngram_lm_alpha)
     short = [i for i, a in enumerate(norm) if len(a.waveform) <= window]
     out = [None] * len(norm)
     with_scores = getattr(model, "token_scores", False)
+    fused = _fused(None if hotwords is None else [hotwords[i] for i in short], ngram_lm_alpha)
     if with_scores and short:
-        texts, scored = model.recognize_batch_scored([norm[i].waveform for i in short])
+        texts, scored = model.recognize_batch_scored([norm[i].waveform for i in short], **fused)
     else:
-        texts, scored = (model.recognize_batch([norm[i].waveform for i in short]) if short else []), None
+        texts, scored = (model.recognize_batch([norm[i].waveform for i in short], **fused) if short else []), None
     pieces = [split_text(model, norm[i].waveform, asr) for i, asr in zip(short, texts)]
     for k, (i, asr, segments) in enumerate(zip(short, texts, pieces)):
         segs = [Segment(start / 16000, end / 16000, text) for start, end, text in segments]
         out[i] = make_result(asr, segs, [scored[k]] if scored is not None else None)
     for i, a in enumerate(norm):
         if out[i] is None:
-            out[i] = transcribe(model, a, TranscribeConfig(verbose=False))
+            out[i] = transcribe(model, a, TranscribeConfig(verbose=False), **_fused(None if hotwords is None else hotwords[i], ngram_lm_alpha))
     return out
 
 
-def _transcribe_pooled(model, norm, window):
+def _transcribe_pooled(model, norm, window, hotwords=None, ngram_lm_alpha=None):
     """`transcribe_batch` with the segmentation on the device: plan the pieces of every recording, then recognise and align
     the pool of all pieces, longest first so that a chunk of 256 holds pieces of similar length"""
     waves = [a.waveform for a in norm]
@@ -232,13 +280,15 @@ def _transcribe_pooled(model, norm, window):
     samples = [waves[pool[k][0]][pool[k][1]:pool[k][1] + pool[k][2]] for k in order]
     texts, timings = [None] * len(pool), [None] * len(pool)
     scored = [None] * len(pool) if getattr(model, "token_scores", False) else None
+    # a piece is recognised with the hotwords of the recording it was cut from
+    fused = _fused(None if hotwords is None else [hotwords[pool[k][0]] for k in order], ngram_lm_alpha)
     if pool:
         if scored is not None:
-            recognised, piece_scores = model.recognize_batch_scored(samples, isolate_overflow=True)
+            recognised, piece_scores = model.recognize_batch_scored(samples, isolate_overflow=True, **fused)
             for k, sc in zip(order, piece_scores):
                 scored[k] = sc
         else:
-            recognised = model.recognize_batch(samples, isolate_overflow=True)
+            recognised = model.recognize_batch(samples, isolate_overflow=True, **fused)
         for k, text in zip(order, recognised):
             texts[k] = text
         for k, t in zip(order, model.align_batch(samples, [texts[k] for k in order])):

@@ -41,6 +41,7 @@ EXPORTS = [
     "rs_rnnt_mbs_lm", "rs_rnnt_mbs_lm_workspace_bytes",
     "rs_rnnt_mbs_nbest", "rs_rnnt_mbs_nbest_workspace_bytes",
     "rs_rnnt_beam_nbest", "rs_rnnt_beam_nbest_workspace_bytes",
+    "rs_rnnt_beam_lm", "rs_rnnt_beam_lm_workspace_bytes",
     "rs_rnnt_alsd_nbest", "rs_rnnt_alsd_nbest_workspace_bytes",
     "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes", "rs_rnnt_align", "rs_rnnt_align_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
@@ -282,6 +283,11 @@ def load():
     lib.rs_rnnt_alsd_nbest.restype = c_int
     lib.rs_rnnt_alsd_nbest_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_double, c_int, c_int]
     lib.rs_rnnt_alsd_nbest_workspace_bytes.restype = c_size_t
+    # the default beam search with tables: the n-best entry's arguments (nbest may be 0), the most general tables before the tail
+    lib.rs_rnnt_beam_lm.argtypes = lib.rs_rnnt_beam_nbest.argtypes[:-3] + hw_args + [POINTER(RsNgram), c_float] + tail
+    lib.rs_rnnt_beam_lm.restype = c_int
+    lib.rs_rnnt_beam_lm_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int, c_int]
+    lib.rs_rnnt_beam_lm_workspace_bytes.restype = c_size_t
     lib.rs_ngram_check.argtypes = [POINTER(RsNgram), c_char_p, c_size_t]
     lib.rs_profile_enable.argtypes = [vp, c_int]
     lib.rs_profile_reset.argtypes = [vp]
@@ -568,16 +574,42 @@ class Context:
         else:
             self.check(self.lib.rs_rnnt_alsd(*head, *tail))
 
-    def beam_workspace_bytes(self, B, beam, tp_max, max_pops=0):
+    def beam_workspace_bytes(self, B, beam, tp_max, max_pops=0, *, hotwords=False, lm=False, nbest=0):
+        """the workspace of `rnnt_beam` (`nbest` > 0: of `rnnt_beam_nbest`) called with a hotword set (`hotwords`) and / or an n-gram
+        LM (`lm`), from the entry's own query"""
+        if hotwords or lm:
+            n = self.lib.rs_rnnt_beam_lm_workspace_bytes(self._h, B, beam, tp_max, max_pops, int(nbest))
+            if n == 0:
+                raise RuntimeError("rs_rnnt_beam_lm_workspace_bytes: invalid arguments (a finalized Conformer context, nbest 0..8 and <= beam)")
+            return n
+        if nbest:
+            return self.beam_nbest_workspace_bytes(B, beam, tp_max, max_pops, nbest)
         n = self.lib.rs_rnnt_beam_workspace_bytes(self._h, B, beam, tp_max, max_pops)
         if n == 0:
             raise RuntimeError("rs_rnnt_beam_workspace_bytes: invalid arguments")
         return n
 
-    def rnnt_beam(self, joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, ids, n_ids, scores, pops, ws, stream, frames=None):
+    def _rnnt_beam_lm(self, joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, nbest, out_cap, ids, frames, n_ids, scores, norm_scores,
+                      n_hyps, pops, ws, stream, hotwords, graph_of, lm, lm_alpha):
+        assert graph_of is None or graph_of.numel() >= B
+        self.check(self.lib.rs_rnnt_beam_lm(
+            self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, 1 if score_norm else 0, int(max_pops), int(nbest), out_cap, _ptr(ids),
+            _ptr(frames) if frames is not None else None, _ptr(n_ids), _ptr(scores), _ptr(norm_scores) if norm_scores is not None else None,
+            _ptr(n_hyps) if n_hyps is not None else None, _ptr(pops), byref(hotwords) if hotwords is not None else None,
+            _ptr(graph_of) if graph_of is not None else None, byref(lm) if lm is not None else None, float(lm_alpha), _ptr(ws),
+            ws.numel() * ws.element_size(), c_void_p(stream)))
+
+    def rnnt_beam(self, joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, ids, n_ids, scores, pops, ws, stream, frames=None, *,
+                  hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
         """ESPnet's default transducer beam search: ids (and frames, optional) int32 [B][out_cap], n_ids / pops int32 [B],
-        scores float32 [B]"""
+        scores float32 [B].
+        Contextual biasing: `hotwords` = an RsHotwords of device pointers, `graph_of` int32 [B] on the device (-1 = the utterance has
+        no graph).  N-gram LM on every label extension: `lm` = an RsNgram of device pointers, `lm_alpha` its weight (0 = no model).
+        The call goes to the narrowest entry that takes what was passed: rs_rnnt_beam_lm or rs_rnnt_beam."""
         assert frames is None or frames.shape == ids.shape
+        if hotwords is not None or graph_of is not None or lm is not None or lm_alpha:
+            return self._rnnt_beam_lm(joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, 0, ids.shape[1], ids, frames, n_ids, scores,
+                                      None, None, pops, ws, stream, hotwords, graph_of, lm, lm_alpha)
         self.check(self.lib.rs_rnnt_beam(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, 1 if score_norm else 0,
                                          int(max_pops), ids.shape[1], _ptr(ids), _ptr(frames) if frames is not None else None, _ptr(n_ids), _ptr(scores), _ptr(pops), _ptr(ws),
                                          ws.numel() * ws.element_size(), c_void_p(stream)))
@@ -589,11 +621,15 @@ class Context:
         return n
 
     def rnnt_beam_nbest(self, joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, nbest, ids, n_ids, scores, norm_scores, n_hyps,
-                        pops, ws, stream, frames=None):
+                        pops, ws, stream, frames=None, *, hotwords=None, graph_of=None, lm=None, lm_alpha=0.0):
         """rs_rnnt_beam_nbest: ESPnet's default beam search with upstream's `sort_nbest(kept_hyps)[:nbest]` — ids (and frames,
-        optional) int32 [B][nbest][out_cap], n_ids int32 [B][nbest], scores / norm_scores float32 [B][nbest], n_hyps / pops int32 [B]"""
+        optional) int32 [B][nbest][out_cap], n_ids int32 [B][nbest], scores / norm_scores float32 [B][nbest], n_hyps / pops int32 [B].
+        Tables as `rnnt_beam`: with any of them the call goes to rs_rnnt_beam_lm."""
         assert ids.dim() == 3 and ids.shape[:2] == (B, nbest) and (frames is None or frames.shape == ids.shape)
         assert n_ids.numel() >= B * nbest and scores.numel() >= B * nbest and norm_scores.numel() >= B * nbest and n_hyps.numel() >= B
+        if hotwords is not None or graph_of is not None or lm is not None or lm_alpha:
+            return self._rnnt_beam_lm(joint_enc, enc_lens, B, tp_max, beam, score_norm, max_pops, nbest, ids.shape[2], ids, frames, n_ids,
+                                      scores, norm_scores, n_hyps, pops, ws, stream, hotwords, graph_of, lm, lm_alpha)
         self.check(self.lib.rs_rnnt_beam_nbest(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, beam, 1 if score_norm else 0, int(max_pops),
                                                int(nbest), ids.shape[2], _ptr(ids), _ptr(frames), _ptr(n_ids), _ptr(scores), _ptr(norm_scores),
                                                _ptr(n_hyps), _ptr(pops), _ptr(ws), ws.numel() * ws.element_size(), c_void_p(stream)))

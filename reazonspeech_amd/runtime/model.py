@@ -519,15 +519,18 @@ class AsrModel:
         fused = dict(lm=lm[0].struct, lm_alpha=lm[1]) if lm is not None else {}
         if cfg.decoding == "beam" and n_best:             # ... with upstream's sort_nbest(kept_hyps)[:nbest] (rs_rnnt_beam_nbest: the same kernels)
             nb = self._nbest_bufs(buf, n_best)
-            sws = self._search_ws(buf, ctx.beam_nbest_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops, n_best))
+            sws = self._search_ws(buf, ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops, hotwords=hw is not None,
+                                                                lm=lm is not None, nbest=n_best))
             ctx.rnnt_beam_nbest(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops, n_best,
-                                nb["ids"], nb["n_ids"], nb["scores"], nb["norm_scores"], nb["n_hyps"], buf.pops, sws, stream, frames=nb["frames"])
+                                nb["ids"], nb["n_ids"], nb["scores"], nb["norm_scores"], nb["n_hyps"], buf.pops, sws, stream, frames=nb["frames"],
+                                **hot, **fused)
             self._nbest_head(buf, nb, stream)
             buf.nbest_n = n_best
         elif cfg.decoding == "beam":
-            sws = self._search_ws(buf, ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops))
+            sws = self._search_ws(buf, ctx.beam_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, cfg.beam_max_pops, hotwords=hw is not None,
+                                                                lm=lm is not None))
             ctx.rnnt_beam(buf.joint_enc, buf.enc_lens, buf.B, buf.tp_max, cfg.beam_size, cfg.beam_score_norm, cfg.beam_max_pops,
-                          buf.ids, buf.n_ids, buf.scores, buf.pops, sws, stream, frames=buf.frames)
+                          buf.ids, buf.n_ids, buf.scores, buf.pops, sws, stream, frames=buf.frames, **hot, **fused)
         elif cfg.decoding == "modified_beam_search" and n_best:      # ... with its ranked list (rs_rnnt_mbs_nbest: the same kernels)
             nb = self._nbest_bufs(buf, n_best)
             sws = self._search_ws(buf, ctx.mbs_nbest_workspace_bytes(buf.B, cfg.beam_size, buf.tp_max, buf.ids.shape[1], n_best))
@@ -777,7 +780,7 @@ class AsrModel:
             return None
         if not (np.isfinite(alpha) and alpha > 0):
             raise ValueError(f"ngram_lm_alpha must be a finite number >= 0, not {alpha!r}")
-        if self.cfg.decoding == "modified_beam_search":  # (the k2 package; its greedy_search is refused in its own words)
+        if self.cfg.decoding in ("modified_beam_search", "beam"):  # (the k2 and espnet packages; their greedy searches are refused in their own words)
             return self.ngram_set(lm), float(alpha)
         if getattr(self.cfg, "family", None) == "k2":
             raise ValueError(f"an n-gram LM needs decoding_method='modified_beam_search', not {self.cfg.decoding!r}")
@@ -793,7 +796,7 @@ class AsrModel:
             raise ValueError(f"hotwords: {len(hotwords)} entries for {n} utterances")
         if all(g is None for g in hotwords):
             return None
-        if self.cfg.decoding not in ("modified_beam_search", "alsd"):      # greedy has no hypotheses to bias; "beam" has no hotword form
+        if self.cfg.decoding not in ("modified_beam_search", "alsd", "beam"):      # greedy has no hypotheses to bias
             if getattr(self.cfg, "family", "") == "k2":
                 raise ValueError("hotwords need decoding_method='modified_beam_search'")
             raise ValueError(f"hotwords need decoding='alsd', not {self.cfg.decoding!r}")
