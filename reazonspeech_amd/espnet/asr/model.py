@@ -14,7 +14,7 @@ beam search with score normalisation (k_rnnt_beam.hip) — the reference's setti
 import numpy as np
 import torch
 
-from ...runtime import k2_hotwords, ngram_lm as ngram
+from ...runtime import fusion, k2_hotwords
 from ...runtime.model import AsrModel
 
 PADDING = (16000, 8000)          # transcribe.py:10
@@ -84,29 +84,17 @@ def check_nbest(nbest, beam_size):
     return nbest
 
 
-NGRAM_TOKEN_MODES = ("pieces", "ids")
-NEEDS_BEAM = "need the beam search (beam_size > 1): greedy_search has no hypotheses to"
 _SPACE = "\ue000"              # stands for '<space>' while a phrase is encoded (runtime/k2_hotwords.py encode drops real whitespace)
-
-
-def has_lm(ngram_lm_model):
-    return ngram_lm_model is not None and not (isinstance(ngram_lm_model, str) and not ngram_lm_model)
 
 
 def check_fusion_keywords(beam_size, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces", hotwords_file="", hotwords_score=1.5):
     """the hotword and n-gram LM keywords of load_model / EspnetModel, checked before anything is loaded: ValueError for an alpha or
     a hotwords_score that is no finite number (alpha >= 0), an unknown token encoding, and — as the k2 package refuses them with
     greedy_search — an LM or a hotwords file with beam_size <= 1.  Needs no GPU."""
-    ngram.check_alpha(ngram_lm_alpha)
-    if ngram_lm_tokens not in NGRAM_TOKEN_MODES:
-        raise ValueError(f"ngram_lm_tokens must be one of {NGRAM_TOKEN_MODES}, not {ngram_lm_tokens!r} ('pieces' = the symbols of token_list)")
-    if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
-        raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
-    greedy = beam_size is None or int(beam_size) <= 1
-    if greedy and has_lm(ngram_lm_model):
-        raise ValueError(f"an n-gram LM {NEEDS_BEAM.replace('need', 'needs', 1)} re-rank")
-    if greedy and hotwords_file:
-        raise ValueError(f"hotwords {NEEDS_BEAM} bias")
+    search = "greedy_batch" if beam_size is None or int(beam_size) <= 1 else fusion.ESPNET.decoding
+    for decoding in (None, search):          # every value is looked at before the search is: a bad score is told before an LM is refused
+        fusion.check_lm_keywords(fusion.ESPNET, decoding, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+        fusion.check_hotword_keywords(fusion.ESPNET, decoding, hotwords_file, hotwords_score)
 
 
 def lm_pieces(token_list, blank_id):
@@ -115,19 +103,6 @@ def lm_pieces(token_list, blank_id):
     entry, `<s>` its start state, and the search appends none of the three to a hypothesis."""
     special = {"<unk>", "<sos/eos>"}
     return [None if (i == blank_id or p in special) else p for i, p in enumerate(token_list)]
-
-
-def model_lm(cfg, token_list, ngram_lm_model, ngram_lm_tokens="pieces"):
-    """`ngram_lm_model` (a path to ARPA text, `.gz` allowed, or an NgramLm) -> the NgramLm a model with configuration `cfg` and
-    `token_list` decodes with; the table's n_logits must be the model's.  A KenLM binary is refused by the reader."""
-    if isinstance(ngram_lm_model, ngram.NgramLm):
-        if ngram_lm_model.n_logits != cfg.n_logits:
-            raise ValueError(f"the n-gram LM was built for {ngram_lm_model.n_logits} logits, the model has {cfg.n_logits}")
-        return ngram_lm_model
-    if ngram_lm_tokens not in NGRAM_TOKEN_MODES:
-        raise ValueError(f"ngram_lm_tokens must be one of {NGRAM_TOKEN_MODES}, not {ngram_lm_tokens!r} ('pieces' = the symbols of token_list)")
-    pieces = lm_pieces(token_list, cfg.blank_id) if ngram_lm_tokens == "pieces" else None
-    return ngram.load(ngram_lm_model, cfg.vocab_size, cfg.blank_id, ngram_lm_tokens, pieces, cfg.n_logits)
 
 
 def encode_phrases(phrases, token_list, blank_id, hotwords_score=k2_hotwords.DEFAULT_SCORE):
@@ -142,7 +117,8 @@ def encode_phrases(phrases, token_list, blank_id, hotwords_score=k2_hotwords.DEF
     return k2_hotwords.encode(phrases, tokens, blank_id, unk_id, hotwords_score)
 
 
-class EspnetModel:
+class EspnetModel(fusion.ForwardedOptions):
+    rule, lm_vocabulary = fusion.ESPNET, "token_list"
     hotwords = None                 # the model's HotwordGraph (None = no hotwords)
     hotwords_score = k2_hotwords.DEFAULT_SCORE
 
@@ -184,8 +160,8 @@ class EspnetModel:
         if self.hotwords is not None:
             self.am.hotword_set((self.hotwords,))         # checked (rs_hotwords_check) and uploaded once, at load
         self.ngram_lm_alpha = ngram_lm_alpha
-        if has_lm(ngram_lm_model):
-            self.ngram_lm = model_lm(cfg, self.token_list, ngram_lm_model, ngram_lm_tokens)
+        if fusion.given(ngram_lm_model):
+            self.ngram_lm = fusion.model_lm(fusion.ESPNET, cfg, self.token_list, ngram_lm_model, ngram_lm_tokens)
 
     # ---- hotwords and the n-gram LM ------------------------------------------------------------------------------------
     def hotword_graph(self, hotwords, hotwords_file=""):
@@ -196,65 +172,21 @@ class EspnetModel:
         else:
             phrases = (k2_hotwords.read_hotwords_file(hotwords_file) if hotwords_file else []) + k2_hotwords.parse_hotwords(hotwords)
             graph = k2_hotwords.build_graph(encode_phrases(phrases, self.token_list, self.cfg.blank_id, self.hotwords_score))
-        if graph is not None and self.cfg.decoding != "beam":
-            raise ValueError(f"hotwords {NEEDS_BEAM} bias")
-        return graph
+        return fusion.check_graph(fusion.ESPNET, self.cfg, graph)
 
     def call_graphs(self, hotwords, n):
         """the `hotwords=` of a call over n windows -> one HotwordGraph or None per window, or None when no window has one.  None =
         the model's graph for every window; a string (phrases separated by `/`) or a HotwordGraph = that one for every window,
         INSTEAD OF the model's; a list = one entry per window, each a string, a list of phrases, a HotwordGraph or None (= the
         model's)."""
-        if hotwords is None:
-            graphs = [self.hotwords] * n
-        elif isinstance(hotwords, (str, k2_hotwords.HotwordGraph)):
-            graphs = [self.hotword_graph(hotwords)] * n
-        else:
-            if len(hotwords) != n:
-                raise ValueError(f"hotwords: {len(hotwords)} entries for {n} windows (a list has one entry per window; one spec for all is a string)")
-            made = {}
-            graphs = []
-            for h in hotwords:
-                if h is None:
-                    graphs.append(self.hotwords)
-                    continue
-                key = h if isinstance(h, str) else id(h)
-                if key not in made:
-                    made[key] = self.hotword_graph(h)
-                graphs.append(made[key])
-        return graphs if any(g is not None for g in graphs) else None
+        if isinstance(hotwords, k2_hotwords.HotwordGraph):
+            hotwords = [hotwords] * n
+        return fusion.per_item(fusion.ESPNET, hotwords, n, self.hotwords, self.hotword_graph, "window")
 
     def call_lm(self, ngram_lm_alpha):
         """the `ngram_lm_alpha=` of a call -> what AsrModel.stage takes: None = the model's LM at the model's weight, else (NgramLm or
         None, alpha); 0 = this call without the LM; a value with no LM loaded raises ValueError"""
-        if ngram_lm_alpha is None:
-            return None
-        alpha = ngram.check_alpha(ngram_lm_alpha)
-        if self.ngram_lm is None and alpha > 0:
-            raise ValueError("ngram_lm_alpha given, but the model has no n-gram LM (load_model(ngram_lm_model=...))")
-        return self.ngram_lm, alpha
-
-    # the model's n-gram LM (an NgramLm, None = no fusion) and its weight: the runtime model's, settable
-    @property
-    def ngram_lm(self):
-        return self.am.ngram_lm
-
-    @ngram_lm.setter
-    def ngram_lm(self, lm):
-        if lm is not None:
-            if self.cfg.decoding != "beam":
-                raise ValueError(f"an n-gram LM {NEEDS_BEAM.replace('need', 'needs', 1)} re-rank")
-            lm = model_lm(self.cfg, self.token_list, lm)
-            self.am.ngram_set(lm)                         # checked (rs_ngram_check) and uploaded once, found again by NgramLm.key
-        self.am.ngram_lm = lm
-
-    @property
-    def ngram_lm_alpha(self):
-        return self.am.ngram_lm_alpha
-
-    @ngram_lm_alpha.setter
-    def ngram_lm_alpha(self, alpha):
-        self.am.ngram_lm_alpha = ngram.check_alpha(alpha)
+        return None if ngram_lm_alpha is None else (self.ngram_lm, fusion.given_alpha(self, ngram_lm_alpha))
 
     # ---- the reference's call forms -------------------------------------------------------------------------------
     def __call__(self, speech, hotwords=None, ngram_lm_alpha=None):
@@ -289,10 +221,6 @@ class EspnetModel:
             out.append((self.tokens2text(tokens), tokens, ids, _NBestHypothesis(ids, score, norm, lp)))
         return out
 
-    @property
-    def nbest(self):
-        return self.am.nbest
-
     def recognize_batch(self, waves, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm_alpha=None):
         """padded like the reference pads each window (np.pad(samples, PADDING), transcribe.py:69) -> [text].
         `isolate_overflow`: see `_search`.  `nbest=N`: per window the list of `model(speech)` instead — N tuples (text, tokens, ids,
@@ -313,14 +241,6 @@ class EspnetModel:
         if res.token_logprobs is None:
             raise ValueError("recognize_batch_scored needs token_scores=True")
         return [self.ids_to_text(ids) for ids in res.ids], list(zip(res.ids, res.token_logprobs))
-
-    @property
-    def token_scores(self):
-        return self.am.token_scores
-
-    @token_scores.setter
-    def token_scores(self, value):
-        self.am.token_scores = bool(value)
 
     def _search(self, waves, max_batch=256, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm=None):
         """the transducer search over a batch of (padded) windows.  Upstream's default beam search has no bound on the
@@ -395,19 +315,6 @@ class EspnetModel:
             if out.nbest is not None:                     # (the greedy fall-back ran without lists: its one hypothesis each)
                 out.nbest += res.nbest if res.nbest is not None else [[(ids, fr, float("nan"), float("nan"))] for ids, fr in zip(res.ids, res.frames)]
         return out
-
-    # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option
-    @property
-    def resample(self):
-        return self.am.resample
-
-    @resample.setter
-    def resample(self, value):
-        from ...runtime.resample import check_mode
-        self.am.resample = check_mode(value)
-
-    def resample_batch(self, waveforms, rates):
-        return self.am.resample_batch(waveforms, rates)
 
     def recognize(self, samples):
         return self.recognize_batch([samples])[0]

@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import torch
 
+from ...runtime import fusion
 from ...runtime.resample import norm_batch
 from .audio import norm_audio, SAMPLERATE
 from .interface import AudioData, TranscribeConfig, TranscribeResult, Segment, make_result
@@ -183,8 +184,7 @@ def per_recording(hotwords, n):
         return None
     if isinstance(hotwords, str) or not hasattr(hotwords, "__len__"):
         return [hotwords] * n
-    if len(hotwords) != n:
-        raise ValueError(f"hotwords: {len(hotwords)} entries for {n} recordings (a list has one entry per recording; one spec for all is a string)")
+    fusion.check_entries(fusion.ESPNET, hotwords, n, "recording")
     return list(hotwords)
 
 

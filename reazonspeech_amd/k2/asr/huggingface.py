@@ -130,10 +130,9 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     from .model import search_config
     search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
                   ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, nbest)
-    if isinstance(ngram_lm_model, (str, os.PathLike)) and ngram_lm_model and not os.path.isfile(ngram_lm_model):
-        raise FileNotFoundError(f"ngram_lm_model {str(ngram_lm_model)!r} does not exist")
-    if hotwords_file and not os.path.isfile(hotwords_file):
-        raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
+    from ...runtime import fusion
+    fusion.check_file("ngram_lm_model", ngram_lm_model)
+    fusion.check_file("hotwords_file", hotwords_file)
     search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample,
                   hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords, token_scores=token_scores,
                   ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens, nbest=nbest)

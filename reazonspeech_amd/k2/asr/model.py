@@ -12,7 +12,7 @@ import re
 
 import numpy as np
 
-from ...runtime import k2_hotwords, ngram_lm as ngram
+from ...runtime import fusion, k2_hotwords
 from ...runtime.model import AsrModel
 
 _BYTE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
@@ -76,20 +76,17 @@ def search_config(cfg, decoding_method="greedy_search", max_active_paths=4, blan
     """`cfg` with the search sherpa_onnx.OfflineRecognizer.from_transducer's keywords ask for (its names and defaults);
     ValueError for anything it does not have or this package does not run.  Needs no GPU.  The hotwords keywords are checked
     here (upstream refuses them with greedy_search too); the graph itself is the model's, not the configuration's.  So are the
-    n-gram LM keywords (runtime/ngram_lm.py: k2_check_keywords): an LM with greedy_search raises.  `nbest` (this project's
+    n-gram LM keywords (runtime/fusion.py: check_lm_keywords): an LM with greedy_search raises.  `nbest` (this project's
     addition, 0 = off) must be an integer in 0..8, at most max_active_paths, and above 1 needs the modified beam search."""
     if not (isinstance(nbest, int) and not isinstance(nbest, bool) and 0 <= nbest <= 8):
         raise ValueError(f"nbest must be an integer in 0..8, not {nbest!r}")
     if nbest > 1 and decoding_method == "greedy_search":
         raise ValueError(f"nbest={nbest} needs decoding_method='modified_beam_search' (greedy_search keeps one hypothesis)")
-    has_hotwords = bool(hotwords_file) or (hotwords is not None and len(hotwords) > 0)
-    if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
-        raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
-    if has_hotwords and decoding_method == "greedy_search":
-        raise ValueError("hotwords need decoding_method='modified_beam_search' (greedy_search has no hypotheses to bias)")
+    # (a method this package does not have is refused in its turn, below: hotwords are refused with the greedy search only)
+    fusion.check_hotword_keywords(fusion.K2, decoding_method if decoding_method in DECODING_METHODS else None, hotwords_file, hotwords_score, hotwords)
     if decoding_method not in DECODING_METHODS:
         raise ValueError(f"decoding_method must be 'greedy_search' or 'modified_beam_search', not {decoding_method!r}")
-    ngram.k2_check_keywords(decoding_method, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+    fusion.check_lm_keywords(fusion.K2, decoding_method, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
     if not float(blank_penalty) >= 0.0:
         raise ValueError(f"blank_penalty must be >= 0, not {blank_penalty!r}")
     if decoding_method == "greedy_search":
@@ -110,7 +107,9 @@ def stream_graphs(model_graph, streams):
     return graphs if any(g is not None for g in graphs) else None
 
 
-class K2Model:
+class K2Model(fusion.ForwardedOptions):
+    rule, lm_vocabulary = fusion.K2, "tokens"
+
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
                  decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host",
                  hotwords_file="", hotwords_score=1.5, hotwords=None, token_scores=False, ngram_lm_model=None, ngram_lm_alpha=0.0,
@@ -161,8 +160,8 @@ class K2Model:
         if self.hotwords is not None:
             self.am.hotword_set((self.hotwords,))         # checked and uploaded once, at load
         self.ngram_lm_alpha = ngram_lm_alpha
-        if ngram.k2_has_lm(ngram_lm_model):
-            self.ngram_lm = ngram.k2_model_lm(cfg, self.tokens, ngram_lm_model, ngram_lm_tokens)
+        if fusion.given(ngram_lm_model):
+            self.ngram_lm = fusion.model_lm(fusion.K2, cfg, self.tokens, ngram_lm_model, ngram_lm_tokens)
 
     def hotword_graph(self, hotwords, hotwords_file=""):
         """a hotwords argument (a string of phrases separated by `/`, or a list; each phrase with an optional ` :score`) -> its
@@ -170,57 +169,10 @@ class K2Model:
         if isinstance(hotwords, k2_hotwords.HotwordGraph):
             return hotwords
         graph = k2_hotwords.make_graph(hotwords, self.tokens, self.cfg.blank_id, self.cfg.unk_id, self.hotwords_score, hotwords_file)
-        if graph is not None and self.cfg.decoding != "modified_beam_search":
-            raise ValueError("hotwords need decoding_method='modified_beam_search' (greedy_search has no hypotheses to bias)")
-        return graph
-
-    # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device"): the runtime model's option
-    @property
-    def resample(self):
-        return self.am.resample
-
-    @resample.setter
-    def resample(self, value):
-        from ...runtime.resample import check_mode
-        self.am.resample = check_mode(value)
-
-    def resample_batch(self, waveforms, rates):
-        return self.am.resample_batch(waveforms, rates)
-
-    @property
-    def token_scores(self):
-        return self.am.token_scores
-
-    @token_scores.setter
-    def token_scores(self, value):
-        self.am.token_scores = bool(value)
-
-    # the model's n-gram LM (an NgramLm, None = no fusion) and its weight: the runtime model's, settable
-    @property
-    def ngram_lm(self):
-        return self.am.ngram_lm
-
-    @ngram_lm.setter
-    def ngram_lm(self, lm):
-        if lm is not None:
-            lm = ngram.k2_model_lm(self.cfg, self.tokens, lm)
-            self.am.ngram_set(lm)                         # checked (rs_ngram_check) and uploaded once, found again by NgramLm.key
-        self.am.ngram_lm = lm
-
-    @property
-    def ngram_lm_alpha(self):
-        return self.am.ngram_lm_alpha
-
-    @ngram_lm_alpha.setter
-    def ngram_lm_alpha(self, alpha):
-        self.am.ngram_lm_alpha = ngram.check_alpha(alpha)
+        return fusion.check_graph(fusion.K2, self.cfg, graph)
 
     # entries of `stream.result.nbest` (0 = off): the runtime model's option, settable
-    @property
-    def nbest(self):
-        return self.am.nbest
-
-    @nbest.setter
+    @fusion.ForwardedOptions.nbest.setter
     def nbest(self, n):
         self.am.nbest = self.am.nbest_plan(n)
 
@@ -235,7 +187,7 @@ class K2Model:
 
     def decode_streams(self, streams, ngram_lm_alpha=None):
         """ngram_lm_alpha: the weight of the model's n-gram LM in this call (None = `model.ngram_lm_alpha`, 0 = without the LM)"""
-        lm = None if ngram_lm_alpha is None else ngram.k2_call_alpha(self, ngram_lm_alpha)
+        lm = None if ngram_lm_alpha is None else fusion.call_alpha(fusion.K2, self, ngram_lm_alpha)
         for st in streams:
             if st.sample_rate != self.cfg.sample_rate:
                 raise ValueError(f"sample rate {st.sample_rate}: the model expects {self.cfg.sample_rate} Hz (sherpa-onnx resamples; resample with norm_audio first)")

@@ -2,6 +2,7 @@
 silence on both sides, warn above TOO_LONG_SECONDS, decode one stream, pair tokens with timestamps."""
 import warnings
 
+from ...runtime import fusion
 from ...runtime.resample import norm_batch
 from .interface import AudioData, TranscribeConfig, TranscribeResult, ScoredTranscribeResult, NBestTranscribeResult, Subword, mean_confidence
 from .audio import pad_audio, norm_audio, SAMPLERATE
@@ -59,24 +60,9 @@ def _result(stream):
 
 def _streams(model, audios, hotwords):
     """one stream per prepared audio; `hotwords`: None, one specification (a string) for all, or a list with one entry per audio"""
-    if hotwords is None or isinstance(hotwords, str):
-        graph = model.hotword_graph(hotwords) if hotwords else None        # built once for the whole list
-        per_audio = [graph] * len(audios)
-    else:
-        if len(hotwords) != len(audios):
-            raise ValueError(f"hotwords: {len(hotwords)} entries for {len(audios)} audios (a list is one entry per audio; pass a string "
-                             "of phrases separated by '/' to use one specification for all)")
-        cache = {}
-        per_audio = []
-        for h in hotwords:
-            key = h if isinstance(h, str) else None
-            if h is None or (key is not None and key in cache):
-                per_audio.append(cache.get(key) if h is not None else None)
-                continue
-            g = model.hotword_graph(h)
-            if key is not None:
-                cache[key] = g
-            per_audio.append(g)
+    # (no graph of its own leaves a stream at None: the model's is put in at decode time, `stream_graphs`)
+    make = lambda spec: model.hotword_graph(spec)         # (asked of the model only when a call has hotwords: a bare recogniser has none)
+    per_audio = fusion.per_item(fusion.K2, hotwords, len(audios), None, make, "audio") or [None] * len(audios)
     streams = []
     for a, g in zip(audios, per_audio):
         st = model.create_stream() if g is None else model.create_stream(hotwords=g)     # (no hotwords: the reference's call)

@@ -16,6 +16,7 @@ import torch
 from .interface import TranscribeConfig, Hypothesis
 from .decode import decode_hypothesis, PAD_SECONDS
 from .audio import norm_audio
+from ...runtime import fusion, nemo_hotwords
 from ...runtime.resample import norm_batch
 
 #: where a real checkpoint is looked for; the reference downloads
@@ -133,15 +134,11 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     from ...runtime.resample import check_mode
 
     check_mode(resample)
-    from ...runtime import nemo_hotwords
-    if hotwords_file and not os.path.isfile(hotwords_file):
-        raise FileNotFoundError(f"hotwords_file {hotwords_file!r} does not exist")
+    fusion.check_file("hotwords_file", hotwords_file)
     if decoding is not None:               # (a checkpoint's own strategy is only known once it is read: checked again below)
-        nemo_hotwords.check_keywords(str(decoding), hotwords_file, hotwords_score, hotwords)
-    from ...runtime import ngram_lm
-    has_lm = ngram_lm.check_keywords(None if decoding is None else str(decoding), ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
-    if has_lm and isinstance(ngram_lm_model, (str, os.PathLike)) and not os.path.isfile(ngram_lm_model):
-        raise FileNotFoundError(f"ngram_lm_model {str(ngram_lm_model)!r} does not exist")
+        fusion.check_hotword_keywords(fusion.NEMO, str(decoding), hotwords_file, hotwords_score, hotwords)
+    has_lm = fusion.check_lm_keywords(fusion.NEMO, None if decoding is None else str(decoding), ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)
+    fusion.check_file("ngram_lm_model", ngram_lm_model)
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if str(device).startswith("cpu"):
@@ -175,19 +172,32 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         cfg = cfg.with_(beam_size=int(beam_size))
     cfg.validate()
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
-    has_hotwords = nemo_hotwords.check_keywords(cfg.decoding, hotwords_file, hotwords_score, hotwords)
-    ngram_lm.check_keywords(cfg.decoding, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)      # the checkpoint's own strategy is known now
+    has_hotwords = fusion.check_hotword_keywords(fusion.NEMO, cfg.decoding, hotwords_file, hotwords_score, hotwords)
+    fusion.check_lm_keywords(fusion.NEMO, cfg.decoding, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)      # the checkpoint's own strategy is known now
     model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, nbest=nbest, **kw)
     model.hotwords_score = float(hotwords_score)
     if has_hotwords:
-        model.hotwords = nemo_hotwords.model_graph(model, hotwords, hotwords_file)     # the model's graph (None = nothing left to bias)
+        model.hotwords = _model_graph(model, hotwords, hotwords_file)                  # the model's graph (None = nothing left to bias)
         if model.hotwords is not None:
             model.hotword_set((model.hotwords,))                                       # checked and uploaded once, at load
     model.ngram_lm_alpha = float(ngram_lm_alpha)
     if has_lm:
-        model.ngram_lm = ngram_lm.model_lm(model, ngram_lm_model, ngram_lm_tokens)
+        model.ngram_lm = fusion.model_lm(fusion.NEMO, cfg, tokenizer, ngram_lm_model, ngram_lm_tokens)
         model.ngram_set(model.ngram_lm)                                                # checked and uploaded once, at load
     return model
+
+
+def _model_graph(model, spec, hotwords_file=""):
+    """`spec` -> the HotwordGraph `model` (an AsrModel of the NeMo family) decodes it with; None for nothing"""
+    cfg = model.cfg
+    graph = nemo_hotwords.make_graph(spec, model.tokenizer, cfg.blank_id, cfg.vocab_size, model.hotwords_score, hotwords_file)
+    return fusion.check_graph(fusion.NEMO, cfg, graph)
+
+
+def _call_graphs(model, hotwords, n):
+    """the `hotwords` argument of a call over n audios -> None (no utterance has a graph) or one HotwordGraph / None per audio
+    (fusion.per_item: None / "" = the model's graph)"""
+    return fusion.per_item(fusion.NEMO, hotwords, n, getattr(model, "hotwords", None), lambda spec: _model_graph(model, spec), "audio")
 
 
 def transcribe_batch(model, audios, config=None, distributed=False, hotwords=None):
@@ -215,9 +225,7 @@ def transcribe_batch(model, audios, config=None, distributed=False, hotwords=Non
     """
     if config is None:
         config = TranscribeConfig()
-    from ...runtime import nemo_hotwords
-    graphs = nemo_hotwords.per_audio(model, hotwords, len(audios))
-    return _transcribe_graphs(model, audios, config, distributed, graphs)
+    return _transcribe_graphs(model, audios, config, distributed, _call_graphs(model, hotwords, len(audios)))
 
 
 def _nbest_result(ret, score, norm):
@@ -230,8 +238,7 @@ def _nbest_result(ret, score, norm):
 def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alpha=None, nbest=None):
     """`transcribe_batch` with the hotwords resolved: `graphs` = None, or one HotwordGraph / None per audio; `ngram_lm_alpha`: the
     n-gram LM's weight in this call (None = the model's value, 0 = without the LM; a value with no LM loaded raises ValueError)"""
-    from ...runtime import ngram_lm
-    lm = ngram_lm.call_alpha(model, ngram_lm_alpha)
+    lm = fusion.call_alpha(fusion.NEMO, model, ngram_lm_alpha)
     # 16 kHz mono float32 waveforms (transcribe.py:44 minus the padding, which the kernel applies)
     waves = [np.ascontiguousarray(w, dtype=np.float32) for w in norm_batch(model, audios, norm_audio)]
     if config.verbose:
@@ -277,15 +284,10 @@ def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alph
         raise ValueError("token_scores is on: the distributed path does not gather token log-probabilities (transcribe_batch(distributed=False) "
                          "on each rank, or load the model without token_scores)")
     if distributed:
-        to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves, hotwords=graphs, **_lm_kw(lm)))
+        to_results(list(range(len(waves))), model.transcribe_waveforms_sharded(waves, hotwords=graphs, ngram_lm=lm))
     else:
-        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs, nbest=nbest, **_lm_kw(lm))
+        model.transcribe_waveforms(waves, on_batch=to_results, hotwords=graphs, nbest=nbest, ngram_lm=lm)
     return results
-
-
-def _lm_kw(lm):
-    """the `ngram_lm` keyword of the runtime for a resolved (NgramLm or None, alpha): (None, 0) runs the call without an LM"""
-    return {"ngram_lm": lm}
 
 
 def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nbest=None):
@@ -308,6 +310,5 @@ def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nb
     """
     if config is None:
         config = TranscribeConfig()
-    from ...runtime import nemo_hotwords
-    graphs = nemo_hotwords.per_audio(model, hotwords, 1, single=True)
+    graphs = _call_graphs(model, None if hotwords is None else [hotwords], 1)     # the argument is ONE audio's entry, whatever its type
     return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha, nbest)[0]

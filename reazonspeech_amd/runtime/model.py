@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, fusion
 from .config import ModelConfig
 from .weights import prepare_weights, DEFAULT_POS_CAP
 
@@ -780,12 +780,8 @@ class AsrModel:
             return None
         if not (np.isfinite(alpha) and alpha > 0):
             raise ValueError(f"ngram_lm_alpha must be a finite number >= 0, not {alpha!r}")
-        if self.cfg.decoding in ("modified_beam_search", "beam"):  # (the k2 and espnet packages; their greedy searches are refused in their own words)
-            return self.ngram_set(lm), float(alpha)
-        if getattr(self.cfg, "family", None) == "k2":
-            raise ValueError(f"an n-gram LM needs decoding_method='modified_beam_search', not {self.cfg.decoding!r}")
-        if self.cfg.decoding != "alsd":
-            raise ValueError(f"an n-gram LM needs decoding='alsd', not {self.cfg.decoding!r}")
+        if self.cfg.decoding not in fusion.FUSED:          # (the packages refuse their greedy searches first, in their own words)
+            raise ValueError(fusion.rule_of(self.cfg).plan_lm_refusal.format(repr(self.cfg.decoding)))
         return self.ngram_set(lm), float(alpha)
 
     def graph_plan(self, hotwords, n):
@@ -796,10 +792,8 @@ class AsrModel:
             raise ValueError(f"hotwords: {len(hotwords)} entries for {n} utterances")
         if all(g is None for g in hotwords):
             return None
-        if self.cfg.decoding not in ("modified_beam_search", "alsd", "beam"):      # greedy has no hypotheses to bias
-            if getattr(self.cfg, "family", "") == "k2":
-                raise ValueError("hotwords need decoding_method='modified_beam_search'")
-            raise ValueError(f"hotwords need decoding='alsd', not {self.cfg.decoding!r}")
+        if self.cfg.decoding not in fusion.FUSED:          # greedy has no hypotheses to bias
+            raise ValueError(fusion.rule_of(self.cfg).plan_hotwords_refusal.format(repr(self.cfg.decoding)))
         distinct, index = [], {}
         for g in hotwords:
             if g is not None and g.key not in index:

@@ -41,51 +41,3 @@ def make_graph(spec, tokenizer, blank_id, vocab_size, hotwords_score=DEFAULT_SCO
         return spec
     phrases = (read_hotwords_file(hotwords_file) if hotwords_file else []) + parse_hotwords(spec)
     return build_graph(encode(phrases, tokenizer, blank_id, vocab_size, hotwords_score))
-
-
-def check_keywords(decoding, hotwords_file="", hotwords_score=DEFAULT_SCORE, hotwords=None):
-    """the hotword keywords of `load_model`, checked before anything is loaded: ValueError for a score that is no finite number and
-    for non-empty hotwords with a decoding other than "alsd" (greedy has no hypotheses to bias; "beam" has no hotword form)"""
-    if not (isinstance(hotwords_score, (int, float)) and not isinstance(hotwords_score, bool) and np.isfinite(hotwords_score)):
-        raise ValueError(f"hotwords_score must be a finite number, not {hotwords_score!r}")
-    has = bool(hotwords_file) or isinstance(hotwords, HotwordGraph) or (hotwords is not None and len(hotwords) > 0)
-    if has and decoding != "alsd":
-        raise ValueError(f"hotwords need decoding='alsd', not {decoding!r}")
-    return has
-
-
-def model_graph(model, spec, hotwords_file=""):
-    """`spec` -> the HotwordGraph `model` (an AsrModel of the NeMo family) decodes it with; None for nothing"""
-    cfg = model.cfg
-    graph = make_graph(spec, model.tokenizer, cfg.blank_id, cfg.vocab_size, model.hotwords_score, hotwords_file)
-    if graph is not None and cfg.decoding != "alsd":
-        raise ValueError(f"hotwords need decoding='alsd', not {cfg.decoding!r}")
-    return graph
-
-
-def per_audio(model, hotwords, n, single=False):
-    """the `hotwords` argument of transcribe / transcribe_batch -> None (no utterance has a graph) or one HotwordGraph / None per
-    audio.  None = the model's graph; a string = one specification for all audios; a list = one entry per audio (None / "" = the
-    model's graph, a string, a list of phrases or a HotwordGraph INSTEAD OF the model's).  `single`: the argument is ONE
-    audio's entry, whatever its type (transcribe)."""
-    own = getattr(model, "hotwords", None)
-    if single and hotwords is not None:
-        hotwords = [hotwords]
-    if hotwords is None or isinstance(hotwords, str):
-        g = model_graph(model, hotwords) if hotwords else own
-        graphs = [g] * n
-    else:
-        if len(hotwords) != n:
-            raise ValueError(f"hotwords: {len(hotwords)} entries for {n} audios (a list is one entry per audio; pass a string of phrases "
-                             "separated by '/' to use one specification for all)")
-        cache, graphs = {}, []
-        for h in hotwords:
-            if h is None or (isinstance(h, str) and not h):
-                graphs.append(own)
-            elif isinstance(h, str):
-                if h not in cache:
-                    cache[h] = model_graph(model, h)
-                graphs.append(cache[h])
-            else:
-                graphs.append(model_graph(model, h))
-    return None if all(g is None for g in graphs) else graphs

@@ -34,9 +34,10 @@ KENLM_MAGIC = b"mmap lm http://kheafield.com/code format version"
 LN10 = math.log(10.0)
 
 
-def check_tokens(ngram_lm_tokens):
-    if ngram_lm_tokens not in TOKEN_MODES:
-        raise ValueError(f"ngram_lm_tokens must be one of {TOKEN_MODES}, not {ngram_lm_tokens!r}")
+def check_tokens(ngram_lm_tokens, modes=TOKEN_MODES, note=""):
+    """`modes`: the encodings a caller reads (a package reads fewer than this reader: runtime/fusion.py), `note`: what it adds"""
+    if ngram_lm_tokens not in modes:
+        raise ValueError(f"ngram_lm_tokens must be one of {modes}, not {ngram_lm_tokens!r}{note}")
     return ngram_lm_tokens
 
 
@@ -266,115 +267,8 @@ def load(path, vocab_size, blank_id, ngram_lm_tokens="nemo", pieces=None, n_logi
     return build(read_arpa(path, vocab_size, blank_id, ngram_lm_tokens, pieces), vocab_size, blank_id, n_logits)
 
 
-# ---- the keywords of the nemo package -------------------------------------------------------------------------------------------
+# ---- the weight (the keywords themselves are checked in runtime/fusion.py) ----------------------------------------------------------
 def check_alpha(alpha, name="ngram_lm_alpha"):
     if not (isinstance(alpha, (int, float, np.floating, np.integer)) and not isinstance(alpha, bool) and math.isfinite(alpha) and alpha >= 0):
         raise ValueError(f"{name} must be a finite number >= 0, not {alpha!r}")
     return float(alpha)
-
-
-def check_keywords(decoding, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="nemo"):
-    """the LM keywords of `load_model`, checked before anything is loaded -> True when there is an LM.  ValueError for an alpha that
-    is no finite number >= 0, an unknown token encoding, and an LM with a decoding other than "alsd" (the only search with a
-    "rank the adjusted score" slot); `decoding` None = not known yet (a checkpoint's own strategy: checked again later)."""
-    check_alpha(ngram_lm_alpha)
-    check_tokens(ngram_lm_tokens)
-    has = ngram_lm_model is not None and not (isinstance(ngram_lm_model, str) and not ngram_lm_model)
-    if has and decoding is not None and decoding != "alsd":
-        raise ValueError(f"an n-gram LM needs decoding='alsd', not {decoding!r}")
-    return has
-
-
-def model_lm(model, ngram_lm_model, ngram_lm_tokens="nemo"):
-    """`ngram_lm_model` (a path or an NgramLm) -> the NgramLm `model` decodes with"""
-    cfg = model.cfg
-    if cfg.decoding != "alsd":
-        raise ValueError(f"an n-gram LM needs decoding='alsd', not {cfg.decoding!r}")
-    if isinstance(ngram_lm_model, NgramLm):
-        if ngram_lm_model.n_logits != cfg.n_logits:
-            raise ValueError(f"the n-gram LM was built for {ngram_lm_model.n_logits} logits, the model has {cfg.n_logits}")
-        return ngram_lm_model
-    pieces = None
-    if ngram_lm_tokens == "pieces":
-        pieces = model.tokenizer.ids_to_tokens(range(cfg.vocab_size))
-    return load(ngram_lm_model, cfg.vocab_size, cfg.blank_id, ngram_lm_tokens, pieces, cfg.n_logits)
-
-
-def call_alpha(model, ngram_lm_alpha):
-    """the `ngram_lm_alpha` of transcribe / transcribe_batch -> (NgramLm or None, alpha) of this call: None = the model's value,
-    0 = this call without the LM; a value with no LM loaded raises ValueError"""
-    lm = getattr(model, "ngram_lm", None)
-    if ngram_lm_alpha is None:
-        alpha = check_alpha(getattr(model, "ngram_lm_alpha", 0.0), "model.ngram_lm_alpha")
-    else:
-        alpha = check_alpha(ngram_lm_alpha)
-        if lm is None and alpha > 0:
-            raise ValueError("ngram_lm_alpha given, but the model has no n-gram LM (load_model(ngram_lm_model=...))")
-    if lm is None or alpha == 0.0:
-        return None, 0.0
-    if model.cfg.decoding != "alsd":
-        raise ValueError(f"an n-gram LM needs decoding='alsd', not {model.cfg.decoding!r}")
-    return lm, alpha
-
-
-# ---- the keywords of the k2 package -----------------------------------------------------------------------------------------------
-K2_TOKEN_MODES = ("pieces", "ids")
-K2_NEEDS_MBS = "an n-gram LM needs decoding_method='modified_beam_search'"
-
-
-def k2_check_tokens(ngram_lm_tokens):
-    if ngram_lm_tokens == "nemo":
-        raise ValueError("ngram_lm_tokens='nemo' is the NeMo package's word encoding; the k2 package reads 'pieces' (the symbols of tokens.txt) or 'ids'")
-    if ngram_lm_tokens not in K2_TOKEN_MODES:
-        raise ValueError(f"ngram_lm_tokens must be one of {K2_TOKEN_MODES}, not {ngram_lm_tokens!r}")
-    return ngram_lm_tokens
-
-
-def k2_has_lm(ngram_lm_model):
-    return ngram_lm_model is not None and not (isinstance(ngram_lm_model, str) and not ngram_lm_model)
-
-
-def k2_check_keywords(decoding_method, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
-    """the LM keywords of the k2 `load_model` / `K2Model`, checked before anything is loaded -> True when there is an LM.  ValueError
-    for an alpha that is no finite number >= 0, the "nemo" or an unknown token encoding, and an LM with greedy_search (it has no
-    hypotheses to re-rank)."""
-    check_alpha(ngram_lm_alpha)
-    k2_check_tokens(ngram_lm_tokens)
-    has = k2_has_lm(ngram_lm_model)
-    if has and decoding_method != "modified_beam_search":
-        raise ValueError(f"{K2_NEEDS_MBS}, not {decoding_method!r}")
-    return has
-
-
-def k2_model_lm(cfg, tokens, ngram_lm_model, ngram_lm_tokens="pieces"):
-    """`ngram_lm_model` (a path or an NgramLm) -> the NgramLm a k2 model with configuration `cfg` and tokens.txt symbols `tokens`
-    decodes with; the table's n_logits must be the model's"""
-    if cfg.decoding != "modified_beam_search":
-        raise ValueError(f"{K2_NEEDS_MBS}, not {cfg.decoding!r}")
-    if isinstance(ngram_lm_model, NgramLm):
-        if ngram_lm_model.n_logits != cfg.n_logits:
-            raise ValueError(f"the n-gram LM was built for {ngram_lm_model.n_logits} logits, the model has {cfg.n_logits}")
-        return ngram_lm_model
-    k2_check_tokens(ngram_lm_tokens)
-    pieces = None
-    if ngram_lm_tokens == "pieces":
-        # the file's `<unk>` is the model's unknown-word entry, never a token of an n-gram: tokens.txt's own <unk> symbol names no id here
-        pieces = [None if i == cfg.unk_id else p for i, p in enumerate(list(tokens)[:cfg.vocab_size])]
-    return load(ngram_lm_model, cfg.vocab_size, cfg.blank_id, ngram_lm_tokens, pieces, cfg.n_logits)
-
-
-def k2_call_alpha(model, ngram_lm_alpha):
-    """the `ngram_lm_alpha` of the k2 `transcribe` -> (NgramLm or None, alpha) of this call: None = the model's value, 0 = this call
-    without the LM; a value with no LM loaded raises ValueError"""
-    lm = getattr(model, "ngram_lm", None)
-    if ngram_lm_alpha is None:
-        alpha = check_alpha(getattr(model, "ngram_lm_alpha", 0.0), "model.ngram_lm_alpha")
-    else:
-        alpha = check_alpha(ngram_lm_alpha)
-        if lm is None and alpha > 0:
-            raise ValueError("ngram_lm_alpha given, but the model has no n-gram LM (load_model(ngram_lm_model=...))")
-    if lm is None or alpha == 0.0:
-        return None, 0.0
-    if model.cfg.decoding != "modified_beam_search":
-        raise ValueError(f"{K2_NEEDS_MBS}, not {model.cfg.decoding!r}")
-    return lm, alpha

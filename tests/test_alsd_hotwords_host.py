@@ -21,7 +21,8 @@ import pytest
 import alsd_hotwords_ref as AR
 import k2_hotwords_ref as KR
 from oracle import greedy as og
-from reazonspeech_amd.runtime import capi, k2_hotwords, nemo_hotwords
+from reazonspeech_amd.nemo.asr.transcribe import _call_graphs as per_audio
+from reazonspeech_amd.runtime import capi, fusion, k2_hotwords, nemo_hotwords
 from reazonspeech_amd.runtime.config import TINY
 from reazonspeech_amd.runtime.tokenizer import SentencePieceTokenizer, SyntheticTokenizer
 from reazonspeech_amd.runtime.weights import synthetic_state_dict
@@ -268,30 +269,30 @@ def test_keyword_errors():
         load_model(device="cuda:0", config=TINY, decoding="alsd", hotwords=[(3,)], hotwords_score=float("nan"))
     with pytest.raises(FileNotFoundError):
         load_model(device="cuda:0", config=TINY, decoding="alsd", hotwords_file="/nonexistent/hotwords.txt")
-    assert nemo_hotwords.check_keywords("greedy_batch") is False and nemo_hotwords.check_keywords("alsd", hotwords=[(1,)]) is True
+    assert fusion.check_hotword_keywords(fusion.NEMO, "greedy_batch") is False and fusion.check_hotword_keywords(fusion.NEMO, "alsd", hotwords=[(1,)]) is True
 
 
 def test_per_audio_meaning():
     m = _model()
-    assert nemo_hotwords.per_audio(m, None, 3) is None and nemo_hotwords.per_audio(m, "", 3) is None
-    one = nemo_hotwords.per_audio(m, [(3, 4), (5,)], 1, single=True)            # transcribe: a list is ONE audio's phrases
+    assert per_audio(m, None, 3) is None and per_audio(m, "", 3) is None
+    one = per_audio(m, [[(3, 4), (5,)]], 1)            # transcribe: a list is ONE audio's phrases
     assert len(one) == 1 and one[0].n_phrases == 2
     tok = m.tokenizer
     text = tok.pieces[7] + tok.pieces[9]
-    allg = nemo_hotwords.per_audio(m, text, 3)
+    allg = per_audio(m, text, 3)
     assert len(allg) == 3 and allg[0] is allg[1] is allg[2] and allg[0].key == ((tok.text_to_ids(text)[0], 1.5),)
-    mixed = nemo_hotwords.per_audio(m, [None, text, [(3, 4)]], 3)
+    mixed = per_audio(m, [None, text, [(3, 4)]], 3)
     assert mixed[0] is None and mixed[1].key == allg[0].key and mixed[2].key == (((3, 4), 1.5),)
     with pytest.raises(ValueError, match="3 entries for 2 audios"):
-        nemo_hotwords.per_audio(m, [None, None, None], 2)
+        per_audio(m, [None, None, None], 2)
     own = k2_hotwords.build_graph([((1, 2), 1.5)])
     m2 = _model(own=own)
-    assert nemo_hotwords.per_audio(m2, None, 2) == [own, own]
-    assert [g.key for g in nemo_hotwords.per_audio(m2, [None, [(3,)]], 2)] == [own.key, (((3,), 1.5),)]
+    assert per_audio(m2, None, 2) == [own, own]
+    assert [g.key for g in per_audio(m2, [None, [(3,)]], 2)] == [own.key, (((3,), 1.5),)]
     with pytest.raises(ValueError, match="alsd"):
-        nemo_hotwords.per_audio(_model("greedy_batch"), [(3, 4)], 1, single=True)
+        per_audio(_model("greedy_batch"), [[(3, 4)]], 1)
     with pytest.warns(UserWarning, match="skipped"):
-        assert nemo_hotwords.per_audio(m, "q", 1) is None
+        assert per_audio(m, "q", 1) is None
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------------------

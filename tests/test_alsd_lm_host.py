@@ -23,7 +23,7 @@ import pytest
 import alsd_hotwords_ref as AR
 import k2_hotwords_ref as KR
 import ngram_lm_ref as NR
-from reazonspeech_amd.runtime import capi, ngram_lm as NL
+from reazonspeech_amd.runtime import capi, fusion, ngram_lm as NL
 from reazonspeech_amd.runtime.config import TINY
 from reazonspeech_amd.runtime.tokenizer import SyntheticTokenizer
 from reazonspeech_amd.runtime.weights import synthetic_state_dict
@@ -245,6 +245,18 @@ def _model(decoding="alsd", lm=None, alpha=0.0):
                                  hotwords_score=1.5, ngram_lm=lm, ngram_lm_alpha=alpha)
 
 
+def check_keywords(decoding, *keywords):
+    return fusion.check_lm_keywords(fusion.NEMO, decoding, *keywords)
+
+
+def model_lm(model, *keywords):
+    return fusion.model_lm(fusion.NEMO, model.cfg, model.tokenizer, *keywords)
+
+
+def call_alpha(model, ngram_lm_alpha):
+    return fusion.call_alpha(fusion.NEMO, model, ngram_lm_alpha)
+
+
 def test_keyword_errors(tmp_path):
     from reazonspeech_amd.nemo.asr import load_model, transcribe
     sig = inspect.signature(load_model).parameters
@@ -263,7 +275,7 @@ def test_keyword_errors(tmp_path):
         load_model(device="cuda:0", config=TINY, decoding="alsd", ngram_lm_model=arpa, ngram_lm_alpha=0.3, ngram_lm_tokens="words")
     with pytest.raises(FileNotFoundError, match="ngram_lm_model"):
         load_model(device="cuda:0", config=TINY, decoding="alsd", ngram_lm_model=str(tmp_path / "missing.arpa"), ngram_lm_alpha=0.3)
-    assert NL.check_keywords("greedy_batch") is False and NL.check_keywords("alsd", arpa, 0.3) is True and NL.check_keywords(None, arpa, 0.3) is True
+    assert check_keywords("greedy_batch") is False and check_keywords("alsd", arpa, 0.3) is True and check_keywords(None, arpa, 0.3) is True
 
 
 def test_model_lm_and_per_call_alpha(tmp_path):
@@ -275,25 +287,25 @@ def test_model_lm_and_per_call_alpha(tmp_path):
         if mode == "pieces" and len(set(toks[i] for i in (3, 4))) < 2:
             continue
         path = NR.write_arpa(str(tmp_path / f"{mode}.arpa"), ent, mode, toks)
-        lm = NL.model_lm(m, path, mode)
+        lm = model_lm(m, path, mode)
         assert lm.n_logits == TINY.n_logits and lm.n_nodes == 4
         keys.add(lm.key)
     assert len(keys) == 1                                       # one model, three spellings
-    assert NL.model_lm(m, lm) is lm
+    assert model_lm(m, lm) is lm
     with pytest.raises(ValueError, match="logits"):
-        NL.model_lm(m, NL.build(ent, 10, 10))
+        model_lm(m, NL.build(ent, 10, 10))
     with pytest.raises(ValueError, match="alsd"):
-        NL.model_lm(_model("greedy_batch"), lm)
+        model_lm(_model("greedy_batch"), lm)
     # None = the model's value, 0 = this call without the LM, a value with no LM loaded raises
-    assert NL.call_alpha(_model(), None) == (None, 0.0) and NL.call_alpha(_model(), 0) == (None, 0.0)
-    assert NL.call_alpha(_model(lm=lm, alpha=0.3), None) == (lm, 0.3) and NL.call_alpha(_model(lm=lm, alpha=0.3), 0.0) == (None, 0.0)
-    assert NL.call_alpha(_model(lm=lm, alpha=0.3), 0.7) == (lm, 0.7) and NL.call_alpha(_model(lm=lm, alpha=0.0), None) == (None, 0.0)
+    assert call_alpha(_model(), None) == (None, 0.0) and call_alpha(_model(), 0) == (None, 0.0)
+    assert call_alpha(_model(lm=lm, alpha=0.3), None) == (lm, 0.3) and call_alpha(_model(lm=lm, alpha=0.3), 0.0) == (None, 0.0)
+    assert call_alpha(_model(lm=lm, alpha=0.3), 0.7) == (lm, 0.7) and call_alpha(_model(lm=lm, alpha=0.0), None) == (None, 0.0)
     with pytest.raises(ValueError, match="no n-gram LM"):
-        NL.call_alpha(_model(), 0.3)
+        call_alpha(_model(), 0.3)
     with pytest.raises(ValueError, match="ngram_lm_alpha"):
-        NL.call_alpha(_model(lm=lm, alpha=0.3), -1.0)
+        call_alpha(_model(lm=lm, alpha=0.3), -1.0)
     with pytest.raises(ValueError, match="alsd"):
-        NL.call_alpha(_model("greedy_batch", lm=lm, alpha=0.3), None)
+        call_alpha(_model("greedy_batch", lm=lm, alpha=0.3), None)
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------------------

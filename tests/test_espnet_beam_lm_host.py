@@ -31,7 +31,7 @@ from reazonspeech_amd.espnet.asr import load_model
 from reazonspeech_amd.espnet.asr import model as em
 from reazonspeech_amd.espnet.asr.interface import AudioData
 from reazonspeech_amd.espnet.asr.model import EspnetModel, synthetic_token_list
-from reazonspeech_amd.runtime import capi, k2_hotwords as kh, ngram_lm as NL
+from reazonspeech_amd.runtime import capi, fusion, k2_hotwords as kh, ngram_lm as NL
 from reazonspeech_amd.runtime.config import ESPNET_TINY
 
 tr = importlib.import_module("reazonspeech_amd.espnet.asr.transcribe")       # (the package exports a function of the same name)
@@ -238,15 +238,20 @@ def test_a_tie_between_two_extensions_after_their_terms_is_resolved_by_position(
 TOKENS = ["<blank>", "<unk>", "あ", "い", "う", "<space>", "え", "<sos/eos>"]
 
 
+def model_lm(cfg, token_list, *keywords):
+    """(the shared function asks the configuration for its search first: the stand-ins below name the fusing one)"""
+    return fusion.model_lm(fusion.ESPNET, cfg, token_list, *keywords)
+
+
 def test_arpa_pieces_map_onto_an_espnet_token_list(tmp_path):
-    cfg = types.SimpleNamespace(vocab_size=len(TOKENS), n_logits=len(TOKENS), blank_id=0)
+    cfg = types.SimpleNamespace(vocab_size=len(TOKENS), n_logits=len(TOKENS), blank_id=0, decoding="beam")
     ent = {("<s>",): (-99.0, -0.25), ("あ",): (-0.5, -0.125), ("い",): (-0.75, 0.0), ("<space>",): (-1.0, -0.125), ("<unk>",): (-2.0, None),
            ("<sos/eos>",): (-1.5, 0.0), ("</s>",): (-1.25, None), ("<s>", "あ"): (-0.25, 0.0), ("あ", "<space>"): (-0.125, 0.0),
            ("<space>", "い"): (-0.375, None)}
     path = NR.write_arpa(str(tmp_path / "toy.arpa"), ent, order=2)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
-        lm = em.model_lm(cfg, TOKENS, path)
+        lm = model_lm(cfg, TOKENS, path)
     assert any("dropped" in str(x.message) for x in w)                     # </s> and <sos/eos> name no token
     assert lm.order == 2 and lm.n_logits == len(TOKENS) and lm.start != 0
     root = lm.arrays["root_child"]
@@ -261,18 +266,18 @@ def test_arpa_pieces_map_onto_an_espnet_token_list(tmp_path):
     gz = NR.write_arpa(str(tmp_path / "toy.arpa.gz"), ent, order=2, gz=True)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        assert em.model_lm(cfg, TOKENS, gz).key == lm.key
-        ids = em.model_lm(cfg, TOKENS, NR.write_arpa(str(tmp_path / "ids.arpa"), {(2,): (-0.5, 0.0), (5,): (-1.0, 0.0)}), "ids")
+        assert model_lm(cfg, TOKENS, gz).key == lm.key
+        ids = model_lm(cfg, TOKENS, NR.write_arpa(str(tmp_path / "ids.arpa"), {(2,): (-0.5, 0.0), (5,): (-1.0, 0.0)}), "ids")
     assert int(ids.arrays["root_child"][5]) >= 0
-    assert em.model_lm(cfg, TOKENS, lm) is lm
+    assert model_lm(cfg, TOKENS, lm) is lm
     with pytest.raises(ValueError, match="built for"):
-        em.model_lm(types.SimpleNamespace(vocab_size=9, n_logits=9, blank_id=0), TOKENS + ["x"], lm)
+        model_lm(types.SimpleNamespace(vocab_size=9, n_logits=9, blank_id=0, decoding="beam"), TOKENS + ["x"], lm)
     with pytest.raises(ValueError, match="ngram_lm_tokens"):
-        em.model_lm(cfg, TOKENS, path, "nemo")
+        model_lm(cfg, TOKENS, path, "nemo")
     kenlm = tmp_path / "lm.bin"
     kenlm.write_bytes(NL.KENLM_MAGIC + b"\0" * 64)
     with pytest.raises(ValueError):
-        em.model_lm(cfg, TOKENS, str(kenlm))
+        model_lm(cfg, TOKENS, str(kenlm))
 
 
 def test_phrases_are_encoded_per_character():

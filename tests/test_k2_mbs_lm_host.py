@@ -31,7 +31,7 @@ from ngram_lm_ref import ArpaDict, BOS
 from reazonspeech_amd import build as rs_build
 from reazonspeech_amd.k2.asr import huggingface as hfm
 from reazonspeech_amd.k2.asr.model import K2Model, search_config, synthetic_tokens
-from reazonspeech_amd.runtime import capi, k2_hotwords as kh, ngram_lm as NL
+from reazonspeech_amd.runtime import capi, fusion, k2_hotwords as kh, ngram_lm as NL
 from reazonspeech_amd.runtime.k2_config import ZIPFORMER_TINY
 from reazonspeech_amd.runtime.k2_weights import synthetic_state_dict_k2
 from reazonspeech_amd.runtime.model import _NgramSet
@@ -251,6 +251,14 @@ def test_merged_candidates_carry_their_lm_terms_into_logaddexp():
 MBS = dict(decoding_method="modified_beam_search")
 
 
+def k2_call_alpha(model, ngram_lm_alpha):
+    return fusion.call_alpha(fusion.K2, model, ngram_lm_alpha)
+
+
+def k2_model_lm(cfg, tokens, *keywords):
+    return fusion.model_lm(fusion.K2, cfg, tokens, *keywords)
+
+
 def test_the_lm_keywords_are_checked_before_anything_is_loaded(tmp_path):
     cfg = ZIPFORMER_TINY
     for call in (lambda **kw: hfm.load_model(**kw), lambda **kw: search_config(cfg, **kw),
@@ -271,12 +279,12 @@ def test_the_lm_keywords_are_checked_before_anything_is_loaded(tmp_path):
     assert search_config(cfg) == cfg and search_config(cfg, ngram_lm_alpha=0.3) == cfg        # no model: today's configuration
     # the per-call weight
     no_lm = types.SimpleNamespace(ngram_lm=None, ngram_lm_alpha=0.0, cfg=search_config(cfg, **MBS))
-    assert NL.k2_call_alpha(no_lm, None) == (None, 0.0) and NL.k2_call_alpha(no_lm, 0) == (None, 0.0)
+    assert k2_call_alpha(no_lm, None) == (None, 0.0) and k2_call_alpha(no_lm, 0) == (None, 0.0)
     with pytest.raises(ValueError, match="the model has no n-gram LM"):
-        NL.k2_call_alpha(no_lm, 0.3)
+        k2_call_alpha(no_lm, 0.3)
     lm = NL.build({(5,): (-1.0, 0.0)}, cfg.vocab_size, cfg.blank_id)
     has = types.SimpleNamespace(ngram_lm=lm, ngram_lm_alpha=0.25, cfg=no_lm.cfg)
-    assert NL.k2_call_alpha(has, None) == (lm, 0.25) and NL.k2_call_alpha(has, 0) == (None, 0.0) and NL.k2_call_alpha(has, 2) == (lm, 2.0)
+    assert k2_call_alpha(has, None) == (lm, 0.25) and k2_call_alpha(has, 0) == (None, 0.0) and k2_call_alpha(has, 2) == (lm, 2.0)
     # the signatures: transcribe gains the keyword last, transcribe_batch and create_stream keep theirs
     assert list(inspect.signature(k2tr.transcribe).parameters) == ["model", "audio", "config", "hotwords", "ngram_lm_alpha"]
     assert list(inspect.signature(k2tr.transcribe_batch).parameters) == ["model", "audios", "config", "hotwords"]
@@ -290,9 +298,9 @@ def test_a_table_for_other_logits_or_one_that_fails_the_check_is_refused():
     tokens = synthetic_tokens(cfg.vocab_size, 3)
     wrong = NL.build({(5,): (-1.0, 0.0)}, cfg.vocab_size + 3, cfg.blank_id)
     with pytest.raises(ValueError, match=f"built for {cfg.vocab_size + 3} logits, the model has {cfg.vocab_size}"):
-        NL.k2_model_lm(cfg, tokens, wrong)
+        k2_model_lm(cfg, tokens, wrong)
     with pytest.raises(ValueError, match="an n-gram LM needs decoding_method='modified_beam_search'"):
-        NL.k2_model_lm(ZIPFORMER_TINY, tokens, NL.build({(5,): (-1.0, 0.0)}, cfg.vocab_size, cfg.blank_id))
+        k2_model_lm(ZIPFORMER_TINY, tokens, NL.build({(5,): (-1.0, 0.0)}, cfg.vocab_size, cfg.blank_id))
     bad = NL.build({(5,): (-1.0, 0.0), (6,): (-1.0, 0.0), (5, 6): (-0.5, 0.0)}, cfg.vocab_size, cfg.blank_id)
     bad.arrays["suffix"][3] = 3                                           # a suffix link that does not lower the level
     with pytest.raises(capi.RsError, match="does not lower the level") as e:
@@ -309,16 +317,16 @@ def test_an_arpa_file_in_the_pieces_of_tokens_txt_reads_back(tmp_path):
     path = NR.write_arpa(str(tmp_path / "lm.arpa"), ent, mode="pieces", pieces=tokens)
     text = open(path, encoding="utf-8").read()
     assert tokens[5] in text and tokens[40] in text and "<s>" in text
-    got = NL.k2_model_lm(cfg, tokens, path)                               # "pieces" is the default
+    got = k2_model_lm(cfg, tokens, path)                               # "pieces" is the default
     assert got.key == want.key and got.order == 3 and got.n_logits == cfg.vocab_size and got.start == want.start != 0
     for k in NL.ARRAYS:
         assert np.array_equal(got.arrays[k], want.arrays[k]), k
-    ids = NL.k2_model_lm(cfg, tokens, NR.write_arpa(str(tmp_path / "ids.arpa"), ent, mode="ids"), "ids")
+    ids = k2_model_lm(cfg, tokens, NR.write_arpa(str(tmp_path / "ids.arpa"), ent, mode="ids"), "ids")
     assert ids.key == want.key
     with pytest.raises(ValueError, match="NeMo package"):
-        NL.k2_model_lm(cfg, tokens, path, "nemo")
+        k2_model_lm(cfg, tokens, path, "nemo")
     # `<unk>` of the file is the unknown-word entry, not tokens.txt's <unk> symbol
-    unk = NL.k2_model_lm(cfg, tokens, NR.write_arpa(str(tmp_path / "unk.arpa"), {**ent, ("<unk>",): (-4.0, None)}, mode="pieces", pieces=tokens))
+    unk = k2_model_lm(cfg, tokens, NR.write_arpa(str(tmp_path / "unk.arpa"), {**ent, ("<unk>",): (-4.0, None)}, mode="pieces", pieces=tokens))
     assert unk.unk_logp == np.float32(-4.0 * math.log(10.0)) and np.array_equal(unk.arrays["logp"], want.arrays["logp"])
 
 
@@ -342,13 +350,13 @@ def test_the_entry_points_are_exported_declared_and_guarded():
 
 def test_the_nemo_packages_helpers_keep_their_messages():
     with pytest.raises(ValueError, match=r"^an n-gram LM needs decoding='alsd', not 'greedy_batch'$"):
-        NL.check_keywords("greedy_batch", "lm.arpa", 0.3)
+        fusion.check_lm_keywords(fusion.NEMO, "greedy_batch", "lm.arpa", 0.3)
     with pytest.raises(ValueError, match=r"^ngram_lm_tokens must be one of \('nemo', 'pieces', 'ids'\), not 'words'$"):
-        NL.check_keywords("alsd", "lm.arpa", 0.3, "words")
+        fusion.check_lm_keywords(fusion.NEMO, "alsd", "lm.arpa", 0.3, "words")
     with pytest.raises(ValueError, match=r"^ngram_lm_alpha must be a finite number >= 0, not -1$"):
-        NL.check_keywords("alsd", "lm.arpa", -1)
-    assert NL.check_keywords("alsd", "lm.arpa", 0.3) is True and NL.check_keywords("greedy_batch", None, 0.0) is False
+        fusion.check_lm_keywords(fusion.NEMO, "alsd", "lm.arpa", -1)
+    assert fusion.check_lm_keywords(fusion.NEMO, "alsd", "lm.arpa", 0.3) is True and fusion.check_lm_keywords(fusion.NEMO, "greedy_batch", None, 0.0) is False
     nemo = types.SimpleNamespace(ngram_lm=None, ngram_lm_alpha=0.0, cfg=types.SimpleNamespace(decoding="alsd"))
     with pytest.raises(ValueError, match=r"^ngram_lm_alpha given, but the model has no n-gram LM \(load_model\(ngram_lm_model=...\)\)$"):
-        NL.call_alpha(nemo, 0.3)
+        fusion.call_alpha(fusion.NEMO, nemo, 0.3)
     assert NL.TOKEN_MODES == ("nemo", "pieces", "ids")
