@@ -948,6 +948,50 @@ int rs_rnnt_align(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, 
                   const int32_t* n_ids, int u_cap, int flags, float* loglik, float* best, int32_t* frames, float* logp,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- several texts per utterance on one lattice (n-best rescoring by full likelihood) — added within ABI 7 ----
+ * rs_rnnt_align over R text rows that share the B utterances: row r is scored against the frames of utterance row_utt[r], and the
+ * lattice cells that rows of one utterance have in common — the columns of a shared label prefix — are computed once.
+ *   joint_enc, enc_lens, B, tp_max   the utterances, as for rs_rnnt_align
+ *   row_utt i32[R] (device)   utterance of row r; -1: the row is skipped and NONE of its output slots is touched.  The non-negative
+ *                             entries are non-decreasing, below B, and at most RS_ALIGN_ROWS_PER_UTT_MAX rows name one utterance.
+ *   ids i32[R][u_cap], n_ids i32[R]; loglik / best f32[R]; frames i32 / logp f32 [R][u_cap]   per row, as rs_rnnt_align's per utterance
+ *   flags    RS_ALIGN_ONE_PER_FRAME as above; RS_ALIGN_NO_SHARING: every row computes its whole lattice (the same bits; for A/B)
+ *   stats    host int64_t[2] or NULL, filled after the internal sync: [0] lattice rows whose joint was computed, [1] lattice rows
+ *            there are without sharing, the sum of T_r (U_r + 1) over the rows with a lattice
+ * THE SHARING RULE.  A row has a lattice as above: not skipped, not bad, T > 0, and U <= T with one label per frame.  For a row r
+ * with a lattice, over the earlier rows r' < r of the same utterance that have a lattice: m(r) = the greatest number of leading
+ * labels r has in common with one of them, donor(r) = the first row that attains it; without such a row m(r) = 0 and there is no
+ * donor (nor is there one at m = 0: nothing would be read from it).  Row r computes its cells with u >= m(r) — column m(r) again,
+ * because ly(t, m) picks another label from the same logits — and reads the cells with u < m(r) from its donor, through the donor's
+ * own donor where u < m(donor): a chain at most RS_ALIGN_ROWS_PER_UTT_MAX - 1 deep.  So stats[0] = sum of T_r (U_r + 1 - m(r)).
+ * A bad or infeasible row is never a donor.  The rule is stated in csrc/rs_align_rows_plan.h (pure integers, also built alone on the
+ * host by the tests).
+ * THE GUARANTEE.  loglik, best, frames and logp of row r equal, bit for bit, what rs_rnnt_align returns for a batch of R utterances
+ * whose row r holds a copy of utterance row_utt[r]'s joint_enc frames and enc_lens — with and without RS_ALIGN_NO_SHARING, whatever
+ * the chunk and whatever else is in the batch: a cell's bits depend on the utterance, the frame and the label prefix only.  A bad
+ * row (a count outside 0..u_cap, an id outside the vocabulary or the blank) is NaN / -1 as above, the call returns RS_EINVAL after
+ * the sync and the other rows keep their bits.
+ * Workspace: rs_rnnt_align_rows_workspace_bytes(ctx, B, R, tp_max, u_cap) is the MINIMUM, sized without sharing (what a group shares
+ * is unknown before the ids are read): R x tp_max x (u_cap + 1) cells, 32 lattice rows per chunk; 0 for invalid arguments.
+ * RS_EINVAL before anything is enqueued as for rs_rnnt_align (R in the place of B in the bound).  row_utt is checked on the device
+ * before anything indexes with it: an entry below -1 or >= B, a decrease, or more than RS_ALIGN_ROWS_PER_UTT_MAX rows on one
+ * utterance make the call return RS_EINVAL after the sync with NOTHING scored and no output written. */
+enum { RS_ALIGN_NO_SHARING = 2 };
+#define RS_ALIGN_ROWS_PER_UTT_MAX 64
+size_t rs_rnnt_align_rows_workspace_bytes(const rs_ctx* ctx, int B, int R, int tp_max, int u_cap);
+int rs_rnnt_align_rows(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* row_utt, int R,
+                       const int32_t* ids, const int32_t* n_ids, int u_cap, int flags, float* loglik, float* best, int32_t* frames,
+                       float* logp, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+
+/* rs_rnnt_token_scores over R rows with the same row_utt contract (a -1 row has no tokens: none of its slots is touched; a row_utt
+ * error returns RS_EINVAL after the first sync with nothing scored).  ids / frames / logp / top1 [R][u_cap] and n_ids [R] are per
+ * row; a frame is checked against the row's utterance.  The results equal rs_rnnt_token_scores on replicated frames, bit for bit.
+ * Nothing is shared here: a text has only U joint rows.  Workspace: the minimum for R rows. */
+size_t rs_rnnt_token_scores_rows_workspace_bytes(const rs_ctx* ctx, int B, int R, int u_cap);
+int rs_rnnt_token_scores_rows(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* row_utt,
+                              int R, const int32_t* ids, const int32_t* frames, const int32_t* n_ids, int u_cap, int flags, float* logp,
+                              int32_t* top1, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC segmentation of a batch (ESPnet family: time stamps of a recognised text) ------------------
  * Replaces: ctc_segmentation.ctc_segmentation(config, lpz, ground_truth_mat) of the third-party aligner the reference calls
  * once per window (pkg/espnet-asr/src/ctc.py:60-75), for the default CtcSegmentationParameters — the only ones the reference

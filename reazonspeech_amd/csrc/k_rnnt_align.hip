@@ -23,7 +23,18 @@
 // THESE GPUS ARE SHARED: the plan kernel checks every count against u_cap and every id against the vocabulary (the blank is no
 // label) before anything indexes with them; a bad row has no lattice cells, its outputs are NaN / -1 and the call returns
 // RS_EINVAL after the sync.  Compiled with -ffp-contract=off.
+//
+// rs_rnnt_align_rows: R text rows, row r scored against the frames of utterance row_utt[r].  Everything above holds with "text row"
+// for "utterance"; only the joint-encoder frames and enc_lens are read through row_utt.  The plan (rs_align_rows_plan.h) gives every
+// row with a lattice m(r) and donor(r): the row owns the columns u >= m of its lattice, a T x (U - m + 1) lattice in the same
+// anti-diagonal order (lat_off / lat_index with U - m), and its compacted list holds those cells alone.  Column m is recomputed —
+// lb(t, m) is the donor's, ly(t, m) picks another label from the same logits — so the pick kernel stays as it is.  The DP of a
+// row walks its donor chain once into LDS (at most 64 entries: first lattice row, U, m) and one byte per column names the
+// chain entry that owns it; a predecessor's lb / ly is then read from its owner's list.  The cells read are, bit for bit, the
+// cells the row would have computed: a cell's bits depend on the utterance, the frame and the label prefix only.  rs_rnnt_align
+// itself runs the kernels it ran (no row_utt, no chain: the template arguments below).
 #include "k_rnnt_common.h"
+#include "rs_align_rows_plan.h"
 
 namespace {
 
@@ -35,7 +46,9 @@ struct AlignArgs {
     const int32_t* enc_lens;   // [B]
     const int32_t* ids;        // [B][u_cap]
     const int32_t* n_ids;      // [B]
-    int B, u_cap, tp_max, V, blank, one;
+    int B, u_cap, tp_max, V, blank, one;                    // B: the text rows (rs_rnnt_align: one per utterance)
+    const int32_t* row_utt;    // [B] rs_rnnt_align_rows: the utterance of text row b (nullptr: row b is utterance b)
+    int n_utt, no_sharing;
     // workspace
     int32_t* n_ok;             // [B] U, or -1 for a bad row
     int32_t* t_of;             // [B] T = min(enc_lens, tp_max), at least 0
@@ -45,7 +58,10 @@ struct AlignArgs {
     float* lat_y;              // [rows] ly of lattice row w (unused at u = U)
     uint32_t* bits;            // [B][tp_max + u_cap + 1][bit_words] Viterbi back-pointers of diagonal d, bit u
     int bit_words;
-    int32_t* row_b;            // [R] utterance, frame and label index of the current chunk's rows
+    int32_t* lat_u;            // rs_rnnt_align_rows, [B] each: U of a row with a lattice else -1; m(b); donor(b) or -1
+    int32_t* m_of;
+    int32_t* donor;
+    int32_t* row_b;            // [R] text row, frame and label index of the current chunk's rows
     int32_t* row_t;
     int32_t* row_u;
 };
@@ -70,7 +86,8 @@ __device__ __forceinline__ void lat_cell(const AlignArgs& a, int w, int& b, int&
         if (a.base[mid] <= w) lo = mid; else hi = mid - 1;
     }
     b = lo;
-    const int i = w - a.base[b], T = a.t_of[b], U = a.n_ok[b];
+    const int m = a.m_of ? a.m_of[b] : 0;                   // the row owns the columns m .. U: a T x (U - m + 1) lattice
+    const int i = w - a.base[b], T = a.t_of[b], U = a.n_ok[b] - m;
     int dl = 0, dh = T + U - 1;                             // the last d with lat_off(d) <= i
     while (dl < dh) {
         const int mid = (dl + dh + 1) >> 1;
@@ -78,6 +95,7 @@ __device__ __forceinline__ void lat_cell(const AlignArgs& a, int w, int& b, int&
     }
     u = lat_ulo(T, dl) + (i - lat_off(T, U, dl));
     t = dl - u;
+    u += m;
 }
 
 // ---- the plan: counts, checks and the lattice's prefix sums.  One workgroup: thread i owns a contiguous run of utterances. ----
@@ -123,6 +141,74 @@ __global__ __launch_bounds__(256) void align_plan_kernel(AlignArgs a) {
         const int n = a.n_ok[b], T = a.t_of[b];
         a.base[b] = w;
         if (n >= 0 && T > 0 && !(a.one && n > T)) w += T * (n + 1);
+    }
+}
+
+// ---- the plan of rs_rnnt_align_rows: row_utt is checked first (nothing indexes with it before), then the rows as above, then
+// m and donor of every row with a lattice, and the prefix sums over the rows each one owns.  One workgroup, as above. ----
+// info: [0] owned rows in all, [1] longest U + 1, [2] a bad text, [3] what row_utt does wrong (RS_ROWS_*), [4] rows without sharing
+__global__ __launch_bounds__(256) void align_rows_plan_kernel(AlignArgs a) {
+    __shared__ int part[256];
+    __shared__ int longest_s, bad_s, err_s, full_s;
+    const int tid = threadIdx.x;
+    if (tid == 0) { longest_s = 0; bad_s = 0; err_s = 0; full_s = 0; }
+    __syncthreads();
+    const int per = (a.B + 255) / 256;
+    const int b0 = tid * per < a.B ? tid * per : a.B, b1 = (b0 + per) < a.B ? (b0 + per) : a.B;
+    int err = 0;
+    for (int b = b0; b < b1; ++b) err |= rs_align_rows_check_row(a.row_utt, a.n_utt, b);
+    if (err) atomicOr(&err_s, err);
+    __syncthreads();
+    if (err_s) {                                            // nothing is scored and nothing is written
+        if (tid == 0) { a.info[0] = 0; a.info[1] = 0; a.info[2] = 0; a.info[3] = err_s; a.info[4] = 0; }
+        return;
+    }
+    int bad = 0;
+    for (int b = b0; b < b1; ++b) {
+        const int utt = a.row_utt[b];
+        int T = 0, n = -1, lu = RS_ROWS_NO_LATTICE;
+        if (utt >= 0) {
+            T = a.enc_lens[utt];
+            T = T < a.tp_max ? T : a.tp_max;
+            T = T > 0 ? T : 0;
+            n = a.n_ids[b];
+            lu = rs_align_rows_lattice_u(n, a.ids + (size_t)b * a.u_cap, a.u_cap, a.V, a.blank, T, a.one);
+            if (lu == RS_ROWS_BAD) { bad = 1; n = -1; }
+        }
+        a.n_ok[b] = n;                                      // -1: skipped (row_utt -1) or bad
+        a.t_of[b] = T;
+        a.lat_u[b] = lu >= 0 ? lu : -1;
+    }
+    if (bad) atomicOr(&bad_s, 1);
+    __syncthreads();
+    int sum = 0, full = 0, longest = 0;
+    for (int b = b0; b < b1; ++b) {
+        int m = 0, from = -1;
+        const int U = a.lat_u[b];
+        if (U >= 0) {
+            if (!a.no_sharing) rs_align_rows_share(a.row_utt, a.lat_u, a.ids, a.u_cap, b, &m, &from);
+            sum += a.t_of[b] * (U + 1 - m);
+            full += a.t_of[b] * (U + 1);
+            longest = U + 1 > longest ? U + 1 : longest;
+        }
+        a.m_of[b] = m;
+        a.donor[b] = from;
+    }
+    part[tid] = sum;
+    if (longest) atomicMax(&longest_s, longest);
+    if (full) atomicAdd(&full_s, full);
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = run; run += v; }
+        a.info[0] = run; a.info[1] = longest_s; a.info[2] = bad_s; a.info[3] = 0; a.info[4] = full_s;
+        a.base[a.B] = run;
+    }
+    __syncthreads();
+    int w = part[tid];
+    for (int b = b0; b < b1; ++b) {
+        a.base[b] = w;
+        if (a.lat_u[b] >= 0) w += a.t_of[b] * (a.lat_u[b] + 1 - a.m_of[b]);
     }
 }
 
@@ -172,7 +258,8 @@ __global__ __launch_bounds__(256) void align_gather_kernel(AlignArgs a, DecodeSt
     if (i >= (long long)n * j4) return;
     const int r = (int)(i / j4), k = (int)(i - (long long)r * j4) * 4;
     const int b = a.row_b[r], t = a.row_t[r], u = a.row_u[r];
-    const float4 fv = *reinterpret_cast<const float4*>(f + ((size_t)b * a.tp_max + t) * J + k);
+    const int fb = a.row_utt ? a.row_utt[b] : b;             // (checked by the plan)
+    const float4 fv = *reinterpret_cast<const float4*>(f + ((size_t)fb * a.tp_max + t) * J + k);
     const float* gr = g_log ? g_log + ((size_t)u * a.B + b) * J : st.g + (size_t)r * J;
     const float4 gv = *reinterpret_cast<const float4*>(gr + k);
     *reinterpret_cast<float4*>(a_pre + (size_t)r * J + k) = rs_joint_act4(fv, gv, st.joint_act);
@@ -216,17 +303,26 @@ __device__ __forceinline__ float lae(float x, float y) {
     return m + rs_logf(rs_expf(x - m) + rs_expf(y - m));
 }
 
-// ---- the DP: one workgroup per utterance ----
+// ---- the DP: one workgroup per text row.  SHARED (rs_rnnt_align_rows with sharing): the columns u < m of the row are read from
+// its donor chain; otherwise every cell is the row's own and the lattice is addressed as rs_rnnt_align always did ----
+template <bool SHARED>
 __global__ __launch_bounds__(ALIGN_THREADS) void align_dp_kernel(AlignArgs a, float* __restrict__ loglik, float* __restrict__ best,
                                                                 int32_t* __restrict__ frames, float* __restrict__ logp) {
     __shared__ float al[3][ALIGN_CELLS];      // the forward sum on diagonals d, d - 1, d - 2 (slot d % 3), indexed by u
     __shared__ float vi[3][ALIGN_CELLS];      // the Viterbi score
+    __shared__ uint8_t own[SHARED ? ALIGN_CELLS : 1];                    // chain entry that owns column u
+    __shared__ int ch_base[SHARED ? RS_ALIGN_ROWS_PER_UTT_MAX : 1];     // per chain entry: first lattice row, U, m
+    __shared__ int ch_u[SHARED ? RS_ALIGN_ROWS_PER_UTT_MAX : 1];
+    __shared__ int ch_m[SHARED ? RS_ALIGN_ROWS_PER_UTT_MAX : 1];
+    __shared__ int ch_hi[SHARED ? RS_ALIGN_ROWS_PER_UTT_MAX : 1];       // the entry owns the columns ch_m .. ch_hi - 1 of this row
+    __shared__ int ch_n;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int U = a.n_ok[b], T = a.t_of[b];
     const float nan = __uint_as_float(0x7fc00000u);
     float* lp = logp + (size_t)b * a.u_cap;
     int32_t* fr = frames + (size_t)b * a.u_cap;
     if (U < 0) {                                             // a bad row: a count outside 0..u_cap, or an id that is no label
+        if (a.row_utt && a.row_utt[b] == -1) return;         // a skipped row: no slot of it is touched
         int n = a.n_ids[b];
         n = n < 0 ? 0 : (n > a.u_cap ? a.u_cap : n);
         for (int u = tid; u < n; u += ALIGN_THREADS) { fr[u] = -1; lp[u] = nan; }
@@ -242,6 +338,31 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_dp_kernel(AlignArgs a, fl
     const float* lb = a.lat_b + a.base[b];
     const float* ly = a.lat_y + a.base[b];
     const int one = a.one;
+    if (SHARED) {
+        if (tid == 0) {                                      // the chain: this row, its donor, the donor's donor .. (donor < row)
+            int q = b, hi = U + 1, k = 0;
+            for (; k < RS_ALIGN_ROWS_PER_UTT_MAX; ++k) {
+                const int mq = a.m_of[q];
+                ch_base[k] = a.base[q]; ch_u[k] = a.n_ok[q]; ch_m[k] = mq; ch_hi[k] = hi;
+                hi = mq < hi ? mq : hi;
+                q = a.donor[q];
+                if (hi == 0 || q < 0) { ++k; break; }
+            }
+            ch_n = k;
+        }
+        __syncthreads();
+        for (int u = tid; u <= U; u += ALIGN_THREADS) {
+            int k = 0;
+            while (k + 1 < ch_n && !(u >= ch_m[k] && u < ch_hi[k])) ++k;
+            own[u] = (uint8_t)k;
+        }
+        __syncthreads();
+    }
+    // lattice row (in the whole list) of cell (t, u) of this row, through the owner of column u
+    auto cell_row = [&](int t, int u) -> int {
+        const int k = own[u], mk = ch_m[k];
+        return ch_base[k] + lat_index(T, ch_u[k] - mk, t, u - mk);
+    };
     const int n_diag = one ? T + U + 1 : T + U;              // diagonals d = t + u with a cell
     const int t_top = one ? T : T - 1;                       // the largest t of the DP's cells
     uint32_t* bits = a.bits + (size_t)b * (a.tp_max + a.u_cap + 1) * a.bit_words;
@@ -269,11 +390,11 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_dp_kernel(AlignArgs a, fl
                 } else {
                     float ab = -INFINITY, vb = -INFINITY, ay = -INFINITY, vy = -INFINITY;
                     if (t >= 1) {                                                    // (t - 1, u): u <= d - 1
-                        const float x = lb[ob + u];
+                        const float x = SHARED ? a.lat_b[cell_row(t - 1, u)] : lb[ob + u];
                         ab = al_1[u] + x; vb = vi_1[u] + x;
                     }
                     if (u >= 1 && (!one || t >= 1)) {
-                        const float x = ly[oy + u - 1];
+                        const float x = SHARED ? a.lat_y[cell_row(one ? t - 1 : t, u - 1)] : ly[oy + u - 1];
                         ay = al_2[u - 1] + x; vy = vi_2[u - 1] + x;
                     }
                     sa = lae(ab, ay);
@@ -294,7 +415,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_dp_kernel(AlignArgs a, fl
     // the last diagonal holds one cell, (t_top, U)
     if (tid == 0) {
         const int d = n_diag - 1;
-        const float x = one ? 0.0f : lb[lat_index(T, U, T - 1, U)];
+        const float x = one ? 0.0f : (SHARED ? a.lat_b[cell_row(T - 1, U)] : lb[lat_index(T, U, T - 1, U)]);
         loglik[b] = one ? al[d % 3][U] : al[d % 3][U] + x;
         best[b] = one ? vi[d % 3][U] : vi[d % 3][U] + x;
         // walk the back-pointers from (t_top, U): at most T + U steps
@@ -317,7 +438,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_dp_kernel(AlignArgs a, fl
     if (tid < 64)
         for (int u = tid; u < U; u += 64) {
             const int t = fr[u];
-            lp[u] = (t >= 0 && t < T) ? ly[lat_index(T, U, t, u)] : nan;
+            lp[u] = (t >= 0 && t < T) ? (SHARED ? a.lat_y[cell_row(t, u)] : ly[lat_index(T, U, t, u)]) : nan;
         }
 }
 
@@ -329,8 +450,8 @@ struct AlignLayout {
     float* a_pre = nullptr;    // [R][J]
 };
 
-// R = rows per chunk (a multiple of 32)
-void align_layout(const rs_ctx* ctx, int B, int tp_max, int u_cap, size_t R, rs_arena& ar, AlignLayout& l) {
+// R = rows per chunk (a multiple of 32); B = the text rows; rows: the form of rs_rnnt_align_rows (three more arrays, at the end)
+void align_layout(const rs_ctx* ctx, int B, int tp_max, int u_cap, size_t R, bool rows, rs_arena& ar, AlignLayout& l) {
     const rs_dims& d = ctx->d;
     const size_t H = d.pred_hidden, J = d.joint_hidden, cells = (size_t)B * tp_max * (u_cap + 1);
     DecodeState& st = l.st;
@@ -362,13 +483,14 @@ void align_layout(const rs_ctx* ctx, int B, int tp_max, int u_cap, size_t R, rs_
     st.zapprox = ar.take<float>(R * (size_t)rs_joint_zstride(d));
     st.a_pre = l.a_pre;
     st.joint_act = d.joint_act;
+    if (rows) { l.a.lat_u = ar.take<int32_t>(B); l.a.m_of = ar.take<int32_t>(B); l.a.donor = ar.take<int32_t>(B); }
 }
 constexpr size_t ALIGN_MAX_R = 32 * 65535;                 // the tile kernel's grid
 
-size_t align_bytes(const rs_ctx* ctx, int B, int tp_max, int u_cap, size_t R) {
+size_t align_bytes(const rs_ctx* ctx, int B, int tp_max, int u_cap, size_t R, bool rows) {
     rs_arena ar;
     AlignLayout l;
-    align_layout(ctx, B, tp_max, u_cap, R, ar, l);
+    align_layout(ctx, B, tp_max, u_cap, R, rows, ar, l);
     return ar.bytes() + RS_DECODE_SLACK;
 }
 
@@ -376,60 +498,64 @@ bool align_dims_ok(int B, int tp_max, int u_cap) {
     return u_cap <= ALIGN_U_MAX && (long long)B * tp_max * (u_cap + 1) <= 0x3fffffffLL && (long long)B * (u_cap + 1) <= 0x3fffffffLL;
 }
 
-}  // namespace
-
-size_t rs_rnnt_align_workspace_bytes_impl(const rs_ctx* ctx, int B, int tp_max, int u_cap) {
-    return align_dims_ok(B, tp_max, u_cap) ? align_bytes(ctx, B, tp_max, u_cap, 32) : 0;
-}
 
 // rows per chunk that `workspace_bytes` holds (0: below the minimum), at most the rows there can be
-size_t rs_rnnt_align_chunk_rows(const rs_ctx* ctx, int B, int tp_max, int u_cap, size_t workspace_bytes) {
-    const size_t least = align_bytes(ctx, B, tp_max, u_cap, 32);
+size_t align_chunk_rows(const rs_ctx* ctx, int B, int tp_max, int u_cap, bool rows, size_t workspace_bytes) {
+    const size_t least = align_bytes(ctx, B, tp_max, u_cap, 32, rows);
     if (workspace_bytes < least) return 0;
-    const size_t per32 = align_bytes(ctx, B, tp_max, u_cap, 64) - least;
+    const size_t per32 = align_bytes(ctx, B, tp_max, u_cap, 64, rows) - least;
     size_t most = ((size_t)B * tp_max * (u_cap + 1) + 31) / 32 * 32;
     if (most < 32) most = 32;
     if (most > ALIGN_MAX_R) most = ALIGN_MAX_R;
     size_t R = 32 + 32 * ((workspace_bytes - least) / per32);
     if (R > most) R = most;
-    while (R > 32 && align_bytes(ctx, B, tp_max, u_cap, R) > workspace_bytes) R -= 32;
+    while (R > 32 && align_bytes(ctx, B, tp_max, u_cap, R, rows) > workspace_bytes) R -= 32;
     return R;
 }
 
-int rs_rnnt_align_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
-                       const int32_t* n_ids, int u_cap, int one_per_frame, float* loglik, float* best, int32_t* frames, float* logp,
-                       void* workspace, size_t workspace_bytes, hipStream_t s) {
+// B text rows; row_utt == nullptr: rs_rnnt_align (row b is utterance b, n_utt = B), else rs_rnnt_align_rows over n_utt utterances
+int align_run(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int n_utt, int tp_max, const int32_t* row_utt, int B,
+              const int32_t* ids, const int32_t* n_ids, int u_cap, int one_per_frame, int no_sharing, float* loglik, float* best,
+              int32_t* frames, float* logp, int64_t* stats, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
-    const bool k2 = ctx->k2_conv_w != nullptr;
+    const bool k2 = ctx->k2_conv_w != nullptr, rows = row_utt != nullptr;
     if (int rc = rs_rnnt_check_dims(ctx, "align"); rc != RS_OK) return rc;
     if (k2 && L != 1) return rs_fail(ctx, RS_EINVAL, "align: unsupported prediction network");
     if (!align_dims_ok(B, tp_max, u_cap)) return rs_fail(ctx, RS_EINVAL, "align: u_cap above %d or B x tp_max x (u_cap + 1) too large", ALIGN_U_MAX);
-    const size_t R = rs_rnnt_align_chunk_rows(ctx, B, tp_max, u_cap, workspace_bytes);
+    const size_t R = align_chunk_rows(ctx, B, tp_max, u_cap, rows, workspace_bytes);
     if (R == 0)
-        return rs_fail(ctx, RS_EINVAL, "align: workspace %zu < %zu", workspace_bytes, rs_rnnt_align_workspace_bytes_impl(ctx, B, tp_max, u_cap));
+        return rs_fail(ctx, RS_EINVAL, "align: workspace %zu < %zu", workspace_bytes, align_bytes(ctx, B, tp_max, u_cap, 32, rows));
     rs_arena arena(workspace);
     AlignLayout l;
-    align_layout(ctx, B, tp_max, u_cap, R, arena, l);
+    align_layout(ctx, B, tp_max, u_cap, R, rows, arena, l);
     DecodeState& st = l.st;
     AlignArgs& a = l.a;
     a.enc_lens = enc_lens; a.ids = ids; a.n_ids = n_ids;
     a.B = B; a.u_cap = u_cap; a.tp_max = tp_max; a.V = V; a.blank = d.blank_id; a.one = one_per_frame;
+    a.row_utt = row_utt; a.n_utt = n_utt; a.no_sharing = no_sharing;
     if (k2) st.unk = rs_k2_unk_id(ctx);
     const int zstride = rs_joint_zstride(d);
+    if (stats) stats[0] = stats[1] = 0;
 
     // three brackets of the decode class, in this order: the plan and the prediction chain, the lattice (its flops: the joint's
     // products over the rows), the DP
-    int32_t info[4] = {0, 0, 0, 0};
+    int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     {
         rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-        hipLaunchKernelGGL(align_plan_kernel, dim3(1), dim3(256), 0, s, a);
-        RS_HIP(ctx, hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, s));
+        if (rows) hipLaunchKernelGGL(align_rows_plan_kernel, dim3(1), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(align_plan_kernel, dim3(1), dim3(256), 0, s, a);
+        RS_HIP(ctx, hipMemcpyAsync(info, a.info, rows ? sizeof info : 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         RS_HIP(ctx, hipStreamSynchronize(s));
     }
+    if (rows && info[3])
+        return rs_fail(ctx, RS_EINVAL, "align: row_utt %s (nothing was scored)",
+                       (info[3] & RS_ROWS_BAD_UTT) ? "names an utterance outside 0..B-1 (-1 skips a row)"
+                       : (info[3] & RS_ROWS_DECREASE) ? "decreases" : "gives one utterance more rows than RS_ALIGN_ROWS_PER_UTT_MAX");
     const int n_rows = info[0], longest = info[1];
     if (n_rows < 0 || (long long)n_rows > (long long)B * tp_max * (u_cap + 1) || longest < 0 || longest > u_cap + 1)
         return rs_fail(ctx, RS_ESTATE, "align: inconsistent plan");
+    if (stats) { stats[0] = n_rows; stats[1] = rows ? info[4] : n_rows; }
     if (!k2 && n_rows > 0) {
         rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
         const size_t state_bytes = (size_t)L * B * H * 4;
@@ -461,10 +587,38 @@ int rs_rnnt_align_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_l
     }
     {
         rs_prof_scope prof(ctx, RS_PROF_DECODE, s, 0.0, 0.0);
-        hipLaunchKernelGGL(align_dp_kernel, dim3(B), dim3(ALIGN_THREADS), 0, s, a, loglik, best, frames, logp);
+        if (rows && !no_sharing)
+            hipLaunchKernelGGL(align_dp_kernel<true>, dim3(B), dim3(ALIGN_THREADS), 0, s, a, loglik, best, frames, logp);
+        else
+            hipLaunchKernelGGL(align_dp_kernel<false>, dim3(B), dim3(ALIGN_THREADS), 0, s, a, loglik, best, frames, logp);
         RS_CHECK_LAUNCH(ctx, "align: dp");
         RS_HIP(ctx, hipStreamSynchronize(s));
     }
     if (info[2]) return rs_fail(ctx, RS_EINVAL, "align: a count outside 0..u_cap, or an id outside the vocabulary or the blank in a text (its row is NaN / -1)");
     return RS_OK;
+}
+
+}  // namespace
+
+size_t rs_rnnt_align_workspace_bytes_impl(const rs_ctx* ctx, int B, int tp_max, int u_cap) {
+    return align_dims_ok(B, tp_max, u_cap) ? align_bytes(ctx, B, tp_max, u_cap, 32, false) : 0;
+}
+
+size_t rs_rnnt_align_rows_workspace_bytes_impl(const rs_ctx* ctx, int R, int tp_max, int u_cap) {
+    return align_dims_ok(R, tp_max, u_cap) ? align_bytes(ctx, R, tp_max, u_cap, 32, true) : 0;
+}
+
+int rs_rnnt_align_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                       const int32_t* n_ids, int u_cap, int one_per_frame, float* loglik, float* best, int32_t* frames, float* logp,
+                       void* workspace, size_t workspace_bytes, hipStream_t s) {
+    return align_run(ctx, joint_enc, enc_lens, B, tp_max, nullptr, B, ids, n_ids, u_cap, one_per_frame, 0, loglik, best, frames, logp,
+                     nullptr, workspace, workspace_bytes, s);
+}
+
+int rs_rnnt_align_rows_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* row_utt,
+                            int R, const int32_t* ids, const int32_t* n_ids, int u_cap, int one_per_frame, int no_sharing,
+                            float* loglik, float* best, int32_t* frames, float* logp, int64_t* stats, void* workspace,
+                            size_t workspace_bytes, hipStream_t s) {
+    return align_run(ctx, joint_enc, enc_lens, B, tp_max, row_utt, R, ids, n_ids, u_cap, one_per_frame, no_sharing, loglik, best,
+                     frames, logp, stats, workspace, workspace_bytes, s);
 }

@@ -22,8 +22,12 @@
 // neither on the chunk size nor on what else is in the batch.
 // THESE GPUS ARE SHARED: frames are checked against enc_lens (and tp_max) and ids against V before they index anything; a bad
 // entry is replaced by frame 0 / the blank for the loads, its slot gets NaN and the call returns RS_EINVAL after the sync.
+// rs_rnnt_token_scores_rows: B text rows, row b scored against the frames of utterance row_utt[b] (-1: the row has no tokens and
+// none of its slots is touched).  row_utt is checked by the plan before anything indexes with it (rs_align_rows_plan.h); only the
+// joint-encoder frames and enc_lens are read through it, so a row's bits are those of rs_rnnt_token_scores on replicated frames.
 // Compiled with -ffp-contract=off.
 #include "k_rnnt_common.h"
+#include "rs_align_rows_plan.h"
 
 namespace {
 
@@ -32,12 +36,14 @@ struct ScoreArgs {
     const int32_t* ids;        // [B][u_cap]
     const int32_t* frames;     // [B][u_cap] frame of each token (steps = 1: alignment step = frame + index)
     const int32_t* n_ids;      // [B]
-    int B, u_cap, tp_max, V, blank, steps;
+    int B, u_cap, tp_max, V, blank, steps;                  // B: the text rows (rs_rnnt_token_scores: one per utterance)
+    const int32_t* row_utt;    // [B] rs_rnnt_token_scores_rows: the utterance of row b (nullptr: row b is utterance b)
+    int n_utt;
     // workspace
     int32_t* n_ok;             // [B] n_ids clamped to 0..u_cap
     int32_t* row_b;            // [B * u_cap] utterance of compacted row w
     int32_t* row_u;            // [B * u_cap] token index of compacted row w
-    int32_t* info;             // [0] rows in all, [1] longest count, [2] a bad entry was met
+    int32_t* info;             // [0] rows in all, [1] longest count, [2] a bad entry was met, [3] what row_utt does wrong (RS_ROWS_*)
 };
 
 __device__ __forceinline__ bool id_ok(const ScoreArgs& a, int id) { return id >= 0 && id < a.V; }
@@ -45,7 +51,7 @@ __device__ __forceinline__ bool id_ok(const ScoreArgs& a, int id) { return id >=
 __device__ __forceinline__ int frame_of(const ScoreArgs& a, int b, int u) {
     int t = a.frames[(size_t)b * a.u_cap + u];
     if (a.steps) t -= u;
-    int T = a.enc_lens[b];
+    int T = a.enc_lens[a.row_utt ? a.row_utt[b] : b];       // (checked by the plan)
     T = T < a.tp_max ? T : a.tp_max;
     return (t >= 0 && t < T) ? t : -1;
 }
@@ -53,15 +59,25 @@ __device__ __forceinline__ int frame_of(const ScoreArgs& a, int b, int u) {
 // ---- the compacted row list, in (b, u) order.  One workgroup of 256 threads: thread i owns a contiguous run of utterances. ----
 __global__ __launch_bounds__(256) void scores_plan_kernel(ScoreArgs a) {
     __shared__ int part[256];
-    __shared__ int longest_s, bad_s;
+    __shared__ int longest_s, bad_s, err_s;
     const int tid = threadIdx.x;
-    if (tid == 0) { longest_s = 0; bad_s = 0; }
+    if (tid == 0) { longest_s = 0; bad_s = 0; err_s = 0; }
     __syncthreads();
     const int per = (a.B + 255) / 256;
     const int b0 = tid * per, b1 = (b0 + per) < a.B ? (b0 + per) : a.B;
+    if (a.row_utt) {                                        // nothing indexes with row_utt before every entry passed
+        int err = 0;
+        for (int b = b0; b < b1; ++b) err |= rs_align_rows_check_row(a.row_utt, a.n_utt, b);
+        if (err) atomicOr(&err_s, err);
+        __syncthreads();
+        if (err_s) {
+            if (tid == 0) { a.info[0] = 0; a.info[1] = 0; a.info[2] = 0; a.info[3] = err_s; }
+            return;
+        }
+    }
     int sum = 0, longest = 0, bad = 0;
     for (int b = b0; b < b1; ++b) {
-        int n = a.n_ids[b];
+        int n = (a.row_utt && a.row_utt[b] == -1) ? 0 : a.n_ids[b];    // a skipped row has no tokens
         if (n < 0 || n > a.u_cap) { bad = 1; n = n < 0 ? 0 : a.u_cap; }
         a.n_ok[b] = n;
         sum += n;
@@ -74,7 +90,7 @@ __global__ __launch_bounds__(256) void scores_plan_kernel(ScoreArgs a) {
     if (tid == 0) {
         int run = 0;
         for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        a.info[0] = run; a.info[1] = longest_s; a.info[2] = bad_s;
+        a.info[0] = run; a.info[1] = longest_s; a.info[2] = bad_s; a.info[3] = 0;
     }
     __syncthreads();
     int w = part[tid];
@@ -128,7 +144,8 @@ __global__ __launch_bounds__(256) void scores_gather_kernel(ScoreArgs a, DecodeS
     const int b = a.row_b[w0 + r], u = a.row_u[w0 + r];
     int t = frame_of(a, b, u);
     if (t < 0) t = 0;                                     // tp_max >= 1: row 0 exists
-    const float4 fv = *reinterpret_cast<const float4*>(f + ((size_t)b * a.tp_max + t) * J + k);
+    const int fb = a.row_utt ? a.row_utt[b] : b;
+    const float4 fv = *reinterpret_cast<const float4*>(f + ((size_t)fb * a.tp_max + t) * J + k);
     const float* gr = g_log ? g_log + ((size_t)u * a.B + b) * J : st.g + (size_t)r * J;
     const float4 gv = *reinterpret_cast<const float4*>(gr + k);
     *reinterpret_cast<float4*>(a_pre + (size_t)r * J + k) = rs_joint_act4(fv, gv, st.joint_act);
@@ -243,9 +260,10 @@ size_t rs_rnnt_token_scores_chunk_rows(const rs_ctx* ctx, int B, int u_cap, size
     return R;
 }
 
-int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
-                              const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
-                              void* workspace, size_t workspace_bytes, hipStream_t s) {
+// B text rows; row_utt == nullptr: rs_rnnt_token_scores (row b is utterance b), else rs_rnnt_token_scores_rows over n_utt utterances
+static int scores_run(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int n_utt, int tp_max, const int32_t* row_utt,
+                      int B, const int32_t* ids, const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp,
+                      int32_t* top1, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const rs_dims& d = ctx->d;
     const int L = d.pred_layers, H = d.pred_hidden, J = d.joint_hidden, V = d.n_logits;
     const bool k2 = ctx->k2_conv_w != nullptr;
@@ -262,6 +280,7 @@ int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t
     ScoreArgs& a = l.a;
     a.enc_lens = enc_lens; a.ids = ids; a.frames = frames; a.n_ids = n_ids;
     a.B = B; a.u_cap = u_cap; a.tp_max = tp_max; a.V = V; a.blank = d.blank_id; a.steps = steps;
+    a.row_utt = row_utt; a.n_utt = n_utt;
     if (k2) st.unk = rs_k2_unk_id(ctx);
     const int zstride = rs_joint_zstride(d);
 
@@ -270,6 +289,10 @@ int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t
     hipLaunchKernelGGL(scores_plan_kernel, dim3(1), dim3(256), 0, s, a);
     RS_HIP(ctx, hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, s));
     RS_HIP(ctx, hipStreamSynchronize(s));
+    if (row_utt && info[3])
+        return rs_fail(ctx, RS_EINVAL, "token scores: row_utt %s (nothing was scored)",
+                       (info[3] & RS_ROWS_BAD_UTT) ? "names an utterance outside 0..B-1 (-1 skips a row)"
+                       : (info[3] & RS_ROWS_DECREASE) ? "decreases" : "gives one utterance more rows than RS_ALIGN_ROWS_PER_UTT_MAX");
     const int n_rows = info[0], longest = info[1];
     if (n_rows < 0 || (long long)n_rows > (long long)B * u_cap || longest < 0 || longest > u_cap)
         return rs_fail(ctx, RS_ESTATE, "token scores: inconsistent plan");
@@ -303,4 +326,19 @@ int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t
     prof.end();
     if (info[2]) return rs_fail(ctx, RS_EINVAL, "token scores: a count outside 0..u_cap, a frame outside its utterance or an id outside the vocabulary (its slot is NaN)");
     return RS_OK;
+}
+
+int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
+                              const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
+                              void* workspace, size_t workspace_bytes, hipStream_t s) {
+    return scores_run(ctx, joint_enc, enc_lens, B, tp_max, nullptr, B, ids, frames, n_ids, u_cap, steps, logp, top1, workspace,
+                      workspace_bytes, s);
+}
+
+int rs_rnnt_token_scores_rows_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max,
+                                   const int32_t* row_utt, int R, const int32_t* ids, const int32_t* frames, const int32_t* n_ids,
+                                   int u_cap, int steps, float* logp, int32_t* top1, void* workspace, size_t workspace_bytes,
+                                   hipStream_t s) {
+    return scores_run(ctx, joint_enc, enc_lens, B, tp_max, row_utt, R, ids, frames, n_ids, u_cap, steps, logp, top1, workspace,
+                      workspace_bytes, s);
 }

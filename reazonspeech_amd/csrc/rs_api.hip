@@ -37,6 +37,15 @@ int rs_rnnt_align_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_l
 int rs_rnnt_token_scores_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* ids,
                               const int32_t* frames, const int32_t* n_ids, int u_cap, int steps, float* logp, int32_t* top1,
                               void* workspace, size_t workspace_bytes, hipStream_t s);
+size_t rs_rnnt_align_rows_workspace_bytes_impl(const rs_ctx* ctx, int R, int tp_max, int u_cap);
+int rs_rnnt_align_rows_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* row_utt,
+                            int R, const int32_t* ids, const int32_t* n_ids, int u_cap, int one_per_frame, int no_sharing,
+                            float* loglik, float* best, int32_t* frames, float* logp, int64_t* stats, void* workspace,
+                            size_t workspace_bytes, hipStream_t s);
+int rs_rnnt_token_scores_rows_impl(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max,
+                                   const int32_t* row_utt, int R, const int32_t* ids, const int32_t* frames, const int32_t* n_ids,
+                                   int u_cap, int steps, float* logp, int32_t* top1, void* workspace, size_t workspace_bytes,
+                                   hipStream_t s);
 size_t rs_ctc_align_workspace_bytes_impl(int B, int tp_max, int c_max);
 int rs_ctc_align_impl(rs_ctx* ctx, const float* probs, int ld, const int32_t* enc_lens, int B, int tp_max, const int32_t* gt,
                       const int32_t* gt_lens, int c_max, int S, int blank, int32_t* frames, int32_t* status, void* ws, hipStream_t s);
@@ -763,6 +772,59 @@ int rs_rnnt_align(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, 
     if (workspace_bytes < least) return rs_fail(ctx, RS_EINVAL, "align: workspace %zu < %zu", workspace_bytes, least);
     return rs_rnnt_align_impl(ctx, joint_enc, enc_lens, B, tp_max, ids, n_ids, u_cap, (flags & RS_ALIGN_ONE_PER_FRAME) != 0, loglik, best,
                               frames, logp, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- several texts per utterance: the row-to-utterance map of both teacher-forced entries ----
+size_t rs_rnnt_align_rows_workspace_bytes(const rs_ctx* ctx, int B, int R, int tp_max, int u_cap) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_align_rows_workspace_bytes, 0);
+    if (!token_scores_ctx_ok(ctx) || B <= 0 || R <= 0 || tp_max < 0 || u_cap < 0 || u_cap > RS_ALIGN_U_CAP_MAX) return 0;
+    return rs_rnnt_align_rows_workspace_bytes_impl(ctx, R, tp_max, u_cap);
+}
+
+int rs_rnnt_align_rows(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* row_utt, int R,
+                       const int32_t* ids, const int32_t* n_ids, int u_cap, int flags, float* loglik, float* best, int32_t* frames,
+                       float* logp, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_align_rows);
+    if (!token_scores_ctx_ok(ctx)) return rs_fail(ctx, RS_EINVAL, "align rows: the context is not finalized");
+    if (B < 0 || R < 0 || tp_max < 0 || u_cap < 0) return rs_fail(ctx, RS_EINVAL, "align rows: negative size");
+    if (flags & ~(RS_ALIGN_ONE_PER_FRAME | RS_ALIGN_NO_SHARING)) return rs_fail(ctx, RS_EINVAL, "align rows: unknown flag %d", flags);
+    if (u_cap > RS_ALIGN_U_CAP_MAX) return rs_fail(ctx, RS_EINVAL, "align rows: u_cap %d is above %d", u_cap, RS_ALIGN_U_CAP_MAX);
+    if (stats) stats[0] = stats[1] = 0;
+    if (R == 0) return RS_OK;
+    if (B == 0) return rs_fail(ctx, RS_EINVAL, "align rows: rows without an utterance");
+    if (!joint_enc || !enc_lens || !row_utt || !ids || !n_ids || !loglik || !best || !frames || !logp || !workspace)
+        return rs_fail(ctx, RS_EINVAL, "align rows: null pointer");
+    const size_t least = rs_rnnt_align_rows_workspace_bytes_impl(ctx, R, tp_max, u_cap);
+    if (least == 0) return rs_fail(ctx, RS_EINVAL, "align rows: R x tp_max x (u_cap + 1) is too large");
+    if (workspace_bytes < least) return rs_fail(ctx, RS_EINVAL, "align rows: workspace %zu < %zu", workspace_bytes, least);
+    return rs_rnnt_align_rows_impl(ctx, joint_enc, enc_lens, B, tp_max, row_utt, R, ids, n_ids, u_cap, (flags & RS_ALIGN_ONE_PER_FRAME) != 0,
+                                   (flags & RS_ALIGN_NO_SHARING) != 0, loglik, best, frames, logp, stats, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
+
+size_t rs_rnnt_token_scores_rows_workspace_bytes(const rs_ctx* ctx, int B, int R, int u_cap) {
+    RS_GUARD_QUERY(ctx, rs_rnnt_token_scores_rows_workspace_bytes, 0);
+    if (!token_scores_ctx_ok(ctx) || B <= 0 || R <= 0 || u_cap < 0) return 0;
+    return rs_rnnt_token_scores_workspace_bytes_impl(ctx, R, u_cap);
+}
+
+int rs_rnnt_token_scores_rows(rs_ctx* ctx, const float* joint_enc, const int32_t* enc_lens, int B, int tp_max, const int32_t* row_utt,
+                              int R, const int32_t* ids, const int32_t* frames, const int32_t* n_ids, int u_cap, int flags, float* logp,
+                              int32_t* top1, void* workspace, size_t workspace_bytes, void* stream) {
+    RS_GUARD(ctx, rs_rnnt_token_scores_rows);
+    if (!token_scores_ctx_ok(ctx)) return rs_fail(ctx, RS_EINVAL, "token scores rows: the context is not finalized");
+    if (B < 0 || R < 0 || tp_max < 0 || u_cap < 0) return rs_fail(ctx, RS_EINVAL, "token scores rows: negative size");
+    if (flags & ~RS_SCORES_FRAMES_ARE_STEPS) return rs_fail(ctx, RS_EINVAL, "token scores rows: unknown flag %d", flags);
+    if (R == 0 || u_cap == 0) return RS_OK;
+    if (B == 0) return rs_fail(ctx, RS_EINVAL, "token scores rows: rows without an utterance");
+    if (!joint_enc || !enc_lens || !row_utt || !ids || !frames || !n_ids || !logp || !workspace)
+        return rs_fail(ctx, RS_EINVAL, "token scores rows: null pointer");
+    const size_t least = rs_rnnt_token_scores_workspace_bytes_impl(ctx, R, u_cap);
+    if (workspace_bytes < least) return rs_fail(ctx, RS_EINVAL, "token scores rows: workspace %zu < %zu", workspace_bytes, least);
+    if (tp_max == 0) return RS_OK;                         // no frames: no row has a token
+    return rs_rnnt_token_scores_rows_impl(ctx, joint_enc, enc_lens, B, tp_max, row_utt, R, ids, frames, n_ids, u_cap,
+                                          (flags & RS_SCORES_FRAMES_ARE_STEPS) != 0, logp, top1, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
 }
 
 size_t rs_ctc_align_workspace_bytes(const rs_ctx* ctx, int B, int tp_max, int c_max, int S) {

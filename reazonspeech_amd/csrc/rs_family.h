@@ -72,6 +72,10 @@ enum { RS_ANYTIME = 0, RS_FINAL = 1 };
     X(rs_rnnt_align_workspace_bytes, CZ, FINAL, RS_HINT_TRANSDUCER)                                                                   \
     /* ANYTIME, as rs_rnnt_token_scores: RS_EINVAL for a context that is not finalized; the entry tests that itself */               \
     X(rs_rnnt_align, CZ, ANYTIME, RS_HINT_TRANSDUCER)                                                                                 \
+    X(rs_rnnt_align_rows_workspace_bytes, CZ, FINAL, RS_HINT_TRANSDUCER)                                                              \
+    X(rs_rnnt_align_rows, CZ, ANYTIME, RS_HINT_TRANSDUCER)                                                                            \
+    X(rs_rnnt_token_scores_rows_workspace_bytes, CZ, FINAL, RS_HINT_TRANSDUCER)                                                       \
+    X(rs_rnnt_token_scores_rows, CZ, ANYTIME, RS_HINT_TRANSDUCER)                                                                     \
     X(rs_ctc_align_workspace_bytes, ALL, ANYTIME, "")                                                                                 \
     X(rs_ctc_align, ALL, ANYTIME, "")                                                                                                 \
     X(rs_ctc_find_blank, C, ANYTIME, "defined for a context with a CTC head (the ESPnet family) only")                                \

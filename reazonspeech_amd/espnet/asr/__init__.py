@@ -3,6 +3,7 @@ load_model, audio_from_numpy, audio_from_tensor, audio_from_path.  Additive: `tr
 from .interface import TranscribeConfig
 from .transcribe import transcribe, transcribe_batch, load_model
 from .align import align_text, align_text_batch      # additive, like transcribe_batch; reached by name, not listed in __all__
+from .align import score_texts, score_texts_batch    # additive: several candidate transcripts per audio on one lattice
 from .audio import audio_from_numpy, audio_from_tensor, audio_from_path
 
 __all__ = ["TranscribeConfig", "transcribe", "transcribe_batch", "load_model", "audio_from_numpy", "audio_from_tensor",

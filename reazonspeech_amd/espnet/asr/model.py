@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from ...runtime import fusion, k2_hotwords
+from ...runtime import rescore as rescoring
 from ...runtime.model import AsrModel
 
 PADDING = (16000, 8000)          # transcribe.py:10
@@ -65,6 +66,18 @@ class _NBestHypothesis:
     def __init__(self, yseq, score, norm_score, token_logprobs=None):
         self.yseq, self.score, self.norm_score = list(yseq), float(score), float(norm_score)
         self.token_logprobs = None if token_logprobs is None else list(token_logprobs)
+
+
+class _RescoredHypothesis(_NBestHypothesis):
+    """4th element of an n-best entry of a model loaded with `nbest=N, rescore=...`: an _NBestHypothesis with `log_likelihood` (log
+    P(text | audio) over ALL alignments of yseq: include/rs_asr.h rs_rnnt_align_rows), `alignment_log_prob` (the best alignment's own
+    score), `norm_log_likelihood` (log_likelihood / max(len(yseq), 1)) and `search_rank` (the entry's position in the search's own
+    list); the list is in descending order of the chosen key.  With `token_scores` on EVERY entry has `token_logprobs`."""
+
+    def __init__(self, yseq, score, norm_score, token_logprobs, log_likelihood, alignment_log_prob, search_rank):
+        super().__init__(yseq, score, norm_score, token_logprobs)
+        self.log_likelihood, self.alignment_log_prob, self.search_rank = float(log_likelihood), float(alignment_log_prob), int(search_rank)
+        self.norm_log_likelihood = rescoring.norm(self.log_likelihood, len(self.yseq))
 
 
 def check_nbest(nbest, beam_size):
@@ -124,8 +137,14 @@ class EspnetModel(fusion.ForwardedOptions):
 
     def __init__(self, cfg, state_dict, token_list, device="cuda", beam_size=1, max_pops=0, precision="bf16", segmentation="host",
                  resample="host", token_scores=False, nbest=None, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces",
-                 hotwords_file="", hotwords_score=1.5):
-        """ngram_lm_model / ngram_lm_alpha / ngram_lm_tokens: shallow fusion of a backoff n-gram language model into the default beam
+                 hotwords_file="", hotwords_score=1.5, rescore=None):
+        """rescore: None (default), "likelihood" or "norm_likelihood", with nbest >= 2 and the beam search: every entry of the list of
+        `model(speech)` / `recognize_batch(..., nbest=)` is scored by log P(text | audio) over ALL alignments on the device right
+        after the search (include/rs_asr.h rs_rnnt_align_rows on the lists, the entries' common prefixes computed once):
+        `hyp.log_likelihood`, `hyp.alignment_log_prob`, `hyp.norm_log_likelihood`, `hyp.search_rank`; the list is re-ranked by the key,
+        descending, ties in the search's order, so `transcribe` follows the re-ranked best.  The list of one of a window the greedy
+        fall-back decoded is scored too.  With token_scores every entry has `token_logprobs`.  Stored as `model.rescore`, settable.
+        ngram_lm_model / ngram_lm_alpha / ngram_lm_tokens: shallow fusion of a backoff n-gram language model into the default beam
         search ([UPSTREAM] the `lm_weight * lm_scores` slot of default_beam_search, which the reference closes with lm_weight = 0;
         include/rs_asr.h rs_rnnt_beam_lm): an ARPA text file (`.gz` allowed) or an `NgramLm` of runtime/ngram_lm.py, its weight, and
         how a word of the file names a token: "pieces" (default) = the symbols of token_list, '<space>' included, "ids" = decimal
@@ -143,6 +162,7 @@ class EspnetModel(fusion.ForwardedOptions):
         assert cfg.espnet and len(token_list) == cfg.vocab_size
         self.segmentation = segmentation
         n_best = check_nbest(nbest, beam_size)
+        rescoring.check(rescore, n_best, beam_size is not None and int(beam_size) > 1)
         check_fusion_keywords(beam_size, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, hotwords_file, hotwords_score)
         if beam_size is not None and int(beam_size) > 1:
             cfg = cfg.with_(decoding="beam", beam_size=int(beam_size), beam_score_norm=True, beam_max_pops=int(max_pops))
@@ -150,7 +170,7 @@ class EspnetModel(fusion.ForwardedOptions):
         self.cfg = cfg
         self.token_list = list(token_list)
         self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=0.0, precision=precision, resample=resample, token_scores=token_scores,
-                           nbest=n_best)
+                           nbest=n_best, rescore=rescore)
         self.device = self.am.device
         self.dtype = "float32"
         self._last_enc = self._last_ctc = None
@@ -215,21 +235,52 @@ class EspnetModel(fusion.ForwardedOptions):
         """window b of a search that ran with lists -> [(text, tokens, ids, hyp)], best first; a window the greedy fall-back decoded
         has the one entry"""
         out = []
+        rescored = getattr(res, "rescored", None)
         for r, (ids, _, score, norm) in enumerate(res.nbest[b]):
             tokens = [self.token_list[i] for i in ids]
-            lp = res.token_logprobs[b] if res.token_logprobs is not None and r == 0 else None
-            out.append((self.tokens2text(tokens), tokens, ids, _NBestHypothesis(ids, score, norm, lp)))
+            if rescored is not None:
+                ll, best, lp = rescored[b][r]
+                hyp = _RescoredHypothesis(ids, score, norm, lp, ll, best, r)
+            else:
+                lp = res.token_logprobs[b] if res.token_logprobs is not None and r == 0 else None
+                hyp = _NBestHypothesis(ids, score, norm, lp)
+            out.append((self.tokens2text(tokens), tokens, ids, hyp))
+        if rescored is not None:                           # re-ranked by full likelihood; ties keep the search's order
+            order = rescoring.order([e[3].log_likelihood for e in out], [len(e[2]) for e in out], self.am.rescore)
+            out = [out[r] for r in order]
         return out
 
-    def recognize_batch(self, waves, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm_alpha=None):
+    def _best(self, res):
+        """per window (ids, token log-probabilities or None) of the hypothesis a search returns: the search's own best — or, when the
+        lists were rescored (`model.rescore`), the re-ranked best, so that `recognize_batch`, `recognize_batch_scored` and with them
+        `transcribe_batch` give what `model(speech)[0]` and `transcribe` give"""
+        lp = res.token_logprobs
+        out = [(ids, lp[b] if lp is not None else None) for b, ids in enumerate(res.ids)]
+        if getattr(res, "rescored", None) is not None:
+            for b in range(len(out)):
+                entries = self._nbest_entries(res, b)
+                if entries:
+                    out[b] = (entries[0][2], entries[0][3].token_logprobs if lp is not None else None)
+        return out
+
+    def recognize_batch(self, waves, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm_alpha=None, rescore=None):
         """padded like the reference pads each window (np.pad(samples, PADDING), transcribe.py:69) -> [text].
         `isolate_overflow`: see `_search`.  `nbest=N`: per window the list of `model(speech)` instead — N tuples (text, tokens, ids,
         hyp), best first (one where the greedy fall-back decoded the window).  `hotwords`: one spec for every window (a string) or
-        a list with one entry per window (see `call_graphs`); `ngram_lm_alpha`: the LM's weight in this call (0 = without the LM)."""
+        a list with one entry per window (see `call_graphs`); `ngram_lm_alpha`: the LM's weight in this call (0 = without the LM).
+        `rescore`: n-best rescoring in this call: None = `model.rescore`, False = without it, a key = the lists of this call
+        re-ranked by it (ValueError for lists shorter than two)."""
+        if rescore is not None:                            # `model.rescore` for the call's duration
+            plan = self.am.rescore_plan(rescore, check_nbest(nbest, self.beam_size) if nbest is not None else None)
+            own, self.am.rescore = self.am.rescore, plan   # (a refused value raised above: the model's own option stays)
+            try:
+                return self.recognize_batch(waves, isolate_overflow, nbest, hotwords, ngram_lm_alpha)
+            finally:
+                self.am.rescore = own
         padded = [np.pad(np.asarray(w, np.float32), PADDING, mode="constant") for w in waves]
         fused = dict(hotwords=self.call_graphs(hotwords, len(padded)), ngram_lm=self.call_lm(ngram_lm_alpha))
         if nbest is None:
-            return [self.ids_to_text(ids) for ids in self._search(padded, isolate_overflow=isolate_overflow, **fused).ids]
+            return [self.ids_to_text(ids) for ids, _ in self._best(self._search(padded, isolate_overflow=isolate_overflow, **fused))]
         res = self._search(padded, isolate_overflow=isolate_overflow, nbest=check_nbest(nbest, self.beam_size) or 1, **fused)
         return [self._nbest_entries(res, b) for b in range(len(padded))]
 
@@ -240,7 +291,8 @@ class EspnetModel(fusion.ForwardedOptions):
                            hotwords=self.call_graphs(hotwords, len(waves)), ngram_lm=self.call_lm(ngram_lm_alpha))
         if res.token_logprobs is None:
             raise ValueError("recognize_batch_scored needs token_scores=True")
-        return [self.ids_to_text(ids) for ids in res.ids], list(zip(res.ids, res.token_logprobs))
+        best = self._best(res)
+        return [self.ids_to_text(ids) for ids, _ in best], best
 
     def _search(self, waves, max_batch=256, isolate_overflow=False, nbest=None, hotwords=None, ngram_lm=None):
         """the transducer search over a batch of (padded) windows.  Upstream's default beam search has no bound on the
@@ -263,9 +315,10 @@ class EspnetModel(fusion.ForwardedOptions):
         (NgramLm or None, alpha) for this call (`call_lm`).  Positive bonuses can make a frame take more pops: the ladder is the same,
         and the greedy fall-back runs without either and stays flagged `degraded`."""
         from ...runtime.capi import RsError, RS_EOVERFLOW
-        from ...runtime.model import DecodedBatch
+        from ...runtime.model import DecodedBatch, RescoredBatch
         am = self.am
         n_best = am.nbest if nbest is None else nbest
+        rescoring_on = am.cfg.decoding == "beam" and am.rescore_plan(None, n_best) is not None
         if am.cfg.decoding != "beam":
             res = am.transcribe_waveforms(waves)
             if n_best:                                    # (nbest = 1 with the greedy search: the one hypothesis as a list)
@@ -273,6 +326,8 @@ class EspnetModel(fusion.ForwardedOptions):
             return res
         bound = am.cfg.beam_max_pops or 16 * am.cfg.beam_size
         out = DecodedBatch([], [], [], [], [], token_logprobs=[] if am.token_scores else None, nbest=[] if n_best else None)
+        if rescoring_on:
+            out = RescoredBatch([], [], [], [], [], token_logprobs=out.token_logprobs, nbest=[], rescored=[])
         for lo in range(0, len(waves), max_batch):
             graphs = None if hotwords is None else list(hotwords[lo:lo + max_batch])
             buf = am.stage([np.asarray(w, np.float32) for w in waves[lo:lo + max_batch]], nbest=n_best,
@@ -298,6 +353,8 @@ class EspnetModel(fusion.ForwardedOptions):
                             out.nbest += one.nbest
                         if out.token_logprobs is not None:
                             out.token_logprobs += one.token_logprobs
+                        if rescoring_on:
+                            out.rescored += one.rescored
                     continue
                 if used is None:
                     import warnings
@@ -306,6 +363,8 @@ class EspnetModel(fusion.ForwardedOptions):
                     am.decode(am.ctx, buf, buf.ws, stream, decoding="greedy_batch")
                     used = "greedy_batch"
                 am.score(am.ctx, buf, stream, decoding=used)
+                if rescoring_on:                          # (the greedy fall-back's list of one is scored too)
+                    am.rescore_step(am.ctx, buf, stream, decoding=used, single=True)
                 res = am.collect(buf, decoding=used)
             out.ids += res.ids; out.frames += res.frames; out.enc_lens += res.enc_lens
             out.scores += res.scores if res.scores is not None else [float("nan")] * buf.B
@@ -314,6 +373,8 @@ class EspnetModel(fusion.ForwardedOptions):
                 out.token_logprobs += res.token_logprobs
             if out.nbest is not None:                     # (the greedy fall-back ran without lists: its one hypothesis each)
                 out.nbest += res.nbest if res.nbest is not None else [[(ids, fr, float("nan"), float("nan"))] for ids, fr in zip(res.ids, res.frames)]
+            if rescoring_on:
+                out.rescored += res.rescored
         return out
 
     def recognize(self, samples):

@@ -25,7 +25,7 @@ CHECKPOINT_ENV = "REAZONSPEECH_ESPNET_CHECKPOINT"
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None, max_pops=0, precision="bf16", synthetic=False,
                segmentation="host", resample="host", token_scores=False, nbest=None, ngram_lm_model=None, ngram_lm_alpha=0.0,
-               ngram_lm_tokens="pieces", hotwords_file="", hotwords_score=1.5):
+               ngram_lm_tokens="pieces", hotwords_file="", hotwords_score=1.5, rescore=None):
     """Load the ReazonSpeech ESPnet model onto a ROCm GPU (transcribe.py:12-32).
 
     Args:
@@ -65,6 +65,16 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         whose `hyp.score` and `hyp.norm_score` are NaN — the greedy search keeps no score; test with `math.isnan` before sorting.  N above the
         beam, or N > 1 with the greedy search, raises ValueError.
 
+      rescore (str): None (default), "likelihood" or "norm_likelihood", with `nbest >= 2`: every entry of the list is scored by
+        log P(text | audio) over ALL alignments, on the device right after the search (include/rs_asr.h rs_rnnt_align_rows: one
+        lattice per window, the entries' common prefixes computed once), and the list is re-ranked by it (or by it divided by
+        max(tokens, 1)), descending, ties in the search's order: `hyp.log_likelihood`, `hyp.alignment_log_prob`,
+        `hyp.norm_log_likelihood`, `hyp.search_rank` on the tuples of `model(speech)` / `recognize_batch`; `transcribe` and
+        `transcribe_batch` (both segmentations; `recognize_batch` without `nbest=` and `recognize_batch_scored` too) follow the
+        re-ranked best.  The list of one of a window the greedy fall-back decoded is scored too.  ValueError (before anything is
+        loaded) for another value, the greedy search or nbest < 2.  Stored as `model.rescore`, may be set later.
+        A batch whose lists are beyond one call's lattice bound is scored over several calls; only lists of more than 2047 labels per entry, or ONE utterance's lists beyond the bound, raise ValueError (window the audio).
+
       ngram_lm_model (str or NgramLm), ngram_lm_alpha (float), ngram_lm_tokens (str): shallow fusion of a backoff n-gram language
         model trained on the user's own text into the default beam search — [UPSTREAM] the `lm_weight * lm_scores` slot of
         default_beam_search, which the reference closes with lm_weight = 0 (include/rs_asr.h rs_rnnt_beam_lm).  An ARPA text file
@@ -86,7 +96,8 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
     from ...runtime.weights_espnet import synthetic_state_dict_espnet
     from .model import EspnetModel, synthetic_token_list, SEGMENTATION_MODES, check_nbest, check_fusion_keywords
     beam_known = beam_size if beam_size is not None else (1 if config is not None or synthetic else 20)
-    check_nbest(nbest, beam_known)                        # argument errors first
+    from ...runtime import rescore as rescoring
+    rescoring.check(rescore, check_nbest(nbest, beam_known), int(beam_known) > 1)       # argument errors first
     check_fusion_keywords(beam_known, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, hotwords_file, hotwords_score)
     fusion = dict(ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens, hotwords_file=hotwords_file,
                   hotwords_score=hotwords_score)
@@ -107,7 +118,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
         cfg, sd, tokens = read_espnet(checkpoint)
         return EspnetModel(cfg, sd, tokens, device=device, beam_size=20 if beam_size is None else beam_size, max_pops=max_pops,
                            precision=precision, segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest,
-                           **fusion)
+                           rescore=rescore, **fusion)
     cfg = config or ESPNET_CONFORMER_120M
     if config is None:
         if not (synthetic or os.environ.get("REAZONSPEECH_AMD_SYNTHETIC", "0") not in ("", "0")):
@@ -118,7 +129,7 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, beam_size=None
               "(`synthetic=True` / $REAZONSPEECH_AMD_SYNTHETIC): timings are valid, transcripts are meaningless.", file=sys.stderr, flush=True)
     return EspnetModel(cfg, synthetic_state_dict_espnet(cfg, seed), synthetic_token_list(cfg.vocab_size, seed), device=device,
                        beam_size=1 if beam_size is None else beam_size, max_pops=max_pops, precision=precision,
-                       segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest, **fusion)
+                       segmentation=segmentation, resample=resample, token_scores=token_scores, nbest=nbest, rescore=rescore, **fusion)
 
 
 def _windows(model, waveform, window):

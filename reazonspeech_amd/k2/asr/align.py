@@ -45,6 +45,33 @@ def align_text_batch(model, audios, texts, config=None):
                            res.feasible[i]) for i in range(len(waves))]
 
 
+def score_texts_batch(model, audios, texts_per_audio, config=None):
+    """Score several candidate transcripts per audio on one lattice each (include/rs_asr.h rs_rnnt_align_rows): `texts_per_audio[i]` is
+    a list of texts for `audios[i]`, each a string or a sequence of token ids, tokenised as `align_text` tokenises.  Every audio goes
+    through the front-end and the encoder ONCE, and the texts of an audio share the lattice cells of their common prefixes.
+
+    Returns:
+      list[list[AlignedTranscribeResult]]: per audio, one result per text in the order given; each equals what `align_text` returns
+      for that (audio, text) pair, field for field.
+    """
+    if len(audios) != len(texts_per_audio):
+        raise ValueError(f"score_texts_batch: {len(audios)} audios but {len(texts_per_audio)} lists of texts")
+    labels = [[text_ids(model, t) for t in texts] for texts in texts_per_audio]
+    waves = [a.waveform for a in _prepare_batch(model, audios)]
+    res, _ = model.am.align_candidates(waves, labels)
+    return [[aligned_result(model, ids, r.frames[j], r.token_logprobs[j], r.log_likelihood[j], r.alignment_log_prob[j], r.feasible[j])
+             for j, ids in enumerate(labels[i])] for i, r in enumerate(res)]
+
+
+def score_texts(model, audio, texts, config=None):
+    """`score_texts_batch` for one audio: its candidate transcripts scored by full likelihood, in the order given.
+
+    Returns:
+      list[AlignedTranscribeResult]
+    """
+    return score_texts_batch(model, [audio], [texts], config)[0]
+
+
 def align_text(model, audio, text, config=None):
     """Place `text` on `audio` and score it: when each token was spoken (the best alignment), log P(text | audio) over all
     alignments, and the best alignment's own score.

@@ -58,7 +58,8 @@ def resolve_checkpoint(language, precision, checkpoint=None):
 
 def load_model(device=None, precision="fp32", language="ja", checkpoint=None, config=None, seed=0, compute=None, synthetic=False,
                decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, resample="host", hotwords_file="",
-               hotwords_score=1.5, hotwords=None, token_scores=False, nbest=0, ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="pieces"):
+               hotwords_score=1.5, hotwords=None, token_scores=False, nbest=0, rescore=None, ngram_lm_model=None, ngram_lm_alpha=0.0,
+               ngram_lm_tokens="pieces"):
     """Load the ReazonSpeech k2 model onto a ROCm GPU (huggingface.py:16-83).
 
     Args:
@@ -108,6 +109,14 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
         device by the rule that picks the winner (include/rs_asr.h rs_rnnt_mbs_nbest): results with tokens / timestamps / text /
         log_prob; entry 0 is the result itself; fewer than N when the last set is smaller.  0 (default) = off, today's objects.
         N above `max_active_paths`, or N > 1 with "greedy_search", raises ValueError.  Stored as `model.nbest`, may be set later.
+      rescore (str): None (default), "likelihood" or "norm_likelihood", with nbest >= 2: every entry of the list is scored by
+        log P(text | audio) over ALL alignments on the device right after the search (include/rs_asr.h rs_rnnt_align_rows: one
+        lattice per utterance, the entries' common prefixes computed once) and the list is re-ranked by it (or by it divided by
+        max(tokens, 1)), descending, ties in the search's order: `stream.result.nbest[k].log_likelihood`, `.alignment_log_prob`,
+        `.norm_log_likelihood`, `.search_rank`; `transcribe(...)` returns a `RescoredTranscribeResult` whose entry 0 is the result
+        itself; with `token_scores=True` every entry carries its token log-probabilities.  ValueError for another value,
+        "greedy_search" or nbest < 2.  Stored as `model.rescore`, may be set later.
+        A batch whose lists are beyond one call's lattice bound is scored over several calls; only lists of more than 2047 labels per entry, or ONE utterance's lists beyond the bound, raise ValueError (window the audio).
       resample (str): where `transcribe` / `transcribe_batch` normalise input at another rate than 16 kHz or with several channels
         (`norm_audio`): "host" (default) = scipy / soxr per utterance as before; "device" = one HIP launch per (rate, channel count)
         group of a call (`AsrModel.resample_batch`, rs_resample; the host path's Kaiser filter).  Stored as `model.resample`;
@@ -130,12 +139,15 @@ def load_model(device=None, precision="fp32", language="ja", checkpoint=None, co
     from .model import search_config
     search_config(ZIPFORMER_159M, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
                   ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, nbest)
+    from ...runtime import rescore as rescoring
+    rescoring.check(rescore, nbest, decoding_method == "modified_beam_search")
     from ...runtime import fusion
     fusion.check_file("ngram_lm_model", ngram_lm_model)
     fusion.check_file("hotwords_file", hotwords_file)
     search = dict(decoding_method=decoding_method, max_active_paths=max_active_paths, blank_penalty=blank_penalty, resample=resample,
                   hotwords_file=hotwords_file, hotwords_score=hotwords_score, hotwords=hotwords, token_scores=token_scores,
-                  ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens, nbest=nbest)
+                  ngram_lm_model=ngram_lm_model, ngram_lm_alpha=ngram_lm_alpha, ngram_lm_tokens=ngram_lm_tokens, nbest=nbest,
+                  rescore=rescore)
     if device is None:
         device = "cuda"
     if not str(device).startswith("cuda"):

@@ -13,6 +13,7 @@ import re
 import numpy as np
 
 from ...runtime import fusion, k2_hotwords
+from ...runtime import rescore as rescoring
 from ...runtime.model import AsrModel
 
 _BYTE = re.compile(r"^<0x([0-9A-Fa-f]{2})>$")
@@ -28,6 +29,10 @@ class _Result:
         # token_scores: the ids behind `tokens` and the log-probability of each ([UPSTREAM] sherpa-onnx keeps per-token log-probs in
         # its hypotheses); None with the option off
         self.token_ids, self.token_log_probs = token_ids, token_log_probs
+        # rescore: log P(text | audio) over all alignments, the best alignment's score, the former / max(tokens, 1) and the position
+        # in the search's own list — on every entry of `nbest`, which is then in descending order of the chosen key; None when off
+        self.log_likelihood = self.alignment_log_prob = self.norm_log_likelihood = self.search_rank = None
+        self.rescore_key = None          # the key the list was re-ranked by (also on a result whose list is empty), None when off
 
 
 class _Stream:
@@ -113,8 +118,14 @@ class K2Model(fusion.ForwardedOptions):
     def __init__(self, cfg, state_dict, tokens, device="cuda", pad_seconds=0.0, precision="bf16", qweights=None,
                  decoding_method="greedy_search", max_active_paths=4, blank_penalty=0.0, pos_cap=None, resample="host",
                  hotwords_file="", hotwords_score=1.5, hotwords=None, token_scores=False, ngram_lm_model=None, ngram_lm_alpha=0.0,
-                 ngram_lm_tokens="pieces", nbest=0):
-        """nbest: this project's addition (sherpa-onnx returns one hypothesis per stream): N >= 1 with the modified beam search makes
+                 ngram_lm_tokens="pieces", nbest=0, rescore=None):
+        """rescore: None (default), "likelihood" or "norm_likelihood", with nbest >= 2 and the modified beam search: every entry of
+        `stream.result.nbest` gets `log_likelihood` (log P(text | audio) over ALL alignments, one label per frame as the search
+        moves; include/rs_asr.h rs_rnnt_align_rows on the lists, right after the search), `alignment_log_prob`,
+        `norm_log_likelihood` and `search_rank`; the list is re-ranked by the key, descending, ties in the search's order, and
+        `stream.result` is its new entry 0.  With token_scores every entry carries `token_log_probs`.  Stored as `model.rescore`,
+        may be set later.  ValueError (before anything is loaded) for another value, greedy_search or nbest < 2.
+        nbest: this project's addition (sherpa-onnx returns one hypothesis per stream): N >= 1 with the modified beam search makes
         `stream.result.nbest` the N best hypotheses of the search's last set, ranked on the device by log_prob / len(ys) as the
         winner is chosen (include/rs_asr.h rs_rnnt_mbs_nbest) — results with tokens / timestamps / text / log_prob / norm_log_prob,
         entry 0 the result itself, fewer than N when the last set is smaller.  0 (default): `result.nbest` is None.  N above
@@ -148,6 +159,7 @@ class K2Model(fusion.ForwardedOptions):
         assert cfg.family == "k2" and len(tokens) == cfg.vocab_size
         cfg = search_config(cfg, decoding_method, max_active_paths, blank_penalty, hotwords_file, hotwords_score, hotwords,
                             ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens, nbest)
+        rescoring.check(rescore, nbest, cfg.decoding == "modified_beam_search")
         self.cfg = cfg
         self.tokens = list(tokens)
         self.hotwords_score = float(hotwords_score)
@@ -155,7 +167,7 @@ class K2Model(fusion.ForwardedOptions):
         # the reference pads with np.pad before handing the samples over (transcribe.py:24); a stream's samples arrive padded
         cap = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
         self.am = AsrModel(cfg, state_dict, None, device=device, pad_seconds=pad_seconds, precision=precision, qweights=qweights, resample=resample, token_scores=token_scores,
-                           nbest=nbest if cfg.decoding == "modified_beam_search" else 0, **cap)
+                           nbest=nbest if cfg.decoding == "modified_beam_search" else 0, rescore=rescore, **cap)
         self.device = self.am.device
         if self.hotwords is not None:
             self.am.hotword_set((self.hotwords,))         # checked and uploaded once, at load
@@ -194,7 +206,17 @@ class K2Model(fusion.ForwardedOptions):
         res = self.am.transcribe_waveforms([st.samples for st in streams], hotwords=stream_graphs(self.hotwords, streams), ngram_lm=lm)
         for k, (st, ids, frames) in enumerate(zip(streams, res.ids, res.frames)):
             st.result = self.convert(ids, frames, res.token_logprobs[k] if res.token_logprobs is not None else None)
-            if res.nbest is not None:                     # the ranked list; entry 0 is the result itself
+            if getattr(res, "rescored", None) is not None and not res.nbest[k]:  # no hypothesis was ranked: an empty list of the same kind
+                st.result.nbest, st.result.rescore_key = [], self.am.rescore
+            elif getattr(res, "rescored", None) is not None:                     # the list re-ranked by full likelihood
+                entries = [self.convert(y, fr, lp) for (y, fr, _, _), (_, _, lp) in zip(res.nbest[k], res.rescored[k])]
+                for rank, (r, (y, _, lp, norm), (ll, best, _)) in enumerate(zip(entries, res.nbest[k], res.rescored[k])):
+                    r.log_prob, r.norm_log_prob, r.search_rank = lp, norm, rank
+                    r.log_likelihood, r.alignment_log_prob, r.norm_log_likelihood = ll, best, rescoring.norm(ll, len(y))
+                order = rescoring.order([r.log_likelihood for r in entries], [len(y) for y, _, _, _ in res.nbest[k]], self.am.rescore)
+                st.result = entries[order[0]]
+                st.result.nbest, st.result.rescore_key = [entries[r] for r in order], self.am.rescore
+            elif res.nbest is not None:                   # the ranked list; entry 0 is the result itself
                 entries = [self.convert(y, fr) for y, fr, _, _ in res.nbest[k][1:]]
                 for r, (_, _, lp, norm) in zip([st.result] + entries, res.nbest[k]):
                     r.log_prob, r.norm_log_prob = lp, norm

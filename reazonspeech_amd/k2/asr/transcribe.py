@@ -4,7 +4,8 @@ import warnings
 
 from ...runtime import fusion
 from ...runtime.resample import norm_batch
-from .interface import AudioData, TranscribeConfig, TranscribeResult, ScoredTranscribeResult, NBestTranscribeResult, Subword, mean_confidence
+from .interface import (AudioData, TranscribeConfig, TranscribeResult, ScoredTranscribeResult, NBestTranscribeResult, RescoredTranscribeResult,
+                        Subword, mean_confidence)
 from .audio import pad_audio, norm_audio, SAMPLERATE
 
 PAD_SECONDS = 0.9
@@ -39,6 +40,10 @@ def _entry(r):
     subwords = [Subword(token=t, seconds=s) for t, s in zip(r.tokens, r.timestamps)]
     lp = r.token_log_probs
     scored = {} if lp is None else dict(token_ids=list(r.token_ids), token_logprobs=list(lp), confidence=mean_confidence(lp), subword_logprobs=list(lp))
+    if getattr(r, "log_likelihood", None) is not None:        # a model loaded with rescore=: the list was re-ranked by full likelihood
+        return RescoredTranscribeResult(r.text, subwords, log_prob=r.log_prob, norm_log_prob=r.norm_log_prob, log_likelihood=r.log_likelihood,
+                                        alignment_log_prob=r.alignment_log_prob, norm_log_likelihood=r.norm_log_likelihood,
+                                        search_rank=r.search_rank, **scored)
     return NBestTranscribeResult(r.text, subwords, log_prob=r.log_prob, norm_log_prob=r.norm_log_prob, **scored)
 
 
@@ -46,7 +51,7 @@ def _result(stream):
     if getattr(stream.result, "nbest", None) is not None:     # a model loaded with nbest=N: entry 0 is the result itself
         entries = [_entry(r) for r in stream.result.nbest]
         if not entries:                                        # no frames: no hypothesis was ranked
-            return NBestTranscribeResult(stream.result.text, [])
+            return (RescoredTranscribeResult if getattr(stream.result, "rescore_key", None) else NBestTranscribeResult)(stream.result.text, [])
         head = _entry(stream.result.nbest[0])
         head.nbest = entries
         return head

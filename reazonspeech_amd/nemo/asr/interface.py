@@ -93,6 +93,21 @@ class NBestTranscribeResult(TranscribeResult):
     segment_confidence: Optional[List[float]] = None
 
 
+@dataclass
+class RescoredTranscribeResult(NBestTranscribeResult):
+    """What `transcribe()` returns from a model loaded with `nbest=N, rescore="likelihood" | "norm_likelihood"` (additive): an
+    NBestTranscribeResult whose list was re-ranked by full likelihood.  Every entry has `log_likelihood` = log P(text | audio) summed
+    over ALL alignments of its tokens (include/rs_asr.h rs_rnnt_align_rows; what `align_text` gives for that text),
+    `alignment_log_prob` = the best alignment's own score, `norm_log_likelihood` = log_likelihood / max(tokens, 1) and `search_rank`
+    = its position in the search's own list.  The list is in descending order of the chosen key (ties in the search's order) and
+    the result itself is its entry 0.  With `token_scores=True` every entry carries the token fields, not entry 0 alone.  With
+    `raw_hypothesis` the four fields are also attributes of the Hypothesis objects of `hypothesis.n_best_hypotheses`."""
+    log_likelihood: Optional[float] = None
+    alignment_log_prob: Optional[float] = None
+    norm_log_likelihood: Optional[float] = None
+    search_rank: Optional[int] = None
+
+
 class NBestHypotheses:
     """[UPSTREAM] NeMo's NBestHypotheses: what `raw_hypothesis` carries when the lists are on"""
 

@@ -62,7 +62,7 @@ SYNTHETIC_ENV = "REAZONSPEECH_AMD_SYNTHETIC"
 
 def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, decoding=None, beam_size=None,
                precision="bf16", synthetic=False, resample="host", token_scores=False, nbest=0, hotwords_file="", hotwords_score=1.5, hotwords=None,
-               ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="nemo"):
+               ngram_lm_model=None, ngram_lm_alpha=0.0, ngram_lm_tokens="nemo", rescore=None):
     """Load the ReazonSpeech FastConformer-RNNT model onto a ROCm GPU.
 
     Args:
@@ -97,6 +97,14 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
         label sequences kept once, ranked inside the search's selection kernel (rs_rnnt_alsd_nbest); entry 0 is the result itself;
         with `raw_hypothesis`, `hypothesis.n_best_hypotheses`.  0 (default): today's objects.  N above the beam, or N > 1 with a
         greedy decoding, raises ValueError.  Stored as `model.nbest`; `transcribe(..., nbest=N)` takes a count for one call.
+      rescore (str): None (default), "likelihood" or "norm_likelihood", with `nbest >= 2`: every entry of the n-best list is scored
+        by log P(text | audio) over ALL alignments, on the device right after the search (include/rs_asr.h rs_rnnt_align_rows: one
+        lattice per utterance, the entries' common prefixes computed once), and the list is re-ranked by that (or by that divided
+        by max(tokens, 1)), descending, ties in the search's order.  Results are `RescoredTranscribeResult` (interface.py): each entry
+        has `log_likelihood`, `alignment_log_prob`, `norm_log_likelihood` and `search_rank`; the result itself is the new entry 0;
+        with `token_scores=True` EVERY entry carries its token log-probabilities.  Needs `decoding="alsd"` and `nbest >= 2`
+        (ValueError before anything is loaded).  Stored as `model.rescore`, may be set later; `transcribe(..., rescore=)` per call.
+        A batch whose lists are beyond one call's lattice bound is scored over several calls; only lists of more than 2047 labels per entry, or ONE utterance's lists beyond the bound, raise ValueError (window the audio).
       token_scores (bool): every result is a `ScoredTranscribeResult` (interface.py): the log-probability of every emitted token
         under the model's own distribution, per subword, and confidences per segment and utterance (exp of the mean) — computed on
         the device right after the search (rs_rnnt_token_scores), valid with every `precision` and `decoding`; with
@@ -134,6 +142,8 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     from ...runtime.resample import check_mode
 
     check_mode(resample)
+    from ...runtime import rescore as rescoring
+    rescoring.check(rescore, nbest, decoding is None or str(decoding) in ("alsd", "beam"))
     fusion.check_file("hotwords_file", hotwords_file)
     if decoding is not None:               # (a checkpoint's own strategy is only known once it is read: checked again below)
         fusion.check_hotword_keywords(fusion.NEMO, str(decoding), hotwords_file, hotwords_score, hotwords)
@@ -174,7 +184,8 @@ def load_model(device=None, checkpoint=None, config=None, seed=0, pos_cap=None, 
     kw = {} if pos_cap is None else {"pos_cap": int(pos_cap)}
     has_hotwords = fusion.check_hotword_keywords(fusion.NEMO, cfg.decoding, hotwords_file, hotwords_score, hotwords)
     fusion.check_lm_keywords(fusion.NEMO, cfg.decoding, ngram_lm_model, ngram_lm_alpha, ngram_lm_tokens)      # the checkpoint's own strategy is known now
-    model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, nbest=nbest, **kw)
+    model = AsrModel(cfg, sd, tokenizer, device=device, pad_seconds=PAD_SECONDS, precision=precision, resample=resample, token_scores=token_scores, nbest=nbest, rescore=rescore,
+                     **kw)
     model.hotwords_score = float(hotwords_score)
     if has_hotwords:
         model.hotwords = _model_graph(model, hotwords, hotwords_file)                  # the model's graph (None = nothing left to bias)
@@ -235,6 +246,36 @@ def _nbest_result(ret, score, norm):
     return NBestTranscribeResult(ret.text, ret.subwords, ret.segments, ret.hypothesis, score=score, norm_score=norm, **scored)
 
 
+def _rescored(model, decoded, k, hyp, config):
+    """utterance k of a `RescoredBatch` -> the RescoredTranscribeResult: every entry scored, the list re-ranked by `model.rescore`
+    (descending, ties in the search's order), the best entry's fields on the result itself"""
+    from ...runtime import rescore as rescoring
+    from .interface import NBestHypotheses, RescoredTranscribeResult
+    entries, hyps = [], []
+    for r, ((y, fr, score, norm), (ll, best, lp)) in enumerate(zip(decoded.nbest[k], decoded.rescored[k])):
+        h = hyp if r == 0 else Hypothesis.from_alsd(y, [f + idx for idx, f in enumerate(fr)], model.cfg.blank_id)
+        h.score = score
+        if lp is not None:
+            h.token_confidence = [float(np.exp(v)) for v in lp]
+        ret = decode_hypothesis(model, h, lp)
+        scored = {f: getattr(ret, f) for f in ("token_ids", "token_logprobs", "confidence", "subword_logprobs", "segment_confidence") if hasattr(ret, f)}
+        extra = dict(log_likelihood=ll, alignment_log_prob=best, norm_log_likelihood=rescoring.norm(ll, len(y)), search_rank=r)
+        for f, v in extra.items():
+            setattr(h, f, v)
+        entries.append(RescoredTranscribeResult(ret.text, ret.subwords, ret.segments, h if config.raw_hypothesis else None, score=score,
+                                                norm_score=norm, **scored, **extra))
+        hyps.append(h)
+    if not entries:
+        return None
+    order = rescoring.order([e.log_likelihood for e in entries], [len(y) for y, _, _, _ in decoded.nbest[k]], model.rescore)
+    entries, hyps = [entries[r] for r in order], [hyps[r] for r in order]
+    head = RescoredTranscribeResult(**{f: getattr(entries[0], f) for f in entries[0].__dataclass_fields__})
+    head.nbest = entries
+    if config.raw_hypothesis:
+        head.hypothesis = NBestHypotheses(hyps)
+    return head
+
+
 def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alpha=None, nbest=None):
     """`transcribe_batch` with the hotwords resolved: `graphs` = None, or one HotwordGraph / None per audio; `ngram_lm_alpha`: the
     n-gram LM's weight in this call (None = the model's value, 0 = without the LM; a value with no LM loaded raises ValueError)"""
@@ -263,7 +304,14 @@ def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alph
             ret = decode_hypothesis(model, hyp, lp)
             if config.raw_hypothesis:
                 ret.hypothesis = hyp
-            if decoded.nbest is not None:                 # the ranked list: entry 0 is the result itself
+            rescored = _rescored(model, decoded, k, hyp, config) if getattr(decoded, "rescored", None) is not None else None
+            if rescored is not None:                      # the list re-ranked by full likelihood: its best entry is the result
+                ret = rescored
+            elif getattr(decoded, "rescored", None) is not None:      # no hypothesis was ranked: the same type, an empty list
+                from .interface import RescoredTranscribeResult
+                scored = {f: getattr(ret, f) for f in ("token_ids", "token_logprobs", "confidence", "subword_logprobs", "segment_confidence") if hasattr(ret, f)}
+                ret = RescoredTranscribeResult(ret.text, ret.subwords, ret.segments, ret.hypothesis, **scored)
+            elif decoded.nbest is not None:               # the ranked list: entry 0 is the result itself
                 from .interface import NBestHypotheses
                 entries, hyps = [], []
                 for r, (y, fr, score, norm) in enumerate(decoded.nbest[k]):
@@ -290,7 +338,7 @@ def _transcribe_graphs(model, audios, config, distributed, graphs, ngram_lm_alph
     return results
 
 
-def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nbest=None):
+def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nbest=None, rescore=None):
     """Inference of one utterance (transcribe.py:30-60).
 
     Args:
@@ -304,6 +352,8 @@ def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nb
         nbest: entries of the n-best list in this call: None = `model.nbest`, 0 = without the list, N = the N best finished
             hypotheses (`NBestTranscribeResult.nbest`; needs `decoding="alsd"` and N <= beam_size, ValueError otherwise).
             `transcribe_batch` decodes with `model.nbest`.
+        rescore: n-best rescoring in this call: None = `model.rescore`, False = without it, "likelihood" / "norm_likelihood" = the
+            list of this call re-ranked by that key (needs a list of at least two: ValueError otherwise; see `load_model`)
 
     Returns:
         TranscribeResult
@@ -311,4 +361,11 @@ def transcribe(model, audio, config=None, hotwords=None, ngram_lm_alpha=None, nb
     if config is None:
         config = TranscribeConfig()
     graphs = _call_graphs(model, None if hotwords is None else [hotwords], 1)     # the argument is ONE audio's entry, whatever its type
-    return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha, nbest)[0]
+    if rescore is None:
+        return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha, nbest)[0]
+    plan = model.rescore_plan(rescore, nbest)             # (ValueError before anything runs, and the model's own option stays)
+    own, model.rescore = model.rescore, plan
+    try:
+        return _transcribe_graphs(model, [audio], config, False, graphs, ngram_lm_alpha, nbest)[0]
+    finally:
+        model.rescore = own

@@ -24,7 +24,9 @@ ALSD_SCORE_NORM, ALSD_MERGE = 1, 2
 MBS_LENGTH_NORM = 1
 SCORES_FRAMES_ARE_STEPS = 1
 ALIGN_ONE_PER_FRAME = 1
+ALIGN_NO_SHARING = 2
 ALIGN_U_CAP_MAX = 2047
+ALIGN_ROWS_PER_UTT_MAX = 64
 PROF_GEMM, PROF_ATTN, PROF_FRONTEND, PROF_DECODE, PROF_ELEMENTWISE, PROF_SUBSAMPLE = 1, 2, 4, 8, 16, 32
 
 # every symbol include/rs_asr.h declares (tests/test_capi_exports.py checks the .so exports them)
@@ -44,6 +46,7 @@ EXPORTS = [
     "rs_rnnt_beam_lm", "rs_rnnt_beam_lm_workspace_bytes",
     "rs_rnnt_alsd_nbest", "rs_rnnt_alsd_nbest_workspace_bytes",
     "rs_rnnt_token_scores", "rs_rnnt_token_scores_workspace_bytes", "rs_rnnt_align", "rs_rnnt_align_workspace_bytes",
+    "rs_rnnt_align_rows", "rs_rnnt_align_rows_workspace_bytes", "rs_rnnt_token_scores_rows", "rs_rnnt_token_scores_rows_workspace_bytes",
     "rs_gemm_f32", "rs_relpos_attention_f32", "rs_glu_dwconv_silu_f32", "rs_profile_read_launches", "rs_encoder_set_ctc_out",
     "rs_gemm_i8q",
     "rs_k2_create", "rs_k2_encoder_set_taps",
@@ -273,6 +276,14 @@ def load():
     lib.rs_rnnt_align_workspace_bytes.restype = c_size_t
     lib.rs_rnnt_align.argtypes = [vp, vp, vp, c_int, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, vp, c_size_t, vp]
     lib.rs_rnnt_align.restype = c_int
+    lib.rs_rnnt_align_rows_workspace_bytes.argtypes = [vp, c_int, c_int, c_int, c_int]
+    lib.rs_rnnt_align_rows_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_align_rows.argtypes = [vp, vp, vp, c_int, c_int, vp, c_int, vp, vp, c_int, c_int, vp, vp, vp, vp, vp, vp, c_size_t, vp]
+    lib.rs_rnnt_align_rows.restype = c_int
+    lib.rs_rnnt_token_scores_rows_workspace_bytes.argtypes = [vp, c_int, c_int, c_int]
+    lib.rs_rnnt_token_scores_rows_workspace_bytes.restype = c_size_t
+    lib.rs_rnnt_token_scores_rows.argtypes = [vp, vp, vp, c_int, c_int, vp, c_int, vp, vp, vp, c_int, c_int, vp, vp, vp, c_size_t, vp]
+    lib.rs_rnnt_token_scores_rows.restype = c_int
     alsd = [vp, vp, vp, c_int, c_int, c_int, c_double, c_int, c_int, c_int, vp, vp, vp, vp]
     lib.rs_rnnt_alsd.argtypes = alsd + tail
     lib.rs_rnnt_alsd_hotwords.argtypes = alsd + hw_args + tail
@@ -717,6 +728,50 @@ class Context:
         self.check(self.lib.rs_rnnt_align(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, _ptr(ids), _ptr(n_ids), ids.shape[1],
                                           ALIGN_ONE_PER_FRAME if one_per_frame else 0, _ptr(loglik), _ptr(best), _ptr(frames), _ptr(logp),
                                           _ptr(ws), ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes), c_void_p(stream)))
+
+    def align_rows_workspace_bytes(self, B, R, tp_max, u_cap):
+        """the MINIMUM workspace of `rnnt_align_rows` for R text rows over B utterances, sized without sharing"""
+        n = self.lib.rs_rnnt_align_rows_workspace_bytes(self._h, int(B), int(R), int(tp_max), int(u_cap))
+        if n == 0:
+            raise RuntimeError(f"rs_rnnt_align_rows_workspace_bytes: invalid arguments (a finalized transducer context, B > 0, R > 0, "
+                               f"tp_max >= 0, 0 <= u_cap <= {ALIGN_U_CAP_MAX}, R x tp_max x (u_cap + 1) < 2^30)")
+        return n
+
+    def rnnt_align_rows(self, joint_enc, enc_lens, B, tp_max, row_utt, ids, n_ids, loglik, best, frames, logp, ws, stream,
+                        one_per_frame=False, share=True, ws_bytes=None):
+        """several texts per utterance on one lattice (include/rs_asr.h rs_rnnt_align_rows): row_utt int32 [R] names the utterance of
+        every text row (-1: skipped, its slots untouched); ids int32 [R][u_cap], n_ids int32 [R]; loglik / best float32 [R], frames
+        int32 / logp float32 [R][u_cap].  share=False: RS_ALIGN_NO_SHARING (the same bits).  Returns the call's stats: (lattice rows
+        computed, lattice rows there are without sharing)."""
+        R = ids.shape[0]
+        assert ids.dim() == 2 and frames.shape == ids.shape and logp.shape == ids.shape
+        assert row_utt.numel() >= R and n_ids.numel() >= R and loglik.numel() >= R and best.numel() >= R
+        stats = (ctypes.c_int64 * 2)(0, 0)
+        flags = (ALIGN_ONE_PER_FRAME if one_per_frame else 0) | (0 if share else ALIGN_NO_SHARING)
+        self.check(self.lib.rs_rnnt_align_rows(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, _ptr(row_utt), R, _ptr(ids), _ptr(n_ids),
+                                               ids.shape[1], flags, _ptr(loglik), _ptr(best), _ptr(frames), _ptr(logp), stats, _ptr(ws),
+                                               ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes), c_void_p(stream)))
+        return int(stats[0]), int(stats[1])
+
+    def token_scores_rows_workspace_bytes(self, B, R, u_cap):
+        """the MINIMUM workspace of `rnnt_token_scores_rows` for R text rows over B utterances"""
+        n = self.lib.rs_rnnt_token_scores_rows_workspace_bytes(self._h, int(B), int(R), int(u_cap))
+        if n == 0:
+            raise RuntimeError("rs_rnnt_token_scores_rows_workspace_bytes: invalid arguments (a finalized transducer context, B > 0, R > 0, u_cap >= 0)")
+        return n
+
+    def rnnt_token_scores_rows(self, joint_enc, enc_lens, B, tp_max, row_utt, ids, frames, n_ids, logp, top1, ws, stream,
+                               frames_are_steps=False, ws_bytes=None):
+        """`rnnt_token_scores` over R text rows, row r against the frames of utterance row_utt[r] (-1: skipped, its slots untouched):
+        ids / frames int32 [R][u_cap], n_ids int32 [R], logp float32 [R][u_cap], top1 int32 [R][u_cap] or None"""
+        R = ids.shape[0]
+        assert ids.dim() == 2 and frames.shape == ids.shape and logp.shape == ids.shape and (top1 is None or top1.shape == ids.shape)
+        assert row_utt.numel() >= R and n_ids.numel() >= R
+        self.check(self.lib.rs_rnnt_token_scores_rows(self._h, _ptr(joint_enc), _ptr(enc_lens), B, tp_max, _ptr(row_utt), R, _ptr(ids),
+                                                      _ptr(frames), _ptr(n_ids), ids.shape[1],
+                                                      SCORES_FRAMES_ARE_STEPS if frames_are_steps else 0, _ptr(logp), _ptr(top1), _ptr(ws),
+                                                      ws.numel() * ws.element_size() if ws_bytes is None else int(ws_bytes),
+                                                      c_void_p(stream)))
 
     def ctc_align_workspace_bytes(self, B, tp_max, c_max, S):
         n = self.lib.rs_ctc_align_workspace_bytes(self._h, int(B), int(tp_max), int(c_max), int(S))

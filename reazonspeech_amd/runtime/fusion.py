@@ -235,6 +235,15 @@ class ForwardedOptions:
     def nbest(self):
         return self.am.nbest
 
+    # n-best rescoring by full likelihood (None = off, "likelihood", "norm_likelihood"): the runtime model's option, settable
+    @property
+    def rescore(self):
+        return self.am.rescore
+
+    @rescore.setter
+    def rescore(self, key):
+        self.am.rescore = None if key is None else self.am.rescore_plan(key)      # (a refused value leaves the option as it was)
+
     # where `transcribe` / `transcribe_batch` normalise their input ("host" / "device")
     @property
     def resample(self):

@@ -49,6 +49,14 @@ class AlignedBatch:
     feasible: List[bool]
 
 
+@dataclass
+class RescoredBatch(DecodedBatch):
+    """`DecodedBatch` of a model with `rescore` on (`AsrModel.rescore`): `rescored[b][k]` belongs to `nbest[b][k]`, the search's own
+    order — (log P(text | audio) over all alignments, the best alignment's score, the token log-probabilities under the model's
+    own distribution or None with `token_scores` off).  Re-ranking is the packages' business: nothing here changes the search's order."""
+    rescored: Optional[List[list]] = None
+
+
 def alsd_label_budget(t_frames: int, max_target_len) -> int:
     """labels a hypothesis may emit beyond the frames (oracle/alsd.py: float = multiple of T', int = absolute)"""
     return int(max_target_len * t_frames) if isinstance(max_target_len, float) else int(max_target_len)
@@ -89,6 +97,9 @@ class _Buffers:
         self.want_nbest = 0              # entries asked for per utterance (`stage` / `fill_host` set it; 0 = the one hypothesis)
         self.nbest_n = 0                 # entries the last `decode` wrote per utterance (0 = it ran without lists)
         self.h_nbest = None              # the lists on the host (a pipeline worker copied them back)
+        self.rescore_bufs = None         # n-best rescoring (`AsrModel.rescore_step`): workspace and per-entry outputs, on first use
+        self.rescored_n = 0              # entries per utterance the last `rescore_step` scored (0 = it did not run)
+        self.h_rescore = None            # its outputs on the host (a pipeline worker copied them back)
         self.ws = torch.empty((ctx.workspace_bytes(B, self.l_pad),), dtype=torch.uint8, device=dev)
         # the decoder of batch i overlaps the encoder of batch i+1 in the pipelined path: own scratch
         self.ws_dec = torch.empty((ctx.workspace_bytes(B, 16),), dtype=torch.uint8, device=dev)
@@ -145,6 +156,7 @@ class _BufView:
         self.h_audio, self.h_lens = cut(base.h_audio, B, l_max), base.h_lens
         self.h_out = None
         self.want_nbest, self.nbest_n, self.h_nbest = 0, 0, None
+        self.rescored_n, self.h_rescore = 0, None
         self.step = -1
 
     def narrow(self, l_max):
@@ -157,6 +169,14 @@ class _BufView:
     @nbest_bufs.setter
     def nbest_bufs(self, v):
         self.base.nbest_bufs = v
+
+    @property
+    def rescore_bufs(self):
+        return self.base.rescore_bufs
+
+    @rescore_bufs.setter
+    def rescore_bufs(self, v):
+        self.base.rescore_bufs = v
 
     @property
     def score_bufs(self):
@@ -205,8 +225,13 @@ class AsrModel:
 
     def __init__(self, cfg: ModelConfig, state_dict, tokenizer, device="cuda", pos_cap: int = DEFAULT_POS_CAP,
                  pad_seconds: float = 0.5, precision: str = "bf16", pad_samples=None, qweights=None, resample: str = "host", token_scores: bool = False,
-                 nbest: int = 0):
-        """nbest: 0 (default) = every search returns its one hypothesis; N >= 1 = the search also returns its N best hypotheses per
+                 nbest: int = 0, rescore=None):
+        """rescore: None (default), "likelihood" or "norm_likelihood": every n-best list is scored by full likelihood on the device
+        right after the search (`rescore_step`: rs_rnnt_align_rows on the lists, one lattice per utterance with shared prefixes
+        computed once) and the result is a `RescoredBatch`.  The two values differ in the key the packages re-rank by; the runtime
+        keeps the search's order.  Needs a beam search and nbest >= 2 (ValueError otherwise, before anything is loaded).  May be
+        changed later.
+        nbest: 0 (default) = every search returns its one hypothesis; N >= 1 = the search also returns its N best hypotheses per
         utterance, ranked on the device (`DecodedBatch.nbest`; include/rs_asr.h rs_rnnt_mbs_nbest / rs_rnnt_beam_nbest state the
         ranking, rs_rnnt_alsd_nbest too).  Built for every beam search; N above the beam, or N > 1 with a
         greedy search, raises ValueError (`nbest_plan`).  May be changed later.
@@ -223,6 +248,8 @@ class AsrModel:
         self.token_scores = bool(token_scores)
         self.cfg = cfg
         self.nbest = self.nbest_plan(nbest)     # (an impossible count is refused before anything is loaded)
+        self.rescore = None
+        self.rescore = self.rescore_plan(rescore)
         self._resample_tables = {}      # rate -> the plan's table on the device
         if precision not in ("bf16", "fp32", "fp32x3", "int8"):
             raise ValueError(f"precision must be 'bf16', 'fp32', 'fp32x3' or 'int8', not {precision!r}")
@@ -427,6 +454,7 @@ class AsrModel:
                              buf.ws, stream)
             self.decode(self.ctx, buf, buf.ws, stream)
             self.score(self.ctx, buf, stream)
+            self.rescore_step(self.ctx, buf, stream)
 
     SCORE_CHUNK_ROWS = 4096     # (b, u) rows whose logits `score` asks room for at once (60 MB at V + 1 = 3001); fewer rows, more chunks, same bits
 
@@ -451,6 +479,97 @@ class AsrModel:
         logp, top1 = sb[1][:B * u_cap].view(B, u_cap), sb[2][:B * u_cap].view(B, u_cap)
         ctx.rnnt_token_scores(buf.joint_enc, buf.enc_lens, B, buf.tp_max, buf.ids, buf.frames, buf.n_ids, logp, top1, sb[0], stream,
                               frames_are_steps=(decoding or cfg.decoding) == "alsd")
+
+    RESCORE_KEYS = ("likelihood", "norm_likelihood")
+
+    def rescore_plan(self, rescore=None, nbest=None, decoding=None):
+        """`rescore`: None = the model's own (`self.rescore`) -> None (off) or the key; ValueError with the reason for a value that is
+        no key, a greedy search, or fewer than two entries per list (`nbest`: as `nbest_plan` takes it)."""
+        r = getattr(self, "rescore", None) if rescore is None else rescore
+        if r is None or r is False:
+            return None
+        if r not in self.RESCORE_KEYS:
+            raise ValueError(f"rescore must be None, 'likelihood' or 'norm_likelihood', not {r!r}")
+        if self.nbest_plan(nbest, decoding) < 2:
+            raise ValueError(f"rescore={r!r} re-ranks an n-best list: it needs a beam search and nbest >= 2")
+        return r
+
+    def rescore_step(self, ctx, buf, stream, decoding=None, single=False):
+        """with `rescore` on, after `decode` and `score` on the same stream: log P(text | audio) and the best alignment of EVERY
+        entry of the n-best lists the search just left in `nbest_bufs`, viewed as [B x n][u_cap] text rows with row b n + k scored
+        against utterance b (k < n_hyps[b], else skipped) while joint_enc is still resident — one rs_rnnt_align_rows call, the
+        entries of a list sharing the lattice cells of their common prefixes (a batch whose rows x tp_max x (u_cap + 1) is beyond
+        one call's bound takes several calls over runs of utterances, on the same joint_enc; ValueError only when the lists of ONE
+        utterance are beyond it, or the label capacity is above `capi.ALIGN_U_CAP_MAX`).  With `token_scores` on, rs_rnnt_token_scores_rows
+        on the same rows too.  Outputs stay in the buffer set's `rescore_bufs` (allocated on first use); `collect` reads them.
+        `single`: a decode that ran WITHOUT lists (the espnet greedy fall-back) is scored as lists of one: buf.ids / n_ids, row b
+        against utterance b.  Synchronises the stream."""
+        buf.rescored_n = 0
+        n = getattr(buf, "nbest_n", 0)
+        if not self.rescore or not (n or single):
+            return
+        cfg = self.cfg
+        if n:
+            nb = buf.nbest_bufs
+        else:
+            n = 1
+            nb = dict(ids=buf.ids[:, None], frames=buf.frames[:, None], n_ids=buf.n_ids[:buf.B, None],
+                      n_hyps=torch.ones((buf.B,), dtype=torch.int32, device=self.device))
+        B, u_cap = buf.B, nb["ids"].shape[2]
+        R = B * n
+        per = min(self.ALIGN_MAX_CELLS // (n * buf.tp_max * (u_cap + 1)), B)       # utterances whose lists one call takes
+        if u_cap > capi.ALIGN_U_CAP_MAX or per < 1:
+            raise ValueError(f"rescore: the {n} hypotheses of one utterance x {buf.tp_max} frames x {u_cap} labels are more than one call "
+                             f"scores (at most {capi.ALIGN_U_CAP_MAX} labels and {self.ALIGN_MAX_CELLS} lattice cells: window the audio)")
+        Rc = per * n
+        decoding = decoding or cfg.decoding
+        one = bool(cfg.max_symbols == 1 and decoding == "modified_beam_search")     # the topology the search moved in
+        hidden = getattr(cfg, "decoder_dim", None) or cfg.pred_hidden
+        per_row = 4 * (2 * cfg.joint_hidden + (cfg.n_logits + 63) // 64 * 64 + 2 * hidden + 16)
+        chunk = (min(self.ALIGN_CHUNK_ROWS, Rc * buf.tp_max * (u_cap + 1)) + 31) // 32 * 32
+        need = ctx.align_rows_workspace_bytes(B, Rc, buf.tp_max, u_cap) + chunk * per_row
+        if self.token_scores:
+            rows = (min(self.SCORE_CHUNK_ROWS, R * u_cap) + 31) // 32 * 32
+            need = max(need, ctx.token_scores_rows_workspace_bytes(B, R, u_cap) + rows * per_row)
+        rb = buf.rescore_bufs
+        if rb is None or rb["ws"].numel() < need or tuple(rb["frames"].shape) != (R, u_cap):
+            dev, i32, f32 = self.device, torch.int32, torch.float32
+            rb = dict(ws=torch.empty((need,), dtype=torch.uint8, device=dev), row_utt=torch.empty((R,), dtype=i32, device=dev),
+                      loglik=torch.empty((R,), dtype=f32, device=dev), best=torch.empty((R,), dtype=f32, device=dev),
+                      frames=torch.empty((R, u_cap), dtype=i32, device=dev), logp=torch.empty((R, u_cap), dtype=f32, device=dev),
+                      token_logp=torch.empty((R, u_cap), dtype=f32, device=dev))
+            buf.rescore_bufs = rb
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=self.device)):
+            k = torch.arange(n, dtype=torch.int32, device=self.device)[None, :]
+            b = torch.arange(B, dtype=torch.int32, device=self.device)[:, None]
+            rb["row_utt"].copy_(torch.where(k < nb["n_hyps"][:B, None], b, -1).reshape(R))
+        ids, n_ids = nb["ids"].reshape(R, u_cap), nb["n_ids"].reshape(R)
+        done = [0, 0]
+        for r0 in range(0, R, Rc):                           # (row_utt keeps naming the utterances of the whole batch)
+            r1 = min(r0 + Rc, R)
+            st = ctx.rnnt_align_rows(buf.joint_enc, buf.enc_lens, B, buf.tp_max, rb["row_utt"][r0:r1], ids[r0:r1], n_ids[r0:r1],
+                                     rb["loglik"][r0:r1], rb["best"][r0:r1], rb["frames"][r0:r1], rb["logp"][r0:r1], rb["ws"], stream,
+                                     one_per_frame=one)
+            done = [done[0] + st[0], done[1] + st[1]]
+        rb["stats"] = (done[0], done[1])
+        if self.token_scores:
+            ctx.rnnt_token_scores_rows(buf.joint_enc, buf.enc_lens, B, buf.tp_max, rb["row_utt"], ids, nb["frames"].reshape(R, u_cap), n_ids,
+                                       rb["token_logp"], None, rb["ws"], stream, frames_are_steps=decoding == "alsd")
+        buf.rescored_n = n
+
+    RESCORE_HOST = ("loglik", "best", "token_logp")
+
+    def rescored_lists(self, rs, nb, B, n):
+        """host copies of `rescore_bufs` and `nbest_bufs` -> per utterance [(log_likelihood, alignment_log_prob, token_logprobs or
+        None)], entry k for entry k of the list"""
+        out = []
+        for b in range(B):
+            rows = []
+            for k in range(int(nb["n_hyps"][b])):
+                r, m = b * n + k, int(nb["n_ids"][b, k])
+                rows.append((float(rs["loglik"][r]), float(rs["best"][r]), rs["token_logp"][r, :m].tolist() if self.token_scores else None))
+            out.append(rows)
+        return out
 
     def score_view(self, buf):
         """the [B][u_cap] log-probabilities `score` left for this batch (None with `token_scores` off)"""
@@ -656,6 +775,7 @@ class AsrModel:
                             # decode scratch lives past the encoder's scratch in buf.ws_dec
                             self.decode(ctx_d, buf, buf.ws_dec, stream.cuda_stream)
                             self.score(ctx_d, buf, stream.cuda_stream)
+                            self.rescore_step(ctx_d, buf, stream.cuda_stream)
                             if from_host:
                                 with torch.cuda.stream(stream):
                                     buf.h_out = (buf.n_ids.cpu(), buf.ids.cpu(), buf.frames.cpu(), buf.enc_lens.cpu(),
@@ -663,6 +783,7 @@ class AsrModel:
                                     if self.token_scores:
                                         buf.h_out = buf.h_out + (self.score_view(buf).cpu(),)
                                     buf.h_nbest = {k: t.cpu() for k, t in buf.nbest_bufs.items()} if buf.nbest_n else None
+                                    buf.h_rescore = {k: buf.rescore_bufs[k].cpu() for k in self.RESCORE_HOST} if buf.rescored_n else None
                             if after_decode is not None:
                                 if i > 0:
                                     hooked[i - 1].wait()
@@ -961,7 +1082,16 @@ class AsrModel:
             res.token_logprobs = [lp[b, :n[b]].tolist() for b in range(buf.B)]
         if getattr(buf, "nbest_n", 0):
             nb = buf.h_nbest if from_worker and buf.h_nbest is not None else {k: t.cpu() for k, t in buf.nbest_bufs.items()}
-            res.nbest = self.nbest_lists({k: t.numpy() for k, t in nb.items()}, buf.B, decoding)
+            nb = {k: t.numpy() for k, t in nb.items()}
+            res.nbest = self.nbest_lists(nb, buf.B, decoding)
+            if getattr(buf, "rescored_n", 0):               # (the lists of `nbest_bufs` were scored: `rescore_step`)
+                rs = buf.h_rescore if from_worker and buf.h_rescore is not None else {k: buf.rescore_bufs[k].cpu() for k in self.RESCORE_HOST}
+                res = RescoredBatch(**{f: getattr(res, f) for f in res.__dataclass_fields__},
+                                    rescored=self.rescored_lists({k: t.numpy() for k, t in rs.items()}, nb, buf.B, buf.rescored_n))
+        elif getattr(buf, "rescored_n", 0):                 # a decode without lists, scored as lists of one
+            rs = {k: buf.rescore_bufs[k].cpu().numpy() for k in self.RESCORE_HOST}
+            one = dict(n_hyps=np.ones((buf.B,), np.int32), n_ids=n[:buf.B, None])
+            res = RescoredBatch(**{f: getattr(res, f) for f in res.__dataclass_fields__}, rescored=self.rescored_lists(rs, one, buf.B, 1))
         return res
 
     @staticmethod
@@ -1040,6 +1170,80 @@ class AsrModel:
                 out.enc_lens[i], out.feasible[i] = int(el[k]), bool(np.isfinite(loglik[k]))
         return out
 
+    def align_candidates(self, waveforms: Sequence[np.ndarray], candidate_rows: Sequence[Sequence[Sequence[int]]], max_batch: int = 256,
+                         one_per_frame: Optional[bool] = None, share: bool = True):
+        """several candidate texts per utterance, scored on one lattice per batch (rs_rnnt_align_rows, csrc/k_rnnt_align.hip):
+        `candidate_rows[i]` is a list of token-id lists for utterance i.  Front-end and encoder run ONCE per utterance; the texts
+        of an utterance share the lattice cells of their common label prefixes (`share=False`: RS_ALIGN_NO_SHARING, the same bits).
+        Every number equals, bit for bit, what `align_waveforms` gives for that (audio, text) pair.  Batches as `align_waveforms`
+        makes them (a batch whose R x tp_max x (u_cap + 1) is beyond one call's bound is halved by utterance); an utterance with
+        more than `capi.ALIGN_ROWS_PER_UTT_MAX` candidates takes one call per that many, on the same encoder output.
+        -> ([AlignedBatch per utterance, its lists running over the utterance's candidates], (lattice rows computed, lattice rows
+        there are without sharing))"""
+        n = len(waveforms)
+        if len(candidate_rows) != n:
+            raise ValueError(f"align_candidates: {n} waveforms but {len(candidate_rows)} candidate lists")
+        one = bool(self.cfg.max_symbols == 1 if one_per_frame is None else one_per_frame)
+        cands = [[[int(i) for i in row] for row in rows] for rows in candidate_rows]
+        longest = max((len(r) for rows in cands for r in rows), default=0)
+        if longest > capi.ALIGN_U_CAP_MAX:
+            raise ValueError(f"align_candidates: a text of {longest} tokens; at most {capi.ALIGN_U_CAP_MAX} are supported (window the audio)")
+        out = [AlignedBatch(*[[None] * len(rows) for _ in range(6)]) for rows in cands]
+        stats = [0, 0]
+        waveforms = [np.asarray(w, dtype=np.float32) for w in waveforms]
+        order = sorted(range(n), key=lambda i: (len(waveforms[i]), i))
+        cfg = self.cfg
+        hidden = getattr(cfg, "decoder_dim", None) or cfg.pred_hidden
+        per_row = 4 * (2 * cfg.joint_hidden + (cfg.n_logits + 63) // 64 * 64 + 2 * hidden + 16)
+        cap = capi.ALIGN_ROWS_PER_UTT_MAX
+        groups = [order[g0:g0 + max_batch] for g0 in range(0, n, max_batch)]
+        while groups:
+            group = groups.pop(0)
+            B = len(group)
+            # the calls of this batch: (position in the batch, utterance, candidate), utterance by utterance, at most `cap` of each
+            passes = max((-(-len(cands[i]) // cap) for i in group), default=0)
+            calls = [[(k, i, j) for k, i in enumerate(group) for j in range(p * cap, min((p + 1) * cap, len(cands[i])))] for p in range(passes)]
+            if not calls:
+                continue
+            buf = self.stage([waveforms[i] for i in group])
+            u_cap = max(max((len(r) for i in group for r in cands[i]), default=0), 1)
+            if max(len(c) for c in calls) * buf.tp_max * (u_cap + 1) > self.ALIGN_MAX_CELLS:
+                if B == 1:
+                    raise ValueError(f"align_candidates: {buf.tp_max} frames x {u_cap} tokens x {len(calls[0])} texts is more than one call "
+                                     f"aligns (window the audio, or pass fewer texts)")
+                groups[:0] = [group[:B // 2], group[B // 2:]]
+                continue
+            with torch.cuda.device(self.device):
+                dev = self.device
+                stream = torch.cuda.current_stream().cuda_stream
+                self.run_encoder(buf, stream)
+                el = buf.enc_lens.cpu().numpy()
+                for rows in calls:
+                    R = len(rows)
+                    ids = np.zeros((R, u_cap), np.int32)
+                    for r, (k, i, j) in enumerate(rows):
+                        ids[r, :len(cands[i][j])] = cands[i][j]
+                    n_ids = np.asarray([len(cands[i][j]) for _, i, j in rows], np.int32)
+                    row_utt = np.asarray([k for k, _, _ in rows], np.int32)
+                    ids_d, n_d, utt_d = (torch.from_numpy(a).to(dev) for a in (ids, n_ids, row_utt))
+                    loglik, best = torch.empty((R,), device=dev), torch.empty((R,), device=dev)
+                    frames = torch.full((R, u_cap), -1, dtype=torch.int32, device=dev)
+                    logp = torch.full((R, u_cap), float("nan"), device=dev)
+                    chunk = min(self.ALIGN_CHUNK_ROWS, R * buf.tp_max * (u_cap + 1))
+                    ws = torch.empty((self.ctx.align_rows_workspace_bytes(B, R, buf.tp_max, u_cap) + (chunk + 31) // 32 * 32 * per_row,),
+                                     dtype=torch.uint8, device=dev)
+                    done = self.ctx.rnnt_align_rows(buf.joint_enc, buf.enc_lens, B, buf.tp_max, utt_d, ids_d, n_d, loglik, best, frames, logp,
+                                                    ws, stream, one_per_frame=one, share=share)
+                    stats[0] += done[0]
+                    stats[1] += done[1]
+                    loglik, best, frames, logp = (t.cpu().numpy() for t in (loglik, best, frames, logp))
+                    for r, (k, i, j) in enumerate(rows):
+                        m, o = int(n_ids[r]), out[i]
+                        o.frames[j], o.token_logprobs[j] = frames[r, :m].tolist(), logp[r, :m].tolist()
+                        o.log_likelihood[j], o.alignment_log_prob[j] = float(loglik[r]), float(best[r])
+                        o.enc_lens[j], o.feasible[j] = int(el[k]), bool(np.isfinite(loglik[r]))
+        return out, (stats[0], stats[1])
+
     def transcribe_waveforms_sharded(self, waveforms: Sequence[np.ndarray], max_batch: int = 256, hotwords=None, ngram_lm=None) -> DecodedBatch:
         """SPMD form of `transcribe_waveforms` for one process per GPU (`torch.distributed` initialised, RCCL):
         every rank passes the same list, decodes its length-balanced shard on its own GPU and receives all
@@ -1050,6 +1254,9 @@ class AsrModel:
         if self.token_scores:
             raise ValueError("token_scores is on: transcribe_waveforms_sharded does not gather token log-probabilities; "
                              "use transcribe_waveforms on each rank, or turn token_scores off")
+        if self.rescore:
+            raise ValueError("rescore is on: transcribe_waveforms_sharded does not gather rescored n-best lists; use "
+                             "transcribe_waveforms on each rank, or set rescore to None")
         if self.nbest:
             raise ValueError("nbest is on: transcribe_waveforms_sharded does not gather n-best lists; use transcribe_waveforms on each "
                              "rank, or set nbest to 0")
@@ -1104,8 +1311,9 @@ class AsrModel:
         `nbest` then holds every utterance's ranked list (`nbest_plan`: ValueError for a count the search cannot give)."""
         n = len(waveforms)
         n_best = self.nbest_plan(nbest)
+        rescoring = self.rescore_plan(None, n_best) is not None      # (ValueError for a call whose lists are shorter than two)
         if n == 0:
-            return DecodedBatch([], [], [], nbest=[] if n_best else None)
+            return RescoredBatch([], [], [], nbest=[], rescored=[]) if rescoring else DecodedBatch([], [], [], nbest=[] if n_best else None)
         waveforms = [np.asarray(w, dtype=np.float32) for w in waveforms]
         plan = self.graph_plan(hotwords, n)
         lm = self.lm_plan(ngram_lm)
@@ -1120,6 +1328,7 @@ class AsrModel:
         ids, frames, enc_lens, scores = [None] * n, [None] * n, [None] * n, [None] * n
         logprobs = [None] * n if self.token_scores else None
         lists = [None] * n if n_best else None
+        rescored = [None] * n if rescoring else None
         groups = [order[i:i + max_batch] for i in range(0, n, max_batch)]
         # longest batch first: what is left after the last encoder is one decode, and the shortest batch's is the shortest
         # (a ragged list's drain shrinks from the longest batch's decode to the shortest's)
@@ -1158,12 +1367,15 @@ class AsrModel:
                     logprobs[i] = res.token_logprobs[k]
                 if lists is not None:
                     lists[i] = res.nbest[k]
+                if rescored is not None:
+                    rescored[i] = res.rescored[k]
             if post_q is not None:
                 m = len(group)
-                post_q.put((group, DecodedBatch(res.ids[:m], res.frames[:m], res.enc_lens[:m],
-                                                res.scores[:m] if res.scores is not None else None,
-                                                token_logprobs=res.token_logprobs[:m] if logprobs is not None else None,
-                                                nbest=res.nbest[:m] if lists is not None else None)))
+                extra = dict(rescored=res.rescored[:m]) if rescored is not None else {}
+                post_q.put((group, (RescoredBatch if extra else DecodedBatch)(
+                    res.ids[:m], res.frames[:m], res.enc_lens[:m], res.scores[:m] if res.scores is not None else None,
+                    token_logprobs=res.token_logprobs[:m] if logprobs is not None else None,
+                    nbest=res.nbest[:m] if lists is not None else None, **extra)))
 
         post = None
         if post_q is not None:
@@ -1187,4 +1399,7 @@ class AsrModel:
                 gc.enable()
         if post_err:
             raise post_err[0]
+        if rescored is not None:
+            return RescoredBatch(ids, frames, enc_lens, scores if self.cfg.has_scores else None, token_logprobs=logprobs, nbest=lists,
+                                 rescored=rescored)
         return DecodedBatch(ids, frames, enc_lens, scores if self.cfg.has_scores else None, token_logprobs=logprobs, nbest=lists)
