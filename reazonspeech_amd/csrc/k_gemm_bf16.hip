@@ -33,6 +33,20 @@
 //   * XCD-aware, grouped blockIdx -> tile order (each XCD, private L2, walks a contiguous run of tiles).
 //   * epilogue through a per-wave 4-KiB LDS scratch (aliasing a dead slot / stage) so every global access is a whole 128 / 256-
 //     byte row segment: +bias, ReLU / SiLU / GLU, *alpha, +residual (f32, prefetched), per-utterance row mask.
+//
+// Template arguments of gemm_smf16_kernel: BM (tile height), OUT (epilogue kind, the OUT_* enum), MASK (per-utterance row
+// mask), EPF (residual chunks requested ahead), TRACE (per-tile time stamps), CONVA (A = 3 x 3 patches read in place), BREG
+// (weights global -> VGPR), and what the epilogue knows when it is compiled:
+//   ACT        ACT_RT: the ReLU / SiLU bits of the flags are tested at run time, per accumulator block of four elements (two
+//              wave-uniform branches per block: 32 basic blocks per 256-row tile, nothing scheduled across them).  ACT_NONE /
+//              ACT_RELU / ACT_SILU: the launcher saw exactly that combination, the epilogue of a 32-row chunk is one basic block,
+//              the exp / rcp chains of its eight accumulator blocks interleave, and SiLU / sigmoid are written on pairs
+//              (sigmoid_pk, silu_pk: v_pk_mul_f32 / v_pk_add_f32 — per element the operations of sigmoid_f / silu_f on the
+//              same operands in the same order, so the bits are the same; ReLU loses the eight canonicalising v_max per block).
+//   UNIT_ALPHA the launcher saw alpha == 1.0f exactly: the multiply is left out.
+// The launcher (pick_epi_form) takes a compile-time form only when it is certain and the form exists (epi_form_built: the
+// shapes where it measured faster); $RS_GEMM_EPI_GENERIC=1 gives every launch ACT_RT, which compiles to the ISA it had before
+// the two arguments existed.  The forms are held to it bit for bit by tests/test_gpu_gemm_epilogue_forms.py.
 #include <stdlib.h>
 
 #include <atomic>
@@ -70,6 +84,12 @@ struct GemmParams {
 // tiles, SiLU) ran 7 % slower (317.6 vs 295.5 us, profiles/r05c_bench.json against BENCH_r04.json).
 // OUT_RES2: OUT_RES that also stores the result as bf16 (GemmParams.out2): the Zipformer layers' residual branches.
 enum { OUT_BF16 = 0, OUT_F32 = 1, OUT_RES = 2, OUT_GLU = 3, OUT_RESLN = 4, OUT_BF16S = 5, OUT_F32S = 6, OUT_RES2 = 7 };
+// ACT: what the epilogue knows about the activation when it is compiled.  ACT_RT = nothing: the ReLU / SiLU bits of
+// GemmParams.flags are tested at run time, once per accumulator block, and every element is multiplied by alpha (the form
+// every launch had before; $RS_GEMM_EPI_GENERIC=1 still gives it to every launch).  ACT_NONE / ACT_RELU / ACT_SILU: the launcher
+// saw exactly that combination of the two bits, so a 32-row chunk of the epilogue is one basic block.  UNIT_ALPHA: the launcher
+// saw alpha == 1.0f exactly and the multiply is left out (x * 1.0f is x bit for bit).  Which combinations exist: epi_form_built.
+enum { ACT_RT = 0, ACT_NONE = 1, ACT_RELU = 2, ACT_SILU = 3 };
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -143,17 +163,34 @@ __host__ __device__ inline void xcd_split(int xcount, int pair_mode, int& n_pair
     n_pairs = (xcount - n_singles) / 2;
 }
 
+// sigmoid_f / silu_f of rs_common.h on pairs, for the compile-time epilogue forms: per element the same operations on the same
+// operands in the same order (x * -log2 e, v_exp_f32, 1 + e, v_rcp_f32, x * s); the multiply and the add are one packed f32
+// instruction per pair (IEEE per half: the bits are those of the scalar form).
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2_t sigmoid_pk(f32x2_t x) {
+    const f32x2_t t = x * (f32x2_t){-0x1.715476p+0f, -0x1.715476p+0f};
+    const f32x2_t e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+    const f32x2_t d = (f32x2_t){1.0f, 1.0f} + e;
+    return (f32x2_t){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+}
+__device__ __forceinline__ void silu_pk(float4& v) {
+    const f32x2_t lo = {v.x, v.y}, hi = {v.z, v.w};
+    const f32x2_t a = lo * sigmoid_pk(lo), b = hi * sigmoid_pk(hi);
+    v.x = a.x; v.y = a.y; v.z = b.x; v.w = b.y;
+}
+
 // ---- epilogue (no workgroup barrier: the scratch is per wave, LDS operations of one wave execute in order).
 // bf16 output: chunks of 32 rows x 64 columns; f32: 16 rows x 64 columns; both 4 KiB, 16-byte pieces XOR-swizzled by
 // row.  All global accesses are raw buffer operations (masked rows / columns get an out-of-range offset), so the
 // number of VMEM operations a wave issues here is a compile-time constant.
 // Lane layout of the accumulators: the weight fragment is the MFMA A operand, so D = (A.W^T)^T and block (i, j) holds
 // m = .. + i*16 + (lane & 15), n = .. + j*16 + 4*(lane >> 4) + 0..3.
-template <int MI, int NI, int OUT_KIND, bool MASK, int PF>
+template <int MI, int NI, int OUT_KIND, bool MASK, int PF, int ACT, bool UNIT_ALPHA>
 __device__ __forceinline__ void smf16_epilogue(const GemmParams& p, f32x4_t (&acc)[MI][NI], char* scr, int cm0, int cn0,
                                                int wm, int wn, int lane) {
     constexpr bool SWOOSH = OUT_KIND == OUT_BF16S || OUT_KIND == OUT_F32S, RES2 = OUT_KIND == OUT_RES2;
     constexpr int OUT = OUT_KIND == OUT_BF16S ? OUT_BF16 : (OUT_KIND == OUT_F32S ? OUT_F32 : (RES2 ? OUT_RES : OUT_KIND));
+    static_assert(ACT == ACT_RT ? !UNIT_ALPHA : !SWOOSH, "the run-time form multiplies by alpha; the Swoosh kinds have no compile-time form");
     // OUT_RESLN: the residual operand is y, the previous layer's output BEFORE its output LayerNorm; that norm is applied
     // here from per-row statistics (layernorm2_kernel writes them instead of the normalised f32 rows: one 145-MB write
     // per layer boundary less), with the arithmetic of the norm kernel: fma((y - mean) * rstd, g, b).
@@ -184,13 +221,19 @@ __device__ __forceinline__ void smf16_epilogue(const GemmParams& p, f32x4_t (&ac
     auto finish = [&](int i, int jj) -> float4 {
         float4 v = make_float4(acc[i][jj][0] + bias_r[jj].x, acc[i][jj][1] + bias_r[jj].y, acc[i][jj][2] + bias_r[jj].z,
                                acc[i][jj][3] + bias_r[jj].w);
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        if (silu) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+        if constexpr (ACT == ACT_RT) {
+            if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (silu) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+        } else if constexpr (ACT == ACT_RELU) {
+            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        } else if constexpr (ACT == ACT_SILU) {
+            silu_pk(v);
+        }
         if constexpr (SWOOSH) {
             if (swl) { v.x = swoosh_l_f(v.x); v.y = swoosh_l_f(v.y); v.z = swoosh_l_f(v.z); v.w = swoosh_l_f(v.w); }
             if (swr) { v.x = swoosh_r_f(v.x); v.y = swoosh_r_f(v.y); v.z = swoosh_r_f(v.z); v.w = swoosh_r_f(v.w); }
         }
-        v.x *= alpha; v.y *= alpha; v.z *= alpha; v.w *= alpha;
+        if constexpr (!UNIT_ALPHA) { v.x *= alpha; v.y *= alpha; v.z *= alpha; v.w *= alpha; }
         return v;
     };
     auto row_keep = [&](int m) -> bool {
@@ -216,8 +259,14 @@ __device__ __forceinline__ void smf16_epilogue(const GemmParams& p, f32x4_t (&ac
                     const float4 a = finish(2 * c + il, jj), g = finish(2 * c + il, jj + 2);
                     const int row = il * 16 + frow;
                     const int piece = (jj * 2 + (fch >> 1)) ^ ((row >> 1) & 3);
-                    *reinterpret_cast<u16x4_t*>(scr + row * 64 + piece * 16 + (fch & 1) * 8) =
-                        pack_bf16x4(a.x * sigmoid_f(g.x), a.y * sigmoid_f(g.y), a.z * sigmoid_f(g.z), a.w * sigmoid_f(g.w));
+                    if constexpr (ACT == ACT_RT) {
+                        *reinterpret_cast<u16x4_t*>(scr + row * 64 + piece * 16 + (fch & 1) * 8) =
+                            pack_bf16x4(a.x * sigmoid_f(g.x), a.y * sigmoid_f(g.y), a.z * sigmoid_f(g.z), a.w * sigmoid_f(g.w));
+                    } else {
+                        const f32x2_t lo = (f32x2_t){a.x, a.y} * sigmoid_pk((f32x2_t){g.x, g.y});
+                        const f32x2_t hi = (f32x2_t){a.z, a.w} * sigmoid_pk((f32x2_t){g.z, g.w});
+                        *reinterpret_cast<u16x4_t*>(scr + row * 64 + piece * 16 + (fch & 1) * 8) = pack_bf16x4(lo.x, lo.y, hi.x, hi.y);
+                    }
                 }
 #pragma unroll
             for (int sgm = 0; sgm < 2; ++sgm) {
@@ -346,7 +395,7 @@ __device__ __forceinline__ void smf16_epilogue(const GemmParams& p, f32x4_t (&ac
 // tile (16 MFMAs each, the guide's 8-phase shape).  Per shape they are within +-4 % of this one either way — the loop is
 // paced by the LDS traffic of the 128 x 64 wave tile and the clock, not by its barrier structure — and on the whole
 // path both lose ~1 % (58.8 vs 59.5 ms / step).
-template <int BM, int OUT, bool MASK, int EPF, bool TRACE, bool CONVA = false, bool BREG = false>
+template <int BM, int OUT, bool MASK, int EPF, bool TRACE, bool CONVA = false, bool BREG = false, int ACT = ACT_RT, bool UNIT_ALPHA = false>
 __global__ __launch_bounds__(512, 2) void gemm_smf16_kernel(GemmParams p) {
     constexpr int BN = 256, WN = 4, NWAVES = 8;
     constexpr int TM = BM / 2, TN = BN / WN, MI = TM / 16, NI = TN / 16;
@@ -651,7 +700,12 @@ __global__ __launch_bounds__(512, 2) void gemm_smf16_kernel(GemmParams p) {
         // happens after the barrier below.
         // (R3: stages sa, sa+1 hold the next tile's K tiles 0 and 1; sa+2 — the last K tile — is dead.)
         char* scr = smem + (R3 ? (sa + 2 >= 3 ? sa - 1 : sa + 2) * STAGE : wrap(sa + 4) * SLOT) + wave * 4096;
-        smf16_epilogue<MI, NI, OUT, MASK, EPF>(p, acc, scr, em0, en0, wm, wn, lane);
+        // compile-time forms: the epilogue's per-lane addresses are recomputed per tile, like em0 / en0 above.  Hoisted out of
+        // the tile loop they were live across the main loop and cost 3 VGPRs MORE than the run-time form (219 against 216 at 256
+        // rows); behind this fence the forms need 7 - 13 fewer.  The run-time forms stay as they were compiled before.
+        int elane = lane;
+        if constexpr (ACT != ACT_RT) asm volatile("" : "+v"(elane));
+        smf16_epilogue<MI, NI, OUT, MASK, EPF, ACT, UNIT_ALPHA>(p, acc, scr, em0, en0, wm, wn, elane);
         if constexpr (TRACE) {
             // wave 0 (group 0) and wave 4 (group 1) each write a record: [0] prologue, [1] main loop, [2] epilogue
             // issue, [3] store drain, [4] cycles stalled in the K-tile waits, [5] block, [6] / [7] wall clock
@@ -718,6 +772,41 @@ int wfm_operand(rs_ctx* ctx, const uint16_t* W, int ldw, int N, int K, hipStream
     return RS_OK;
 }
 
+// The compile-time epilogue forms that exist (tile height, output kind, row mask, ACT, UNIT_ALPHA): what the FastConformer
+// launches with bf16 output at the heights pick_tile_height gives its shapes at the benchmark batch — 256 rows: ffn_up (bf16 +
+// SiLU) and qkv (bf16); 192 rows: pw1 (GLU) and the subsampling's pointwise convs (bf16 + ReLU + row mask); all with alpha 1.
+// Per launch against the run-time form (profiles/pr_gemm_epilogue_per_shape.txt): ffn_up -5.7 .. -8.5 us of 280, qkv -2.5 ..
+// -3.2 of 200, pw1 GLU -6.3 .. -6.8 of 140, the subsampling convs -20 .. -23 of 385 and -7 .. -8 of 110.  Built, measured and
+// gone again: the f32 kinds (residual, normalised residual, plain f32; alpha 1 and alpha a variable), whose epilogue is paced
+// by its HBM traffic — within the run-time form's range or behind it (ffn_down with alpha 0.5: +3.1 us of 279) — and the
+// 192-row plain bf16 form (the unfused pw1: -1.7 us against a range of 2.9).  Everything else — the other heights, both
+// activation bits at once, the Swoosh kinds, OUT_RES2, BREG, CONVA — keeps the run-time form too.
+constexpr bool epi_form_built(int bm, int out, bool mask, int act, bool unit) {
+    if (!unit || (bm != 256 && bm != 192)) return false;
+    if (mask) return bm == 192 && out == OUT_BF16 && act == ACT_RELU;
+    if (out == OUT_BF16) return bm == 256 && (act == ACT_SILU || act == ACT_NONE);
+    if (out == OUT_GLU) return bm == 192 && act == ACT_NONE;
+    return false;
+}
+
+int epi_out_kind(int flags, bool ln_stats, bool out2) {
+    const bool swoosh = flags & (RS_GEMM_SWOOSHL | RS_GEMM_SWOOSHR);
+    return (flags & RS_GEMM_RESIDUAL) ? (ln_stats ? OUT_RESLN : (out2 ? OUT_RES2 : OUT_RES))
+         : ((flags & RS_GEMM_OUT_F32) ? (swoosh ? OUT_F32S : OUT_F32) : ((flags & RS_GEMM_GLU) ? OUT_GLU : (swoosh ? OUT_BF16S : OUT_BF16)));
+}
+
+// The epilogue form of a launch: ACT | (UNIT_ALPHA ? 8 : 0), or 0 = the run-time form.  A compile-time form is taken only when
+// the launcher is certain: alpha compares equal to 1.0f, at most one of the two activation bits is set, the form exists, and
+// $RS_GEMM_EPI_GENERIC is not set.
+int pick_epi_form(int bm, int out, bool mask, int flags, float alpha) {
+    if (rs_knob(RS_KNOB_GEMM_EPI_GENERIC) > 0) return 0;
+    const bool relu = flags & RS_GEMM_RELU, silu = flags & RS_GEMM_SILU;
+    if (relu && silu) return 0;
+    const int act = relu ? ACT_RELU : (silu ? ACT_SILU : ACT_NONE);
+    const bool unit = alpha == 1.0f;
+    return epi_form_built(bm, out, mask, act, unit) ? (act | (unit ? 8 : 0)) : 0;
+}
+
 template <int BM>
 int launch_smf16(rs_ctx* ctx, GemmParams& p, hipStream_t s) {
     constexpr int LDS = 5 * 32768;
@@ -742,9 +831,7 @@ int launch_smf16(rs_ctx* ctx, GemmParams& p, hipStream_t s) {
     const int group_m = rs_knob(RS_KNOB_GEMM_GROUP_M);
     p.group_m = group_m > 0 ? group_m
               : (p.tiles_n == 4 ? (p.K >= 4096 ? 2 : 6) : (p.K >= 4096 ? 4 : (p.tiles_n <= 8 && p.K <= 2560 ? 16 : 8)));
-    const bool swoosh = p.flags & (RS_GEMM_SWOOSHL | RS_GEMM_SWOOSHR);
-    const int out = (p.flags & RS_GEMM_RESIDUAL) ? (p.res_ln_stats ? OUT_RESLN : (p.out2 ? OUT_RES2 : OUT_RES))
-                  : ((p.flags & RS_GEMM_OUT_F32) ? (swoosh ? OUT_F32S : OUT_F32) : ((p.flags & RS_GEMM_GLU) ? OUT_GLU : (swoosh ? OUT_BF16S : OUT_BF16)));
+    const int out = epi_out_kind(p.flags, p.res_ln_stats != nullptr, p.out2 != nullptr);
     const bool mask = p.flags & RS_GEMM_ROWMASK;
     if (p.cv_tps > 0) {                                           // patches read in place (launcher: plain bf16 output + row mask)
         if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)gemm_smf16_kernel<BM, OUT_BF16, true, EPF, false, true>, LDS); rc != RS_OK) return rc;
@@ -777,13 +864,40 @@ int launch_smf16(rs_ctx* ctx, GemmParams& p, hipStream_t s) {
     } while (0)
     if (p.trace) {
         if constexpr (BM >= 192) {
-            if (out == OUT_RES && !mask) RS_SMF(OUT_RES, false, true);
+            // (the two compile-time forms scripts/gemm_trace.py times have TRACE builds at 256 rows; $RS_GEMM_EPI_GENERIC=1 traces the run-time form)
+            const int form = BM == 256 && out == OUT_BF16 && !mask ? pick_epi_form(BM, out, mask, p.flags, p.alpha) : 0;
+            if (form == (ACT_SILU | 8) || form == (ACT_NONE | 8)) {
+                if constexpr (BM == 256) {
+                    if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)gemm_smf16_kernel<BM, OUT_BF16, false, EPF, true, false, false, ACT_SILU, true>, LDS); rc != RS_OK) return rc;
+                    if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)gemm_smf16_kernel<BM, OUT_BF16, false, EPF, true, false, false, ACT_NONE, true>, LDS); rc != RS_OK) return rc;
+                    if (form == (ACT_SILU | 8)) hipLaunchKernelGGL((gemm_smf16_kernel<BM, OUT_BF16, false, EPF, true, false, false, ACT_SILU, true>), dim3(nwg), dim3(512), LDS, s, p);
+                    else hipLaunchKernelGGL((gemm_smf16_kernel<BM, OUT_BF16, false, EPF, true, false, false, ACT_NONE, true>), dim3(nwg), dim3(512), LDS, s, p);
+                }
+            }
+            else if (out == OUT_RES && !mask) RS_SMF(OUT_RES, false, true);
             else if (out == OUT_BF16 && !mask) RS_SMF(OUT_BF16, false, true);
             else return rs_fail(ctx, RS_EINVAL, "gemm trace: plain bf16 or residual output only");
             return RS_OK;
         } else {
             return rs_fail(ctx, RS_EINVAL, "gemm trace: 256- / 192-row tiles only");
         }
+    }
+    // compile-time epilogue forms (epi_form_built): the same arithmetic without the per-block flag tests
+    if (const int form = pick_epi_form(BM, out, mask, p.flags, p.alpha)) {
+#define RS_SMF_E(O, MK, A, U)                                                                                      \
+        if constexpr (epi_form_built(BM, O, MK, A, U)) {                                                           \
+            if (out == O && mask == MK && form == (A | (U ? 8 : 0))) {                                             \
+                if (int rc = rs_ensure_dynamic_lds(ctx, (const void*)gemm_smf16_kernel<BM, O, MK, EPF, false, false, false, A, U>, LDS); rc != RS_OK) return rc; \
+                hipLaunchKernelGGL((gemm_smf16_kernel<BM, O, MK, EPF, false, false, false, A, U>), dim3(nwg), dim3(512), LDS, s, p); \
+                return RS_OK;                                                                                      \
+            }                                                                                                      \
+        }
+        RS_SMF_E(OUT_BF16, false, ACT_SILU, true)
+        RS_SMF_E(OUT_BF16, false, ACT_NONE, true)
+        RS_SMF_E(OUT_BF16, true, ACT_RELU, true)
+        RS_SMF_E(OUT_GLU, false, ACT_NONE, true)
+#undef RS_SMF_E
+        return rs_fail(ctx, RS_EINVAL, "gemm: epilogue form %d of output kind %d has no kernel", form, out);
     }
     if (out == OUT_RES && !mask) RS_SMF(OUT_RES, false, false);
     else if (out == OUT_RESLN && !mask) RS_SMF(OUT_RESLN, false, false);
@@ -835,6 +949,21 @@ extern "C" void rs_debug_set_gemm_group_m(int v) { rs_knob_set(RS_KNOB_GEMM_GROU
 extern "C" void rs_debug_set_gemm_pairs(int v) { rs_knob_set(RS_KNOB_GEMM_PAIRS, v); }
 extern "C" void rs_debug_set_gemm_breg(int v) { rs_knob_set(RS_KNOB_GEMM_BREG, v); }
 extern "C" int rs_debug_gemm_tile_height(int M, int N, int K, int n_cus, int flags) { return pick_tile_height(M, N, K, n_cus > 0 ? n_cus : 256, flags); }
+
+// the launcher's epilogue-form choice (host arithmetic, callable without a GPU): ACT | (UNIT_ALPHA ? 8 : 0), 0 = the run-time form
+extern "C" int rs_debug_gemm_epi_form(int bm, int flags, float alpha, int ln_stats, int out_bf16) {
+    return pick_epi_form(bm, epi_out_kind(flags, ln_stats != 0, out_bf16 != 0), (flags & RS_GEMM_ROWMASK) != 0, flags, alpha);
+}
+// rs_gemm_bf16 with the two residual operands the public entry point does not carry (tests: the normalised residual and the bf16 copy)
+extern "C" int rs_debug_gemm_bf16_res(rs_ctx* ctx, const uint16_t* A, int lda, const uint16_t* W, int ldw, float* out, int ldc, int M, int N, int K,
+                                      int flags, const float* bias, float alpha, const float* residual, const float* res_ln_stats,
+                                      const float* res_ln_g, const float* res_ln_b, uint16_t* out_bf16, int ld_bf16, void* stream) {
+    if (!ctx || !A || !W || !out) return RS_EINVAL;
+    rs_gemm_args g{A, lda, W, ldw, out, ldc, M, N, K, flags, bias, alpha, residual, nullptr, 0, 0};
+    g.res_ln_stats = res_ln_stats; g.res_ln_g = res_ln_g; g.res_ln_b = res_ln_b;
+    g.out_bf16 = out_bf16; g.ld_bf16 = ld_bf16;
+    return rs_launch_gemm(ctx, g, (hipStream_t)stream);
+}
 
 static int launch_rows(rs_ctx* ctx, GemmParams& p, int bm, hipStream_t s) {
     switch (bm) {

@@ -23,7 +23,8 @@
     X(GEMM_GROUP_M, "RS_GEMM_GROUP_M", INT, 0, "row panels per XCD tile group; 0 = by shape")                                         \
     X(GEMM_PAIRS, "RS_GEMM_PAIRS", INT, 2, "2 = two tiles per workgroup, LDS ring carried over; 1 = ring restarted; 0 = one tile")    \
     X(GEMM_BREG, "RS_GEMM_BREG", INT, 0, "1 = 256- / 192-row launches keep the weight operand out of LDS (global -> VGPR)")           \
-    X(ATTN_PERSIST, "RS_ATTN_PERSIST", INT, 0, "1 = full attention on resident workgroups that walk the items (n >= 2: on n)")        \
+    X(GEMM_EPI_GENERIC, "RS_GEMM_EPI_GENERIC", INT, 0, "1 = every GEMM launch takes the epilogue that tests ReLU / SiLU and multiplies by alpha at run time") \
+    X(ATTN_PERSIST,"RS_ATTN_PERSIST", INT, 0, "1 = full attention on resident workgroups that walk the items (n >= 2: on n)")        \
     X(ATTN_STREAM, "RS_ATTN_STREAM", INT, 0, "1 = the streaming attention form (+ 16 x mask: phases left out, for timing)")           \
     X(ATTN64, "RS_ATTN64", INT, 4, "head_dim 64: key blocks per chunk; 0 = the one-workgroup-per-CU geometry")                        \
     X(ATTN64_NW, "RS_ATTN64_NW", INT, 4, "head_dim 64: waves per workgroup (the second number of $RS_ATTN64)")                        \

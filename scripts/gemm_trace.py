@@ -1,6 +1,7 @@
 """Per-tile timeline of the GEMM kernel (gemm_smf16_kernel, TRACE build with s_memtime stamps).
 
-    python scripts/gemm_trace.py [--shape=qkv]
+    python scripts/gemm_trace.py [--shape=qkv] [--epi-ab]
+--epi-ab: every shape twice, the epilogue form the launcher picks and the run-time-flag form ($RS_GEMM_EPI_GENERIC=1).
 
 For every output tile, wave 0 (wave group 0) and wave 4 (wave group 1) record: prologue (launch -> first K tile
 landed), main loop, epilogue issue, store drain (s_waitcnt vmcnt(0) after the last store), the cycles spent inside
@@ -28,7 +29,7 @@ SHAPES = [
 
 
 def main():
-    scheds = [0]
+    scheds = [0, 1] if "--epi-ab" in sys.argv else [0]           # $RS_GEMM_EPI_GENERIC
     only = [a.split("=")[1] for a in sys.argv[1:] if a.startswith("--shape=")]
     ctx = capi.Context(FASTCONFORMER_619M, 0)
     lib = ctx.lib
@@ -40,6 +41,7 @@ def main():
             continue
         for v in scheds:
             lib.rs_debug_set_gemm_tile(bm)
+            assert lib.rs_debug_set_knob(b"RS_GEMM_EPI_GENERIC", v) == 0
             A = torch.randn((M, k), device=dev).to(torch.bfloat16)
             W = (torch.randn((n, k), device=dev) / k ** 0.5).to(torch.bfloat16)
             bias = torch.randn((n,), device=dev)
@@ -67,7 +69,7 @@ def main():
             cyc = t[:, 0, 0] + t[:, 0, 1] + t[:, 0, 2] + t[:, 0, 3]
             cyc_per_us = (cyc / np.maximum(w1 - w0, 1e-3)).mean()
             mfma_floor = 2.0 * bm * 256 * k / (2.5e15 / 256) * 1e6
-            print(f"== {name}: {len(t)} tiles of {bm}x256, traced launch {total_us:.1f} us, shader clock ~{cyc_per_us / 1e3:.2f} GHz, "
+            print(f"== {name}{' [run-time-flag epilogue]' if v else ''}: {len(t)} tiles of {bm}x256, traced launch {total_us:.1f} us, shader clock ~{cyc_per_us / 1e3:.2f} GHz, "
                   f"MFMA floor per tile {mfma_floor:.1f} us @2.4 GHz")
             for g in (0, 1):
                 print(f"   wave group {g}:")
@@ -80,6 +82,7 @@ def main():
             hist, _ = np.histogram(w0, bins=20, range=(0, w1.max()))
             print("   tile starts per 5% of the span:", hist.tolist())
     lib.rs_debug_set_gemm_tile(0)
+    lib.rs_debug_set_knob(b"RS_GEMM_EPI_GENERIC", 0)
 
 
 if __name__ == "__main__":
